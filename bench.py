@@ -2,6 +2,7 @@
 """bench.py - graph-pairs/sec of the SG_PR hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kitti00|kitti5seq|pairlist|pairs128|stress]
+                    [--dump-outputs DIR (e.g. bench_outputs, git-ignored)]
 
 `--gpus N` with N > 1 and no torch.distributed environment: this script re-launches itself as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU, backend
@@ -36,11 +37,17 @@ operand width instead of the default two f16 planes) and prices the all-fp32 var
 
 Other workloads (parity-test shapes, not the headline): `pairs128` (config 2: 128 pairs, N=64, k=10, faithful
 per-pair forward) and `stress` (config 5: 1024 pairs, N=256, k=20).
+
+`--dump-outputs DIR` writes what the LAST timed step returned (rank 0's view: the score matrix of every sequence, or the
+scores of the listed / batched pairs) as DIR/<name>.npy in float32, copied right after the timed region.  Inputs are
+seeded, so two builds run with the same arguments can be compared output for output.  At most DUMP_BUDGET_BYTES are
+written: a matrix beyond its share of that budget keeps a seeded sample of its rows (`dump` in the line names them).
 """
 import argparse
 import hashlib
 import json
 import os
+import re
 import socket
 import subprocess
 import sys
@@ -54,6 +61,8 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8 TB/s HBM3E
 FP32_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: fp32 vector peak (= fp32 matrix peak)
 SHADER_CLOCK_HZ = 2.4e9      # MI355X_MICROARCH.md: peak engine clock (used only when the --pmc passes carry no measured one)
 KITTI_FRAMES = {"00": 4541, "02": 4661, "05": 2761, "06": 1101, "08": 4071}
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # --dump-outputs: all .npy files together, headers included
+DUMP_HEADER_BYTES = 4096           # reserved per file for the .npy header
 
 
 def embed_flops_per_graph(n, k):
@@ -120,7 +129,15 @@ def parse():
                     help="skip the untimed pass at the reference's operand width (wide-range embed instance forced)")
     ap.add_argument("--d2h-pieces", type=int, default=4,
                     help="end_to_end.d2h: row blocks whose device-to-host copy overlaps the scoring of the next one")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all: a "
+                         "seeded sample of the rows of a matrix beyond that)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def respawn_under_launcher(a):
@@ -274,12 +291,14 @@ def main():
             set_embed = counted("embed", lambda c, l: eng.embed(c, l, k, node_cap=node_cap_report, order=set_order)[0])
 
         def step(gather=not a.no_gather):
+            """-> one score matrix per sequence (this rank's row block where the matrix stays sharded)"""
             if seqset is not None:
-                return seqset.run(embed_fn=set_embed, gather=gather, outs=[j["out"] for j in jobs], chunks=a.chunks)[-1]
-            out = None
-            for j in jobs:
-                out = j["scorer"].run(j["d_centers"], j["d_labels"], gather=gather, out=j["out"], chunks=a.chunks)
-            return out
+                return seqset.run(embed_fn=set_embed, gather=gather, outs=[j["out"] for j in jobs], chunks=a.chunks)
+            return [j["scorer"].run(j["d_centers"], j["d_labels"], gather=gather, out=j["out"], chunks=a.chunks)
+                    for j in jobs]
+
+        def output_names():
+            return ["scores_" + re.sub(r"[^A-Za-z0-9_.-]", "_", j["name"]) for j in jobs]
 
         # one embed call / one tail call exactly as the step issues them (this rank's shard), for the duration pass
         if seqset is not None:
@@ -376,7 +395,10 @@ def main():
             sc = tail_t(embed_t())
             if world > 1 and gather:
                 sc = allpairs.all_gather_varlen(sc, None)[0]
-            return sc
+            return [sc]
+
+        def output_names():
+            return ["scores"]
     else:
         centers, labels, _ = (synth.config2_pairs(seed=0) if a.workload == "pairs128" else synth.config5_pairs(seed=0))
         host_inputs.append((centers, labels, None))
@@ -401,7 +423,10 @@ def main():
 
         def step(gather=True):
             pooled = embed_t()
-            return eng.score_pairs(pooled[:b], pooled[b:])
+            return [eng.score_pairs(pooled[:b], pooled[b:])]
+
+        def output_names():
+            return ["scores"]
 
     def sync_all():
         torch.cuda.synchronize()
@@ -409,8 +434,8 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed_steps(count, fn):
-        """Barrier + synchronize on both sides, MAX over ranks."""
+    def timed_steps(count, fn, keep=None):
+        """Barrier + synchronize on both sides, MAX over ranks.  keep: a list that receives what the last step returned."""
         sync_all()
         t0 = time.perf_counter()
         for _ in range(count):
@@ -424,6 +449,8 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if keep is not None:
+            keep.extend(out)
         del out
         return dt
 
@@ -444,7 +471,14 @@ def main():
         step()
     torch.cuda.synchronize()
     calls["embed"] = calls["tail"] = 0
-    dt = timed_steps(a.steps, step)
+    last_outputs = [] if a.dump_outputs else None
+    dt = timed_steps(a.steps, step, keep=last_outputs)
+    dumped = None
+    if last_outputs is not None:
+        # copied before any later pass can reuse an output buffer (the pair-list tail scores into one)
+        if rank == 0:
+            dumped = dump_outputs(a.dump_outputs, list(zip(output_names(), last_outputs)))
+        del last_outputs
     launches_per_step = max(1, round(calls["embed"] / max(a.steps, 1)))
     tail_calls_per_step = calls["tail"] / max(a.steps, 1)
 
@@ -691,6 +725,7 @@ def main():
                                  "launches_timed": launches_timed},
             "sharded_output": sharded,
             "end_to_end": end_to_end,
+            "dump": dumped,
             "roofline": {"kernel": "sgpr::embed_big_kernel" if a.workload == "stress" else "sgpr::embed_kernel", "bound": "valu",
                          "bound_note": "frac = useful-work-equivalent throughput (algorithmic FLOPs of the factored formulation at "
                                        "each graph's processed slots / launch time) against the fp32 VECTOR peak - not a pipe "
@@ -759,6 +794,39 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, named):
+    """[(name, tensor)] of the last timed step -> out_dir/<name>.npy (float32; float64 stays float64), all files within
+    DUMP_BUDGET_BYTES.  Each tensor's share of the budget is proportional to its size; a matrix beyond its share keeps
+    the rows numpy.random.default_rng(0) draws (sorted), the same sample in every run of the same arguments.  Returns the
+    `dump` object of the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    as_dtype = [torch.float64 if t.dtype == torch.float64 else torch.float32 for _, t in named]
+    sizes = [t.numel() * (8 if d == torch.float64 else 4) for (_, t), d in zip(named, as_dtype)]
+    payload = DUMP_BUDGET_BYTES - DUMP_HEADER_BYTES * len(named)
+    arrays, written = {}, 0
+    for (name, t), d, size in zip(named, as_dtype, sizes):
+        t = t.detach()
+        share = payload * size / max(sum(sizes), 1)
+        rows = "all"
+        if size > share:
+            if t.dim() != 2:
+                raise ValueError("--dump-outputs: %s (%s) exceeds its share of the budget and is not a matrix"
+                                 % (name, tuple(t.shape)))
+            m = t.shape[0]
+            keep = max(1, int(share // (size // m)))
+            idx = np.sort(np.random.default_rng(0).choice(m, size=keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+            rows = "%d of %d: numpy.random.default_rng(0).choice(%d, %d, replace=False), sorted" % (keep, m, m, keep)
+        arr = t.to(d).cpu().numpy()
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, arr)
+        written += os.path.getsize(path)
+        arrays[name] = {"shape": list(arr.shape), "dtype": str(arr.dtype), "rows": rows}
+    return {"dir": out_dir, "bytes": written, "step": "last timed step", "arrays": arrays}
 
 
 def cpu_model():

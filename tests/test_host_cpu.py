@@ -342,6 +342,7 @@ def _allpairs_worker(rank, world, port, golden, out_dir):
         torch.testing.assert_close(rag_set[0], plain, rtol=0, atol=2e-6)
         assert rag_set[1].shape == (5, 5)
         torch.save(full, os.path.join(out_dir, "w%d.pt" % world))
+        torch.save(plain, os.path.join(out_dir, "w%d_plain.pt" % world))
     # several sequences as one job (allpairs.SequenceSet): the shards of both embedded by one call, matrices as before
     tc, tl = torch.from_numpy(centers), torch.from_numpy(labels)
     sset = allpairs.SequenceSet(scorer, [(tc, tl), (tc[:5], tl[:5])])
@@ -383,28 +384,38 @@ def _allpairs_worker(rank, world, port, golden, out_dir):
 
 @pytest.mark.timeout(300)
 def test_allpairs_two_ranks_equals_one(tmp_path, golden_dir):
-    """The gathered matrix of a 2-rank run is bit-identical to the single-process one."""
+    """The gathered matrix of a 2-rank run is bit-identical to the single-process one (plain gather and the chunked
+    one)."""
     import torch.multiprocessing as mp
     from oracle import sgpr_oracle as oracle
     from sg_pr_amd import synth, allpairs
     mp.spawn(_allpairs_worker, args=(2, 29611, golden_dir, str(tmp_path)), nprocs=2, join=True)
     mp.spawn(_allpairs_worker, args=(3, 29613, golden_dir, str(tmp_path)), nprocs=3, join=True)   # uneven: 4 + 4 + 3 rows
     two = torch.load(os.path.join(str(tmp_path), "w2.pt"))
+    two_plain = torch.load(os.path.join(str(tmp_path), "w2_plain.pt"))
     three = torch.load(os.path.join(str(tmp_path), "w3.pt"))
     sd = oracle.load_checkpoint(os.path.join(golden_dir, "model.pth"))
     centers, labels, _, poses = synth.kitti_like_sequence(11, 100, 3)
     poses[:, [3, 11]] *= 4.0                                 # (as in the worker)
     torch.set_num_threads(2)
-    # same shard shapes as the two ranks (torch-CPU matmuls are not bitwise batch-invariant; the HIP engine is,
-    # which tests/test_gpu_parity.py checks on the GPU)
+    # same shard shapes as the two ranks, and the same row pieces as their scoring (torch-CPU matmuls are not bitwise
+    # batch-invariant - whether a 1-row and a 6-row product agree depends on the host's BLAS; the HIP engine is
+    # invariant, which tests/test_gpu_parity.py checks on the GPU)
     def emb(lo, hi):
         return oracle.embed(sd, torch.from_numpy(synth.dense_features(centers[lo:hi], labels[lo:hi])), 10)[0]
+
+    def pieces(lo, hi, chunks=4):                            # AllPairsScorer.run's row pieces of one rank's block
+        n = max(1, min(chunks, hi - lo))
+        return [(lo + (hi - lo) * i // n, lo + (hi - lo) * (i + 1) // n) for i in range(n)]
 
     bounds = [allpairs.shard_bounds(11, 2, r) for r in range(2)]
     pooled = torch.cat([emb(lo, hi) for lo, hi in bounds])
     one = torch.cat([oracle.score_all_pairs(sd, pooled[lo:hi].contiguous(), pooled) for lo, hi in bounds])
-    assert two.shape == (11, 11)
-    assert torch.equal(one, two)
+    one_pieces = torch.cat([oracle.score_all_pairs(sd, pooled[a:b].contiguous(), pooled)
+                            for lo, hi in bounds for a, b in pieces(lo, hi)])
+    assert two.shape == (11, 11) and two_plain.shape == (11, 11)
+    assert torch.equal(one, two_plain)                       # chunks = 1: one block per rank, one gather
+    assert torch.equal(one_pieces, two)                      # chunks = 4: pieces shipped while the next is scored
     # the oracle's torch-CPU embed is not bitwise batch-invariant (see above): 3 ranks embed other shard shapes
     torch.testing.assert_close(three, two, rtol=0, atol=2e-6)
     assert not torch.equal(two, two.t())                 # the NTN is asymmetric: full square needed
