@@ -103,6 +103,24 @@ int main(int argc, char** argv) {
     printf("pair list: %lld pairs over %d row graphs in %d work items, %lld differ from the dense matrix\n", (long long)P, n_rows,
            n_items, (long long)differ);
     if (differ) return 4;
+
+    /* loop-closure candidates without the matrix (sgpr_score_topk): the best earlier frame of every frame, at least 1
+     * frame away - its score must be the dense matrix's entry, bit for bit */
+    float* d_best;
+    int32_t* d_best_idx;
+    void* d_ws4 = NULL;
+    const size_t ws4 = sgpr_score_topk_workspace_bytes(h, G, G, 1, SGPR_TOPK_CAUSAL);
+    CHECK_HIP(hipMalloc((void**)&d_best, (size_t)G * 4));
+    CHECK_HIP(hipMalloc((void**)&d_best_idx, (size_t)G * 4));
+    if (ws4) CHECK_HIP(hipMalloc(&d_ws4, ws4));
+    CHECK_SGPR(sgpr_score_topk(h, d_pooled, G, d_pooled, G, NULL, 0, 0, SGPR_TOPK_CAUSAL, 1, d_best, d_best_idx, d_ws4, ws4, NULL));
+    float* best = (float*)malloc((size_t)G * 4);
+    int32_t* best_idx = (int32_t*)malloc((size_t)G * 4);
+    CHECK_HIP(hipMemcpy(best, d_best, (size_t)G * 4, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(best_idx, d_best_idx, (size_t)G * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < G; ++r) differ += best_idx[r] >= 0 ? best[r] != score[(size_t)r * G + best_idx[r]] : r > 0;
+    printf("top-1 earlier frame per frame: %lld differ from the dense matrix\n", (long long)differ);
+    if (differ) return 5;
     FILE* out = fopen(argv[3], "wb");
     if (!out || fwrite(score, 4, (size_t)G * G, out) != (size_t)G * G) { fprintf(stderr, "cannot write %s\n", argv[3]); return 1; }
     fclose(out);

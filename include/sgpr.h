@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPR_ABI_VERSION 8
+#define SGPR_ABI_VERSION 9
 
 enum {
     SGPR_OK = 0,
@@ -327,6 +327,23 @@ int sgpr_f1_max(const sgpr_handle* h, const float* d_score, int R, int M, int64_
  * qualify.  One wave per row, one pass over the row. */
 int sgpr_topk_rows(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int row0, int window, int k,
                    float* d_values, int32_t* d_indices, void* stream);
+
+/* Loop-closure candidates straight from pooled vectors, without the R x M matrix: for every row r the k (1..16)
+ * best-scoring columns c of the rectangle d_pooled_rows [R] x d_pooled_cols [M], in sgpr_topk_rows' order and with its
+ * rules (score descending, column ascending; NaN never qualifies; (-inf, -1) where fewer than k columns qualify).  Column
+ * c qualifies for row r iff |c - self_r| > window (window < 0: no window) and, with SGPR_TOPK_CAUSAL in flags, c < self_r,
+ * where self_r = d_row_self[r] (device, [R], each in [0, M): sgpr_check_status reports an entry outside) or, with
+ * d_row_self NULL, row0 + r.  Every value is bit-identical to sgpr_score_all_pairs' entry at (r, c) on the same
+ * rectangle.  The production handle runs one fused launch (the all-pairs tail feeding per-row lists) plus a small merge
+ * launch; its workspace grows with R + M, never with R * M.  Wide-range and any-shape handles score row blocks of at
+ * most 64 MB with their own tail and select from each.  d_values / d_indices [R][k], device.  Arguments are checked
+ * before the device is touched: a NULL pointer, k outside 1..16 or unknown flag bits give SGPR_E_INVALID, a workspace
+ * below sgpr_score_topk_workspace_bytes SGPR_E_WORKSPACE.  Asynchronous on `stream`. */
+#define SGPR_TOPK_CAUSAL 1
+size_t sgpr_score_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags);
+int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                    const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
+                    int32_t* d_indices, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* LDS bytes per workgroup the embed kernel uses for (N, k) on this handle; 0 if unsupported. */
 size_t sgpr_embed_lds_bytes(const sgpr_handle* h, int N, int k);

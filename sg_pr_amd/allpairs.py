@@ -180,17 +180,20 @@ class AllPairsScorer:
     With an `sg_net.SG` model the two callables are its HIP paths; tests inject CPU
     stand-ins to exercise the sharding / collective logic under gloo."""
 
-    def __init__(self, model=None, embed_fn=None, score_fn=None, group=None):
+    def __init__(self, model=None, embed_fn=None, score_fn=None, group=None, topk_fn=None):
         self._engine = None
         if model is not None:
             embed_fn = lambda c, l: model.embed(c, l)[0]   # noqa: E731
             score_fn = model.score_all_pairs
+            topk_fn = topk_fn or model.loop_closures
             self._engine = model.engine()
 
         if embed_fn is None or score_fn is None:
             raise ValueError("need a model or both embed_fn and score_fn")
         self.embed_fn = embed_fn
         self.score_fn = score_fn
+        # topk_fn(rows, cols, k=, window=, row0=, causal=) -> (values [R,k], indices [R,k]): model.loop_closures
+        self.topk_fn = topk_fn
         self.group = group
 
     def _world(self):
@@ -320,6 +323,21 @@ class AllPairsScorer:
         world, rank = self._world()
         lo, _ = shard_bounds(block.shape[1], world, rank)
         return self._engine.topk_rows(block, k=k, row0=lo, window=window)
+
+    def topk(self, centers, labels, k=1, window=50, causal=False, local_pooled=None):
+        """Loop-closure candidates of the whole set without any score matrix: every rank embeds its shard, the pooled
+        vectors are all-gathered (pooled_all), each rank selects the k best columns of its rows [lo, hi) (row0 = lo)
+        and one all_gather_rows hands every rank all M rows -> (values f32 [M,k], indices i32 [M,k])."""
+        if self.topk_fn is None:
+            raise ValueError("AllPairsScorer.topk needs a model or a topk_fn")
+        pooled = self.pooled_all(centers, labels, local=local_pooled)
+        world, rank = self._world()
+        m = pooled.shape[0]
+        lo, hi = shard_bounds(m, world, rank)
+        vals, idx = self.topk_fn(pooled[lo:hi].contiguous(), pooled, k=k, window=window, row0=lo, causal=causal)
+        both = torch.cat((vals.view(torch.int32), idx), dim=1)       # one collective for both halves (bit copies)
+        both = all_gather_rows(both, m, self.group)
+        return both[:, :k].contiguous().view(torch.float32), both[:, k:].contiguous()
 
     def run(self, centers, labels, gather=True, out=None, chunks=4, local_pooled=None):
         """Whole job: returns the [M, M] matrix on rank 0 (row block elsewhere / if gather=False).

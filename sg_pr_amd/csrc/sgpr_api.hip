@@ -1149,6 +1149,73 @@ static int check_jobs(const sgpr_handle* h, int n, const sgpr_pairs_job* jobs) {
     return SGPR_OK;
 }
 
+// ---- sgpr_score_topk: the fused kernel on the production handle; the other handles score bounded row blocks with their
+//      own tail into the workspace and select from each block (the same selection, bit-equal to matrix + top-k)
+static const size_t kTopkBlockBytes = (size_t)64 << 20;    // score block of the chunked path
+
+static bool topk_fused(const sgpr_handle* h) { return !h->generic_only && !wide_range(h); }
+
+static int topk_block_rows(int R, int M) {
+    const size_t rows = kTopkBlockBytes / ((size_t)M * sizeof(float));
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)R, rows));
+}
+
+static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+size_t sgpr_score_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
+    if (!h || R < 0 || M < 0 || k < 1 || k > 16 || (flags & ~SGPR_TOPK_CAUSAL)) return 0;
+    if (R == 0 || M == 0) return 0;
+    if (topk_fused(h)) return score_topk_ws_bytes(h, R, M, k);
+    const int rb = topk_block_rows(R, M);
+    return a256((size_t)rb * M * sizeof(float)) + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
+}
+
+int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                    const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values, int32_t* d_indices,
+                    void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!h || R < 0 || M < 0 || (R > 0 && (!d_values || !d_indices)) || (R > 0 && M > 0 && (!d_pooled_rows || !d_pooled_cols))) {
+        set_error("sgpr_score_topk: NULL argument or negative count");
+        return SGPR_E_INVALID;
+    }
+    if (k < 1 || k > 16) {
+        set_error("sgpr_score_topk: k must lie in 1..16");
+        return SGPR_E_INVALID;
+    }
+    if (flags & ~SGPR_TOPK_CAUSAL) {
+        set_error("sgpr_score_topk: unknown flag bits " + std::to_string(flags & ~SGPR_TOPK_CAUSAL));
+        return SGPR_E_INVALID;
+    }
+    if ((int64_t)row0 + R > 0x7fffffffLL) {
+        set_error("sgpr_score_topk: row0 + R must fit an int");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = sgpr_score_topk_workspace_bytes(h, R, M, k, flags);
+    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
+        set_error("sgpr_score_topk: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    if (R == 0) return SGPR_OK;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0 || topk_fused(h))
+        return launch_score_topk(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, k, d_values,
+                                 d_indices, d_workspace, s);
+    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
+    float* block = static_cast<float*>(d_workspace);
+    unsigned char* ws = static_cast<unsigned char*>(d_workspace) + a256((size_t)rb * M * sizeof(float));
+    const size_t ws_bytes = workspace_bytes - a256((size_t)rb * M * sizeof(float));
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = std::min(rb, R - r0);
+        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
+        if (rc != SGPR_OK) return rc;
+        rc = launch_topk_rows_ext(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, k,
+                                  d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
+        if (rc != SGPR_OK) return rc;
+    }
+    return SGPR_OK;
+}
+
 size_t sgpr_score_all_pairs_multi_workspace_bytes(const sgpr_handle* h, int n_jobs, const sgpr_pairs_job* jobs) {
     if (check_jobs(h, n_jobs, jobs) != SGPR_OK) return 0;
     size_t any = 0;
@@ -1430,6 +1497,10 @@ int sgpr_check_status(const sgpr_handle* h, void* stream) {
         e = hipMemsetAsync(h->d_status, 0, sizeof(flag), s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(e, "sgpr_check_status: reset");
+        if (flag & 16) {
+            set_error("a d_row_self entry of sgpr_score_topk lies outside [0, M)");
+            return SGPR_E_INVALID;
+        }
         if (flag & 4) {
             set_error("internal: a semantic wave of the split embed launch did not deliver (pooled vector set to NaN)");
             return SGPR_E_HIP;

@@ -212,6 +212,12 @@ int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const
                            int64_t ld, void* ws, hipStream_t stream, bool wide = false);
 size_t score_all_pairs_multi_ws_bytes(int n, const sgpr_pairs_job* jobs);
 int launch_score_all_pairs_multi(const sgpr_handle* h, int n, const sgpr_pairs_job* jobs, void* ws, hipStream_t stream);
+size_t score_topk_ws_bytes(const sgpr_handle* h, int R, int M, int k);
+int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
+                      int row0, int window, int causal, int k, float* val, int32_t* idx, void* ws, hipStream_t stream);
+// sgpr_topk_rows' selection with a row_self table, the causal rule and an output row stride of k (sgpr_metrics.hip)
+int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                         int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
 size_t score_pair_list_ws_bytes(int NR, int M);
 int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float* cols, int M, const int32_t* plan,
                            int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream);

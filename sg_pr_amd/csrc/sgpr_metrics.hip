@@ -1470,10 +1470,14 @@ __global__ __launch_bounds__(F1_THREADS) void f1_refine_kernel(const PairScan sc
 }
 
 // ------------------------------------------------------------------ top-K per row
-template <int K>
+// EXT (sgpr_score_topk on the handles without a fused instance): own frames from row_self when given (an entry outside
+// [0, M) raises status bit 16), CAUSAL also drops every column from the own frame on, and the first kout of the K
+// entries leave at a row stride of kout
+template <int K, bool EXT = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ score, int R, int M, int64_t ld,
                                                         int row0, int window, float* __restrict__ out_val,
-                                                        int32_t* __restrict__ out_idx) {
+                                                        int32_t* __restrict__ out_idx, const int32_t* __restrict__ row_self = nullptr,
+                                                        int kout = K, int32_t* __restrict__ status = nullptr) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;
@@ -1486,8 +1490,17 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
         ix[q] = 0x7fffffff;
     }
     const float* sp = score + (int64_t)r * ld;
-    const int self = row0 + r;
+    int self = row0 + r;
+    if constexpr (EXT) {
+        if (row_self) {
+            self = row_self[r];
+            if (lane == 0 && (self < 0 || self >= M)) atomicOr(status, 16);
+        }
+    }
     for (int c = lane; c < M; c += 64) {
+        if constexpr (CAUSAL) {
+            if (c >= self) break;
+        }
         const int dc = c - self;
         if ((dc < 0 ? -dc : dc) <= window) continue;
         float x = sp[c];
@@ -1521,9 +1534,9 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
             bv = take ? ov : bv;
             bi = take ? oi : bi;
         }
-        if (lane == 0) {
-            out_val[(size_t)r * K + round] = bv;
-            out_idx[(size_t)r * K + round] = bi == 0x7fffffff ? -1 : bi;
+        if (lane == 0 && (!EXT || round < kout)) {
+            out_val[(size_t)r * (EXT ? kout : K) + round] = bv;
+            out_idx[(size_t)r * (EXT ? kout : K) + round] = bi == 0x7fffffff ? -1 : bi;
         }
         if (ix[0] == bi && bi != 0x7fffffff) {              // columns are unique: exactly one lane owns the winner
 #pragma unroll
@@ -1535,6 +1548,34 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
             ix[K - 1] = 0x7fffffff;
         }
     }
+}
+
+int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                         int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t s) {
+    if (R == 0) return SGPR_OK;
+    const dim3 grid((R + 3) / 4), block(256);
+    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;
+#define SGPR_TOPK_EXT(KK, C) hipLaunchKernelGGL((topk_rows_kernel<KK, true, C>), grid, block, 0, s, score, R, M, ld, row0, \
+                                                window, val, idx, row_self, k, status)
+    if (causal) {
+        switch (K) {
+            case 1: SGPR_TOPK_EXT(1, true); break;
+            case 4: SGPR_TOPK_EXT(4, true); break;
+            case 8: SGPR_TOPK_EXT(8, true); break;
+            default: SGPR_TOPK_EXT(16, true); break;
+        }
+    } else {
+        switch (K) {
+            case 1: SGPR_TOPK_EXT(1, false); break;
+            case 4: SGPR_TOPK_EXT(4, false); break;
+            case 8: SGPR_TOPK_EXT(8, false); break;
+            default: SGPR_TOPK_EXT(16, false); break;
+        }
+    }
+#undef SGPR_TOPK_EXT
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "topk_rows_kernel launch");
+    return SGPR_OK;
 }
 
 }  // namespace sgpr

@@ -593,13 +593,152 @@ __device__ __forceinline__ int ap_mode(float am, float um, float em, float l1) {
     return (um + l1 * em < 1024.f) ? 2 : 1;
 }
 
+// ------------------------------------------------------------------ fused top-k epilogue (sgpr_score_topk)
+// Instead of storing a super-block's scores, the instance with TK > 0 feeds them to a per-row top-TK list:
+//   TK = 1   every lane keeps the best (score, column) of ITS columns of row g in two registers (columns reach a lane in
+//            ascending order, so a strict comparison keeps the lower column of a tie); the 16 lanes of the row meet when
+//            the row group is flushed (four xor-shuffles).
+//   TK > 1   lane l15 of lane group g holds entry l15 of row g's list (TK <= 16 lanes), the TK-th entry is the row's
+//            threshold (two registers).  A column block whose candidates all fail their threshold costs a compare and a
+//            ballot; otherwise the 16 candidates of each row and its list are merged by rank (each value counts what beats
+//            it - 16 + TK shuffles -) and scattered through 512 bytes of LDS per wave.  No runtime-indexed array: nothing
+//            of the list can go to scratch.
+// Order: score descending, then column ascending; NaN never qualifies; (-inf, INT_MAX) is an empty slot (written as -1).
+// A workgroup's work items are one contiguous row-major range, so it sees every column chunk of the row groups inside
+// its range and writes their lists straight to the result; the row groups at its two ends are shared with neighbours and
+// go to partial list slots [wg][2][16 rows][k] that topk_merge_kernel folds together: at most R + 32 grid lists.
+struct TopkArgs {
+    const int32_t* row_self;   // [R] the column index of each query row's own frame, or nullptr: row0 + r
+    int row0, window, causal, k, wg;
+    float* val;                // [R][k]
+    int32_t* idx;
+    float* pval;               // [grid][2][AP_ROWS][k] partial lists of the row groups at the ends of a workgroup's range
+    int32_t* pidx;
+    int32_t* status;           // bit 16: a row_self entry outside [0, M)
+};
+
+constexpr int TK_EMPTY = 0x7fffffff;
+
+__device__ __forceinline__ bool tk_beats(float av, int ac, float bv, int bc) { return av > bv || (av == bv && ac < bc); }
+
+// eligibility of column c for a row whose own frame is s: c < M and (c < ea or c > eb) - the window [s - w, s + w] and,
+// causal, everything from s on are cut out
+__device__ __forceinline__ void tk_bounds(long long s, int window, int causal, int& ea, int& eb) {
+    const long long w = window < 0 ? 0 : window;
+    long long a = window < 0 ? (causal ? s : 0x7fffffffLL) : s - w;
+    long long b = (causal || window < 0) ? 0x7fffffffLL : s + w;
+    ea = (int)(a < -1 ? -1 : (a > 0x7fffffffLL ? 0x7fffffffLL : a));
+    eb = (int)(b < -2 ? -2 : (b > 0x7fffffffLL ? 0x7fffffffLL : b));
+}
+
+// merge the candidate (cv, cc) of every lane (ok: it qualifies) into its lane group's list (entry l15 in (lv, lc));
+// sv / sc: this wave's 64-entry LDS slice
+template <int K>
+__device__ __forceinline__ void tk_merge(float& lv, int& lc, float cv, int cc, bool ok, float* sv, int* sc) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15, base = lane & 48;
+    if (!ok) {
+        cv = -INFINITY;
+        cc = TK_EMPTY;
+    }
+    int rc = 0, rl = l15;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const float ov = __shfl(cv, base + j);
+        const int oc = __shfl(cc, base + j);
+        rc += tk_beats(ov, oc, cv, cc) ? 1 : 0;
+        rl += tk_beats(ov, oc, lv, lc) ? 1 : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const float ov = __shfl(lv, base + j);
+        const int oc = __shfl(lc, base + j);
+        rc += tk_beats(ov, oc, cv, cc) ? 1 : 0;
+    }
+    if (ok && rc < K) {
+        sv[base + rc] = cv;
+        sc[base + rc] = cc;
+    }
+    if (l15 < K && rl < K) {
+        sv[base + rl] = lv;
+        sc[base + rl] = lc;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (l15 < K) {
+        lv = sv[lane];
+        lc = sc[lane];
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// one super-block's scores of row g (lane: columns c0 .. c0 + 3) into the row's list
+template <int K>
+__device__ __forceinline__ void tk_push(const float (&sc)[4], int c0, int M, int ea, int eb, bool live, float& tv, int& tc,
+                                        float& thv, int& thc, float* lsv, int* lsc) {
+    if constexpr (K == 1) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int c = c0 + b;
+            const float v = sc[b];
+            if (live && c < M && (c < ea || c > eb) && v == v && tk_beats(v, c, tv, tc)) {
+                tv = v;
+                tc = c;
+            }
+        }
+    } else {
+        // (a rolled loop with one merge body spills more, 300 against 248-312 bytes per lane: kept unrolled)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int c = c0 + b;
+            const float v = sc[b];
+            const bool q = live && c < M && (c < ea || c > eb) && v == v && tk_beats(v, c, thv, thc);
+            if (__any(q)) {
+                tk_merge<K>(tv, tc, v, c, q, lsv, lsc);
+                const int src = (threadIdx.x & 48) + K - 1;
+                thv = __shfl(tv, src);
+                thc = __shfl(tc, src);
+            }
+        }
+    }
+}
+
+// the lists of row group rg (lane group g of this wave: row r) leave: to the result when this workgroup saw every column
+// chunk of the row group, else to partial slot 0 (the row group its range starts in) or 1 (the one it ends in)
+template <int K>
+__device__ __forceinline__ void tk_flush(const TopkArgs& a, int rg, int ncc, int it0, int it1, int r, int R, float tv, int tc) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15;
+    if constexpr (K == 1) {
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) {
+            const float ov = __shfl_xor(tv, m);
+            const int oc = __shfl_xor(tc, m);
+            if (tk_beats(ov, oc, tv, tc)) {
+                tv = ov;
+                tc = oc;
+            }
+        }
+    }
+    if (r >= R || l15 >= a.k) return;
+    if ((int64_t)rg * ncc >= it0 && (int64_t)(rg + 1) * ncc <= it1) {
+        a.val[(size_t)r * a.k + l15] = tv;
+        a.idx[(size_t)r * a.k + l15] = tc == TK_EMPTY ? -1 : tc;
+    } else {
+        const int slot = rg == it0 / ncc ? 0 : 1;
+        const size_t p = ((size_t)(a.wg * 2 + slot) * AP_ROWS + (r - rg * AP_ROWS)) * a.k + l15;
+        a.pval[p] = tv;
+        a.pidx[p] = tc;
+    }
+}
+
 // the work items [it0, it1) of one R x M rectangle
-template <int NI, int VAR, bool CL>
+// TK = 0: the matrix is stored to score; TK > 0: the scores feed per-row top-TK lists (*tk), nothing is stored
+template <int NI, int VAR, bool CL, int TK = 0>
 __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k, const bool fast, int R, int M,
                                          const unsigned short* __restrict__ Ab, const unsigned short* __restrict__ Cb,
                                          const float* __restrict__ ur, const float* __restrict__ prow,
                                          const float* __restrict__ pcol, float* __restrict__ score, int64_t ld,
-                                         const int it0, const int it1) {
+                                         const int it0, const int it1, const TopkArgs* tk = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const f16x8 w1hi = k.w1hi, w1lo = k.w1lo;
@@ -611,9 +750,28 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
     f32x4 u4[AP_RW];
     int cur_rg = -1, rbase = 0;
     const int nsb = (M + AP_SB - 1) / AP_SB;
+    // top-k state (TK > 0): the list entry / best of this lane (row rbase + g), the row's threshold, its eligible columns
+    float tv = -INFINITY, thv = -INFINITY;
+    int tc = TK_EMPTY, thc = TK_EMPTY, ea = 0, eb = 0;
+    __shared__ float tk_sv[TK > 1 ? 4 : 1][64];
+    __shared__ int tk_sc[TK > 1 ? 4 : 1][64];
+    float* const lsv = tk_sv[TK > 1 ? wave : 0];
+    int* const lsc = tk_sc[TK > 1 ? wave : 0];
     for (int it = it0; it < it1; ++it) {
         const int rg = it / ncc, cc = it - rg * ncc;
         if (rg != cur_rg) {
+            if constexpr (TK > 0) {
+                if (cur_rg >= 0) tk_flush<TK>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
+                tv = thv = -INFINITY;
+                tc = thc = TK_EMPTY;
+                const int r = rg * AP_ROWS + wave * AP_RW + g;
+                long long s = tk->row0 + (long long)r;
+                if (tk->row_self) {
+                    s = tk->row_self[min(r, R - 1)];
+                    if (r < R && l15 == 0 && (s < 0 || s >= M)) atomicOr(tk->status, 16);
+                }
+                tk_bounds(s, tk->window, tk->causal, ea, eb);
+            }
             cur_rg = rg;
             rbase = rg * AP_ROWS + wave * AP_RW;
 #pragma unroll
@@ -628,8 +786,36 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
         }
         const int sb0 = cc * (AP_COLS / AP_SB), sb1 = min(nsb, sb0 + AP_COLS / AP_SB);
         if (rbase >= R) continue;                          // this wave's rows lie past the matrix edge
+        if constexpr (TK > 0) {
+            // causal without a row_self table: a work item whose first column is ineligible for the last row of the row
+            // group (the largest own frame) has no eligible column for any row of it
+            if (tk->causal && !tk->row_self) {
+                const long long smax = tk->row0 + (long long)min(R, (rg + 1) * AP_ROWS) - 1;
+                if ((long long)sb0 * AP_SB >= smax - (tk->window > 0 ? tk->window : 0)) continue;
+            }
+        }
         if (!fast) {      // inputs outside the f16 range: exact fp32 per-pair arithmetic
-            slow_tile(w, prow, pcol, rbase, min(R, rbase + AP_RW), sb0 * AP_SB, min(M, sb1 * AP_SB), score, ld);
+            if constexpr (TK == 0) {
+                slow_tile(w, prow, pcol, rbase, min(R, rbase + AP_RW), sb0 * AP_SB, min(M, sb1 * AP_SB), score, ld);
+            } else {
+                // the same per-pair values, gathered into the lane layout of the fast path (lane (g, l15): row g,
+                // columns 4 l15 .. 4 l15 + 3 of the super-block) and handed to the lists
+#pragma unroll 1
+                for (int sb = sb0; sb < sb1; ++sb) {
+                    float sc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+                    for (int rr = 0; rr < AP_RW && rbase + rr < R; ++rr)
+#pragma unroll 1
+                        for (int cl = 0; cl < AP_SB && sb * AP_SB + cl < M; ++cl) {
+                            const float v = slow_pair(w, prow + (size_t)(rbase + rr) * F, pcol + (size_t)(sb * AP_SB + cl) * F);
+                            if (rr == g && (cl >> 2) == l15) {
+#pragma unroll
+                                for (int b = 0; b < 4; ++b) sc[b] = (cl & 3) == b ? v : sc[b];
+                            }
+                        }
+                    tk_push<TK>(sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, tv, tc, thv, thc, lsv, lsc);
+                }
+            }
             continue;
         }
         // column operands of block (sb, b): e2_c[8g .. 8g+7], c = 64 sb + 4 l15 + b; 1 KB contiguous per wave and plane,
@@ -722,6 +908,10 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                 sc[b] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(zsel, -kL2E, nb2)));
             }
             const int r = rbase + g, c0 = sb * AP_SB + 4 * l15;
+            if constexpr (TK > 0) {
+                tk_push<TK>(sc, c0, M, ea, eb, r < R, tv, tc, thv, thc, lsv, lsc);
+                continue;
+            }
             if ((VAR & 2) && sc[0] + sc[1] + sc[2] + sc[3] != 12345.678f) continue;
             if (r < R) {
                 float* dst = score + (size_t)r * ld + c0;
@@ -739,6 +929,9 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                 }
             }
         }
+    }
+    if constexpr (TK > 0) {
+        if (cur_rg >= 0) tk_flush<TK>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
     }
 }
 
@@ -797,6 +990,86 @@ __global__ __launch_bounds__(256, OCC) void score_all_pairs_multi_kernel(const D
             ap_items<NI, 0, true>(w, k, true, q.R, q.M, q.Ab, q.Cb, q.ur, q.rows, q.cols, q.score, q.ld, lo, hi);
         else
             ap_items<NI, 0, false>(w, k, mode != 0, q.R, q.M, q.Ab, q.Cb, q.ur, q.rows, q.cols, q.score, q.ld, lo, hi);
+    }
+}
+
+// the rectangle's top-K per row (sgpr_score_topk): score_all_pairs_kernel's range question, work split and arithmetic,
+// the TK epilogue of ap_items instead of the store
+#ifndef SGPR_TK_OCC
+#define SGPR_TK_OCC 3        // (at four workgroups per CU the k = 1 instance spills 356 bytes per lane, at three nothing)
+#endif
+constexpr int TK_OCC = SGPR_TK_OCC;
+
+template <int OCC, int NI, int K>
+__global__ __launch_bounds__(256, OCC) void score_topk_kernel(const DevWeights w, int R, int M,
+                                                              const unsigned short* __restrict__ Ab,
+                                                              const unsigned short* __restrict__ Cb,
+                                                              const float* __restrict__ ur,
+                                                              const float* __restrict__ rng, int nrng,
+                                                              const float* __restrict__ prow,
+                                                              const float* __restrict__ pcol, TopkArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
+    ap_range(rng, nrng, am, um, em, l1);
+    const int mode = ap_mode(am, um, em, l1);
+    const ApConsts k = ap_consts(w, l15, g);
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const unsigned nwg = gridDim.x;
+    const unsigned wg = (nwg & 7u) == 0u ? (blockIdx.x & 7u) * (nwg >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int it0 = (int)(items * wg / nwg), it1 = (int)(items * (wg + 1) / nwg);
+    a.wg = (int)wg;
+    if (mode == 2)
+        ap_items<NI, 0, true, K>(w, k, true, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, &a);
+    else
+        ap_items<NI, 0, false, K>(w, k, mode != 0, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, &a);
+}
+
+// row groups shared by several workgroups: their partial lists -> the result.  One workgroup per row group, lane group g
+// of wave v: row 16 rg + 4 v + g.  The workgroups that touched row group rg are a contiguous run of logical indices.
+template <int K>
+__global__ __launch_bounds__(256) void topk_merge_kernel(int R, int M, int nwg, TopkArgs a) {
+    __shared__ float sv[4][64];
+    __shared__ int sc[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15;
+    const int rg = blockIdx.x;
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const int64_t lo = (int64_t)rg * ncc, hi = lo + ncc;
+    int w0 = 0, w1 = nwg - 1;                           // first workgroup whose range ends past lo
+    for (int n = nwg - 1; w0 < n;) {
+        const int m = (w0 + n) >> 1;
+        if (items * (m + 1) / nwg > lo) n = m; else w0 = m + 1;
+    }
+    for (int n = 0; n < w1;) {                          // last workgroup whose range starts before hi
+        const int m = (n + w1 + 1) >> 1;
+        if (items * m / nwg < hi) n = m; else w1 = m - 1;
+    }
+    if (w0 >= w1) return;                               // one workgroup saw the whole row group: its lists are the result
+    const int rr = wave * AP_RW + (lane >> 4), r = rg * AP_ROWS + rr;
+    float tv = -INFINITY;
+    int tc = TK_EMPTY;
+#pragma unroll 1
+    for (int wv = w0; wv <= w1; ++wv) {
+        const int slot = (items * wv / nwg) / ncc == rg ? 0 : 1;
+        const size_t p = ((size_t)(wv * 2 + slot) * AP_ROWS + rr) * a.k + l15;
+        const bool ok = r < R && l15 < a.k;
+        const float cv = ok ? a.pval[p] : -INFINITY;
+        const int cc = ok ? a.pidx[p] : TK_EMPTY;
+        tk_merge<K>(tv, tc, cv, cc, ok && cc != TK_EMPTY, sv[wave], sc[wave]);
+    }
+    if (r < R && l15 < a.k) {
+        a.val[(size_t)r * a.k + l15] = tv;
+        a.idx[(size_t)r * a.k + l15] = tc == TK_EMPTY ? -1 : tc;
+    }
+}
+
+__global__ __launch_bounds__(256) void topk_fill_kernel(int64_t n, float* __restrict__ val, int32_t* __restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        val[i] = -INFINITY;
+        idx[i] = -1;
     }
 }
 
@@ -1065,6 +1338,74 @@ int launch_score_all_pairs_multi(const sgpr_handle* h, int n, const sgpr_pairs_j
     hipLaunchKernelGGL((score_all_pairs_multi_kernel<AP_MULTI_OCC, 1>), dim3(grid), dim3(256), 0, stream, h->w, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_all_pairs_multi_kernel launch");
+    return SGPR_OK;
+}
+
+// ------------------------------------------------------------------ fused score + top-k (sgpr_score_topk)
+// workspace: score_all_pairs' operands | partial lists [grid][2][AP_ROWS][k] values f32 | the same, columns i32
+static int64_t topk_grid(const sgpr_handle* h, int R, int M) {
+    const int64_t items = (int64_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
+    const int64_t slots = (int64_t)h->num_cus * TK_OCC;
+    return items < slots ? items : slots;
+}
+
+size_t score_topk_ws_bytes(const sgpr_handle* h, int R, int M, int k) {
+    if (R == 0 || M == 0) return 0;
+    const size_t lists = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS * k;
+    return align256(score_all_pairs_ws_bytes(R, M)) + align256(lists * sizeof(float)) + lists * sizeof(int32_t);
+}
+
+int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
+                      int row0, int window, int causal, int k, float* val, int32_t* idx, void* ws, hipStream_t stream) {
+    if (R == 0) return SGPR_OK;
+    hipError_t e;
+    if (M == 0) {                                          // no column at all: every slot is empty
+        const int64_t n = (int64_t)R * k;
+        hipLaunchKernelGGL(topk_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, val, idx);
+        e = hipGetLastError();
+        return e == hipSuccess ? SGPR_OK : hip_fail(e, "topk_fill_kernel launch");
+    }
+    const int ngroups = ap_prep_groups(R, M), nrng = 2 * ngroups;
+    unsigned char* base = static_cast<unsigned char*>(ws);
+    float* ur = reinterpret_cast<float*>(base);            // the operand layout of launch_score_all_pairs
+    float* rng = ur + (size_t)R * T;
+    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
+    unsigned short* Cb = Ab + (size_t)R * 2 * 64 * 8;
+    const int64_t grid = topk_grid(h, R, M);
+    const size_t lists = (size_t)grid * 2 * AP_ROWS * k;
+    TopkArgs a;
+    a.row_self = row_self;
+    a.row0 = row0;
+    a.window = window;
+    a.causal = causal;
+    a.k = k;
+    a.wg = 0;
+    a.val = val;
+    a.idx = idx;
+    a.pval = reinterpret_cast<float*>(base + align256(score_all_pairs_ws_bytes(R, M)));
+    a.pidx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(a.pval) + align256(lists * sizeof(float)));
+    a.status = h->d_status;
+    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+    const dim3 gd((unsigned)grid), bd(256), gm((unsigned)((R + AP_ROWS - 1) / AP_ROWS));
+    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;  // the compiled instance: the first k of its K entries
+    switch (K) {
+        case 1: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 1>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
+        case 4: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 4>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
+        case 8: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 8>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
+        default: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 16>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "score_topk_kernel launch");
+    switch (K) {
+        case 1: hipLaunchKernelGGL(topk_merge_kernel<1>, gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 4: hipLaunchKernelGGL(topk_merge_kernel<4>, gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 8: hipLaunchKernelGGL(topk_merge_kernel<8>, gm, bd, 0, stream, R, M, (int)grid, a); break;
+        default: hipLaunchKernelGGL(topk_merge_kernel<16>, gm, bd, 0, stream, R, M, (int)grid, a); break;
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "topk_merge_kernel launch");
     return SGPR_OK;
 }
 

@@ -41,6 +41,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_forward_workspace_bytes", "sgpr_forward_dense", "sgpr_check_status",
                "sgpr_pair_positives", "sgpr_pair_threshold_counts_workspace_bytes", "sgpr_pair_threshold_counts",
                "sgpr_f1_max_workspace_bytes", "sgpr_f1_max", "sgpr_topk_rows",
+               "sgpr_score_topk_workspace_bytes", "sgpr_score_topk",
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
                "sgpr_attention_pool_any", "sgpr_ntn_any",
                "sgpr_cluster_workspace_bytes", "sgpr_cluster_scan", "sgpr_graph_edges",
@@ -163,6 +164,10 @@ def load_library():
     lib.sgpr_f1_max.argtypes = [vp, vp, i32, i32, i64, i32, vp, dbl, dbl, vp, i64, vp, vp, sz, vp]
     lib.sgpr_topk_rows.restype = i32
     lib.sgpr_topk_rows.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, vp, vp]
+    lib.sgpr_score_topk_workspace_bytes.restype = sz
+    lib.sgpr_score_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
+    lib.sgpr_score_topk.restype = i32
+    lib.sgpr_score_topk.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
     lib.sgpr_embed_lds_bytes.restype = sz
     lib.sgpr_embed_lds_bytes.argtypes = [vp, i32, i32]
     lib.sgpr_knn.restype = i32
@@ -759,6 +764,35 @@ class Engine:
         idx = torch.empty(r, k, dtype=torch.int32, device=self.device)
         rc = self.lib.sgpr_topk_rows(self._h, _ptr(score), r, m, score.stride(0), int(row0), int(window), int(k),
                                      _ptr(vals), _ptr(idx), self._stream())
+        self._check(rc)
+        return vals, idx
+
+    TOPK_CAUSAL = 1     # SGPR_TOPK_CAUSAL of include/sgpr.h
+
+    def score_topk_workspace_bytes(self, r, m, k=1, causal=False):
+        return int(self.lib.sgpr_score_topk_workspace_bytes(self._h, int(r), int(m), int(k),
+                                                            self.TOPK_CAUSAL if causal else 0))
+
+    def score_topk(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None):
+        """Best k columns per row of the rectangle pooled_rows x pooled_cols without forming it (sgpr_score_topk):
+        column c qualifies for row r iff |c - self_r| > window (window < 0: no window) and, causal, c < self_r, where
+        self_r = row_self[r] or row0 + r.  -> (values f32 [R,k], indices i32 [R,k]); every value is bit-identical to
+        score_all_pairs' entry (r, c); (-inf, -1) where fewer than k columns qualify."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        rs = None
+        if row_self is not None:
+            rs = self._dev(row_self, torch.int32, "row_self")
+            if rs.shape != (r,):
+                raise ValueError("row_self must be [%d], got %s" % (r, tuple(rs.shape)))
+        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
+        flags = self.TOPK_CAUSAL if causal else 0
+        ws_bytes = self.lib.sgpr_score_topk_workspace_bytes(self._h, r, m, int(k), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_score_topk(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window), flags,
+                                      int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         return vals, idx
 

@@ -225,3 +225,38 @@ def counts_of(score, gt):
             rank_sum = int((2 * gt_s + eq_s).sum())
         return counts, rank_sum
     return pos, count_fn
+
+
+def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1024):
+    """Recall@1..K of loop-closure candidates (sgpr_score_topk's indices [M,K] of query frames 0..M-1 against frames
+    0..M'-1; -1 = no candidate).  A query counts only if some frame it was allowed to match (|c - r| > window, window < 0:
+    no window; causal: c < r) lies within p_thresh of it; it is a hit at N if one of its first N indices does.
+    pose_xz: [M', 2] (or [M', 12] KITTI rows).  Plain torch on the indices' device, chunked by rows (not a hot path).
+    -> float64 numpy [K]: hits at N / counted queries (0 when no query counts)."""
+    import torch
+    from .allpairs import pose_xz as _xz
+    idx = torch.as_tensor(indices)
+    dev = idx.device
+    xz = _xz(pose_xz).to(dev)
+    m, kk = idx.shape
+    cols = torch.arange(xz.shape[0], device=dev)
+    hits = torch.zeros(kk, dtype=torch.float64, device=dev)
+    counted = 0
+    for lo in range(0, m, chunk):
+        hi = min(m, lo + chunk)
+        rows = torch.arange(lo, hi, device=dev)
+        near = torch.cdist(xz[lo:hi], xz) <= p_thresh                        # [n, M']
+        ok = torch.ones_like(near)
+        if window >= 0:
+            ok &= (cols[None, :] - rows[:, None]).abs() > window
+        if causal:
+            ok &= cols[None, :] < rows[:, None]
+        valid = (near & ok).any(dim=1)                                       # queries with a revisit to find
+        ix = idx[lo:hi].long()
+        got = torch.zeros(ix.shape, dtype=torch.bool, device=dev)
+        has = ix >= 0
+        got[has] = near.gather(1, ix.clamp(min=0))[has]
+        first = torch.cummax(got.to(torch.int32), dim=1).values.bool()       # hit within the first N
+        hits += (first & valid[:, None]).sum(dim=0).to(torch.float64)
+        counted += int(valid.sum())
+    return (hits / counted).cpu().numpy() if counted else np.zeros(kk)

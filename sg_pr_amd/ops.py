@@ -1,9 +1,11 @@
-"""`torch.library` custom ops over the C-ABI (SURVEY §8b "Custom ops"): the hot path as four dispatcher-visible ops.
+"""`torch.library` custom ops over the C-ABI (SURVEY §8b "Custom ops"): the hot path as five dispatcher-visible ops.
 
     torch.ops.sgpr.embed(centers [G,N,3] f32, labels [G,N] i32, weights_blob [48689] f32, k) -> (pooled, att)
     torch.ops.sgpr.score_pairs(pooled1 [B,32], pooled2 [B,32], weights_blob)                -> score [B]
     torch.ops.sgpr.score_all_pairs(pooled_rows [R,32], pooled_cols [M,32], weights_blob)    -> score [R,M]
     torch.ops.sgpr.forward_dense(features_1 [B,15,N], features_2 [B,15,N], weights_blob, k) -> (score, att1, att2)
+    torch.ops.sgpr.score_topk(pooled_rows [R,32], pooled_cols [M,32], weights_blob, k, window, row0, causal, row_self)
+                                                                                            -> (values [R,k], indices [R,k])
 
 `weights_blob` is the flat fp32 tensor of `engine.blob_from_state_dict` (order in include/sgpr.h); one engine handle is
 kept per (blob tensor, version, device) and released with the tensor.  GPU tensors only: there is no CPU implementation - a CPU call raises.  Fake (meta)
@@ -93,3 +95,17 @@ def forward_dense(features_1: torch.Tensor, features_2: torch.Tensor, weights_bl
 def _(features_1, features_2, weights_blob, k):
     b, _, n = features_1.shape
     return features_1.new_empty((b,)), features_1.new_empty((b, n)), features_1.new_empty((b, n))
+
+
+@torch.library.custom_op("sgpr::score_topk", mutates_args=())
+def score_topk(pooled_rows: torch.Tensor, pooled_cols: torch.Tensor, weights_blob: torch.Tensor, k: int = 1,
+               window: int = -1, row0: int = 0, causal: bool = False,
+               row_self: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    return _engine_for(weights_blob, pooled_rows.device).score_topk(pooled_rows, pooled_cols, k=k, window=window,
+                                                                    row0=row0, causal=causal, row_self=row_self)
+
+
+@score_topk.register_fake
+def _(pooled_rows, pooled_cols, weights_blob, k=1, window=-1, row0=0, causal=False, row_self=None):
+    r = pooled_rows.shape[0]
+    return pooled_rows.new_empty((r, k)), pooled_rows.new_empty((r, k), dtype=torch.int32)

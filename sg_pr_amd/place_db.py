@@ -1,0 +1,148 @@
+"""A place database for loop-closure retrieval: the pooled vectors of every graph added so far, on the device, queried
+with sgpr_score_topk - the k best matches per query, no similarity matrix at any size.
+
+    db = PlaceDatabase(model)
+    ids = db.add(centers, labels)                      # embed (ordered launch), append; -> new ids
+    vals, idx = db.query(centers, labels, k=1, window=50, causal=True)   # new graphs: frames len(db), len(db) + 1, ...
+    vals, idx = db.query_ids(ids, k=4, window=50)      # members: row_self = their ids
+    db.save("map.npz"); db = PlaceDatabase.load("map.npz", model)
+
+A vector costs 128 bytes of device memory (the matrix of a 100 k-graph map would be 40 GB).  The file keeps the vectors,
+the architecture and a sha256 of the checkpoint's weight blob: vectors of one checkpoint are meaningless to another, so
+`load` refuses them.
+
+    python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal]
+
+runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
+frame, indices [M,K], scores [M,K] and recall@1..K.
+"""
+import argparse
+import hashlib
+import os
+
+import numpy as np
+import torch
+
+from . import engine as _engine
+from . import metrics
+
+_DIMS = [f for f, _ in _engine.SgprDims._fields_]
+
+
+def weights_sha256(model):
+    """sha256 of the flat fp32 weight blob the engine is built from (include/sgpr.h order)."""
+    return hashlib.sha256(_engine.blob_from_state_dict(model.state_dict()).tobytes()).hexdigest()
+
+
+class PlaceDatabase:
+    def __init__(self, model, capacity=1024):
+        self.model = model
+        self.eng = model.engine()
+        self.k = int(model.args.K)
+        self._buf = torch.empty(max(int(capacity), 1), self.eng.pw, dtype=torch.float32, device=self.eng.device)
+        self.n = 0
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def pooled(self):
+        """[len, pooled width] device view of the stored vectors."""
+        return self._buf[:self.n]
+
+    def _embed(self, centers, labels):
+        order, cap = self.eng.size_order(centers, labels, self.k)
+        pooled = self.eng.embed(centers, labels, self.k, node_cap=cap, order=order)[0]
+        self.eng.check_status()
+        return pooled
+
+    def append_pooled(self, pooled):
+        """Store already embedded vectors [g, pooled width] -> their ids (int64 [g])."""
+        pooled = self.eng._pooled(pooled, "pooled")
+        g = pooled.shape[0]
+        if self.n + g > self._buf.shape[0]:                  # geometric growth: amortised O(1) copies per vector
+            cap = max(2 * self._buf.shape[0], self.n + g)
+            buf = torch.empty(cap, self._buf.shape[1], dtype=torch.float32, device=self._buf.device)
+            buf[:self.n] = self._buf[:self.n]
+            self._buf = buf
+        self._buf[self.n:self.n + g] = pooled
+        ids = torch.arange(self.n, self.n + g, dtype=torch.int64)
+        self.n += g
+        return ids
+
+    def add(self, centers, labels):
+        """Embed packed graphs (centers [g,N,3], labels [g,N]) and append them -> their ids (int64 [g])."""
+        return self.append_pooled(self._embed(centers, labels))
+
+    def query(self, centers, labels, k=1, window=-1, causal=False):
+        """The k best members for graphs that are NOT in the database, taken as frames len(db), len(db) + 1, ...
+        -> (scores f32 [g,k], ids i32 [g,k]) on the device."""
+        return self.eng.score_topk(self._embed(centers, labels), self.pooled, k=k, window=window, row0=self.n,
+                                   causal=causal)
+
+    def query_ids(self, ids, k=1, window=-1, causal=False):
+        """The k best members for members `ids` (their own id is their frame: row_self = ids)."""
+        ids = torch.as_tensor(ids, dtype=torch.int64).to(self._buf.device)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n):
+            raise IndexError("query_ids: ids must lie in [0, %d)" % self.n)
+        rows = self.pooled.index_select(0, ids)
+        return self.eng.score_topk(rows, self.pooled, k=k, window=window, causal=causal,
+                                   row_self=ids.to(torch.int32))
+
+    def save(self, path):
+        dims = np.array([getattr(self.eng.dims, f) for f in _DIMS], dtype=np.int64)
+        np.savez(path, pooled=self.pooled.cpu().numpy(), dims=dims, weights_sha256=np.array(weights_sha256(self.model)))
+
+    @classmethod
+    def load(cls, path, model):
+        with np.load(path, allow_pickle=False) as z:
+            pooled, dims, sha = z["pooled"], z["dims"], str(z["weights_sha256"])
+        if sha != weights_sha256(model):
+            raise ValueError("%s was built with another checkpoint (weights sha256 %s...)" % (path, sha[:12]))
+        db = cls(model, capacity=max(pooled.shape[0], 1))
+        have = np.array([getattr(db.eng.dims, f) for f in _DIMS], dtype=np.int64)
+        if not np.array_equal(have, dims) or pooled.shape[1] != db.eng.pw:
+            raise ValueError("%s holds vectors of another architecture (dims %s)" % (path, dims.tolist()))
+        db.append_pooled(torch.from_numpy(pooled))
+        return db
+
+
+def main(argv=None):
+    import sys
+    from .graph_store import PackedSequence, pack_directory
+    from .parser_sg import sgpr_args
+    from .sg_net import SGTrainer
+    ap = argparse.ArgumentParser(prog="python -m sg_pr_amd.place_db")
+    ap.add_argument("config", nargs="?", default="./config/config.yml")
+    ap.add_argument("--k", type=int, default=1)
+    ap.add_argument("--window", type=int, default=50)
+    ap.add_argument("--causal", action="store_true")
+    opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    args = sgpr_args()
+    args.load(opt.config)
+    trainer = SGTrainer(args, False)
+    trainer.model.eval()
+    os.makedirs(args.output_path, exist_ok=True)
+    results = {}
+    for sequence in args.sequences:
+        cache = os.path.join(args.output_path, sequence + "_packed.npz")
+        if os.path.exists(cache):
+            seq = PackedSequence.load(cache)
+        else:
+            seq = pack_directory(os.path.join(args.graph_pairs_dir, sequence), int(args.node_num),
+                                 trainer.number_of_labels)
+            seq.save(cache)
+        db = PlaceDatabase(trainer.model, capacity=len(seq))
+        db.add(seq.centers, seq.labels)                    # the launch evaluate_all_pairs makes: size_order + ordered embed
+        m = len(seq)
+        vals, idx = db.query_ids(torch.arange(m), k=opt.k, window=opt.window, causal=opt.causal)
+        recall = metrics.recall_at_n(idx, seq.poses, p_thresh=float(args.p_thresh), window=opt.window, causal=opt.causal)
+        np.savez(os.path.join(args.output_path, sequence + "_topk.npz"), frame=np.arange(m),
+                 indices=idx.cpu().numpy(), scores=vals.cpu().numpy(), recall=recall)
+        print("sequence", sequence, "frames", m, "recall@1..%d" % opt.k, " ".join("%.4f" % r for r in recall))
+        results[sequence] = recall
+    return results
+
+
+if __name__ == "__main__":
+    main()

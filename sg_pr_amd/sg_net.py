@@ -146,6 +146,12 @@ class SG(torch.nn.Module):
     def score_all_pairs(self, pooled_rows, pooled_cols, out=None):
         return self.engine().score_all_pairs(pooled_rows, pooled_cols, out=out)
 
+    def loop_closures(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None):
+        """The k best columns per row of pooled_rows x pooled_cols without forming the matrix (engine.Engine.score_topk)
+        -> (values f32 [R,k], indices i32 [R,k]) on the device."""
+        return self.engine().score_topk(pooled_rows, pooled_cols, k=k, window=window, row0=row0, causal=causal,
+                                        row_self=row_self)
+
     def forward_packed(self, centers_1, labels_1, centers_2, labels_2, validate=True):
         """Faithful per-pair scoring of packed graphs: both sides embedded, then the tail.
         validate (default): synchronise and raise SgprError if the kernel saw a label outside [-1, L) (the reference
