@@ -207,7 +207,10 @@ int sgpr_score_pairs(const sgpr_handle* h, const float* d_pooled1, const int32_t
  * (eval_batch.py:30-36 walks `<seq>.txt`, utils.py:61-70: 10^4 - 10^5 listed pairs over 10^3 graphs, ~15 per row graph).
  * sgpr_score_pairs spends a whole wave and a 64 KB weight read on every pair; here the bilinear form is hoisted per
  * DISTINCT row graph and the listed columns of a row go through the matrix cores 16 at a time, exactly like a row of
- * the dense rectangle: the scores are bit-identical to sgpr_score_all_pairs' entries at the listed (row, column).
+ * the dense rectangle: on an f16 handle the scores are bit-identical to sgpr_score_all_pairs' entries at the listed
+ * (row, column).  A handle whose tail runs at fp32's range (weights or scoring head outside the f16 range, debug bit 13)
+ * scores the list with the kernel's exact fp32 per-pair arithmetic - sgpr_score_pairs' values to rounding, not the bits
+ * of its three-plane matrix.
  *
  * sgpr_pair_plan (HOST memory in and out, no GPU work): groups pair p = (idx1[p], idx2[p]), 0 <= idx1 < R, 0 <= idx2 < M,
  * P < 2^31, by row graph (stable: a row's pairs keep their list order) and cuts every row's pairs into work items of

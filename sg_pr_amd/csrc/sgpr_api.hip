@@ -266,6 +266,13 @@ static int build_generic_model(const float* weights, const sgpr_dims* d, sgpr_ha
     m.fc1_b = q;    q += bn;
     m.fc2_w = q;    q += bn;
     m.fc2_b = q;
+    {
+        const float* fc1 = host.data() + off_tail + (f * f + f * f * t + t * 2 * f + t);   // (the host copy of m.fc1_w ...)
+        const HeadRange hr = head_range(fc1, fc1 + bn * t + bn, (int)bn, (int)t);         // (... and of m.fc2_w)
+        m.head_scale = hr.scale;
+        m.head_nl2e = hr.nl2e;
+        m.head_f16 = hr.f16_ok;
+    }
     // ---- the matrix-core form of the same folded weights (WideModel, sgpr_wide.hip) for moderately larger architectures:
     //      widths padded to 32 with zeros, two f16 planes (w = hi + lo, 22 bits) in MFMA operand order.  Only for an
     //      any-shape handle (the built shape runs on the tuned kernels) inside the limits and the f16 range.
@@ -589,6 +596,12 @@ int sgpr_create(const float* weights, size_t n_floats, const sgpr_dims* dims, in
     h->w.fc1_b = h->d_blob + o_fc1b;
     h->w.fc2_w = h->d_blob + o_fc2w;
     h->w.fc2_b = h->d_blob + o_fc2b;
+    {
+        const HeadRange hr = head_range(packed.data() + o_fc1w, packed.data() + o_fc2w, (int)bn, (int)t);
+        h->w.head_scale = hr.scale;
+        h->w.head_nl2e = hr.nl2e;
+        h->head_f16 = hr.f16_ok;
+    }
     h->w.sem_g = h->w.sem_xx = h->w.sem_a2 = h->w.sem_b2 = nullptr;
     if (f16_ok) {
         // the graph-independent part of the super-node branch, by the kernels' own instructions (bit-identical to the
@@ -652,6 +665,9 @@ static constexpr int kProductionSkipBits = 8192 | (1 << 20);
 #define SGPR_AUTO_LEAN 1      // 0 (A/B builds): a launch without a node_cap promise is sized for node_num
 #endif
 static bool wide_range(const sgpr_handle* h) { return !h->f16_weights || (h->dbg_skip & 8192); }
+// the tails of the built shape at fp32's range: a wide-range handle, or a scoring head whose fold leaves the f16 range
+// (head_range: the embed keeps its f16 planes then)
+static bool tail_wide(const sgpr_handle* h) { return wide_range(h) || !h->head_f16; }
 
 static int check_nk(int G, int N, int k, int node_cap, EmbedPlan* plan, bool wide, bool small_park = false) {
     if (G < 0) {
@@ -1086,8 +1102,10 @@ int sgpr_score_pair_list(const sgpr_handle* h, const float* d_pooled_rows, int R
         return SGPR_E_WORKSPACE;
     }
     DeviceGuard guard(h->device);
+    // (a wide-range tail: the kernel's exact fp32 per-pair arithmetic - the f16 planes are not this handle's, and there is
+    //  no three-plane instance of the list kernel)
     return launch_score_pair_list(h, d_pooled_rows, d_pooled_cols, M, d_plan, n_rows, n_items, P, d_score, d_workspace,
-                                  static_cast<hipStream_t>(stream));
+                                  static_cast<hipStream_t>(stream), tail_wide(h));
 }
 
 size_t sgpr_score_all_pairs_workspace_bytes(const sgpr_handle* h, int R, int M) {
@@ -1128,9 +1146,9 @@ int sgpr_score_all_pairs(const sgpr_handle* h, const float* d_pooled_rows, int R
         return SGPR_E_WORKSPACE;
     }
     DeviceGuard guard(h->device);
-    // (debug bit 13 / weights outside the f16 range: the instance with three bf16 planes per operand, as for the embed)
+    // (debug bit 13 / weights or head outside the f16 range: the instance with three bf16 planes per operand, as for the embed)
     return launch_score_all_pairs(h, d_pooled_rows, R, d_pooled_cols, M, d_score, ld, d_workspace,
-                                  static_cast<hipStream_t>(stream), wide_range(h));
+                                  static_cast<hipStream_t>(stream), tail_wide(h));
 }
 
 static int check_jobs(const sgpr_handle* h, int n, const sgpr_pairs_job* jobs) {
@@ -1153,7 +1171,7 @@ static int check_jobs(const sgpr_handle* h, int n, const sgpr_pairs_job* jobs) {
 //      own tail into the workspace and select from each block (the same selection, bit-equal to matrix + top-k)
 static const size_t kTopkBlockBytes = (size_t)64 << 20;    // score block of the chunked path
 
-static bool topk_fused(const sgpr_handle* h) { return !h->generic_only && !wide_range(h); }
+static bool topk_fused(const sgpr_handle* h) { return !h->generic_only && !tail_wide(h); }
 
 static int topk_block_rows(int R, int M) {
     const size_t rows = kTopkBlockBytes / ((size_t)M * sizeof(float));
@@ -1243,6 +1261,17 @@ int sgpr_score_all_pairs_multi(const sgpr_handle* h, int n_jobs, const sgpr_pair
         return SGPR_E_WORKSPACE;
     }
     DeviceGuard guard(h->device);
+    if (tail_wide(h)) {             // the three-plane instance has no multi-rectangle form: job by job, in stream order,
+        unsigned char* ws = static_cast<unsigned char*>(d_workspace);    // each in its slice of the workspace - the bits
+        for (int j = 0; j < n_jobs && rc == SGPR_OK; ++j) {              // of sgpr_score_all_pairs on every rectangle
+            const sgpr_pairs_job& q = jobs[j];
+            if (q.R == 0 || q.M == 0) continue;
+            rc = launch_score_all_pairs(h, q.d_pooled_rows, q.R, q.d_pooled_cols, q.M, q.d_score, q.ld, ws,
+                                        static_cast<hipStream_t>(stream), true);
+            ws += (score_all_pairs_ws_bytes(q.R, q.M) + 255) & ~(size_t)255;
+        }
+        return rc;
+    }
     return launch_score_all_pairs_multi(h, n_jobs, jobs, d_workspace, static_cast<hipStream_t>(stream));
 }
 

@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libsgpr_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <atomic>
 #include <string>
@@ -21,6 +22,35 @@ constexpr int kKPad = 16;  // layer-1 inputs (3 / 12 channels) are zero-padded t
 //     wf[l] : [2*cout][kp] row-major.  rows [0,cout)      = s * W[:, :C]          (acts on x_j)
 //                                      rows [cout,2cout)  = s * (W[:, C:] - W[:, :C])  (acts on x_i)
 //     tb[l] : [cout] = beta - mean * s,  s = gamma / sqrt(var + 1e-5)   (eval BatchNorm folded)
+// The scoring head's fold v[o][t] = fc2_w[o] fc1_w[o][t] (fp32, as every tail forms it) is cut into two f16 planes by
+// the matrix-core tails.  A plane pair keeps 22 significant bits only where the low plane is normal (|v| >= 2^-3); below
+// that the low plane's step is a fixed 2^-24.  The tails therefore cut 2^k v, k >= 0 the largest power that keeps
+// max |2^k v| below 2^15 (k <= 64), scale b1 by the same factor and undo it in the sigmoid's constant: exp2(z' (-log2 e
+// 2^-k) + ...) with z' = 2^k z is the unscaled product exactly.  f16_ok = 0: max |v| reaches 60000, no f16 plane can hold
+// the fold and the handle's tails run at fp32's range (the bf16 instance / the plain-fp32 kernel).
+struct HeadRange {
+    float scale, nl2e;
+    int f16_ok;
+};
+inline HeadRange head_range(const float* fc1_w, const float* fc2_w, int B, int T) {
+    float vmax = 0.f;
+    bool finite = true;
+    for (int o = 0; o < B; ++o)
+        for (int t = 0; t < T; ++t) {
+            const float v = fabsf(fc2_w[o] * fc1_w[(size_t)o * T + t]);
+            if (!(v <= 3.0e38f)) finite = false;
+            vmax = v > vmax ? v : vmax;
+        }
+    HeadRange r;
+    r.f16_ok = finite && vmax < 60000.f;
+    int k = 0;
+    if (r.f16_ok && vmax > 0.f)
+        while (k < 64 && ldexpf(vmax, k + 1) < 32768.f) ++k;
+    r.scale = ldexpf(1.f, k);
+    r.nl2e = ldexpf(-1.4426950408889634f, -k);
+    return r;
+}
+
 struct DevWeights {
     const float* wf[6];             // folded fp32 weights [2*cout][kp] (a rows, then b rows); host-side source of wb
     // the same weights as three bf16 planes (w = hi + mid + lo, exact to 24 bits) in MFMA operand order:
@@ -45,6 +75,8 @@ struct DevWeights {
     const float* fc1_b;   // [16]
     const float* fc2_w;   // [16]
     const float* fc2_b;   // [1]
+    float head_scale;     // 2^k of the scoring head's f16 planes and -log2(e) 2^-k (head_range)
+    float head_nl2e;
     // Semantic branch on label super-nodes, what does not depend on the graph (sgpr_embed.hip, sem_table_kernel; filled on
     // the device at sgpr_create by the instructions of the per-graph path; NULL: the per-graph path computes it).  A label
     // row of layer 1 has two versions - "fewer than K nodes carry the label" (bit 1: the padding representative is among
@@ -82,6 +114,8 @@ struct GenericModel {
     const float* fc1_b;                 // [B]
     const float* fc2_w;                 // [B]
     const float* fc2_b;                 // [1]
+    float head_scale, head_nl2e;        // head_range of fc1_w / fc2_w (the matrix-core tail, sgpr_wide.hip)
+    int head_f16;                       // ... and whether its fold fits the f16 range
 };
 
 // Matrix-core form of a GenericModel for MODERATELY larger architectures (sgpr_wide.hip): labels <= 32, filters_1 / 2 <= 128,
@@ -116,6 +150,7 @@ struct sgpr_handle {
     int dbg_skip;
     unsigned long long* dbg_prof;
     int f16_weights;     // every folded weight fits the f16 range (else the wide-range layouts are used throughout)
+    int head_f16;        // the scoring head's fold fits the f16 range (else the tails take the wide-range instance)
     int generic_only;    // the architecture is larger than the built shape: every call runs on the any-shape kernels
     float* d_gblob;      // owns the any-shape model's weights
     sgpr::GenericModel gm;
@@ -220,7 +255,7 @@ int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int
                          int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
 size_t score_pair_list_ws_bytes(int NR, int M);
 int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float* cols, int M, const int32_t* plan,
-                           int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream);
+                           int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream, bool exact = false);
 int generic_embed_slots(const sgpr_handle* h, int G);
 size_t generic_embed_ws_bytes(const sgpr_handle* h, int G, int N, int k);   // 0: the working memory fits LDS
 size_t generic_embed_lds_bytes(const sgpr_handle* h, int N, int k);

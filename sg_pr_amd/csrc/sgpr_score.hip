@@ -530,16 +530,18 @@ __device__ __forceinline__ void slow_tile(const DevWeights& w, const float* __re
 struct ApConsts {
     f16x8 w1hi, w1lo;
     float4 b1v, side;
-    float nb2;
+    float nb2, nl2e;
 };
 
 // The head's weight w2[o] is folded into layer 2 (row o of W1 and b1[o] scaled by it - in fp32, before the planes are
 // cut), so that the accumulator holds q''[o] = w2[o] (b1[o] + W1[o].H) and the pair's term w2[o] relu(q[o]) is q''[o]
 // clamped to its own side of zero: max(q'', 0) for w2 > 0, min(q'', 0) for w2 < 0 = ONE v_med3_f32 against
 // (0, side[o]), side = +inf / -inf - instead of an integer maximum and a multiply-add per value.
+// Both are also scaled by the handle's power of two head_scale (head_range, sgpr_internal.hpp: the largest fold weight
+// in [2^14, 2^15), so that no low plane is an f16 subnormal), undone exactly in the sigmoid's constant nl2e.
 __device__ __forceinline__ ApConsts ap_consts(const DevWeights& w, int l15, int g) {
     ApConsts c;
-    const float s = w.fc2_w[l15];                                                      // the A operand's row is o = l15
+    const float s = w.fc2_w[l15] * w.head_scale;                                       // the A operand's row is o = l15
     float4 w1v = *reinterpret_cast<const float4*>(w.fc1_w + l15 * T + 4 * g);         // W1[o = l15][t = 4g..4g+3]
     w1v = make_float4(s * w1v.x, s * w1v.y, s * w1v.z, s * w1v.w);
     const _Float16 wh0 = (_Float16)w1v.x, wh1 = (_Float16)w1v.y, wh2 = (_Float16)w1v.z, wh3 = (_Float16)w1v.w;
@@ -549,10 +551,12 @@ __device__ __forceinline__ ApConsts ap_consts(const DevWeights& w, int l15, int 
                         (_Float16)(w1v.w - (float)wh3), z16, z16, z16, z16};            // meets the hi plane only
     const float4 b1 = *reinterpret_cast<const float4*>(w.fc1_b + 4 * g);              // the accumulator's rows are o = 4g + r
     const float4 w2 = *reinterpret_cast<const float4*>(w.fc2_w + 4 * g);
-    c.b1v = make_float4(w2.x * b1.x, w2.y * b1.y, w2.z * b1.z, w2.w * b1.w);
+    const float hs = w.head_scale;
+    c.b1v = make_float4((w2.x * hs) * b1.x, (w2.y * hs) * b1.y, (w2.z * hs) * b1.z, (w2.w * hs) * b1.w);
     c.side = make_float4(w2.x < 0.f ? -INFINITY : INFINITY, w2.y < 0.f ? -INFINITY : INFINITY,
                          w2.z < 0.f ? -INFINITY : INFINITY, w2.w < 0.f ? -INFINITY : INFINITY);
     c.nb2 = -w.fc2_b[0] * 1.4426950408889634f;
+    c.nl2e = w.head_nl2e;                                 // -log2(e) / head_scale: fmaf(2^k z, nl2e, nb2) = fmaf(z, -log2 e, nb2)
     return c;
 }
 
@@ -743,7 +747,7 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
     const int l15 = lane & 15, g = lane >> 4;
     const f16x8 w1hi = k.w1hi, w1lo = k.w1lo;
     const float4 b1v = k.b1v, side = k.side;
-    const float kL2E = 1.4426950408889634f;
+    const float nl2e = k.nl2e;
     const float nb2 = k.nb2;
     const int ncc = (M + AP_COLS - 1) / AP_COLS;
     f16x8 ah[AP_RW], al[AP_RW];
@@ -807,7 +811,11 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                     for (int rr = 0; rr < AP_RW && rbase + rr < R; ++rr)
 #pragma unroll 1
                         for (int cl = 0; cl < AP_SB && sb * AP_SB + cl < M; ++cl) {
-                            const float v = slow_pair(w, prow + (size_t)(rbase + rr) * F, pcol + (size_t)(sb * AP_SB + cl) * F);
+                            // (lane 0's value - the one slow_tile stores -, read into a scalar register: with
+                            //  contracted multiply-adds in its shuffle reductions slow_pair's lanes need not agree to
+                            //  the last bit; every lane is active here, the loop bounds are wave-uniform)
+                            const float v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(
+                                slow_pair(w, prow + (size_t)(rbase + rr) * F, pcol + (size_t)(sb * AP_SB + cl) * F))));
                             if (rr == g && (cl >> 2) == l15) {
 #pragma unroll
                                 for (int b = 0; b < 4; ++b) sc[b] = (cl & 3) == b ? v : sc[b];
@@ -905,7 +913,7 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                 const float p13 = swap32_add(zb[b][1], zb[b][3]);    // likewise rows 1 / 3
                 const float zsel = swap16_add(p02, p13);             // even 16-lane rows: row 0 / 2, odd: row 1 / 3
                 // sigmoid: v_exp_f32 / v_rcp_f32 (1 ulp each) - far inside the 1e-4 score tolerance
-                sc[b] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(zsel, -kL2E, nb2)));
+                sc[b] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(zsel, nl2e, nb2)));
             }
             const int r = rbase + g, c0 = sb * AP_SB + 4 * l15;
             if constexpr (TK > 0) {
@@ -1452,7 +1460,7 @@ __device__ __forceinline__ void pl_items(const DevWeights& w, const ApConsts& k,
     const int lane = threadIdx.x & 63, l15 = lane & 15, g = lane >> 4;
     const f16x8 w1hi = k.w1hi, w1lo = k.w1lo;
     const float4 b1v = k.b1v, side = k.side;
-    const float kL2E = 1.4426950408889634f;
+    const float nl2e = k.nl2e;
     const float nb2 = k.nb2;
     const int nquad = (pl.NI + 3) >> 2;
     const int wave0 = (int)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int)gridDim.x * 4;
@@ -1505,7 +1513,7 @@ __device__ __forceinline__ void pl_items(const DevWeights& w, const ApConsts& k,
         const float p02 = swap32_add(zb[0], zb[2]);
         const float p13 = swap32_add(zb[1], zb[3]);
         const float zsel = swap16_add(p02, p13);             // lane group g: item g of the quad, its pair l15
-        const float sc = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(zsel, -kL2E, nb2)));
+        const float sc = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(zsel, nl2e, nb2)));
         if (l15 < my_cnt) score[pl.pos[my_beg + l15]] = sc;
     }
 }
@@ -1517,11 +1525,11 @@ __global__ __launch_bounds__(256) void score_pair_list_kernel(const DevWeights w
                                                               const float* __restrict__ rng, int nrng,
                                                               const float* __restrict__ prow,
                                                               const float* __restrict__ pcol,
-                                                              float* __restrict__ score) {
+                                                              float* __restrict__ score, const int exact) {
     const int lane = threadIdx.x & 63;
     float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
     ap_range(rng, nrng, am, um, em, l1);
-    const int mode = ap_mode(am, um, em, l1);
+    const int mode = exact ? 0 : ap_mode(am, um, em, l1);
     const ApConsts k = ap_consts(w, lane & 15, lane >> 4);
     if (mode == 2)
         pl_items<true>(w, k, true, pl, Ab, Cg, ur, prow, pcol, score);
@@ -1530,7 +1538,7 @@ __global__ __launch_bounds__(256) void score_pair_list_kernel(const DevWeights w
 }
 
 int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float* cols, int M, const int32_t* plan,
-                           int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream) {
+                           int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream, bool exact) {
     if (P == 0 || NI == 0) return SGPR_OK;
     PairPlan pl;
     pl.row_ids = plan;
@@ -1553,7 +1561,7 @@ int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float*
     const int64_t slots = (int64_t)h->num_cus * 8;
     const unsigned grid = (unsigned)(wgs < slots ? wgs : slots);
     hipLaunchKernelGGL(score_pair_list_kernel, dim3(grid), dim3(256), 0, stream, h->w, pl, Ab, Cg, ur, rng, nrng, rows, cols,
-                       score);
+                       score, exact ? 1 : 0);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_pair_list_kernel launch");
     return SGPR_OK;

@@ -796,13 +796,14 @@ __global__ __launch_bounds__(256) void wide_tail_kernel(const GenericModel m, co
     }
     const int lane = threadIdx.x & 63, l15 = lane & 15, g = lane >> 4;
     const int T = m.T, B = m.B;
-    // the head folded into layer 2 (sgpr_score.hip, ap_consts), per (o tile, t tile)
+    // the head folded into layer 2 and scaled by head_scale (sgpr_score.hip, ap_consts), per (o tile, t tile)
     f16x8 w1hi[2][2], w1lo[2][2];
     f32x4 b1v[2], side[2];
+    const float hs = m.head_scale;
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot) {
         const int o = 16 * ot + l15;                         // the A operand's row
-        const float s = o < B ? m.fc2_w[o] : 0.f;
+        const float s = o < B ? m.fc2_w[o] * hs : 0.f;
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             float w[4];
@@ -820,12 +821,12 @@ __global__ __launch_bounds__(256) void wide_tail_kernel(const GenericModel m, co
         for (int r = 0; r < 4; ++r) {                        // the accumulator's rows are o = 16 ot + 4 g + r
             const int oo = 16 * ot + 4 * g + r;
             const float w2 = oo < B ? m.fc2_w[oo] : 0.f;
-            b1v[ot][r] = oo < B ? w2 * m.fc1_b[oo] : 0.f;
+            b1v[ot][r] = oo < B ? (w2 * hs) * m.fc1_b[oo] : 0.f;
             side[ot][r] = w2 < 0.f ? -INFINITY : INFINITY;
         }
     }
-    const float kL2E = 1.4426950408889634f;
-    const float nb2 = -m.fc2_b[0] * kL2E;
+    const float nl2e = m.head_nl2e;                         // -log2(e) / head_scale
+    const float nb2 = -m.fc2_b[0] * 1.4426950408889634f;
     const int nblk = (M + 15) >> 4, nch = (nblk + 15) >> 4;  // 16-column blocks; chunks of 16 blocks
     const long long items = (long long)R * nch;
     const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (long long)gridDim.x * 4;
@@ -882,7 +883,7 @@ __global__ __launch_bounds__(256) void wide_tail_kernel(const GenericModel m, co
             }
             z += __shfl_xor(z, 16);
             z += __shfl_xor(z, 32);
-            const float sc = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(z, -kL2E, nb2)));
+            const float sc = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(z, nl2e, nb2)));
             const int c = 16 * blk + l15;
             if (g == 0 && c < M) score[(size_t)r * ld + c] = sc;
         }
@@ -896,8 +897,10 @@ size_t wide_tail_ws(int R, int M) {
 
 }  // namespace
 
+// (a head whose fold leaves the f16 range, head_range: the plain-fp32 kernel, like the rectangles whose inputs do)
 bool wide_tail_serves(const sgpr_handle* h) {
-    return h->generic_only && h->wm.ok && h->gm.f3 <= TFP && h->gm.T <= TTP && h->gm.B <= TBP && !(h->dbg_skip & (1 << 23));
+    return h->generic_only && h->wm.ok && h->gm.f3 <= TFP && h->gm.T <= TTP && h->gm.B <= TBP && h->gm.head_f16 &&
+           !(h->dbg_skip & (1 << 23));
 }
 size_t wide_tail_ws_bytes(int R, int M) { return wide_tail_ws(R, M); }
 

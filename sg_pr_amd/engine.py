@@ -604,7 +604,9 @@ class Engine:
     def score_pair_list(self, pooled_rows, pooled_cols, plan, out=None):
         """score[p] = SG-tail(pooled_rows[idx1[p]], pooled_cols[idx2[p]]) for the pairs of `plan` (sgpr_score_pair_list):
         the bilinear form hoisted per distinct row graph, a row's listed columns through the matrix cores 16 at a time;
-        bit-identical to score_all_pairs' entries at the listed indices."""
+        on an f16 handle bit-identical to score_all_pairs' entries at the listed indices (a handle whose tail runs at fp32's
+        range - weights or scoring head outside the f16 range, debug bit 13 - scores the list in exact fp32: score_pairs'
+        values to rounding)."""
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
         if rows.shape[0] != plan.num_rows or cols.shape[0] != plan.num_cols:
