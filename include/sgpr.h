@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPR_ABI_VERSION 9
+#define SGPR_ABI_VERSION 10
 
 enum {
     SGPR_OK = 0,
@@ -347,6 +347,44 @@ size_t sgpr_score_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int k
 int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
                     const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
                     int32_t* d_indices, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Range retrieval without the R x M matrix: every eligible pair (r, c) of the rectangle d_pooled_rows [R] x
+ * d_pooled_cols [M] whose score is >= threshold.
+ * - Eligibility is sgpr_score_topk's: |c - self_r| > window (window < 0: no window) and, with SGPR_TOPK_CAUSAL in flags,
+ *   c < self_r, where self_r = d_row_self[r] (device, [R], each in [0, M): sgpr_check_status reports an entry outside)
+ *   or, with d_row_self NULL, row0 + r.  A NaN score never qualifies; threshold = -inf takes every non-NaN eligible pair.
+ * - Every value is bit-identical to sgpr_score_all_pairs' entry (r, c) on the same rectangle and handle (every handle
+ *   kind, both sides of the f16 range guard).
+ * - Order: row-major (r ascending, then c ascending), independent of grid, occupancy and timing: two calls return
+ *   identical bytes.
+ * - *d_count (device, 64-bit) receives the exact number of qualifying pairs; d_row_ptr (device [R + 1] int64, may be
+ *   NULL) its CSR row pointer: row_ptr[0] = 0, row_ptr[R] = count.  Only the first min(count, capacity) pairs in that
+ *   order are written to d_rows / d_cols (int32) and d_values (f32), device [capacity].  capacity = 0 with NULL arrays
+ *   counts only.  M = 0 gives count 0 and an all-zero row_ptr.  Positions are 64-bit: R * M may exceed 2^31.
+ * - Checked before the device is touched (SGPR_E_INVALID): a NULL handle, d_count or pooled vector (R, M > 0), a negative
+ *   count or capacity, capacity > 0 with a NULL output array, unknown flag bits, a NaN threshold, row0 + R beyond an
+ *   int.  A workspace below sgpr_score_above_workspace_bytes is SGPR_E_WORKSPACE.
+ * - The production handle runs two passes of one fused instance of the all-pairs tail (count, then write the flagged
+ *   work items) around a small fold + scan; its workspace grows with R + M and the grid, never with R * M (the operands,
+ *   O(R) counters and row pointers, O(grid) partial counts, one byte per 16 x 256 work item).  Wide-range and any-shape
+ *   handles score row blocks of at most 64 MB with their own tail and select from each with sgpr_rows_above's kernels,
+ *   positions continuing on the device.  Asynchronous on `stream`, no host synchronisation inside. */
+size_t sgpr_score_above_workspace_bytes(const sgpr_handle* h, int R, int M, int flags);
+int sgpr_score_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                     const int32_t* d_row_self, int row0, int window, int flags, float threshold,
+                     int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity,
+                     int64_t* d_row_ptr, unsigned long long* d_count,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* sgpr_score_above's selection, contract and checks on a resident matrix d_score [R][ld] (ld >= M; NULL with R or M
+ * zero): the same pairs, order and counts (a NULL d_score with R, M > 0 or ld < M is SGPR_E_INVALID).  Workspace
+ * O(R). */
+size_t sgpr_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M);
+int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld,
+                    const int32_t* d_row_self, int row0, int window, int flags, float threshold,
+                    int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity,
+                    int64_t* d_row_ptr, unsigned long long* d_count,
+                    void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* LDS bytes per workgroup the embed kernel uses for (N, k) on this handle; 0 if unsupported. */
 size_t sgpr_embed_lds_bytes(const sgpr_handle* h, int N, int k);

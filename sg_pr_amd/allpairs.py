@@ -180,12 +180,13 @@ class AllPairsScorer:
     With an `sg_net.SG` model the two callables are its HIP paths; tests inject CPU
     stand-ins to exercise the sharding / collective logic under gloo."""
 
-    def __init__(self, model=None, embed_fn=None, score_fn=None, group=None, topk_fn=None):
+    def __init__(self, model=None, embed_fn=None, score_fn=None, group=None, topk_fn=None, above_fn=None):
         self._engine = None
         if model is not None:
             embed_fn = lambda c, l: model.embed(c, l)[0]   # noqa: E731
             score_fn = model.score_all_pairs
             topk_fn = topk_fn or model.loop_closures
+            above_fn = above_fn or model.loop_closures_above
             self._engine = model.engine()
 
         if embed_fn is None or score_fn is None:
@@ -194,6 +195,9 @@ class AllPairsScorer:
         self.score_fn = score_fn
         # topk_fn(rows, cols, k=, window=, row0=, causal=) -> (values [R,k], indices [R,k]): model.loop_closures
         self.topk_fn = topk_fn
+        # above_fn(rows, cols, threshold, window=, row0=, causal=) -> (rows i32 [n], cols i32 [n], values f32 [n],
+        # row_ptr i64 [R+1]): model.loop_closures_above
+        self.above_fn = above_fn
         self.group = group
 
     def _world(self):
@@ -338,6 +342,26 @@ class AllPairsScorer:
         both = torch.cat((vals.view(torch.int32), idx), dim=1)       # one collective for both halves (bit copies)
         both = all_gather_rows(both, m, self.group)
         return both[:, :k].contiguous().view(torch.float32), both[:, k:].contiguous()
+
+    def above(self, centers, labels, threshold, window=50, causal=False, local_pooled=None):
+        """Every pair of the whole set scoring >= threshold, without any score matrix: every rank embeds its shard, the
+        pooled vectors are all-gathered (pooled_all), each rank selects over its rows [lo, hi) (row0 = lo), one
+        all_gather_varlen hands every rank all pairs (rank order is row order: the global row-major list) and one
+        all_gather_rows the per-row counts -> (rows i32 [n], cols i32 [n], values f32 [n], row_ptr i64 [M+1])."""
+        if self.above_fn is None:
+            raise ValueError("AllPairsScorer.above needs a model or an above_fn")
+        pooled = self.pooled_all(centers, labels, local=local_pooled)
+        world, rank = self._world()
+        m = pooled.shape[0]
+        lo, hi = shard_bounds(m, world, rank)
+        rows, cols, vals, row_ptr = self.above_fn(pooled[lo:hi].contiguous(), pooled, threshold, window=window,
+                                                  row0=lo, causal=causal)
+        trip = torch.stack((rows + lo, cols, vals.view(torch.int32)), dim=1)   # one collective for all three (bit copies)
+        trip = all_gather_varlen(trip.reshape(-1), self.group)[0].view(-1, 3)
+        counts = all_gather_rows((row_ptr[1:] - row_ptr[:-1]).view(-1, 1), m, self.group).view(-1)
+        rp = torch.zeros(m + 1, dtype=torch.int64, device=counts.device)
+        rp[1:] = torch.cumsum(counts, 0)
+        return trip[:, 0].contiguous(), trip[:, 1].contiguous(), trip[:, 2].contiguous().view(torch.float32), rp
 
     def run(self, centers, labels, gather=True, out=None, chunks=4, local_pooled=None):
         """Whole job: returns the [M, M] matrix on rank 0 (row block elsewhere / if gather=False).

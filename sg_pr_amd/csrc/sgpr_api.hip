@@ -1234,6 +1234,110 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
     return SGPR_OK;
 }
 
+// ---- sgpr_score_above / sgpr_rows_above: the fused two-pass kernel on the production handle; the other handles score
+//      bounded row blocks with their own tail and select from each block, positions continuing on the device
+static bool above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int row0, int flags, float threshold,
+                          int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity, unsigned long long* d_count) {
+    if (!h || R < 0 || M < 0 || capacity < 0 || !d_count || (capacity > 0 && (!d_rows || !d_cols || !d_values))) {
+        set_error(std::string(fn) + ": NULL argument, negative count or negative capacity");
+        return false;
+    }
+    if (flags & ~SGPR_TOPK_CAUSAL) {
+        set_error(std::string(fn) + ": unknown flag bits " + std::to_string(flags & ~SGPR_TOPK_CAUSAL));
+        return false;
+    }
+    if (threshold != threshold) {
+        set_error(std::string(fn) + ": the threshold is NaN");
+        return false;
+    }
+    if ((int64_t)row0 + R > 0x7fffffffLL) {
+        set_error(std::string(fn) + ": row0 + R must fit an int");
+        return false;
+    }
+    return true;
+}
+
+// chunked path layout: score block [rb][M] | cnt [rb] i32 | row_ptr [R + 1] i64 | the block's all-pairs workspace
+static size_t above_chunk_head(int R, int M) {
+    const int rb = topk_block_rows(R, M);
+    return a256((size_t)rb * M * sizeof(float)) + a256((size_t)rb * 4) + a256((size_t)(R + 1) * 8);
+}
+
+size_t sgpr_score_above_workspace_bytes(const sgpr_handle* h, int R, int M, int flags) {
+    if (!h || R < 0 || M < 0 || (flags & ~SGPR_TOPK_CAUSAL)) return 0;
+    if (R == 0 || M == 0) return 0;
+    if (topk_fused(h)) return score_above_ws_bytes(h, R, M);
+    return above_chunk_head(R, M) + sgpr_score_all_pairs_workspace_bytes(h, topk_block_rows(R, M), M);
+}
+
+int sgpr_score_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                     const int32_t* d_row_self, int row0, int window, int flags, float threshold, int32_t* d_rows,
+                     int32_t* d_cols, float* d_values, int64_t capacity, int64_t* d_row_ptr, unsigned long long* d_count,
+                     void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!above_args_ok("sgpr_score_above", h, R, M, row0, flags, threshold, d_rows, d_cols, d_values, capacity, d_count))
+        return SGPR_E_INVALID;
+    if (R > 0 && M > 0 && (!d_pooled_rows || !d_pooled_cols)) {
+        set_error("sgpr_score_above: NULL pooled vectors");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = sgpr_score_above_workspace_bytes(h, R, M, flags);
+    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
+        set_error("sgpr_score_above: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R == 0 || M == 0 || topk_fused(h))
+        return launch_score_above(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, threshold,
+                                  d_rows, d_cols, d_values, capacity, d_row_ptr, d_count, d_workspace, s);
+    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
+    unsigned char* base = static_cast<unsigned char*>(d_workspace);
+    float* block = reinterpret_cast<float*>(base);
+    unsigned char* cnt = base + a256((size_t)rb * M * sizeof(float));
+    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(cnt + a256((size_t)rb * 4));
+    unsigned char* ws = base + above_chunk_head(R, M);
+    const size_t ws_bytes = workspace_bytes - above_chunk_head(R, M);
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = std::min(rb, R - r0);
+        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
+        if (rc != SGPR_OK) return rc;
+        rc = launch_rows_above(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, threshold,
+                               d_rows, d_cols, d_values, capacity, rp + r0, r0, d_count, r0 > 0, cnt, h->d_status, s);
+        if (rc != SGPR_OK) return rc;
+    }
+    return SGPR_OK;
+}
+
+size_t sgpr_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M) {
+    if (!h || R < 0 || M < 0 || R == 0 || M == 0) return 0;
+    return rows_above_ws_bytes(R);
+}
+
+int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, const int32_t* d_row_self,
+                    int row0, int window, int flags, float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values,
+                    int64_t capacity, int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace,
+                    size_t workspace_bytes, void* stream) {
+    if (!above_args_ok("sgpr_rows_above", h, R, M, row0, flags, threshold, d_rows, d_cols, d_values, capacity, d_count))
+        return SGPR_E_INVALID;
+    if (ld < M || (R > 0 && M > 0 && !d_score)) {
+        set_error("sgpr_rows_above: NULL score or ld < M");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = sgpr_rows_above_workspace_bytes(h, R, M);
+    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
+        set_error("sgpr_rows_above: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R == 0 || M == 0) return launch_above_empty(R, d_row_ptr, d_count, s);
+    unsigned char* cnt = static_cast<unsigned char*>(d_workspace);
+    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(cnt + a256((size_t)R * 4));
+    return launch_rows_above(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, threshold,
+                             d_rows, d_cols, d_values, capacity, rp, 0, d_count, 0, cnt, h->d_status, s);
+}
+
 size_t sgpr_score_all_pairs_multi_workspace_bytes(const sgpr_handle* h, int n_jobs, const sgpr_pairs_job* jobs) {
     if (check_jobs(h, n_jobs, jobs) != SGPR_OK) return 0;
     size_t any = 0;
@@ -1526,8 +1630,13 @@ int sgpr_check_status(const sgpr_handle* h, void* stream) {
         e = hipMemsetAsync(h->d_status, 0, sizeof(flag), s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(e, "sgpr_check_status: reset");
+        if (flag & 32) {
+            set_error("internal: the second pass of sgpr_score_above / sgpr_rows_above wrote a different number of pairs "
+                      "than its first pass counted");
+            return SGPR_E_HIP;
+        }
         if (flag & 16) {
-            set_error("a d_row_self entry of sgpr_score_topk lies outside [0, M)");
+            set_error("a d_row_self entry of sgpr_score_topk / sgpr_score_above lies outside [0, M)");
             return SGPR_E_INVALID;
         }
         if (flag & 4) {

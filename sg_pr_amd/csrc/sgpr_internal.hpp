@@ -253,6 +253,17 @@ int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const floa
 // sgpr_topk_rows' selection with a row_self table, the causal rule and an output row stride of k (sgpr_metrics.hip)
 int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
                          int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
+size_t score_above_ws_bytes(const sgpr_handle* h, int R, int M);
+size_t rows_above_ws_bytes(int R);
+int launch_above_empty(int R, int64_t* row_ptr, unsigned long long* count, hipStream_t stream);
+int launch_score_above(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
+                       int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
+                       int64_t cap, int64_t* row_ptr, unsigned long long* count, void* ws, hipStream_t stream);
+// the range selection of a resident R x M block (sgpr_rows_above, the chunked path of sgpr_score_above): row_ptr [R + 1]
+// of the block's rows, output rows rout0 + r; accumulate: positions continue from *count
+int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                      int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals, int64_t cap, int64_t* row_ptr,
+                      int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status, hipStream_t stream);
 size_t score_pair_list_ws_bytes(int NR, int M);
 int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float* cols, int M, const int32_t* plan,
                            int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream, bool exact = false);

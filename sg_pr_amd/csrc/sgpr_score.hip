@@ -735,14 +735,119 @@ __device__ __forceinline__ void tk_flush(const TopkArgs& a, int rg, int ncc, int
     }
 }
 
+// ------------------------------------------------------------------ fused range epilogue (sgpr_score_above)
+// Every eligible pair with score >= thr, in row-major order, from two runs of the same kernel instance (TK = TK_ABOVE):
+//   pass 1  each lane counts the hits among its four columns of row g; the 16 lanes of the row meet at the flush (four
+//           xor-shuffles) and the row's count goes to cnt[r] - or, for the two row groups at the ends of the workgroup's
+//           range, to partial slots [wg][2][16 rows] (tk_flush's split).  A super-block with a hit marks its work item in
+//           flag[] (a plain byte store of 1: the waves that share the item store the same value).
+//   fold + scan  above_fold_kernel adds the partial counts of each shared row and leaves every share's offset within its
+//           row in poff; above_scan_kernel turns the counts into row_ptr (int64) and the total.
+//   pass 2  re-scores the flagged work items only (an unflagged item holds no hit for any row of its workgroup, so the
+//           running positions stay right).  Hit (r, c) goes to row_ptr[r] + (the share's offset) + the hits of row r
+//           before it: a running position per row plus, within a super-block, the row's hits of lower lanes (four ballots,
+//           masked to the lane group) and of lower columns of the same lane.  Written only below cap.
+// Both passes take the same range decision and the same arithmetic (one instance), so they agree hit for hit; pass 2
+// checks that (status bit 32).
+constexpr int TK_ABOVE = -1;
+
+struct AboveArgs {
+    const int32_t* row_self;   // [R] own frame of each row, or nullptr: row0 + r
+    int row0, window, causal, pass, wg;
+    int rout0;                 // output row index of row 0 (the row block of a long launch)
+    float thr;
+    unsigned char* flag;       // [items] 1: the work item holds a hit (pass 1 writes, pass 2 reads)
+    int32_t* cnt;              // [R] hits per row
+    int32_t* pcnt;             // [grid][2][AP_ROWS] hits of the row groups at the ends of a workgroup's range
+    int32_t* poff;             // [grid][2][AP_ROWS] where that share starts within its row (above_fold_kernel)
+    const int64_t* row_ptr;    // [R + 1] (pass 2)
+    int32_t* rows;             // [cap] outputs (pass 2)
+    int32_t* cols;
+    float* vals;
+    int64_t cap;
+    int32_t* status;           // bit 16: a row_self entry outside [0, M); bit 32: pass 2 disagreed with pass 1
+};
+
+// one super-block's scores of row g (lane: columns c0 .. c0 + 3): pass 1 counts them into cnt and flags the item, pass 2
+// writes them from the row's running position pos
+__device__ __forceinline__ void ab_push(const AboveArgs& a, const float (&sc)[4], int c0, int M, int ea, int eb, bool live,
+                                        int r, int it, int& cnt, long long& pos) {
+    bool h[4];
+    int nh = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int c = c0 + b;
+        h[b] = live && c < M && (c < ea || c > eb) && sc[b] >= a.thr;
+        nh += h[b] ? 1 : 0;
+    }
+    if (a.pass == 1) {
+        cnt += nh;
+        if (__any(nh != 0) && (threadIdx.x & 63) == 0) a.flag[it] = 1;
+        return;
+    }
+    if (!__any(nh != 0)) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long gmask = 0xffffull << (lane & 48), below = gmask & ((1ull << lane) - 1ull);
+    int before = 0, total = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const unsigned long long B = __ballot(h[b]);
+        before += __popcll(B & below);
+        total += __popcll(B & gmask);
+    }
+    long long p = pos + before;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        if (h[b]) {
+            if (p < a.cap) {
+                a.rows[p] = a.rout0 + r;
+                a.cols[p] = c0 + b;
+                a.vals[p] = sc[b];
+            }
+            ++p;
+        }
+    }
+    pos += total;
+}
+
+// row group rg leaves (lane group g of this wave: row r).  Pass 1: the row's count to cnt[r], or to partial slot 0 / 1
+// when the row group is shared with a neighbouring workgroup.  Pass 2: the hits written must equal that count.
+__device__ __forceinline__ void ab_flush(const AboveArgs& a, int rg, int ncc, int it0, int it1, int r, int R, int cnt,
+                                         long long pos, long long start) {
+    const int l15 = threadIdx.x & 15;
+    const bool inside = (int64_t)rg * ncc >= it0 && (int64_t)(rg + 1) * ncc <= it1;
+    const size_t p = ((size_t)(a.wg * 2 + (rg == it0 / ncc ? 0 : 1))) * AP_ROWS + (r - rg * AP_ROWS);
+    if (a.pass == 1) {
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) cnt += __shfl_xor(cnt, m);
+        if (r >= R || l15 != 0) return;
+        if (inside) a.cnt[r] = cnt;
+        else a.pcnt[p] = cnt;
+    } else {
+        if (r >= R || l15 != 0) return;
+        if (pos - start != (inside ? a.cnt[r] : a.pcnt[p])) atomicOr(a.status, 32);
+    }
+}
+
+// pass 2: where row r's hits of this workgroup start
+__device__ __forceinline__ long long ab_start(const AboveArgs& a, int rg, int ncc, int it0, int it1, int r, int R) {
+    if (r >= R) return 0;
+    const bool inside = (int64_t)rg * ncc >= it0 && (int64_t)(rg + 1) * ncc <= it1;
+    long long s = a.row_ptr[r];
+    if (!inside) s += a.poff[((size_t)(a.wg * 2 + (rg == it0 / ncc ? 0 : 1))) * AP_ROWS + (r - rg * AP_ROWS)];
+    return s;
+}
+
 // the work items [it0, it1) of one R x M rectangle
-// TK = 0: the matrix is stored to score; TK > 0: the scores feed per-row top-TK lists (*tk), nothing is stored
+// TK = 0: the matrix is stored to score; TK > 0: the scores feed per-row top-TK lists (*tk), nothing is stored;
+// TK = TK_ABOVE: one pass of the range selection (*ab), nothing is stored
 template <int NI, int VAR, bool CL, int TK = 0>
 __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k, const bool fast, int R, int M,
                                          const unsigned short* __restrict__ Ab, const unsigned short* __restrict__ Cb,
                                          const float* __restrict__ ur, const float* __restrict__ prow,
                                          const float* __restrict__ pcol, float* __restrict__ score, int64_t ld,
-                                         const int it0, const int it1, const TopkArgs* tk = nullptr) {
+                                         const int it0, const int it1, const TopkArgs* tk = nullptr,
+                                         const AboveArgs* ab = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const f16x8 w1hi = k.w1hi, w1lo = k.w1lo;
@@ -761,9 +866,24 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
     __shared__ int tk_sc[TK > 1 ? 4 : 1][64];
     float* const lsv = tk_sv[TK > 1 ? wave : 0];
     int* const lsc = tk_sc[TK > 1 ? wave : 0];
+    // range state (TK_ABOVE): this lane's hits of row rbase + g (pass 1), the row's running / first position (pass 2)
+    int acnt = 0;
+    long long apos = 0, astart = 0;
     for (int it = it0; it < it1; ++it) {
         const int rg = it / ncc, cc = it - rg * ncc;
         if (rg != cur_rg) {
+            if constexpr (TK == TK_ABOVE) {
+                if (cur_rg >= 0) ab_flush(*ab, cur_rg, ncc, it0, it1, rbase + g, R, acnt, apos, astart);
+                const int r = rg * AP_ROWS + wave * AP_RW + g;
+                long long s = ab->row0 + (long long)r;
+                if (ab->row_self) {
+                    s = ab->row_self[min(r, R - 1)];
+                    if (ab->pass == 1 && r < R && l15 == 0 && (s < 0 || s >= M)) atomicOr(ab->status, 16);
+                }
+                tk_bounds(s, ab->window, ab->causal, ea, eb);
+                acnt = 0;
+                if (ab->pass == 2) apos = astart = ab_start(*ab, rg, ncc, it0, it1, r, R);
+            }
             if constexpr (TK > 0) {
                 if (cur_rg >= 0) tk_flush<TK>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
                 tv = thv = -INFINITY;
@@ -798,6 +918,14 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                 if ((long long)sb0 * AP_SB >= smax - (tk->window > 0 ? tk->window : 0)) continue;
             }
         }
+        if constexpr (TK == TK_ABOVE) {
+            // the same skip rule as top-k; pass 2 also skips every work item pass 1 found no hit in
+            if (ab->causal && !ab->row_self) {
+                const long long smax = ab->row0 + (long long)min(R, (rg + 1) * AP_ROWS) - 1;
+                if ((long long)sb0 * AP_SB >= smax - (ab->window > 0 ? ab->window : 0)) continue;
+            }
+            if (ab->pass == 2 && !ab->flag[it]) continue;
+        }
         if (!fast) {      // inputs outside the f16 range: exact fp32 per-pair arithmetic
             if constexpr (TK == 0) {
                 slow_tile(w, prow, pcol, rbase, min(R, rbase + AP_RW), sb0 * AP_SB, min(M, sb1 * AP_SB), score, ld);
@@ -821,7 +949,10 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                                 for (int b = 0; b < 4; ++b) sc[b] = (cl & 3) == b ? v : sc[b];
                             }
                         }
-                    tk_push<TK>(sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, tv, tc, thv, thc, lsv, lsc);
+                    if constexpr (TK == TK_ABOVE)
+                        ab_push(*ab, sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, rbase + g, it, acnt, apos);
+                    else
+                        tk_push<TK>(sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, tv, tc, thv, thc, lsv, lsc);
                 }
             }
             continue;
@@ -920,6 +1051,10 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                 tk_push<TK>(sc, c0, M, ea, eb, r < R, tv, tc, thv, thc, lsv, lsc);
                 continue;
             }
+            if constexpr (TK == TK_ABOVE) {
+                ab_push(*ab, sc, c0, M, ea, eb, r < R, r, it, acnt, apos);
+                continue;
+            }
             if ((VAR & 2) && sc[0] + sc[1] + sc[2] + sc[3] != 12345.678f) continue;
             if (r < R) {
                 float* dst = score + (size_t)r * ld + c0;
@@ -940,6 +1075,9 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
     }
     if constexpr (TK > 0) {
         if (cur_rg >= 0) tk_flush<TK>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
+    }
+    if constexpr (TK == TK_ABOVE) {
+        if (cur_rg >= 0) ab_flush(*ab, cur_rg, ncc, it0, it1, rbase + g, R, acnt, apos, astart);
     }
 }
 
@@ -1078,6 +1216,145 @@ __global__ __launch_bounds__(256) void topk_fill_kernel(int64_t n, float* __rest
     if (i < n) {
         val[i] = -INFINITY;
         idx[i] = -1;
+    }
+}
+
+// one pass (a.pass) of the rectangle's range selection (sgpr_score_above): score_topk_kernel with the TK_ABOVE epilogue
+template <int OCC, int NI>
+__global__ __launch_bounds__(256, OCC) void score_above_kernel(const DevWeights w, int R, int M,
+                                                               const unsigned short* __restrict__ Ab,
+                                                               const unsigned short* __restrict__ Cb,
+                                                               const float* __restrict__ ur,
+                                                               const float* __restrict__ rng, int nrng,
+                                                               const float* __restrict__ prow,
+                                                               const float* __restrict__ pcol, AboveArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
+    ap_range(rng, nrng, am, um, em, l1);
+    const int mode = ap_mode(am, um, em, l1);
+    const ApConsts k = ap_consts(w, l15, g);
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const unsigned nwg = gridDim.x;
+    const unsigned wg = (nwg & 7u) == 0u ? (blockIdx.x & 7u) * (nwg >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int it0 = (int)(items * wg / nwg), it1 = (int)(items * (wg + 1) / nwg);
+    a.wg = (int)wg;
+    if (mode == 2)
+        ap_items<NI, 0, true, TK_ABOVE>(w, k, true, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, &a);
+    else
+        ap_items<NI, 0, false, TK_ABOVE>(w, k, mode != 0, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, &a);
+}
+
+// rows of the row groups shared by several workgroups: the partial counts -> cnt[r], and each share's offset within its
+// row -> poff (in logical workgroup order = column order).  One wave per row group (topk_merge_kernel's run arithmetic).
+__global__ __launch_bounds__(64) void above_fold_kernel(int R, int M, int nwg, AboveArgs a) {
+    const int rg = blockIdx.x, rr = threadIdx.x;
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const int64_t lo = (int64_t)rg * ncc, hi = lo + ncc;
+    int w0 = 0, w1 = nwg - 1;                           // first workgroup whose range ends past lo
+    for (int n = nwg - 1; w0 < n;) {
+        const int m = (w0 + n) >> 1;
+        if (items * (m + 1) / nwg > lo) n = m; else w0 = m + 1;
+    }
+    for (int n = 0; n < w1;) {                          // last workgroup whose range starts before hi
+        const int m = (n + w1 + 1) >> 1;
+        if (items * m / nwg < hi) n = m; else w1 = m - 1;
+    }
+    const int r = rg * AP_ROWS + rr;
+    if (w0 >= w1 || rr >= AP_ROWS || r >= R) return;   // one workgroup saw the whole row group: cnt is final
+    int sum = 0;
+#pragma unroll 1
+    for (int wv = w0; wv <= w1; ++wv) {
+        const size_t p = (size_t)(wv * 2 + ((items * wv / nwg) / ncc == rg ? 0 : 1)) * AP_ROWS + rr;
+        a.poff[p] = sum;
+        sum += a.pcnt[p];
+    }
+    a.cnt[r] = sum;
+}
+
+// cnt [R] -> row_ptr [R + 1] (exclusive, int64) and *count = the total; accumulate: both start from *count (the row
+// blocks of the chunked path), else from 0.  One workgroup: each thread adds a contiguous run of rows, the runs' sums are
+// scanned across the workgroup, then each thread writes its run.
+__global__ __launch_bounds__(1024) void above_scan_kernel(const int32_t* __restrict__ cnt, int R, int64_t* __restrict__ row_ptr,
+                                                          unsigned long long* __restrict__ count, int accumulate) {
+    __shared__ long long wsum[16];
+    __shared__ long long sbase;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int per = (R + 1023) / 1024;
+    const int lo = (int)min((int64_t)R, (int64_t)t * per), hi = min(R, lo + per);
+    long long s = 0;
+    for (int i = lo; i < hi; ++i) s += cnt[i];
+    long long x = s;                                    // inclusive scan over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const long long y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    if (t == 0) sbase = accumulate ? (long long)*count : 0;
+    __syncthreads();
+    long long run = sbase + x - s;
+    for (int v = 0; v < wave; ++v) run += wsum[v];
+    for (int i = lo; i < hi; ++i) {
+        row_ptr[i] = run;
+        run += cnt[i];
+    }
+    if (t == 0) {
+        long long total = sbase;
+        for (int v = 0; v < 16; ++v) total += wsum[v];
+        row_ptr[R] = total;
+        *count = (unsigned long long)total;
+    }
+}
+
+// the range selection on a resident matrix (sgpr_rows_above and the chunked path): one wave per row.  PASS 1 counts the
+// row's hits into cnt[r]; PASS 2 writes them in column order from row_ptr[r] (64 columns per ballot) to output row
+// rout0 + r, below cap, and checks the count (status bit 32)
+template <int PASS>
+__global__ __launch_bounds__(256) void rows_above_kernel(const float* __restrict__ score, int R, int M, int64_t ld,
+                                                         const int32_t* __restrict__ row_self, int row0, int window,
+                                                         int causal, float thr, int32_t* __restrict__ cnt,
+                                                         const int64_t* __restrict__ row_ptr, int rout0,
+                                                         int32_t* __restrict__ orows, int32_t* __restrict__ ocols,
+                                                         float* __restrict__ ovals, int64_t cap, int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    long long s = row0 + (long long)r;
+    if (row_self) {
+        s = row_self[r];
+        if (PASS == 1 && lane == 0 && (s < 0 || s >= M)) atomicOr(status, 16);
+    }
+    int ea, eb;
+    tk_bounds(s, window, causal, ea, eb);
+    const int cend = eb == 0x7fffffff ? min(M, max(ea, 0)) : M;    // nothing at or beyond ea is eligible then
+    const float* sp = score + (size_t)r * ld;
+    if constexpr (PASS == 1) {
+        int n = 0;
+        for (int c = lane; c < cend; c += 64) n += ((c < ea || c > eb) && sp[c] >= thr) ? 1 : 0;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) n += __shfl_xor(n, m);
+        if (lane == 0) cnt[r] = n;
+    } else {
+        const long long start = row_ptr[r];
+        long long pos = start;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        for (int c0 = 0; c0 < cend; c0 += 64) {
+            const int c = c0 + lane;
+            const float v = c < cend ? sp[c] : 0.f;
+            const bool h = c < cend && (c < ea || c > eb) && v >= thr;
+            const unsigned long long B = __ballot(h);
+            const long long p = pos + __popcll(B & below);
+            if (h && p < cap) {
+                orows[p] = rout0 + r;
+                ocols[p] = c;
+                ovals[p] = v;
+            }
+            pos += __popcll(B);
+        }
+        if (lane == 0 && pos - start != cnt[r]) atomicOr(status, 32);
     }
 }
 
@@ -1414,6 +1691,130 @@ int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const floa
     }
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "topk_merge_kernel launch");
+    return SGPR_OK;
+}
+
+// ------------------------------------------------------------------ fused score + range selection (sgpr_score_above)
+// Rows go in blocks of at most AB_ROWS (the row operands take 2 KB per row: 0.6 GB at 300 k rows in one launch); the
+// positions of a block continue from the device-resident count of the blocks before it.
+// workspace: row_ptr [R + 1] i64 (used when the caller passes none) | for one row block: score_all_pairs' operands |
+// flag [items] u8 | cnt [rows] i32 | pcnt, poff [grid][2][AP_ROWS] i32
+constexpr int AB_ROWS = 131072;
+
+static size_t above_block_ws_bytes(const sgpr_handle* h, int R, int M) {
+    const size_t items = (size_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
+    const size_t slots = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS;
+    return align256(score_all_pairs_ws_bytes(R, M)) + align256(items) + align256((size_t)R * 4) + 2 * align256(slots * 4);
+}
+
+size_t score_above_ws_bytes(const sgpr_handle* h, int R, int M) {
+    if (R == 0 || M == 0) return 0;
+    return align256((size_t)(R + 1) * 8) + above_block_ws_bytes(h, R < AB_ROWS ? R : AB_ROWS, M);
+}
+
+size_t rows_above_ws_bytes(int R) { return R == 0 ? 0 : align256((size_t)R * 4) + align256((size_t)(R + 1) * 8); }
+
+int launch_above_empty(int R, int64_t* row_ptr, unsigned long long* count, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess && row_ptr) e = hipMemsetAsync(row_ptr, 0, (size_t)(R + 1) * sizeof(int64_t), stream);
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "sgpr_score_above: clearing the counts");
+}
+
+// one row block: rows [rout0, rout0 + R) of the call; rp = the call's row_ptr + rout0
+static int launch_above_block(const sgpr_handle* h, const float* rows, int R, const float* cols, int M,
+                              const int32_t* row_self, int row0, int window, int causal, float thr, int32_t* orows,
+                              int32_t* ocols, float* ovals, int64_t cap, int64_t* rp, int rout0,
+                              unsigned long long* count, void* ws, hipStream_t stream) {
+    const int ngroups = ap_prep_groups(R, M), nrng = 2 * ngroups;
+    unsigned char* base = static_cast<unsigned char*>(ws);
+    float* ur = reinterpret_cast<float*>(base);            // the operand layout of launch_score_all_pairs
+    float* rng = ur + (size_t)R * T;
+    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
+    unsigned short* Cb = Ab + (size_t)R * 2 * 64 * 8;
+    const int64_t grid = topk_grid(h, R, M);
+    const size_t items = (size_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
+    const size_t slots = (size_t)grid * 2 * AP_ROWS;
+    unsigned char* p = base + align256(score_all_pairs_ws_bytes(R, M));
+    AboveArgs a;
+    a.row_self = row_self;
+    a.row0 = row0;
+    a.window = window;
+    a.causal = causal;
+    a.pass = 1;
+    a.wg = 0;
+    a.thr = thr;
+    a.flag = p;
+    p += align256(items);
+    a.cnt = reinterpret_cast<int32_t*>(p);
+    p += align256((size_t)R * 4);
+    a.pcnt = reinterpret_cast<int32_t*>(p);
+    p += align256(slots * 4);
+    a.poff = reinterpret_cast<int32_t*>(p);
+    a.rout0 = rout0;
+    a.row_ptr = rp;
+    a.rows = orows;
+    a.cols = ocols;
+    a.vals = ovals;
+    a.cap = cap;
+    a.status = h->d_status;
+    hipError_t e = hipMemsetAsync(a.flag, 0, items, stream);
+    if (e != hipSuccess) return hip_fail(e, "sgpr_score_above: clearing the item flags");
+    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+    const dim3 gd((unsigned)grid), bd(256);
+    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 1)");
+    hipLaunchKernelGGL(above_fold_kernel, dim3((unsigned)((R + AP_ROWS - 1) / AP_ROWS)), dim3(64), 0, stream, R, M, (int)grid, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "above_fold_kernel launch");
+    hipLaunchKernelGGL(above_scan_kernel, dim3(1), dim3(1024), 0, stream, a.cnt, R, rp, count, rout0 > 0 ? 1 : 0);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "above_scan_kernel launch");
+    if (cap == 0) return SGPR_OK;                          // count only
+    a.pass = 2;
+    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 2)");
+    return SGPR_OK;
+}
+
+int launch_score_above(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
+                       int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
+                       int64_t cap, int64_t* row_ptr, unsigned long long* count, void* ws, hipStream_t stream) {
+    if (R == 0 || M == 0) return launch_above_empty(R, row_ptr, count, stream);
+    unsigned char* base = static_cast<unsigned char*>(ws);
+    int64_t* rp = row_ptr ? row_ptr : reinterpret_cast<int64_t*>(base);
+    void* bws = base + align256((size_t)(R + 1) * 8);
+    for (int r0 = 0; r0 < R; r0 += AB_ROWS) {
+        const int n = R - r0 < AB_ROWS ? R - r0 : AB_ROWS;
+        const int rc = launch_above_block(h, rows + (size_t)r0 * F, n, cols, M, row_self ? row_self + r0 : nullptr,
+                                          row0 + r0, window, causal, thr, orows, ocols, ovals, cap, rp + r0, r0, count,
+                                          bws, stream);
+        if (rc != SGPR_OK) return rc;
+    }
+    return SGPR_OK;
+}
+
+int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                      int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals, int64_t cap, int64_t* row_ptr,
+                      int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status, hipStream_t stream) {
+    if (R == 0) return SGPR_OK;
+    int32_t* cnt = static_cast<int32_t*>(ws);
+    const dim3 grid((unsigned)((R + 3) / 4)), block(256);
+    hipLaunchKernelGGL(rows_above_kernel<1>, grid, block, 0, stream, score, R, M, ld, row_self, row0, window, causal, thr,
+                       cnt, row_ptr, rout0, orows, ocols, ovals, cap, status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "rows_above_kernel launch (pass 1)");
+    hipLaunchKernelGGL(above_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, R, row_ptr, count, accumulate);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "above_scan_kernel launch");
+    if (cap == 0) return SGPR_OK;
+    hipLaunchKernelGGL(rows_above_kernel<2>, grid, block, 0, stream, score, R, M, ld, row_self, row0, window, causal, thr,
+                       cnt, row_ptr, rout0, orows, ocols, ovals, cap, status);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "rows_above_kernel launch (pass 2)");
     return SGPR_OK;
 }
 

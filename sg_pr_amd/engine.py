@@ -42,6 +42,8 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_pair_positives", "sgpr_pair_threshold_counts_workspace_bytes", "sgpr_pair_threshold_counts",
                "sgpr_f1_max_workspace_bytes", "sgpr_f1_max", "sgpr_topk_rows",
                "sgpr_score_topk_workspace_bytes", "sgpr_score_topk",
+               "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
+               "sgpr_rows_above",
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
                "sgpr_attention_pool_any", "sgpr_ntn_any",
                "sgpr_cluster_workspace_bytes", "sgpr_cluster_scan", "sgpr_graph_edges",
@@ -168,6 +170,15 @@ def load_library():
     lib.sgpr_score_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
     lib.sgpr_score_topk.restype = i32
     lib.sgpr_score_topk.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    f32 = ctypes.c_float
+    lib.sgpr_score_above_workspace_bytes.restype = sz
+    lib.sgpr_score_above_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.sgpr_score_above.restype = i32
+    lib.sgpr_score_above.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
+    lib.sgpr_rows_above_workspace_bytes.restype = sz
+    lib.sgpr_rows_above_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.sgpr_rows_above.restype = i32
+    lib.sgpr_rows_above.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, f32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
     lib.sgpr_embed_lds_bytes.restype = sz
     lib.sgpr_embed_lds_bytes.argtypes = [vp, i32, i32]
     lib.sgpr_knn.restype = i32
@@ -797,6 +808,95 @@ class Engine:
                                       int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         return vals, idx
+
+    def score_above_workspace_bytes(self, r, m, causal=False):
+        return int(self.lib.sgpr_score_above_workspace_bytes(self._h, int(r), int(m), self.TOPK_CAUSAL if causal else 0))
+
+    def rows_above_workspace_bytes(self, r, m):
+        return int(self.lib.sgpr_rows_above_workspace_bytes(self._h, int(r), int(m)))
+
+    @staticmethod
+    def above_estimate(r, m):
+        """first output capacity of score_above / rows_above with capacity=None"""
+        return min(int(r) * int(m), max(1 << 16, 16 * int(r)))
+
+    def _above(self, r, m, capacity, call):
+        """run call(cap, rows, cols, values, row_ptr, count) -> rc: with capacity=None once at above_estimate and, if
+        the count read back exceeds it, once more at the exact count; else once, asynchronously"""
+        def run(cap):
+            out_r = torch.empty(cap, dtype=torch.int32, device=self.device)
+            out_c = torch.empty(cap, dtype=torch.int32, device=self.device)
+            out_v = torch.empty(cap, dtype=torch.float32, device=self.device)
+            row_ptr = torch.empty(r + 1, dtype=torch.int64, device=self.device)
+            count = torch.empty(1, dtype=torch.int64, device=self.device)
+            self._check(call(cap, out_r, out_c, out_v, row_ptr, count))
+            return out_r, out_c, out_v, row_ptr, count
+        if capacity is not None:
+            if int(capacity) < 0:
+                raise ValueError("capacity must be >= 0, got %d" % int(capacity))
+            return run(int(capacity))[:4]
+        cap = self.above_estimate(r, m)
+        out_r, out_c, out_v, row_ptr, count = run(cap)
+        n = int(count.item())                               # the one synchronisation
+        if n > cap:
+            out_r, out_c, out_v, row_ptr, count = run(n)
+        return out_r[:n], out_c[:n], out_v[:n], row_ptr
+
+    def _row_self(self, row_self, r):
+        if row_self is None:
+            return None
+        rs = self._dev(row_self, torch.int32, "row_self")
+        if rs.shape != (r,):
+            raise ValueError("row_self must be [%d], got %s" % (r, tuple(rs.shape)))
+        return rs
+
+    def score_above(self, pooled_rows, pooled_cols, threshold, window=-1, row0=0, causal=False, row_self=None,
+                    capacity=None):
+        """Every pair (r, c) of the rectangle pooled_rows x pooled_cols with score >= threshold, without forming the
+        matrix (sgpr_score_above).  Column c is eligible for row r iff |c - self_r| > window (window < 0: no window)
+        and, causal, c < self_r, where self_r = row_self[r] or row0 + r; NaN scores never qualify.
+        -> (rows i32 [n], cols i32 [n], values f32 [n], row_ptr i64 [R+1]) on the device, row-major (r, then c
+        ascending); every value is bit-identical to score_all_pairs' entry (r, c); row_ptr[-1] is the exact total.
+        capacity=None: the call runs at an estimated capacity and reads the 8-byte count back - the only host
+        synchronisation -; if more pairs qualify it runs again at the exact count, and n = the total.
+        capacity=K: fully asynchronous; the arrays are [K] and hold the first min(total, K) pairs (the rest of them
+        is undefined when fewer qualify: row_ptr[-1] tells how many)."""
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        flags = self.TOPK_CAUSAL if causal else 0
+        ws_bytes = self.lib.sgpr_score_above_workspace_bytes(self._h, r, m, flags)
+        ws = self._ws(ws_bytes)
+
+        def call(cap, out_r, out_c, out_v, row_ptr, count):
+            return self.lib.sgpr_score_above(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window),
+                                             flags, float(threshold), _ptr(out_r), _ptr(out_c), _ptr(out_v), cap,
+                                             _ptr(row_ptr), _ptr(count), _ptr(ws), ws_bytes, self._stream())
+        return self._above(r, m, capacity, call)
+
+    def rows_above(self, score, threshold, window=-1, row0=0, causal=False, row_self=None, capacity=None):
+        """score_above's selection on a resident matrix score [R, M] (sgpr_rows_above; any row stride >= M with unit
+        column stride is read in place) -> (rows, cols, values, row_ptr), with score_above's rules and capacity."""
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
+                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
+            score = self._dev(score, torch.float32, "score")
+        r, m = score.shape
+        ld = max(score.stride(0), m)
+        rs = self._row_self(row_self, r)
+        flags = self.TOPK_CAUSAL if causal else 0
+        ws_bytes = self.lib.sgpr_rows_above_workspace_bytes(self._h, r, m)
+        ws = self._ws(ws_bytes)
+
+        def call(cap, out_r, out_c, out_v, row_ptr, count):
+            return self.lib.sgpr_rows_above(self._h, _ptr(score), r, m, ld, _ptr(rs), int(row0), int(window), flags,
+                                            float(threshold), _ptr(out_r), _ptr(out_c), _ptr(out_v), cap,
+                                            _ptr(row_ptr), _ptr(count), _ptr(ws), ws_bytes, self._stream())
+        return self._above(r, m, capacity, call)
 
     def forward_dense(self, features_1, features_2, k, want_att=True):
         """Drop-in SG.forward on dense [B,3+L,N] inputs -> (score [B], att1 [B,N], att2 [B,N])."""

@@ -260,3 +260,37 @@ def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1
         hits += (first & valid[:, None]).sum(dim=0).to(torch.float64)
         counted += int(valid.sum())
     return (hits / counted).cpu().numpy() if counted else np.zeros(kk)
+
+
+def precision_recall_at(rows, cols, pose_xz, p_thresh=3.0, n_thresh=20.0, window=50, causal=False, chunk=None):
+    """Precision and recall of a list of accepted pairs (sgpr_score_above's rows / cols of query frames 0..M-1 against
+    frames 0..M-1, M = len(pose_xz)) under the repository's pair classes: distance <= p_thresh positive, >= n_thresh
+    negative, in between not counted.  precision = positives / (positives + negatives) among the pairs; recall =
+    positives among the pairs / every eligible positive pair (|c - r| > window, window < 0: no window; causal: c < r),
+    counted with plain torch on the poses, chunked by rows (not a hot path).  Distances are compared squared, in float64.
+    pose_xz: [M, 2] (or [M, 12] KITTI rows).  -> (precision, recall) floats, 0 where the denominator is 0."""
+    import torch
+    from .allpairs import pose_xz as _xz
+    rows = torch.as_tensor(rows).long()
+    cols = torch.as_tensor(cols).long().to(rows.device)
+    xz = _xz(pose_xz).to(device=rows.device, dtype=torch.float64)
+    m = xz.shape[0]
+    p2, n2 = float(p_thresh) ** 2, float(n_thresh) ** 2
+    d2 = ((xz[rows] - xz[cols]) ** 2).sum(dim=1)
+    tp = int((d2 <= p2).sum())
+    fp = int((d2 >= n2).sum())
+    chunk = chunk or max(1, (1 << 24) // max(m, 1))
+    allc = torch.arange(m, device=xz.device)
+    positives = 0
+    for lo in range(0, m, chunk):
+        hi = min(m, lo + chunk)
+        r = torch.arange(lo, hi, device=xz.device)
+        near = ((xz[lo:hi, None, :] - xz[None, :, :]) ** 2).sum(dim=2) <= p2
+        if window >= 0:
+            near &= (allc[None, :] - r[:, None]).abs() > window
+        if causal:
+            near &= allc[None, :] < r[:, None]
+        positives += int(near.sum())
+    precision = tp / (tp + fp) if tp + fp else 0.0
+    recall = tp / positives if positives else 0.0
+    return precision, recall

@@ -1,4 +1,4 @@
-"""`torch.library` custom ops over the C-ABI (SURVEY §8b "Custom ops"): the hot path as five dispatcher-visible ops.
+"""`torch.library` custom ops over the C-ABI (SURVEY §8b "Custom ops"): the hot path as six dispatcher-visible ops.
 
     torch.ops.sgpr.embed(centers [G,N,3] f32, labels [G,N] i32, weights_blob [48689] f32, k) -> (pooled, att)
     torch.ops.sgpr.score_pairs(pooled1 [B,32], pooled2 [B,32], weights_blob)                -> score [B]
@@ -6,6 +6,8 @@
     torch.ops.sgpr.forward_dense(features_1 [B,15,N], features_2 [B,15,N], weights_blob, k) -> (score, att1, att2)
     torch.ops.sgpr.score_topk(pooled_rows [R,32], pooled_cols [M,32], weights_blob, k, window, row0, causal, row_self)
                                                                                             -> (values [R,k], indices [R,k])
+    torch.ops.sgpr.score_above(pooled_rows [R,32], pooled_cols [M,32], weights_blob, threshold, window, row0, causal,
+                               row_self, capacity)             -> (rows [n] i32, cols [n] i32, values [n], row_ptr [R+1] i64)
 
 `weights_blob` is the flat fp32 tensor of `engine.blob_from_state_dict` (order in include/sgpr.h); one engine handle is
 kept per (blob tensor, version, device) and released with the tensor.  GPU tensors only: there is no CPU implementation - a CPU call raises.  Fake (meta)
@@ -109,3 +111,21 @@ def score_topk(pooled_rows: torch.Tensor, pooled_cols: torch.Tensor, weights_blo
 def _(pooled_rows, pooled_cols, weights_blob, k=1, window=-1, row0=0, causal=False, row_self=None):
     r = pooled_rows.shape[0]
     return pooled_rows.new_empty((r, k)), pooled_rows.new_empty((r, k), dtype=torch.int32)
+
+
+@torch.library.custom_op("sgpr::score_above", mutates_args=())
+def score_above(pooled_rows: torch.Tensor, pooled_cols: torch.Tensor, weights_blob: torch.Tensor, threshold: float,
+                window: int = -1, row0: int = 0, causal: bool = False, row_self: torch.Tensor | None = None,
+                capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return tuple(t.clone() if capacity is None else t for t in _engine_for(weights_blob, pooled_rows.device).score_above(
+        pooled_rows, pooled_cols, threshold, window=window, row0=row0, causal=causal, row_self=row_self,
+        capacity=capacity))
+
+
+@score_above.register_fake
+def _(pooled_rows, pooled_cols, weights_blob, threshold, window=-1, row0=0, causal=False, row_self=None, capacity=None):
+    r = pooled_rows.shape[0]
+    n = torch.library.get_ctx().new_dynamic_size() if capacity is None else capacity
+    i32 = torch.int32
+    return (pooled_rows.new_empty((n,), dtype=i32), pooled_rows.new_empty((n,), dtype=i32), pooled_rows.new_empty((n,)),
+            pooled_rows.new_empty((r + 1,), dtype=torch.int64))

@@ -5,16 +5,18 @@ with sgpr_score_topk - the k best matches per query, no similarity matrix at any
     ids = db.add(centers, labels)                      # embed (ordered launch), append; -> new ids
     vals, idx = db.query(centers, labels, k=1, window=50, causal=True)   # new graphs: frames len(db), len(db) + 1, ...
     vals, idx = db.query_ids(ids, k=4, window=50)      # members: row_self = their ids
+    rows, cols, vals, row_ptr = db.query_ids_above(ids, 0.9, window=50)   # every member scoring >= 0.9
     db.save("map.npz"); db = PlaceDatabase.load("map.npz", model)
 
 A vector costs 128 bytes of device memory (the matrix of a 100 k-graph map would be 40 GB).  The file keeps the vectors,
 the architecture and a sha256 of the checkpoint's weight blob: vectors of one checkpoint are meaningless to another, so
 `load` refuses them.
 
-    python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal]
+    python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
-frame, indices [M,K], scores [M,K] and recall@1..K.
+frame, indices [M,K], scores [M,K] and recall@1..K; with --threshold also `<seq>_above.npz` with every pair scoring
+>= T (rows, cols, scores) and its precision / recall (metrics.precision_recall_at).
 """
 import argparse
 import hashlib
@@ -89,6 +91,21 @@ class PlaceDatabase:
         return self.eng.score_topk(rows, self.pooled, k=k, window=window, causal=causal,
                                    row_self=ids.to(torch.int32))
 
+    def query_above(self, centers, labels, threshold, window=-1, causal=False):
+        """Every member scoring >= threshold for graphs that are NOT in the database (frames len(db), len(db) + 1, ...)
+        -> (rows i32 [n], ids i32 [n], scores f32 [n], row_ptr i64 [g+1]) on the device (engine.Engine.score_above)."""
+        return self.eng.score_above(self._embed(centers, labels), self.pooled, threshold, window=window, row0=self.n,
+                                    causal=causal)
+
+    def query_ids_above(self, ids, threshold, window=-1, causal=False):
+        """Every member scoring >= threshold for members `ids` (row_self = ids)."""
+        ids = torch.as_tensor(ids, dtype=torch.int64).to(self._buf.device)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n):
+            raise IndexError("query_ids_above: ids must lie in [0, %d)" % self.n)
+        rows = self.pooled.index_select(0, ids)
+        return self.eng.score_above(rows, self.pooled, threshold, window=window, causal=causal,
+                                    row_self=ids.to(torch.int32))
+
     def save(self, path):
         dims = np.array([getattr(self.eng.dims, f) for f in _DIMS], dtype=np.int64)
         np.savez(path, pooled=self.pooled.cpu().numpy(), dims=dims, weights_sha256=np.array(weights_sha256(self.model)))
@@ -117,6 +134,7 @@ def main(argv=None):
     ap.add_argument("--k", type=int, default=1)
     ap.add_argument("--window", type=int, default=50)
     ap.add_argument("--causal", action="store_true")
+    ap.add_argument("--threshold", type=float, default=None)
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
     args = sgpr_args()
     args.load(opt.config)
@@ -141,6 +159,15 @@ def main(argv=None):
                  indices=idx.cpu().numpy(), scores=vals.cpu().numpy(), recall=recall)
         print("sequence", sequence, "frames", m, "recall@1..%d" % opt.k, " ".join("%.4f" % r for r in recall))
         results[sequence] = recall
+        if opt.threshold is not None:
+            rows, cols, scores, _ = db.query_ids_above(torch.arange(m), opt.threshold, window=opt.window,
+                                                       causal=opt.causal)
+            precision, rec = metrics.precision_recall_at(rows, cols, seq.poses, p_thresh=float(args.p_thresh),
+                                                         window=opt.window, causal=opt.causal)
+            np.savez(os.path.join(args.output_path, sequence + "_above.npz"), rows=rows.cpu().numpy(),
+                     cols=cols.cpu().numpy(), scores=scores.cpu().numpy(), precision=precision, recall=rec)
+            print("sequence", sequence, "threshold", opt.threshold, "pairs", rows.numel(),
+                  "precision %.4f recall %.4f" % (precision, rec))
     return results
 
 

@@ -152,6 +152,13 @@ class SG(torch.nn.Module):
         return self.engine().score_topk(pooled_rows, pooled_cols, k=k, window=window, row0=row0, causal=causal,
                                         row_self=row_self)
 
+    def loop_closures_above(self, pooled_rows, pooled_cols, threshold, window=-1, row0=0, causal=False, row_self=None,
+                            capacity=None):
+        """Every pair of pooled_rows x pooled_cols scoring >= threshold, without forming the matrix
+        (engine.Engine.score_above) -> (rows i32 [n], cols i32 [n], values f32 [n], row_ptr i64 [R+1]) on the device."""
+        return self.engine().score_above(pooled_rows, pooled_cols, threshold, window=window, row0=row0, causal=causal,
+                                         row_self=row_self, capacity=capacity)
+
     def forward_packed(self, centers_1, labels_1, centers_2, labels_2, validate=True):
         """Faithful per-pair scoring of packed graphs: both sides embedded, then the tail.
         validate (default): synchronise and raise SgprError if the kernel saw a label outside [-1, L) (the reference
