@@ -19,6 +19,14 @@
  *     streams/threads (the sgpr_debug_* hooks are the one exception: they are
  *     per handle, off by default and not meant for production).  One process
  *     per GPU.
+ *   - the device status word (label / node_cap / row_self reports) belongs to
+ *     the handle, not to a call: sgpr_check_status reports and clears the
+ *     flags raised by ANY call on the handle since the last check, on any
+ *     stream or thread.
+ *   - results depend on the arguments alone: every workspace region is set by
+ *     the call that reads it (a memset, a producer kernel or a per-call token),
+ *     so a workspace may hold anything - another entry point's leftovers
+ *     included - and output buffers need no clearing.
  *   - every entry point that takes a handle runs on the handle's device and
  *     restores the caller's current device before it returns; the handle-free
  *     entry points (sgpr_knn, sgpr_graph_feature, sgpr_attention_pool,
@@ -266,7 +274,9 @@ int sgpr_forward_dense(const sgpr_handle* h, const float* d_features_1, const fl
 
 /* Synchronises `stream` and returns SGPR_E_LABEL if any launch on this handle
  * saw a label outside [-1, num_labels) since the last check (the reference
- * raises KeyError at sg_net.py:277), else SGPR_OK.  Clears the flag. */
+ * raises KeyError at sg_net.py:277), else SGPR_OK.  Clears the flag.  The flags
+ * are the handle's: a launch on another stream or thread raises them too, and
+ * only the work of `stream` is waited for. */
 int sgpr_check_status(const sgpr_handle* h, void* stream);
 
 /* ---- consumers of the score matrix that keep it on the device ----------------------------------------

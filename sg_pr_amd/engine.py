@@ -6,6 +6,7 @@ There is NO CPU fallback: a missing library or a non-GPU tensor raises.
 """
 import ctypes
 import os
+import threading
 
 import numpy as np
 import torch
@@ -266,6 +267,8 @@ class Engine:
         self.any_shape = bool(self.lib.sgpr_is_any_shape(h))
         self.num_cus = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
         self._order_cache = []            # (tensor objects, offsets, shape, versions, K) -> device launch order + node_cap, see embed()
+        self._order_lock = threading.Lock()
+        self._host_bufs = threading.local()  # per-thread pinned read-back buffers (f1_max)
 
     def close(self):
         if self._h is not None:
@@ -411,34 +414,45 @@ class Engine:
         """The largest-first launch order and the node_cap of a RESIDENT batch (sgpr_size_order, asynchronous), remembered per
         tensor pair, so that evaluating the same packed store again costs nothing -> (order, node_cap or 0).  An entry
         belongs to the tensors' base OBJECTS (weak references: a new tensor that happens to reuse the address of a freed
-        one is a different object), their storage offsets / shapes, torch's in-place version counters and K.  The order is
-        used at once; the node_cap travels to pinned host memory behind an event and is used from the first later call
-        that finds the copy complete (no synchronisation, ever).  Whatever the cache says, the kernels check it: an order
-        is a permutation of the batch's graphs (it decides when a graph runs, never what it yields), a node_cap a
-        promise (a graph beyond it: NaN + SGPR_E_NODES, never a wrong result).  A data-set property kept by the binding;
+        one is a different object), their storage offsets / shapes, torch's in-place version counters and K.  Inference
+        tensors (torch.inference_mode) have no version counter: their entry is kept by object, offsets, shape and K alone.
+        The node_cap travels to pinned host memory behind an event and is returned from the first later call that finds
+        the copy complete (no synchronisation, ever); embed() does not promise it (see there).  The order is made on the
+        stream current at the first call: a hit on another stream waits for that event and records the order on its own
+        stream.  A stale order is harmless - it is a permutation of the batch's graphs and decides when a graph runs,
+        never what it yields.  A data-set property kept by the binding (under a lock: one Engine serves several threads);
         the C-ABI stays stateless."""
         import weakref
         bc = centers._base if centers._base is not None else centers
         bl = labels._base if labels._base is not None else labels
-        key = (centers.storage_offset(), labels.storage_offset(), tuple(labels.shape), centers._version, labels._version, int(k))
-        live = []
-        hit = None
-        for rc, rl, kk, order, info_h, ev in self._order_cache:
-            if rc() is None or rl() is None:
-                continue                                   # a tensor of the entry is gone
-            live.append((rc, rl, kk, order, info_h, ev))
-            if kk == key and rc() is bc and rl() is bl:
-                hit = (order, int(info_h[0]) if ev.query() else 0)
-        self._order_cache = live
-        if hit is not None:
-            return hit
-        order, info = self.size_order_device(centers, labels, None, labels.shape[1], k)
-        info_h = torch.empty(2, dtype=torch.int32).pin_memory()
-        info_h.copy_(info, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self._order_cache = self._order_cache[-7:] + [(weakref.ref(bc), weakref.ref(bl), key, order, info_h, ev)]
-        return order, 0
+        tracked = not (centers.is_inference() or labels.is_inference())
+        versions = (centers._version, labels._version) if tracked else (None, None)
+        key = (centers.storage_offset(), labels.storage_offset(), tuple(labels.shape)) + versions + (int(k),)
+        cur = torch.cuda.current_stream(self.device)
+        with self._order_lock:
+            live = []
+            hit = None
+            for entry in self._order_cache:
+                rc, rl, kk, order, info_h, ev, made_on = entry
+                if rc() is None or rl() is None:
+                    continue                                   # a tensor of the entry is gone
+                live.append(entry)
+                if kk == key and rc() is bc and rl() is bl:
+                    hit = entry
+            self._order_cache = live
+            if hit is not None:
+                _, _, _, order, info_h, ev, made_on = hit
+                if made_on != cur:
+                    cur.wait_event(ev)                         # the order is complete before this stream reads it ...
+                    order.record_stream(cur)                   # ... and its memory is not reused while it may
+                return order, int(info_h[0]) if ev.query() else 0
+            order, info = self.size_order_device(centers, labels, None, labels.shape[1], k)
+            info_h = torch.empty(2, dtype=torch.int32).pin_memory()
+            info_h.copy_(info, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._order_cache = self._order_cache[-7:] + [(weakref.ref(bc), weakref.ref(bl), key, order, info_h, ev, cur)]
+            return order, 0
 
     def embed(self, centers, labels, k, want_att=False, want_emb=False, debug=False, node_cap=0, order=None, auto_order=True):
         """centers [G,N,3] f32, labels [G,N] i32 (-1 = pad) -> pooled [G,32] (+ att [G,N], emb [G,N,32]).
@@ -446,8 +460,10 @@ class Engine:
         order: optional i32 launch order (size_order) - graphs not listed keep uninitialised output rows.
         auto_order: no order given and the arrays already resident on this device (more graphs than CUs, the tuned kernels'
         node_num): launch in the largest-first order sgpr_size_order makes on the device, computed once per tensor pair
-        (_cached_order) - same bits, ~5 % faster than storage order on KITTI-like data; from the second call on the batch's
-        node_cap (made by the same kernels) is promised as well; False = the plain C-ABI call."""
+        (_cached_order) - same bits, faster than storage order on KITTI-like data; False = the plain C-ABI call.  The
+        cached node_cap is NOT promised: a write torch does not track (`x.data.copy_`, DLPack, a kernel writing through
+        data_ptr()) leaves the cache key as it was, and a promise made from it could be broken by the data (NaN +
+        SGPR_E_NODES).  Callers who know their data pass node_cap= themselves (size_order gives it)."""
         resident = (isinstance(centers, torch.Tensor) and isinstance(labels, torch.Tensor) and centers.device == self.device
                     and labels.device == self.device and centers.dtype == torch.float32 and labels.dtype == torch.int32
                     and centers.is_contiguous() and labels.is_contiguous())
@@ -457,9 +473,7 @@ class Engine:
         assert centers.shape == (g, n, 3), "centers must be [G, N, 3]"
         if (order is None and auto_order and resident and not debug and g > self.num_cus and n <= MAX_NODES and k <= n
                 and not self.any_shape):
-            order, cap = self._cached_order(centers, labels, k)
-            if node_cap == 0 and 0 < cap < n:
-                node_cap = cap
+            order = self._cached_order(centers, labels, k)[0]
         pooled = torch.empty(g, self.pw, dtype=torch.float32, device=self.device)
         att = torch.empty(g, n, dtype=torch.float32, device=self.device) if (want_att or debug) else None
         emb = torch.empty(g, n, self.pw, dtype=torch.float32, device=self.device) if (want_emb or debug) else None
@@ -760,10 +774,11 @@ class Engine:
         rc = self.lib.sgpr_f1_max(self._h, _ptr(score), r, m, score.stride(0), int(row0), _ptr(pose_xz), float(d_pos),
                                   float(d_neg), _ptr(gt), m, _ptr(res), _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
-        # (the 64 bytes land in a pinned buffer of this engine: a pageable copy is staged by the runtime)
-        host = getattr(self, "_f1_host", None)
+        # (the 64 bytes land in a pinned buffer of this engine and thread: a pageable copy is staged by the runtime, and a
+        #  buffer shared by the threads of one engine let one thread's copy overwrite another's result before it was read)
+        host = getattr(self._host_bufs, "f1", None)
         if host is None:
-            host = self._f1_host = torch.empty(8, dtype=torch.float64).pin_memory()
+            host = self._host_bufs.f1 = torch.empty(8, dtype=torch.float64).pin_memory()
         host.copy_(res, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         return host.numpy().copy()

@@ -388,7 +388,7 @@ def test_plain_embed_hands_oversize_graphs_on(eng):
     oc, ol = torch.from_numpy(other_c).cuda(), torch.from_numpy(other_l).cuda()
     assert torch.equal(eng.embed(oc, ol, 10)[0], eng.embed(other_c, other_l, 10)[0])
     torch.cuda.synchronize()
-    assert torch.equal(eng.embed(oc, ol, 10)[0], eng.embed(other_c, other_l, 10)[0])               # (now with its own node_cap)
+    assert torch.equal(eng.embed(oc, ol, 10)[0], eng.embed(other_c, other_l, 10)[0])               # (a hit: its own order)
     eng.check_status()
     # a promise above 64 slots: two tiers as well (the small graphs on the 64-row layout, the others on the instance sized
     # for the promise) - same bits; broken: loud
