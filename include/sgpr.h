@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define SGPR_ABI_VERSION 10
+#define SGPR_ABI_VERSION 11
 
 enum {
     SGPR_OK = 0,
@@ -395,6 +395,42 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
                     int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity,
                     int64_t* d_row_ptr, unsigned long long* d_count,
                     void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Whole-sequence evaluation without the R x M matrix: sgpr_pair_positives and sgpr_pair_threshold_counts on the
+ * rectangle d_pooled_rows [R] x d_pooled_cols [M] that sgpr_score_all_pairs would write, scored as they go and never
+ * stored.  Ground truth arguments (d_pose_xz / d_pos / d_neg or d_gt [R][ldg], row0) and outputs are exactly those of the
+ * matrix versions.
+ * - sgpr_score_positives: the same multiset of positive scores as sgpr_pair_positives on that matrix, bit for bit
+ *   (unordered, the first `capacity` of them written), and the same d_count[0..1].
+ * - sgpr_score_threshold_counts: d_out[0..T+2] equal to sgpr_pair_threshold_counts' on that matrix (bucket counts, the
+ *   skipped negative / NaN count, the rank sum).  T <= SGPR_SCORE_COUNT_MAX_THRESHOLDS (2047: the threshold tree,
+ *   counters and ranking table of a workgroup live in 32 KB of LDS beside the scoring tail); a larger T is
+ *   SGPR_E_INVALID.
+ * - Checked before the device is touched (SGPR_E_INVALID): a NULL handle, output, ground truth or pooled vector (R, M >
+ *   0), R or M < 0, row0 + R beyond an int, T out of range, a ranking without thresholds / groups / d_at_least, capacity
+ *   < 0 or > 0 with a NULL d_out.  A workspace below the *_workspace_bytes query is SGPR_E_WORKSPACE.  Any workspace
+ *   contents give the same result.  Asynchronous on `stream`; the caller's device is restored.
+ * - Production handle: fused epilogues of the all-pairs tail.  With poses, a 16 x 256 work item whose row and column
+ *   pose boxes are farther apart than d_pos is not scored by the positives pass, and one farther than max(d_pos, d_neg)
+ *   is counted without per-pair float64 arithmetic.  Counting is per workgroup in 32-bit LDS counters, one slab per
+ *   workgroup, folded by a small kernel; rows run in blocks of at most 131 072 and of fewer than 2^20 work items per
+ *   workgroup, so no counter can overflow and any int R, M is supported (R * M < 2^62).  The workspace grows with
+ *   R + M, T and the grid, never with R * M.
+ * - Wide-range (debug bit 13, out-of-range weights) and any-shape handles score row blocks of at most 64 MB with their
+ *   own tail and run the matrix kernels on each block, row0 advancing; the blocks' counts are summed on the device. */
+#define SGPR_SCORE_COUNT_MAX_THRESHOLDS 2047
+size_t sgpr_score_positives_workspace_bytes(const sgpr_handle* h, int R, int M);
+int sgpr_score_positives(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int row0, const double* d_pose_xz, double d_pos, double d_neg, const signed char* d_gt,
+                         int64_t ldg, float* d_out, int64_t capacity, unsigned long long* d_count,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
+size_t sgpr_score_threshold_counts_workspace_bytes(const sgpr_handle* h, int R, int M, int T);
+int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
+                                int M, int row0, const double* d_pose_xz, double d_pos, double d_neg,
+                                const signed char* d_gt, int64_t ldg, const float* d_thresholds, int T,
+                                const sgpr_rank_group* d_rank, int groups_per_threshold,
+                                const unsigned long long* d_at_least, unsigned long long* d_out,
+                                void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* LDS bytes per workgroup the embed kernel uses for (N, k) on this handle; 0 if unsupported. */
 size_t sgpr_embed_lds_bytes(const sgpr_handle* h, int N, int k);

@@ -14,7 +14,8 @@ Every score depends on its two graphs only, so the matrix is bit-identical for a
 world size.
 
 Consumers that never move the matrix: `pr_roc` / `f1_max` (eval_batch.py:48-49, 69-87: the positives'
-scores all-gathered, per-rank counts of the negatives summed with one small all_reduce per pass) and `loop_closures` (best matches per query row).
+scores all-gathered, per-rank counts of the negatives summed with one small all_reduce per pass; `pr_roc_pooled` the same
+without any matrix) and `loop_closures` (best matches per query row).
 """
 import torch
 import torch.distributed as dist
@@ -264,12 +265,13 @@ class AllPairsScorer:
                 q.wait()
         return None
 
-    def pr_roc(self, block, poses, p_thresh=3.0, n_thresh=20.0, fns=None, want_auc=True):
+    def pr_roc(self, block, poses, p_thresh=3.0, n_thresh=20.0, fns=None, want_auc=True, max_thresholds=None):
         """(F1-max of eval_batch.py:85-87, ROC area of eval_batch.py:48-49) over this job's matrix WITHOUT gathering it:
         `block` is this rank's row block (score_rows), ground truth comes from the poses ([M,12] KITTI rows or [M,2]
         x/z).  Every rank returns the same values: the scores of the positive pairs are all-gathered (they are few),
         the per-threshold counts of the negatives all-reduced (sg_pr_amd/metrics.py:pr_roc_from_counts).
-        fns(block, row0, pose_xz) -> (positive scores of the block, count_fn) overrides the engine (CPU tests)."""
+        fns(block, row0, pose_xz) -> (positive scores of the block, count_fn) overrides the engine (CPU tests).
+        max_thresholds: the counting function's threshold budget per pass (default metrics.MAX_THRESHOLDS)."""
         import numpy as np
         from . import metrics
         world, rank = self._world()
@@ -314,8 +316,31 @@ class AllPairsScorer:
             elif bad:
                 raise err_c
             return counts, rank_sum
-        f1, auc, _ = metrics.pr_roc_from_counts(pos, count_fn, want_auc=want_auc)
+        f1, auc, _ = metrics.pr_roc_from_counts(pos, count_fn, want_auc=want_auc,
+                                                max_thresholds=max_thresholds or metrics.MAX_THRESHOLDS)
         return f1, auc
+
+    def pr_roc_pooled(self, centers, labels, poses, p_thresh=3.0, n_thresh=20.0, want_auc=True, local_pooled=None,
+                      engine=None):
+        """pr_roc of the whole set without any score matrix: every rank embeds its shard, the pooled vectors are
+        all-gathered (pooled_all) and each rank scores and counts its rows [lo, hi) as it goes (metrics._pooled_fns,
+        row0 = lo); the positives' scores are all-gathered and the counts all-reduced by pr_roc's collectives, with its
+        rule that a rank-local error is agreed on first.  engine: the producer of score_positives /
+        score_threshold_counts (default: the model's engine).  -> (F1-max, ROC area), the same on every rank."""
+        from . import metrics
+        eng = engine or self._engine
+        if eng is None:
+            raise ValueError("AllPairsScorer.pr_roc_pooled needs a model or an engine")
+        pooled = self.pooled_all(centers, labels, local=local_pooled)
+        world, rank = self._world()
+        lo, hi = shard_bounds(pooled.shape[0], world, rank)
+        rows = pooled[lo:hi].contiguous()
+
+        def fns(block, row0, xz):
+            return metrics._pooled_fns(eng, rows, pooled, xz.to(pooled.device), p_thresh, n_thresh, None, row0,
+                                       distinct=False, to_host=False)
+        return self.pr_roc(rows, poses, p_thresh, n_thresh, fns=fns, want_auc=want_auc,
+                           max_thresholds=getattr(eng, "MAX_POOLED_THRESHOLDS", metrics.MAX_THRESHOLDS))
 
     def f1_max(self, block, poses, p_thresh=3.0, n_thresh=20.0, fns=None):
         """F1-max of pr_roc alone (no ranking of the negatives)."""

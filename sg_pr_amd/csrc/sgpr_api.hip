@@ -1338,6 +1338,147 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
                              d_rows, d_cols, d_values, capacity, rp, 0, d_count, 0, cnt, h->d_status, s);
 }
 
+// ---- sgpr_score_positives / sgpr_score_threshold_counts: the fused evaluation epilogues on the production handle; the
+//      other handles score bounded row blocks with their own tail and run the matrix kernels on each block, row0
+//      advancing, the blocks' results added up on the device
+static bool eval_args_ok(const char* fn, const sgpr_handle* h, const float* rows, int R, const float* cols, int M,
+                         int row0, const double* pose, const signed char* gt, int64_t ldg) {
+    if (!h || R < 0 || M < 0 || (R > 0 && M > 0 && (!rows || !cols)) || (!pose && !gt) || (gt && !pose && ldg < M)) {
+        set_error(std::string(fn) + ": NULL argument, negative count, no ground truth or ldg below M");
+        return false;
+    }
+    if ((int64_t)row0 + R > 0x7fffffffLL) {
+        set_error(std::string(fn) + ": row0 + R must fit an int");
+        return false;
+    }
+    return true;
+}
+
+static PairTruth eval_truth(int row0, const double* pose, double d_pos, double d_neg, const signed char* gt, int64_t ldg) {
+    PairTruth t;
+    memset(&t, 0, sizeof(t));
+    t.row0 = row0;
+    t.pose = pose;
+    t.d_pos = d_pos;
+    t.d_neg = d_neg;
+    t.gt = pose ? nullptr : gt;
+    t.ldg = ldg;
+    return t;
+}
+
+// chunked path layout: score block [rb][M] | (counts: the block's d_out [T + 3] u64 | its counting slabs) | the block's
+// all-pairs workspace
+static size_t eval_chunk_head(const sgpr_handle* h, int R, int M, int T) {
+    size_t b = a256((size_t)topk_block_rows(R, M) * M * sizeof(float));
+    if (T >= 0) b += a256((size_t)(T + 3) * 8) + a256(sgpr_pair_threshold_counts_workspace_bytes(h, T));
+    return b;
+}
+
+size_t sgpr_score_positives_workspace_bytes(const sgpr_handle* h, int R, int M) {
+    if (!h || R < 0 || M < 0 || R == 0 || M == 0) return 0;
+    if (topk_fused(h)) return score_eval_ws_bytes(h, R, M, -1);
+    return eval_chunk_head(h, R, M, -1) + sgpr_score_all_pairs_workspace_bytes(h, topk_block_rows(R, M), M);
+}
+
+size_t sgpr_score_threshold_counts_workspace_bytes(const sgpr_handle* h, int R, int M, int T) {
+    if (!h || R < 0 || M < 0 || T < 0 || T > SGPR_SCORE_COUNT_MAX_THRESHOLDS || R == 0 || M == 0) return 0;
+    if (topk_fused(h)) return score_eval_ws_bytes(h, R, M, T);
+    return eval_chunk_head(h, R, M, T) + sgpr_score_all_pairs_workspace_bytes(h, topk_block_rows(R, M), M);
+}
+
+int sgpr_score_positives(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int row0, const double* d_pose_xz, double d_pos, double d_neg, const signed char* d_gt,
+                         int64_t ldg, float* d_out, int64_t capacity, unsigned long long* d_count,
+                         void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!eval_args_ok("sgpr_score_positives", h, d_pooled_rows, R, d_pooled_cols, M, row0, d_pose_xz, d_gt, ldg))
+        return SGPR_E_INVALID;
+    if (!d_count || capacity < 0 || (capacity > 0 && !d_out)) {
+        set_error("sgpr_score_positives: NULL count buffer or capacity without an output buffer");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = sgpr_score_positives_workspace_bytes(h, R, M);
+    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
+        set_error("sgpr_score_positives: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
+    float* out = capacity > 0 ? d_out : nullptr;
+    if ((int64_t)R * M == 0 || topk_fused(h))
+        return launch_score_eval(h, d_pooled_rows, R, d_pooled_cols, M, truth, out, capacity, d_count, nullptr, -1, nullptr,
+                                 0, nullptr, nullptr, d_workspace, s);
+    hipError_t e = hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return hip_fail(e, "sgpr_score_positives: memset");
+    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
+    float* block = static_cast<float*>(d_workspace);
+    unsigned char* ws = static_cast<unsigned char*>(d_workspace) + eval_chunk_head(h, R, M, -1);
+    const size_t ws_bytes = workspace_bytes - eval_chunk_head(h, R, M, -1);
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = std::min(rb, R - r0);
+        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
+        if (rc != SGPR_OK) return rc;
+        PairTruth tb = truth;
+        tb.row0 = row0 + r0;
+        if (tb.gt) tb.gt += (int64_t)r0 * ldg;
+        rc = launch_pair_positives_more(h, block, n, M, M, tb, out, capacity, d_count, s);
+        if (rc != SGPR_OK) return rc;
+    }
+    return SGPR_OK;
+}
+
+int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
+                                int M, int row0, const double* d_pose_xz, double d_pos, double d_neg,
+                                const signed char* d_gt, int64_t ldg, const float* d_thresholds, int T,
+                                const sgpr_rank_group* d_rank, int groups_per_threshold,
+                                const unsigned long long* d_at_least, unsigned long long* d_out,
+                                void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!eval_args_ok("sgpr_score_threshold_counts", h, d_pooled_rows, R, d_pooled_cols, M, row0, d_pose_xz, d_gt, ldg))
+        return SGPR_E_INVALID;
+    if (!d_out || T < 0 || T > SGPR_SCORE_COUNT_MAX_THRESHOLDS || (T > 0 && !d_thresholds)) {
+        set_error("sgpr_score_threshold_counts: 0.." + std::to_string(SGPR_SCORE_COUNT_MAX_THRESHOLDS) +
+                  " thresholds and an output buffer");
+        return SGPR_E_INVALID;
+    }
+    if (d_rank && (T < 1 || groups_per_threshold < 1 || !d_at_least)) {
+        set_error("sgpr_score_threshold_counts: the ranking needs thresholds, >= 1 value group per threshold and the pair counts");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = sgpr_score_threshold_counts_workspace_bytes(h, R, M, T);
+    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
+        set_error("sgpr_score_threshold_counts: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
+    if ((int64_t)R * M == 0 || topk_fused(h))
+        return launch_score_eval(h, d_pooled_rows, R, d_pooled_cols, M, truth, nullptr, 0, nullptr, d_thresholds, T, d_rank,
+                                 groups_per_threshold, d_at_least, d_out, d_workspace, s);
+    hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return hip_fail(e, "sgpr_score_threshold_counts: memset");
+    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
+    unsigned char* base = static_cast<unsigned char*>(d_workspace);
+    float* block = reinterpret_cast<float*>(base);
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(base + a256((size_t)rb * M * sizeof(float)));
+    unsigned char* slabs = reinterpret_cast<unsigned char*>(part) + a256((size_t)(T + 3) * 8);
+    const size_t slab_bytes = sgpr_pair_threshold_counts_workspace_bytes(h, T);
+    unsigned char* ws = base + eval_chunk_head(h, R, M, T);
+    const size_t ws_bytes = workspace_bytes - eval_chunk_head(h, R, M, T);
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = std::min(rb, R - r0);
+        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
+        if (rc != SGPR_OK) return rc;
+        rc = sgpr_pair_threshold_counts(h, block, n, M, M, row0 + r0, d_pose_xz, d_pos, d_neg,
+                                        truth.gt ? truth.gt + (int64_t)r0 * ldg : nullptr, ldg, d_thresholds, T, d_rank,
+                                        groups_per_threshold, d_at_least, part, slabs, slab_bytes, stream);
+        if (rc != SGPR_OK) return rc;
+        rc = launch_eval_add(d_out, part, T + 3, s);
+        if (rc != SGPR_OK) return rc;
+    }
+    return SGPR_OK;
+}
+
 size_t sgpr_score_all_pairs_multi_workspace_bytes(const sgpr_handle* h, int n_jobs, const sgpr_pairs_job* jobs) {
     if (check_jobs(h, n_jobs, jobs) != SGPR_OK) return 0;
     size_t any = 0;

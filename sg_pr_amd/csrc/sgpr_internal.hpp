@@ -234,6 +234,34 @@ struct EmbedArgs {
     int skip;                   // debug/ablation only (sgpr_debug_set_profile_buffer's companion): phases to skip
 };
 
+// (sgpr_metrics.hip's matrix consumers and the fused evaluation epilogues of sgpr_score.hip label pairs alike)
+// how a pair (row r of the rectangle, column c) is labelled
+struct PairTruth {
+    int row0;                 // global index of row 0 (rows are a shard of the square matrix)
+    const double* pose;       // [>= row0 + R and >= M][2] planar pose (x, z) or NULL; float64 like the reference
+    double d_pos, d_neg;      // positive if distance <= d_pos, negative if >= d_neg, ignored in between
+    const signed char* gt;    // explicit labels [R][ldg]: 1 / 0 / negative = ignore (used when pose == NULL)
+    int64_t ldg;
+};
+
+// 1 positive, 0 negative, -1 ignored
+__device__ __forceinline__ int classify_pair(const PairTruth& t, int r, int c, double px, double pz, double lo2, double hi2) {
+    if (t.pose) {
+        // utils.py:36 in float64, operation by operation (no fused multiply-add)
+        const double dx = px - t.pose[2 * c], dz = pz - t.pose[2 * c + 1];
+        const double s2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dz, dz));
+        // sqrt is monotone and correctly rounded: away from the two thresholds the squared distance decides; only
+        // within a relative 1e-12 of them is the reference's `sqrt(...) <= t` evaluated literally
+        if (s2 < lo2 * (1.0 - 1e-12)) return 1;
+        if (s2 > lo2 * (1.0 + 1e-12) && s2 < hi2 * (1.0 - 1e-12)) return -1;
+        if (s2 > hi2 * (1.0 + 1e-12)) return 0;
+        const double d = sqrt(s2);
+        return d <= t.d_pos ? 1 : (d >= t.d_neg ? 0 : -1);
+    }
+    const int g = t.gt[(int64_t)r * t.ldg + c];
+    return g < 0 ? -1 : (g != 0);
+}
+
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
 
@@ -264,6 +292,17 @@ int launch_score_above(const sgpr_handle* h, const float* rows, int R, const flo
 int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
                       int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals, int64_t cap, int64_t* row_ptr,
                       int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status, hipStream_t stream);
+// the fused evaluation epilogues of the all-pairs tail (production handle): T >= 0 the threshold counts (count == NULL,
+// d_out [T + 3]), T < 0 the positives (out [cap], count [2]); the chunked path of the other handles adds block counts up
+size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T);
+int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const PairTruth& truth,
+                      float* out, int64_t cap, unsigned long long* count, const float* thr, int T,
+                      const sgpr_rank_group* rank, int gpt, const unsigned long long* at_least, unsigned long long* d_out,
+                      void* ws, hipStream_t stream);
+int launch_eval_add(unsigned long long* out, const unsigned long long* in, int n, hipStream_t stream);
+// sgpr_pair_positives' kernel without clearing d_count: the appends of a row block continue the list (sgpr_metrics.hip)
+int launch_pair_positives_more(const sgpr_handle* h, const float* score, int R, int M, int64_t ld, const PairTruth& truth,
+                               float* out, int64_t cap, unsigned long long* count, hipStream_t stream);
 size_t score_pair_list_ws_bytes(int NR, int M);
 int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float* cols, int M, const int32_t* plan,
                            int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream, bool exact = false);

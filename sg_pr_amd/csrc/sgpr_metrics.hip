@@ -25,33 +25,6 @@ namespace sgpr {
 constexpr int PC_THREADS = 1024;
 constexpr int PC_MAX_THRESHOLDS = 8191;   // + at least one +inf pad = 8192 floats of LDS, 8192 counters beside them
 
-// how a pair (row r of the rectangle, column c) is labelled
-struct PairTruth {
-    int row0;                 // global index of row 0 (rows are a shard of the square matrix)
-    const double* pose;       // [>= row0 + R and >= M][2] planar pose (x, z) or NULL; float64 like the reference
-    double d_pos, d_neg;      // positive if distance <= d_pos, negative if >= d_neg, ignored in between
-    const signed char* gt;    // explicit labels [R][ldg]: 1 / 0 / negative = ignore (used when pose == NULL)
-    int64_t ldg;
-};
-
-// 1 positive, 0 negative, -1 ignored
-__device__ __forceinline__ int classify_pair(const PairTruth& t, int r, int c, double px, double pz, double lo2, double hi2) {
-    if (t.pose) {
-        // utils.py:36 in float64, operation by operation (no fused multiply-add)
-        const double dx = px - t.pose[2 * c], dz = pz - t.pose[2 * c + 1];
-        const double s2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dz, dz));
-        // sqrt is monotone and correctly rounded: away from the two thresholds the squared distance decides; only
-        // within a relative 1e-12 of them is the reference's `sqrt(...) <= t` evaluated literally
-        if (s2 < lo2 * (1.0 - 1e-12)) return 1;
-        if (s2 > lo2 * (1.0 + 1e-12) && s2 < hi2 * (1.0 - 1e-12)) return -1;
-        if (s2 > hi2 * (1.0 + 1e-12)) return 0;
-        const double d = sqrt(s2);
-        return d <= t.d_pos ? 1 : (d >= t.d_neg ? 0 : -1);
-    }
-    const int g = t.gt[(int64_t)r * t.ldg + c];
-    return g < 0 ? -1 : (g != 0);
-}
-
 struct PairScan {
     const float* score;
     int R, M;
@@ -1629,6 +1602,18 @@ int sgpr_pair_positives(const sgpr_handle* h, const float* d_score, int R, int M
     if (e != hipSuccess) return hip_fail(e, "pair_positives_kernel launch");
     return SGPR_OK;
 }
+
+namespace sgpr {
+int launch_pair_positives_more(const sgpr_handle* h, const float* score, int R, int M, int64_t ld, const PairTruth& truth,
+                               float* out, int64_t cap, unsigned long long* count, hipStream_t stream) {
+    if ((int64_t)R * M == 0) return SGPR_OK;
+    const PairScan sc = make_scan(score, R, M, ld, truth.row0, truth.pose, truth.d_pos, truth.d_neg, truth.gt, truth.ldg);
+    hipLaunchKernelGGL(pair_positives_kernel, dim3(h->num_cus * 8), dim3(256), 0, stream, sc, cap > 0 ? out : nullptr,
+                       (long long)cap, count);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "pair_positives_kernel launch");
+}
+}  // namespace sgpr
 
 static int slab_words(int T) { return ((T + 2) & ~1) + 4; }
 

@@ -838,16 +838,190 @@ __device__ __forceinline__ long long ab_start(const AboveArgs& a, int rg, int nc
     return s;
 }
 
+// ------------------------------------------------------------------ fused evaluation epilogues (sgpr_score_positives,
+// sgpr_score_threshold_counts): sgpr_pair_positives / sgpr_pair_threshold_counts on the scores as the tail makes them.
+//   TK_POS  every pair is labelled (classify_pair: float64 poses, or the explicit labels); the scores of the positive
+//           ones are appended to the output list (one ballot prefix and one global atomic per wave and super-block that
+//           holds any), positives with a negative / NaN score are counted instead.
+//   TK_CNT  every negative pair descends the threshold tree in LDS (breadth-first, padded with +inf), is optionally
+//           ranked among the positive values (the rank groups) and is counted with the wave-aggregated LDS atomics of
+//           pair_threshold_count_kernel into the workgroup's counters; a workgroup's counters go to its own slab at the
+//           end (no global atomic in the loop) and eval_fold_kernel adds the slabs up.
+// With poses, a work item is first tested as a whole: the bounding box of the wave's four row poses against the box of
+// the chunk's 256 column poses (eval_colbox_kernel), float64, the gap cut by 2^-40 of the largest magnitude and the
+// squared distance to clear the class boundary by 0.1 % - far beyond the roundings of utils.py:36's arithmetic.  An item
+// farther than d_pos from every row holds no positive (TK_POS skips it unscored); one farther than max(d_pos, d_neg)
+// holds negatives only (TK_CNT counts it without per-pair float64 arithmetic).  A NaN pose widens its box to the plane.
+constexpr int TK_POS = -2;
+constexpr int TK_CNT = -3;
+constexpr int EV_MAX_T = SGPR_SCORE_COUNT_MAX_THRESHOLDS;   // 2047: tree 8 KB + counters 8 KB + at_least 16 KB of LDS
+constexpr int EV_TP = EV_MAX_T + 1;                          // tree nodes (a power of two)
+
+struct EvalArgs {
+    PairTruth truth;
+    double lo2, hi2, cut_pos, cut_neg;   // squared class boundaries; squared gaps that rule a work item out
+    const double* cbox;                  // [ncc][4] column chunk boxes: x lo, x hi, z lo, z hi (pose mode)
+    // TK_POS
+    float* out;                          // [cap] positive scores, appended
+    long long cap;
+    unsigned long long* count;           // [0] positives with a usable score, [1] positives with a negative / NaN one
+    // TK_CNT (LDS)
+    const float* tree;                   // [Tp] breadth-first threshold tree
+    unsigned* cnt;                       // [T + 1]
+    const unsigned long long* at_least;  // [T] (ranking only)
+    const sgpr_rank_group* rank;         // [T * gpt] or nullptr
+    int T, lg, gpt;
+    // per lane: labelled pairs skipped for a negative / NaN score, the rank sum
+    unsigned nbad;
+    unsigned long long rank2;
+};
+
+__device__ __forceinline__ bool ev_bad(float s) { return __float_as_uint(s) > 0x7f800000u; }   // negative or NaN
+
+// the pose box of the wave's four rows (lane group g: row r) - wave-uniform after the shuffles
+__device__ __forceinline__ void ev_row_box(double px, double pz, double (&bx)[4]) {
+    const bool nan = px != px || pz != pz;
+    bx[0] = nan ? -INFINITY : px;
+    bx[1] = nan ? INFINITY : px;
+    bx[2] = nan ? -INFINITY : pz;
+    bx[3] = nan ? INFINITY : pz;
+#pragma unroll
+    for (int m = 16; m < 64; m <<= 1) {
+        bx[0] = fmin(bx[0], __shfl_xor(bx[0], m));
+        bx[1] = fmax(bx[1], __shfl_xor(bx[1], m));
+        bx[2] = fmin(bx[2], __shfl_xor(bx[2], m));
+        bx[3] = fmax(bx[3], __shfl_xor(bx[3], m));
+    }
+}
+
+// squared lower bound of every (row, column) distance of the two boxes, 0 when they may touch (NaN / inf: 0)
+__device__ __forceinline__ double ev_gap2(const double (&rb)[4], const double* __restrict__ cb) {
+    const double amax = fmax(fmax(fmax(fabs(rb[0]), fabs(rb[1])), fmax(fabs(rb[2]), fabs(rb[3]))),
+                             fmax(fmax(fabs(cb[0]), fabs(cb[1])), fmax(fabs(cb[2]), fabs(cb[3]))));
+    const double e = amax * 9.094947017729282e-13;          // 2^-40
+    const double gx = fmax(fmax(rb[0] - cb[1], cb[0] - rb[1]) - e, 0.0);
+    const double gz = fmax(fmax(rb[2] - cb[3], cb[2] - rb[3]) - e, 0.0);
+    const double g2 = gx * gx + gz * gz;
+    return g2 == g2 ? g2 : 0.0;
+}
+
+__device__ __forceinline__ int ev_class(const EvalArgs& e, int r, int c, double px, double pz) {
+    return classify_pair(e.truth, r, c, px, pz, e.lo2, e.hi2);
+}
+
+// TK_POS: row r's four pairs (r, c0 .. c0 + 3) of one super-block (live: r < R)
+__device__ __forceinline__ void ev_pos_push(EvalArgs& e, const float (&sc)[4], int c0, int M, bool live, int r,
+                                            double px, double pz) {
+    bool p[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int c = c0 + b;
+        p[b] = live && c < M && ev_class(e, r, c, px, pz) == 1;
+        if (p[b] && ev_bad(sc[b])) {
+            ++e.nbad;
+            p[b] = false;
+        }
+    }
+    unsigned long long m[4];
+    int tot = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        m[b] = __ballot(p[b]);
+        tot += __popcll(m[b]);
+    }
+    if (tot == 0) return;                                  // (wave-uniform)
+    const int lane = threadIdx.x & 63;
+    unsigned long long base = 0ull;
+    if (lane == 0) base = atomicAdd(&e.count[0], (unsigned long long)tot);
+    base = __shfl(base, 0);
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        if (p[b]) {
+            const long long idx = (long long)base + __popcll(m[b] & below);
+            if (idx < e.cap) e.out[idx] = sc[b];
+        }
+        base += __popcll(m[b]);
+    }
+}
+
+// TK_CNT: row r's four pairs of one super-block; allneg: the item's boxes are so far apart that every pair is negative
+__device__ __forceinline__ void ev_cnt_push(EvalArgs& e, const float (&s)[4], int c0, int M, bool live, int r, double px,
+                                            double pz, bool allneg) {
+    bool neg[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int c = c0 + b;
+        neg[b] = live && c < M && (allneg || ev_class(e, r, c, px, pz) == 0);
+        if (neg[b] && ev_bad(s[b])) {
+            ++e.nbad;
+            neg[b] = false;
+        }
+    }
+    if (!__any(neg[0] || neg[1] || neg[2] || neg[3])) return;
+    // four interleaved descents of the tree: right whenever the key is <= s; the leaf is the number of thresholds <= s
+    const int Tp = 1 << e.lg;
+    int bq[4] = {1, 1, 1, 1};
+    for (int lvl = 0; lvl < e.lg; ++lvl) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bq[q] = 2 * bq[q] + ((e.tree[bq[q]] <= s[q]) ? 1 : 0);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bq[q] = min(bq[q] - Tp, e.T);
+    if (e.rank) {
+        // pairs above s = pairs from the bucket's first value on - pairs of the bucket's values <= s
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            unsigned le = 0u, eq = 0u;
+            const sgpr_rank_group* g0 = e.rank + (size_t)max(bq[q] - 1, 0) * e.gpt;
+            for (int gi = 0; gi < e.gpt; ++gi) {
+                const uint4* rec = reinterpret_cast<const uint4*>(g0 + gi);
+                const float4 v0 = *reinterpret_cast<const float4*>(rec), v1 = *reinterpret_cast<const float4*>(rec + 1);
+                const uint4 m0 = rec[2], m1 = rec[3];
+                const float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+                const unsigned mm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    le += vv[i] <= s[q] ? mm[i] : 0u;
+                    eq += vv[i] == s[q] ? mm[i] : 0u;
+                }
+            }
+            // bucket 0: s lies below every positive value, all P = at_least[0] pairs rank above it
+            const unsigned long long gt_s = bq[q] > 0 ? e.at_least[bq[q] - 1] - le : e.at_least[0];
+            e.rank2 += neg[q] ? 2ull * gt_s + (bq[q] > 0 ? eq : 0u) : 0ull;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        // wave-aggregated counting (pair_threshold_count_kernel's rule): up to three rounds take the bucket of the first
+        // waiting lane with one atomic for every lane that shares it; whoever is left counts on its own
+        int idx = neg[q] ? bq[q] : -1;
+        unsigned long long todo = __ballot(idx >= 0);
+#pragma unroll 1
+        for (int round = 0; round < 3 && todo; ++round) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int lidx = __shfl(idx, leader);
+            const unsigned long long same = __ballot(idx == lidx);
+            if ((int)(threadIdx.x & 63) == leader) atomicAdd(&e.cnt[lidx], (unsigned)__popcll(same));
+            if (idx == lidx) idx = -1;
+            todo &= ~same;
+            if (__popcll(same) < 4) break;
+        }
+        if (idx >= 0) atomicAdd(&e.cnt[idx], 1u);
+    }
+}
+
 // the work items [it0, it1) of one R x M rectangle
 // TK = 0: the matrix is stored to score; TK > 0: the scores feed per-row top-TK lists (*tk), nothing is stored;
-// TK = TK_ABOVE: one pass of the range selection (*ab), nothing is stored
+// TK = TK_ABOVE: one pass of the range selection (*ab), nothing is stored; TK = TK_POS / TK_CNT: the evaluation
+// epilogues (*ev), nothing is stored
 template <int NI, int VAR, bool CL, int TK = 0>
 __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k, const bool fast, int R, int M,
                                          const unsigned short* __restrict__ Ab, const unsigned short* __restrict__ Cb,
                                          const float* __restrict__ ur, const float* __restrict__ prow,
                                          const float* __restrict__ pcol, float* __restrict__ score, int64_t ld,
                                          const int it0, const int it1, const TopkArgs* tk = nullptr,
-                                         const AboveArgs* ab = nullptr) {
+                                         const AboveArgs* ab = nullptr, EvalArgs* ev = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const f16x8 w1hi = k.w1hi, w1lo = k.w1lo;
@@ -869,6 +1043,8 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
     // range state (TK_ABOVE): this lane's hits of row rbase + g (pass 1), the row's running / first position (pass 2)
     int acnt = 0;
     long long apos = 0, astart = 0;
+    // evaluation state (TK_POS / TK_CNT): the pose of this lane's row rbase + g and the box of the wave's four rows
+    double epx = 0.0, epz = 0.0, erb[4] = {0.0, 0.0, 0.0, 0.0};
     for (int it = it0; it < it1; ++it) {
         const int rg = it / ncc, cc = it - rg * ncc;
         if (rg != cur_rg) {
@@ -898,6 +1074,14 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
             }
             cur_rg = rg;
             rbase = rg * AP_ROWS + wave * AP_RW;
+            if constexpr (TK == TK_POS || TK == TK_CNT) {
+                if (ev->truth.pose) {
+                    const int r = min(rbase + g, R - 1);
+                    epx = ev->truth.pose[2 * ((int64_t)ev->truth.row0 + r)];
+                    epz = ev->truth.pose[2 * ((int64_t)ev->truth.row0 + r) + 1];
+                    ev_row_box(epx, epz, erb);
+                }
+            }
 #pragma unroll
             for (int rr = 0; rr < AP_RW; ++rr) {
                 const int r = min(rbase + rr, R - 1);
@@ -926,6 +1110,17 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
             }
             if (ab->pass == 2 && !ab->flag[it]) continue;
         }
+        bool eneg = false;   // TK_CNT: every pair of this item (and wave) is a negative
+        if constexpr (TK == TK_POS || TK == TK_CNT) {
+            if (ev->truth.pose) {
+                const double g2 = ev_gap2(erb, ev->cbox + 4 * (size_t)cc);
+                if constexpr (TK == TK_POS) {
+                    if (g2 > ev->cut_pos) continue;        // no positive: not even scored
+                } else {
+                    eneg = g2 > ev->cut_neg;
+                }
+            }
+        }
         if (!fast) {      // inputs outside the f16 range: exact fp32 per-pair arithmetic
             if constexpr (TK == 0) {
                 slow_tile(w, prow, pcol, rbase, min(R, rbase + AP_RW), sb0 * AP_SB, min(M, sb1 * AP_SB), score, ld);
@@ -951,6 +1146,10 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                         }
                     if constexpr (TK == TK_ABOVE)
                         ab_push(*ab, sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, rbase + g, it, acnt, apos);
+                    else if constexpr (TK == TK_POS)
+                        ev_pos_push(*ev, sc, sb * AP_SB + 4 * l15, M, rbase + g < R, rbase + g, epx, epz);
+                    else if constexpr (TK == TK_CNT)
+                        ev_cnt_push(*ev, sc, sb * AP_SB + 4 * l15, M, rbase + g < R, rbase + g, epx, epz, eneg);
                     else
                         tk_push<TK>(sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, tv, tc, thv, thc, lsv, lsc);
                 }
@@ -1053,6 +1252,14 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
             }
             if constexpr (TK == TK_ABOVE) {
                 ab_push(*ab, sc, c0, M, ea, eb, r < R, r, it, acnt, apos);
+                continue;
+            }
+            if constexpr (TK == TK_POS) {
+                ev_pos_push(*ev, sc, c0, M, r < R, r, epx, epz);
+                continue;
+            }
+            if constexpr (TK == TK_CNT) {
+                ev_cnt_push(*ev, sc, c0, M, r < R, r, epx, epz, eneg);
                 continue;
             }
             if ((VAR & 2) && sc[0] + sc[1] + sc[2] + sc[3] != 12345.678f) continue;
@@ -1816,6 +2023,276 @@ int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "rows_above_kernel launch (pass 2)");
     return SGPR_OK;
+}
+
+// ------------------------------------------------------------------ fused evaluation (sgpr_score_positives / sgpr_score_threshold_counts)
+// score_topk_kernel's range question, work split and arithmetic with the TK_POS / TK_CNT epilogue.  Rows go in blocks:
+// at most AB_ROWS of them, and few enough that no workgroup sees 2^20 work items (4096 pairs each): its 32-bit LDS
+// counters cannot overflow.  workspace: column boxes [ncc][4] f64 | slabs [grid][slab words] u32 (counts only) | for one
+// row block: score_all_pairs' operands
+constexpr int64_t EV_ITEMS_PER_WG = (1 << 20) - 1;
+
+// the pose box of every 256-column chunk: one wave per chunk, four columns per lane (a NaN pose: the whole plane)
+__global__ __launch_bounds__(64) void eval_colbox_kernel(const double* __restrict__ pose, int M, double* __restrict__ box) {
+    const int cc = blockIdx.x, lane = threadIdx.x;
+    double xl = INFINITY, xh = -INFINITY, zl = INFINITY, zh = -INFINITY;
+    bool nan = false;
+    for (int c = cc * AP_COLS + lane; c < min(M, (cc + 1) * AP_COLS); c += 64) {
+        const double x = pose[2 * (size_t)c], z = pose[2 * (size_t)c + 1];
+        nan = nan || x != x || z != z;
+        xl = fmin(xl, x);
+        xh = fmax(xh, x);
+        zl = fmin(zl, z);
+        zh = fmax(zh, z);
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        xl = fmin(xl, __shfl_xor(xl, m));
+        xh = fmax(xh, __shfl_xor(xh, m));
+        zl = fmin(zl, __shfl_xor(zl, m));
+        zh = fmax(zh, __shfl_xor(zh, m));
+    }
+    if (__any(nan)) {
+        xl = zl = -INFINITY;
+        xh = zh = INFINITY;
+    }
+    if (lane == 0) {
+        box[4 * (size_t)cc] = xl;
+        box[4 * (size_t)cc + 1] = xh;
+        box[4 * (size_t)cc + 2] = zl;
+        box[4 * (size_t)cc + 3] = zh;
+    }
+}
+
+template <int OCC, int NI>
+__global__ __launch_bounds__(256, OCC) void score_positives_kernel(const DevWeights w, int R, int M,
+                                                                   const unsigned short* __restrict__ Ab,
+                                                                   const unsigned short* __restrict__ Cb,
+                                                                   const float* __restrict__ ur,
+                                                                   const float* __restrict__ rng, int nrng,
+                                                                   const float* __restrict__ prow,
+                                                                   const float* __restrict__ pcol, EvalArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
+    ap_range(rng, nrng, am, um, em, l1);
+    const int mode = ap_mode(am, um, em, l1);
+    const ApConsts k = ap_consts(w, l15, g);
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const unsigned nwg = gridDim.x;
+    const unsigned wg = (nwg & 7u) == 0u ? (blockIdx.x & 7u) * (nwg >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int it0 = (int)(items * wg / nwg), it1 = (int)(items * (wg + 1) / nwg);
+    a.nbad = 0u;
+    if (mode == 2)
+        ap_items<NI, 0, true, TK_POS>(w, k, true, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, nullptr, &a);
+    else
+        ap_items<NI, 0, false, TK_POS>(w, k, mode != 0, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, nullptr, &a);
+    unsigned nb = a.nbad;
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) nb += __shfl_xor(nb, m);
+    if (lane == 0 && nb) atomicAdd(&a.count[1], (unsigned long long)nb);
+}
+
+template <int OCC, int NI>
+__global__ __launch_bounds__(256, OCC) void score_counts_kernel(const DevWeights w, int R, int M,
+                                                                const unsigned short* __restrict__ Ab,
+                                                                const unsigned short* __restrict__ Cb,
+                                                                const float* __restrict__ ur,
+                                                                const float* __restrict__ rng, int nrng,
+                                                                const float* __restrict__ prow,
+                                                                const float* __restrict__ pcol, EvalArgs a,
+                                                                const float* __restrict__ thr,
+                                                                const unsigned long long* __restrict__ at_least,
+                                                                unsigned* __restrict__ slabs, int slab_words) {
+    __shared__ float tree[EV_TP];
+    __shared__ unsigned cnt[EV_TP];
+    __shared__ unsigned long long atl[EV_MAX_T];
+    __shared__ unsigned long long tail[2];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    // the thresholds as a complete binary search tree in breadth-first order (node 1 = root), padded with +inf
+    const int Tp = 1 << a.lg;
+    for (int node = tid; node < Tp; node += 256) {
+        float v = INFINITY;
+        if (node > 0) {
+            const int l = 31 - __clz(node), i = node - (1 << l);
+            const int idx = ((2 * i + 1) << (a.lg - 1 - l)) - 1;          // position of the node's key in sorted order
+            if (idx < a.T) v = thr[idx];
+        }
+        tree[node] = v;
+    }
+    for (int i = tid; i <= a.T; i += 256) cnt[i] = 0u;
+    if (a.rank)
+        for (int i = tid; i < a.T; i += 256) atl[i] = at_least[i];
+    if (tid < 2) tail[tid] = 0ull;
+    __syncthreads();
+    a.tree = tree;
+    a.cnt = cnt;
+    a.at_least = atl;
+    a.nbad = 0u;
+    a.rank2 = 0ull;
+    float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
+    ap_range(rng, nrng, am, um, em, l1);
+    const int mode = ap_mode(am, um, em, l1);
+    const ApConsts k = ap_consts(w, l15, g);
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const unsigned nwg = gridDim.x;
+    const unsigned wg = (nwg & 7u) == 0u ? (blockIdx.x & 7u) * (nwg >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int it0 = (int)(items * wg / nwg), it1 = (int)(items * (wg + 1) / nwg);
+    if (mode == 2)
+        ap_items<NI, 0, true, TK_CNT>(w, k, true, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, nullptr, &a);
+    else
+        ap_items<NI, 0, false, TK_CNT>(w, k, mode != 0, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, nullptr, &a);
+    unsigned long long r2 = a.rank2, nb = a.nbad;
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        r2 += __shfl_xor(r2, m);
+        nb += __shfl_xor(nb, m);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        if (nb) atomicAdd(&tail[0], nb);
+        if (r2) atomicAdd(&tail[1], r2);
+    }
+    __syncthreads();
+    unsigned* slab = slabs + (size_t)blockIdx.x * slab_words;
+    for (int i = tid; i <= a.T; i += 256) slab[i] = cnt[i];
+    if (tid < 2) reinterpret_cast<unsigned long long*>(slab + slab_words - 4)[tid] = tail[tid];
+}
+
+// out[i] (+)= the sum over the slabs of counter i (0..T), then the skipped count and the rank sum (u64 words of the slab
+// tail): 32 counters per workgroup, 32 threads per counter, 128-B coalesced reads.  accumulate: the row blocks after
+// the first add to what the blocks before them left in out.
+__global__ __launch_bounds__(1024) void eval_fold_kernel(const unsigned* __restrict__ slabs, int n_slabs, int slab_words,
+                                                         int T, unsigned long long* __restrict__ out, int accumulate) {
+    __shared__ unsigned long long part[32][33];
+    const int b = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const int i = blockIdx.x * 32 + b;
+    unsigned long long s = 0ull;
+    if (i <= T) {
+        for (int q = grp; q < n_slabs; q += 32) s += slabs[(size_t)q * slab_words + i];
+    } else if (i <= T + 2) {
+        for (int q = grp; q < n_slabs; q += 32)
+            s += reinterpret_cast<const unsigned long long*>(slabs + (size_t)q * slab_words + slab_words - 4)[i - T - 1];
+    }
+    part[grp][b] = s;
+    __syncthreads();
+    if (grp == 0 && i <= T + 2) {
+#pragma unroll
+        for (int q = 1; q < 32; ++q) s += part[q][b];
+        out[i] = accumulate ? out[i] + s : s;
+    }
+}
+
+static int eval_slab_words(int T) { return ((T + 2) & ~1) + 4; }
+
+static int eval_block_rows(const sgpr_handle* h, int R, int M) {
+    const int64_t ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t slots = (int64_t)h->num_cus * TK_OCC;
+    int64_t rg = AB_ROWS / AP_ROWS;
+    if (slots * EV_ITEMS_PER_WG / ncc < rg) rg = slots * EV_ITEMS_PER_WG / ncc;
+    if (0x7fffffffLL / ncc < rg) rg = 0x7fffffffLL / ncc;
+    rg = rg < 1 ? 1 : rg;
+    return (int)(rg * AP_ROWS < R ? rg * AP_ROWS : R);
+}
+
+size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T) {
+    if (R == 0 || M == 0) return 0;
+    const int rb = eval_block_rows(h, R, M);
+    const size_t ncc = (size_t)(M + AP_COLS - 1) / AP_COLS;
+    size_t b = align256(ncc * 4 * sizeof(double)) + align256(score_all_pairs_ws_bytes(rb, M));
+    if (T >= 0) b += align256((size_t)topk_grid(h, rb, M) * eval_slab_words(T) * sizeof(unsigned));
+    return b;
+}
+
+int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const PairTruth& truth,
+                      float* out, int64_t cap, unsigned long long* count, const float* thr, int T,
+                      const sgpr_rank_group* rank, int gpt, const unsigned long long* at_least, unsigned long long* d_out,
+                      void* ws, hipStream_t stream) {
+    const bool counts = count == nullptr;
+    hipError_t e = counts ? hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), stream)
+                          : hipMemsetAsync(count, 0, 2 * sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return hip_fail(e, "fused evaluation: clearing the outputs");
+    if ((int64_t)R * M == 0) return SGPR_OK;
+    const int rb = eval_block_rows(h, R, M), ncc = (M + AP_COLS - 1) / AP_COLS;
+    unsigned char* p = static_cast<unsigned char*>(ws);
+    double* cbox = reinterpret_cast<double*>(p);
+    p += align256((size_t)ncc * 4 * sizeof(double));
+    unsigned* slabs = nullptr;
+    const int sw = eval_slab_words(T < 0 ? 0 : T);
+    if (counts) {
+        slabs = reinterpret_cast<unsigned*>(p);
+        p += align256((size_t)topk_grid(h, rb, M) * sw * sizeof(unsigned));
+    }
+    if (truth.pose) {
+        hipLaunchKernelGGL(eval_colbox_kernel, dim3((unsigned)ncc), dim3(64), 0, stream, truth.pose, M, cbox);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "eval_colbox_kernel launch");
+    }
+    EvalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.truth = truth;
+    a.lo2 = truth.d_pos * truth.d_pos;
+    a.hi2 = truth.d_neg * truth.d_neg;
+    a.cut_pos = a.lo2 * 1.001;
+    a.cut_neg = (a.lo2 > a.hi2 ? a.lo2 : a.hi2) * 1.001;
+    a.cbox = cbox;
+    a.out = out;
+    a.cap = cap;
+    a.count = count;
+    a.rank = rank;
+    a.gpt = rank ? gpt : 0;
+    a.T = T < 0 ? 0 : T;
+    int lg = 0;
+    while ((1 << lg) <= a.T) ++lg;
+    a.lg = lg;
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = R - r0 < rb ? R - r0 : rb;
+        const int nrng = 2 * ap_prep_groups(n, M);
+        float* ur = reinterpret_cast<float*>(p);           // the operand layout of launch_score_all_pairs
+        float* rng = ur + (size_t)n * kT;
+        unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
+        unsigned short* Cb = Ab + (size_t)n * 2 * 64 * 8;
+        const float* brows = rows + (size_t)r0 * F;
+        a.truth.row0 = truth.row0 + r0;
+        a.truth.gt = truth.gt ? truth.gt + (int64_t)r0 * truth.ldg : nullptr;
+        hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, brows, n, cols, M, Ab, ur, rng, Cb);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+        const int64_t grid = topk_grid(h, n, M);
+        const dim3 gd((unsigned)grid), bd(256);
+        if (!counts) {
+            hipLaunchKernelGGL((score_positives_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, Ab, Cb, ur, rng, nrng,
+                               brows, cols, a);
+            e = hipGetLastError();
+            if (e != hipSuccess) return hip_fail(e, "score_positives_kernel launch");
+            continue;
+        }
+        hipLaunchKernelGGL((score_counts_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, Ab, Cb, ur, rng, nrng, brows,
+                           cols, a, thr, at_least, slabs, sw);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "score_counts_kernel launch");
+        hipLaunchKernelGGL(eval_fold_kernel, dim3((unsigned)((T + 3 + 31) / 32)), dim3(1024), 0, stream, slabs, (int)grid, sw,
+                           T, d_out, r0 > 0 ? 1 : 0);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "eval_fold_kernel launch");
+    }
+    return SGPR_OK;
+}
+
+// out[i] += in[i] (the row blocks of the chunked counting path)
+__global__ __launch_bounds__(256) void eval_add_kernel(unsigned long long* __restrict__ out,
+                                                       const unsigned long long* __restrict__ in, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] += in[i];
+}
+
+int launch_eval_add(unsigned long long* out, const unsigned long long* in, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(eval_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, out, in, n);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "eval_add_kernel launch");
 }
 
 // ------------------------------------------------------------------ grouped pair list (sgpr_score_pair_list)

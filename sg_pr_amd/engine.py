@@ -44,7 +44,8 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_f1_max_workspace_bytes", "sgpr_f1_max", "sgpr_topk_rows",
                "sgpr_score_topk_workspace_bytes", "sgpr_score_topk",
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
-               "sgpr_rows_above",
+               "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
+               "sgpr_score_threshold_counts_workspace_bytes", "sgpr_score_threshold_counts",
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
                "sgpr_attention_pool_any", "sgpr_ntn_any",
                "sgpr_cluster_workspace_bytes", "sgpr_cluster_scan", "sgpr_graph_edges",
@@ -180,6 +181,15 @@ def load_library():
     lib.sgpr_rows_above_workspace_bytes.argtypes = [vp, i32, i32]
     lib.sgpr_rows_above.restype = i32
     lib.sgpr_rows_above.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, f32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
+    lib.sgpr_score_positives_workspace_bytes.restype = sz
+    lib.sgpr_score_positives_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.sgpr_score_positives.restype = i32
+    lib.sgpr_score_positives.argtypes = [vp, vp, i32, vp, i32, i32, vp, dbl, dbl, vp, i64, vp, i64, vp, vp, sz, vp]
+    lib.sgpr_score_threshold_counts_workspace_bytes.restype = sz
+    lib.sgpr_score_threshold_counts_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.sgpr_score_threshold_counts.restype = i32
+    lib.sgpr_score_threshold_counts.argtypes = [vp, vp, i32, vp, i32, i32, vp, dbl, dbl, vp, i64, vp, i32, vp, i32, vp, vp,
+                                                vp, sz, vp]
     lib.sgpr_embed_lds_bytes.restype = sz
     lib.sgpr_embed_lds_bytes.argtypes = [vp, i32, i32]
     lib.sgpr_knn.restype = i32
@@ -734,30 +744,101 @@ class Engine:
         out = torch.empty(t + 3, dtype=torch.int64, device=self.device)
         ws_bytes = self.lib.sgpr_pair_threshold_counts_workspace_bytes(self._h, t)
         ws = self._ws(ws_bytes)
-        table, at_least, gpt = None, None, 0
-        if rank is not None:
-            vals, step, above = rank
-            vals = np.asarray(vals, dtype=np.float32)
-            above = np.asarray(above, dtype=np.int64)
-            u, step = int(vals.size), int(step)
-            assert above.size == u + 1 and t == -(-u // step) and int(above[0]) < 2 ** 32
-            gpt = -(-step // 8)
-            # values / pair counts of threshold q's bucket = entries q * step .. (q + 1) * step, padded to gpt * 8
-            pad = t * step - u
-            v2 = np.concatenate((vals, np.full(pad, np.inf, dtype=np.float32))).reshape(t, step)
-            m2 = np.concatenate((above[:-1] - above[1:], np.zeros(pad, dtype=np.int64))).reshape(t, step)
-            v3 = np.full((t, gpt * 8), np.inf, dtype=np.float32)
-            m3 = np.zeros((t, gpt * 8), dtype=np.uint32)
-            v3[:, :step] = v2
-            m3[:, :step] = m2
-            ent = np.zeros((t, gpt), dtype=RANK_GROUP)
-            ent["value"] = v3.reshape(t, gpt, 8)
-            ent["pairs"] = m3.reshape(t, gpt, 8)
-            table = torch.from_numpy(ent.view(np.uint8).reshape(-1)).to(self.device)
-            at_least = torch.from_numpy(np.ascontiguousarray(above[:-1][::step])).to(self.device)
+        table, at_least, gpt = self._rank_table(rank, t)
         rc = self.lib.sgpr_pair_threshold_counts(self._h, _ptr(score), r, m, score.stride(0), int(row0), _ptr(pose_xz),
                                                  float(d_pos), float(d_neg), _ptr(gt), m, _ptr(thr), t, _ptr(table), gpt,
                                                  _ptr(at_least), _ptr(out), _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        h = out.cpu().numpy()
+        rank_sum = int(h[t + 2].astype(np.uint64)) if rank is not None else None
+        return h[:t + 1].copy(), int(h[t + 1]), rank_sum
+
+    def _rank_table(self, rank, t):
+        """rank = (values, step, above) -> (sgpr_rank_group table, at_least, groups per threshold) on the device"""
+        if rank is None:
+            return None, None, 0
+        vals, step, above = rank
+        vals = np.asarray(vals, dtype=np.float32)
+        above = np.asarray(above, dtype=np.int64)
+        u, step = int(vals.size), int(step)
+        assert above.size == u + 1 and t == -(-u // step) and int(above[0]) < 2 ** 32
+        gpt = -(-step // 8)
+        # values / pair counts of threshold q's bucket = entries q * step .. (q + 1) * step, padded to gpt * 8
+        pad = t * step - u
+        v2 = np.concatenate((vals, np.full(pad, np.inf, dtype=np.float32))).reshape(t, step)
+        m2 = np.concatenate((above[:-1] - above[1:], np.zeros(pad, dtype=np.int64))).reshape(t, step)
+        v3 = np.full((t, gpt * 8), np.inf, dtype=np.float32)
+        m3 = np.zeros((t, gpt * 8), dtype=np.uint32)
+        v3[:, :step] = v2
+        m3[:, :step] = m2
+        ent = np.zeros((t, gpt), dtype=RANK_GROUP)
+        ent["value"] = v3.reshape(t, gpt, 8)
+        ent["pairs"] = m3.reshape(t, gpt, 8)
+        table = torch.from_numpy(ent.view(np.uint8).reshape(-1)).to(self.device)
+        at_least = torch.from_numpy(np.ascontiguousarray(above[:-1][::step])).to(self.device)
+        return table, at_least, gpt
+
+    # ------------------------------------------------------------------ the same consumers without the matrix
+    MAX_POOLED_THRESHOLDS = 2047     # SGPR_SCORE_COUNT_MAX_THRESHOLDS of include/sgpr.h
+
+    def _pooled_truth(self, r, m, row0, pose_xz, gt):
+        if pose_xz is not None:
+            pose_xz = self._dev(pose_xz, torch.float64, "pose_xz")
+            assert pose_xz.dim() == 2 and pose_xz.shape[1] == 2 and pose_xz.shape[0] >= max(m, row0 + r)
+            return pose_xz, None
+        if gt is not None:
+            gt = self._dev(gt, torch.int8, "gt")
+            assert gt.shape == (r, m)
+            return None, gt
+        raise ValueError("the pair consumers need poses or explicit labels")
+
+    def score_positives_workspace_bytes(self, r, m):
+        return int(self.lib.sgpr_score_positives_workspace_bytes(self._h, int(r), int(m)))
+
+    def score_threshold_counts_workspace_bytes(self, r, m, t):
+        return int(self.lib.sgpr_score_threshold_counts_workspace_bytes(self._h, int(r), int(m), int(t)))
+
+    def score_positives(self, pooled_rows, pooled_cols, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None):
+        """pair_positives on the rectangle pooled_rows x pooled_cols without forming it (sgpr_score_positives): the
+        scores of the positive pairs (float32 device tensor, unordered; bit-identical to score_all_pairs' entries) and
+        the number of positives skipped for a negative / NaN score."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        pose_xz, gt = self._pooled_truth(r, m, row0, pose_xz, gt)
+        ws_bytes = self.score_positives_workspace_bytes(r, m)
+        ws = self._ws(ws_bytes)
+        count = torch.empty(2, dtype=torch.int64, device=self.device)
+        cap = min(r * m, 1 << 20)
+        while True:
+            out = torch.empty(cap, dtype=torch.float32, device=self.device)
+            rc = self.lib.sgpr_score_positives(self._h, _ptr(rows), r, _ptr(cols), m, int(row0), _ptr(pose_xz),
+                                               float(d_pos), float(d_neg), _ptr(gt), m, _ptr(out) if cap else None, cap,
+                                               _ptr(count), _ptr(ws), ws_bytes, self._stream())
+            self._check(rc)
+            n, bad = (int(v) for v in count.tolist())
+            if n <= cap:
+                return out[:n], bad
+            cap = n
+
+    def score_threshold_counts(self, pooled_rows, pooled_cols, thresholds, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0,
+                               gt=None, rank=None):
+        """pair_threshold_counts on the rectangle pooled_rows x pooled_cols without forming it
+        (sgpr_score_threshold_counts): thresholds ascending float32, at most MAX_POOLED_THRESHOLDS.
+        Returns (counts int64 [T+1], skipped, rank_sum or None), equal to pair_threshold_counts' on the matrix."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        pose_xz, gt = self._pooled_truth(r, m, row0, pose_xz, gt)
+        thr = self._dev(torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float32)), torch.float32, "thresholds")
+        t = int(thr.numel())
+        out = torch.empty(t + 3, dtype=torch.int64, device=self.device)
+        ws_bytes = self.score_threshold_counts_workspace_bytes(r, m, t)
+        ws = self._ws(ws_bytes)
+        table, at_least, gpt = self._rank_table(rank, t)
+        rc = self.lib.sgpr_score_threshold_counts(self._h, _ptr(rows), r, _ptr(cols), m, int(row0), _ptr(pose_xz),
+                                                  float(d_pos), float(d_neg), _ptr(gt), m, _ptr(thr), t, _ptr(table), gpt,
+                                                  _ptr(at_least), _ptr(out), _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         h = out.cpu().numpy()
         rank_sum = int(h[t + 2].astype(np.uint64)) if rank is not None else None

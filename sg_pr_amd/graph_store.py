@@ -78,9 +78,11 @@ def pack_directory(graph_dir, node_num, number_of_labels=12, names=None):
     return PackedSequence(centers, labels, poses, names)
 
 
-def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=50, scorer=None):
+def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=50, scorer=None, keep_matrix=True):
     """Whole-sequence evaluation on the device.  Returns {"f1_max", "roc_auc", "closure_scores" [M,k], "closure_frames"
-    [M,k], "matrix" (device tensor: this rank's row block)}.  `scorer`: an AllPairsScorer for multi-GPU runs."""
+    [M,k], "matrix" (device tensor: this rank's row block)}.  `scorer`: an AllPairsScorer for multi-GPU runs.
+    keep_matrix=False never forms the matrix: F1-max and the area come from AllPairsScorer.pr_roc_pooled, the
+    closures from Engine.score_topk (the same values), and "matrix" is None."""
     from . import allpairs
     if scorer is None:
         scorer = allpairs.AllPairsScorer(model=model)
@@ -91,6 +93,8 @@ def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=
     order, cap = eng.size_order(seq.centers[lo:hi], seq.labels[lo:hi], k)
     scorer.embed_fn = lambda c, l: eng.embed(c, l, k, node_cap=cap, order=order)[0]     # noqa: E731
     pooled = scorer.pooled_all(seq.centers, seq.labels)
+    if not keep_matrix:
+        return _evaluate_pooled(model, seq, pooled, p_thresh, n_thresh, top_k, window, scorer)
     block = scorer.score_rows(pooled)
     err = None
     try:
@@ -103,14 +107,33 @@ def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=
     return {"f1_max": f1, "roc_auc": auc, "closure_scores": vals, "closure_frames": idx, "matrix": block}
 
 
+def _evaluate_pooled(model, seq, pooled, p_thresh, n_thresh, top_k, window, scorer):
+    from . import allpairs
+    world, rank = scorer._world()
+    lo, hi = allpairs.shard_bounds(len(seq), world, rank)
+    err = None
+    try:
+        model.engine().check_status()
+    except RuntimeError as e:
+        err = e
+    allpairs.agree_on_error(err, like=pooled, group=scorer.group)
+    f1, auc = scorer.pr_roc_pooled(seq.centers, seq.labels, seq.poses, p_thresh=p_thresh, n_thresh=n_thresh,
+                                   local_pooled=pooled[lo:hi], engine=model.engine())
+    vals, idx = model.loop_closures(pooled[lo:hi].contiguous(), pooled, k=top_k, window=window, row0=lo)
+    return {"f1_max": f1, "roc_auc": auc, "closure_scores": vals, "closure_frames": idx, "matrix": None}
+
+
 def main(argv=None):
     """python -m sg_pr_amd.graph_store config.yml   - all-pairs evaluation of every `eva_batch.sequences` entry:
     packs `<graph_pairs_dir>/<seq>/` once (cached as `<output_path>/<seq>_packed.npz`), writes
-    `<seq>_allpairs_F1_max.txt` and `<seq>_loop_closures.npy` (frame, best match, score)."""
+    `<seq>_allpairs_F1_max.txt` and `<seq>_loop_closures.npy` (frame, best match, score).
+    --no-matrix: the same outputs without ever forming the M x M score matrix (evaluate_all_pairs keep_matrix=False)."""
     import sys
     from .parser_sg import sgpr_args
     from .sg_net import SGTrainer
     argv = sys.argv[1:] if argv is None else argv
+    keep_matrix = "--no-matrix" not in argv
+    argv = [a for a in argv if a != "--no-matrix"]
     args = sgpr_args()
     args.load(argv[0] if argv else "./config/config.yml")
     trainer = SGTrainer(args, False)
@@ -125,7 +148,7 @@ def main(argv=None):
             seq = pack_directory(os.path.join(args.graph_pairs_dir, sequence), int(args.node_num),
                                  trainer.number_of_labels)
             seq.save(cache)
-        r = evaluate_all_pairs(trainer.model, seq, p_thresh=float(args.p_thresh))
+        r = evaluate_all_pairs(trainer.model, seq, p_thresh=float(args.p_thresh), keep_matrix=keep_matrix)
         with open(os.path.join(args.output_path, sequence + "_allpairs_F1_max.txt"), "w") as f:
             f.write(str(r["f1_max"]))
         m = len(seq)

@@ -205,6 +205,51 @@ def roc_auc_device(engine, score, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=
     return pr_roc_device(engine, score, pose_xz, p_thresh, n_thresh, gt, row0, refine=False)[1]
 
 
+def _pooled_fns(engine, pooled_rows, pooled_cols, pose_xz, p_thresh, n_thresh, gt, row0, distinct=True, to_host=True):
+    """_device_fns with the matrix-free producers (Engine.score_positives / score_threshold_counts): the pairs of
+    pooled_rows x pooled_cols are scored as they are counted and never stored."""
+    def count_fn(thresholds, rank):
+        counts, bad, rank_sum = engine.score_threshold_counts(pooled_rows, pooled_cols, thresholds, row0=row0,
+                                                              pose_xz=pose_xz, d_pos=p_thresh, d_neg=n_thresh, gt=gt,
+                                                              rank=rank)
+        if bad:
+            raise ValueError("%d scores are negative or NaN" % bad)
+        return counts, rank_sum
+    pos, bad = engine.score_positives(pooled_rows, pooled_cols, row0=row0, pose_xz=pose_xz, d_pos=p_thresh,
+                                      d_neg=n_thresh, gt=gt)
+    if bad:
+        raise ValueError("%d scores are negative or NaN" % bad)
+    if not distinct:
+        return (pos.cpu().numpy() if to_host else pos), count_fn
+    import torch
+    u, mult = torch.unique(pos, sorted=True, return_counts=True)
+    return (u.cpu().numpy(), mult.cpu().numpy().astype(np.int64)), count_fn
+
+
+def pr_roc_pooled(engine, pooled_rows, pooled_cols, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None, row0=0,
+                  want_auc=True, refine=True, max_thresholds=None):
+    """(F1-max, ROC area, counting passes) of the pairs pooled_rows x pooled_cols WITHOUT the score matrix: pr_roc_device
+    with producers that score the pairs as they count them.  The same counts reach the same host code, so F1 and the
+    area equal pr_roc_device's on the matrix exactly; a pass takes at most max_thresholds (default: the engine's
+    MAX_POOLED_THRESHOLDS) thresholds, so refining F1 may take more passes than on the matrix."""
+    if max_thresholds is None:
+        max_thresholds = getattr(engine, "MAX_POOLED_THRESHOLDS", MAX_THRESHOLDS)
+    distinct, count_fn = _pooled_fns(engine, pooled_rows, pooled_cols, pose_xz, p_thresh, n_thresh, gt, row0)
+    return pr_roc_from_counts(None, count_fn, want_auc=want_auc, max_thresholds=max_thresholds, distinct=distinct,
+                              refine=refine)
+
+
+def f1_max_pooled(engine, pooled_rows, pooled_cols, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None, row0=0):
+    """F1-max of the pairs pooled_rows x pooled_cols without the score matrix -> (f1_max, counting passes)."""
+    f1, _, passes = pr_roc_pooled(engine, pooled_rows, pooled_cols, pose_xz, p_thresh, n_thresh, gt, row0, want_auc=False)
+    return f1, passes
+
+
+def roc_auc_pooled(engine, pooled_rows, pooled_cols, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None, row0=0):
+    """ROC area of the pairs pooled_rows x pooled_cols without the score matrix: exact, one counting pass."""
+    return pr_roc_pooled(engine, pooled_rows, pooled_cols, pose_xz, p_thresh, n_thresh, gt, row0, refine=False)[1]
+
+
 def counts_of(score, gt):
     """numpy stand-ins for sgpr_pair_positives / sgpr_pair_threshold_counts (tests, small inputs): gt 1 / 0 / negative
     = ignored.  Returns (positive scores, count_fn)."""

@@ -159,6 +159,14 @@ class SG(torch.nn.Module):
         return self.engine().score_above(pooled_rows, pooled_cols, threshold, window=window, row0=row0, causal=causal,
                                          row_self=row_self, capacity=capacity)
 
+    def evaluate_pooled(self, pooled_rows, pooled_cols, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None, row0=0,
+                        want_auc=True):
+        """(F1-max, ROC area, counting passes) of the pairs pooled_rows x pooled_cols without forming the matrix
+        (metrics.pr_roc_pooled): ground truth from planar poses [.,2] or explicit int8 labels [R,M]."""
+        from . import metrics
+        return metrics.pr_roc_pooled(self.engine(), pooled_rows, pooled_cols, pose_xz=pose_xz, p_thresh=p_thresh,
+                                     n_thresh=n_thresh, gt=gt, row0=row0, want_auc=want_auc)
+
     def forward_packed(self, centers_1, labels_1, centers_2, labels_2, validate=True):
         """Faithful per-pair scoring of packed graphs: both sides embedded, then the tail.
         validate (default): synchronise and raise SgprError if the kernel saw a label outside [-1, L) (the reference
