@@ -438,16 +438,21 @@ size_t sgpr_embed_lds_bytes(const sgpr_handle* h, int N, int k);
 /* ---- stand-alone forms of the reference's building blocks (SURVEY.md 8b "signatures to keep") -------------------
  * Inside sgpr_embed / sgpr_forward_dense these run fused and never materialise their outputs; the entry points below
  * serve callers of the individual symbols.  They need no handle: a stand-alone module owns its own parameters, which
- * are passed as device pointers.
+ * are passed as device pointers.  Sizes are checked first; an empty batch (B = 0) is a valid call that touches nothing,
+ * and its pointers may be NULL (the data pointer of an empty torch tensor).
  *
  * sgpr_knn replaces dgcnn.knn (dgcnn.py:14-20): d_x [B,C,N] f32 -> d_idx [B,N,k] int64 (torch.topk's index type), the
  * k nearest candidates of every node under pd[i][j] = -|x_j|^2 + 2 x_i.x_j - |x_i|^2, best first; equal distances keep
  * the lower candidate index first (torch.topk's tie order is implementation-defined).  N <= SGPR_ANY_MAX_NODES, k <= N,
- * k <= SGPR_ANY_MAX_K (beyond SGPR_MAX_NODES / SGPR_MAX_K: one wave per row instead of the LDS-resident kernel). */
+ * k <= SGPR_ANY_MAX_K, any C (beyond SGPR_MAX_NODES / SGPR_MAX_K, or when the graph does not fit one workgroup's LDS:
+ * one wave per row instead of the LDS-resident kernel - the same keys and order, so the same lists).  A NaN distance
+ * (a NaN node) or -inf one (an overflowing node) ranks after every finite distance, NaN last; every row still holds
+ * k distinct indices. */
 int sgpr_knn(const float* d_x, int B, int C, int N, int k, int64_t* d_idx, void* stream);
 
 /* Replaces dgcnn.get_graph_feature (dgcnn.py:23-49) for given neighbour lists d_idx [B,N,k] (int64, from sgpr_knn or
- * the caller): d_out [B,2C,N,k] f32 = cat(x_j - x_i, x_i) in the reference's channel order (dgcnn.py:47). */
+ * the caller): d_out [B,2C,N,k] f32 = cat(x_j - x_i, x_i) in the reference's channel order (dgcnn.py:47).  An index
+ * outside [0, N) is clamped to it (a negative one reads node 0, one >= N node N-1): no read leaves the graph. */
 int sgpr_graph_feature(const float* d_x, const int64_t* d_idx, int B, int C, int N, int k, float* d_out, void* stream);
 
 /* Replaces AttentionModule.forward (layers_batch.py:28-39): d_weight [F3,F3] (attention.weight_matrix),

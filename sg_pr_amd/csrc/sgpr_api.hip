@@ -1638,8 +1638,8 @@ int sgpr_forward_dense(const sgpr_handle* h, const float* d_features_1, const fl
 }
 
 int sgpr_knn(const float* d_x, int B, int C, int N, int k, int64_t* d_idx, void* stream) {
-    if (!d_x || !d_idx || B < 0 || C < 1) {
-        set_error("sgpr_knn: NULL argument, negative batch or no channels");
+    if (B < 0 || C < 1) {
+        set_error("sgpr_knn: negative batch or no channels");
         return SGPR_E_INVALID;
     }
     if (N < 1 || N > SGPR_ANY_MAX_NODES) {
@@ -1650,13 +1650,17 @@ int sgpr_knn(const float* d_x, int B, int C, int N, int k, int64_t* d_idx, void*
         set_error("sgpr_knn: K " + std::to_string(k) + " outside [1, min(N, " + std::to_string(SGPR_ANY_MAX_K) + ")]");
         return SGPR_E_K;
     }
+    if (B > 0 && (!d_x || !d_idx)) {                            // an empty batch may come with NULL (torch's empty data_ptr)
+        set_error("sgpr_knn: NULL argument");
+        return SGPR_E_INVALID;
+    }
     if (N > SGPR_MAX_NODES || k > SGPR_MAX_K)                    // beyond the LDS-resident kernel: one wave per row
         return launch_knn_any(d_x, B, C, N, k, d_idx, static_cast<hipStream_t>(stream));
     return launch_knn(d_x, B, C, N, k, d_idx, static_cast<hipStream_t>(stream));
 }
 
 int sgpr_graph_feature(const float* d_x, const int64_t* d_idx, int B, int C, int N, int k, float* d_out, void* stream) {
-    if (!d_x || !d_idx || !d_out || B < 0 || C < 1 || N < 1 || k < 1) {
+    if (B < 0 || C < 1 || N < 1 || k < 1 || (B > 0 && (!d_x || !d_idx || !d_out))) {
         set_error("sgpr_graph_feature: NULL argument or non-positive size");
         return SGPR_E_INVALID;
     }
@@ -1665,21 +1669,25 @@ int sgpr_graph_feature(const float* d_x, const int64_t* d_idx, int B, int C, int
 
 int sgpr_attention_pool(const float* d_weight, const float* d_emb, int B, int N, float* d_rep, float* d_att,
                         void* stream) {
-    if (!d_weight || !d_emb || !d_rep || B < 0 || N < 1) {
-        set_error("sgpr_attention_pool: NULL argument, negative batch or no nodes");
+    if (B < 0 || N < 1) {
+        set_error("sgpr_attention_pool: negative batch or no nodes");
         return SGPR_E_INVALID;
     }
     if ((size_t)N * sizeof(float) > 48 * 1024) {
         set_error("sgpr_attention_pool: more than 12288 nodes per graph");
         return SGPR_E_NODES;
     }
+    if (B > 0 && (!d_weight || !d_emb || !d_rep)) {
+        set_error("sgpr_attention_pool: NULL argument");
+        return SGPR_E_INVALID;
+    }
     return launch_attention_pool(d_weight, d_emb, B, N, d_rep, d_att, static_cast<hipStream_t>(stream));
 }
 
 int sgpr_attention_pool_any(const float* d_weight, const float* d_emb, int B, int N, int F, float* d_rep, float* d_att,
                             void* stream) {
-    if (!d_weight || !d_emb || !d_rep || B < 0 || N < 1) {
-        set_error("sgpr_attention_pool_any: NULL argument, negative batch or no nodes");
+    if (B < 0 || N < 1) {
+        set_error("sgpr_attention_pool_any: negative batch or no nodes");
         return SGPR_E_INVALID;
     }
     if (F < 1 || F > SGPR_ANY_MAX_FILTERS_3) {
@@ -1687,13 +1695,17 @@ int sgpr_attention_pool_any(const float* d_weight, const float* d_emb, int B, in
                   std::to_string(SGPR_ANY_MAX_FILTERS_3) + "]");
         return SGPR_E_DIMS;
     }
+    if (B > 0 && (!d_weight || !d_emb || !d_rep)) {
+        set_error("sgpr_attention_pool_any: NULL argument");
+        return SGPR_E_INVALID;
+    }
     return launch_attention_any(d_weight, d_emb, B, N, F, d_rep, d_att, static_cast<hipStream_t>(stream));
 }
 
 int sgpr_ntn_any(const float* d_weight, const float* d_weight_block, const float* d_bias, const float* d_e1,
                  const float* d_e2, int64_t B, int F, int T, float* d_out, void* stream) {
-    if (!d_weight || !d_weight_block || !d_bias || !d_e1 || !d_e2 || !d_out || B < 0) {
-        set_error("sgpr_ntn_any: NULL argument or negative batch");
+    if (B < 0) {
+        set_error("sgpr_ntn_any: negative batch");
         return SGPR_E_INVALID;
     }
     if (F < 1 || F > SGPR_ANY_MAX_FILTERS_3 || T < 1 || T > SGPR_ANY_MAX_NEURONS) {
@@ -1701,12 +1713,16 @@ int sgpr_ntn_any(const float* d_weight, const float* d_weight_block, const float
                   std::to_string(SGPR_ANY_MAX_FILTERS_3) + "] / [1, " + std::to_string(SGPR_ANY_MAX_NEURONS) + "]");
         return SGPR_E_DIMS;
     }
+    if (B > 0 && (!d_weight || !d_weight_block || !d_bias || !d_e1 || !d_e2 || !d_out)) {
+        set_error("sgpr_ntn_any: NULL argument");
+        return SGPR_E_INVALID;
+    }
     return launch_ntn_any(d_weight, d_weight_block, d_bias, d_e1, d_e2, B, F, T, d_out, static_cast<hipStream_t>(stream));
 }
 
 int sgpr_ntn(const float* d_weight, const float* d_weight_block, const float* d_bias, const float* d_e1,
              const float* d_e2, int64_t B, float* d_out, void* stream) {
-    if (!d_weight || !d_weight_block || !d_bias || !d_e1 || !d_e2 || !d_out || B < 0) {
+    if (B < 0 || (B > 0 && (!d_weight || !d_weight_block || !d_bias || !d_e1 || !d_e2 || !d_out))) {
         set_error("sgpr_ntn: NULL argument or negative batch");
         return SGPR_E_INVALID;
     }

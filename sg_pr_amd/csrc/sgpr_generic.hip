@@ -638,44 +638,28 @@ __global__ __launch_bounds__(GEN_THREADS) void generic_knn_kernel(const float* _
     const int i = blockIdx.x * (GEN_THREADS / 64) + (threadIdx.x >> 6);
     if (i >= N) return;
     const float* xb = x + (size_t)b * C * N;
-    float xi2 = __fmul_rn(xb[i], xb[i]);
-    for (int c = 1; c < C; ++c) xi2 = __fadd_rn(xi2, __fmul_rn(xb[(size_t)c * N + i], xb[(size_t)c * N + i]));
-    float key[GEN_MAX_PER_LANE];
+    const float xi2 = knn_sq_norm(xb + i, C, N);
+    // total order (key, index) on the order-preserving image of the key (knn_rank): +inf keys (overflowing features) and
+    // NaN keys rank last but ARE ranked - every row gets k distinct indices, as knn_select_row and knn_kernel give
+    unsigned long long rank[GEN_MAX_PER_LANE];
 #pragma unroll
     for (int q = 0; q < GEN_MAX_PER_LANE; ++q) {
         const int j = lane + 64 * q;
-        key[q] = INFINITY;
+        rank[q] = ~0ull;
         if (j < N) {
-            float xj2 = __fmul_rn(xb[j], xb[j]);
             float dot = __fmul_rn(xb[i], xb[j]);
-            for (int c = 1; c < C; ++c) {
-                const float vi = xb[(size_t)c * N + i], vj = xb[(size_t)c * N + j];
-                xj2 = __fadd_rn(xj2, __fmul_rn(vj, vj));
-                dot = fmaf(vi, vj, dot);
-            }
-            key[q] = __fsub_rn(xi2, fmaf(2.f, dot, -xj2));
+            for (int c = 1; c < C; ++c) dot = fmaf(xb[(size_t)c * N + i], xb[(size_t)c * N + j], dot);
+            rank[q] = knn_rank(knn_key(xi2, knn_sq_norm(xb + j, C, N), dot), j);
         }
     }
-    // total order (key, index) on the order-preserving image of the key: +inf keys (overflowing features) and NaN keys rank
-    // last but ARE ranked - every row gets k distinct indices, as knn_select_row and the tuned kernel give
-    auto image = [](float f) {
-        if (f != f) return 0xffffffffu;                       // NaN after everything
-        f += 0.0f;
-        const unsigned u = __float_as_uint(f);
-        return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
-    };
-    unsigned okey[GEN_MAX_PER_LANE];
     unsigned taken = 0u;                                      // bit q: candidate lane + 64 q is in the list already
-#pragma unroll
-    for (int q = 0; q < GEN_MAX_PER_LANE; ++q) okey[q] = image(key[q]);
     long long* out = idx + ((size_t)b * N + i) * k;
     for (int m = 0; m < k; ++m) {
         unsigned long long best = ~0ull;                      // (image << 32 | index): one comparison orders both
 #pragma unroll
         for (int q = 0; q < GEN_MAX_PER_LANE; ++q) {
-            const int j = lane + 64 * q;
-            const unsigned long long cand = ((unsigned long long)okey[q] << 32) | (unsigned)j;
-            if (j < N && !((taken >> q) & 1u) && cand < best) best = cand;
+            const unsigned long long cand = rank[q];
+            if (lane + 64 * q < N && !((taken >> q) & 1u) && cand < best) best = cand;
         }
 #pragma unroll
         for (int sft = 1; sft < 64; sft <<= 1) {

@@ -348,6 +348,27 @@ int launch_cluster_scan(const float* pts, int stride, const uint32_t* label, int
 int launch_graph_edges(const float* pts, int stride, const int32_t* point_node, int P, int n, const double* centers,
                        double* min_dis, void* ws, hipStream_t stream);
 
+// sgpr_knn's ranking, shared by its two instances (knn_kernel, generic_knn_kernel) so that they return the same lists:
+//   key(i, j) = |x_i|^2 - (2 x_i.x_j - |x_j|^2) = -pd[i][j],  |x|^2 = rounded squares summed in channel order,
+//   x_i.x_j = an fma chain in channel order from the rounded first product (no contraction beyond the fmaf calls)
+__device__ __forceinline__ float knn_sq_norm(const float* v, int C, size_t stride) {
+    float s = __fmul_rn(v[0], v[0]);
+    for (int c = 1; c < C; ++c) s = __fadd_rn(s, __fmul_rn(v[(size_t)c * stride], v[(size_t)c * stride]));
+    return s;
+}
+__device__ __forceinline__ float knn_key(float xi2, float xj2, float dot) { return __fsub_rn(xi2, fmaf(2.f, dot, -xj2)); }
+// (key, index) under one total order: the order-preserving image of the key (-0 as +0, +inf after every finite key, NaN
+// after everything) above the candidate index - the smaller value ranks first, equal keys lower index first
+__device__ __forceinline__ unsigned long long knn_rank(float key, int j) {
+    unsigned img = 0xffffffffu;
+    if (key == key) {
+        key += 0.0f;
+        const unsigned u = __float_as_uint(key);
+        img = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+    }
+    return ((unsigned long long)img << 32) | (unsigned)j;
+}
+
 // Raising a kernel's dynamic-LDS limit (hipFuncSetAttribute) applies to the CURRENT device only: remembered per device
 // (one bit each; a process that drives several GPUs raises it once on each), with a message that says what did not fit -
 // a part with 64 KB of LDS per workgroup cannot run the kernels that stage a whole graph / histogram in 130 - 160 KB.

@@ -11,66 +11,58 @@ namespace sgpr {
 
 constexpr int KNN_THREADS = 256;
 
+// bytes of knn_kernel's x and |x|^2 ahead of its 8-byte list words
+__host__ __device__ constexpr size_t knn_list_offset(int C, int N) {
+    return (((size_t)C * N + N) * sizeof(float) + 7) & ~(size_t)7;
+}
+
 // dgcnn.knn: x [B][C][N] -> idx [B][N][k] (int64 like torch.topk's indices).
-//   pd[i][j] = -xx[j] - inner[i][j] - xx[i],  inner = -2 <x_i, x_j>        (dgcnn.py:15-17, same operation order)
+//   pd[i][j] = -xx[j] - inner[i][j] - xx[i],  inner = -2 <x_i, x_j>        (dgcnn.py:15-17)
 //   idx[i][:] = the k largest pd[i][j], best first; equal values keep the lower candidate index first (torch.topk's
 //   tie order is implementation-defined - CPU and CUDA already disagree; this is the engine's deterministic rule).
-// One workgroup per graph: x is staged in LDS, thread i owns row i (N <= 256) and keeps its running top-k list in LDS
-// ([slot][thread] layout: conflict-free), inserting a candidate only when it beats the current k-th.
+// Keys and their order are knn_key / knn_rank (sgpr_internal.hpp), the same as generic_knn_kernel's: both instances
+// return the same lists, and a NaN or +inf key (a non-finite or overflowing node) ranks after every finite one.
+// One workgroup per graph: x is staged in LDS, thread i owns row i (N <= 256) and keeps its running top-k list of
+// (key image, index) words in LDS ([slot][thread] layout: conflict-free), inserting a candidate only when it ranks
+// ahead of the current k-th.
 __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const float* __restrict__ x, int C, int N, int k,
                                                           long long* __restrict__ idx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* xs = reinterpret_cast<float*>(smem);                 // [C][N]
     float* xx = xs + (size_t)C * N;                             // [N]
-    float* lv = xx + N;                                         // [k][KNN_THREADS] values, descending
-    int* li = reinterpret_cast<int*>(lv + (size_t)k * KNN_THREADS);   // [k][KNN_THREADS]
+    unsigned long long* lr = reinterpret_cast<unsigned long long*>(smem + knn_list_offset(C, N));   // [k][KNN_THREADS]
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* xb = x + (size_t)b * C * N;
     for (int e = tid; e < C * N; e += KNN_THREADS) xs[e] = xb[e];
     __syncthreads();
-    if (tid < N) {
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s = fmaf(xs[c * N + tid], xs[c * N + tid], s);
-        xx[tid] = s;
-    }
+    if (tid < N) xx[tid] = knn_sq_norm(xs + tid, C, N);
     __syncthreads();
     if (tid >= N) return;
     const int i = tid;
-    for (int s = 0; s < k; ++s) {
-        lv[s * KNN_THREADS + tid] = -INFINITY;
-        li[s * KNN_THREADS + tid] = N;                          // sentinel: loses every tie
-    }
+    for (int s = 0; s < k; ++s) lr[s * KNN_THREADS + tid] = ~0ull;   // ranks after every candidate
     const float xi = xx[i];
-    int filled = 0;
     for (int j = 0; j < N; ++j) {
-        float dot = 0.f;
-        for (int c = 0; c < C; ++c) dot = fmaf(xs[c * N + i], xs[c * N + j], dot);
-        const float inner = -2.f * dot;
-        const float pd = (-xx[j] - inner) - xi;
-        // candidates arrive in ascending j: a strict comparison keeps the lower index ahead among equal values
-        if (filled < k || pd > lv[(k - 1) * KNN_THREADS + tid]) {
-            int s = filled < k ? filled : k - 1;
-            while (s > 0 && pd > lv[(s - 1) * KNN_THREADS + tid]) {
-                lv[s * KNN_THREADS + tid] = lv[(s - 1) * KNN_THREADS + tid];
-                li[s * KNN_THREADS + tid] = li[(s - 1) * KNN_THREADS + tid];
+        float dot = __fmul_rn(xs[i], xs[j]);
+        for (int c = 1; c < C; ++c) dot = fmaf(xs[c * N + i], xs[c * N + j], dot);
+        const unsigned long long cand = knn_rank(knn_key(xi, xx[j], dot), j);
+        if (cand < lr[(k - 1) * KNN_THREADS + tid]) {
+            int s = k - 1;
+            while (s > 0 && cand < lr[(s - 1) * KNN_THREADS + tid]) {
+                lr[s * KNN_THREADS + tid] = lr[(s - 1) * KNN_THREADS + tid];
                 --s;
             }
-            lv[s * KNN_THREADS + tid] = pd;
-            li[s * KNN_THREADS + tid] = j;
-            if (filled < k) ++filled;
+            lr[s * KNN_THREADS + tid] = cand;
         }
     }
     long long* out = idx + ((size_t)b * N + i) * k;
-    for (int s = 0; s < k; ++s) out[s] = li[s * KNN_THREADS + tid];
+    for (int s = 0; s < k; ++s) out[s] = (long long)(unsigned)lr[s * KNN_THREADS + tid];
 }
 
 int launch_knn(const float* x, int B, int C, int N, int k, int64_t* idx, hipStream_t stream) {
     if (B == 0) return SGPR_OK;
-    const size_t lds = ((size_t)C * N + N) * sizeof(float) + (size_t)k * KNN_THREADS * (sizeof(float) + sizeof(int));
-    if (lds > 160 * 1024) {
-        set_error("sgpr_knn: C * N too large for one workgroup's LDS (" + std::to_string(lds) + " bytes)");
-        return SGPR_E_NODES;
-    }
+    const size_t lds = knn_list_offset(C, N) + (size_t)k * KNN_THREADS * sizeof(unsigned long long);
+    if (lds > 160 * 1024)                  // the graph does not fit one workgroup's LDS: one wave per row, same lists
+        return launch_knn_any(x, B, C, N, k, idx, stream);
     static LdsLimitOnce once;
     if (int rc = raise_lds_limit(&once, reinterpret_cast<const void*>(&knn_kernel), 160 * 1024, "sgpr_knn")) return rc;
     hipLaunchKernelGGL(knn_kernel, dim3(B), dim3(KNN_THREADS), lds, stream, x, C, N, k,

@@ -9,6 +9,8 @@ Tie order: `torch.topk` leaves the order of equal distances implementation-defin
 disagree); `knn` here returns equal-distance candidates lowest index first.  With >= k-1 padded slots per graph the
 choice does not change any EdgeConv output.
 """
+import math
+
 import torch
 
 from . import engine as _engine
@@ -26,7 +28,7 @@ def get_graph_feature(x, k=20, cuda=0, idx=None, xyz=False):
     the result lives on x's device.  `idx`: precomputed neighbour lists; `xyz=True` ranks by the first three channels."""
     batch_size = x.size(0)
     num_points = x.size(2)
-    x = x.reshape(batch_size, -1, num_points)
+    x = x.reshape(batch_size, math.prod(x.shape[1:]) // max(num_points, 1), num_points)   # (no -1: B may be 0)
     if idx is None:
         idx = knn(x[:, :3, :] if xyz else x, k=k)
     return _engine.graph_feature(x, idx)

@@ -1081,6 +1081,9 @@ def graph_feature(x, idx):
     return out
 
 
+ATTENTION_MAX_NODES = 12288     # sgpr_attention_pool keeps a graph's N scores in 48 KB of LDS
+
+
 def attention_pool(weight, emb):
     """AttentionModule.forward (layers_batch.py:28-39): weight [32,32], emb [B,N,32] -> (rep [B,32], att [B,N])."""
     lib = load_library()
@@ -1089,7 +1092,8 @@ def attention_pool(weight, emb):
     b, n, f = emb.shape
     if tuple(weight.shape) != (f, f):
         raise ValueError("attention_pool: weight_matrix must be [%d, %d]" % (f, f))
-    if f > F3:          # wider than the built module: the any-width kernel (plain fp32)
+    # wider than the built module, or more nodes than its LDS holds scores for: the any-width kernel (plain fp32)
+    if f > F3 or n > ATTENTION_MAX_NODES:
         rep = torch.empty(b, f, dtype=torch.float32, device=emb.device)
         att = torch.empty(b, n, dtype=torch.float32, device=emb.device)
         with torch.cuda.device(emb.device):

@@ -40,7 +40,7 @@ class TenorNetworkModule(torch.nn.Module):
 
     def forward(self, embedding_1, embedding_2):
         """layers_batch.py:70-83 - embedding_1/2 [B, F3, 1] -> scores [B, T, 1]."""
-        b = embedding_1.shape[0]
+        b, f = embedding_1.shape[0], self.weight_matrix.shape[0]
         out = _engine.ntn(self.weight_matrix, self.weight_matrix_block, self.bias,
-                          embedding_1.reshape(b, -1), embedding_2.reshape(b, -1))
+                          embedding_1.reshape(b, f), embedding_2.reshape(b, f))
         return out.unsqueeze(-1)
