@@ -475,6 +475,34 @@ int sgpr_ntn(const float* d_weight, const float* d_weight_block, const float* d_
 int sgpr_ntn_any(const float* d_weight, const float* d_weight_block, const float* d_bias, const float* d_e1,
                  const float* d_e2, int64_t B, int F, int T, float* d_out, void* stream);
 
+/* ---- training: one EdgeConv block with BatchNorm in train mode ---------------------------
+ * Replaces, for training, get_graph_feature -> Conv2d 1x1 -> BatchNorm2d (batch statistics) -> LeakyReLU(0.2) -> max
+ * over k (sg_net.py:50-73, 79-110; dgcnn.py:23-49) without forming the [B, 2C, N, k] edge tensor.  The caller splits
+ * the conv weight W [F, 2C] = [Wa | Wb] and forms the per-node products d_P = Wa x and d_Q = (Wb - Wa) x, both
+ * [B, F, N] f32, so that edge (i, k) with neighbour j = d_idx[b][i][k] has z = P[b,f,j] + Q[b,f,i].
+ *   forward : d_y [B,F,N] = max_k LeakyReLU(gamma (z - mean) / sqrt(var + eps) + beta) with mean / biased var over all
+ *             M = B N k edges per channel (d_mean, d_var [F]); saves d_sel [B,F,N] u8 (the selected k: the largest P
+ *             for gamma >= 0, the smallest for gamma < 0, ties to the lowest k) and d_s1 [B,F,N] (sum_k P_nbr) for the
+ *             backward.
+ *   backward: from d_dy [B,F,N] and what the forward saved -> d_dP, d_dQ [B,F,N], d_dgamma, d_dbeta [F].  d_dQ also
+ *             serves as the call's scratch (it may alias nothing else).
+ * d_idx [B,N,k] int64 (sgpr_knn's lists); an index outside [0, N) is clamped to it.  N <= SGPR_TRAIN_MAX_NODES,
+ * 1 <= k <= min(N, SGPR_TRAIN_MAX_K), any F >= 1, B >= 1.  d_workspace: sgpr_edgeconv_train_workspace_bytes(B, F)
+ * bytes (per-graph fp64 partial sums), any contents.  Deterministic: no float atomics, fixed summation orders - two
+ * calls on the same inputs give the same bits on any stream.  Handle-free; runs on the caller's current device. */
+#define SGPR_TRAIN_MAX_NODES 1024
+#define SGPR_TRAIN_MAX_K 64
+size_t sgpr_edgeconv_train_workspace_bytes(int B, int F);
+int sgpr_edgeconv_train_forward(const float* d_P, const float* d_Q, const int64_t* d_idx, const float* d_gamma,
+                                const float* d_beta, int B, int F, int N, int k, float eps, float* d_y,
+                                uint8_t* d_sel, float* d_s1, float* d_mean, float* d_var, void* d_workspace,
+                                size_t workspace_bytes, void* stream);
+int sgpr_edgeconv_train_backward(const float* d_dy, const float* d_P, const float* d_Q, const int64_t* d_idx,
+                                 const uint8_t* d_sel, const float* d_s1, const float* d_mean, const float* d_var,
+                                 const float* d_gamma, const float* d_beta, int B, int F, int N, int k, float eps,
+                                 float* d_dP, float* d_dQ, float* d_dgamma, float* d_dbeta, void* d_workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* ---- upstream of the path: labelled LiDAR scan -> semantic-graph nodes -------------------------
  * Replaces, for one scan, gen_labels + the node half of gen_graphs (data_process/gen_label_graph.py:196-365):
  * raw SemanticKITTI labels are remapped (learning_map, :23-58); road / parking and the discarded classes produce no

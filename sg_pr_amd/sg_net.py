@@ -1,7 +1,7 @@
 """`SG` / `SGTrainer` with the reference's API (sg_net.py:18-138, 141-206, 241-310,
 434-525) backed by the MI355X HIP engine.
 
-Only inference is built (training is out of scope): the model
+Only inference is built here (training lives in sg_pr_amd.train): the model
 must be in eval mode - BatchNorm running statistics are folded into the kernels'
 weights.  There is no CPU fallback.
 """
