@@ -310,8 +310,10 @@ static int check_sizes(const char* what, int B, int F, int N, int K, float eps, 
                   std::to_string(SGPR_TRAIN_MAX_K) + ")]");
         return SGPR_E_K;
     }
-    const int ft = pick_tile(F, N, K, true);
-    if ((F + ft - 1) / ft > 65535 || (long long)B > 0x7fffffffLL) {
+    // both launch shapes: stats / grad kernels on the 56 KB tile, scatter_kernel on the 160 KB one (either can be the
+    // narrower); 64-bit, so that an F near INT_MAX cannot wrap the count
+    const long long fs = pick_tile(F, N, K, false), fc = pick_tile(F, N, K, true);
+    if ((F + fs - 1) / fs > 65535 || (F + fc - 1) / fc > 65535) {
         set_error(std::string(what) + ": F " + std::to_string(F) + " needs more channel tiles than one launch holds");
         return SGPR_E_DIMS;
     }

@@ -46,6 +46,30 @@ def pq_block(P, Q, idx, gamma, beta, eps=1e-5):
     return Fn.leaky_relu(u, 0.2).max(dim=-1)[0], mean, var
 
 
+def pq_block_selected(P, Q, idx, gamma, beta, eps=1e-5):
+    """pq_block with the op's documented choice of the max edge (include/sgpr.h), exact on ties.
+
+    idx is clamped to [0, N).  The batch mean / biased var run over every one of the M = B N k edges.  The edge of
+    (b, f, i) is chosen on P, not on the activation: the largest P for gamma >= 0, the smallest for gamma < 0 (gamma = 0
+    selects as gamma > 0), the lowest k among equal P.  y is a gather at that k, so autograd sends dy to that edge only.
+    -> (y [B,F,N], mean [F], biased var [F], sel [B,F,N] int64, s1 [B,F,N] = sum_k P[b,f,idx[b,i,k]])."""
+    b, f, n = P.shape
+    k = idx.shape[2]
+    idx = idx.to(P.device).long().clamp(0, n - 1)
+    g = idx.reshape(b, 1, n * k).expand(b, f, n * k)
+    Pn = torch.gather(P, 2, g).view(b, f, n, k)
+    z = Pn + Q.unsqueeze(-1)
+    mean = z.mean(dim=(0, 2, 3))
+    var = z.var(dim=(0, 2, 3), unbiased=False)
+    key = torch.where(gamma.detach().view(1, -1, 1, 1) < 0, -Pn.detach(), Pn.detach())
+    best = key.max(dim=-1, keepdim=True).values
+    ks = torch.arange(k, device=P.device).view(1, 1, 1, k).expand_as(key)
+    sel = torch.where(key == best, ks, k).min(dim=-1).values
+    z_sel = torch.gather(z, 3, sel.unsqueeze(-1)).squeeze(-1)
+    u = (z_sel - mean.view(1, -1, 1)) / torch.sqrt(var.view(1, -1, 1) + eps) * gamma.view(1, -1, 1) + beta.view(1, -1, 1)
+    return Fn.leaky_relu(u, 0.2), mean, var, sel, Pn.detach().sum(dim=-1)
+
+
 def conv_pass(p, feats, idx_lists, eps=1e-5):
     """dgcnn_conv_pass in train mode -> (emb [G,N,F3], {bn name: (mean, biased var, count)})."""
     stats = {}
