@@ -358,6 +358,44 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
                     const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
                     int32_t* d_indices, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Hard-pair mining without the R x M matrix: for every row r the k (1..16) hardest pose-labelled pairs (r, c) of the
+ * rectangle d_pooled_rows [R] x d_pooled_cols [M].
+ * - Column c is eligible for row r iff it is for sgpr_score_topk (window, SGPR_TOPK_CAUSAL, self_r = d_row_self[r] or
+ *   row0 + r), c != self_r, and the pair's pose class is the one flags ask for.  The class is sgpr_pair_positives'
+ *   float64 rule on the row pose and d_col_pose_xz[c] (device, [M][2] x, z): the row pose is d_row_pose_xz[r] (device,
+ *   [R][2]) or, with d_row_pose_xz NULL, d_col_pose_xz[self_r] (none when self_r lies outside [0, M): the row gets
+ *   nothing).
+ * - SGPR_MINE_NEGATIVES: distance >= d_neg, score descending, then column ascending (-inf, -1 in empty slots) - the
+ *   perceptual aliases a back end must reject.  SGPR_MINE_POSITIVES: distance <= d_pos, score ascending, then column
+ *   ascending (+inf, -1 in empty slots) - the missed revisits.  Exactly one of the two is set.
+ * - A NaN score or a NaN pose never qualifies.  Every value is bit-identical to sgpr_score_all_pairs' entry (r, c); two
+ *   calls return identical bytes.
+ * - The production handle runs sgpr_score_topk's fused launch with the pose test in its epilogue: a 256-column chunk
+ *   whose pose box lies beyond d_pos of the wave's rows is not scored at all for the positives, and one beyond
+ *   max(d_pos, d_neg) needs no per-pair arithmetic for the negatives.  Its workspace grows with R + M, never R * M.
+ *   Wide-range and any-shape handles score row blocks of at most 64 MB with their own tail and run sgpr_mine_rows on
+ *   each.
+ * d_values / d_indices [R][k], device.  Arguments are checked before the device is touched: a NULL handle, pooled
+ * array, column pose array or output, k outside 1..16, zero or both mode flags or unknown bits, a NaN d_pos / d_neg,
+ * d_pos < 0, d_pos > d_neg or row0 + R beyond an int give SGPR_E_INVALID, a workspace below sgpr_score_mine_workspace_bytes
+ * SGPR_E_WORKSPACE; a d_row_self entry outside [0, M) is reported by sgpr_check_status.  Asynchronous on `stream`. */
+#define SGPR_MINE_NEGATIVES 2
+#define SGPR_MINE_POSITIVES 4
+size_t sgpr_score_mine_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags);
+int sgpr_score_mine(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                    const double* d_col_pose_xz, const double* d_row_pose_xz, const int32_t* d_row_self, int row0,
+                    int window, int flags, double d_pos, double d_neg, int k, float* d_values, int32_t* d_indices,
+                    void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* sgpr_score_mine's selection on a resident matrix d_score [R][ld] (ld >= M), with its rules, flags, checks and order:
+ * one wave per row, one pass over the row.  Needs no workspace (sgpr_mine_rows_workspace_bytes returns 0; the
+ * arguments are kept for later use). */
+size_t sgpr_mine_rows_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags);
+int sgpr_mine_rows(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, const double* d_col_pose_xz,
+                   const double* d_row_pose_xz, const int32_t* d_row_self, int row0, int window, int flags, double d_pos,
+                   double d_neg, int k, float* d_values, int32_t* d_indices, void* d_workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* Range retrieval without the R x M matrix: every eligible pair (r, c) of the rectangle d_pooled_rows [R] x
  * d_pooled_cols [M] whose score is >= threshold.
  * - Eligibility is sgpr_score_topk's: |c - self_r| > window (window < 0: no window) and, with SGPR_TOPK_CAUSAL in flags,

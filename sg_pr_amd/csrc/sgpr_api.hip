@@ -1234,6 +1234,116 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
     return SGPR_OK;
 }
 
+// ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks
+//      and sgpr_mine_rows' kernel on the others) with the pose-class condition of the mined pairs
+static const int kMineFlags = SGPR_TOPK_CAUSAL | SGPR_MINE_NEGATIVES | SGPR_MINE_POSITIVES;
+
+static bool mine_flags_ok(int flags) {
+    const int mode = flags & (SGPR_MINE_NEGATIVES | SGPR_MINE_POSITIVES);
+    return !(flags & ~kMineFlags) && (mode == SGPR_MINE_NEGATIVES || mode == SGPR_MINE_POSITIVES);
+}
+
+static bool mine_args_ok(const char* fn, const sgpr_handle* h, int R, int M, const double* col_pose, int row0, int flags,
+                         double d_pos, double d_neg, int k, const float* d_values, const int32_t* d_indices) {
+    if (!h || R < 0 || M < 0 || !col_pose || !d_values || !d_indices) {
+        set_error(std::string(fn) + ": NULL argument or negative count");
+        return false;
+    }
+    if (k < 1 || k > 16) {
+        set_error(std::string(fn) + ": k must lie in 1..16");
+        return false;
+    }
+    if (!mine_flags_ok(flags)) {
+        set_error(std::string(fn) + ": flags must hold exactly one of SGPR_MINE_NEGATIVES / SGPR_MINE_POSITIVES and no "
+                  "unknown bit (got " + std::to_string(flags) + ")");
+        return false;
+    }
+    if (d_pos != d_pos || d_neg != d_neg || d_pos < 0.0 || d_pos > d_neg) {
+        // (a negative d_pos: the squared rule would take s2 < d_pos^2 as positive, PairSet._targets' d <= d_pos never)
+        set_error(std::string(fn) + ": d_pos / d_neg NaN, d_pos < 0 or d_pos > d_neg");
+        return false;
+    }
+    if ((int64_t)row0 + R > 0x7fffffffLL) {
+        set_error(std::string(fn) + ": row0 + R must fit an int");
+        return false;
+    }
+    return true;
+}
+
+size_t sgpr_score_mine_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
+    if (!h || R < 0 || M < 0 || k < 1 || k > 16 || !mine_flags_ok(flags)) return 0;
+    if (R == 0 || M == 0) return 0;
+    if (topk_fused(h)) return score_mine_ws_bytes(h, R, M, k);
+    const int rb = topk_block_rows(R, M);
+    return a256((size_t)rb * M * sizeof(float)) + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
+}
+
+int sgpr_score_mine(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                    const double* d_col_pose_xz, const double* d_row_pose_xz, const int32_t* d_row_self, int row0,
+                    int window, int flags, double d_pos, double d_neg, int k, float* d_values, int32_t* d_indices,
+                    void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!mine_args_ok("sgpr_score_mine", h, R, M, d_col_pose_xz, row0, flags, d_pos, d_neg, k, d_values, d_indices))
+        return SGPR_E_INVALID;
+    if (!d_pooled_rows || !d_pooled_cols) {
+        set_error("sgpr_score_mine: NULL pooled array");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = sgpr_score_mine_workspace_bytes(h, R, M, k, flags);
+    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
+        set_error("sgpr_score_mine: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    if (R == 0) return SGPR_OK;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, positives = (flags & SGPR_MINE_POSITIVES) ? 1 : 0;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0 || topk_fused(h))
+        return launch_score_mine(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, positives,
+                                 d_col_pose_xz, d_row_pose_xz, d_pos, d_neg, k, d_values, d_indices, d_workspace, s);
+    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
+    float* block = static_cast<float*>(d_workspace);
+    unsigned char* ws = static_cast<unsigned char*>(d_workspace) + a256((size_t)rb * M * sizeof(float));
+    const size_t ws_bytes = workspace_bytes - a256((size_t)rb * M * sizeof(float));
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = std::min(rb, R - r0);
+        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
+        if (rc != SGPR_OK) return rc;
+        rc = launch_mine_rows(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, positives,
+                              d_col_pose_xz, d_row_pose_xz ? d_row_pose_xz + 2 * (size_t)r0 : nullptr, d_pos, d_neg, k,
+                              d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
+        if (rc != SGPR_OK) return rc;
+    }
+    return SGPR_OK;
+}
+
+size_t sgpr_mine_rows_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
+    (void)h;
+    (void)R;
+    (void)M;
+    (void)k;
+    (void)flags;
+    return 0;
+}
+
+int sgpr_mine_rows(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, const double* d_col_pose_xz,
+                   const double* d_row_pose_xz, const int32_t* d_row_self, int row0, int window, int flags, double d_pos,
+                   double d_neg, int k, float* d_values, int32_t* d_indices, void* d_workspace, size_t workspace_bytes,
+                   void* stream) {
+    (void)d_workspace;
+    (void)workspace_bytes;
+    if (!mine_args_ok("sgpr_mine_rows", h, R, M, d_col_pose_xz, row0, flags, d_pos, d_neg, k, d_values, d_indices))
+        return SGPR_E_INVALID;
+    if (!d_score || ld < M) {
+        set_error("sgpr_mine_rows: NULL score matrix or leading dimension below M");
+        return SGPR_E_INVALID;
+    }
+    if (R == 0) return SGPR_OK;
+    DeviceGuard guard(h->device);
+    return launch_mine_rows(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0,
+                            (flags & SGPR_MINE_POSITIVES) ? 1 : 0, d_col_pose_xz, d_row_pose_xz, d_pos, d_neg, k,
+                            d_values, d_indices, h->d_status, static_cast<hipStream_t>(stream));
+}
+
 // ---- sgpr_score_above / sgpr_rows_above: the fused two-pass kernel on the production handle; the other handles score
 //      bounded row blocks with their own tail and select from each block, positions continuing on the device
 static bool above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int row0, int flags, float threshold,
@@ -1793,7 +1903,7 @@ int sgpr_check_status(const sgpr_handle* h, void* stream) {
             return SGPR_E_HIP;
         }
         if (flag & 16) {
-            set_error("a d_row_self entry of sgpr_score_topk / sgpr_score_above lies outside [0, M)");
+            set_error("a d_row_self entry of sgpr_score_topk / sgpr_score_above / sgpr_score_mine lies outside [0, M)");
             return SGPR_E_INVALID;
         }
         if (flag & 4) {

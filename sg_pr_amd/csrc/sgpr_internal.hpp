@@ -262,6 +262,23 @@ __device__ __forceinline__ int classify_pair(const PairTruth& t, int r, int c, d
     return g < 0 ? -1 : (g != 0);
 }
 
+// classify_pair's pose rule for sgpr_score_mine / sgpr_mine_rows with floating-point contraction off: __dmul_rn /
+// __dadd_rn are a plain x * y and x + y here, and with HIP's default contraction the compiler fuses dz * dz into the
+// sum - one rounding fewer than utils.py:36 / PairSet._targets, which flips pairs at exactly d_pos or d_neg (a pose
+// (1.8, 2.4) from the origin: 9.0 unfused, 9.000000000000002 fused).  (classify_pair itself is left as it is: its
+// instances' code is unchanged by this addition.)
+__device__ __forceinline__ int classify_pose_exact(const double* __restrict__ pose, int c, double px, double pz,
+                                                   double d_pos, double d_neg, double lo2, double hi2) {
+#pragma clang fp contract(off)
+    const double dx = px - pose[2 * (size_t)c], dz = pz - pose[2 * (size_t)c + 1];
+    const double s2 = dx * dx + dz * dz;
+    if (s2 < lo2 * (1.0 - 1e-12)) return 1;
+    if (s2 > lo2 * (1.0 + 1e-12) && s2 < hi2 * (1.0 - 1e-12)) return -1;
+    if (s2 > hi2 * (1.0 + 1e-12)) return 0;
+    const double d = sqrt(s2);
+    return d <= d_pos ? 1 : (d >= d_neg ? 0 : -1);
+}
+
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
 
@@ -281,6 +298,15 @@ int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const floa
 // sgpr_topk_rows' selection with a row_self table, the causal rule and an output row stride of k (sgpr_metrics.hip)
 int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
                          int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
+// sgpr_score_mine on the production handle (positives: SGPR_MINE_POSITIVES, else the negatives) and its selection on a
+// resident block (sgpr_mine_rows, the chunked path of the other handles; sgpr_metrics.hip)
+size_t score_mine_ws_bytes(const sgpr_handle* h, int R, int M, int k);
+int launch_score_mine(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
+                      int row0, int window, int causal, int positives, const double* col_pose, const double* row_pose,
+                      double d_pos, double d_neg, int k, float* val, int32_t* idx, void* ws, hipStream_t stream);
+int launch_mine_rows(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                     int causal, int positives, const double* col_pose, const double* row_pose, double d_pos, double d_neg,
+                     int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
 size_t score_above_ws_bytes(const sgpr_handle* h, int R, int M);
 size_t rows_above_ws_bytes(int R);
 int launch_above_empty(int R, int64_t* row_ptr, unsigned long long* count, hipStream_t stream);

@@ -1551,6 +1551,132 @@ int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int
     return SGPR_OK;
 }
 
+// ------------------------------------------------------------------ mined pairs per row (sgpr_mine_rows)
+// topk_rows_kernel's selection with sgpr_score_mine's eligibility: the window / causal rule, c != self_r and the pose
+// class of the pair (classify_pair: 0 for MINE = 1, the negatives; 1 for MINE = 2, the positives).  The positives rank
+// by -score in the same descending lists and leave negated (exact).  Order: value (descending, or ascending for the
+// positives), then column ascending - every (value, column) comparison is tk_beats' total order, so a resident matrix
+// gives the fused path's lists entry for entry.
+template <int K, int MINE, bool CAUSAL>
+__global__ __launch_bounds__(256) void mine_rows_kernel(const float* __restrict__ score, int R, int M, int64_t ld,
+                                                        const int32_t* __restrict__ row_self, int row0, int window,
+                                                        PairTruth t, const double* __restrict__ row_pose, int kout,
+                                                        float* __restrict__ out_val, int32_t* __restrict__ out_idx,
+                                                        int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    float v[K];
+    int ix[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        v[q] = -INFINITY;
+        ix[q] = 0x7fffffff;
+    }
+    const float* sp = score + (int64_t)r * ld;
+    long long self = (long long)row0 + r;
+    if (row_self) {
+        self = row_self[r];
+        if (lane == 0 && (self < 0 || self >= M)) atomicOr(status, 16);
+    }
+    double px, pz;
+    if (row_pose) {
+        px = row_pose[2 * (size_t)r];
+        pz = row_pose[2 * (size_t)r + 1];
+    } else if (self >= 0 && self < M) {
+        px = t.pose[2 * (size_t)self];
+        pz = t.pose[2 * (size_t)self + 1];
+    } else {
+        px = pz = __longlong_as_double(0x7ff8000000000000LL);
+    }
+    const double lo2 = t.d_pos * t.d_pos, hi2 = t.d_neg * t.d_neg;
+    for (int c = lane; c < M; c += 64) {
+        if constexpr (CAUSAL) {
+            if (c >= self - (window > 0 ? window : 0)) break;
+        }
+        const long long dc = c - self;
+        if (dc == 0 || (window >= 0 && (dc < 0 ? -dc : dc) <= window)) continue;
+        float x = sp[c];
+        if (MINE == 2) x = -x;
+        if (!(x == x)) continue;                            // NaN never qualifies
+        if (!(x > v[K - 1] || (x == v[K - 1] && c < ix[K - 1]))) continue;
+        if (classify_pose_exact(t.pose, c, px, pz, t.d_pos, t.d_neg, lo2, hi2) != (MINE == 2 ? 1 : 0)) continue;
+        int xi = c;
+        bool carry = false;                                 // once an entry is displaced, everything behind it shifts
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            const bool before = carry || x > v[q] || (x == v[q] && xi < ix[q]);
+            carry = before;
+            const float tv = before ? v[q] : x;
+            const int ti = before ? ix[q] : xi;
+            v[q] = before ? x : v[q];
+            ix[q] = before ? xi : ix[q];
+            x = tv;
+            xi = ti;
+        }
+    }
+    // kout rounds: the wave's best head wins (tk_beats), its lane pops
+#pragma unroll 1
+    for (int round = 0; round < kout; ++round) {
+        float bv = v[0];
+        int bi = ix[0];
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const float ov = __shfl_xor(bv, m);
+            const int oi = __shfl_xor(bi, m);
+            const bool take = ov > bv || (ov == bv && oi < bi);
+            bv = take ? ov : bv;
+            bi = take ? oi : bi;
+        }
+        if (lane == 0) {
+            out_val[(size_t)r * kout + round] = MINE == 2 ? -bv : bv;
+            out_idx[(size_t)r * kout + round] = bi == 0x7fffffff ? -1 : bi;
+        }
+        if (ix[0] == bi && bi != 0x7fffffff) {              // columns are unique: exactly one lane owns the winner
+#pragma unroll
+            for (int q = 0; q + 1 < K; ++q) {
+                v[q] = v[q + 1];
+                ix[q] = ix[q + 1];
+            }
+            v[K - 1] = -INFINITY;
+            ix[K - 1] = 0x7fffffff;
+        }
+    }
+}
+
+int launch_mine_rows(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                     int causal, int positives, const double* col_pose, const double* row_pose, double d_pos, double d_neg,
+                     int k, float* val, int32_t* idx, int32_t* status, hipStream_t s) {
+    if (R == 0) return SGPR_OK;
+    PairTruth t;
+    memset(&t, 0, sizeof(t));
+    t.pose = col_pose;
+    t.d_pos = d_pos;
+    t.d_neg = d_neg;
+    const dim3 grid((R + 3) / 4), block(256);
+    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;
+    const int sel = K * 4 + (positives ? 2 : 0) + (causal ? 1 : 0);
+#define SGPR_MINE_ROWS(KK, MM, C) \
+    case KK * 4 + (MM == 2 ? 2 : 0) + (C ? 1 : 0): \
+        hipLaunchKernelGGL((mine_rows_kernel<KK, MM, C>), grid, block, 0, s, score, R, M, ld, row_self, row0, window, t, \
+                           row_pose, k, val, idx, status); \
+        break;
+#define SGPR_MINE_ROWS_K(KK) SGPR_MINE_ROWS(KK, 1, false) SGPR_MINE_ROWS(KK, 1, true) SGPR_MINE_ROWS(KK, 2, false) \
+    SGPR_MINE_ROWS(KK, 2, true)
+    switch (sel) {
+        SGPR_MINE_ROWS_K(1)
+        SGPR_MINE_ROWS_K(4)
+        SGPR_MINE_ROWS_K(8)
+        SGPR_MINE_ROWS_K(16)
+        default: break;
+    }
+#undef SGPR_MINE_ROWS_K
+#undef SGPR_MINE_ROWS
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "mine_rows_kernel launch");
+    return SGPR_OK;
+}
+
 }  // namespace sgpr
 
 using namespace sgpr;

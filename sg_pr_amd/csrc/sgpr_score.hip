@@ -709,7 +709,8 @@ __device__ __forceinline__ void tk_push(const float (&sc)[4], int c0, int M, int
 
 // the lists of row group rg (lane group g of this wave: row r) leave: to the result when this workgroup saw every column
 // chunk of the row group, else to partial slot 0 (the row group its range starts in) or 1 (the one it ends in)
-template <int K>
+// (NEG: the lists hold negated scores - sgpr_score_mine's positives -; the result gets them back, bit for bit)
+template <int K, bool NEG = false>
 __device__ __forceinline__ void tk_flush(const TopkArgs& a, int rg, int ncc, int it0, int it1, int r, int R, float tv, int tc) {
     const int lane = threadIdx.x & 63, l15 = lane & 15;
     if constexpr (K == 1) {
@@ -725,7 +726,7 @@ __device__ __forceinline__ void tk_flush(const TopkArgs& a, int rg, int ncc, int
     }
     if (r >= R || l15 >= a.k) return;
     if ((int64_t)rg * ncc >= it0 && (int64_t)(rg + 1) * ncc <= it1) {
-        a.val[(size_t)r * a.k + l15] = tv;
+        a.val[(size_t)r * a.k + l15] = NEG ? -tv : tv;
         a.idx[(size_t)r * a.k + l15] = tc == TK_EMPTY ? -1 : tc;
     } else {
         const int slot = rg == it0 / ncc ? 0 : 1;
@@ -1011,17 +1012,91 @@ __device__ __forceinline__ void ev_cnt_push(EvalArgs& e, const float (&s)[4], in
     }
 }
 
+// ------------------------------------------------------------------ fused mining epilogue (sgpr_score_mine)
+// The top-k epilogue (TK > 0) with one more condition on a candidate: the pose class of the pair (classify_pair's
+// float64 rule) must be the one asked for, and c != self_r.  MN_NEG keeps class 0 in top-k's order; MN_POS keeps class 1
+// lowest score first - it feeds -score to the same descending lists (tk_merge, tk_flush, topk_merge_kernel) and negates
+// on the way out (exact).  The row pose is d_row_pose[r], or the column pose of the row's own frame (mine_rowpose_kernel
+// writes them, and every wave's four-row box, to the workspace).  Work items are tested as a whole with the evaluation
+// epilogues' gap (ev_gap2 against eval_colbox_kernel's chunk boxes): MN_POS skips an item farther than d_pos from every
+// row unscored, MN_NEG takes every pair of an item farther than max(d_pos, d_neg) as a negative without per-pair float64.
+// Candidates are classified (classify_pose_exact) only once they beat the row's threshold.
+constexpr int MN_NEG = 1;
+constexpr int MN_POS = 2;
+
+struct MineArgs {
+    PairTruth truth;          // pose: the column poses [M][2], d_pos, d_neg
+    const double* rpose;      // [R][2] the pose of every row (mine_rowpose_kernel)
+    const double* rbox;       // [ceil(R / 4)][4] the box of every wave's four rows (x lo, x hi, z lo, z hi)
+    const double* cbox;       // [ncc][4] column chunk boxes (eval_colbox_kernel)
+    double lo2, hi2, cut_pos, cut_neg;
+};
+
+// (the row poses and boxes live in memory, not in registers: the top-k instances spill already, and a candidate is
+//  classified only once it beats its row's threshold)
+template <int MINE>
+__device__ __forceinline__ bool mn_class_ok(const MineArgs& m, int r, int c, bool allneg) {
+    if (MINE == MN_NEG && allneg) return true;
+    asm volatile("" : "+v"(r));                        // (keeps the row pose load here: hoisted, it stays live throughout)
+    const double px = m.rpose[2 * (size_t)r], pz = m.rpose[2 * (size_t)r + 1];
+    return classify_pose_exact(m.truth.pose, c, px, pz, m.truth.d_pos, m.truth.d_neg, m.lo2, m.hi2) == (MINE == MN_POS ? 1 : 0);
+}
+
+// tk_push with the pose class of the pair (allneg: every pair of the work item is a negative); c != self_r is part of
+// the window (launch_score_mine passes a window of at least 0).  The four columns are first tested against the row's
+// threshold as it stands, the survivors are classified in one rolled loop (one copy of the float64 code, not four), and
+// the list takes them with the threshold re-tested as it rises.
+template <int K, int MINE>
+__device__ __forceinline__ void mn_push(const MineArgs& m, const float (&sc)[4], int c0, int M, int ea, int eb, bool live,
+                                        int r, bool allneg, float& tv, int& tc, float& thv, int& thc, float* lsv,
+                                        int* lsc) {
+    unsigned cand = 0u;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int c = c0 + b;
+        const float v = MINE == MN_POS ? -sc[b] : sc[b];
+        const bool q = live && c < M && (c < ea || c > eb) && v == v && (K == 1 ? tk_beats(v, c, tv, tc) : tk_beats(v, c, thv, thc));
+        cand |= q ? 1u << b : 0u;
+    }
+    if (cand != 0u && !(MINE == MN_NEG && allneg)) {
+#pragma unroll 1
+        for (int b = 0; b < 4; ++b)
+            if (((cand >> b) & 1u) && !mn_class_ok<MINE>(m, r, c0 + b, false)) cand &= ~(1u << b);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int c = c0 + b;
+        const float v = MINE == MN_POS ? -sc[b] : sc[b];
+        if constexpr (K == 1) {
+            if (((cand >> b) & 1u) && tk_beats(v, c, tv, tc)) {
+                tv = v;
+                tc = c;
+            }
+        } else {
+            const bool q = ((cand >> b) & 1u) && tk_beats(v, c, thv, thc);
+            if (__any(q)) {
+                tk_merge<K>(tv, tc, v, c, q, lsv, lsc);
+                const int src = (threadIdx.x & 48) + K - 1;
+                thv = __shfl(tv, src);
+                thc = __shfl(tc, src);
+            }
+        }
+    }
+}
+
 // the work items [it0, it1) of one R x M rectangle
-// TK = 0: the matrix is stored to score; TK > 0: the scores feed per-row top-TK lists (*tk), nothing is stored;
+// TK = 0: the matrix is stored to score; TK > 0: the scores feed per-row top-TK lists (*tk), nothing is stored; with
+// MINE (MN_NEG / MN_POS) the lists take the mined pairs only (*mn);
 // TK = TK_ABOVE: one pass of the range selection (*ab), nothing is stored; TK = TK_POS / TK_CNT: the evaluation
 // epilogues (*ev), nothing is stored
-template <int NI, int VAR, bool CL, int TK = 0>
+template <int NI, int VAR, bool CL, int TK = 0, int MINE = 0>
 __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k, const bool fast, int R, int M,
                                          const unsigned short* __restrict__ Ab, const unsigned short* __restrict__ Cb,
                                          const float* __restrict__ ur, const float* __restrict__ prow,
                                          const float* __restrict__ pcol, float* __restrict__ score, int64_t ld,
                                          const int it0, const int it1, const TopkArgs* tk = nullptr,
-                                         const AboveArgs* ab = nullptr, EvalArgs* ev = nullptr) {
+                                         const AboveArgs* ab = nullptr, EvalArgs* ev = nullptr,
+                                         const MineArgs* mn = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const f16x8 w1hi = k.w1hi, w1lo = k.w1lo;
@@ -1061,7 +1136,7 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                 if (ab->pass == 2) apos = astart = ab_start(*ab, rg, ncc, it0, it1, r, R);
             }
             if constexpr (TK > 0) {
-                if (cur_rg >= 0) tk_flush<TK>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
+                if (cur_rg >= 0) tk_flush<TK, MINE == MN_POS>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
                 tv = thv = -INFINITY;
                 tc = thc = TK_EMPTY;
                 const int r = rg * AP_ROWS + wave * AP_RW + g;
@@ -1110,7 +1185,17 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
             }
             if (ab->pass == 2 && !ab->flag[it]) continue;
         }
-        bool eneg = false;   // TK_CNT: every pair of this item (and wave) is a negative
+        bool eneg = false;   // TK_CNT / MN_NEG: every pair of this item (and wave) is a negative
+        if constexpr (MINE != 0) {
+            const double* rb = mn->rbox + 4 * (size_t)(rbase >> 2);
+            const double rbv[4] = {rb[0], rb[1], rb[2], rb[3]};
+            const double g2 = ev_gap2(rbv, mn->cbox + 4 * (size_t)cc);
+            if constexpr (MINE == MN_POS) {
+                if (g2 > mn->cut_pos) continue;            // no positive: not even scored
+            } else {
+                eneg = g2 > mn->cut_neg;
+            }
+        }
         if constexpr (TK == TK_POS || TK == TK_CNT) {
             if (ev->truth.pose) {
                 const double g2 = ev_gap2(erb, ev->cbox + 4 * (size_t)cc);
@@ -1150,6 +1235,9 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                         ev_pos_push(*ev, sc, sb * AP_SB + 4 * l15, M, rbase + g < R, rbase + g, epx, epz);
                     else if constexpr (TK == TK_CNT)
                         ev_cnt_push(*ev, sc, sb * AP_SB + 4 * l15, M, rbase + g < R, rbase + g, epx, epz, eneg);
+                    else if constexpr (MINE != 0)
+                        mn_push<TK, MINE>(*mn, sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, rbase + g, eneg, tv,
+                                          tc, thv, thc, lsv, lsc);
                     else
                         tk_push<TK>(sc, sb * AP_SB + 4 * l15, M, ea, eb, rbase + g < R, tv, tc, thv, thc, lsv, lsc);
                 }
@@ -1246,6 +1334,10 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
                 sc[b] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(zsel, nl2e, nb2)));
             }
             const int r = rbase + g, c0 = sb * AP_SB + 4 * l15;
+            if constexpr (TK > 0 && MINE != 0) {
+                mn_push<TK, MINE>(*mn, sc, c0, M, ea, eb, r < R, r, eneg, tv, tc, thv, thc, lsv, lsc);
+                continue;
+            }
             if constexpr (TK > 0) {
                 tk_push<TK>(sc, c0, M, ea, eb, r < R, tv, tc, thv, thc, lsv, lsc);
                 continue;
@@ -1281,7 +1373,7 @@ __device__ __forceinline__ void ap_items(const DevWeights& w, const ApConsts& k,
         }
     }
     if constexpr (TK > 0) {
-        if (cur_rg >= 0) tk_flush<TK>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
+        if (cur_rg >= 0) tk_flush<TK, MINE == MN_POS>(*tk, cur_rg, ncc, it0, it1, rbase + g, R, tv, tc);
     }
     if constexpr (TK == TK_ABOVE) {
         if (cur_rg >= 0) ab_flush(*ab, cur_rg, ncc, it0, it1, rbase + g, R, acnt, apos, astart);
@@ -1379,9 +1471,45 @@ __global__ __launch_bounds__(256, OCC) void score_topk_kernel(const DevWeights w
         ap_items<NI, 0, false, K>(w, k, mode != 0, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, &a);
 }
 
+// the rectangle's mined pairs per row (sgpr_score_mine): score_topk_kernel with the mining conditions (MINE).  At
+// three workgroups per CU (top-k's) the float64 pair test spills 36 - 100 bytes per lane more than top-k's instance of
+// the same K; at two it spills nothing.
+#ifndef SGPR_MN_OCC
+#define SGPR_MN_OCC 2
+#endif
+constexpr int MN_OCC = SGPR_MN_OCC;
+
+template <int OCC, int NI, int K, int MINE>
+__global__ __launch_bounds__(256, OCC) void score_mine_kernel(const DevWeights w, int R, int M,
+                                                              const unsigned short* __restrict__ Ab,
+                                                              const unsigned short* __restrict__ Cb,
+                                                              const float* __restrict__ ur,
+                                                              const float* __restrict__ rng, int nrng,
+                                                              const float* __restrict__ prow,
+                                                              const float* __restrict__ pcol, TopkArgs a, MineArgs m) {
+    const int lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
+    ap_range(rng, nrng, am, um, em, l1);
+    const int mode = ap_mode(am, um, em, l1);
+    const ApConsts k = ap_consts(w, l15, g);
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const unsigned nwg = gridDim.x;
+    const unsigned wg = (nwg & 7u) == 0u ? (blockIdx.x & 7u) * (nwg >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int it0 = (int)(items * wg / nwg), it1 = (int)(items * (wg + 1) / nwg);
+    a.wg = (int)wg;
+    if (mode == 2)
+        ap_items<NI, 0, true, K, MINE>(w, k, true, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, &a, nullptr, nullptr,
+                                       &m);
+    else
+        ap_items<NI, 0, false, K, MINE>(w, k, mode != 0, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, &a, nullptr,
+                                        nullptr, &m);
+}
+
 // row groups shared by several workgroups: their partial lists -> the result.  One workgroup per row group, lane group g
 // of wave v: row 16 rg + 4 v + g.  The workgroups that touched row group rg are a contiguous run of logical indices.
-template <int K>
+template <int K, bool NEG = false>
 __global__ __launch_bounds__(256) void topk_merge_kernel(int R, int M, int nwg, TopkArgs a) {
     __shared__ float sv[4][64];
     __shared__ int sc[4][64];
@@ -1413,7 +1541,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(int R, int M, int nwg, 
         tk_merge<K>(tv, tc, cv, cc, ok && cc != TK_EMPTY, sv[wave], sc[wave]);
     }
     if (r < R && l15 < a.k) {
-        a.val[(size_t)r * a.k + l15] = tv;
+        a.val[(size_t)r * a.k + l15] = NEG ? -tv : tv;
         a.idx[(size_t)r * a.k + l15] = tc == TK_EMPTY ? -1 : tc;
     }
 }
@@ -2279,6 +2407,152 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "eval_fold_kernel launch");
     }
+    return SGPR_OK;
+}
+
+// ------------------------------------------------------------------ fused score + mining (sgpr_score_mine)
+// workspace: sgpr_score_topk's | column boxes [ncc][4] f64 | row poses [R][2] f64 | row boxes [ceil(R / 4)][4] f64
+
+// the pose of every row (d_row_pose[r], or the column pose of its own frame; NaN when that lies outside [0, M)) and the
+// box of every four rows a wave of ap_items takes (ev_row_box's rule: a NaN pose widens the box to the plane)
+__global__ __launch_bounds__(256) void mine_rowpose_kernel(int R, int M, const int32_t* __restrict__ row_self, int row0,
+                                                           const double* __restrict__ row_pose,
+                                                           const double* __restrict__ col_pose, double* __restrict__ rpose,
+                                                           double* __restrict__ rbox) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q * 4 >= R) return;
+    double bx[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
+    for (int r = 4 * q; r < min(R, 4 * q + 4); ++r) {
+        double px, pz;
+        const long long s = row_self ? (long long)row_self[r] : (long long)row0 + r;
+        if (row_pose) {
+            px = row_pose[2 * (size_t)r];
+            pz = row_pose[2 * (size_t)r + 1];
+        } else if (s >= 0 && s < M) {
+            px = col_pose[2 * (size_t)s];
+            pz = col_pose[2 * (size_t)s + 1];
+        } else {
+            px = pz = __longlong_as_double(0x7ff8000000000000LL);
+        }
+        rpose[2 * (size_t)r] = px;
+        rpose[2 * (size_t)r + 1] = pz;
+        const bool nan = px != px || pz != pz;
+        bx[0] = fmin(bx[0], nan ? -INFINITY : px);
+        bx[1] = fmax(bx[1], nan ? INFINITY : px);
+        bx[2] = fmin(bx[2], nan ? -INFINITY : pz);
+        bx[3] = fmax(bx[3], nan ? INFINITY : pz);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rbox[4 * (size_t)q + i] = bx[i];
+}
+__global__ __launch_bounds__(256) void mine_fill_kernel(int64_t n, float v, float* __restrict__ val,
+                                                        int32_t* __restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        val[i] = v;
+        idx[i] = -1;
+    }
+}
+
+size_t score_mine_ws_bytes(const sgpr_handle* h, int R, int M, int k) {
+    if (R == 0 || M == 0) return 0;
+    return align256(score_topk_ws_bytes(h, R, M, k)) + align256((size_t)((M + AP_COLS - 1) / AP_COLS) * 4 * sizeof(double)) +
+           align256((size_t)R * 2 * sizeof(double)) + (size_t)((R + 3) / 4) * 4 * sizeof(double);
+}
+
+int launch_score_mine(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
+                      int row0, int window, int causal, int positives, const double* col_pose, const double* row_pose,
+                      double d_pos, double d_neg, int k, float* val, int32_t* idx, void* ws, hipStream_t stream) {
+    if (R == 0) return SGPR_OK;
+    hipError_t e;
+    if (M == 0) {                                          // no column at all: every slot is empty
+        const int64_t n = (int64_t)R * k;
+        hipLaunchKernelGGL(mine_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n,
+                           positives ? INFINITY : -INFINITY, val, idx);
+        e = hipGetLastError();
+        return e == hipSuccess ? SGPR_OK : hip_fail(e, "mine_fill_kernel launch");
+    }
+    const int ngroups = ap_prep_groups(R, M), nrng = 2 * ngroups, ncc = (M + AP_COLS - 1) / AP_COLS;
+    unsigned char* base = static_cast<unsigned char*>(ws);
+    float* ur = reinterpret_cast<float*>(base);            // the operand layout of launch_score_all_pairs
+    float* rng = ur + (size_t)R * T;
+    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
+    unsigned short* Cb = Ab + (size_t)R * 2 * 64 * 8;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    const int64_t grid = std::min<int64_t>(items, (int64_t)h->num_cus * MN_OCC);   // (<= topk_grid: the lists fit)
+    const size_t lists = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS * k;
+    TopkArgs a;
+    a.row_self = row_self;
+    a.row0 = row0;
+    a.window = window < 0 ? 0 : window;                    // (c != self_r: a window of at least 0 cuts the own frame out)
+    a.causal = causal;
+    a.k = k;
+    a.wg = 0;
+    a.val = val;
+    a.idx = idx;
+    a.pval = reinterpret_cast<float*>(base + align256(score_all_pairs_ws_bytes(R, M)));
+    a.pidx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(a.pval) + align256(lists * sizeof(float)));
+    a.status = h->d_status;
+    MineArgs m;
+    memset(&m, 0, sizeof(m));
+    m.truth.pose = col_pose;
+    m.truth.d_pos = d_pos;
+    m.truth.d_neg = d_neg;
+    double* cbox = reinterpret_cast<double*>(base + align256(score_topk_ws_bytes(h, R, M, k)));
+    double* rpose = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(cbox) + align256((size_t)ncc * 4 * sizeof(double)));
+    double* rbox = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(rpose) + align256((size_t)R * 2 * sizeof(double)));
+    m.cbox = cbox;
+    m.rpose = rpose;
+    m.rbox = rbox;
+    m.lo2 = d_pos * d_pos;
+    m.hi2 = d_neg * d_neg;
+    m.cut_pos = m.lo2 * 1.001;                             // (the evaluation epilogues' margins, launch_score_eval)
+    m.cut_neg = (m.lo2 > m.hi2 ? m.lo2 : m.hi2) * 1.001;
+    hipLaunchKernelGGL(eval_colbox_kernel, dim3((unsigned)ncc), dim3(64), 0, stream, col_pose, M, cbox);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "eval_colbox_kernel launch");
+    hipLaunchKernelGGL(mine_rowpose_kernel, dim3((unsigned)(((R + 3) / 4 + 255) / 256)), dim3(256), 0, stream, R, M, row_self,
+                       row0, row_pose, col_pose, rpose, rbox);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "mine_rowpose_kernel launch");
+    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+    const dim3 gd((unsigned)grid), bd(256), gm((unsigned)((R + AP_ROWS - 1) / AP_ROWS));
+    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;  // the compiled instance: the first k of its K entries
+#define SGPR_MINE(KK, MM) hipLaunchKernelGGL((score_mine_kernel<MN_OCC, AP_NI, KK, MM>), gd, bd, 0, stream, h->w, R, M, Ab, \
+                                             Cb, ur, rng, nrng, rows, cols, a, m)
+    if (positives) {
+        switch (K) {
+            case 1: SGPR_MINE(1, MN_POS); break;
+            case 4: SGPR_MINE(4, MN_POS); break;
+            case 8: SGPR_MINE(8, MN_POS); break;
+            default: SGPR_MINE(16, MN_POS); break;
+        }
+    } else {
+        switch (K) {
+            case 1: SGPR_MINE(1, MN_NEG); break;
+            case 4: SGPR_MINE(4, MN_NEG); break;
+            case 8: SGPR_MINE(8, MN_NEG); break;
+            default: SGPR_MINE(16, MN_NEG); break;
+        }
+    }
+#undef SGPR_MINE
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "score_mine_kernel launch");
+    // (the lists of the negatives are top-k's: its merge instances; the positives' take the negating ones)
+    switch (K + (positives ? 100 : 0)) {
+        case 1: hipLaunchKernelGGL((topk_merge_kernel<1>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 4: hipLaunchKernelGGL((topk_merge_kernel<4>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 8: hipLaunchKernelGGL((topk_merge_kernel<8>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 16: hipLaunchKernelGGL((topk_merge_kernel<16>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 101: hipLaunchKernelGGL((topk_merge_kernel<1, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 104: hipLaunchKernelGGL((topk_merge_kernel<4, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+        case 108: hipLaunchKernelGGL((topk_merge_kernel<8, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+        default: hipLaunchKernelGGL((topk_merge_kernel<16, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "topk_merge_kernel launch");
     return SGPR_OK;
 }
 

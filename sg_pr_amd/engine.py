@@ -43,6 +43,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_pair_positives", "sgpr_pair_threshold_counts_workspace_bytes", "sgpr_pair_threshold_counts",
                "sgpr_f1_max_workspace_bytes", "sgpr_f1_max", "sgpr_topk_rows",
                "sgpr_score_topk_workspace_bytes", "sgpr_score_topk",
+               "sgpr_score_mine_workspace_bytes", "sgpr_score_mine", "sgpr_mine_rows_workspace_bytes", "sgpr_mine_rows",
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
                "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
                "sgpr_score_threshold_counts_workspace_bytes", "sgpr_score_threshold_counts",
@@ -173,6 +174,14 @@ def load_library():
     lib.sgpr_score_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
     lib.sgpr_score_topk.restype = i32
     lib.sgpr_score_topk.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.sgpr_score_mine_workspace_bytes.restype = sz
+    lib.sgpr_score_mine_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
+    lib.sgpr_score_mine.restype = i32
+    lib.sgpr_score_mine.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, sz, vp]
+    lib.sgpr_mine_rows_workspace_bytes.restype = sz
+    lib.sgpr_mine_rows_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
+    lib.sgpr_mine_rows.restype = i32
+    lib.sgpr_mine_rows.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, sz, vp]
     f32 = ctypes.c_float
     lib.sgpr_score_above_workspace_bytes.restype = sz
     lib.sgpr_score_above_workspace_bytes.argtypes = [vp, i32, i32, i32]
@@ -909,6 +918,75 @@ class Engine:
         ws = self._ws(ws_bytes)
         rc = self.lib.sgpr_score_topk(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window), flags,
                                       int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        return vals, idx
+
+    MINE_NEGATIVES = 2  # SGPR_MINE_NEGATIVES of include/sgpr.h
+    MINE_POSITIVES = 4  # SGPR_MINE_POSITIVES
+
+    def _mine_flags(self, positives, causal):
+        return (self.MINE_POSITIVES if positives else self.MINE_NEGATIVES) | (self.TOPK_CAUSAL if causal else 0)
+
+    def _mine_poses(self, col_pose, row_pose, r, m):
+        """[.,12] KITTI or [.,2] planar poses -> float64 (x, z) device tensors ([m,2] columns, [r,2] rows or None)"""
+        def planar(p, n, name):
+            p = torch.as_tensor(p) if not isinstance(p, torch.Tensor) else p
+            if p.dim() != 2 or p.shape[1] not in (2, 12) or p.shape[0] != n:
+                raise ValueError("%s must be [%d, 12] (KITTI 3x4) or [%d, 2] planar (x, z), got %s"
+                                 % (name, n, n, tuple(p.shape)))
+            if p.shape[1] == 12:
+                p = p[:, [3, 11]]
+            return self._dev(p, torch.float64, name)
+        return planar(col_pose, m, "col_pose"), None if row_pose is None else planar(row_pose, r, "row_pose")
+
+    def score_mine_workspace_bytes(self, r, m, k=1, positives=False, causal=False):
+        return int(self.lib.sgpr_score_mine_workspace_bytes(self._h, int(r), int(m), int(k),
+                                                            self._mine_flags(positives, causal)))
+
+    def score_mine(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
+                   row0=0, causal=False, row_self=None, row_pose=None):
+        """The k hardest pose-labelled pairs per row of pooled_rows x pooled_cols without forming the matrix
+        (sgpr_score_mine).  Column c is eligible for row r iff it is for score_topk and c != self_r; the pair's class
+        comes from the float64 distance of the row pose (row_pose[r], else col_pose[self_r]) to col_pose[c].
+        positives=False: negatives (distance >= d_neg), highest score first; (-inf, -1) in empty slots.
+        positives=True: positives (distance <= d_pos), lowest score first; (+inf, -1) in empty slots.
+        Poses are [.,12] KITTI or [.,2] planar.  -> (values f32 [R,k], indices i32 [R,k]); every value is
+        bit-identical to score_all_pairs' entry (r, c)."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        cp, rp = self._mine_poses(col_pose, row_pose, r, m)
+        rs = self._row_self(row_self, r)
+        flags = self._mine_flags(positives, causal)
+        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
+        ws_bytes = self.lib.sgpr_score_mine_workspace_bytes(self._h, r, m, int(k), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_score_mine(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(cp), _ptr(rp), _ptr(rs), int(row0),
+                                      int(window), flags, float(d_pos), float(d_neg), int(k), _ptr(vals), _ptr(idx),
+                                      _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        return vals, idx
+
+    def mine_rows(self, score, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1, row0=0, causal=False,
+                  row_self=None, row_pose=None):
+        """score_mine's selection on a resident matrix score [R, M] (sgpr_mine_rows; any row stride >= M with unit
+        column stride is read in place) -> (values f32 [R,k], indices i32 [R,k])."""
+        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
+                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
+            score = self._dev(score, torch.float32, "score")
+        r, m = score.shape
+        ld = max(score.stride(0), m)
+        cp, rp = self._mine_poses(col_pose, row_pose, r, m)
+        rs = self._row_self(row_self, r)
+        flags = self._mine_flags(positives, causal)
+        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
+        ws_bytes = self.lib.sgpr_mine_rows_workspace_bytes(self._h, r, m, int(k), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_mine_rows(self._h, _ptr(score), r, m, ld, _ptr(cp), _ptr(rp), _ptr(rs), int(row0),
+                                     int(window), flags, float(d_pos), float(d_neg), int(k), _ptr(vals), _ptr(idx),
+                                     _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         return vals, idx
 

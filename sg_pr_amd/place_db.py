@@ -12,11 +12,14 @@ A vector costs 128 bytes of device memory (the matrix of a 100 k-graph map would
 the architecture and a sha256 of the checkpoint's weight blob: vectors of one checkpoint are meaningless to another, so
 `load` refuses them.
 
-    python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T]
+    python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K; with --threshold also `<seq>_above.npz` with every pair scoring
->= T (rows, cols, scores) and its precision / recall (metrics.precision_recall_at).
+>= T (rows, cols, scores) and its precision / recall (metrics.precision_recall_at); with --hard K also `<seq>_hard.npz`
+with every frame's K hardest negatives (highest scores at >= 20 m) and K hardest positives (lowest scores within
+p_thresh), indices and scores (Engine.score_mine; the window applies to both), and the number of frames that have a
+negative scoring above their best positive.
 """
 import argparse
 import hashlib
@@ -91,6 +94,14 @@ class PlaceDatabase:
         return self.eng.score_topk(rows, self.pooled, k=k, window=window, causal=causal,
                                    row_self=ids.to(torch.int32))
 
+    def query_ids_hard(self, ids, poses, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1, causal=False):
+        """The k hardest negatives (positives=True: positives) of stored members ids among all members
+        (Engine.score_mine with row_self = ids); poses [len, 12] or [len, 2] of every member."""
+        ids = torch.as_tensor(ids, dtype=torch.int64, device=self.eng.device)
+        rows = self.pooled.index_select(0, ids)
+        return self.eng.score_mine(rows, self.pooled, poses, k=k, positives=positives, d_pos=d_pos, d_neg=d_neg,
+                                   window=window, causal=causal, row_self=ids.to(torch.int32))
+
     def query_above(self, centers, labels, threshold, window=-1, causal=False):
         """Every member scoring >= threshold for graphs that are NOT in the database (frames len(db), len(db) + 1, ...)
         -> (rows i32 [n], ids i32 [n], scores f32 [n], row_ptr i64 [g+1]) on the device (engine.Engine.score_above)."""
@@ -135,6 +146,8 @@ def main(argv=None):
     ap.add_argument("--window", type=int, default=50)
     ap.add_argument("--causal", action="store_true")
     ap.add_argument("--threshold", type=float, default=None)
+    ap.add_argument("--hard", type=int, default=None, metavar="K",
+                    help="also write <seq>_hard.npz: every frame's K hardest negatives and positives (1..16)")
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
     args = sgpr_args()
     args.load(opt.config)
@@ -168,7 +181,30 @@ def main(argv=None):
                      cols=cols.cpu().numpy(), scores=scores.cpu().numpy(), precision=precision, recall=rec)
             print("sequence", sequence, "threshold", opt.threshold, "pairs", rows.numel(),
                   "precision %.4f recall %.4f" % (precision, rec))
+        if opt.hard is not None:
+            hard = hard_pairs_of(db, seq.poses, opt.hard, float(args.p_thresh), window=opt.window, causal=opt.causal)
+            np.savez(os.path.join(args.output_path, sequence + "_hard.npz"), frame=np.arange(m), **hard)
+            print("sequence", sequence, "hard pairs k", opt.hard, "frames with a negative above their best positive",
+                  int(hard["neg_above_pos"].sum()), "(exact: %d frames of %d)" % (int(hard["exact"].sum()), m))
     return results
+
+
+def hard_pairs_of(db, poses, k, p_thresh, window=-1, causal=False):
+    """Every member's k hardest negatives and positives (one mining call each) -> dict of numpy arrays:
+    neg_indices / neg_scores, pos_indices / pos_scores [M, k] (-1 / -inf / +inf where a frame has fewer), and per frame
+    neg_above_pos: its hardest negative scores above its best positive.  The best positive is the highest of the mined
+    ones: the frame's best overall when it has at most k positives (exact), else a lower bound of it."""
+    from .train import NEG_DISTANCE
+    ids = torch.arange(len(db))
+    nv, ni = db.query_ids_hard(ids, poses, k=k, positives=False, d_pos=p_thresh, d_neg=NEG_DISTANCE, window=window,
+                               causal=causal)
+    pv, pi = db.query_ids_hard(ids, poses, k=k, positives=True, d_pos=p_thresh, d_neg=NEG_DISTANCE, window=window,
+                               causal=causal)
+    nv, ni, pv, pi = nv.cpu().numpy(), ni.cpu().numpy(), pv.cpu().numpy(), pi.cpu().numpy()
+    best_pos = np.where(pi >= 0, pv, -np.inf).max(axis=1)
+    has_pos, has_neg = pi[:, 0] >= 0, ni[:, 0] >= 0
+    return {"neg_indices": ni, "neg_scores": nv, "pos_indices": pi, "pos_scores": pv,
+            "neg_above_pos": has_pos & has_neg & (nv[:, 0] > best_pos), "exact": pi[:, -1] < 0}
 
 
 if __name__ == "__main__":

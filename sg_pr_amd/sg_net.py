@@ -152,6 +152,14 @@ class SG(torch.nn.Module):
         return self.engine().score_topk(pooled_rows, pooled_cols, k=k, window=window, row0=row0, causal=causal,
                                         row_self=row_self)
 
+    def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
+                   row0=0, causal=False, row_self=None, row_pose=None):
+        """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming
+        the matrix (engine.Engine.score_mine) -> (values f32 [R,k], indices i32 [R,k]) on the device."""
+        return self.engine().score_mine(pooled_rows, pooled_cols, col_pose, k=k, positives=positives, d_pos=d_pos,
+                                        d_neg=d_neg, window=window, row0=row0, causal=causal, row_self=row_self,
+                                        row_pose=row_pose)
+
     def loop_closures_above(self, pooled_rows, pooled_cols, threshold, window=-1, row0=0, causal=False, row_self=None,
                             capacity=None):
         """Every pair of pooled_rows x pooled_cols scoring >= threshold, without forming the matrix

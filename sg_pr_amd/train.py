@@ -19,6 +19,7 @@ import json
 import math
 import os
 import sys
+import time
 from collections import OrderedDict
 
 import numpy as np
@@ -278,15 +279,22 @@ def _planar(poses):
 
 class PairSet(object):
     """Packed graphs (centers f32 [G,N,3], labels i32 [G,N], -1 = pad), their poses and the train / eval pair index
-    arrays [P,2] into them: what SGFitter trains on.  Targets follow the reference's rule (target_of)."""
+    arrays [P,2] into them: what SGFitter trains on.  Targets follow the reference's rule (target_of).
+    sequence: one id per graph (int [G]): poses of different sequences are in different frames, so hard pairs are mined
+    within one sequence only; None = one sequence."""
 
-    def __init__(self, centers, labels, poses, train_pairs, eval_pairs, p_thresh=3.0):
+    def __init__(self, centers, labels, poses, train_pairs, eval_pairs, p_thresh=3.0, sequence=None):
         self.centers = np.ascontiguousarray(centers, dtype=np.float32)
         self.labels = np.ascontiguousarray(labels, dtype=np.int32)
         xz = _planar(poses)
         if self.centers.ndim != 3 or self.centers.shape[2] != 3 or self.labels.shape != self.centers.shape[:2] or \
                 len(xz) != len(self.labels):
             raise ValueError("centers [G,N,3], labels [G,N] and poses [G,.] must describe the same G graphs")
+        self.xz = np.ascontiguousarray(xz, dtype=np.float64)
+        self.p_thresh = float(p_thresh)
+        self.sequence = None if sequence is None else np.asarray(sequence, dtype=np.int64).reshape(-1)
+        if self.sequence is not None and len(self.sequence) != len(self.labels):
+            raise ValueError("sequence must hold one id per graph (%d), got %d" % (len(self.labels), len(self.sequence)))
         self.train_pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
         self.eval_pairs = np.asarray(eval_pairs, dtype=np.int64).reshape(-1, 2)
         for pairs in (self.train_pairs, self.eval_pairs):
@@ -304,18 +312,22 @@ class PairSet(object):
     def from_files(cls, args, number_of_labels=NUM_LABELS):
         """The reference's file layer (sg_net.py:182-199): <pair_list_dir>/<seq>.txt for train_sequences and
         eval_sequences (utils.load_paires), graph JSONs under graph_pairs_dir.  Every graph is read and packed once."""
+        seq_id = {}
+
         def lists(seqs):
             out = []
             for sq in seqs:
-                out.extend(load_paires(os.path.join(args.pair_list_dir, str(sq) + ".txt"), args.graph_pairs_dir))
+                sid = seq_id.setdefault(str(sq), len(seq_id))
+                out.extend((a, b, sid) for a, b in load_paires(os.path.join(args.pair_list_dir, str(sq) + ".txt"),
+                                                              args.graph_pairs_dir))
             return out
 
         train, evl = lists(args.train_sequences), lists(args.eval_sequences)
         if not train or not evl:
             raise ValueError("no training or no evaluation pairs (train_sequences / eval_sequences / pair_list_dir)")
-        slot, centers, labels, poses = {}, [], [], []
+        slot, centers, labels, poses, sequence = {}, [], [], [], []
 
-        def index(path):
+        def index(path, sid):
             if path not in slot:
                 d = read_graph(path)
                 c, l = pack_graph(d["centers"], d["nodes"], int(args.node_num), number_of_labels)
@@ -323,11 +335,38 @@ class PairSet(object):
                 centers.append(c)
                 labels.append(l)
                 poses.append(d["pose"])
+                sequence.append(sid)             # (a graph file lives in its sequence's list: the first one naming it)
             return slot[path]
 
-        tp = [[index(a), index(b)] for a, b in train]
-        ep = [[index(a), index(b)] for a, b in evl]
-        return cls(np.stack(centers), np.stack(labels), np.asarray(poses, dtype=np.float64), tp, ep, args.p_thresh)
+        tp = [[index(a, s), index(b, s)] for a, b, s in train]
+        ep = [[index(a, s), index(b, s)] for a, b, s in evl]
+        return cls(np.stack(centers), np.stack(labels), np.asarray(poses, dtype=np.float64), tp, ep, args.p_thresh,
+                   sequence=np.asarray(sequence, dtype=np.int64))
+
+
+def mined_pairs(groups, base_pairs):
+    """Mined lists -> new unordered training pairs (pure function).
+    groups: [(members int [n], indices int [n, k]), ...] - row r of a mining call over the graphs `members` (rows = columns
+    = one sequence) listed columns indices[r] (-1 = empty slot).  Every (members[r], members[c]) becomes the unordered pair
+    (min, max); duplicates and the pairs already in base_pairs (in either order) are dropped.  -> int64 [P, 2], sorted."""
+    out = []
+    for members, idx in groups:
+        members = np.asarray(members, dtype=np.int64)
+        idx = np.asarray(idx, dtype=np.int64)
+        r, c = np.nonzero(idx >= 0)
+        a, b = members[r], members[idx[r, c]]
+        out.append(np.stack((np.minimum(a, b), np.maximum(a, b)), axis=1))
+    pairs = np.concatenate(out) if out else np.zeros((0, 2), np.int64)
+    pairs = pairs[pairs[:, 0] != pairs[:, 1]]
+    if len(pairs) == 0:
+        return np.zeros((0, 2), np.int64)
+    pairs = np.unique(pairs, axis=0)
+    base = np.asarray(base_pairs, dtype=np.int64).reshape(-1, 2)
+    if len(base):
+        key = lambda p: p[:, 0] * (1 << 32) + p[:, 1]                                        # noqa: E731
+        known = key(np.stack((base.min(1), base.max(1)), axis=1))
+        pairs = pairs[~np.isin(key(pairs), known)]
+    return pairs
 
 
 def batches_of(n, batch_size, rng):
@@ -352,8 +391,15 @@ class SGFitter(object):
 
     LOG_NAME = "train_log.jsonl"
 
-    def __init__(self, args, init=None, seed=0, data=None):
+    def __init__(self, args, init=None, seed=0, data=None, hard_negatives=0, hard_positives=0, mine_every=2):
         self.args = args
+        self.hard_negatives, self.hard_positives = int(hard_negatives), int(hard_positives)
+        self.mine_every = int(mine_every)
+        for k in (self.hard_negatives, self.hard_positives):
+            if k < 0 or k > 16:
+                raise ValueError("hard_negatives / hard_positives must lie in 0..16 (the mining lists' length)")
+        if self.mine_every < 1:
+            raise ValueError("mine_every must be >= 1")
         self.seed = int(seed)
         self.number_of_labels = NUM_LABELS
         self.device = torch.device("cuda", int(getattr(args, "gpu", 0)))
@@ -374,6 +420,7 @@ class SGFitter(object):
         self.augment = True
         self.optimizer = torch.optim.Adam(self.model.parameters(), lr=args.learning_rate, weight_decay=args.weight_decay)
         self.f1_max_best = 0.0
+        self.last_mined = None       # the latest self.mine() of fit (pairs, targets, lists, seconds)
 
     # ---------------------------------------------------------------- one batch
     def batch(self, pairs, training=True):
@@ -385,12 +432,15 @@ class SGFitter(object):
             centers = augment(centers, self.generator)
         return dense_features(centers, labels, self.number_of_labels), centers, labels
 
-    def step(self, pair_ids):
-        """process_batch(training=True) (sg_net.py:358-387) on the train pairs pair_ids -> loss (float)."""
+    def step(self, pair_ids, pairs=None, targets=None):
+        """process_batch(training=True) (sg_net.py:358-387) on the train pairs pair_ids -> loss (float).
+        pairs / targets: the epoch's pair list when it is not data.train_pairs (base + mined pairs)."""
         self.model.train()
-        pairs = self.data.train_pairs[pair_ids]
+        pairs_all = self.data.train_pairs if pairs is None else pairs
+        targets_all = self.data.train_targets if targets is None else targets
+        pairs = pairs_all[pair_ids]
         feats, _, _ = self.batch(pairs, True)
-        target = torch.from_numpy(self.data.train_targets[pair_ids]).to(self.device)
+        target = torch.from_numpy(targets_all[pair_ids]).to(self.device)
         self.optimizer.zero_grad(set_to_none=True)
         loss, _, _ = train_loss(self.model, feats, target)
         loss.backward()
@@ -430,6 +480,48 @@ class SGFitter(object):
         print("\nModel " + split + " loss: " + str(loss) + ".")
         return loss, f1
 
+    # ---------------------------------------------------------------- hard-pair mining
+    def mine(self):
+        """The hardest pairs of the current weights (Engine.score_mine): the model in eval mode embeds, without
+        augmentation, the graphs that appear in train_pairs on the inference engine; per sequence, every graph takes its
+        hard_negatives highest-scoring graphs at >= 20 m and its hard_positives lowest-scoring graphs within p_thresh.
+        No BatchNorm statistic moves and self.generator is not drawn from.
+        -> {"pairs" int64 [P,2] (new unordered pairs, base pairs dropped), "targets" f32 [P], "lists": [(sequence id,
+        members, positives, values, indices), ...], "seconds"}"""
+        t0 = time.perf_counter()
+        data = self.data
+        used = np.unique(data.train_pairs)
+        seq = data.sequence if data.sequence is not None else np.zeros(len(data.labels), np.int64)
+        was_training = self.model.training
+        self.model.eval()
+        lists, groups = [], []
+        try:
+            with torch.no_grad():
+                eng = self.model.engine()
+                for sid in np.unique(seq[used]):
+                    members = used[seq[used] == sid]
+                    g = torch.from_numpy(members).to(self.device)
+                    pooled, _, _ = self.model.embed(self.centers[g], self.labels[g])
+                    eng.check_status()
+                    for positives, k in ((False, self.hard_negatives), (True, self.hard_positives)):
+                        if k == 0:
+                            continue
+                        v, i = eng.score_mine(pooled, pooled, data.xz[members], k=k, positives=positives,
+                                              d_pos=data.p_thresh, d_neg=NEG_DISTANCE)
+                        v, i = v.cpu().numpy(), i.cpu().numpy()
+                        lists.append((int(sid), members, positives, v, i))
+                        groups.append((members, i))
+        finally:
+            if was_training:
+                self.model.train()
+        pairs = mined_pairs(groups, data.train_pairs)
+        targets = PairSet._targets(data.xz, pairs, data.p_thresh)
+        return {"pairs": pairs, "targets": targets, "lists": lists, "seconds": time.perf_counter() - t0}
+
+    def _mines(self, epoch):
+        return (self.hard_negatives > 0 or self.hard_positives > 0) and epoch >= self.mine_every and \
+            epoch % self.mine_every == 0
+
     # ---------------------------------------------------------------- the loop
     def _log(self, record):
         os.makedirs(self.args.logdir, exist_ok=True)
@@ -445,13 +537,25 @@ class SGFitter(object):
     def fit(self, epochs=None):
         """fit (sg_net.py:389-410): Adam(lr, weight_decay); every epoch one shuffled pass over the train pairs; every
         second epoch (0, 2, ...) score("eval"), <epoch>.pth, and <epoch>_best.pth when F1-max >= the best so far.
-        Progress goes to <logdir>/train_log.jsonl, one JSON object per line."""
+        Progress goes to <logdir>/train_log.jsonl, one JSON object per line.  With hard_negatives / hard_positives, every
+        epoch e >= mine_every with e % mine_every == 0 first mines (self.mine) and trains on the base plus the mined
+        pairs; the log records their count and the time mining took."""
         epochs = int(self.args.epochs if epochs is None else epochs)
         bs = int(self.args.batch_size)
         for epoch in range(epochs):
             seen, loss_sum = 0, 0.0
-            for ids in batches_of(len(self.data.train_pairs), bs, self.rng):
-                loss = self.step(ids)
+            pairs = targets = None
+            if self._mines(epoch):
+                mined = self.mine()
+                self.last_mined = mined
+                pairs = np.concatenate((self.data.train_pairs, mined["pairs"]))
+                targets = np.concatenate((self.data.train_targets, mined["targets"]))
+                self._log({"epoch": epoch, "mined_pairs": int(len(mined["pairs"])),
+                           "mined_negatives": int((mined["targets"] == 0).sum()),
+                           "mined_positives": int((mined["targets"] == 1).sum()), "mine_seconds": mined["seconds"]})
+            n = len(self.data.train_pairs) if pairs is None else len(pairs)
+            for ids in batches_of(n, bs, self.rng):
+                loss = self.step(ids, pairs, targets)
                 seen += len(ids)
                 loss_sum += loss * len(ids)
                 self._log({"epoch": epoch, "pairs": seen, "loss": loss, "loss_avg": loss_sum / seen})
@@ -473,6 +577,12 @@ def parse_cli(argv=None):
     p.add_argument("--epochs", type=int, default=None, help="override train.epochs of the config")
     p.add_argument("--init", default=None, help="checkpoint to fine-tune from (default: a fresh model)")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--hard-negatives", type=int, default=0, metavar="K",
+                   help="per graph and mining epoch, add its K highest-scoring pairs at >= 20 m (0..16; default 0: off)")
+    p.add_argument("--hard-positives", type=int, default=0, metavar="K",
+                   help="per graph and mining epoch, add its K lowest-scoring pairs within p_thresh (0..16; default 0)")
+    p.add_argument("--mine-every", type=int, default=2, metavar="E",
+                   help="mine at the start of every epoch e >= E with e %% E == 0 (default 2)")
     return p.parse_args(argv)
 
 
@@ -485,7 +595,8 @@ def main(argv=None):
     if cli.epochs is not None:
         args.epochs = cli.epochs
     tab_printer(args)
-    fitter = SGFitter(args, init=cli.init, seed=cli.seed)
+    fitter = SGFitter(args, init=cli.init, seed=cli.seed, hard_negatives=cli.hard_negatives,
+                      hard_positives=cli.hard_positives, mine_every=cli.mine_every)
     fitter.fit()
     fitter.score()
     return fitter
