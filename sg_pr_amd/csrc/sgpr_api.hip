@@ -39,6 +39,24 @@ int hip_fail(hipError_t e, const char* what) {
     return SGPR_E_HIP;
 }
 
+// the caller's workspace holds the `need` bytes entry point fn asks for (need 0: any pointer, NULL included)
+static bool workspace_ok(const char* fn, size_t need, const void* ws, size_t ws_bytes) {
+    if (need > 0 && (!ws || ws_bytes < need)) {
+        set_error(std::string(fn) + ": workspace of " + std::to_string(need) + " bytes required");
+        return false;
+    }
+    return true;
+}
+
+// global row indices row0 .. row0 + R fit an int
+static bool row0_ok(const char* fn, int row0, int R) {
+    if ((int64_t)row0 + R > 0x7fffffffLL) {
+        set_error(std::string(fn) + ": row0 + R must fit an int");
+        return false;
+    }
+    return true;
+}
+
 // The kernels are written for {12, 64, 64, 32, 16, 16}.  A SMALLER architecture is served exactly by the same kernels:
 // its tensors are embedded into the built shapes with zero weights (and neutral BatchNorm statistics) for the channels
 // it does not have - a channel whose weights are all zero stays 0 through conv / BN / LeakyReLU, adds 0 to every
@@ -1096,11 +1114,8 @@ int sgpr_score_pair_list(const sgpr_handle* h, const float* d_pooled_rows, int R
         return launch_score_plan_generic(h, d_pooled_rows, d_pooled_cols, d_plan, n_rows, n_items, P, d_score,
                                          static_cast<hipStream_t>(stream));
     }
-    const size_t need = score_pair_list_ws_bytes(n_rows, M);
-    if (!d_workspace || workspace_bytes < need) {
-        set_error("sgpr_score_pair_list: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_score_pair_list", score_pair_list_ws_bytes(n_rows, M), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     DeviceGuard guard(h->device);
     // (a wide-range tail: the kernel's exact fp32 per-pair arithmetic - the f16 planes are not this handle's, and there is
     //  no three-plane instance of the list kernel)
@@ -1140,11 +1155,8 @@ int sgpr_score_all_pairs(const sgpr_handle* h, const float* d_pooled_rows, int R
         return score_rect_any_shape(h, d_pooled_rows, R, d_pooled_cols, M, d_score, ld, d_workspace, workspace_bytes,
                                     static_cast<hipStream_t>(stream));
     }
-    const size_t need = score_all_pairs_ws_bytes(R, M);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_score_all_pairs: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_score_all_pairs", score_all_pairs_ws_bytes(R, M), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     DeviceGuard guard(h->device);
     // (debug bit 13 / weights or head outside the f16 range: the instance with three bf16 planes per operand, as for the embed)
     return launch_score_all_pairs(h, d_pooled_rows, R, d_pooled_cols, M, d_score, ld, d_workspace,
@@ -1167,25 +1179,53 @@ static int check_jobs(const sgpr_handle* h, int n, const sgpr_pairs_job* jobs) {
     return SGPR_OK;
 }
 
-// ---- sgpr_score_topk: the fused kernel on the production handle; the other handles score bounded row blocks with their
-//      own tail into the workspace and select from each block (the same selection, bit-equal to matrix + top-k)
-static const size_t kTopkBlockBytes = (size_t)64 << 20;    // score block of the chunked path
+// ---- the fused epilogues of the all-pairs tail (sgpr_score_topk, _mine, _above, _positives, _threshold_counts) run on
+//      the production handle.  The other handles (wide-range, any-shape) score bounded row blocks with their own tail
+//      and hand each block to the epilogue's matrix kernel (the same selection, bit-equal to matrix + selection).
+static const size_t kScoreBlockBytes = (size_t)64 << 20;   // score block of the row-block path
 
-static bool topk_fused(const sgpr_handle* h) { return !h->generic_only && !tail_wide(h); }
+static bool has_fused_epilogues(const sgpr_handle* h) { return !h->generic_only && !tail_wide(h); }
 
-static int topk_block_rows(int R, int M) {
-    const size_t rows = kTopkBlockBytes / ((size_t)M * sizeof(float));
+static int score_block_rows(int R, int M) {
+    const size_t rows = kScoreBlockBytes / ((size_t)M * sizeof(float));
     return (int)std::max<size_t>(1, std::min<size_t>((size_t)R, rows));
 }
 
 static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// row-block path layout: score block [rb][M] | the caller's head (head_bytes) | the block's all-pairs workspace
+static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t head_bytes) {
+    const int rb = score_block_rows(R, M);
+    return a256((size_t)rb * M * sizeof(float)) + head_bytes + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
+}
+
+// sgpr_score_all_pairs on rows [r0, r0 + n) of the rectangle, one block after the other, each followed by
+// consume(block, head, r0, n): block [n][M] (ld M), head the caller's region of the workspace
+extern "C++" {   // (a template, inside the C-ABI block)
+template <class Consume>
+static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, size_t head_bytes,
+                            void* ws, size_t ws_bytes, void* stream, Consume&& consume) {
+    const int rb = score_block_rows(R, M), pw = pooled_width(h);
+    const size_t block_bytes = a256((size_t)rb * M * sizeof(float));
+    float* block = static_cast<float*>(ws);
+    unsigned char* head = static_cast<unsigned char*>(ws) + block_bytes;
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = std::min(rb, R - r0);
+        int rc = sgpr_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, head + head_bytes,
+                                      ws_bytes - block_bytes - head_bytes, stream);
+        if (rc != SGPR_OK) return rc;
+        rc = consume(block, head, r0, n);
+        if (rc != SGPR_OK) return rc;
+    }
+    return SGPR_OK;
+}
+}  // extern "C++"
+
 size_t sgpr_score_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
     if (!h || R < 0 || M < 0 || k < 1 || k > 16 || (flags & ~SGPR_TOPK_CAUSAL)) return 0;
     if (R == 0 || M == 0) return 0;
-    if (topk_fused(h)) return score_topk_ws_bytes(h, R, M, k);
-    const int rb = topk_block_rows(R, M);
-    return a256((size_t)rb * M * sizeof(float)) + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
+    if (has_fused_epilogues(h)) return score_topk_ws_bytes(h, R, M, k);
+    return row_blocks_ws_bytes(h, R, M, 0);
 }
 
 int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1203,35 +1243,21 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
         set_error("sgpr_score_topk: unknown flag bits " + std::to_string(flags & ~SGPR_TOPK_CAUSAL));
         return SGPR_E_INVALID;
     }
-    if ((int64_t)row0 + R > 0x7fffffffLL) {
-        set_error("sgpr_score_topk: row0 + R must fit an int");
-        return SGPR_E_INVALID;
-    }
-    const size_t need = sgpr_score_topk_workspace_bytes(h, R, M, k, flags);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_score_topk: workspace of " + std::to_string(need) + " bytes required");
+    if (!row0_ok("sgpr_score_topk", row0, R)) return SGPR_E_INVALID;
+    if (!workspace_ok("sgpr_score_topk", sgpr_score_topk_workspace_bytes(h, R, M, k, flags), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     if (R == 0) return SGPR_OK;
     const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0 || topk_fused(h))
+    if (M == 0 || has_fused_epilogues(h))
         return launch_score_topk(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, k, d_values,
                                  d_indices, d_workspace, s);
-    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
-    float* block = static_cast<float*>(d_workspace);
-    unsigned char* ws = static_cast<unsigned char*>(d_workspace) + a256((size_t)rb * M * sizeof(float));
-    const size_t ws_bytes = workspace_bytes - a256((size_t)rb * M * sizeof(float));
-    for (int r0 = 0; r0 < R; r0 += rb) {
-        const int n = std::min(rb, R - r0);
-        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
-        if (rc != SGPR_OK) return rc;
-        rc = launch_topk_rows_ext(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, k,
-                                  d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
-        if (rc != SGPR_OK) return rc;
-    }
-    return SGPR_OK;
+    auto select = [&](const float* block, unsigned char*, int r0, int n) {
+        return launch_topk_rows_ext(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, k,
+                                    d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, 0, d_workspace, workspace_bytes, stream, select);
 }
 
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks
@@ -1263,19 +1289,14 @@ static bool mine_args_ok(const char* fn, const sgpr_handle* h, int R, int M, con
         set_error(std::string(fn) + ": d_pos / d_neg NaN, d_pos < 0 or d_pos > d_neg");
         return false;
     }
-    if ((int64_t)row0 + R > 0x7fffffffLL) {
-        set_error(std::string(fn) + ": row0 + R must fit an int");
-        return false;
-    }
-    return true;
+    return row0_ok(fn, row0, R);
 }
 
 size_t sgpr_score_mine_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
     if (!h || R < 0 || M < 0 || k < 1 || k > 16 || !mine_flags_ok(flags)) return 0;
     if (R == 0 || M == 0) return 0;
-    if (topk_fused(h)) return score_mine_ws_bytes(h, R, M, k);
-    const int rb = topk_block_rows(R, M);
-    return a256((size_t)rb * M * sizeof(float)) + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
+    if (has_fused_epilogues(h)) return score_mine_ws_bytes(h, R, M, k);
+    return row_blocks_ws_bytes(h, R, M, 0);
 }
 
 int sgpr_score_mine(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1288,32 +1309,21 @@ int sgpr_score_mine(const sgpr_handle* h, const float* d_pooled_rows, int R, con
         set_error("sgpr_score_mine: NULL pooled array");
         return SGPR_E_INVALID;
     }
-    const size_t need = sgpr_score_mine_workspace_bytes(h, R, M, k, flags);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_score_mine: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_score_mine", sgpr_score_mine_workspace_bytes(h, R, M, k, flags), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     if (R == 0) return SGPR_OK;
     const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, positives = (flags & SGPR_MINE_POSITIVES) ? 1 : 0;
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0 || topk_fused(h))
+    if (M == 0 || has_fused_epilogues(h))
         return launch_score_mine(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, positives,
                                  d_col_pose_xz, d_row_pose_xz, d_pos, d_neg, k, d_values, d_indices, d_workspace, s);
-    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
-    float* block = static_cast<float*>(d_workspace);
-    unsigned char* ws = static_cast<unsigned char*>(d_workspace) + a256((size_t)rb * M * sizeof(float));
-    const size_t ws_bytes = workspace_bytes - a256((size_t)rb * M * sizeof(float));
-    for (int r0 = 0; r0 < R; r0 += rb) {
-        const int n = std::min(rb, R - r0);
-        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
-        if (rc != SGPR_OK) return rc;
-        rc = launch_mine_rows(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, positives,
-                              d_col_pose_xz, d_row_pose_xz ? d_row_pose_xz + 2 * (size_t)r0 : nullptr, d_pos, d_neg, k,
-                              d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
-        if (rc != SGPR_OK) return rc;
-    }
-    return SGPR_OK;
+    auto select = [&](const float* block, unsigned char*, int r0, int n) {
+        return launch_mine_rows(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, positives,
+                                d_col_pose_xz, d_row_pose_xz ? d_row_pose_xz + 2 * (size_t)r0 : nullptr, d_pos, d_neg, k,
+                                d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, 0, d_workspace, workspace_bytes, stream, select);
 }
 
 size_t sgpr_mine_rows_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
@@ -1360,24 +1370,19 @@ static bool above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, in
         set_error(std::string(fn) + ": the threshold is NaN");
         return false;
     }
-    if ((int64_t)row0 + R > 0x7fffffffLL) {
-        set_error(std::string(fn) + ": row0 + R must fit an int");
-        return false;
-    }
-    return true;
+    return row0_ok(fn, row0, R);
 }
 
-// chunked path layout: score block [rb][M] | cnt [rb] i32 | row_ptr [R + 1] i64 | the block's all-pairs workspace
-static size_t above_chunk_head(int R, int M) {
-    const int rb = topk_block_rows(R, M);
-    return a256((size_t)rb * M * sizeof(float)) + a256((size_t)rb * 4) + a256((size_t)(R + 1) * 8);
+// head of sgpr_score_above's row-block path: cnt [rb] i32 | row_ptr [R + 1] i64 (used when the caller passes none)
+static size_t above_head_bytes(int R, int M) {
+    return a256((size_t)score_block_rows(R, M) * 4) + a256((size_t)(R + 1) * 8);
 }
 
 size_t sgpr_score_above_workspace_bytes(const sgpr_handle* h, int R, int M, int flags) {
     if (!h || R < 0 || M < 0 || (flags & ~SGPR_TOPK_CAUSAL)) return 0;
     if (R == 0 || M == 0) return 0;
-    if (topk_fused(h)) return score_above_ws_bytes(h, R, M);
-    return above_chunk_head(R, M) + sgpr_score_all_pairs_workspace_bytes(h, topk_block_rows(R, M), M);
+    if (has_fused_epilogues(h)) return score_above_ws_bytes(h, R, M);
+    return row_blocks_ws_bytes(h, R, M, above_head_bytes(R, M));
 }
 
 int sgpr_score_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1390,33 +1395,22 @@ int sgpr_score_above(const sgpr_handle* h, const float* d_pooled_rows, int R, co
         set_error("sgpr_score_above: NULL pooled vectors");
         return SGPR_E_INVALID;
     }
-    const size_t need = sgpr_score_above_workspace_bytes(h, R, M, flags);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_score_above: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_score_above", sgpr_score_above_workspace_bytes(h, R, M, flags), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (R == 0 || M == 0 || topk_fused(h))
+    if (R == 0 || M == 0 || has_fused_epilogues(h))
         return launch_score_above(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, threshold,
                                   d_rows, d_cols, d_values, capacity, d_row_ptr, d_count, d_workspace, s);
-    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
-    unsigned char* base = static_cast<unsigned char*>(d_workspace);
-    float* block = reinterpret_cast<float*>(base);
-    unsigned char* cnt = base + a256((size_t)rb * M * sizeof(float));
-    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(cnt + a256((size_t)rb * 4));
-    unsigned char* ws = base + above_chunk_head(R, M);
-    const size_t ws_bytes = workspace_bytes - above_chunk_head(R, M);
-    for (int r0 = 0; r0 < R; r0 += rb) {
-        const int n = std::min(rb, R - r0);
-        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
-        if (rc != SGPR_OK) return rc;
-        rc = launch_rows_above(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, threshold,
-                               d_rows, d_cols, d_values, capacity, rp + r0, r0, d_count, r0 > 0, cnt, h->d_status, s);
-        if (rc != SGPR_OK) return rc;
-    }
-    return SGPR_OK;
+    const size_t cnt_bytes = a256((size_t)score_block_rows(R, M) * 4);
+    auto select = [&](const float* block, unsigned char* cnt, int r0, int n) {
+        int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(cnt + cnt_bytes);
+        return launch_rows_above(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, threshold,
+                                 d_rows, d_cols, d_values, capacity, rp + r0, r0, d_count, r0 > 0, cnt, h->d_status, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, above_head_bytes(R, M), d_workspace, workspace_bytes,
+                            stream, select);
 }
 
 size_t sgpr_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M) {
@@ -1434,11 +1428,8 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
         set_error("sgpr_rows_above: NULL score or ld < M");
         return SGPR_E_INVALID;
     }
-    const size_t need = sgpr_rows_above_workspace_bytes(h, R, M);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_rows_above: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_rows_above", sgpr_rows_above_workspace_bytes(h, R, M), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (R == 0 || M == 0) return launch_above_empty(R, d_row_ptr, d_count, s);
@@ -1457,11 +1448,7 @@ static bool eval_args_ok(const char* fn, const sgpr_handle* h, const float* rows
         set_error(std::string(fn) + ": NULL argument, negative count, no ground truth or ldg below M");
         return false;
     }
-    if ((int64_t)row0 + R > 0x7fffffffLL) {
-        set_error(std::string(fn) + ": row0 + R must fit an int");
-        return false;
-    }
-    return true;
+    return row0_ok(fn, row0, R);
 }
 
 static PairTruth eval_truth(int row0, const double* pose, double d_pos, double d_neg, const signed char* gt, int64_t ldg) {
@@ -1476,24 +1463,21 @@ static PairTruth eval_truth(int row0, const double* pose, double d_pos, double d
     return t;
 }
 
-// chunked path layout: score block [rb][M] | (counts: the block's d_out [T + 3] u64 | its counting slabs) | the block's
-// all-pairs workspace
-static size_t eval_chunk_head(const sgpr_handle* h, int R, int M, int T) {
-    size_t b = a256((size_t)topk_block_rows(R, M) * M * sizeof(float));
-    if (T >= 0) b += a256((size_t)(T + 3) * 8) + a256(sgpr_pair_threshold_counts_workspace_bytes(h, T));
-    return b;
+// head of sgpr_score_threshold_counts' row-block path: the block's d_out [T + 3] u64 | its counting slabs
+static size_t counts_head_bytes(const sgpr_handle* h, int T) {
+    return a256((size_t)(T + 3) * 8) + a256(sgpr_pair_threshold_counts_workspace_bytes(h, T));
 }
 
 size_t sgpr_score_positives_workspace_bytes(const sgpr_handle* h, int R, int M) {
     if (!h || R < 0 || M < 0 || R == 0 || M == 0) return 0;
-    if (topk_fused(h)) return score_eval_ws_bytes(h, R, M, -1);
-    return eval_chunk_head(h, R, M, -1) + sgpr_score_all_pairs_workspace_bytes(h, topk_block_rows(R, M), M);
+    if (has_fused_epilogues(h)) return score_eval_ws_bytes(h, R, M, -1);
+    return row_blocks_ws_bytes(h, R, M, 0);
 }
 
 size_t sgpr_score_threshold_counts_workspace_bytes(const sgpr_handle* h, int R, int M, int T) {
     if (!h || R < 0 || M < 0 || T < 0 || T > SGPR_SCORE_COUNT_MAX_THRESHOLDS || R == 0 || M == 0) return 0;
-    if (topk_fused(h)) return score_eval_ws_bytes(h, R, M, T);
-    return eval_chunk_head(h, R, M, T) + sgpr_score_all_pairs_workspace_bytes(h, topk_block_rows(R, M), M);
+    if (has_fused_epilogues(h)) return score_eval_ws_bytes(h, R, M, T);
+    return row_blocks_ws_bytes(h, R, M, counts_head_bytes(h, T));
 }
 
 int sgpr_score_positives(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1506,35 +1490,24 @@ int sgpr_score_positives(const sgpr_handle* h, const float* d_pooled_rows, int R
         set_error("sgpr_score_positives: NULL count buffer or capacity without an output buffer");
         return SGPR_E_INVALID;
     }
-    const size_t need = sgpr_score_positives_workspace_bytes(h, R, M);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_score_positives: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_score_positives", sgpr_score_positives_workspace_bytes(h, R, M), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
     float* out = capacity > 0 ? d_out : nullptr;
-    if ((int64_t)R * M == 0 || topk_fused(h))
+    if ((int64_t)R * M == 0 || has_fused_epilogues(h))
         return launch_score_eval(h, d_pooled_rows, R, d_pooled_cols, M, truth, out, capacity, d_count, nullptr, -1, nullptr,
                                  0, nullptr, nullptr, d_workspace, s);
     hipError_t e = hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_positives: memset");
-    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
-    float* block = static_cast<float*>(d_workspace);
-    unsigned char* ws = static_cast<unsigned char*>(d_workspace) + eval_chunk_head(h, R, M, -1);
-    const size_t ws_bytes = workspace_bytes - eval_chunk_head(h, R, M, -1);
-    for (int r0 = 0; r0 < R; r0 += rb) {
-        const int n = std::min(rb, R - r0);
-        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
-        if (rc != SGPR_OK) return rc;
+    auto count = [&](const float* block, unsigned char*, int r0, int n) {
         PairTruth tb = truth;
         tb.row0 = row0 + r0;
         if (tb.gt) tb.gt += (int64_t)r0 * ldg;
-        rc = launch_pair_positives_more(h, block, n, M, M, tb, out, capacity, d_count, s);
-        if (rc != SGPR_OK) return rc;
-    }
-    return SGPR_OK;
+        return launch_pair_positives_more(h, block, n, M, M, tb, out, capacity, d_count, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, 0, d_workspace, workspace_bytes, stream, count);
 }
 
 int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
@@ -1554,39 +1527,28 @@ int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows
         set_error("sgpr_score_threshold_counts: the ranking needs thresholds, >= 1 value group per threshold and the pair counts");
         return SGPR_E_INVALID;
     }
-    const size_t need = sgpr_score_threshold_counts_workspace_bytes(h, R, M, T);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_score_threshold_counts: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_score_threshold_counts", sgpr_score_threshold_counts_workspace_bytes(h, R, M, T), d_workspace,
+                      workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
-    if ((int64_t)R * M == 0 || topk_fused(h))
+    if ((int64_t)R * M == 0 || has_fused_epilogues(h))
         return launch_score_eval(h, d_pooled_rows, R, d_pooled_cols, M, truth, nullptr, 0, nullptr, d_thresholds, T, d_rank,
                                  groups_per_threshold, d_at_least, d_out, d_workspace, s);
     hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_threshold_counts: memset");
-    const int rb = topk_block_rows(R, M), pw = pooled_width(h);
-    unsigned char* base = static_cast<unsigned char*>(d_workspace);
-    float* block = reinterpret_cast<float*>(base);
-    unsigned long long* part = reinterpret_cast<unsigned long long*>(base + a256((size_t)rb * M * sizeof(float)));
-    unsigned char* slabs = reinterpret_cast<unsigned char*>(part) + a256((size_t)(T + 3) * 8);
-    const size_t slab_bytes = sgpr_pair_threshold_counts_workspace_bytes(h, T);
-    unsigned char* ws = base + eval_chunk_head(h, R, M, T);
-    const size_t ws_bytes = workspace_bytes - eval_chunk_head(h, R, M, T);
-    for (int r0 = 0; r0 < R; r0 += rb) {
-        const int n = std::min(rb, R - r0);
-        int rc = sgpr_score_all_pairs(h, d_pooled_rows + (size_t)r0 * pw, n, d_pooled_cols, M, block, M, ws, ws_bytes, stream);
-        if (rc != SGPR_OK) return rc;
-        rc = sgpr_pair_threshold_counts(h, block, n, M, M, row0 + r0, d_pose_xz, d_pos, d_neg,
-                                        truth.gt ? truth.gt + (int64_t)r0 * ldg : nullptr, ldg, d_thresholds, T, d_rank,
-                                        groups_per_threshold, d_at_least, part, slabs, slab_bytes, stream);
-        if (rc != SGPR_OK) return rc;
-        rc = launch_eval_add(d_out, part, T + 3, s);
-        if (rc != SGPR_OK) return rc;
-    }
-    return SGPR_OK;
+    const size_t part_bytes = a256((size_t)(T + 3) * 8), slab_bytes = sgpr_pair_threshold_counts_workspace_bytes(h, T);
+    auto count = [&](const float* block, unsigned char* head, int r0, int n) {
+        unsigned long long* part = reinterpret_cast<unsigned long long*>(head);
+        const int rc = sgpr_pair_threshold_counts(h, block, n, M, M, row0 + r0, d_pose_xz, d_pos, d_neg,
+                                                  truth.gt ? truth.gt + (int64_t)r0 * ldg : nullptr, ldg, d_thresholds, T,
+                                                  d_rank, groups_per_threshold, d_at_least, part, head + part_bytes,
+                                                  slab_bytes, stream);
+        return rc != SGPR_OK ? rc : launch_eval_add(d_out, part, T + 3, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, counts_head_bytes(h, T), d_workspace, workspace_bytes,
+                            stream, count);
 }
 
 size_t sgpr_score_all_pairs_multi_workspace_bytes(const sgpr_handle* h, int n_jobs, const sgpr_pairs_job* jobs) {
@@ -1610,11 +1572,9 @@ int sgpr_score_all_pairs_multi(const sgpr_handle* h, int n_jobs, const sgpr_pair
                                                                                      // lets the jobs share one workspace)
         return rc;
     }
-    const size_t need = score_all_pairs_multi_ws_bytes(n_jobs, jobs);
-    if (need > 0 && (!d_workspace || workspace_bytes < need)) {
-        set_error("sgpr_score_all_pairs_multi: workspace of " + std::to_string(need) + " bytes required");
+    if (!workspace_ok("sgpr_score_all_pairs_multi", score_all_pairs_multi_ws_bytes(n_jobs, jobs), d_workspace,
+                      workspace_bytes))
         return SGPR_E_WORKSPACE;
-    }
     DeviceGuard guard(h->device);
     if (tail_wide(h)) {             // the three-plane instance has no multi-rectangle form: job by job, in stream order,
         unsigned char* ws = static_cast<unsigned char*>(d_workspace);    // each in its slice of the workspace - the bits

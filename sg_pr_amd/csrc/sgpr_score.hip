@@ -15,6 +15,8 @@
 
 #include <string.h>
 
+#include <type_traits>
+
 #include "sgpr_internal.hpp"
 
 namespace sgpr {
@@ -164,6 +166,23 @@ size_t score_all_pairs_ws_bytes(int R, int M) {
     const size_t nsb = (size_t)(M + AP_SB - 1) / AP_SB;
     return (size_t)R * T * sizeof(float) + (size_t)2 * ap_prep_groups(R, M) * 4 * sizeof(float) +
            (size_t)R * 3 * 64 * 8 * sizeof(unsigned short) + nsb * 3 * 4 * 64 * 8 * sizeof(unsigned short);
+}
+
+// the operand regions of that layout in a workspace: R rows of `planes` planes (2, or 3 for the wide-range instance) and
+// nrng prep groups (a rectangle's 2 ap_prep_groups; the pair list carves its own count and takes Cb as its Cg)
+struct ApOperands {
+    float* ur;
+    float* rng;
+    unsigned short* Ab;
+    unsigned short* Cb;
+};
+static ApOperands ap_operands(void* ws, int R, int nrng, int planes) {
+    ApOperands o;
+    o.ur = static_cast<float*>(ws);
+    o.rng = o.ur + (size_t)R * T;
+    o.Ab = reinterpret_cast<unsigned short*>(o.rng + (size_t)nrng * 4);
+    o.Cb = o.Ab + (size_t)R * planes * 64 * 8;
+    return o;
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1453,6 +1472,9 @@ __global__ __launch_bounds__(256, OCC) void score_topk_kernel(const DevWeights w
                                                               const float* __restrict__ rng, int nrng,
                                                               const float* __restrict__ prow,
                                                               const float* __restrict__ pcol, TopkArgs a) {
+    // (this prologue - range question, ap_consts, XCD-swizzled item range - recurs word for word in score_mine_kernel,
+    //  score_above_kernel and score_positives_kernel.  Moved into a __forceinline__ helper with its statement order kept,
+    //  it still changes their register allocation and scratch, so each kernel keeps its own copy.)
     const int lane = threadIdx.x & 63;
     const int l15 = lane & 15, g = lane >> 4;
     float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
@@ -1869,36 +1891,40 @@ __global__ __launch_bounds__(256, APW_OCC) void score_all_pairs_wide_kernel(cons
     }
 }
 
+// ntn_prep_kernel: the two-plane operands of the R x M rectangle into o, nrng prep workgroups
+static int launch_ntn_prep(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const ApOperands& o,
+                           int nrng, hipStream_t stream) {
+    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, o.Ab, o.ur, o.rng, o.Cb);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "ntn_prep_kernel launch");
+}
+
 int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score,
                            int64_t ld, void* ws, hipStream_t stream, bool wide) {
     if (R == 0 || M == 0) return SGPR_OK;
-    const int ngroups = ap_prep_groups(R, M), nrng = 2 * ngroups;
-    const size_t nsb = (size_t)(M + AP_SB - 1) / AP_SB;
-    float* ur = static_cast<float*>(ws);
-    float* rng = ur + (size_t)R * T;
-    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
-    unsigned short* Cb = Ab + (size_t)R * (wide ? 3 : 2) * 64 * 8;
-    (void)nsb;
+    const int nrng = 2 * ap_prep_groups(R, M);
+    const ApOperands o = ap_operands(ws, R, nrng, wide ? 3 : 2);
     const int64_t items = (int64_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
     if (wide) {                                            // three bf16 planes: the reference's operand width, fp32's range
-        hipLaunchKernelGGL(ntn_prep_wide_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
+        hipLaunchKernelGGL(ntn_prep_wide_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, o.Ab, o.ur, o.rng,
+                           o.Cb);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "ntn_prep_wide_kernel launch");
         const int64_t slots = (int64_t)h->num_cus * APW_OCC;
         const unsigned grid = (unsigned)(items < slots ? items : slots);
-        hipLaunchKernelGGL(score_all_pairs_wide_kernel, dim3(grid), dim3(256), 0, stream, h->w, R, M, Ab, Cb, ur, score, ld);
+        hipLaunchKernelGGL(score_all_pairs_wide_kernel, dim3(grid), dim3(256), 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, score,
+                           ld);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "score_all_pairs_wide_kernel launch");
         return SGPR_OK;
     }
-    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+    const int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
+    if (rc != SGPR_OK) return rc;
     const int64_t slots = (int64_t)h->num_cus * AP_OCC;   // one resident slot per workgroup: a single, full round
     const unsigned grid = (unsigned)(items < slots ? items : slots);
-    hipLaunchKernelGGL((score_all_pairs_kernel<AP_OCC, AP_NI, 0>), dim3(grid), dim3(256), 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows,
-                       cols, score, ld);
-    e = hipGetLastError();
+    hipLaunchKernelGGL((score_all_pairs_kernel<AP_OCC, AP_NI, 0>), dim3(grid), dim3(256), 0, stream, h->w, R, M, o.Ab, o.Cb,
+                       o.ur, o.rng, nrng, rows, cols, score, ld);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_all_pairs_kernel launch");
     return SGPR_OK;
 }
@@ -1929,10 +1955,11 @@ int launch_score_all_pairs_multi(const sgpr_handle* h, int n, const sgpr_pairs_j
         q.R = R;
         q.M = M;
         q.nrng = nrng;
-        q.ur = reinterpret_cast<float*>(base);             // the layout of launch_score_all_pairs, per job
-        q.rng = q.ur + (size_t)R * T;
-        q.Ab = reinterpret_cast<unsigned short*>(q.rng + (size_t)nrng * 4);
-        q.Cb = q.Ab + (size_t)R * 2 * 64 * 8;
+        const ApOperands o = ap_operands(base, R, nrng, 2);   // the layout of launch_score_all_pairs, per job
+        q.ur = o.ur;
+        q.rng = o.rng;
+        q.Ab = o.Ab;
+        q.Cb = o.Cb;
         base += align256(score_all_pairs_ws_bytes(R, M));
         a.block0[a.n] = blocks;
         a.item0[a.n] = (int)items;
@@ -1975,58 +2002,55 @@ size_t score_topk_ws_bytes(const sgpr_handle* h, int R, int M, int k) {
     return align256(score_all_pairs_ws_bytes(R, M)) + align256(lists * sizeof(float)) + lists * sizeof(int32_t);
 }
 
+// the list arguments of sgpr_score_topk / sgpr_score_mine: the result, and the partial lists behind the operands
+static TopkArgs topk_args(const sgpr_handle* h, int R, int M, const int32_t* row_self, int row0, int window, int causal,
+                          int k, float* val, int32_t* idx, void* ws) {
+    const size_t lists = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS * k;
+    float* pval = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + align256(score_all_pairs_ws_bytes(R, M)));
+    int32_t* pidx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(pval) + align256(lists * sizeof(float)));
+    return TopkArgs{row_self, row0, window, causal, k, 0, val, idx, pval, pidx, h->d_status};
+}
+
+// launches launch(std::integral_constant<int, K>()) for the compiled list instance of k (the first k of its K = 1, 4, 8 or
+// 16 entries)
+template <class Launch>
+static int launch_list_k(int k, const char* what, Launch&& launch) {
+    if (k <= 1)
+        launch(std::integral_constant<int, 1>());
+    else if (k <= 4)
+        launch(std::integral_constant<int, 4>());
+    else if (k <= 8)
+        launch(std::integral_constant<int, 8>());
+    else
+        launch(std::integral_constant<int, 16>());
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, what);
+}
+
 int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
                       int row0, int window, int causal, int k, float* val, int32_t* idx, void* ws, hipStream_t stream) {
     if (R == 0) return SGPR_OK;
-    hipError_t e;
     if (M == 0) {                                          // no column at all: every slot is empty
         const int64_t n = (int64_t)R * k;
         hipLaunchKernelGGL(topk_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, val, idx);
-        e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         return e == hipSuccess ? SGPR_OK : hip_fail(e, "topk_fill_kernel launch");
     }
-    const int ngroups = ap_prep_groups(R, M), nrng = 2 * ngroups;
-    unsigned char* base = static_cast<unsigned char*>(ws);
-    float* ur = reinterpret_cast<float*>(base);            // the operand layout of launch_score_all_pairs
-    float* rng = ur + (size_t)R * T;
-    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
-    unsigned short* Cb = Ab + (size_t)R * 2 * 64 * 8;
+    const int nrng = 2 * ap_prep_groups(R, M);
+    const ApOperands o = ap_operands(ws, R, nrng, 2);
     const int64_t grid = topk_grid(h, R, M);
-    const size_t lists = (size_t)grid * 2 * AP_ROWS * k;
-    TopkArgs a;
-    a.row_self = row_self;
-    a.row0 = row0;
-    a.window = window;
-    a.causal = causal;
-    a.k = k;
-    a.wg = 0;
-    a.val = val;
-    a.idx = idx;
-    a.pval = reinterpret_cast<float*>(base + align256(score_all_pairs_ws_bytes(R, M)));
-    a.pidx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(a.pval) + align256(lists * sizeof(float)));
-    a.status = h->d_status;
-    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+    const TopkArgs a = topk_args(h, R, M, row_self, row0, window, causal, k, val, idx, ws);
+    int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
+    if (rc != SGPR_OK) return rc;
     const dim3 gd((unsigned)grid), bd(256), gm((unsigned)((R + AP_ROWS - 1) / AP_ROWS));
-    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;  // the compiled instance: the first k of its K entries
-    switch (K) {
-        case 1: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 1>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
-        case 4: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 4>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
-        case 8: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 8>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
-        default: hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, 16>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a); break;
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_topk_kernel launch");
-    switch (K) {
-        case 1: hipLaunchKernelGGL(topk_merge_kernel<1>, gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 4: hipLaunchKernelGGL(topk_merge_kernel<4>, gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 8: hipLaunchKernelGGL(topk_merge_kernel<8>, gm, bd, 0, stream, R, M, (int)grid, a); break;
-        default: hipLaunchKernelGGL(topk_merge_kernel<16>, gm, bd, 0, stream, R, M, (int)grid, a); break;
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "topk_merge_kernel launch");
-    return SGPR_OK;
+    rc = launch_list_k(k, "score_topk_kernel launch", [&](auto K) {
+        hipLaunchKernelGGL((score_topk_kernel<TK_OCC, AP_NI, K>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, o.rng, nrng,
+                           rows, cols, a);
+    });
+    if (rc != SGPR_OK) return rc;
+    return launch_list_k(k, "topk_merge_kernel launch", [&](auto K) {
+        hipLaunchKernelGGL((topk_merge_kernel<K>), gm, bd, 0, stream, R, M, (int)grid, a);
+    });
 }
 
 // ------------------------------------------------------------------ fused score + range selection (sgpr_score_above)
@@ -2060,16 +2084,12 @@ static int launch_above_block(const sgpr_handle* h, const float* rows, int R, co
                               const int32_t* row_self, int row0, int window, int causal, float thr, int32_t* orows,
                               int32_t* ocols, float* ovals, int64_t cap, int64_t* rp, int rout0,
                               unsigned long long* count, void* ws, hipStream_t stream) {
-    const int ngroups = ap_prep_groups(R, M), nrng = 2 * ngroups;
-    unsigned char* base = static_cast<unsigned char*>(ws);
-    float* ur = reinterpret_cast<float*>(base);            // the operand layout of launch_score_all_pairs
-    float* rng = ur + (size_t)R * T;
-    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
-    unsigned short* Cb = Ab + (size_t)R * 2 * 64 * 8;
+    const int nrng = 2 * ap_prep_groups(R, M);
+    const ApOperands o = ap_operands(ws, R, nrng, 2);
     const int64_t grid = topk_grid(h, R, M);
     const size_t items = (size_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
     const size_t slots = (size_t)grid * 2 * AP_ROWS;
-    unsigned char* p = base + align256(score_all_pairs_ws_bytes(R, M));
+    unsigned char* p = static_cast<unsigned char*>(ws) + align256(score_all_pairs_ws_bytes(R, M));
     AboveArgs a;
     a.row_self = row_self;
     a.row0 = row0;
@@ -2094,11 +2114,11 @@ static int launch_above_block(const sgpr_handle* h, const float* rows, int R, co
     a.status = h->d_status;
     hipError_t e = hipMemsetAsync(a.flag, 0, items, stream);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_above: clearing the item flags");
-    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+    const int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
+    if (rc != SGPR_OK) return rc;
     const dim3 gd((unsigned)grid), bd(256);
-    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a);
+    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, o.rng, nrng, rows,
+                       cols, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 1)");
     hipLaunchKernelGGL(above_fold_kernel, dim3((unsigned)((R + AP_ROWS - 1) / AP_ROWS)), dim3(64), 0, stream, R, M, (int)grid, a);
@@ -2109,7 +2129,8 @@ static int launch_above_block(const sgpr_handle* h, const float* rows, int R, co
     if (e != hipSuccess) return hip_fail(e, "above_scan_kernel launch");
     if (cap == 0) return SGPR_OK;                          // count only
     a.pass = 2;
-    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, Ab, Cb, ur, rng, nrng, rows, cols, a);
+    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, o.rng, nrng, rows,
+                       cols, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 2)");
     return SGPR_OK;
@@ -2335,6 +2356,15 @@ size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T) {
     return b;
 }
 
+// the pose rule's squared class boundaries and the squared gaps that rule a work item out (EvalArgs, MineArgs)
+template <class Args>
+static void set_pose_cuts(Args& a, double d_pos, double d_neg) {
+    a.lo2 = d_pos * d_pos;
+    a.hi2 = d_neg * d_neg;
+    a.cut_pos = a.lo2 * 1.001;
+    a.cut_neg = (a.lo2 > a.hi2 ? a.lo2 : a.hi2) * 1.001;
+}
+
 int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const PairTruth& truth,
                       float* out, int64_t cap, unsigned long long* count, const float* thr, int T,
                       const sgpr_rank_group* rank, int gpt, const unsigned long long* at_least, unsigned long long* d_out,
@@ -2362,10 +2392,7 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
     EvalArgs a;
     memset(&a, 0, sizeof(a));
     a.truth = truth;
-    a.lo2 = truth.d_pos * truth.d_pos;
-    a.hi2 = truth.d_neg * truth.d_neg;
-    a.cut_pos = a.lo2 * 1.001;
-    a.cut_neg = (a.lo2 > a.hi2 ? a.lo2 : a.hi2) * 1.001;
+    set_pose_cuts(a, truth.d_pos, truth.d_neg);
     a.cbox = cbox;
     a.out = out;
     a.cap = cap;
@@ -2379,27 +2406,23 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
     for (int r0 = 0; r0 < R; r0 += rb) {
         const int n = R - r0 < rb ? R - r0 : rb;
         const int nrng = 2 * ap_prep_groups(n, M);
-        float* ur = reinterpret_cast<float*>(p);           // the operand layout of launch_score_all_pairs
-        float* rng = ur + (size_t)n * kT;
-        unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
-        unsigned short* Cb = Ab + (size_t)n * 2 * 64 * 8;
+        const ApOperands o = ap_operands(p, n, nrng, 2);
         const float* brows = rows + (size_t)r0 * F;
         a.truth.row0 = truth.row0 + r0;
         a.truth.gt = truth.gt ? truth.gt + (int64_t)r0 * truth.ldg : nullptr;
-        hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, brows, n, cols, M, Ab, ur, rng, Cb);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+        const int rc = launch_ntn_prep(h, brows, n, cols, M, o, nrng, stream);
+        if (rc != SGPR_OK) return rc;
         const int64_t grid = topk_grid(h, n, M);
         const dim3 gd((unsigned)grid), bd(256);
         if (!counts) {
-            hipLaunchKernelGGL((score_positives_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, Ab, Cb, ur, rng, nrng,
-                               brows, cols, a);
+            hipLaunchKernelGGL((score_positives_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, o.rng,
+                               nrng, brows, cols, a);
             e = hipGetLastError();
             if (e != hipSuccess) return hip_fail(e, "score_positives_kernel launch");
             continue;
         }
-        hipLaunchKernelGGL((score_counts_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, Ab, Cb, ur, rng, nrng, brows,
-                           cols, a, thr, at_least, slabs, sw);
+        hipLaunchKernelGGL((score_counts_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, o.rng, nrng,
+                           brows, cols, a, thr, at_least, slabs, sw);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "score_counts_kernel launch");
         hipLaunchKernelGGL(eval_fold_kernel, dim3((unsigned)((T + 3 + 31) / 32)), dim3(1024), 0, stream, slabs, (int)grid, sw,
@@ -2472,42 +2495,25 @@ int launch_score_mine(const sgpr_handle* h, const float* rows, int R, const floa
         e = hipGetLastError();
         return e == hipSuccess ? SGPR_OK : hip_fail(e, "mine_fill_kernel launch");
     }
-    const int ngroups = ap_prep_groups(R, M), nrng = 2 * ngroups, ncc = (M + AP_COLS - 1) / AP_COLS;
-    unsigned char* base = static_cast<unsigned char*>(ws);
-    float* ur = reinterpret_cast<float*>(base);            // the operand layout of launch_score_all_pairs
-    float* rng = ur + (size_t)R * T;
-    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
-    unsigned short* Cb = Ab + (size_t)R * 2 * 64 * 8;
+    const int nrng = 2 * ap_prep_groups(R, M), ncc = (M + AP_COLS - 1) / AP_COLS;
+    const ApOperands o = ap_operands(ws, R, nrng, 2);
     const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
     const int64_t grid = std::min<int64_t>(items, (int64_t)h->num_cus * MN_OCC);   // (<= topk_grid: the lists fit)
-    const size_t lists = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS * k;
-    TopkArgs a;
-    a.row_self = row_self;
-    a.row0 = row0;
-    a.window = window < 0 ? 0 : window;                    // (c != self_r: a window of at least 0 cuts the own frame out)
-    a.causal = causal;
-    a.k = k;
-    a.wg = 0;
-    a.val = val;
-    a.idx = idx;
-    a.pval = reinterpret_cast<float*>(base + align256(score_all_pairs_ws_bytes(R, M)));
-    a.pidx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(a.pval) + align256(lists * sizeof(float)));
-    a.status = h->d_status;
+    // (c != self_r: a window of at least 0 cuts the own frame out)
+    const TopkArgs a = topk_args(h, R, M, row_self, row0, window < 0 ? 0 : window, causal, k, val, idx, ws);
     MineArgs m;
     memset(&m, 0, sizeof(m));
     m.truth.pose = col_pose;
     m.truth.d_pos = d_pos;
     m.truth.d_neg = d_neg;
+    unsigned char* base = static_cast<unsigned char*>(ws);
     double* cbox = reinterpret_cast<double*>(base + align256(score_topk_ws_bytes(h, R, M, k)));
     double* rpose = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(cbox) + align256((size_t)ncc * 4 * sizeof(double)));
     double* rbox = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(rpose) + align256((size_t)R * 2 * sizeof(double)));
     m.cbox = cbox;
     m.rpose = rpose;
     m.rbox = rbox;
-    m.lo2 = d_pos * d_pos;
-    m.hi2 = d_neg * d_neg;
-    m.cut_pos = m.lo2 * 1.001;                             // (the evaluation epilogues' margins, launch_score_eval)
-    m.cut_neg = (m.lo2 > m.hi2 ? m.lo2 : m.hi2) * 1.001;
+    set_pose_cuts(m, d_pos, d_neg);
     hipLaunchKernelGGL(eval_colbox_kernel, dim3((unsigned)ncc), dim3(64), 0, stream, col_pose, M, cbox);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "eval_colbox_kernel launch");
@@ -2515,45 +2521,27 @@ int launch_score_mine(const sgpr_handle* h, const float* rows, int R, const floa
                        row0, row_pose, col_pose, rpose, rbox);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "mine_rowpose_kernel launch");
-    hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, Ab, ur, rng, Cb);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ntn_prep_kernel launch");
+    int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
+    if (rc != SGPR_OK) return rc;
     const dim3 gd((unsigned)grid), bd(256), gm((unsigned)((R + AP_ROWS - 1) / AP_ROWS));
-    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;  // the compiled instance: the first k of its K entries
-#define SGPR_MINE(KK, MM) hipLaunchKernelGGL((score_mine_kernel<MN_OCC, AP_NI, KK, MM>), gd, bd, 0, stream, h->w, R, M, Ab, \
-                                             Cb, ur, rng, nrng, rows, cols, a, m)
-    if (positives) {
-        switch (K) {
-            case 1: SGPR_MINE(1, MN_POS); break;
-            case 4: SGPR_MINE(4, MN_POS); break;
-            case 8: SGPR_MINE(8, MN_POS); break;
-            default: SGPR_MINE(16, MN_POS); break;
-        }
-    } else {
-        switch (K) {
-            case 1: SGPR_MINE(1, MN_NEG); break;
-            case 4: SGPR_MINE(4, MN_NEG); break;
-            case 8: SGPR_MINE(8, MN_NEG); break;
-            default: SGPR_MINE(16, MN_NEG); break;
-        }
-    }
-#undef SGPR_MINE
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_mine_kernel launch");
+    if (positives)
+        rc = launch_list_k(k, "score_mine_kernel launch", [&](auto K) {
+            hipLaunchKernelGGL((score_mine_kernel<MN_OCC, AP_NI, K, MN_POS>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur,
+                               o.rng, nrng, rows, cols, a, m);
+        });
+    else
+        rc = launch_list_k(k, "score_mine_kernel launch", [&](auto K) {
+            hipLaunchKernelGGL((score_mine_kernel<MN_OCC, AP_NI, K, MN_NEG>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur,
+                               o.rng, nrng, rows, cols, a, m);
+        });
+    if (rc != SGPR_OK) return rc;
     // (the lists of the negatives are top-k's: its merge instances; the positives' take the negating ones)
-    switch (K + (positives ? 100 : 0)) {
-        case 1: hipLaunchKernelGGL((topk_merge_kernel<1>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 4: hipLaunchKernelGGL((topk_merge_kernel<4>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 8: hipLaunchKernelGGL((topk_merge_kernel<8>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 16: hipLaunchKernelGGL((topk_merge_kernel<16>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 101: hipLaunchKernelGGL((topk_merge_kernel<1, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 104: hipLaunchKernelGGL((topk_merge_kernel<4, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-        case 108: hipLaunchKernelGGL((topk_merge_kernel<8, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-        default: hipLaunchKernelGGL((topk_merge_kernel<16, true>), gm, bd, 0, stream, R, M, (int)grid, a); break;
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "topk_merge_kernel launch");
-    return SGPR_OK;
+    return launch_list_k(k, "topk_merge_kernel launch", [&](auto K) {
+        if (positives)
+            hipLaunchKernelGGL((topk_merge_kernel<K, true>), gm, bd, 0, stream, R, M, (int)grid, a);
+        else
+            hipLaunchKernelGGL((topk_merge_kernel<K>), gm, bd, 0, stream, R, M, (int)grid, a);
+    });
 }
 
 // out[i] += in[i] (the row blocks of the chunked counting path)
@@ -2701,19 +2689,16 @@ int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float*
     pl.NR = NR;
     pl.NI = NI;
     const int nrng = 2 * pl_prep_groups(NR, M);
-    float* ur = static_cast<float*>(ws);
-    float* rng = ur + (size_t)NR * T;
-    unsigned short* Ab = reinterpret_cast<unsigned short*>(rng + (size_t)nrng * 4);
-    unsigned short* Cg = Ab + (size_t)NR * 2 * 64 * 8;
-    hipLaunchKernelGGL(ntn_prep_list_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, pl.row_ids, NR, cols, M, Ab, ur,
-                       rng, Cg);
+    const ApOperands o = ap_operands(ws, NR, nrng, 2);
+    hipLaunchKernelGGL(ntn_prep_list_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, pl.row_ids, NR, cols, M, o.Ab, o.ur,
+                       o.rng, o.Cb);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "ntn_prep_list_kernel launch");
     const int64_t wgs = ((int64_t)(NI + 3) / 4 + 3) / 4;          // one quad of items per wave, four waves per workgroup
     const int64_t slots = (int64_t)h->num_cus * 8;
     const unsigned grid = (unsigned)(wgs < slots ? wgs : slots);
-    hipLaunchKernelGGL(score_pair_list_kernel, dim3(grid), dim3(256), 0, stream, h->w, pl, Ab, Cg, ur, rng, nrng, rows, cols,
-                       score, exact ? 1 : 0);
+    hipLaunchKernelGGL(score_pair_list_kernel, dim3(grid), dim3(256), 0, stream, h->w, pl, o.Ab, o.Cb, o.ur, o.rng, nrng, rows,
+                       cols, score, exact ? 1 : 0);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_pair_list_kernel launch");
     return SGPR_OK;
