@@ -349,7 +349,9 @@ int sgpr_topk_rows(const sgpr_handle* h, const float* d_score, int R, int M, int
  * d_row_self NULL, row0 + r.  Every value is bit-identical to sgpr_score_all_pairs' entry at (r, c) on the same
  * rectangle.  The production handle runs one fused launch (the all-pairs tail feeding per-row lists) plus a small merge
  * launch; its workspace grows with R + M, never with R * M.  Wide-range and any-shape handles score row blocks of at
- * most 64 MB with their own tail and select from each.  d_values / d_indices [R][k], device.  Arguments are checked
+ * most 64 MB with their own tail and select from each.  Wherever a call runs in row blocks, the f16-range question is
+ * answered once per call, over the whole rectangle, before its first block: every block takes the datapath
+ * sgpr_score_all_pairs takes on that rectangle.  d_values / d_indices [R][k], device.  Arguments are checked
  * before the device is touched: a NULL pointer, k outside 1..16 or unknown flag bits give SGPR_E_INVALID, a workspace
  * below sgpr_score_topk_workspace_bytes SGPR_E_WORKSPACE.  Asynchronous on `stream`. */
 #define SGPR_TOPK_CAUSAL 1
@@ -374,7 +376,7 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
  *   whose pose box lies beyond d_pos of the wave's rows is not scored at all for the positives, and one beyond
  *   max(d_pos, d_neg) needs no per-pair arithmetic for the negatives.  Its workspace grows with R + M, never R * M.
  *   Wide-range and any-shape handles score row blocks of at most 64 MB with their own tail and run sgpr_mine_rows on
- *   each.
+ *   each; the f16 range is decided once per call, as for sgpr_score_topk.
  * d_values / d_indices [R][k], device.  Arguments are checked before the device is touched: a NULL handle, pooled
  * array, column pose array or output, k outside 1..16, zero or both mode flags or unknown bits, a NaN d_pos / d_neg,
  * d_pos < 0, d_pos > d_neg or row0 + R beyond an int give SGPR_E_INVALID, a workspace below sgpr_score_mine_workspace_bytes
@@ -416,7 +418,8 @@ int sgpr_mine_rows(const sgpr_handle* h, const float* d_score, int R, int M, int
  *   work items) around a small fold + scan; its workspace grows with R + M and the grid, never with R * M (the operands,
  *   O(R) counters and row pointers, O(grid) partial counts, one byte per 16 x 256 work item).  Wide-range and any-shape
  *   handles score row blocks of at most 64 MB with their own tail and select from each with sgpr_rows_above's kernels,
- *   positions continuing on the device.  Asynchronous on `stream`, no host synchronisation inside. */
+ *   positions continuing on the device.  The production handle's launches take at most 131 072 rows each; on every
+ *   handle the f16 range of a row-blocked call is decided once, over the whole rectangle.  Asynchronous on `stream`, no host synchronisation inside. */
 size_t sgpr_score_above_workspace_bytes(const sgpr_handle* h, int R, int M, int flags);
 int sgpr_score_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
                      const int32_t* d_row_self, int row0, int window, int flags, float threshold,
@@ -455,7 +458,9 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
  *   workgroup, so no counter can overflow and any int R, M is supported (R * M < 2^62).  The workspace grows with
  *   R + M, T and the grid, never with R * M.
  * - Wide-range (debug bit 13, out-of-range weights) and any-shape handles score row blocks of at most 64 MB with their
- *   own tail and run the matrix kernels on each block, row0 advancing; the blocks' counts are summed on the device. */
+ *   own tail and run the matrix kernels on each block, row0 advancing; the blocks' counts are summed on the device.
+ * - On every handle the f16-range question of a row-blocked call is answered once, over the whole rectangle, before
+ *   its first block, so the values counted are sgpr_score_all_pairs' on the same rectangle. */
 #define SGPR_SCORE_COUNT_MAX_THRESHOLDS 2047
 size_t sgpr_score_positives_workspace_bytes(const sgpr_handle* h, int R, int M);
 int sgpr_score_positives(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,

@@ -1132,11 +1132,12 @@ size_t sgpr_score_all_pairs_workspace_bytes(const sgpr_handle* h, int R, int M) 
 // One rectangle of an any-shape handle: a moderately larger tensor network (pooled width <= 64, <= 32 neurons) on the matrix
 // cores (sgpr_wide.hip) when the caller brought its workspace; the plain-fp32 kernel behind it runs only if the inputs left
 // the f16 range (a device word).  Handles beyond those limits: the plain-fp32 kernel alone, no workspace.
+// fresh = false: the range header at the start of ws already holds a larger rectangle's (score_row_blocks).
 static int score_rect_any_shape(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score, int64_t ld,
-                                void* ws, size_t ws_bytes, hipStream_t stream) {
+                                void* ws, size_t ws_bytes, hipStream_t stream, bool fresh = true) {
     const unsigned* gate = nullptr;
     if (wide_tail_serves(h) && ws && ws_bytes >= wide_tail_ws_bytes(R, M)) {
-        const int rc = launch_score_all_pairs_wide_any(h, rows, R, cols, M, score, ld, ws, &gate, stream);
+        const int rc = launch_score_all_pairs_wide_any(h, rows, R, cols, M, score, ld, ws, &gate, stream, fresh);
         if (rc != SGPR_OK) return rc;
     }
     return launch_score_generic(h, rows, nullptr, cols, nullptr, (int64_t)R * M, M, score, ld, stream, gate);
@@ -1200,7 +1201,10 @@ static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t hea
 }
 
 // sgpr_score_all_pairs on rows [r0, r0 + n) of the rectangle, one block after the other, each followed by
-// consume(block, head, r0, n): block [n][M] (ld M), head the caller's region of the workspace
+// consume(block, head, r0, n): block [n][M] (ld M), head the caller's region of the workspace.
+// The f16-range question is the whole rectangle's, as in sgpr_score_all_pairs on it: on an any-shape handle's matrix-core
+// tail a first pass preps every block into the all-pairs region, its TailHdr cleared once and accumulating the maxima of
+// all blocks, and no block's scoring clears it (the other handles' row blocks take the three-plane instance: no gate).
 extern "C++" {   // (a template, inside the C-ABI block)
 template <class Consume>
 static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, size_t head_bytes,
@@ -1209,10 +1213,22 @@ static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, cons
     const size_t block_bytes = a256((size_t)rb * M * sizeof(float));
     float* block = static_cast<float*>(ws);
     unsigned char* head = static_cast<unsigned char*>(ws) + block_bytes;
+    unsigned char* aws = head + head_bytes;
+    const size_t aws_bytes = ws_bytes - block_bytes - head_bytes;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool one_range = h->generic_only && wide_tail_serves(h) && rb < R;
+    if (one_range) {
+        hipError_t e = hipMemsetAsync(aws, 0, 256, s);    // (the TailHdr)
+        if (e != hipSuccess) return hip_fail(e, "row blocks: clearing the range header");
+        for (int r0 = 0; r0 < R; r0 += rb) {
+            const int rc = launch_wide_tail_prep(h, rows + (size_t)r0 * pw, std::min(rb, R - r0), cols, M, aws, s);
+            if (rc != SGPR_OK) return rc;
+        }
+    }
     for (int r0 = 0; r0 < R; r0 += rb) {
         const int n = std::min(rb, R - r0);
-        int rc = sgpr_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, head + head_bytes,
-                                      ws_bytes - block_bytes - head_bytes, stream);
+        int rc = one_range ? score_rect_any_shape(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, aws_bytes, s, false)
+                           : sgpr_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, aws_bytes, stream);
         if (rc != SGPR_OK) return rc;
         rc = consume(block, head, r0, n);
         if (rc != SGPR_OK) return rc;

@@ -345,8 +345,12 @@ int launch_embed_wide(const sgpr_handle* h, const EmbedArgs& a, int N, int k, hi
 // plain-fp32 kernel behind the call tests (non-zero: inputs outside the f16 range, the rectangle is its)
 bool wide_tail_serves(const sgpr_handle* h);
 size_t wide_tail_ws_bytes(int R, int M);
+// fresh = false: the header in ws is not cleared - it already holds the range maxima of the caller's whole rectangle,
+// accumulated by launch_wide_tail_prep over each of its row blocks after one clear (a row-blocked call's range is the call's)
 int launch_score_all_pairs_wide_any(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score,
-                                    int64_t ld, void* ws, const unsigned** d_gate, hipStream_t stream);
+                                    int64_t ld, void* ws, const unsigned** d_gate, hipStream_t stream, bool fresh = true);
+int launch_wide_tail_prep(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, void* ws,
+                          hipStream_t stream);
 // list form (M == 0: pair p = (i1 ? i1[p] : p, i2 ? i2[p] : p) -> score[p]) or dense rectangle (M > 0: P = R * M pairs -> score[r * ld + c])
 int launch_knn_any(const float* x, int B, int C, int N, int k, int64_t* idx, hipStream_t stream);
 int launch_attention_any(const float* w, const float* emb, int B, int N, int F, float* rep, float* att, hipStream_t stream);

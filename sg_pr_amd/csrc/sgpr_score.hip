@@ -1899,6 +1899,34 @@ static int launch_ntn_prep(const sgpr_handle* h, const float* rows, int R, const
     return e == hipSuccess ? SGPR_OK : hip_fail(e, "ntn_prep_kernel launch");
 }
 
+// one call's range partials folded into g (a float4, max with what g holds): its launches then read g alone (nrng = 1)
+__global__ __launch_bounds__(256) void ap_range_fold_kernel(const float* __restrict__ rng, int nrng, float* __restrict__ g) {
+    float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
+    ap_range(rng, nrng, am, um, em, l1);
+    if (threadIdx.x == 0)
+        *reinterpret_cast<float4*>(g) = make_float4(fmaxf(g[0], am), fmaxf(g[1], um), fmaxf(g[2], em), fmaxf(g[3], l1));
+}
+
+// The f16-range question of a call that scores R rows in blocks of rb, answered once over the whole rectangle: a first
+// pass preps every block into the operand region ws (the block's launch preps it again) and folds its partials into g, so
+// that every block takes the datapath sgpr_score_all_pairs takes on the same rectangle.
+static int launch_call_range(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, int rb, void* ws,
+                             float* g, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(g, 0, 4 * sizeof(float), stream);
+    if (e != hipSuccess) return hip_fail(e, "call range: clearing");
+    for (int r0 = 0; r0 < R; r0 += rb) {
+        const int n = R - r0 < rb ? R - r0 : rb;
+        const int nrng = 2 * ap_prep_groups(n, M);
+        const ApOperands o = ap_operands(ws, n, nrng, 2);
+        const int rc = launch_ntn_prep(h, rows + (size_t)r0 * F, n, cols, M, o, nrng, stream);
+        if (rc != SGPR_OK) return rc;
+        hipLaunchKernelGGL(ap_range_fold_kernel, dim3(1), dim3(256), 0, stream, o.rng, nrng, g);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "ap_range_fold_kernel launch");
+    }
+    return SGPR_OK;
+}
+
 int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score,
                            int64_t ld, void* ws, hipStream_t stream, bool wide) {
     if (R == 0 || M == 0) return SGPR_OK;
@@ -2055,9 +2083,10 @@ int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const floa
 
 // ------------------------------------------------------------------ fused score + range selection (sgpr_score_above)
 // Rows go in blocks of at most AB_ROWS (the row operands take 2 KB per row: 0.6 GB at 300 k rows in one launch); the
-// positions of a block continue from the device-resident count of the blocks before it.
+// positions of a block continue from the device-resident count of the blocks before it, and the f16 range is the
+// call's (launch_call_range).
 // workspace: row_ptr [R + 1] i64 (used when the caller passes none) | for one row block: score_all_pairs' operands |
-// flag [items] u8 | cnt [rows] i32 | pcnt, poff [grid][2][AP_ROWS] i32
+// flag [items] u8 | cnt [rows] i32 | pcnt, poff [grid][2][AP_ROWS] i32 | (more than one block) the call's range, a float4
 constexpr int AB_ROWS = 131072;
 
 static size_t above_block_ws_bytes(const sgpr_handle* h, int R, int M) {
@@ -2068,7 +2097,7 @@ static size_t above_block_ws_bytes(const sgpr_handle* h, int R, int M) {
 
 size_t score_above_ws_bytes(const sgpr_handle* h, int R, int M) {
     if (R == 0 || M == 0) return 0;
-    return align256((size_t)(R + 1) * 8) + above_block_ws_bytes(h, R < AB_ROWS ? R : AB_ROWS, M);
+    return align256((size_t)(R + 1) * 8) + above_block_ws_bytes(h, R < AB_ROWS ? R : AB_ROWS, M) + (R > AB_ROWS ? 256 : 0);
 }
 
 size_t rows_above_ws_bytes(int R) { return R == 0 ? 0 : align256((size_t)R * 4) + align256((size_t)(R + 1) * 8); }
@@ -2079,13 +2108,16 @@ int launch_above_empty(int R, int64_t* row_ptr, unsigned long long* count, hipSt
     return e == hipSuccess ? SGPR_OK : hip_fail(e, "sgpr_score_above: clearing the counts");
 }
 
-// one row block: rows [rout0, rout0 + R) of the call; rp = the call's row_ptr + rout0
+// one row block: rows [rout0, rout0 + R) of the call; rp = the call's row_ptr + rout0; crng: the call's range (or
+// nullptr: the block is the call, its own partials are)
 static int launch_above_block(const sgpr_handle* h, const float* rows, int R, const float* cols, int M,
                               const int32_t* row_self, int row0, int window, int causal, float thr, int32_t* orows,
                               int32_t* ocols, float* ovals, int64_t cap, int64_t* rp, int rout0,
-                              unsigned long long* count, void* ws, hipStream_t stream) {
+                              unsigned long long* count, const float* crng, void* ws, hipStream_t stream) {
     const int nrng = 2 * ap_prep_groups(R, M);
     const ApOperands o = ap_operands(ws, R, nrng, 2);
+    const float* krng = crng ? crng : o.rng;
+    const int knrng = crng ? 1 : nrng;
     const int64_t grid = topk_grid(h, R, M);
     const size_t items = (size_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
     const size_t slots = (size_t)grid * 2 * AP_ROWS;
@@ -2117,8 +2149,8 @@ static int launch_above_block(const sgpr_handle* h, const float* rows, int R, co
     const int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
     if (rc != SGPR_OK) return rc;
     const dim3 gd((unsigned)grid), bd(256);
-    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, o.rng, nrng, rows,
-                       cols, a);
+    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, krng, knrng,
+                       rows, cols, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 1)");
     hipLaunchKernelGGL(above_fold_kernel, dim3((unsigned)((R + AP_ROWS - 1) / AP_ROWS)), dim3(64), 0, stream, R, M, (int)grid, a);
@@ -2129,8 +2161,8 @@ static int launch_above_block(const sgpr_handle* h, const float* rows, int R, co
     if (e != hipSuccess) return hip_fail(e, "above_scan_kernel launch");
     if (cap == 0) return SGPR_OK;                          // count only
     a.pass = 2;
-    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, o.rng, nrng, rows,
-                       cols, a);
+    hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, krng, knrng,
+                       rows, cols, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 2)");
     return SGPR_OK;
@@ -2143,11 +2175,17 @@ int launch_score_above(const sgpr_handle* h, const float* rows, int R, const flo
     unsigned char* base = static_cast<unsigned char*>(ws);
     int64_t* rp = row_ptr ? row_ptr : reinterpret_cast<int64_t*>(base);
     void* bws = base + align256((size_t)(R + 1) * 8);
+    float* crng = nullptr;
+    if (R > AB_ROWS) {
+        crng = reinterpret_cast<float*>(static_cast<unsigned char*>(bws) + above_block_ws_bytes(h, AB_ROWS, M));
+        const int rc = launch_call_range(h, rows, R, cols, M, AB_ROWS, bws, crng, stream);
+        if (rc != SGPR_OK) return rc;
+    }
     for (int r0 = 0; r0 < R; r0 += AB_ROWS) {
         const int n = R - r0 < AB_ROWS ? R - r0 : AB_ROWS;
         const int rc = launch_above_block(h, rows + (size_t)r0 * F, n, cols, M, row_self ? row_self + r0 : nullptr,
                                           row0 + r0, window, causal, thr, orows, ocols, ovals, cap, rp + r0, r0, count,
-                                          bws, stream);
+                                          crng, bws, stream);
         if (rc != SGPR_OK) return rc;
     }
     return SGPR_OK;
@@ -2177,8 +2215,9 @@ int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_
 // ------------------------------------------------------------------ fused evaluation (sgpr_score_positives / sgpr_score_threshold_counts)
 // score_topk_kernel's range question, work split and arithmetic with the TK_POS / TK_CNT epilogue.  Rows go in blocks:
 // at most AB_ROWS of them, and few enough that no workgroup sees 2^20 work items (4096 pairs each): its 32-bit LDS
-// counters cannot overflow.  workspace: column boxes [ncc][4] f64 | slabs [grid][slab words] u32 (counts only) | for one
-// row block: score_all_pairs' operands
+// counters cannot overflow; the f16 range is the whole call's (launch_call_range).  workspace: column boxes [ncc][4] f64 |
+// slabs [grid][slab words] u32 (counts only) | for one row block: score_all_pairs' operands | (more than one block) the
+// call's range, a float4
 constexpr int64_t EV_ITEMS_PER_WG = (1 << 20) - 1;
 
 // the pose box of every 256-column chunk: one wave per chunk, four columns per lane (a NaN pose: the whole plane)
@@ -2353,7 +2392,7 @@ size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T) {
     const size_t ncc = (size_t)(M + AP_COLS - 1) / AP_COLS;
     size_t b = align256(ncc * 4 * sizeof(double)) + align256(score_all_pairs_ws_bytes(rb, M));
     if (T >= 0) b += align256((size_t)topk_grid(h, rb, M) * eval_slab_words(T) * sizeof(unsigned));
-    return b;
+    return b + (rb < R ? 256 : 0);                        // (more than one block: the call's range, launch_call_range)
 }
 
 // the pose rule's squared class boundaries and the squared gaps that rule a work item out (EvalArgs, MineArgs)
@@ -2403,10 +2442,18 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
     int lg = 0;
     while ((1 << lg) <= a.T) ++lg;
     a.lg = lg;
+    float* crng = nullptr;                                // more than one block: the f16 range of the whole rectangle
+    if (rb < R) {
+        crng = reinterpret_cast<float*>(p + align256(score_all_pairs_ws_bytes(rb, M)));
+        const int rc = launch_call_range(h, rows, R, cols, M, rb, p, crng, stream);
+        if (rc != SGPR_OK) return rc;
+    }
     for (int r0 = 0; r0 < R; r0 += rb) {
         const int n = R - r0 < rb ? R - r0 : rb;
         const int nrng = 2 * ap_prep_groups(n, M);
         const ApOperands o = ap_operands(p, n, nrng, 2);
+        const float* krng = crng ? crng : o.rng;
+        const int knrng = crng ? 1 : nrng;
         const float* brows = rows + (size_t)r0 * F;
         a.truth.row0 = truth.row0 + r0;
         a.truth.gt = truth.gt ? truth.gt + (int64_t)r0 * truth.ldg : nullptr;
@@ -2415,13 +2462,13 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
         const int64_t grid = topk_grid(h, n, M);
         const dim3 gd((unsigned)grid), bd(256);
         if (!counts) {
-            hipLaunchKernelGGL((score_positives_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, o.rng,
-                               nrng, brows, cols, a);
+            hipLaunchKernelGGL((score_positives_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, krng,
+                               knrng, brows, cols, a);
             e = hipGetLastError();
             if (e != hipSuccess) return hip_fail(e, "score_positives_kernel launch");
             continue;
         }
-        hipLaunchKernelGGL((score_counts_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, o.rng, nrng,
+        hipLaunchKernelGGL((score_counts_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, krng, knrng,
                            brows, cols, a, thr, at_least, slabs, sw);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "score_counts_kernel launch");

@@ -904,19 +904,32 @@ bool wide_tail_serves(const sgpr_handle* h) {
 }
 size_t wide_tail_ws_bytes(int R, int M) { return wide_tail_ws(R, M); }
 
-// returns through *d_gate the device word the plain-fp32 kernel behind this call must test (non-zero: the rectangle is its)
-int launch_score_all_pairs_wide_any(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score,
-                                    int64_t ld, void* ws, const unsigned** d_gate, hipStream_t stream) {
+// wide_tail_prep_kernel on the R x M rectangle: the operands into ws, the range maxima into its TailHdr (atomicMax: they
+// add to what the header holds)
+int launch_wide_tail_prep(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, void* ws,
+                          hipStream_t stream) {
     TailHdr* hdr = static_cast<TailHdr*>(ws);
     unsigned short* Ab = reinterpret_cast<unsigned short*>(static_cast<unsigned char*>(ws) + 256);
     float* ur = reinterpret_cast<float*>(Ab + (size_t)R * 8 * 512);
     unsigned short* Cb = reinterpret_cast<unsigned short*>(ur + (size_t)R * TTP);
-    hipError_t e = hipMemsetAsync(hdr, 0, sizeof(TailHdr), stream);
-    if (e != hipSuccess) return hip_fail(e, "wide tail: header");
     const int nrg = (R + 15) / 16, ncb = (((M + 15) & ~15) + 63) / 64, pw = h->gm.f3;
     hipLaunchKernelGGL(wide_tail_prep_kernel, dim3(4 * nrg + ncb), dim3(256), 0, stream, h->gm, rows, R, cols, M, pw, nrg, Ab, ur, Cb, hdr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "wide_tail_prep_kernel launch");
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "wide_tail_prep_kernel launch");
+}
+
+// returns through *d_gate the device word the plain-fp32 kernel behind this call must test (non-zero: the rectangle is its);
+// fresh: the call's header starts cleared (false: it already holds the range of the caller's whole rectangle)
+int launch_score_all_pairs_wide_any(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score,
+                                    int64_t ld, void* ws, const unsigned** d_gate, hipStream_t stream, bool fresh) {
+    TailHdr* hdr = static_cast<TailHdr*>(ws);
+    unsigned short* Ab = reinterpret_cast<unsigned short*>(static_cast<unsigned char*>(ws) + 256);
+    float* ur = reinterpret_cast<float*>(Ab + (size_t)R * 8 * 512);
+    unsigned short* Cb = reinterpret_cast<unsigned short*>(ur + (size_t)R * TTP);
+    hipError_t e = fresh ? hipMemsetAsync(hdr, 0, sizeof(TailHdr), stream) : hipSuccess;
+    if (e != hipSuccess) return hip_fail(e, "wide tail: header");
+    const int rc = launch_wide_tail_prep(h, rows, R, cols, M, ws, stream);
+    if (rc != SGPR_OK) return rc;
     const long long items = (long long)R * ((((M + 15) >> 4) + 15) >> 4);
     const long long slots = (long long)h->num_cus * 8;
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((items + 3) / 4, slots));

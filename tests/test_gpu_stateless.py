@@ -33,8 +33,10 @@ Workspace and output audit: what initialises each region in the same call before
 | | partial lists `[grid][2][16][k]` values / columns | producer: a workgroup stores the lists of the row groups at both ends of its range; `topk_merge_kernel` reads only the slots of the workgroups that cover a row group |
 | | d_values / d_indices (outputs) | producer: every [R][k] entry is written, (-inf, -1) where fewer than k columns qualify |
 | sgpr_score_topk (wide-range, any-shape) | score block + the all-pairs workspace | producer: the block's all-pairs call; the selection reads only that block |
+| every row-blocked epilogue (any-shape, matrix-core tail) | the all-pairs region's `TailHdr` | memset once per call, then a prep pass over every block; no block's scoring clears it |
 | sgpr_score_above (fused) | row_ptr [R + 1] in the workspace when the caller passes none | producer: `above_scan_kernel` |
 | | item flags, one byte per 16 x 256 work item | memset of `items` bytes per row block |
+| | the call's range `float4` (more than one row block; also sgpr_score_positives / _threshold_counts) | memset, then `ap_range_fold_kernel` after each block's first-pass prep, before any block is scored |
 | | per-row counts `cnt` | producer: pass 1 (rows inside one workgroup) or `above_fold_kernel` (rows shared between workgroups) |
 | | partial counts / offsets `pcnt`, `poff` | producer: pass 1 stores the shares it owns; the fold reads only those |
 | | d_count, d_row_ptr (outputs) | `above_scan_kernel` (the first block stores, later blocks add to the count the first stored); memsets when R or M is 0 |
