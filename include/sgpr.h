@@ -360,6 +360,33 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
                     const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
                     int32_t* d_indices, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Loop-closure candidates for k up to SGPR_TOPK_LARGE_MAX (recall@1 %, candidate lists for a geometric check).  Same
+ * lists as sgpr_score_topk / sgpr_topk_rows: for every row r the k best eligible columns by (value descending, column
+ * ascending), IEEE comparison (-0.0 ties +0.0, the lower column first; the stored bits are reported), NaN and -inf never
+ * qualify, (-inf, -1) in the slots past the last qualifying column (k > M is allowed).  Eligibility is sgpr_score_topk's:
+ * |c - self_r| > window (window < 0: no window), with SGPR_TOPK_CAUSAL c < self_r, self_r = d_row_self[r] or row0 + r
+ * (an entry of d_row_self outside [0, M): sgpr_check_status reports it).  For k <= 16 both return the bits and indices
+ * of the k <= 16 entry points.
+ * - sgpr_topk_rows_large: a resident matrix d_score [R][ld] (ld >= M, window >= -1, as sgpr_topk_rows).
+ * - sgpr_score_topk_large: the rectangle d_pooled_rows [R] x d_pooled_cols [M] scored in row blocks of at most 64 MB
+ *   (every handle), each selected as it is written; every value is sgpr_score_all_pairs' entry on the whole rectangle
+ *   (the f16-range question is answered once per call).
+ * A radix select over order-preserving keys, each row split across workgroups (sgpr_select.hip).
+ * Workspace: one 64 MB score block (pooled form) plus terms linear in min(R, 4096) and M, never R * M.  Arguments are
+ * checked before the device is touched: a NULL pointer, k outside 1..SGPR_TOPK_LARGE_MAX, unknown flag bits or
+ * row0 + R past INT_MAX give SGPR_E_INVALID, a workspace below the _workspace_bytes answer SGPR_E_WORKSPACE (which is
+ * 0 for invalid arguments).  Results depend on the arguments alone, never on the workspace's contents.  Asynchronous
+ * on `stream`. */
+#define SGPR_TOPK_LARGE_MAX 4096
+size_t sgpr_topk_rows_large_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags);
+int sgpr_topk_rows_large(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, const int32_t* d_row_self,
+                         int row0, int window, int flags, int k, float* d_values, int32_t* d_indices, void* d_workspace,
+                         size_t workspace_bytes, void* stream);
+size_t sgpr_score_topk_large_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags);
+int sgpr_score_topk_large(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                          const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
+                          int32_t* d_indices, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Hard-pair mining without the R x M matrix: for every row r the k (1..16) hardest pose-labelled pairs (r, c) of the
  * rectangle d_pooled_rows [R] x d_pooled_cols [M].
  * - Column c is eligible for row r iff it is for sgpr_score_topk (window, SGPR_TOPK_CAUSAL, self_r = d_row_self[r] or

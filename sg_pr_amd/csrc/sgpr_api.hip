@@ -1205,10 +1205,12 @@ static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t hea
 // The f16-range question is the whole rectangle's, as in sgpr_score_all_pairs on it: on an any-shape handle's matrix-core
 // tail a first pass preps every block into the all-pairs region, its TailHdr cleared once and accumulating the maxima of
 // all blocks, and no block's scoring clears it (the other handles' row blocks take the three-plane instance: no gate).
+// crng (a float4 in the caller's head, used on the production handle alone): there launch_call_range answers the
+// question once for all blocks, and every block's all-pairs launch reads that answer instead of its own rows' partials.
 extern "C++" {   // (a template, inside the C-ABI block)
 template <class Consume>
 static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, size_t head_bytes,
-                            void* ws, size_t ws_bytes, void* stream, Consume&& consume) {
+                            void* ws, size_t ws_bytes, void* stream, Consume&& consume, float* crng = nullptr) {
     const int rb = score_block_rows(R, M), pw = pooled_width(h);
     const size_t block_bytes = a256((size_t)rb * M * sizeof(float));
     float* block = static_cast<float*>(ws);
@@ -1217,6 +1219,11 @@ static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, cons
     const size_t aws_bytes = ws_bytes - block_bytes - head_bytes;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool one_range = h->generic_only && wide_tail_serves(h) && rb < R;
+    const bool call_range = crng && has_fused_epilogues(h) && rb < R;
+    if (call_range) {
+        const int rc = launch_call_range(h, rows, R, cols, M, rb, aws, crng, s);
+        if (rc != SGPR_OK) return rc;
+    }
     if (one_range) {
         hipError_t e = hipMemsetAsync(aws, 0, 256, s);    // (the TailHdr)
         if (e != hipSuccess) return hip_fail(e, "row blocks: clearing the range header");
@@ -1227,8 +1234,9 @@ static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, cons
     }
     for (int r0 = 0; r0 < R; r0 += rb) {
         const int n = std::min(rb, R - r0);
-        int rc = one_range ? score_rect_any_shape(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, aws_bytes, s, false)
-                           : sgpr_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, aws_bytes, stream);
+        int rc = one_range  ? score_rect_any_shape(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, aws_bytes, s, false)
+                 : call_range ? launch_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, s, false, crng)
+                              : sgpr_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, aws_bytes, stream);
         if (rc != SGPR_OK) return rc;
         rc = consume(block, head, r0, n);
         if (rc != SGPR_OK) return rc;
@@ -1274,6 +1282,80 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
                                     d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
     };
     return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, 0, d_workspace, workspace_bytes, stream, select);
+}
+
+// ---- sgpr_score_topk_large / sgpr_topk_rows_large: k up to SGPR_TOPK_LARGE_MAX through the large-k selection
+//      (sgpr_select.hip); the pooled form scores 64 MB row blocks on every handle and selects from each
+static bool topk_large_args_ok(const char* fn, int R, int k, int flags, int row0) {
+    if (k < 1 || k > SGPR_TOPK_LARGE_MAX) {
+        set_error(std::string(fn) + ": k must lie in 1.." + std::to_string(SGPR_TOPK_LARGE_MAX));
+        return false;
+    }
+    if (flags & ~SGPR_TOPK_CAUSAL) {
+        set_error(std::string(fn) + ": unknown flag bits " + std::to_string(flags & ~SGPR_TOPK_CAUSAL));
+        return false;
+    }
+    return row0_ok(fn, row0, R);
+}
+
+// head of the pooled form: the call's f16 range (a float4) | the selection's workspace for one block
+static size_t topk_large_head_bytes(int R, int M) { return 256 + a256(select_ws_bytes(score_block_rows(R, M), M)); }
+
+size_t sgpr_topk_rows_large_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
+    if (!h || R < 0 || M < 0 || k < 1 || k > SGPR_TOPK_LARGE_MAX || (flags & ~SGPR_TOPK_CAUSAL)) return 0;
+    return select_ws_bytes(R, M);
+}
+
+int sgpr_topk_rows_large(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, const int32_t* d_row_self,
+                         int row0, int window, int flags, int k, float* d_values, int32_t* d_indices, void* d_workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!h || (!d_score && M > 0) || !d_values || !d_indices || R < 0 || M < 0 || ld < M || window < -1) {
+        set_error("sgpr_topk_rows_large: NULL argument, negative size, leading dimension below M or window below -1");
+        return SGPR_E_INVALID;
+    }
+    if (!topk_large_args_ok("sgpr_topk_rows_large", R, k, flags, row0)) return SGPR_E_INVALID;
+    if (!workspace_ok("sgpr_topk_rows_large", sgpr_topk_rows_large_workspace_bytes(h, R, M, k, flags), d_workspace,
+                      workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    if (R == 0) return SGPR_OK;
+    DeviceGuard guard(h->device);
+    return launch_select_rows(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, k, d_values,
+                              d_indices, d_workspace, false, h->d_status, static_cast<hipStream_t>(stream));
+}
+
+size_t sgpr_score_topk_large_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
+    if (!h || R < 0 || M < 0 || k < 1 || k > SGPR_TOPK_LARGE_MAX || (flags & ~SGPR_TOPK_CAUSAL)) return 0;
+    if (R == 0 || M == 0) return 0;
+    return row_blocks_ws_bytes(h, R, M, topk_large_head_bytes(R, M));
+}
+
+int sgpr_score_topk_large(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                          const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
+                          int32_t* d_indices, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!h || R < 0 || M < 0 || (R > 0 && (!d_values || !d_indices)) || (R > 0 && M > 0 && (!d_pooled_rows || !d_pooled_cols))) {
+        set_error("sgpr_score_topk_large: NULL argument or negative count");
+        return SGPR_E_INVALID;
+    }
+    if (!topk_large_args_ok("sgpr_score_topk_large", R, k, flags, row0)) return SGPR_E_INVALID;
+    if (!workspace_ok("sgpr_score_topk_large", sgpr_score_topk_large_workspace_bytes(h, R, M, k, flags), d_workspace,
+                      workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    if (R == 0) return SGPR_OK;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0)
+        return launch_select_rows(nullptr, R, 0, 0, d_row_self, row0, window, causal, k, d_values, d_indices, nullptr, false,
+                                  h->d_status, s);
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256((size_t)score_block_rows(R, M) * M * sizeof(float)));
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        return launch_select_rows(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, k,
+                                  d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, head + 256, r0 > 0, h->d_status,
+                                  s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, topk_large_head_bytes(R, M), d_workspace,
+                            workspace_bytes, stream, select, crng);
 }
 
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks

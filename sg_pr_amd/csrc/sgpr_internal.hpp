@@ -288,8 +288,12 @@ int launch_sem_tables(const DevWeights& w, float* d_table, float* d_vmax, hipStr
 int launch_score_pairs(const sgpr_handle* h, const float* p1, const int32_t* i1, const float* p2, const int32_t* i2,
                        int64_t P, float* score, hipStream_t stream);
 size_t score_all_pairs_ws_bytes(int R, int M);
+// crng: the f16 range of a larger call this rectangle is a row block of (launch_call_range), read instead of its own
 int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score,
-                           int64_t ld, void* ws, hipStream_t stream, bool wide = false);
+                           int64_t ld, void* ws, hipStream_t stream, bool wide = false, const float* crng = nullptr);
+// the f16-range question of R rows scored in blocks of rb, answered once into the float4 g (ws: score_all_pairs_ws_bytes(rb, M))
+int launch_call_range(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, int rb, void* ws,
+                      float* g, hipStream_t stream);
 size_t score_all_pairs_multi_ws_bytes(int n, const sgpr_pairs_job* jobs);
 int launch_score_all_pairs_multi(const sgpr_handle* h, int n, const sgpr_pairs_job* jobs, void* ws, hipStream_t stream);
 size_t score_topk_ws_bytes(const sgpr_handle* h, int R, int M, int k);
@@ -298,6 +302,12 @@ int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const floa
 // sgpr_topk_rows' selection with a row_self table, the causal rule and an output row stride of k (sgpr_metrics.hip)
 int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
                          int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
+// the large-k selection of a resident n x M block into [n][k] (sgpr_select.hip); ws_clean: ws is what an earlier call on
+// the same stream left (its histograms are clear)
+size_t select_ws_bytes(int n, int M);
+int launch_select_rows(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                       int causal, int k, float* val, int32_t* idx, void* ws, bool ws_clean, int32_t* status,
+                       hipStream_t stream);
 // sgpr_score_mine on the production handle (positives: SGPR_MINE_POSITIVES, else the negatives) and its selection on a
 // resident block (sgpr_mine_rows, the chunked path of the other handles; sgpr_metrics.hip)
 size_t score_mine_ws_bytes(const sgpr_handle* h, int R, int M, int k);

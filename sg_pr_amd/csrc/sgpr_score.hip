@@ -1910,8 +1910,8 @@ __global__ __launch_bounds__(256) void ap_range_fold_kernel(const float* __restr
 // The f16-range question of a call that scores R rows in blocks of rb, answered once over the whole rectangle: a first
 // pass preps every block into the operand region ws (the block's launch preps it again) and folds its partials into g, so
 // that every block takes the datapath sgpr_score_all_pairs takes on the same rectangle.
-static int launch_call_range(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, int rb, void* ws,
-                             float* g, hipStream_t stream) {
+int launch_call_range(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, int rb, void* ws, float* g,
+                      hipStream_t stream) {
     hipError_t e = hipMemsetAsync(g, 0, 4 * sizeof(float), stream);
     if (e != hipSuccess) return hip_fail(e, "call range: clearing");
     for (int r0 = 0; r0 < R; r0 += rb) {
@@ -1928,7 +1928,7 @@ static int launch_call_range(const sgpr_handle* h, const float* rows, int R, con
 }
 
 int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, float* score,
-                           int64_t ld, void* ws, hipStream_t stream, bool wide) {
+                           int64_t ld, void* ws, hipStream_t stream, bool wide, const float* crng) {
     if (R == 0 || M == 0) return SGPR_OK;
     const int nrng = 2 * ap_prep_groups(R, M);
     const ApOperands o = ap_operands(ws, R, nrng, wide ? 3 : 2);
@@ -1951,7 +1951,7 @@ int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const
     const int64_t slots = (int64_t)h->num_cus * AP_OCC;   // one resident slot per workgroup: a single, full round
     const unsigned grid = (unsigned)(items < slots ? items : slots);
     hipLaunchKernelGGL((score_all_pairs_kernel<AP_OCC, AP_NI, 0>), dim3(grid), dim3(256), 0, stream, h->w, R, M, o.Ab, o.Cb,
-                       o.ur, o.rng, nrng, rows, cols, score, ld);
+                       o.ur, crng ? crng : o.rng, crng ? 1 : nrng, rows, cols, score, ld);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "score_all_pairs_kernel launch");
     return SGPR_OK;

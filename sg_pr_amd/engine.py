@@ -43,6 +43,8 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_pair_positives", "sgpr_pair_threshold_counts_workspace_bytes", "sgpr_pair_threshold_counts",
                "sgpr_f1_max_workspace_bytes", "sgpr_f1_max", "sgpr_topk_rows",
                "sgpr_score_topk_workspace_bytes", "sgpr_score_topk",
+               "sgpr_topk_rows_large_workspace_bytes", "sgpr_topk_rows_large",
+               "sgpr_score_topk_large_workspace_bytes", "sgpr_score_topk_large",
                "sgpr_score_mine_workspace_bytes", "sgpr_score_mine", "sgpr_mine_rows_workspace_bytes", "sgpr_mine_rows",
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
                "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
@@ -174,6 +176,14 @@ def load_library():
     lib.sgpr_score_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
     lib.sgpr_score_topk.restype = i32
     lib.sgpr_score_topk.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.sgpr_topk_rows_large_workspace_bytes.restype = sz
+    lib.sgpr_topk_rows_large_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
+    lib.sgpr_topk_rows_large.restype = i32
+    lib.sgpr_topk_rows_large.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.sgpr_score_topk_large_workspace_bytes.restype = sz
+    lib.sgpr_score_topk_large_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
+    lib.sgpr_score_topk_large.restype = i32
+    lib.sgpr_score_topk_large.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
     lib.sgpr_score_mine_workspace_bytes.restype = sz
     lib.sgpr_score_mine_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
     lib.sgpr_score_mine.restype = i32
@@ -880,19 +890,76 @@ class Engine:
         torch.cuda.current_stream(self.device).synchronize()
         return host.numpy().copy()
 
-    def topk_rows(self, score, k=1, row0=0, window=-1):
-        """Best k columns per row outside |col - (row0 + row)| <= window -> (values f32 [R,k], indices i32 [R,k])."""
+    def topk_rows(self, score, k=1, row0=0, window=-1, causal=False, row_self=None):
+        """Best k columns per row outside |col - (row0 + row)| <= window -> (values f32 [R,k], indices i32 [R,k]).
+        k in {1, 4, 8, 16} without causal / row_self: sgpr_topk_rows; any other k in 1..4096 (or the causal rule, or a
+        row_self table, as score_topk takes them): topk_rows_large."""
+        if int(k) in (1, 4, 8, 16) and not causal and row_self is None:
+            score = self._dev(score, torch.float32, "score")
+            r, m = score.shape
+            assert score.stride(1) == 1
+            vals = torch.empty(r, k, dtype=torch.float32, device=self.device)
+            idx = torch.empty(r, k, dtype=torch.int32, device=self.device)
+            rc = self.lib.sgpr_topk_rows(self._h, _ptr(score), r, m, score.stride(0), int(row0), int(window), int(k),
+                                         _ptr(vals), _ptr(idx), self._stream())
+            self._check(rc)
+            return vals, idx
+        return self.topk_rows_large(score, k=k, row0=row0, window=window, causal=causal, row_self=row_self)
+
+    def _row_self(self, row_self, r):
+        if row_self is None:
+            return None
+        rs = self._dev(row_self, torch.int32, "row_self")
+        if rs.shape != (r,):
+            raise ValueError("row_self must be [%d], got %s" % (r, tuple(rs.shape)))
+        return rs
+
+    def topk_rows_large_workspace_bytes(self, r, m, k, causal=False):
+        return int(self.lib.sgpr_topk_rows_large_workspace_bytes(self._h, int(r), int(m), int(k),
+                                                                 self.TOPK_CAUSAL if causal else 0))
+
+    def topk_rows_large(self, score, k=1, row0=0, window=-1, causal=False, row_self=None):
+        """sgpr_topk_rows_large: the best k (1..4096) eligible columns per row of a resident matrix (score_topk's rules:
+        window, causal, row_self) -> (values f32 [R,k], indices i32 [R,k]); (-inf, -1) past the last eligible column."""
         score = self._dev(score, torch.float32, "score")
         r, m = score.shape
-        assert score.stride(1) == 1
-        vals = torch.empty(r, k, dtype=torch.float32, device=self.device)
-        idx = torch.empty(r, k, dtype=torch.int32, device=self.device)
-        rc = self.lib.sgpr_topk_rows(self._h, _ptr(score), r, m, score.stride(0), int(row0), int(window), int(k),
-                                     _ptr(vals), _ptr(idx), self._stream())
+        if score.stride(1) != 1:
+            score = score.contiguous()
+        rs = self._row_self(row_self, r)
+        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
+        flags = self.TOPK_CAUSAL if causal else 0
+        ws_bytes = self.lib.sgpr_topk_rows_large_workspace_bytes(self._h, r, m, int(k), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_topk_rows_large(self._h, _ptr(score), r, m, max(score.stride(0), m), _ptr(rs), int(row0),
+                                           int(window), flags, int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes,
+                                           self._stream())
         self._check(rc)
         return vals, idx
 
     TOPK_CAUSAL = 1     # SGPR_TOPK_CAUSAL of include/sgpr.h
+    TOPK_LARGE_MAX = 4096   # SGPR_TOPK_LARGE_MAX
+
+    def score_topk_large_workspace_bytes(self, r, m, k, causal=False):
+        return int(self.lib.sgpr_score_topk_large_workspace_bytes(self._h, int(r), int(m), int(k),
+                                                                  self.TOPK_CAUSAL if causal else 0))
+
+    def score_topk_large(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None):
+        """sgpr_score_topk_large: score_topk's lists for k in 1..4096, the rectangle scored in row blocks of at most
+        64 MB and each selected as it is written (the large-k selection, whatever k)."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
+        flags = self.TOPK_CAUSAL if causal else 0
+        ws_bytes = self.lib.sgpr_score_topk_large_workspace_bytes(self._h, r, m, int(k), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_score_topk_large(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window),
+                                            flags, int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        return vals, idx
 
     def score_topk_workspace_bytes(self, r, m, k=1, causal=False):
         return int(self.lib.sgpr_score_topk_workspace_bytes(self._h, int(r), int(m), int(k),
@@ -902,7 +969,10 @@ class Engine:
         """Best k columns per row of the rectangle pooled_rows x pooled_cols without forming it (sgpr_score_topk):
         column c qualifies for row r iff |c - self_r| > window (window < 0: no window) and, causal, c < self_r, where
         self_r = row_self[r] or row0 + r.  -> (values f32 [R,k], indices i32 [R,k]); every value is bit-identical to
-        score_all_pairs' entry (r, c); (-inf, -1) where fewer than k columns qualify."""
+        score_all_pairs' entry (r, c); (-inf, -1) where fewer than k columns qualify.  k in 17..4096: score_topk_large."""
+        if int(k) > 16:
+            return self.score_topk_large(pooled_rows, pooled_cols, k=k, window=window, row0=row0, causal=causal,
+                                         row_self=row_self)
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]

@@ -307,6 +307,23 @@ def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1
     return (hits / counted).cpu().numpy() if counted else np.zeros(kk)
 
 
+def recall_percent_n(num_frames, percent=1.0):
+    """Candidates per query of recall@percent (PointNetVLAD): N = max(1, round(M' * percent / 100)), M' database frames."""
+    return max(1, int(round(num_frames * float(percent) / 100.0)))
+
+
+def recall_at_percent(indices, pose_xz, percent=1.0, p_thresh=3.0, window=50, causal=False):
+    """Recall@percent of loop-closure candidates: recall_at_n at N = max(1, round(M' * percent / 100)) candidates per
+    query, M' = len(pose_xz) database frames.  indices [M, K] with K >= N (ValueError otherwise).  -> (recall, N)."""
+    import torch
+    from .allpairs import pose_xz as _xz
+    idx = torch.as_tensor(indices)
+    n = recall_percent_n(_xz(pose_xz).shape[0], percent)
+    if idx.dim() != 2 or idx.shape[1] < n:
+        raise ValueError("recall@%g%% needs %d candidates per query, indices hold %s" % (percent, n, tuple(idx.shape)))
+    return float(recall_at_n(idx[:, :n], pose_xz, p_thresh=p_thresh, window=window, causal=causal)[n - 1]), n
+
+
 def precision_recall_at(rows, cols, pose_xz, p_thresh=3.0, n_thresh=20.0, window=50, causal=False, chunk=None):
     """Precision and recall of a list of accepted pairs (sgpr_score_above's rows / cols of query frames 0..M-1 against
     frames 0..M-1, M = len(pose_xz)) under the repository's pair classes: distance <= p_thresh positive, >= n_thresh

@@ -13,9 +13,11 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
 `load` refuses them.
 
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
+                                            [--recall-percent P]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
-frame, indices [M,K], scores [M,K] and recall@1..K; with --threshold also `<seq>_above.npz` with every pair scoring
+frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
+max(K, N) candidates, N = max(1, round(M * P / 100)), and the file adds recall_percent and recall_percent_n; with --threshold also `<seq>_above.npz` with every pair scoring
 >= T (rows, cols, scores) and its precision / recall (metrics.precision_recall_at); with --hard K also `<seq>_hard.npz`
 with every frame's K hardest negatives (highest scores at >= 20 m) and K hardest positives (lowest scores within
 p_thresh), indices and scores (Engine.score_mine; the window applies to both), and the number of frames that have a
@@ -148,6 +150,8 @@ def main(argv=None):
     ap.add_argument("--threshold", type=float, default=None)
     ap.add_argument("--hard", type=int, default=None, metavar="K",
                     help="also write <seq>_hard.npz: every frame's K hardest negatives and positives (1..16)")
+    ap.add_argument("--recall-percent", type=float, default=None, metavar="P",
+                    help="also report recall@P%% (N = max(1, round(frames * P / 100)) candidates, k = max(--k, N))")
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
     args = sgpr_args()
     args.load(opt.config)
@@ -166,11 +170,22 @@ def main(argv=None):
         db = PlaceDatabase(trainer.model, capacity=len(seq))
         db.add(seq.centers, seq.labels)                    # the launch evaluate_all_pairs makes: size_order + ordered embed
         m = len(seq)
-        vals, idx = db.query_ids(torch.arange(m), k=opt.k, window=opt.window, causal=opt.causal)
+        k = opt.k
+        extra = {}
+        if opt.recall_percent is not None:
+            k = max(k, metrics.recall_percent_n(m, opt.recall_percent))
+        vals, idx = db.query_ids(torch.arange(m), k=k, window=opt.window, causal=opt.causal)
         recall = metrics.recall_at_n(idx, seq.poses, p_thresh=float(args.p_thresh), window=opt.window, causal=opt.causal)
+        if opt.recall_percent is not None:
+            rp, n = metrics.recall_at_percent(idx, seq.poses, percent=opt.recall_percent, p_thresh=float(args.p_thresh),
+                                              window=opt.window, causal=opt.causal)
+            extra = {"recall_percent": np.float64(rp), "recall_percent_n": np.int64(n)}
         np.savez(os.path.join(args.output_path, sequence + "_topk.npz"), frame=np.arange(m),
-                 indices=idx.cpu().numpy(), scores=vals.cpu().numpy(), recall=recall)
-        print("sequence", sequence, "frames", m, "recall@1..%d" % opt.k, " ".join("%.4f" % r for r in recall))
+                 indices=idx.cpu().numpy(), scores=vals.cpu().numpy(), recall=recall, **extra)
+        print("sequence", sequence, "frames", m, "recall@1..%d" % k, " ".join("%.4f" % r for r in recall))
+        if extra:
+            print("sequence", sequence, "recall@%g%% (N = %d) %.4f" % (opt.recall_percent, extra["recall_percent_n"],
+                                                                       extra["recall_percent"]))
         results[sequence] = recall
         if opt.threshold is not None:
             rows, cols, scores, _ = db.query_ids_above(torch.arange(m), opt.threshold, window=opt.window,
