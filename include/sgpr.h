@@ -573,6 +573,37 @@ int sgpr_edgeconv_train_backward(const float* d_dy, const float* d_P, const floa
                                  float* d_dP, float* d_dQ, float* d_dgamma, float* d_dbeta, void* d_workspace,
                                  size_t workspace_bytes, void* stream);
 
+/* ---- training: the tail over every ordered pair of a batch (tensor network + head + weighted BCE) ------------------
+ * Replaces, for training, TenorNetworkModule.forward + fully_connected_first + scoring_layer + binary_cross_entropy
+ * (layers_batch.py:70-83, sg_net.py:128-137) for ALL G x G ordered pairs of d_rep [G,F] at once, forward and backward,
+ * without a [G^2, F, T] intermediate.  For the ordered pair (i, j):
+ *   z_t = relu(sum_{f,g} rep[i,f] W[f,g,t] rep[j,g] + sum_f V[t,f] rep[i,f] + sum_g V[t,F+g] rep[j,g] + b_t),
+ *   h = relu(fc1_w z + fc1_b), d_pred[i,j] = sigmoid(fc2_w . h + fc2_b) for every (i, j), the diagonal included.
+ *   d_cls [G,G] u8: 0 = negative (y = 0, weight w_neg), 1 = positive (y = 1, weight w_pos), anything else = not in the
+ *   loss; about ORDERED pairs, need not be symmetric.  d_loss[0] = sum w l / sum w with l = -(y log s + (1-y) log(1-s)),
+ *   both logs clamped at -100; d_wsum[0] = sum w.  No labelled pair (or sum w = 0): loss 0 and every gradient 0.
+ *   backward: d_dloss[0] (device) is the gradient at the loss; dlogit = (w / wsum) dloss (s - y) / max(s (1-s), 1e-12)
+ *   * s (1-s) (torch's BCE-then-sigmoid chain: a saturated prediction has a zero gradient); ReLU' is 0 at 0.  Needs the
+ *   forward's d_pred and d_wsum and the same inputs -> d_drep [G,F], d_dW [F,F,T], d_dV [T,2F], d_db [T], d_dfc1_w
+ *   [H,T], d_dfc1_b [H], d_dfc2_w [H], d_dfc2_b [1].
+ * fp32 operands, fp64 accumulators for every sum over pairs; no atomics and fixed summation orders, so two calls on the
+ * same inputs give the same bits on any stream.  1 <= G <= SGPR_TRAIN_PAIRS_MAX_GRAPHS, F <= SGPR_ANY_MAX_FILTERS_3,
+ * T, H <= SGPR_ANY_MAX_NEURONS (beyond: SGPR_E_DIMS, and the workspace query answers 0); a NULL pointer or a negative
+ * weight is SGPR_E_INVALID, a missing or short workspace SGPR_E_WORKSPACE; all checked before the device is touched.
+ * d_workspace: sgpr_pairs_train_workspace_bytes bytes, any contents.  Handle-free; runs on the caller's current device. */
+#define SGPR_TRAIN_PAIRS_MAX_GRAPHS 1024
+size_t sgpr_pairs_train_workspace_bytes(int G, int F, int T, int H);
+int sgpr_pairs_train_forward(const float* d_rep, const float* d_W, const float* d_V, const float* d_b,
+                             const float* d_fc1_w, const float* d_fc1_b, const float* d_fc2_w, const float* d_fc2_b,
+                             const uint8_t* d_cls, float w_neg, float w_pos, int G, int F, int T, int H, float* d_pred,
+                             float* d_loss, float* d_wsum, void* d_workspace, size_t workspace_bytes, void* stream);
+int sgpr_pairs_train_backward(const float* d_dloss, const float* d_wsum, const float* d_pred, const float* d_rep,
+                              const float* d_W, const float* d_V, const float* d_b, const float* d_fc1_w,
+                              const float* d_fc1_b, const float* d_fc2_w, const float* d_fc2_b, const uint8_t* d_cls,
+                              float w_neg, float w_pos, int G, int F, int T, int H, float* d_drep, float* d_dW,
+                              float* d_dV, float* d_db, float* d_dfc1_w, float* d_dfc1_b, float* d_dfc2_w,
+                              float* d_dfc2_b, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- upstream of the path: labelled LiDAR scan -> semantic-graph nodes -------------------------
  * Replaces, for one scan, gen_labels + the node half of gen_graphs (data_process/gen_label_graph.py:196-365):
  * raw SemanticKITTI labels are remapped (learning_map, :23-58); road / parking and the discarded classes produce no

@@ -52,6 +52,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
                "sgpr_attention_pool_any", "sgpr_ntn_any",
                "sgpr_edgeconv_train_workspace_bytes", "sgpr_edgeconv_train_forward", "sgpr_edgeconv_train_backward",
+               "sgpr_pairs_train_workspace_bytes", "sgpr_pairs_train_forward", "sgpr_pairs_train_backward",
                "sgpr_cluster_workspace_bytes", "sgpr_cluster_scan", "sgpr_graph_edges",
                "sgpr_debug_set_profile_buffer", "sgpr_debug_set_skip_mask", "sgpr_debug_uses_f16_planes", "sgpr_last_error",
                "sgpr_abi_version"]
@@ -230,6 +231,12 @@ def load_library():
     lib.sgpr_edgeconv_train_forward.argtypes = [vp] * 5 + [i32] * 4 + [ctypes.c_float] + [vp] * 6 + [sz, vp]
     lib.sgpr_edgeconv_train_backward.restype = i32
     lib.sgpr_edgeconv_train_backward.argtypes = [vp] * 10 + [i32] * 4 + [ctypes.c_float] + [vp] * 5 + [sz, vp]
+    lib.sgpr_pairs_train_workspace_bytes.restype = sz
+    lib.sgpr_pairs_train_workspace_bytes.argtypes = [i32] * 4
+    lib.sgpr_pairs_train_forward.restype = i32
+    lib.sgpr_pairs_train_forward.argtypes = [vp] * 9 + [ctypes.c_float] * 2 + [i32] * 4 + [vp] * 4 + [sz, vp]
+    lib.sgpr_pairs_train_backward.restype = i32
+    lib.sgpr_pairs_train_backward.argtypes = [vp] * 12 + [ctypes.c_float] * 2 + [i32] * 4 + [vp] * 9 + [sz, vp]
     lib.sgpr_cluster_workspace_bytes.restype = sz
     lib.sgpr_cluster_workspace_bytes.argtypes = [i32]
     lib.sgpr_cluster_scan.restype = i32

@@ -8,6 +8,10 @@ torch forms (and differentiates), and the kernels do the gather, the batch stati
 and the backward through all of it.  conv_end (Conv1d + BatchNorm1d), attention, the tensor network, the head and the
 BCE loss are small dense work in torch ops.  SG's inference engine is untouched: `SGFitter.score` runs on it.
 
+`SGFitter(in_batch="all" | "balanced")` trains on every pose-labelled ordered pair among the 2 * batch graphs of a step
+instead of the 2 * batch listed ones: `pair_classes` labels the G x G square on the host and `PairsTail` (tensor network
++ head + weighted BCE over the square, csrc/sgpr_train_pairs.hip) replaces the torch tail, forward and backward.
+
 The reference feeds every pair twice (features_1 = [a, b], features_2 = [b, a]: sg_net.py:369-376), and both conv
 passes see the same multiset of graphs, so the same batch statistics.  Here the 2 * batch distinct graphs are embedded
 once, the pairs are the concatenations (pA, pB) and (pB, pA), and each BatchNorm running-stat update is applied twice,
@@ -106,6 +110,74 @@ class EdgeConvBN(torch.autograd.Function):
 def edgeconv_bn(P, Q, idx, gamma, beta, eps=1e-5):
     """Functional form of EdgeConvBN -> (y, mean, biased var)."""
     return EdgeConvBN.apply(P, Q, idx, gamma, beta, eps)
+
+
+class PairsTail(torch.autograd.Function):
+    """Tensor network + head + weighted BCE over every ordered pair of rep [G,F] (sgpr_pairs_train_forward / _backward,
+    csrc/sgpr_train_pairs.hip) -> (loss, pred [G,G], wsum).  cls [G,G] uint8: 0 = negative (weight w_neg), 1 = positive
+    (w_pos), anything else = not in the loss.  W [F,F,T], V [T,2F], b [T], fc1_w [H,T], fc1_b [H], fc2_w [H], fc2_b [1].
+    Differentiable in rep and the seven parameter tensors; pred and wsum carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, rep, cls, W, V, b, fc1_w, fc1_b, fc2_w, fc2_b, w_neg=1.0, w_pos=1.0):
+        lib = _engine.load_library()
+        if not rep.is_cuda:
+            raise RuntimeError("PairsTail runs on the MI355X only (there is no CPU fallback)")
+        dev = rep.device
+        shapes = (rep.shape, W.shape, V.shape, b.shape, fc1_w.shape, fc1_b.shape, fc2_w.shape, fc2_b.shape)
+        rep, W, V, b, fc1_w, fc1_b, fc2_w, fc2_b = (t.detach().to(device=dev, dtype=torch.float32).contiguous()
+                                                    for t in (rep, W, V, b, fc1_w, fc1_b, fc2_w, fc2_b))
+        if rep.dim() != 2 or W.dim() != 3:
+            raise ValueError("PairsTail: rep [G,F], W [F,F,T]")
+        g, f = rep.shape
+        t, h = W.shape[2], fc1_w.shape[0]
+        cls = cls.to(device=dev, dtype=torch.uint8).contiguous()
+        if tuple(W.shape) != (f, f, t) or V.numel() != 2 * f * t or b.numel() != t or tuple(fc1_w.shape) != (h, t) or \
+                fc1_b.numel() != h or fc2_w.numel() != h or fc2_b.numel() != 1 or tuple(cls.shape) != (g, g):
+            raise ValueError("PairsTail: rep [G,F], cls [G,G], W [F,F,T], V [T,2F], b [T], fc1_w [H,T], fc1_b [H], "
+                             "fc2_w [H], fc2_b [1]")
+        pred = torch.empty(g, g, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        wsum = torch.empty((), dtype=torch.float32, device=dev)
+        ws_bytes = int(lib.sgpr_pairs_train_workspace_bytes(g, f, t, h))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        p = _engine._ptr
+        with torch.cuda.device(dev):
+            _checked(lib, lib.sgpr_pairs_train_forward(p(rep), p(W), p(V), p(b), p(fc1_w), p(fc1_b), p(fc2_w), p(fc2_b),
+                                                       p(cls), float(w_neg), float(w_pos), g, f, t, h, p(pred), p(loss),
+                                                       p(wsum), p(ws), ws_bytes, ctypes_stream(rep)))
+        ctx.save_for_backward(rep, cls, W, V, b, fc1_w, fc1_b, fc2_w, fc2_b, pred, wsum)
+        ctx.weights = (float(w_neg), float(w_pos))
+        ctx.shapes = shapes
+        ctx.mark_non_differentiable(pred, wsum)
+        return loss, pred, wsum
+
+    @staticmethod
+    def backward(ctx, dloss, _dpred, _dwsum):
+        lib = _engine.load_library()
+        rep, cls, W, V, b, fc1_w, fc1_b, fc2_w, fc2_b, pred, wsum = ctx.saved_tensors
+        g, f = rep.shape
+        t, h = W.shape[2], fc1_w.shape[0]
+        dloss = dloss.detach().to(device=rep.device, dtype=torch.float32).reshape(1).contiguous()
+        grads = [torch.empty_like(x) for x in (rep, W, V, b, fc1_w, fc1_b, fc2_w, fc2_b)]
+        ws_bytes = int(lib.sgpr_pairs_train_workspace_bytes(g, f, t, h))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=rep.device)
+        p = _engine._ptr
+        with torch.cuda.device(rep.device):
+            _checked(lib, lib.sgpr_pairs_train_backward(p(dloss), p(wsum), p(pred), p(rep), p(W), p(V), p(b), p(fc1_w),
+                                                        p(fc1_b), p(fc2_w), p(fc2_b), p(cls), ctx.weights[0],
+                                                        ctx.weights[1], g, f, t, h, *[p(x) for x in grads], p(ws),
+                                                        ws_bytes, ctypes_stream(rep)))
+        grads = [x.view(s) for x, s in zip(grads, ctx.shapes)]
+        return (grads[0], None) + tuple(grads[1:]) + (None, None)
+
+
+def pairs_tail(rep, cls, tensor_network, fully_connected_first, scoring_layer, w_neg=1.0, w_pos=1.0):
+    """The training tail over all G x G ordered pairs of rep [G,F] (PairsTail) with the modules' own parameters
+    -> (loss, pred [G,G], wsum)."""
+    return PairsTail.apply(rep, cls, tensor_network.weight_matrix, tensor_network.weight_matrix_block,
+                           tensor_network.bias, fully_connected_first.weight, fully_connected_first.bias,
+                           scoring_layer.weight, scoring_layer.bias, w_neg, w_pos)
 
 
 # ---------------------------------------------------------------------------------------------------- model forward
@@ -207,6 +279,17 @@ def train_loss(model, feats, target, updates=2, idx_lists=None):
     return Fn.binary_cross_entropy(pred, tgt), pred, lists
 
 
+def train_loss_in_batch(model, feats, cls, w_neg=1.0, w_pos=1.0, updates=2, idx_lists=None):
+    """One train-mode forward on G graphs that trains on every labelled ordered pair among them: embed_train and
+    attention as train_loss, then pairs_tail on the pooled vectors -> (weighted mean BCE, predictions [G,G], the six
+    kNN lists).  cls [G,G] uint8 as pair_classes gives it."""
+    emb, lists = embed_train(model, feats, updates, idx_lists)
+    rep, _ = attention(model.attention, emb)
+    loss, pred, _ = pairs_tail(rep[:, :, 0], cls, model.tensor_network, model.fully_connected_first,
+                               model.scoring_layer, w_neg, w_pos)
+    return loss, pred, lists
+
+
 # ---------------------------------------------------------------------------------------------------- augmentation
 def _rot_z(angle):
     c, s = torch.cos(angle), torch.sin(angle)
@@ -226,7 +309,7 @@ def _rot_x(angle):
     return torch.stack((o, z, z, z, c, -s, z, s, c), dim=1).view(-1, 3, 3)
 
 
-def augment(centers, generator):
+def augment(centers, generator, shared_flip=False):
     """transfer_to_torch's training branch (sg_net.py:286-292) + augment_data (sg_net.py:226-233, utils.py:86-178) on
     the device, for 2b packed graphs ordered [A_0..A_b-1, B_0..B_b-1] (centers [2b, N, 3]) -> new f32 tensor.
 
@@ -234,7 +317,9 @@ def augment(centers, generator):
     per graph a rotation about z by U(0, 2 pi), a jitter N(0, 0.01) clipped to +-0.05 per coordinate, a scale U(0.8,
     1.25), a small rotation R = Rz Ry Rx with angles N(0, 0.015) clipped to +-0.045, and a shift U(-0.3, 0.3) per axis.
     Points are row vectors (p' = p R), as np.dot(shape_pc, R).  Padded slots are transformed too, as in the reference.
-    The draws come from `generator` (a torch.Generator on the centres' device), not from the global RNGs."""
+    The draws come from `generator` (a torch.Generator on the centres' device), not from the global RNGs.
+    shared_flip: the x-flip is ONE draw for the whole batch (a mirrored scan is not the place its unmirrored neighbour
+    shows, and in-batch pairs join graphs of different listed pairs); every other draw keeps its distribution and order."""
     g, n, _ = centers.shape
     b = g // 2
     dev = centers.device
@@ -246,8 +331,11 @@ def augment(centers, generator):
     def randn(*shape):
         return torch.randn(*shape, generator=generator, device=dev, dtype=torch.float64)
 
-    flip = rand(b) > 0.5
-    flip = torch.cat((flip, flip))
+    if shared_flip:
+        flip = (rand(1) > 0.5).expand(g)
+    else:
+        flip = rand(b) > 0.5
+        flip = torch.cat((flip, flip))
     x = torch.cat((torch.where(flip.view(g, 1, 1), -x[..., :1], x[..., :1]), x[..., 1:]), dim=2)
     x = torch.bmm(x, _rot_z(rand(g) * (2.0 * math.pi))).to(torch.float32).to(torch.float64)   # utils.py: f32 result
     x = x + torch.clamp(0.01 * randn(g, n, 3), -0.05, 0.05)
@@ -268,6 +356,25 @@ def target_of(distance, p_thresh):
         return 0.0
     print("distance error: ", distance)
     sys.exit(-1)
+
+
+def pair_classes(xz, graph_ids, sequence=None, p_thresh=3.0, d_neg=NEG_DISTANCE):
+    """The class of every ordered pair of a batch, by target_of's rule: xz [n,2] planar poses (float64), graph_ids [G]
+    the batch's slots (indices into xz, repeats allowed) -> uint8 [G,G]: 1 at distance <= p_thresh, 0 at >= d_neg, 2
+    (not in the loss) in between, on the diagonal and between graphs of different `sequence` ids (their poses are in
+    different frames).  PairSet._targets' arithmetic: sqrt(dx*dx + dz*dz) in float64."""
+    xz = np.asarray(xz, dtype=np.float64)
+    ids = np.asarray(graph_ids, dtype=np.int64).reshape(-1)
+    p = xz[ids]
+    d = np.sqrt(((p[:, None, :] - p[None, :, :]) ** 2).sum(2))
+    cls = np.full(d.shape, 2, dtype=np.uint8)
+    cls[d <= p_thresh] = 1
+    cls[d >= d_neg] = 0
+    if sequence is not None:
+        sq = np.asarray(sequence, dtype=np.int64).reshape(-1)[ids]
+        cls[sq[:, None] != sq[None, :]] = 2
+    np.fill_diagonal(cls, 2)
+    return cls
 
 
 def _planar(poses):
@@ -387,12 +494,21 @@ class SGFitter(object):
     SGFitter(args, init=None, seed=0, data=None): data is a PairSet (the in-memory entry point); None reads the
     reference's pair lists and graph JSONs (PairSet.from_files).  init loads a checkpoint (with or without the
     `module.` prefix) for fine-tuning; the reference always starts from scratch.  seed fixes the initial weights, the
-    batch order and the augmentation."""
+    batch order and the augmentation.  in_batch: "off" trains on the listed pairs (both orders), as the reference;
+    "all" embeds the same 2b slots of every batch and trains on EVERY labelled ordered pair among them (pair_classes)
+    with weight 1; "balanced" weighs the positives of a batch by n_neg / n_pos when both are present."""
 
     LOG_NAME = "train_log.jsonl"
 
-    def __init__(self, args, init=None, seed=0, data=None, hard_negatives=0, hard_positives=0, mine_every=2):
+    IN_BATCH = ("off", "all", "balanced")
+
+    def __init__(self, args, init=None, seed=0, data=None, hard_negatives=0, hard_positives=0, mine_every=2,
+                 in_batch="off"):
         self.args = args
+        if in_batch not in self.IN_BATCH:
+            raise ValueError("in_batch must be one of %s" % (self.IN_BATCH,))
+        self.in_batch = in_batch
+        self.last_step = None        # in-batch modes: {"pairs_in_loss", "positives", "negatives"} of the latest step
         self.hard_negatives, self.hard_positives = int(hard_negatives), int(hard_positives)
         self.mine_every = int(mine_every)
         for k in (self.hard_negatives, self.hard_positives):
@@ -429,7 +545,7 @@ class SGFitter(object):
         g = torch.from_numpy(np.concatenate((pairs[:, 0], pairs[:, 1]))).to(self.device)
         centers, labels = self.centers[g], self.labels[g]
         if training and self.augment:
-            centers = augment(centers, self.generator)
+            centers = augment(centers, self.generator, shared_flip=self.in_batch != "off")
         return dense_features(centers, labels, self.number_of_labels), centers, labels
 
     def step(self, pair_ids, pairs=None, targets=None):
@@ -440,8 +556,18 @@ class SGFitter(object):
         targets_all = self.data.train_targets if targets is None else targets
         pairs = pairs_all[pair_ids]
         feats, _, _ = self.batch(pairs, True)
-        target = torch.from_numpy(targets_all[pair_ids]).to(self.device)
         self.optimizer.zero_grad(set_to_none=True)
+        if self.in_batch != "off":
+            cls = pair_classes(self.data.xz, np.concatenate((pairs[:, 0], pairs[:, 1])), self.data.sequence,
+                               self.data.p_thresh)
+            n_pos, n_neg = int((cls == 1).sum()), int((cls == 0).sum())
+            w_pos = n_neg / n_pos if self.in_batch == "balanced" and n_pos and n_neg else 1.0
+            self.last_step = {"pairs_in_loss": n_pos + n_neg, "positives": n_pos, "negatives": n_neg}
+            loss, _, _ = train_loss_in_batch(self.model, feats, torch.from_numpy(cls).to(self.device), 1.0, w_pos)
+            loss.backward()
+            self.optimizer.step()
+            return float(loss.item())
+        target = torch.from_numpy(targets_all[pair_ids]).to(self.device)
         loss, _, _ = train_loss(self.model, feats, target)
         loss.backward()
         self.optimizer.step()
@@ -558,7 +684,10 @@ class SGFitter(object):
                 loss = self.step(ids, pairs, targets)
                 seen += len(ids)
                 loss_sum += loss * len(ids)
-                self._log({"epoch": epoch, "pairs": seen, "loss": loss, "loss_avg": loss_sum / seen})
+                rec = {"epoch": epoch, "pairs": seen, "loss": loss, "loss_avg": loss_sum / seen}
+                if self.in_batch != "off":
+                    rec.update(self.last_step)
+                self._log(rec)
             if epoch % 2 == 0:
                 eval_loss, f1 = self.score("eval")
                 rec = {"epoch": epoch, "eval_loss": eval_loss, "f1_max": f1, "checkpoint": self.save(epoch)}
@@ -583,6 +712,9 @@ def parse_cli(argv=None):
                    help="per graph and mining epoch, add its K lowest-scoring pairs within p_thresh (0..16; default 0)")
     p.add_argument("--mine-every", type=int, default=2, metavar="E",
                    help="mine at the start of every epoch e >= E with e %% E == 0 (default 2)")
+    p.add_argument("--in-batch", choices=SGFitter.IN_BATCH, default="off",
+                   help="train on every pose-labelled ordered pair among the graphs of a batch: all = weight 1, "
+                        "balanced = positives weighted by n_neg / n_pos per batch (default off: the listed pairs)")
     return p.parse_args(argv)
 
 
@@ -596,7 +728,7 @@ def main(argv=None):
         args.epochs = cli.epochs
     tab_printer(args)
     fitter = SGFitter(args, init=cli.init, seed=cli.seed, hard_negatives=cli.hard_negatives,
-                      hard_positives=cli.hard_positives, mine_every=cli.mine_every)
+                      hard_positives=cli.hard_positives, mine_every=cli.mine_every, in_batch=cli.in_batch)
     fitter.fit()
     fitter.score()
     return fitter
