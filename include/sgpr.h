@@ -387,6 +387,45 @@ int sgpr_score_topk_large(const sgpr_handle* h, const float* d_pooled_rows, int 
                           const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
                           int32_t* d_indices, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Sequence-matched loop closures: a score averaged along a diagonal of the similarity matrix.  Rows and columns are
+ * consecutive scans of a trajectory (row r - 1 is the scan before row r; the columns are ONE trajectory).  A revisited
+ * place is a run of good scores along c - r = const (driven the same way, SGPR_SEQ_FORWARD) or c + r = const (driven the
+ * opposite way, SGPR_SEQ_REVERSE).  For a sequence length L in 1..SGPR_SEQ_MAX_LEN and sigma = +1 forward, -1 reverse:
+ *     D(r, c)      = { d in 0..L-1 : r - d >= 0 and 0 <= c - sigma d < M }       (d = 0 is always in it)
+ *     Q_sigma[r,c] = (S[r, c] + S[r-1, c-sigma] + ...) * rcp[|D|],               rcp[n] = (float)(1.0 / n)
+ * plain fp32 additions in ascending d starting from the d = 0 term, one fp32 multiplication, nothing fused: reproducible
+ * bit for bit.  Both flags: Q = Q_reverse and dir = 1 where Q_reverse > Q_forward or Q_forward is NaN, else Q = Q_forward
+ * and dir = 0 (forward wins ties); one flag: dir is that direction (0 forward, 1 reverse) everywhere.  NaN and +-inf terms
+ * propagate by IEEE rules.  Terms are never masked: the window applies to the end point (r, c) alone, and
+ * window >= 2 (L - 1) keeps the self diagonal c = r out of every reverse sum of an eligible end point.  The first `ctx`
+ * rows are context only: outputs exist for rows ctx .. R-1 at output row r - ctx (ctx == R: an empty result).
+ * - sgpr_seq_filter: a resident matrix d_score [R][ld] -> d_out [R - ctx][ldo] (ld, ldo >= M) and, unless NULL, d_dir
+ *   u8 [R - ctx][ldo].  Out of place: d_out overlapping d_score is undefined.  No workspace.
+ * - sgpr_score_seq_topk: the rectangle d_pooled_rows [R] x d_pooled_cols [M] on any handle, scored in row blocks; for
+ *   every row r >= ctx the k (1..SGPR_TOPK_LARGE_MAX) best eligible columns by Q, in sgpr_topk_rows_large's order and with
+ *   its padding and NaN rules (a NaN Q never qualifies) -> d_values / d_indices [R - ctx][k] and, unless NULL, d_dirs u8
+ *   [R - ctx][k]: the direction of each listed Q, 0 in a padding slot.  Eligibility is sgpr_score_topk's on (r, c):
+ *   window, SGPR_TOPK_CAUSAL, self_r = d_row_self[r] (device, [R]: context rows have entries too) or row0 + r, r counted
+ *   over all R rows.  Every S term is sgpr_score_all_pairs' entry on the whole rectangle (the f16-range question is
+ *   answered once per call).  A score block holds at most 64 MB including L - 1 context rows, so a block yields
+ *   max(1, 64 MB / 4M - (L - 1)) output rows; its last L - 1 rows become the next block's context by a device-to-device
+ *   copy and are not scored again.  Workspace: that block, a Q block (and a dir block with both directions) of the same
+ *   rows, the selection's, the all-pairs tail's: linear in M and min(R, block rows), never R * M.
+ * Arguments are checked before the device is touched: a NULL pointer, L outside 1..SGPR_SEQ_MAX_LEN, ctx outside 0..R, no
+ * direction flag, unknown flag bits, k outside 1..SGPR_TOPK_LARGE_MAX or row0 + R past INT_MAX give SGPR_E_INVALID, a
+ * workspace below the _workspace_bytes answer SGPR_E_WORKSPACE (which is 0 for invalid arguments).  Results depend on the
+ * arguments alone.  Asynchronous on `stream`. */
+#define SGPR_SEQ_FORWARD 2
+#define SGPR_SEQ_REVERSE 4
+#define SGPR_SEQ_MAX_LEN 32
+int sgpr_seq_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx, int L, int flags,
+                    float* d_out, int64_t ldo, unsigned char* d_dir, void* stream);
+size_t sgpr_score_seq_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int flags);
+int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                        int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L, int k,
+                        float* d_values, int32_t* d_indices, unsigned char* d_dirs, void* d_workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Hard-pair mining without the R x M matrix: for every row r the k (1..16) hardest pose-labelled pairs (r, c) of the
  * rectangle d_pooled_rows [R] x d_pooled_cols [M].
  * - Column c is eligible for row r iff it is for sgpr_score_topk (window, SGPR_TOPK_CAUSAL, self_r = d_row_self[r] or

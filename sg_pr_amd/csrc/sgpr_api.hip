@@ -1187,17 +1187,19 @@ static const size_t kScoreBlockBytes = (size_t)64 << 20;   // score block of the
 
 static bool has_fused_epilogues(const sgpr_handle* h) { return !h->generic_only && !tail_wide(h); }
 
-static int score_block_rows(int R, int M) {
+// rows scored per block; ctx_rows (sgpr_score_seq_topk): rows of the block that hold the block before's last scores
+static int score_block_rows(int R, int M, int ctx_rows = 0) {
     const size_t rows = kScoreBlockBytes / ((size_t)M * sizeof(float));
-    return (int)std::max<size_t>(1, std::min<size_t>((size_t)R, rows));
+    const size_t fresh = rows > (size_t)ctx_rows ? rows - ctx_rows : 0;
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)R, fresh));
 }
 
 static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// row-block path layout: score block [rb][M] | the caller's head (head_bytes) | the block's all-pairs workspace
-static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t head_bytes) {
-    const int rb = score_block_rows(R, M);
-    return a256((size_t)rb * M * sizeof(float)) + head_bytes + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
+// row-block path layout: score block [ctx_rows + rb][M] | the caller's head (head_bytes) | the block's all-pairs workspace
+static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t head_bytes, int ctx_rows = 0) {
+    const int rb = score_block_rows(R, M, ctx_rows);
+    return a256(((size_t)ctx_rows + rb) * M * sizeof(float)) + head_bytes + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
 }
 
 // sgpr_score_all_pairs on rows [r0, r0 + n) of the rectangle, one block after the other, each followed by
@@ -1207,13 +1209,18 @@ static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t hea
 // all blocks, and no block's scoring clears it (the other handles' row blocks take the three-plane instance: no gate).
 // crng (a float4 in the caller's head, used on the production handle alone): there launch_call_range answers the
 // question once for all blocks, and every block's all-pairs launch reads that answer instead of its own rows' partials.
+// ctx_rows > 0 (sgpr_score_seq_topk): the block buffer has ctx_rows rows in front of the scored ones; after each block
+// but the last, the last ctx_rows scored rows are copied there, so consume finds the min(ctx_rows, r0) rows before r0
+// right in front of `block`.
 extern "C++" {   // (a template, inside the C-ABI block)
 template <class Consume>
 static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, size_t head_bytes,
-                            void* ws, size_t ws_bytes, void* stream, Consume&& consume, float* crng = nullptr) {
-    const int rb = score_block_rows(R, M), pw = pooled_width(h);
-    const size_t block_bytes = a256((size_t)rb * M * sizeof(float));
-    float* block = static_cast<float*>(ws);
+                            void* ws, size_t ws_bytes, void* stream, Consume&& consume, float* crng = nullptr,
+                            int ctx_rows = 0) {
+    const int rb = score_block_rows(R, M, ctx_rows), pw = pooled_width(h);
+    const size_t block_bytes = a256(((size_t)ctx_rows + rb) * M * sizeof(float));
+    float* carry = static_cast<float*>(ws);
+    float* block = carry + (size_t)ctx_rows * M;
     unsigned char* head = static_cast<unsigned char*>(ws) + block_bytes;
     unsigned char* aws = head + head_bytes;
     const size_t aws_bytes = ws_bytes - block_bytes - head_bytes;
@@ -1240,6 +1247,16 @@ static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, cons
         if (rc != SGPR_OK) return rc;
         rc = consume(block, head, r0, n);
         if (rc != SGPR_OK) return rc;
+        if (ctx_rows > 0 && r0 + n < R) {
+            // rows [n, n + ctx_rows) of the buffer move to its front: one copy, or (a block shorter than the context:
+            // the ranges overlap) ascending pieces of n rows, each disjoint from its source
+            for (int i = 0; i < ctx_rows; i += n) {
+                const int m = std::min(n, ctx_rows - i);
+                hipError_t e = hipMemcpyAsync(carry + (size_t)i * M, carry + (size_t)(i + n) * M,
+                                              (size_t)m * M * sizeof(float), hipMemcpyDeviceToDevice, s);
+                if (e != hipSuccess) return hip_fail(e, "row blocks: carrying the context rows");
+            }
+        }
     }
     return SGPR_OK;
 }
@@ -1356,6 +1373,117 @@ int sgpr_score_topk_large(const sgpr_handle* h, const float* d_pooled_rows, int 
     };
     return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, topk_large_head_bytes(R, M), d_workspace,
                             workspace_bytes, stream, select, crng);
+}
+
+// ---- sgpr_seq_filter / sgpr_score_seq_topk: the diagonal score filter (sgpr_seq.hip) on a resident matrix, and on
+//      row blocks that carry their last L - 1 rows over as the next block's context, each selected by the large-k selection
+static const int kSeqFlags = SGPR_TOPK_CAUSAL | SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE;
+
+static bool seq_args_ok(const char* fn, int R, int ctx, int L, int flags, int allowed) {
+    if (L < 1 || L > SGPR_SEQ_MAX_LEN) {
+        set_error(std::string(fn) + ": the sequence length must lie in 1.." + std::to_string(SGPR_SEQ_MAX_LEN));
+        return false;
+    }
+    if (ctx < 0 || ctx > R) {
+        set_error(std::string(fn) + ": ctx must lie in 0..R");
+        return false;
+    }
+    if (flags & ~allowed) {
+        set_error(std::string(fn) + ": unknown flag bits " + std::to_string(flags & ~allowed));
+        return false;
+    }
+    if (!(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE))) {
+        set_error(std::string(fn) + ": no direction flag (SGPR_SEQ_FORWARD, SGPR_SEQ_REVERSE)");
+        return false;
+    }
+    return true;
+}
+
+int sgpr_seq_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx, int L, int flags,
+                    float* d_out, int64_t ldo, unsigned char* d_dir, void* stream) {
+    if (!h || R < 0 || M < 0 || ld < M || ldo < M) {
+        set_error("sgpr_seq_filter: NULL handle, negative size or leading dimension below M");
+        return SGPR_E_INVALID;
+    }
+    if (!seq_args_ok("sgpr_seq_filter", R, ctx, L, flags, SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)) return SGPR_E_INVALID;
+    if (R > ctx && M > 0 && (!d_score || !d_out)) {       // (an empty result needs no buffers)
+        set_error("sgpr_seq_filter: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (R == ctx || M == 0) return SGPR_OK;
+    DeviceGuard guard(h->device);
+    return launch_seq_filter(d_score, R, M, ld, ctx, L, flags, d_out, ldo, d_dir, ldo, static_cast<hipStream_t>(stream));
+}
+
+static bool seq_both(int flags) { return (flags & SGPR_SEQ_FORWARD) && (flags & SGPR_SEQ_REVERSE); }
+
+// head of sgpr_score_seq_topk: the call's f16 range (a float4) | the selection's workspace for one block | Q block
+// [rb][M] | dir block [rb][M] (both directions)
+static size_t seq_head_bytes(int R, int M, int L, int flags) {
+    const size_t rb = (size_t)score_block_rows(R, M, L - 1);
+    return 256 + a256(select_ws_bytes((int)rb, M)) + a256(rb * M * sizeof(float)) + (seq_both(flags) ? a256(rb * M) : 0);
+}
+
+size_t sgpr_score_seq_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int flags) {
+    if (!h || R < 0 || M < 0 || k < 1 || k > SGPR_TOPK_LARGE_MAX || L < 1 || L > SGPR_SEQ_MAX_LEN || ctx < 0 || ctx > R ||
+        (flags & ~kSeqFlags) || !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
+        return 0;
+    if (R == ctx || M == 0) return 0;
+    return row_blocks_ws_bytes(h, R, M, seq_head_bytes(R, M, L, flags), L - 1);
+}
+
+int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                        int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L, int k,
+                        float* d_values, int32_t* d_indices, unsigned char* d_dirs, void* d_workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (!h || R < 0 || M < 0) {
+        set_error("sgpr_score_seq_topk: NULL handle or negative count");
+        return SGPR_E_INVALID;
+    }
+    if (!seq_args_ok("sgpr_score_seq_topk", R, ctx, L, flags, kSeqFlags)) return SGPR_E_INVALID;
+    if ((R > ctx && (!d_values || !d_indices)) || (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols))) {
+        set_error("sgpr_score_seq_topk: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (!topk_large_args_ok("sgpr_score_seq_topk", R, k, flags & SGPR_TOPK_CAUSAL, row0)) return SGPR_E_INVALID;
+    if (!workspace_ok("sgpr_score_seq_topk", sgpr_score_seq_topk_workspace_bytes(h, R, M, ctx, L, k, flags), d_workspace,
+                      workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    if (R == ctx) return SGPR_OK;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_dir = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0) {
+        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, window,
+                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
+        if (rc != SGPR_OK || !d_dirs) return rc;
+        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_dir, d_dirs, s);
+    }
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), q_bytes = a256((size_t)rb * M * sizeof(float));
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    int clean_rows = 0;                                   // histogram rows the selection before left clear
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0), no = r0 + n - first;
+        float* q = reinterpret_cast<float*>(head + 256 + sel_bytes);
+        unsigned char* dir = seq_both(flags) ? head + 256 + sel_bytes + q_bytes : nullptr;
+        // the rectangle the filter sees starts c rows before r0: global row 0, or L - 1 rows back (no sum reaches further)
+        int rc = launch_seq_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, q, M, dir, M, s);
+        if (rc != SGPR_OK) return rc;
+        const size_t o = (size_t)(first - ctx) * k;
+        rc = launch_select_rows(q, no, M, M, d_row_self ? d_row_self + first : nullptr, row0 + first, window, causal, k,
+                                d_values + o, d_indices + o, head + 256, select_group_rows(no) <= clean_rows, h->d_status, s);
+        // (the first block's outputs start at ctx: the block after it may select more rows, whose histograms reach into
+        //  what this one used for its state and counts)
+        clean_rows = select_group_rows(no);
+        if (rc != SGPR_OK || !d_dirs) return rc;
+        return launch_seq_dirs(d_indices + o, no, k, dir, M, fixed_dir, d_dirs + o, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_head_bytes(R, M, L, flags), d_workspace,
+                            workspace_bytes, stream, select, crng, L - 1);
 }
 
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks

@@ -305,9 +305,19 @@ int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int
 // the large-k selection of a resident n x M block into [n][k] (sgpr_select.hip); ws_clean: ws is what an earlier call on
 // the same stream left (its histograms are clear)
 size_t select_ws_bytes(int n, int M);
+// ws_clean holds only for a block whose select_group_rows is at most that of the call before it on the same ws: a call
+// leaves its own histogram rows clear and its state / counts right behind them
+int select_group_rows(int n);
 int launch_select_rows(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
                        int causal, int k, float* val, int32_t* idx, void* ws, bool ws_clean, int32_t* status,
                        hipStream_t stream);
+// the diagonal score filter of a resident R x M matrix (sgpr_seq.hip): Q for rows ctx .. R-1 into out [R - ctx][ldo],
+// the direction taken into dir [R - ctx][ldd] (or nullptr); flags: SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE, at least one
+int launch_seq_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, float* out, int64_t ldo,
+                      unsigned char* dir, int64_t ldd, hipStream_t stream);
+// out [n][k] = dir [n][ld] at the selected columns idx [n][k] (dir == nullptr: `fixed`); 0 where idx is -1
+int launch_seq_dirs(const int32_t* idx, int n, int k, const unsigned char* dir, int64_t ld, int fixed,
+                    unsigned char* out, hipStream_t stream);
 // sgpr_score_mine on the production handle (positives: SGPR_MINE_POSITIVES, else the negatives) and its selection on a
 // resident block (sgpr_mine_rows, the chunked path of the other handles; sgpr_metrics.hip)
 size_t score_mine_ws_bytes(const sgpr_handle* h, int R, int M, int k);

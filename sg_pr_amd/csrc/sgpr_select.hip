@@ -358,6 +358,10 @@ size_t select_ws_bytes(int n, int M) {
     return a256s(g * SEL_BINS * 4) + a256s(g * 16) + a256s(g * nch * 8);
 }
 
+// rows per round of launches for a block of n rows: what the workspace's layout depends on (the histograms of
+// select_group_rows(n) rows come first, state and chunk counts behind them)
+int select_group_rows(int n) { return std::min(n, SEL_GROUP); }
+
 int launch_select_rows(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
                        int causal, int k, float* val, int32_t* idx, void* ws, bool ws_clean, int32_t* status,
                        hipStream_t s) {

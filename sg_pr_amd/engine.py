@@ -45,6 +45,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_score_topk_workspace_bytes", "sgpr_score_topk",
                "sgpr_topk_rows_large_workspace_bytes", "sgpr_topk_rows_large",
                "sgpr_score_topk_large_workspace_bytes", "sgpr_score_topk_large",
+               "sgpr_seq_filter", "sgpr_score_seq_topk_workspace_bytes", "sgpr_score_seq_topk",
                "sgpr_score_mine_workspace_bytes", "sgpr_score_mine", "sgpr_mine_rows_workspace_bytes", "sgpr_mine_rows",
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
                "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
@@ -185,6 +186,12 @@ def load_library():
     lib.sgpr_score_topk_large_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
     lib.sgpr_score_topk_large.restype = i32
     lib.sgpr_score_topk_large.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.sgpr_seq_filter.restype = i32
+    lib.sgpr_seq_filter.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, i64, vp, vp]
+    lib.sgpr_score_seq_topk_workspace_bytes.restype = sz
+    lib.sgpr_score_seq_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]
+    lib.sgpr_score_seq_topk.restype = i32
+    lib.sgpr_score_seq_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.sgpr_score_mine_workspace_bytes.restype = sz
     lib.sgpr_score_mine_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
     lib.sgpr_score_mine.restype = i32
@@ -967,6 +974,82 @@ class Engine:
                                             flags, int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         return vals, idx
+
+    SEQ_FORWARD = 2     # SGPR_SEQ_FORWARD of include/sgpr.h
+    SEQ_REVERSE = 4     # SGPR_SEQ_REVERSE
+    SEQ_MAX_LEN = 32    # SGPR_SEQ_MAX_LEN
+
+    def _seq_flags(self, reverse):
+        """reverse: False (forward diagonals c - r = const), True (reverse, c + r = const) or "both" (the larger)"""
+        if isinstance(reverse, str):
+            if reverse != "both":
+                raise ValueError('reverse must be False, True or "both", got %r' % (reverse,))
+            return self.SEQ_FORWARD | self.SEQ_REVERSE
+        return self.SEQ_REVERSE if reverse else self.SEQ_FORWARD
+
+    def seq_filter(self, score, seq_len, context=0, reverse=False, want_dir=False, out=None, out_dir=None):
+        """sgpr_seq_filter: the mean of a resident matrix along the diagonal of up to seq_len entries that ends in
+        (r, c) - rows and columns in trajectory order - for rows context .. R-1 -> Q f32 [R - context, M] (and, want_dir,
+        the direction taken, u8: 0 forward, 1 reverse).  fp32 sums in a fixed order: bit-reproducible (include/sgpr.h).
+        A row-strided view (unit column stride) is read in place.  out / out_dir: device tensors [R - context, M] to
+        write into, with one common row stride >= M and unit column stride (they must not overlap score)."""
+        if not isinstance(score, torch.Tensor):
+            score = torch.as_tensor(score)
+        if score.dim() != 2:
+            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
+        if score.device != self.device or score.dtype != torch.float32:
+            score = score.to(device=self.device, dtype=torch.float32)
+        r, m = score.shape
+        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
+            score = score.contiguous()
+        ro = max(r - int(context), 0)
+        if out is None:
+            out = torch.empty(ro, m, dtype=torch.float32, device=self.device)
+        if out_dir is None and want_dir:
+            out_dir = torch.empty(ro, m, dtype=torch.uint8, device=self.device)
+        ldo = m
+        for t, dt, name in ((out, torch.float32, "out"), (out_dir, torch.uint8, "out_dir")):
+            if t is None:
+                continue
+            if t.device != self.device or t.dtype != dt or tuple(t.shape) != (ro, m) or (m > 1 and t.stride(1) != 1):
+                raise ValueError("%s must be a %s device tensor [%d, %d] with unit column stride" % (name, dt, ro, m))
+            if ro > 1:
+                ldo = max(ldo, t.stride(0))
+        if ro > 1 and out_dir is not None and max(out.stride(0), m) != max(out_dir.stride(0), m):
+            raise ValueError("out and out_dir must share one row stride")
+        rc = self.lib.sgpr_seq_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m, int(context),
+                                      int(seq_len), self._seq_flags(reverse), _ptr(out), ldo, _ptr(out_dir),
+                                      self._stream())
+        self._check(rc)
+        return (out, out_dir) if (want_dir or out_dir is not None) else out
+
+    def score_seq_topk_workspace_bytes(self, r, m, seq_len, k=1, causal=False, context=0, reverse="both"):
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        return int(self.lib.sgpr_score_seq_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
+                                                                int(k), flags))
+
+    def score_seq_topk(self, pooled_rows, pooled_cols, seq_len, k=1, window=-1, row0=0, causal=False, row_self=None,
+                       context=0, reverse="both"):
+        """sgpr_score_seq_topk: score_topk_large's lists of the sequence-matched score (seq_filter of the rectangle,
+        never formed beyond 64 MB row blocks) for rows context .. R-1 -> (values f32 [R - context, k], indices i32,
+        dirs u8: 0 forward, 1 reverse, 0 in a padding slot).  Eligibility is score_topk's on the end point, with
+        row_self [R] / row0 + r counted over all R rows."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        ro = max(r - int(context), 0)
+        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
+        dirs = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        ws_bytes = self.lib.sgpr_score_seq_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len), int(k), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_score_seq_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
+                                          int(window), flags, int(seq_len), int(k), _ptr(vals), _ptr(idx), _ptr(dirs),
+                                          _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        return vals, idx, dirs
 
     def score_topk_workspace_bytes(self, r, m, k=1, causal=False):
         return int(self.lib.sgpr_score_topk_workspace_bytes(self._h, int(r), int(m), int(k),

@@ -78,17 +78,26 @@ def pack_directory(graph_dir, node_num, number_of_labels=12, names=None):
     return PackedSequence(centers, labels, poses, names)
 
 
-def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=50, scorer=None, keep_matrix=True):
+def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=50, scorer=None, keep_matrix=True,
+                       seq_len=1, seq_reverse="both"):
     """Whole-sequence evaluation on the device.  Returns {"f1_max", "roc_auc", "closure_scores" [M,k], "closure_frames"
     [M,k], "matrix" (device tensor: this rank's row block)}.  `scorer`: an AllPairsScorer for multi-GPU runs.
     keep_matrix=False never forms the matrix: F1-max and the area come from AllPairsScorer.pr_roc_pooled, the
-    closures from Engine.score_topk (the same values), and "matrix" is None."""
+    closures from Engine.score_topk (the same values), and "matrix" is None.
+    seq_len > 1 (frames in trajectory order, one GPU, keep_matrix=True): the kept matrix is also sequence-matched
+    (Engine.seq_filter, seq_reverse False / True / "both") and the result adds "seq_f1_max", "seq_roc_auc",
+    "seq_closure_scores", "seq_closure_frames" and "seq_matrix" of the filtered scores beside the unfiltered ones."""
     from . import allpairs
+    seq_len = int(seq_len)
+    if seq_len != 1 and not keep_matrix:
+        raise ValueError("evaluate_all_pairs: seq_len > 1 filters the kept matrix; keep_matrix=False is not supported")
     if scorer is None:
         scorer = allpairs.AllPairsScorer(model=model)
     eng = model.engine()
     k = int(model.args.K)
     world, rank = scorer._world()
+    if seq_len != 1 and world > 1:
+        raise ValueError("evaluate_all_pairs: seq_len > 1 runs on one GPU (a row shard lacks its context rows)")
     lo, hi = allpairs.shard_bounds(len(seq), world, rank)
     order, cap = eng.size_order(seq.centers[lo:hi], seq.labels[lo:hi], k)
     scorer.embed_fn = lambda c, l: eng.embed(c, l, k, node_cap=cap, order=order)[0]     # noqa: E731
@@ -104,7 +113,13 @@ def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=
     allpairs.agree_on_error(err, like=block, group=scorer.group)
     f1, auc = scorer.pr_roc(block, seq.poses, p_thresh=p_thresh, n_thresh=n_thresh)
     vals, idx = scorer.loop_closures(block, k=top_k, window=window)
-    return {"f1_max": f1, "roc_auc": auc, "closure_scores": vals, "closure_frames": idx, "matrix": block}
+    res = {"f1_max": f1, "roc_auc": auc, "closure_scores": vals, "closure_frames": idx, "matrix": block}
+    if seq_len != 1:
+        q = eng.seq_filter(block, seq_len, reverse=seq_reverse)
+        res["seq_f1_max"], res["seq_roc_auc"] = scorer.pr_roc(q, seq.poses, p_thresh=p_thresh, n_thresh=n_thresh)
+        res["seq_closure_scores"], res["seq_closure_frames"] = scorer.loop_closures(q, k=top_k, window=window)
+        res["seq_matrix"] = q
+    return res
 
 
 def _evaluate_pooled(model, seq, pooled, p_thresh, n_thresh, top_k, window, scorer):
@@ -127,13 +142,28 @@ def main(argv=None):
     """python -m sg_pr_amd.graph_store config.yml   - all-pairs evaluation of every `eva_batch.sequences` entry:
     packs `<graph_pairs_dir>/<seq>/` once (cached as `<output_path>/<seq>_packed.npz`), writes
     `<seq>_allpairs_F1_max.txt` and `<seq>_loop_closures.npy` (frame, best match, score).
-    --no-matrix: the same outputs without ever forming the M x M score matrix (evaluate_all_pairs keep_matrix=False)."""
+    --no-matrix: the same outputs without ever forming the M x M score matrix (evaluate_all_pairs keep_matrix=False).
+    --seq-len L [--seq-reverse off|on|both]: also the F1-max and ROC area of the sequence-matched matrix
+    (`<seq>_seq_F1_max.txt`, evaluate_all_pairs seq_len=) and its closures (`<seq>_seq_loop_closures.npy`)."""
     import sys
     from .parser_sg import sgpr_args
     from .sg_net import SGTrainer
     argv = sys.argv[1:] if argv is None else argv
     keep_matrix = "--no-matrix" not in argv
     argv = [a for a in argv if a != "--no-matrix"]
+    seq_len, seq_reverse = 1, "both"
+    for flag in ("--seq-len", "--seq-reverse"):
+        if flag in argv:
+            i = argv.index(flag)
+            if i + 1 >= len(argv):
+                raise SystemExit(flag + " needs a value")
+            if flag == "--seq-len":
+                seq_len = int(argv[i + 1])
+            else:
+                if argv[i + 1] not in ("off", "on", "both"):
+                    raise SystemExit("--seq-reverse must be off, on or both")
+                seq_reverse = {"off": False, "on": True, "both": "both"}[argv[i + 1]]
+            argv = argv[:i] + argv[i + 2:]
     args = sgpr_args()
     args.load(argv[0] if argv else "./config/config.yml")
     trainer = SGTrainer(args, False)
@@ -148,7 +178,8 @@ def main(argv=None):
             seq = pack_directory(os.path.join(args.graph_pairs_dir, sequence), int(args.node_num),
                                  trainer.number_of_labels)
             seq.save(cache)
-        r = evaluate_all_pairs(trainer.model, seq, p_thresh=float(args.p_thresh), keep_matrix=keep_matrix)
+        r = evaluate_all_pairs(trainer.model, seq, p_thresh=float(args.p_thresh), keep_matrix=keep_matrix,
+                               seq_len=seq_len, seq_reverse=seq_reverse)
         with open(os.path.join(args.output_path, sequence + "_allpairs_F1_max.txt"), "w") as f:
             f.write(str(r["f1_max"]))
         m = len(seq)
@@ -156,6 +187,14 @@ def main(argv=None):
                 np.stack((np.arange(m), r["closure_frames"][:, 0].cpu().numpy(),
                           r["closure_scores"][:, 0].cpu().numpy()), axis=1))
         print("sequence", sequence, "frames", m, "roc_auc: ", r["roc_auc"], "F1 max score", r["f1_max"])
+        if seq_len != 1:
+            with open(os.path.join(args.output_path, sequence + "_seq_F1_max.txt"), "w") as f:
+                f.write(str(r["seq_f1_max"]))
+            np.save(os.path.join(args.output_path, sequence + "_seq_loop_closures.npy"),
+                    np.stack((np.arange(m), r["seq_closure_frames"][:, 0].cpu().numpy(),
+                              r["seq_closure_scores"][:, 0].cpu().numpy()), axis=1))
+            print("sequence", sequence, "sequence length", seq_len, "roc_auc: ", r["seq_roc_auc"], "F1 max score",
+                  r["seq_f1_max"])
         results[sequence] = r["f1_max"]
     return results
 

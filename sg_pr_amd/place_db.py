@@ -6,6 +6,8 @@ with sgpr_score_topk - the k best matches per query, no similarity matrix at any
     vals, idx = db.query(centers, labels, k=1, window=50, causal=True)   # new graphs: frames len(db), len(db) + 1, ...
     vals, idx = db.query_ids(ids, k=4, window=50)      # members: row_self = their ids
     rows, cols, vals, row_ptr = db.query_ids_above(ids, 0.9, window=50)   # every member scoring >= 0.9
+    vals, idx, dirs = db.query_seq(centers, labels, seq_len=8, k=4, window=50, causal=True)   # sequence-matched
+    vals, idx, dirs = db.query_ids_seq(first, count, seq_len=8, k=4, window=50)               # a run of members
     db.save("map.npz"); db = PlaceDatabase.load("map.npz", model)
 
 A vector costs 128 bytes of device memory (the matrix of a 100 k-graph map would be 40 GB).  The file keeps the vectors,
@@ -13,7 +15,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
 `load` refuses them.
 
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
-                                            [--recall-percent P]
+                                            [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -21,7 +23,10 @@ max(K, N) candidates, N = max(1, round(M * P / 100)), and the file adds recall_p
 >= T (rows, cols, scores) and its precision / recall (metrics.precision_recall_at); with --hard K also `<seq>_hard.npz`
 with every frame's K hardest negatives (highest scores at >= 20 m) and K hardest positives (lowest scores within
 p_thresh), indices and scores (Engine.score_mine; the window applies to both), and the number of frames that have a
-negative scoring above their best positive.
+negative scoring above their best positive.  With --seq-len L (2..32) the lists of `<seq>_topk.npz` rank the
+sequence-matched score (the mean along the diagonal of the last L frames of both trajectories, engine.Engine.seq_filter;
+--seq-reverse: forward diagonals only (off), reverse only (on) or the larger of both, the default) and the file adds
+seq_len and dirs [M,K] (0 forward, 1 reverse).
 """
 import argparse
 import hashlib
@@ -96,6 +101,27 @@ class PlaceDatabase:
         return self.eng.score_topk(rows, self.pooled, k=k, window=window, causal=causal,
                                    row_self=ids.to(torch.int32))
 
+    def query_seq(self, centers, labels, seq_len, k=1, window=-1, causal=False, reverse="both", pooled=None):
+        """Sequence-matched query for graphs that are NOT in the database, taken as the next frames len(db),
+        len(db) + 1, ... of the trajectory the members form (or, pooled=, their already embedded vectors): the k best
+        members by the score averaged along the last seq_len frames (engine.Engine.score_seq_topk), the database's last
+        seq_len - 1 members serving as context rows -> (scores f32 [g,k], ids i32 [g,k], dirs u8 [g,k])."""
+        new = self._embed(centers, labels) if pooled is None else self.eng._pooled(pooled, "pooled")
+        ctx = min(int(seq_len) - 1, self.n)
+        rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
+        return self.eng.score_seq_topk(rows, self.pooled, int(seq_len), k=k, window=window, row0=self.n - ctx,
+                                       causal=causal, context=ctx, reverse=reverse)
+
+    def query_ids_seq(self, first, count, seq_len, k=1, window=-1, causal=False, reverse="both"):
+        """Sequence-matched lists for the run of members first .. first + count - 1 (their ids are their frames), the
+        up to seq_len - 1 members before `first` serving as context rows -> (scores, ids, dirs) [count, k]."""
+        first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > self.n:
+            raise IndexError("query_ids_seq: first .. first + count must lie in [0, %d]" % self.n)
+        ctx = min(int(seq_len) - 1, first)
+        return self.eng.score_seq_topk(self._buf[first - ctx:first + count], self.pooled, int(seq_len), k=k,
+                                       window=window, row0=first - ctx, causal=causal, context=ctx, reverse=reverse)
+
     def query_ids_hard(self, ids, poses, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1, causal=False):
         """The k hardest negatives (positives=True: positives) of stored members ids among all members
         (Engine.score_mine with row_self = ids); poses [len, 12] or [len, 2] of every member."""
@@ -152,7 +178,13 @@ def main(argv=None):
                     help="also write <seq>_hard.npz: every frame's K hardest negatives and positives (1..16)")
     ap.add_argument("--recall-percent", type=float, default=None, metavar="P",
                     help="also report recall@P%% (N = max(1, round(frames * P / 100)) candidates, k = max(--k, N))")
+    ap.add_argument("--seq-len", type=int, default=1, metavar="L",
+                    help="rank the sequence-matched score: the mean along the last L frames of both trajectories (1..32)")
+    ap.add_argument("--seq-reverse", choices=("off", "on", "both"), default="both",
+                    help="with --seq-len: forward diagonals only (off), reverse only (on) or the larger of both")
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if not 1 <= opt.seq_len <= _engine.Engine.SEQ_MAX_LEN:
+        ap.error("--seq-len must lie in 1..%d" % _engine.Engine.SEQ_MAX_LEN)
     args = sgpr_args()
     args.load(opt.config)
     trainer = SGTrainer(args, False)
@@ -174,16 +206,21 @@ def main(argv=None):
         extra = {}
         if opt.recall_percent is not None:
             k = max(k, metrics.recall_percent_n(m, opt.recall_percent))
-        vals, idx = db.query_ids(torch.arange(m), k=k, window=opt.window, causal=opt.causal)
+        if opt.seq_len > 1:
+            vals, idx, dirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
+                                               reverse={"off": False, "on": True, "both": "both"}[opt.seq_reverse])
+            extra = {"seq_len": np.int64(opt.seq_len), "dirs": dirs.cpu().numpy()}
+        else:
+            vals, idx = db.query_ids(torch.arange(m), k=k, window=opt.window, causal=opt.causal)
         recall = metrics.recall_at_n(idx, seq.poses, p_thresh=float(args.p_thresh), window=opt.window, causal=opt.causal)
         if opt.recall_percent is not None:
             rp, n = metrics.recall_at_percent(idx, seq.poses, percent=opt.recall_percent, p_thresh=float(args.p_thresh),
                                               window=opt.window, causal=opt.causal)
-            extra = {"recall_percent": np.float64(rp), "recall_percent_n": np.int64(n)}
+            extra.update({"recall_percent": np.float64(rp), "recall_percent_n": np.int64(n)})
         np.savez(os.path.join(args.output_path, sequence + "_topk.npz"), frame=np.arange(m),
                  indices=idx.cpu().numpy(), scores=vals.cpu().numpy(), recall=recall, **extra)
         print("sequence", sequence, "frames", m, "recall@1..%d" % k, " ".join("%.4f" % r for r in recall))
-        if extra:
+        if opt.recall_percent is not None:
             print("sequence", sequence, "recall@%g%% (N = %d) %.4f" % (opt.recall_percent, extra["recall_percent_n"],
                                                                        extra["recall_percent"]))
         results[sequence] = recall

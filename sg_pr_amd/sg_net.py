@@ -146,9 +146,15 @@ class SG(torch.nn.Module):
     def score_all_pairs(self, pooled_rows, pooled_cols, out=None):
         return self.engine().score_all_pairs(pooled_rows, pooled_cols, out=out)
 
-    def loop_closures(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None):
+    def loop_closures(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None, seq_len=1,
+                      seq_reverse="both"):
         """The k best columns per row of pooled_rows x pooled_cols without forming the matrix (engine.Engine.score_topk)
-        -> (values f32 [R,k], indices i32 [R,k]) on the device."""
+        -> (values f32 [R,k], indices i32 [R,k]) on the device.  seq_len > 1: rows and columns are consecutive scans and
+        the lists rank the sequence-matched score (engine.Engine.score_seq_topk; seq_reverse False / True / "both")
+        -> (values, indices, dirs u8 [R,k])."""
+        if int(seq_len) != 1:
+            return self.engine().score_seq_topk(pooled_rows, pooled_cols, int(seq_len), k=k, window=window, row0=row0,
+                                                causal=causal, row_self=row_self, reverse=seq_reverse)
         return self.engine().score_topk(pooled_rows, pooled_cols, k=k, window=window, row0=row0, causal=causal,
                                         row_self=row_self)
 
