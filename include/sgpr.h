@@ -541,6 +541,57 @@ int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows
                                 const unsigned long long* d_at_least, unsigned long long* d_out,
                                 void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Range retrieval and pooled evaluation on the sequence-matched score Q of sgpr_seq_filter (same D, Q, dir, ctx, L and
+ * direction flags; every call reports the bits sgpr_seq_filter would write for the same S).
+ * - sgpr_seq_rows_above (a resident matrix d_score [R][ld]) and sgpr_score_seq_above (the rectangle d_pooled_rows [R] x
+ *   d_pooled_cols [M], every handle): every pair (r, c) with ctx <= r < R that is eligible and has Q[r, c] >= threshold.
+ *   Eligibility is sgpr_score_topk's on the end point alone - self_r = d_row_self[r] (device, [R]: context rows have
+ *   entries too) or row0 + r, r counted over all R rows; window and SGPR_TOPK_CAUSAL as there; terms are never masked.
+ *   A NaN Q never qualifies, threshold = -inf takes every non-NaN eligible pair, a NaN threshold is SGPR_E_INVALID.
+ *   Order, capacity and counts are sgpr_score_above's: row-major (r, then c ascending), two calls return identical bytes;
+ *   d_rows holds the output row r - ctx, d_values the bits of Q, d_dirs (u8, may be NULL) the direction of each listed Q
+ *   (the fixed direction with one flag); d_row_ptr (int64 [R - ctx + 1], may be NULL) and *d_count are exact also when
+ *   `capacity` cuts the output; capacity = 0 with NULL arrays counts only.  A d_row_self entry outside [0, M) is reported
+ *   by sgpr_check_status.  ctx == R, R == 0 and M == 0 are valid empty calls (count 0, all-zero row pointer).
+ *   Two passes of the filter's tile kernel with a range-select epilogue (count per 64-column segment, scan, write): no
+ *   Q or dir block exists.  sgpr_score_seq_above runs them on sgpr_score_seq_topk's row blocks (at most 64 MB including
+ *   the L - 1 context rows, the f16-range question answered once per call), positions continuing on the device; its
+ *   workspace is that block, 4 bytes per 64 columns and row of a block, O(R) counters and the all-pairs tail's.
+ * - sgpr_score_seq_positives / sgpr_score_seq_threshold_counts: what sgpr_pair_positives / sgpr_pair_threshold_counts
+ *   return on the matrix Q[ctx..R-1][M] - the same multiset of positives bit for bit, equal d_count[0..1] and
+ *   d_out[0..T+2] - from the pooled vectors, on every handle.  With poses the row pose of output row o is
+ *   d_pose_xz[row0 + ctx + o]; explicit labels d_gt are [R - ctx][ldg], indexed by output row.  flags hold direction
+ *   flags only.  T <= SGPR_SCORE_COUNT_MAX_THRESHOLDS.  Each row block is filtered into a Q block of its own rows and
+ *   counted by the matrix kernels; the blocks' results are added up on the device.
+ * Arguments are checked before the device is touched (sgpr_score_seq_topk's, sgpr_score_above's and
+ * sgpr_score_positives' rules and return codes); the _workspace_bytes queries answer 0 for invalid arguments, a workspace
+ * below them is SGPR_E_WORKSPACE.  Results depend on the arguments alone.  Asynchronous on `stream`. */
+size_t sgpr_seq_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx);
+int sgpr_seq_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx,
+                        const int32_t* d_row_self, int row0, int window, int flags, int L, float threshold,
+                        int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_dirs, int64_t capacity,
+                        int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
+                        void* stream);
+size_t sgpr_score_seq_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags);
+int sgpr_score_seq_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L, float threshold,
+                         int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_dirs, int64_t capacity,
+                         int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
+                         void* stream);
+size_t sgpr_score_seq_positives_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags);
+int sgpr_score_seq_positives(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                             int ctx, int L, int flags, int row0, const double* d_pose_xz, double d_pos, double d_neg,
+                             const signed char* d_gt, int64_t ldg, float* d_out, int64_t capacity,
+                             unsigned long long* d_count, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t sgpr_score_seq_threshold_counts_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags,
+                                                       int T);
+int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
+                                    int M, int ctx, int L, int flags, int row0, const double* d_pose_xz, double d_pos,
+                                    double d_neg, const signed char* d_gt, int64_t ldg, const float* d_thresholds, int T,
+                                    const sgpr_rank_group* d_rank, int groups_per_threshold,
+                                    const unsigned long long* d_at_least, unsigned long long* d_out, void* d_workspace,
+                                    size_t workspace_bytes, void* stream);
+
 /* LDS bytes per workgroup the embed kernel uses for (N, k) on this handle; 0 if unsupported. */
 size_t sgpr_embed_lds_bytes(const sgpr_handle* h, int N, int k);
 

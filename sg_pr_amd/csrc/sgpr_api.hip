@@ -1665,6 +1665,101 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
                              d_rows, d_cols, d_values, capacity, rp, 0, d_count, 0, cnt, h->d_status, s);
 }
 
+// ---- sgpr_seq_rows_above / sgpr_score_seq_above: the range selection on the sequence-matched score (seq_above_kernel,
+//      sgpr_seq.hip) on a resident matrix, and on sgpr_score_seq_topk's row blocks with context - no Q or dir block
+static bool seq_above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int ctx, int row0, int flags, int L,
+                              float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity,
+                              unsigned long long* d_count) {
+    if (!above_args_ok(fn, h, R, M, row0, flags & SGPR_TOPK_CAUSAL, threshold, d_rows, d_cols, d_values, capacity, d_count))
+        return false;
+    return seq_args_ok(fn, R, ctx, L, flags, kSeqFlags);
+}
+
+static bool seq_query_ok(const sgpr_handle* h, int R, int M, int ctx, int L, int flags) {
+    return h && R >= 0 && M >= 0 && L >= 1 && L <= SGPR_SEQ_MAX_LEN && ctx >= 0 && ctx <= R && !(flags & ~kSeqFlags) &&
+           (flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE));
+}
+
+// workspace of sgpr_seq_rows_above: seg, cnt (seq_above_ws_bytes) | row_ptr [R - ctx + 1] i64 (the caller passes none)
+size_t sgpr_seq_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx) {
+    if (!h || R < 0 || M < 0 || ctx < 0 || ctx > R || R == ctx || M == 0) return 0;
+    return seq_above_ws_bytes(R - ctx, M) + a256((size_t)(R - ctx + 1) * 8);
+}
+
+int sgpr_seq_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx,
+                        const int32_t* d_row_self, int row0, int window, int flags, int L, float threshold,
+                        int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_dirs, int64_t capacity,
+                        int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (!seq_above_args_ok("sgpr_seq_rows_above", h, R, M, ctx, row0, flags, L, threshold, d_rows, d_cols, d_values,
+                           capacity, d_count))
+        return SGPR_E_INVALID;
+    if (ld < M || (R > ctx && M > 0 && !d_score)) {
+        set_error("sgpr_seq_rows_above: NULL score or ld < M");
+        return SGPR_E_INVALID;
+    }
+    if (!workspace_ok("sgpr_seq_rows_above", sgpr_seq_rows_above_workspace_bytes(h, R, M, ctx), d_workspace,
+                      workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
+    unsigned char* ws = static_cast<unsigned char*>(d_workspace);
+    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(ws + seq_above_ws_bytes(R - ctx, M));
+    return launch_seq_above(d_score, R, M, ld, ctx, L, flags, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0,
+                            threshold, d_rows, d_cols, d_values, d_dirs, capacity, rp, 0, d_count, 0, ws, h->d_status, s);
+}
+
+// head of sgpr_score_seq_above: the call's f16 range (a float4) | seg, cnt for one block | row_ptr [R - ctx + 1] i64
+// (used when the caller passes none)
+static size_t seq_above_head_bytes(int R, int M, int ctx, int L) {
+    return 256 + seq_above_ws_bytes(score_block_rows(R, M, L - 1), M) + a256((size_t)(R - ctx + 1) * 8);
+}
+
+size_t sgpr_score_seq_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags) {
+    if (!seq_query_ok(h, R, M, ctx, L, flags)) return 0;
+    if (R == ctx || M == 0) return 0;
+    return row_blocks_ws_bytes(h, R, M, seq_above_head_bytes(R, M, ctx, L), L - 1);
+}
+
+int sgpr_score_seq_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L, float threshold,
+                         int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_dirs, int64_t capacity,
+                         int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
+                         void* stream) {
+    if (!seq_above_args_ok("sgpr_score_seq_above", h, R, M, ctx, row0, flags, L, threshold, d_rows, d_cols, d_values,
+                           capacity, d_count))
+        return SGPR_E_INVALID;
+    if (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols)) {
+        set_error("sgpr_score_seq_above: NULL pooled vectors");
+        return SGPR_E_INVALID;
+    }
+    if (!workspace_ok("sgpr_score_seq_above", sgpr_score_seq_above_workspace_bytes(h, R, M, ctx, L, flags), d_workspace,
+                      workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = seq_above_ws_bytes(rb, M);
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0);
+        int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(head + 256 + sel_bytes);
+        // the rectangle starts c rows before r0 (sgpr_score_seq_topk's): its row 0 is row r0 - c of the call
+        return launch_seq_above(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags,
+                                d_row_self ? d_row_self + (r0 - c) : nullptr, row0 + (r0 - c), window, causal, threshold,
+                                d_rows, d_cols, d_values, d_dirs, capacity, rp + (first - ctx), first - ctx, d_count,
+                                first > ctx ? 1 : 0, head + 256, h->d_status, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_above_head_bytes(R, M, ctx, L), d_workspace,
+                            workspace_bytes, stream, select, crng, L - 1);
+}
+
 // ---- sgpr_score_positives / sgpr_score_threshold_counts: the fused evaluation epilogues on the production handle; the
 //      other handles score bounded row blocks with their own tail and run the matrix kernels on each block, row0
 //      advancing, the blocks' results added up on the device
@@ -1775,6 +1870,141 @@ int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows
     };
     return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, counts_head_bytes(h, T), d_workspace, workspace_bytes,
                             stream, count);
+}
+
+// ---- sgpr_score_seq_positives / sgpr_score_seq_threshold_counts: the evaluation of the sequence-matched score on
+//      sgpr_score_seq_topk's row blocks with context (every handle): each block is filtered into a Q block and handed
+//      to the matrix kernels, row0 and d_gt advanced to the block's first output row - the wide-range path above with
+//      the filter in between.  (The counting kernels carry a threshold tree and rank sums: they are not fused into the
+//      filter.)
+static bool seq_eval_args_ok(const char* fn, const sgpr_handle* h, const float* rows, int R, const float* cols, int M,
+                             int ctx, int L, int flags, int row0, const double* pose, const signed char* gt, int64_t ldg) {
+    if (!h || R < 0 || M < 0 || (!pose && !gt) || (gt && !pose && ldg < M)) {
+        set_error(std::string(fn) + ": NULL argument, negative count, no ground truth or ldg below M");
+        return false;
+    }
+    if (!seq_args_ok(fn, R, ctx, L, flags, SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)) return false;
+    if (R > ctx && M > 0 && (!rows || !cols)) {
+        set_error(std::string(fn) + ": NULL pooled vectors");
+        return false;
+    }
+    return row0_ok(fn, row0, R);
+}
+
+static bool seq_eval_query_ok(const sgpr_handle* h, int R, int M, int ctx, int L, int flags) {
+    return seq_query_ok(h, R, M, ctx, L, flags) && !(flags & SGPR_TOPK_CAUSAL);
+}
+
+// head of the two calls: the call's f16 range (a float4) | Q block [rb][M] | (counts) the block's d_out and slabs
+static size_t seq_eval_head_bytes(int R, int M, int L) {
+    return 256 + a256((size_t)score_block_rows(R, M, L - 1) * M * sizeof(float));
+}
+
+size_t sgpr_score_seq_positives_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags) {
+    if (!seq_eval_query_ok(h, R, M, ctx, L, flags) || R == ctx || M == 0) return 0;
+    return row_blocks_ws_bytes(h, R, M, seq_eval_head_bytes(R, M, L), L - 1);
+}
+
+size_t sgpr_score_seq_threshold_counts_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags,
+                                                       int T) {
+    if (!seq_eval_query_ok(h, R, M, ctx, L, flags) || T < 0 || T > SGPR_SCORE_COUNT_MAX_THRESHOLDS || R == ctx || M == 0)
+        return 0;
+    return row_blocks_ws_bytes(h, R, M, seq_eval_head_bytes(R, M, L) + counts_head_bytes(h, T), L - 1);
+}
+
+extern "C++" {
+// score_row_blocks with L - 1 context rows; each block with output rows is filtered into the Q block and
+// consume(q, tail, first, no) sees Q of the call's rows [first, first + no) (ld M); tail: the head behind the Q block
+template <class Consume>
+static int seq_eval_blocks(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, int ctx, int L,
+                           int flags, size_t head_bytes, void* ws, size_t ws_bytes, void* stream, Consume&& consume) {
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t q_bytes = a256((size_t)rb * M * sizeof(float));
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto filter = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0);
+        float* q = reinterpret_cast<float*>(head + 256);
+        const int rc = launch_seq_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, q, M, nullptr, M, s);
+        return rc != SGPR_OK ? rc : consume(q, head + 256 + q_bytes, first, r0 + n - first);
+    };
+    return score_row_blocks(h, rows, R, cols, M, head_bytes, ws, ws_bytes, stream, filter, crng, L - 1);
+}
+}  // extern "C++"
+
+int sgpr_score_seq_positives(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                             int ctx, int L, int flags, int row0, const double* d_pose_xz, double d_pos, double d_neg,
+                             const signed char* d_gt, int64_t ldg, float* d_out, int64_t capacity,
+                             unsigned long long* d_count, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!seq_eval_args_ok("sgpr_score_seq_positives", h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags, row0,
+                          d_pose_xz, d_gt, ldg))
+        return SGPR_E_INVALID;
+    if (!d_count || capacity < 0 || (capacity > 0 && !d_out)) {
+        set_error("sgpr_score_seq_positives: NULL count buffer or capacity without an output buffer");
+        return SGPR_E_INVALID;
+    }
+    if (!workspace_ok("sgpr_score_seq_positives", sgpr_score_seq_positives_workspace_bytes(h, R, M, ctx, L, flags),
+                      d_workspace, workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return hip_fail(e, "sgpr_score_seq_positives: memset");
+    if (R == ctx || M == 0) return SGPR_OK;
+    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
+    float* out = capacity > 0 ? d_out : nullptr;
+    auto count = [&](const float* q, unsigned char*, int first, int no) {
+        PairTruth tb = truth;
+        tb.row0 = row0 + first;
+        if (tb.gt) tb.gt += (int64_t)(first - ctx) * ldg;
+        return launch_pair_positives_more(h, q, no, M, M, tb, out, capacity, d_count, s);
+    };
+    return seq_eval_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags, seq_eval_head_bytes(R, M, L), d_workspace,
+                           workspace_bytes, stream, count);
+}
+
+int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
+                                    int M, int ctx, int L, int flags, int row0, const double* d_pose_xz, double d_pos,
+                                    double d_neg, const signed char* d_gt, int64_t ldg, const float* d_thresholds, int T,
+                                    const sgpr_rank_group* d_rank, int groups_per_threshold,
+                                    const unsigned long long* d_at_least, unsigned long long* d_out, void* d_workspace,
+                                    size_t workspace_bytes, void* stream) {
+    if (!seq_eval_args_ok("sgpr_score_seq_threshold_counts", h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags, row0,
+                          d_pose_xz, d_gt, ldg))
+        return SGPR_E_INVALID;
+    if (!d_out || T < 0 || T > SGPR_SCORE_COUNT_MAX_THRESHOLDS || (T > 0 && !d_thresholds)) {
+        set_error("sgpr_score_seq_threshold_counts: 0.." + std::to_string(SGPR_SCORE_COUNT_MAX_THRESHOLDS) +
+                  " thresholds and an output buffer");
+        return SGPR_E_INVALID;
+    }
+    if (d_rank && (T < 1 || groups_per_threshold < 1 || !d_at_least)) {
+        set_error("sgpr_score_seq_threshold_counts: the ranking needs thresholds, >= 1 value group per threshold and the pair counts");
+        return SGPR_E_INVALID;
+    }
+    if (!workspace_ok("sgpr_score_seq_threshold_counts",
+                      sgpr_score_seq_threshold_counts_workspace_bytes(h, R, M, ctx, L, flags, T), d_workspace,
+                      workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return hip_fail(e, "sgpr_score_seq_threshold_counts: memset");
+    if (R == ctx || M == 0) return SGPR_OK;
+    const signed char* gt = d_pose_xz ? nullptr : d_gt;
+    const size_t part_bytes = a256((size_t)(T + 3) * 8), slab_bytes = sgpr_pair_threshold_counts_workspace_bytes(h, T);
+    auto count = [&](const float* q, unsigned char* tail, int first, int no) {
+        unsigned long long* part = reinterpret_cast<unsigned long long*>(tail);
+        const int rc = sgpr_pair_threshold_counts(h, q, no, M, M, row0 + first, d_pose_xz, d_pos, d_neg,
+                                                  gt ? gt + (int64_t)(first - ctx) * ldg : nullptr, ldg, d_thresholds, T,
+                                                  d_rank, groups_per_threshold, d_at_least, part, tail + part_bytes,
+                                                  slab_bytes, stream);
+        return rc != SGPR_OK ? rc : launch_eval_add(d_out, part, T + 3, s);
+    };
+    return seq_eval_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags,
+                           seq_eval_head_bytes(R, M, L) + counts_head_bytes(h, T), d_workspace, workspace_bytes, stream,
+                           count);
 }
 
 size_t sgpr_score_all_pairs_multi_workspace_bytes(const sgpr_handle* h, int n_jobs, const sgpr_pairs_job* jobs) {

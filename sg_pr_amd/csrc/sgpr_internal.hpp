@@ -338,6 +338,18 @@ int launch_score_above(const sgpr_handle* h, const float* rows, int R, const flo
 int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
                       int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals, int64_t cap, int64_t* row_ptr,
                       int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status, hipStream_t stream);
+// above_scan_kernel on its own: cnt [n] -> row_ptr [n + 1] and *count, both continuing from *count with accumulate
+int launch_above_scan(const int32_t* cnt, int n, int64_t* row_ptr, unsigned long long* count, int accumulate,
+                      hipStream_t stream);
+// the range selection of the sequence-matched score of a resident R x M block (sgpr_seq.hip; sgpr_seq_rows_above and
+// each row block of sgpr_score_seq_above): the eligible pairs of rows ctx .. R-1 with Q >= thr, row-major, as output
+// rows rout0 + r - ctx; row_self [R] / row0 belong to the block's row 0, row_ptr [R - ctx + 1] to its first output row;
+// accumulate: positions continue from *count.  ws: seq_above_ws_bytes(R - ctx, M)
+size_t seq_above_ws_bytes(int n, int M);
+int launch_seq_above(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* row_self,
+                     int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
+                     unsigned char* odirs, int64_t cap, int64_t* row_ptr, int rout0, unsigned long long* count,
+                     int accumulate, void* ws, int32_t* status, hipStream_t stream);
 // the fused evaluation epilogues of the all-pairs tail (production handle): T >= 0 the threshold counts (count == NULL,
 // d_out [T + 3]), T < 0 the positives (out [cap], count [2]); the chunked path of the other handles adds block counts up
 size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T);
@@ -397,6 +409,16 @@ int launch_cluster_scan(const float* pts, int stride, const uint32_t* label, int
 
 int launch_graph_edges(const float* pts, int stride, const int32_t* point_node, int P, int n, const double* centers,
                        double* min_dis, void* ws, hipStream_t stream);
+
+// eligibility of column c for a row whose own frame is s: c < M and (c < ea or c > eb) - the window [s - w, s + w] and,
+// causal, everything from s on are cut out
+__device__ __forceinline__ void tk_bounds(long long s, int window, int causal, int& ea, int& eb) {
+    const long long w = window < 0 ? 0 : window;
+    long long a = window < 0 ? (causal ? s : 0x7fffffffLL) : s - w;
+    long long b = (causal || window < 0) ? 0x7fffffffLL : s + w;
+    ea = (int)(a < -1 ? -1 : (a > 0x7fffffffLL ? 0x7fffffffLL : a));
+    eb = (int)(b < -2 ? -2 : (b > 0x7fffffffLL ? 0x7fffffffLL : b));
+}
 
 // sgpr_knn's ranking, shared by its two instances (knn_kernel, generic_knn_kernel) so that they return the same lists:
 //   key(i, j) = |x_i|^2 - (2 x_i.x_j - |x_j|^2) = -pd[i][j],  |x|^2 = rounded squares summed in channel order,

@@ -644,15 +644,7 @@ constexpr int TK_EMPTY = 0x7fffffff;
 
 __device__ __forceinline__ bool tk_beats(float av, int ac, float bv, int bc) { return av > bv || (av == bv && ac < bc); }
 
-// eligibility of column c for a row whose own frame is s: c < M and (c < ea or c > eb) - the window [s - w, s + w] and,
-// causal, everything from s on are cut out
-__device__ __forceinline__ void tk_bounds(long long s, int window, int causal, int& ea, int& eb) {
-    const long long w = window < 0 ? 0 : window;
-    long long a = window < 0 ? (causal ? s : 0x7fffffffLL) : s - w;
-    long long b = (causal || window < 0) ? 0x7fffffffLL : s + w;
-    ea = (int)(a < -1 ? -1 : (a > 0x7fffffffLL ? 0x7fffffffLL : a));
-    eb = (int)(b < -2 ? -2 : (b > 0x7fffffffLL ? 0x7fffffffLL : b));
-}
+// (tk_bounds, the eligibility rule of every list and range epilogue: sgpr_internal.hpp)
 
 // merge the candidate (cv, cc) of every lane (ok: it qualifies) into its lane group's list (entry l15 in (lv, lc));
 // sv / sc: this wave's 64-entry LDS slice
@@ -2189,6 +2181,13 @@ int launch_score_above(const sgpr_handle* h, const float* rows, int R, const flo
         if (rc != SGPR_OK) return rc;
     }
     return SGPR_OK;
+}
+
+int launch_above_scan(const int32_t* cnt, int n, int64_t* row_ptr, unsigned long long* count, int accumulate,
+                      hipStream_t stream) {
+    hipLaunchKernelGGL(above_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, n, row_ptr, count, accumulate);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "above_scan_kernel launch");
 }
 
 int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,

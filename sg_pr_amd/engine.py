@@ -50,6 +50,10 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
                "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
                "sgpr_score_threshold_counts_workspace_bytes", "sgpr_score_threshold_counts",
+               "sgpr_seq_rows_above_workspace_bytes", "sgpr_seq_rows_above",
+               "sgpr_score_seq_above_workspace_bytes", "sgpr_score_seq_above",
+               "sgpr_score_seq_positives_workspace_bytes", "sgpr_score_seq_positives",
+               "sgpr_score_seq_threshold_counts_workspace_bytes", "sgpr_score_seq_threshold_counts",
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
                "sgpr_attention_pool_any", "sgpr_ntn_any",
                "sgpr_edgeconv_train_workspace_bytes", "sgpr_edgeconv_train_forward", "sgpr_edgeconv_train_backward",
@@ -218,6 +222,26 @@ def load_library():
     lib.sgpr_score_threshold_counts.restype = i32
     lib.sgpr_score_threshold_counts.argtypes = [vp, vp, i32, vp, i32, i32, vp, dbl, dbl, vp, i64, vp, i32, vp, i32, vp, vp,
                                                 vp, sz, vp]
+    lib.sgpr_seq_rows_above_workspace_bytes.restype = sz
+    lib.sgpr_seq_rows_above_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.sgpr_seq_rows_above.restype = i32
+    lib.sgpr_seq_rows_above.argtypes = [vp, vp, i32, i32, i64, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp,
+                                        vp, vp, sz, vp]
+    lib.sgpr_score_seq_above_workspace_bytes.restype = sz
+    lib.sgpr_score_seq_above_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32]
+    lib.sgpr_score_seq_above.restype = i32
+    lib.sgpr_score_seq_above.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp,
+                                         vp, vp, sz, vp]
+    lib.sgpr_score_seq_positives_workspace_bytes.restype = sz
+    lib.sgpr_score_seq_positives_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32]
+    lib.sgpr_score_seq_positives.restype = i32
+    lib.sgpr_score_seq_positives.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, dbl, dbl, vp, i64, vp, i64, vp,
+                                             vp, sz, vp]
+    lib.sgpr_score_seq_threshold_counts_workspace_bytes.restype = sz
+    lib.sgpr_score_seq_threshold_counts_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]
+    lib.sgpr_score_seq_threshold_counts.restype = i32
+    lib.sgpr_score_seq_threshold_counts.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, dbl, dbl, vp, i64, vp,
+                                                    i32, vp, i32, vp, vp, vp, sz, vp]
     lib.sgpr_embed_lds_bytes.restype = sz
     lib.sgpr_embed_lds_bytes.argtypes = [vp, i32, i32]
     lib.sgpr_knn.restype = i32
@@ -1238,6 +1262,146 @@ class Engine:
                                             float(threshold), _ptr(out_r), _ptr(out_c), _ptr(out_v), cap,
                                             _ptr(row_ptr), _ptr(count), _ptr(ws), ws_bytes, self._stream())
         return self._above(r, m, capacity, call)
+
+    # ------------------------------------------------------------------ the same on the sequence-matched score
+    def seq_rows_above_workspace_bytes(self, r, m, context=0):
+        return int(self.lib.sgpr_seq_rows_above_workspace_bytes(self._h, int(r), int(m), int(context)))
+
+    def score_seq_above_workspace_bytes(self, r, m, seq_len, causal=False, context=0, reverse="both"):
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        return int(self.lib.sgpr_score_seq_above_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
+                                                                 flags))
+
+    def _seq_above(self, r, m, context, capacity, call, want_dirs=True):
+        """_above for the outputs of rows context .. r - 1, with the direction of every listed pair"""
+        ro = max(r - int(context), 0)
+        dirs = []
+
+        def call_dirs(cap, out_r, out_c, out_v, row_ptr, count):
+            d = torch.empty(cap, dtype=torch.uint8, device=self.device) if want_dirs else None
+            dirs[:] = [d]
+            return call(cap, out_r, out_c, out_v, d, row_ptr, count)
+        out_r, out_c, out_v, row_ptr = self._above(ro, m, capacity, call_dirs)
+        d = dirs[0]
+        return out_r, out_c, out_v, (d[:out_r.numel()] if d is not None else None), row_ptr
+
+    def seq_rows_above(self, score, seq_len, threshold, window=-1, row0=0, causal=False, row_self=None, context=0,
+                       reverse="both", capacity=None, want_dirs=True):
+        """rows_above on the sequence-matched score of a resident matrix score [R, M] (sgpr_seq_rows_above; any row
+        stride >= M with unit column stride is read in place): every eligible pair of rows context .. R-1 whose
+        seq_filter value is >= threshold -> (rows i32 [n] counted from `context`, cols i32 [n], values f32 [n] - the bits
+        seq_filter writes -, dirs u8 [n] (0 forward, 1 reverse; None for want_dirs=False), row_ptr i64 [R - context + 1]),
+        row-major.  Eligibility is score_topk's on the end point, with row_self [R] / row0 + r counted over all R rows;
+        capacity as in score_above.  The filtered matrix is never written."""
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
+                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
+            score = self._dev(score, torch.float32, "score")
+        r, m = score.shape
+        ld = max(score.stride(0), m)
+        rs = self._row_self(row_self, r)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        ws_bytes = self.lib.sgpr_seq_rows_above_workspace_bytes(self._h, r, m, int(context))
+        ws = self._ws(ws_bytes)
+
+        def call(cap, out_r, out_c, out_v, out_d, row_ptr, count):
+            return self.lib.sgpr_seq_rows_above(self._h, _ptr(score), r, m, ld, int(context), _ptr(rs), int(row0),
+                                                int(window), flags, int(seq_len), float(threshold), _ptr(out_r),
+                                                _ptr(out_c), _ptr(out_v), _ptr(out_d), cap, _ptr(row_ptr), _ptr(count),
+                                                _ptr(ws), ws_bytes, self._stream())
+        return self._seq_above(r, m, context, capacity, call, want_dirs)
+
+    def score_seq_above(self, pooled_rows, pooled_cols, seq_len, threshold, window=-1, row0=0, causal=False,
+                        row_self=None, context=0, reverse="both", capacity=None, want_dirs=True):
+        """seq_rows_above on the rectangle pooled_rows x pooled_cols without forming it (sgpr_score_seq_above): the
+        rectangle is scored in row blocks of at most 64 MB that carry their last seq_len - 1 rows over as context, and
+        neither the filtered scores nor their directions are ever stored -> (rows, cols, values, dirs, row_ptr)."""
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        ws_bytes = self.lib.sgpr_score_seq_above_workspace_bytes(self._h, r, m, int(context), int(seq_len), flags)
+        ws = self._ws(ws_bytes)
+
+        def call(cap, out_r, out_c, out_v, out_d, row_ptr, count):
+            return self.lib.sgpr_score_seq_above(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
+                                                 int(window), flags, int(seq_len), float(threshold), _ptr(out_r),
+                                                 _ptr(out_c), _ptr(out_v), _ptr(out_d), cap, _ptr(row_ptr), _ptr(count),
+                                                 _ptr(ws), ws_bytes, self._stream())
+        return self._seq_above(r, m, context, capacity, call, want_dirs)
+
+    def score_seq_positives_workspace_bytes(self, r, m, seq_len, context=0, reverse="both"):
+        return int(self.lib.sgpr_score_seq_positives_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
+                                                                     self._seq_flags(reverse)))
+
+    def score_seq_threshold_counts_workspace_bytes(self, r, m, seq_len, t, context=0, reverse="both"):
+        return int(self.lib.sgpr_score_seq_threshold_counts_workspace_bytes(self._h, int(r), int(m), int(context),
+                                                                            int(seq_len), self._seq_flags(reverse), int(t)))
+
+    def _seq_truth(self, r, m, context, row0, pose_xz, gt):
+        ro = max(r - int(context), 0)
+        if pose_xz is None and gt is not None:
+            gt = self._dev(gt, torch.int8, "gt")
+            assert gt.shape == (ro, m)
+            return None, gt
+        return self._pooled_truth(r, m, row0, pose_xz, gt)
+
+    def score_seq_positives(self, pooled_rows, pooled_cols, seq_len, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None,
+                            context=0, reverse="both"):
+        """pair_positives on seq_filter(score_all_pairs(pooled_rows, pooled_cols)) without the matrix
+        (sgpr_score_seq_positives): the sequence-matched scores of the positive pairs of rows context .. R-1 (float32
+        device tensor, unordered, the bits seq_filter writes) and the number skipped for a negative / NaN score.  The row
+        pose of output row o is pose_xz[row0 + context + o]; gt is [R - context, M]."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        pose_xz, gt = self._seq_truth(r, m, context, row0, pose_xz, gt)
+        flags = self._seq_flags(reverse)
+        ws_bytes = self.lib.sgpr_score_seq_positives_workspace_bytes(self._h, r, m, int(context), int(seq_len), flags)
+        ws = self._ws(ws_bytes)
+        count = torch.empty(2, dtype=torch.int64, device=self.device)
+        cap = min(max(r - int(context), 0) * m, 1 << 20)
+        while True:
+            out = torch.empty(cap, dtype=torch.float32, device=self.device)
+            rc = self.lib.sgpr_score_seq_positives(self._h, _ptr(rows), r, _ptr(cols), m, int(context), int(seq_len),
+                                                   flags, int(row0), _ptr(pose_xz), float(d_pos), float(d_neg), _ptr(gt),
+                                                   m, _ptr(out) if cap else None, cap, _ptr(count), _ptr(ws), ws_bytes,
+                                                   self._stream())
+            self._check(rc)
+            n, bad = (int(v) for v in count.tolist())
+            if n <= cap:
+                return out[:n], bad
+            cap = n
+
+    def score_seq_threshold_counts(self, pooled_rows, pooled_cols, seq_len, thresholds, row0=0, pose_xz=None, d_pos=3.0,
+                                   d_neg=20.0, gt=None, rank=None, context=0, reverse="both"):
+        """pair_threshold_counts on seq_filter(score_all_pairs(pooled_rows, pooled_cols)) without the matrix
+        (sgpr_score_seq_threshold_counts): thresholds ascending float32, at most MAX_POOLED_THRESHOLDS.
+        Returns (counts int64 [T+1], skipped, rank_sum or None), equal to pair_threshold_counts' on that matrix."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        pose_xz, gt = self._seq_truth(r, m, context, row0, pose_xz, gt)
+        thr = self._dev(torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float32)), torch.float32, "thresholds")
+        t = int(thr.numel())
+        out = torch.empty(t + 3, dtype=torch.int64, device=self.device)
+        flags = self._seq_flags(reverse)
+        ws_bytes = self.lib.sgpr_score_seq_threshold_counts_workspace_bytes(self._h, r, m, int(context), int(seq_len),
+                                                                            flags, t)
+        ws = self._ws(ws_bytes)
+        table, at_least, gpt = self._rank_table(rank, t)
+        rc = self.lib.sgpr_score_seq_threshold_counts(self._h, _ptr(rows), r, _ptr(cols), m, int(context), int(seq_len),
+                                                      flags, int(row0), _ptr(pose_xz), float(d_pos), float(d_neg),
+                                                      _ptr(gt), m, _ptr(thr), t, _ptr(table), gpt, _ptr(at_least),
+                                                      _ptr(out), _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        h = out.cpu().numpy()
+        rank_sum = int(h[t + 2].astype(np.uint64)) if rank is not None else None
+        return h[:t + 1].copy(), int(h[t + 1]), rank_sum
 
     def forward_dense(self, features_1, features_2, k, want_att=True):
         """Drop-in SG.forward on dense [B,3+L,N] inputs -> (score [B], att1 [B,N], att2 [B,N])."""

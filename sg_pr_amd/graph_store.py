@@ -86,7 +86,8 @@ def evaluate_all_pairs(model, seq, p_thresh=3.0, n_thresh=20.0, top_k=1, window=
     closures from Engine.score_topk (the same values), and "matrix" is None.
     seq_len > 1 (frames in trajectory order, one GPU, keep_matrix=True): the kept matrix is also sequence-matched
     (Engine.seq_filter, seq_reverse False / True / "both") and the result adds "seq_f1_max", "seq_roc_auc",
-    "seq_closure_scores", "seq_closure_frames" and "seq_matrix" of the filtered scores beside the unfiltered ones."""
+    "seq_closure_scores", "seq_closure_frames" and "seq_matrix" of the filtered scores beside the unfiltered ones
+    (without the matrix: evaluate_seq_pooled)."""
     from . import allpairs
     seq_len = int(seq_len)
     if seq_len != 1 and not keep_matrix:
@@ -138,13 +139,32 @@ def _evaluate_pooled(model, seq, pooled, p_thresh, n_thresh, top_k, window, scor
     return {"f1_max": f1, "roc_auc": auc, "closure_scores": vals, "closure_frames": idx, "matrix": None}
 
 
+def evaluate_seq_pooled(model, seq, seq_len, seq_reverse="both", p_thresh=3.0, n_thresh=20.0, top_k=1, window=50):
+    """The sequence-matched half of evaluate_all_pairs(seq_len=) without the score matrix or the filtered one (one GPU;
+    frames in trajectory order): {"seq_f1_max", "seq_roc_auc"} from metrics.pr_roc_seq_pooled and {"seq_closure_scores",
+    "seq_closure_frames", "seq_closure_dirs"} [M,k] from Engine.score_seq_topk - the values the matrix run reports."""
+    from . import allpairs, metrics
+    eng = model.engine()
+    k = int(model.args.K)
+    order, cap = eng.size_order(seq.centers, seq.labels, k)
+    pooled = eng.embed(seq.centers, seq.labels, k, node_cap=cap, order=order)[0]
+    eng.check_status()
+    xz = allpairs.pose_xz(seq.poses).to(pooled.device)
+    f1, auc, _ = metrics.pr_roc_seq_pooled(eng, pooled, pooled, int(seq_len), pose_xz=xz, p_thresh=p_thresh,
+                                           n_thresh=n_thresh, reverse=seq_reverse)
+    vals, idx, dirs = eng.score_seq_topk(pooled, pooled, int(seq_len), k=top_k, window=window, reverse=seq_reverse)
+    return {"seq_f1_max": f1, "seq_roc_auc": auc, "seq_closure_scores": vals, "seq_closure_frames": idx,
+            "seq_closure_dirs": dirs}
+
+
 def main(argv=None):
     """python -m sg_pr_amd.graph_store config.yml   - all-pairs evaluation of every `eva_batch.sequences` entry:
     packs `<graph_pairs_dir>/<seq>/` once (cached as `<output_path>/<seq>_packed.npz`), writes
     `<seq>_allpairs_F1_max.txt` and `<seq>_loop_closures.npy` (frame, best match, score).
     --no-matrix: the same outputs without ever forming the M x M score matrix (evaluate_all_pairs keep_matrix=False).
     --seq-len L [--seq-reverse off|on|both]: also the F1-max and ROC area of the sequence-matched matrix
-    (`<seq>_seq_F1_max.txt`, evaluate_all_pairs seq_len=) and its closures (`<seq>_seq_loop_closures.npy`)."""
+    (`<seq>_seq_F1_max.txt`, evaluate_all_pairs seq_len=) and its closures (`<seq>_seq_loop_closures.npy`); with
+    --no-matrix the same two files without the matrix or the filtered one (evaluate_seq_pooled)."""
     import sys
     from .parser_sg import sgpr_args
     from .sg_net import SGTrainer
@@ -178,8 +198,12 @@ def main(argv=None):
             seq = pack_directory(os.path.join(args.graph_pairs_dir, sequence), int(args.node_num),
                                  trainer.number_of_labels)
             seq.save(cache)
-        r = evaluate_all_pairs(trainer.model, seq, p_thresh=float(args.p_thresh), keep_matrix=keep_matrix,
-                               seq_len=seq_len, seq_reverse=seq_reverse)
+        if keep_matrix or seq_len == 1:
+            r = evaluate_all_pairs(trainer.model, seq, p_thresh=float(args.p_thresh), keep_matrix=keep_matrix,
+                                   seq_len=seq_len, seq_reverse=seq_reverse)
+        else:
+            r = evaluate_all_pairs(trainer.model, seq, p_thresh=float(args.p_thresh), keep_matrix=False)
+            r.update(evaluate_seq_pooled(trainer.model, seq, seq_len, seq_reverse, p_thresh=float(args.p_thresh)))
         with open(os.path.join(args.output_path, sequence + "_allpairs_F1_max.txt"), "w") as f:
             f.write(str(r["f1_max"]))
         m = len(seq)

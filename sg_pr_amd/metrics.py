@@ -250,6 +250,58 @@ def roc_auc_pooled(engine, pooled_rows, pooled_cols, pose_xz=None, p_thresh=3.0,
     return pr_roc_pooled(engine, pooled_rows, pooled_cols, pose_xz, p_thresh, n_thresh, gt, row0, refine=False)[1]
 
 
+def _seq_pooled_fns(engine, pooled_rows, pooled_cols, seq_len, pose_xz, p_thresh, n_thresh, gt, row0, context, reverse,
+                    distinct=True, to_host=True):
+    """_pooled_fns on the sequence-matched score (Engine.score_seq_positives / score_seq_threshold_counts): rows and
+    columns are consecutive scans, the first `context` rows serve as context only."""
+    kw = dict(row0=row0, pose_xz=pose_xz, d_pos=p_thresh, d_neg=n_thresh, gt=gt, context=context, reverse=reverse)
+
+    def count_fn(thresholds, rank):
+        counts, bad, rank_sum = engine.score_seq_threshold_counts(pooled_rows, pooled_cols, seq_len, thresholds, rank=rank,
+                                                                  **kw)
+        if bad:
+            raise ValueError("%d scores are negative or NaN" % bad)
+        return counts, rank_sum
+    pos, bad = engine.score_seq_positives(pooled_rows, pooled_cols, seq_len, **kw)
+    if bad:
+        raise ValueError("%d scores are negative or NaN" % bad)
+    if not distinct:
+        return (pos.cpu().numpy() if to_host else pos), count_fn
+    import torch
+    u, mult = torch.unique(pos, sorted=True, return_counts=True)
+    return (u.cpu().numpy(), mult.cpu().numpy().astype(np.int64)), count_fn
+
+
+def pr_roc_seq_pooled(engine, pooled_rows, pooled_cols, seq_len, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None,
+                      row0=0, context=0, reverse="both", want_auc=True, refine=True, max_thresholds=None):
+    """(F1-max, ROC area, counting passes) of the sequence-matched score of the pairs pooled_rows x pooled_cols (rows
+    context .. R-1; Engine.seq_filter's definition) WITHOUT the score matrix or the filtered one: pr_roc_pooled's host
+    code over producers that filter each 64 MB row block as they count it.  Equal to pr_roc_device on
+    seq_filter(score_all_pairs(...)) exactly.  The row pose of output row o is pose_xz[row0 + context + o]; gt is
+    [R - context, M]."""
+    if max_thresholds is None:
+        max_thresholds = getattr(engine, "MAX_POOLED_THRESHOLDS", MAX_THRESHOLDS)
+    distinct, count_fn = _seq_pooled_fns(engine, pooled_rows, pooled_cols, seq_len, pose_xz, p_thresh, n_thresh, gt, row0,
+                                         context, reverse)
+    return pr_roc_from_counts(None, count_fn, want_auc=want_auc, max_thresholds=max_thresholds, distinct=distinct,
+                              refine=refine)
+
+
+def f1_max_seq_pooled(engine, pooled_rows, pooled_cols, seq_len, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None,
+                      row0=0, context=0, reverse="both"):
+    """F1-max of the sequence-matched score without any matrix -> (f1_max, counting passes)."""
+    f1, _, passes = pr_roc_seq_pooled(engine, pooled_rows, pooled_cols, seq_len, pose_xz, p_thresh, n_thresh, gt, row0,
+                                      context, reverse, want_auc=False)
+    return f1, passes
+
+
+def roc_auc_seq_pooled(engine, pooled_rows, pooled_cols, seq_len, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None,
+                       row0=0, context=0, reverse="both"):
+    """ROC area of the sequence-matched score without any matrix: exact, one counting pass."""
+    return pr_roc_seq_pooled(engine, pooled_rows, pooled_cols, seq_len, pose_xz, p_thresh, n_thresh, gt, row0, context,
+                             reverse, refine=False)[1]
+
+
 def counts_of(score, gt):
     """numpy stand-ins for sgpr_pair_positives / sgpr_pair_threshold_counts (tests, small inputs): gt 1 / 0 / negative
     = ignored.  Returns (positive scores, count_fn)."""

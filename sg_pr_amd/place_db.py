@@ -8,6 +8,7 @@ with sgpr_score_topk - the k best matches per query, no similarity matrix at any
     rows, cols, vals, row_ptr = db.query_ids_above(ids, 0.9, window=50)   # every member scoring >= 0.9
     vals, idx, dirs = db.query_seq(centers, labels, seq_len=8, k=4, window=50, causal=True)   # sequence-matched
     vals, idx, dirs = db.query_ids_seq(first, count, seq_len=8, k=4, window=50)               # a run of members
+    rows, cols, vals, dirs, row_ptr = db.query_seq_above(centers, labels, seq_len=8, threshold=0.9, window=50, causal=True)
     db.save("map.npz"); db = PlaceDatabase.load("map.npz", model)
 
 A vector costs 128 bytes of device memory (the matrix of a 100 k-graph map would be 40 GB).  The file keeps the vectors,
@@ -26,7 +27,9 @@ p_thresh), indices and scores (Engine.score_mine; the window applies to both), a
 negative scoring above their best positive.  With --seq-len L (2..32) the lists of `<seq>_topk.npz` rank the
 sequence-matched score (the mean along the diagonal of the last L frames of both trajectories, engine.Engine.seq_filter;
 --seq-reverse: forward diagonals only (off), reverse only (on) or the larger of both, the default) and the file adds
-seq_len and dirs [M,K] (0 forward, 1 reverse).
+seq_len and dirs [M,K] (0 forward, 1 reverse).  With --threshold and --seq-len L > 1 also `<seq>_seq_above.npz`: every
+pair whose sequence-matched score is >= T (rows, cols, scores, dirs, precision, recall, seq_len; Engine.score_seq_above);
+`<seq>_above.npz` stays the single-scan result.
 """
 import argparse
 import hashlib
@@ -145,6 +148,27 @@ class PlaceDatabase:
         return self.eng.score_above(rows, self.pooled, threshold, window=window, causal=causal,
                                     row_self=ids.to(torch.int32))
 
+    def query_seq_above(self, centers, labels, seq_len, threshold, window=-1, causal=False, reverse="both", pooled=None):
+        """query_seq's rows (new scans as the next frames, the last seq_len - 1 members as context rows) thresholded
+        instead of ranked: every member whose sequence-matched score is >= threshold (engine.Engine.score_seq_above)
+        -> (rows i32 [n], ids i32 [n], scores f32 [n], dirs u8 [n], row_ptr i64 [g+1]).  Fed one scan at a time it
+        returns the pairs of one offline call, under query_seq's condition (causal, window >= seq_len - 1)."""
+        new = self._embed(centers, labels) if pooled is None else self.eng._pooled(pooled, "pooled")
+        ctx = min(int(seq_len) - 1, self.n)
+        rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
+        return self.eng.score_seq_above(rows, self.pooled, int(seq_len), threshold, window=window, row0=self.n - ctx,
+                                        causal=causal, context=ctx, reverse=reverse)
+
+    def query_ids_seq_above(self, first, count, seq_len, threshold, window=-1, causal=False, reverse="both"):
+        """Every member whose sequence-matched score is >= threshold for the run of members first .. first + count - 1
+        (rows counted from `first`), the up to seq_len - 1 members before it serving as context rows."""
+        first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > self.n:
+            raise IndexError("query_ids_seq_above: first .. first + count must lie in [0, %d]" % self.n)
+        ctx = min(int(seq_len) - 1, first)
+        return self.eng.score_seq_above(self._buf[first - ctx:first + count], self.pooled, int(seq_len), threshold,
+                                        window=window, row0=first - ctx, causal=causal, context=ctx, reverse=reverse)
+
     def save(self, path):
         dims = np.array([getattr(self.eng.dims, f) for f in _DIMS], dtype=np.int64)
         np.savez(path, pooled=self.pooled.cpu().numpy(), dims=dims, weights_sha256=np.array(weights_sha256(self.model)))
@@ -232,6 +256,17 @@ def main(argv=None):
             np.savez(os.path.join(args.output_path, sequence + "_above.npz"), rows=rows.cpu().numpy(),
                      cols=cols.cpu().numpy(), scores=scores.cpu().numpy(), precision=precision, recall=rec)
             print("sequence", sequence, "threshold", opt.threshold, "pairs", rows.numel(),
+                  "precision %.4f recall %.4f" % (precision, rec))
+        if opt.threshold is not None and opt.seq_len > 1:
+            rows, cols, scores, dirs, _ = db.query_ids_seq_above(
+                0, m, opt.seq_len, opt.threshold, window=opt.window, causal=opt.causal,
+                reverse={"off": False, "on": True, "both": "both"}[opt.seq_reverse])
+            precision, rec = metrics.precision_recall_at(rows, cols, seq.poses, p_thresh=float(args.p_thresh),
+                                                         window=opt.window, causal=opt.causal)
+            np.savez(os.path.join(args.output_path, sequence + "_seq_above.npz"), rows=rows.cpu().numpy(),
+                     cols=cols.cpu().numpy(), scores=scores.cpu().numpy(), dirs=dirs.cpu().numpy(), precision=precision,
+                     recall=rec, seq_len=np.int64(opt.seq_len))
+            print("sequence", sequence, "sequence length", opt.seq_len, "threshold", opt.threshold, "pairs", rows.numel(),
                   "precision %.4f recall %.4f" % (precision, rec))
         if opt.hard is not None:
             hard = hard_pairs_of(db, seq.poses, opt.hard, float(args.p_thresh), window=opt.window, causal=opt.causal)

@@ -167,17 +167,28 @@ class SG(torch.nn.Module):
                                         row_pose=row_pose)
 
     def loop_closures_above(self, pooled_rows, pooled_cols, threshold, window=-1, row0=0, causal=False, row_self=None,
-                            capacity=None):
+                            capacity=None, seq_len=1, seq_reverse="both"):
         """Every pair of pooled_rows x pooled_cols scoring >= threshold, without forming the matrix
-        (engine.Engine.score_above) -> (rows i32 [n], cols i32 [n], values f32 [n], row_ptr i64 [R+1]) on the device."""
+        (engine.Engine.score_above) -> (rows i32 [n], cols i32 [n], values f32 [n], row_ptr i64 [R+1]) on the device.
+        seq_len > 1: rows and columns are consecutive scans and the sequence-matched score is thresholded
+        (engine.Engine.score_seq_above; seq_reverse False / True / "both") -> (rows, cols, values, dirs u8 [n], row_ptr)."""
+        if int(seq_len) != 1:
+            return self.engine().score_seq_above(pooled_rows, pooled_cols, int(seq_len), threshold, window=window,
+                                                 row0=row0, causal=causal, row_self=row_self, reverse=seq_reverse,
+                                                 capacity=capacity)
         return self.engine().score_above(pooled_rows, pooled_cols, threshold, window=window, row0=row0, causal=causal,
                                          row_self=row_self, capacity=capacity)
 
     def evaluate_pooled(self, pooled_rows, pooled_cols, pose_xz=None, p_thresh=3.0, n_thresh=20.0, gt=None, row0=0,
-                        want_auc=True):
+                        want_auc=True, seq_len=1, seq_reverse="both"):
         """(F1-max, ROC area, counting passes) of the pairs pooled_rows x pooled_cols without forming the matrix
-        (metrics.pr_roc_pooled): ground truth from planar poses [.,2] or explicit int8 labels [R,M]."""
+        (metrics.pr_roc_pooled): ground truth from planar poses [.,2] or explicit int8 labels [R,M].
+        seq_len > 1: of their sequence-matched score (metrics.pr_roc_seq_pooled)."""
         from . import metrics
+        if int(seq_len) != 1:
+            return metrics.pr_roc_seq_pooled(self.engine(), pooled_rows, pooled_cols, int(seq_len), pose_xz=pose_xz,
+                                             p_thresh=p_thresh, n_thresh=n_thresh, gt=gt, row0=row0, reverse=seq_reverse,
+                                             want_auc=want_auc)
         return metrics.pr_roc_pooled(self.engine(), pooled_rows, pooled_cols, pose_xz=pose_xz, p_thresh=p_thresh,
                                      n_thresh=n_thresh, gt=gt, row0=row0, want_auc=want_auc)
 
