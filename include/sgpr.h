@@ -207,7 +207,11 @@ int sgpr_embed_debug(const sgpr_handle* h, const float* d_centers, const int32_t
 /* Pair-coupled half of SG.forward: TenorNetworkModule.forward
  * (layers_batch.py:70-83) + fully_connected_first/ReLU + scoring_layer/sigmoid
  * (sg_net.py:131-136) for P pairs.  Pair p scores
- *   (d_pooled1[idx1 ? idx1[p] : p], d_pooled2[idx2 ? idx2[p] : p]); idx may be NULL. */
+ *   (d_pooled1[idx1 ? idx1[p] : p], d_pooled2[idx2 ? idx2[p] : p]); idx may be NULL.
+ * Non-finite pooled vectors (every scoring entry point below follows this rule): a NaN anywhere in a graph's vector - the
+ * embed entry points' marker of a graph that broke its node promise - gives a NaN score for every pair of that graph,
+ * never the score of a healthy graph; a +-inf gives NaN or the score of the limit, depending on the order in which the
+ * kernel at work meets infinite terms; pairs of two finite graphs are not affected. */
 int sgpr_score_pairs(const sgpr_handle* h, const float* d_pooled1, const int32_t* d_idx1,
                      const float* d_pooled2, const int32_t* d_idx2, int64_t P, float* d_score, void* stream);
 
@@ -231,7 +235,8 @@ int sgpr_score_pairs(const sgpr_handle* h, const float* d_pooled1, const int32_t
  * sgpr_score_pair_list: d_score[p] = SG-tail(d_pooled_rows[idx1[p]], d_pooled_cols[idx2[p]]) for the P pairs of the plan
  * (d_plan: the plan words in DEVICE memory; R, M, n_rows, n_items and P are the values sgpr_pair_plan was given and
  * returned - the kernels trust the plan's indices, as sgpr_score_pairs trusts idx1 / idx2).  Workspace:
- * sgpr_score_pair_list_workspace_bytes(h, n_rows, M). */
+ * sgpr_score_pair_list_workspace_bytes(h, n_rows, M).  A NaN or +-inf in a listed row graph or in ANY of the M column
+ * graphs puts the whole list on the exact fp32 per-pair path; every pair of a NaN graph scores NaN (sgpr_score_pairs). */
 size_t sgpr_pair_plan_ints(int64_t P, int R);
 int sgpr_pair_plan(const int32_t* h_idx1, const int32_t* h_idx2, int64_t P, int R, int M, int32_t* h_plan,
                    size_t plan_capacity_ints, size_t* plan_ints, int32_t* n_rows, int32_t* n_items);
@@ -242,7 +247,10 @@ int sgpr_score_pair_list(const sgpr_handle* h, const float* d_pooled_rows, int R
 
 /* Dense all-pairs form of the same tail: score[r, c] = SG-tail(rows[r], cols[c])
  * (the NTN is asymmetric, layers_batch.py:77-83, so the full rectangle is computed).
- * d_score is [R, ld] with ld >= M.  Workspace: sgpr_score_all_pairs_workspace_bytes. */
+ * d_score is [R, ld] with ld >= M.  Workspace: sgpr_score_all_pairs_workspace_bytes.
+ * A NaN or +-inf pooled vector among the rows or columns puts the whole rectangle on the exact fp32 per-pair path (like
+ * inputs beyond the f16 range, on every handle kind): row r and column c of a NaN graph are NaN, every other entry is
+ * within the exact path's error of the reference (sgpr_score_pairs states the rule). */
 size_t sgpr_score_all_pairs_workspace_bytes(const sgpr_handle* h, int R, int M);
 int sgpr_score_all_pairs(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
                          int M, float* d_score, int64_t ld, void* d_workspace, size_t workspace_bytes,
@@ -251,7 +259,8 @@ int sgpr_score_all_pairs(const sgpr_handle* h, const float* d_pooled_rows, int R
 /* Several independent rectangles with ONE pair of launches - the matrices of the sequences of an evaluation job
  * (eval_batch.py:26-36 loops over `eva_batch.sequences`): the work items of all jobs form one list that the workgroups
  * split evenly, so small matrices do not leave the GPU half empty and the launch gaps between them disappear.  `jobs` is
- * a HOST array (its device pointers are read at launch); results are bit-identical to one sgpr_score_all_pairs per job. */
+ * a HOST array (its device pointers are read at launch); results are bit-identical to one sgpr_score_all_pairs per job,
+ * NaN entries of a job with a non-finite pooled vector included (that job alone takes the exact path). */
 #define SGPR_MAX_PAIR_JOBS 8
 typedef struct sgpr_pairs_job {
     const float* d_pooled_rows;   /* [R][32] */
@@ -353,7 +362,9 @@ int sgpr_topk_rows(const sgpr_handle* h, const float* d_score, int R, int M, int
  * answered once per call, over the whole rectangle, before its first block: every block takes the datapath
  * sgpr_score_all_pairs takes on that rectangle.  d_values / d_indices [R][k], device.  Arguments are checked
  * before the device is touched: a NULL pointer, k outside 1..16 or unknown flag bits give SGPR_E_INVALID, a workspace
- * below sgpr_score_topk_workspace_bytes SGPR_E_WORKSPACE.  Asynchronous on `stream`. */
+ * below sgpr_score_topk_workspace_bytes SGPR_E_WORKSPACE.  Asynchronous on `stream`.
+ * A row graph whose pooled vector holds a NaN gets (-inf, -1) in every slot and a NaN column graph is never listed: their
+ * scores are NaN (sgpr_score_pairs).  The same holds for sgpr_score_topk_large and sgpr_score_seq_topk below. */
 #define SGPR_TOPK_CAUSAL 1
 size_t sgpr_score_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags);
 int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -446,7 +457,8 @@ int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R,
  * d_values / d_indices [R][k], device.  Arguments are checked before the device is touched: a NULL handle, pooled
  * array, column pose array or output, k outside 1..16, zero or both mode flags or unknown bits, a NaN d_pos / d_neg,
  * d_pos < 0, d_pos > d_neg or row0 + R beyond an int give SGPR_E_INVALID, a workspace below sgpr_score_mine_workspace_bytes
- * SGPR_E_WORKSPACE; a d_row_self entry outside [0, M) is reported by sgpr_check_status.  Asynchronous on `stream`. */
+ * SGPR_E_WORKSPACE; a d_row_self entry outside [0, M) is reported by sgpr_check_status.  Asynchronous on `stream`.
+ * A graph whose pooled vector holds a NaN is never mined, as a row (empty slots) or as a column: its scores are NaN. */
 #define SGPR_MINE_NEGATIVES 2
 #define SGPR_MINE_POSITIVES 4
 size_t sgpr_score_mine_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags);
@@ -485,7 +497,10 @@ int sgpr_mine_rows(const sgpr_handle* h, const float* d_score, int R, int M, int
  *   O(R) counters and row pointers, O(grid) partial counts, one byte per 16 x 256 work item).  Wide-range and any-shape
  *   handles score row blocks of at most 64 MB with their own tail and select from each with sgpr_rows_above's kernels,
  *   positions continuing on the device.  The production handle's launches take at most 131 072 rows each; on every
- *   handle the f16 range of a row-blocked call is decided once, over the whole rectangle.  Asynchronous on `stream`, no host synchronisation inside. */
+ *   handle the f16 range of a row-blocked call is decided once, over the whole rectangle.  Asynchronous on `stream`, no host synchronisation inside.
+ *   A pair of a graph whose pooled vector holds a NaN is never listed (its score is NaN, sgpr_score_pairs): at
+ *   threshold -inf exactly the pairs of two NaN-free graphs come back.  The same holds for sgpr_score_seq_above, where a
+ *   NaN score makes every Q whose diagonals all run through it NaN. */
 size_t sgpr_score_above_workspace_bytes(const sgpr_handle* h, int R, int M, int flags);
 int sgpr_score_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
                      const int32_t* d_row_self, int row0, int window, int flags, float threshold,
@@ -526,7 +541,9 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
  * - Wide-range (debug bit 13, out-of-range weights) and any-shape handles score row blocks of at most 64 MB with their
  *   own tail and run the matrix kernels on each block, row0 advancing; the blocks' counts are summed on the device.
  * - On every handle the f16-range question of a row-blocked call is answered once, over the whole rectangle, before
- *   its first block, so the values counted are sgpr_score_all_pairs' on the same rectangle. */
+ *   its first block, so the values counted are sgpr_score_all_pairs' on the same rectangle.
+ * - Every labelled pair of a graph whose pooled vector holds a NaN lands in the skipped counts (d_count[1], d_out[T+1]):
+ *   its score is NaN (sgpr_score_pairs). */
 #define SGPR_SCORE_COUNT_MAX_THRESHOLDS 2047
 size_t sgpr_score_positives_workspace_bytes(const sgpr_handle* h, int R, int M);
 int sgpr_score_positives(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -626,7 +643,8 @@ int sgpr_attention_pool_any(const float* d_weight, const float* d_emb, int B, in
                             void* stream);
 
 /* Replaces TenorNetworkModule.forward (layers_batch.py:70-83): d_weight [F3,F3,T], d_weight_block [T,2*F3],
- * d_bias [T], d_e1 / d_e2 [B,F3] -> d_out [B,T] = relu(e1^T W e2 + Wb [e1;e2] + bias).  F3 = 32, T = 16. */
+ * d_bias [T], d_e1 / d_e2 [B,F3] -> d_out [B,T] = relu(e1^T W e2 + Wb [e1;e2] + bias).  F3 = 32, T = 16.
+ * A NaN in e1 or e2 of a pair is NaN in all T outputs of that pair (the ReLU keeps a NaN); sgpr_ntn_any alike. */
 int sgpr_ntn(const float* d_weight, const float* d_weight_block, const float* d_bias, const float* d_e1,
              const float* d_e2, int64_t B, float* d_out, void* stream);
 
@@ -680,7 +698,11 @@ int sgpr_edgeconv_train_backward(const float* d_dy, const float* d_P, const floa
  * same inputs give the same bits on any stream.  1 <= G <= SGPR_TRAIN_PAIRS_MAX_GRAPHS, F <= SGPR_ANY_MAX_FILTERS_3,
  * T, H <= SGPR_ANY_MAX_NEURONS (beyond: SGPR_E_DIMS, and the workspace query answers 0); a NULL pointer or a negative
  * weight is SGPR_E_INVALID, a missing or short workspace SGPR_E_WORKSPACE; all checked before the device is touched.
- * d_workspace: sgpr_pairs_train_workspace_bytes bytes, any contents.  Handle-free; runs on the caller's current device. */
+ * d_workspace: sgpr_pairs_train_workspace_bytes bytes, any contents.  Handle-free; runs on the caller's current device.
+ * Non-finite inputs are handed on as torch's tail does, never swallowed: a NaN in d_rep[i] makes row i and column i of
+ * d_pred NaN (every other entry keeps its bits), a NaN parameter makes d_pred NaN; if a NaN d_pred entry is labelled
+ * (cls 0 / 1) the loss is NaN and every one of the eight gradients holds a non-finite value; if all of its pairs are
+ * unlabelled the loss is unaffected, while d_rep, d_W, d_V, d_fc1_w and d_fc2_w still pick the NaN up (0 x NaN). */
 #define SGPR_TRAIN_PAIRS_MAX_GRAPHS 1024
 size_t sgpr_pairs_train_workspace_bytes(int G, int F, int T, int H);
 int sgpr_pairs_train_forward(const float* d_rep, const float* d_W, const float* d_V, const float* d_b,

@@ -408,7 +408,7 @@ __device__ void pair_ntn_wg(const float* __restrict__ w, const float* __restrict
         for (int j = 0; j < F; ++j) s += prod[j * T + t];
         float blk = 0.f;
         for (int q = 0; q < 2 * F; ++q) blk = fmaf(wb[(size_t)t * 2 * F + q], se[q], blk);
-        hout[t] = fmaxf(s + blk + bias[t], 0.f);
+        hout[t] = relu_keep_nan(s + blk + bias[t]);
     }
     __syncthreads();
 }
@@ -419,7 +419,7 @@ __device__ float pair_head_wg(const GenericModel& m, const float* __restrict__ h
     for (int o = tid; o < m.B; o += TAIL_THREADS) {
         float gsum = m.fc1_b[o];
         for (int t = 0; t < m.T; ++t) gsum = fmaf(m.fc1_w[(size_t)o * m.T + t], hbuf[t], gsum);
-        gbuf[o] = fmaxf(gsum, 0.f);
+        gbuf[o] = relu_keep_nan(gsum);
     }
     __syncthreads();
     float z = 0.f;
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void generic_score_rect_kernel(const 
             }
         }
 #pragma unroll
-        for (int t = 0; t < TMAX; ++t) acc[t] = fmaxf(acc[t] + u[t], 0.f);      // (neurons >= T: 0 + 0)
+        for (int t = 0; t < TMAX; ++t) acc[t] = relu_keep_nan(acc[t] + u[t]);      // (neurons >= T: 0 + 0)
         float z = fc2b;
         for (int o = 0; o < B; ++o) {
             const float4* fp = reinterpret_cast<const float4*>(fc1 + o * TMAX);
@@ -579,7 +579,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void generic_score_rect_kernel(const 
                 gsum = fmaf(wv.z, acc[4 * t4 + 2], gsum);
                 gsum = fmaf(wv.w, acc[4 * t4 + 3], gsum);
             }
-            z = fmaf(fcb[B + o], fmaxf(gsum, 0.f), z);
+            z = fmaf(fcb[B + o], relu_keep_nan(gsum), z);
         }
         score[(size_t)r * ld + c] = 1.f / (1.f + expf(-z));
     }

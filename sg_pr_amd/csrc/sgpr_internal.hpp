@@ -420,6 +420,11 @@ __device__ __forceinline__ void tk_bounds(long long s, int window, int causal, i
     eb = (int)(b < -2 ? -2 : (b > 0x7fffffffLL ? 0x7fffffffLL : b));
 }
 
+// The ReLU of the exact fp32 tails (per-pair scoring, the f16 tails' fallback, the any-shape tail, training): fmaxf(NaN, 0)
+// is 0, which would score a graph whose pooled vector is NaN - the library's own error marker - like a healthy one.
+// A NaN stays a NaN; every other value gets fmaxf's bits.
+__device__ __forceinline__ float relu_keep_nan(float x) { return x != x ? x : fmaxf(x, 0.f); }
+
 // sgpr_knn's ranking, shared by its two instances (knn_kernel, generic_knn_kernel) so that they return the same lists:
 //   key(i, j) = |x_i|^2 - (2 x_i.x_j - |x_j|^2) = -pd[i][j],  |x|^2 = rounded squares summed in channel order,
 //   x_i.x_j = an fma chain in channel order from the rounded first product (no contraction beyond the fmaf calls)

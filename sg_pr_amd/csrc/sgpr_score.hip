@@ -54,7 +54,7 @@ __device__ __forceinline__ float ntn_neuron(const float* __restrict__ ntn_w, con
     }
     s += __shfl_xor(s, 16);
     s += __shfl_xor(s, 32);
-    return fmaxf(s + bias[t], 0.f);
+    return relu_keep_nan(s + bias[t]);
 }
 
 __global__ __launch_bounds__(256) void score_pairs_kernel(const DevWeights w, const float* __restrict__ p1,
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void score_pairs_kernel(const DevWeights w, co
     // fully_connected_first + ReLU: lane t computes output neuron t
     float gacc = w.fc1_b[t];
     for (int tt = 0; tt < T; ++tt) gacc = fmaf(w.fc1_w[t * T + tt], __shfl(h, tt), gacc);
-    float z = fmaxf(gacc, 0.f) * w.fc2_w[t];
+    float z = relu_keep_nan(gacc) * w.fc2_w[t];
     z += __shfl_xor(z, 1);
     z += __shfl_xor(z, 2);
     z += __shfl_xor(z, 4);
@@ -204,6 +204,10 @@ __device__ __forceinline__ void split3_bf16(float x, unsigned& hb, unsigned& mb,
     lb = __float_as_uint(r2);                // (the plane is the upper 16 bits of each word)
 }
 
+// max(m, |x|) of the range partials, with +infinity standing for a NaN x: fmaxf drops a NaN, and infinity fails every bound
+// of ap_mode, so a launch that met one takes the exact fp32 path (whose ReLU keeps it: relu_keep_nan)
+__device__ __forceinline__ float range_max(float m, float x) { return fmaxf(m, x != x ? INFINITY : fabsf(x)); }
+
 __device__ __forceinline__ float wave_max_f32(float v) {
     v = fmaxf(v, __shfl_xor(v, 1));
     v = fmaxf(v, __shfl_xor(v, 2));
@@ -279,7 +283,7 @@ __device__ __forceinline__ void ntn_prep_body(const DevWeights& w, const float* 
                 const int g = g0 + 4 * lq + r;
                 if (g < R) {
                     const float a = acc[r] + wbc;
-                    amax = fmaxf(amax, fabsf(a));
+                    amax = range_max(amax, a);
                     l1r[r] += fabsf(a);
                     // staged through LDS in the operand layout: the lanes hold one f16 each of a 16-byte operand unit
                     // (8 consecutive j of one (graph, plane, t)); 2-byte global stores cost the kernel a quarter of its time
@@ -331,13 +335,13 @@ __device__ __forceinline__ void ntn_prep_body(const DevWeights& w, const float* 
             s += __shfl_xor(s, 16);
             s += __shfl_xor(s, 32);
             s += w.ntn_bias[l15];
-            umax = fmaxf(umax, fabsf(s));
+            umax = range_max(umax, s);
             if (lq == 0) ur[(size_t)g * T + l15] = s;
         }
         const int msb = LIST ? M : (M + AP_SB - 1) / AP_SB * AP_SB;
         if (g < msb && lane < F) {                          // the column operand itself, two f16 planes (zeros past M)
             const float x = g < M ? cols[(size_t)g * F + lane] : 0.f;
-            emax = fmaxf(emax, fabsf(x));
+            emax = range_max(emax, x);
             _Float16 h, l;
             split2_f16(x, h, l);
             if (LIST) {
@@ -360,7 +364,8 @@ __device__ __forceinline__ void ntn_prep_body(const DevWeights& w, const float* 
             }
         }
     }
-    // NaN inputs: fmaxf drops them, so fold an explicit "not finite" marker in (infinity fails every bound)
+    // (a NaN among A', u or e2 sits in its maximum as +infinity, range_max; l1max needs none of its own: a row of A' with a
+    //  NaN has marked amax)
     amax = wave_max_f32(amax);
     umax = wave_max_f32(umax);
     emax = wave_max_f32(emax);
@@ -504,11 +509,11 @@ __device__ __forceinline__ float slow_pair(const DevWeights& w, const float* __r
     for (int m = 16 * q; m < 16 * q + 16; ++m) s = fmaf(w.ntn_wb[t * 2 * F + m], m < F ? e1[m] : e2[m - F], s);
     s += __shfl_xor(s, 16);
     s += __shfl_xor(s, 32);
-    const float h = fmaxf(s + w.ntn_bias[t], 0.f);
+    const float h = relu_keep_nan(s + w.ntn_bias[t]);
     float gacc = w.fc1_b[t];
 #pragma unroll 1
     for (int tt = 0; tt < T; ++tt) gacc = fmaf(w.fc1_w[t * T + tt], __shfl(h, tt), gacc);
-    float z = fmaxf(gacc, 0.f) * w.fc2_w[t];
+    float z = relu_keep_nan(gacc) * w.fc2_w[t];
     z += __shfl_xor(z, 1);
     z += __shfl_xor(z, 2);
     z += __shfl_xor(z, 4);
@@ -1712,6 +1717,10 @@ __global__ __launch_bounds__(256) void rows_above_kernel(const float* __restrict
 // v_mfma_f32_16x16x32_bf16 - the tail of layers_batch.py:70-83 / sg_net.py:131-136 at fp32's own operand width, as the
 // embed kernel's wide-range instance is for dgcnn_conv_pass.  Selected per handle (weights outside the f16 range) or by
 // debug bit 13, never by the data (out-of-range data keeps the exact per-pair path of score_all_pairs_kernel).
+// A launch whose range partials are not finite - a NaN or an infinity among A', u or e2 (range_max) - is scored again by
+// score_all_pairs_exact_kernel behind this one: the plane cuts, the signed-integer ReLU and the v_med3_f32 of the head
+// below do not hand a NaN on (measured: a NaN graph scored like H = 0), and this kernel has no registers left for a
+// per-pair path of its own (156 of its 168).
 //   layer 1  six significant cross products (lo.hi, hi.lo, mid.mid, mid.hi, hi.mid in a chain of their own - smallest
 //            first, never against the large accumulator -, then hi.hi on u_r), one vector add
 //   layer 2  H = relu(.) cut into three planes by truncation (upper halves of x, x - hi, x - hi - mid: same sign, so the
@@ -1883,6 +1892,29 @@ __global__ __launch_bounds__(256, APW_OCC) void score_all_pairs_wide_kernel(cons
     }
 }
 
+// Behind score_all_pairs_wide_kernel, on the same stream: nothing unless a range partial of the launch is not finite (a
+// NaN, which range_max turns into +infinity, or an infinity among A', u or e2); then the whole rectangle again in exact
+// fp32 per-pair arithmetic, which keeps a NaN (slow_pair) - the work items of the tails, AP_RW rows of a wave x AP_COLS
+// columns, grid-strided.
+__global__ __launch_bounds__(256) void score_all_pairs_exact_kernel(const DevWeights w, int R, int M,
+                                                                    const float* __restrict__ rng, int nrng,
+                                                                    const float* __restrict__ prow,
+                                                                    const float* __restrict__ pcol,
+                                                                    float* __restrict__ score, int64_t ld) {
+    float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
+    ap_range(rng, nrng, am, um, em, l1);
+    if (am < INFINITY && um < INFINITY && em < INFINITY) return;
+    const int wave = threadIdx.x >> 6;
+    const int ncc = (M + AP_COLS - 1) / AP_COLS;
+    const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const int rg = (int)(it / ncc), cc = (int)(it - (int64_t)rg * ncc);
+        const int rbase = rg * AP_ROWS + wave * AP_RW;
+        if (rbase >= R) continue;
+        slow_tile(w, prow, pcol, rbase, min(R, rbase + AP_RW), cc * AP_COLS, min(M, (cc + 1) * AP_COLS), score, ld);
+    }
+}
+
 // ntn_prep_kernel: the two-plane operands of the R x M rectangle into o, nrng prep workgroups
 static int launch_ntn_prep(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const ApOperands& o,
                            int nrng, hipStream_t stream) {
@@ -1936,6 +1968,11 @@ int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const
                            ld);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "score_all_pairs_wide_kernel launch");
+        const int64_t eslots = (int64_t)h->num_cus * AP_OCC;      // (every workgroup reads the partials, as the f16 tail's do)
+        hipLaunchKernelGGL(score_all_pairs_exact_kernel, dim3((unsigned)(items < eslots ? items : eslots)), dim3(256), 0,
+                           stream, h->w, R, M, o.rng, nrng, rows, cols, score, ld);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "score_all_pairs_exact_kernel launch");
         return SGPR_OK;
     }
     const int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);

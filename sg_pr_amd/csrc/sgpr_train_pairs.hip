@@ -160,7 +160,7 @@ __global__ __launch_bounds__(TP_THREADS) void pairs_kernel(
             const float* er = es + jl * F1;
             float a = cs[t];
             for (int g = 0; g < F; ++g) a = fmaf(As[g * T + t], er[g], a);
-            zs[e] = fmaxf(a, 0.f);
+            zs[e] = relu_keep_nan(a);
         }
         __syncthreads();
         for (int e = tid; e < nb * H; e += TP_THREADS) {
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(TP_THREADS) void pairs_kernel(
             const float* wr = w1 + h * T1;
             float a = b1[h];
             for (int t = 0; t < T; ++t) a = fmaf(wr[t], zr[t], a);
-            hs[e] = fmaxf(a, 0.f);
+            hs[e] = relu_keep_nan(a);
         }
         __syncthreads();
         if (tid < nb) {
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(TP_THREADS) void pairs_kernel(
                 pred[pi] = s;
                 if (c <= 1) {
                     const double lg = c == 1 ? log((double)s) : log(1.0 - (double)s);   // -inf at s = 0 / 1
-                    my_l += (double)w * -(lg > -100.0 ? lg : -100.0);
+                    my_l += (double)w * -(lg < -100.0 ? -100.0 : lg);   // (torch's clamp: a NaN stays a NaN)
                     my_w += (double)w;
                 }
             } else {
@@ -205,8 +205,9 @@ __global__ __launch_bounds__(TP_THREADS) void pairs_kernel(
                 dl_out[pi] = dl;
                 if (dl != 0.f) {                             // the forward's ReLU masks, for the column pass
                     unsigned long long zm = 0ull, hm = 0ull;
-                    for (int t = 0; t < T; ++t) zm |= (unsigned long long)(zs[tid * T + t] > 0.f) << t;
-                    for (int h = 0; h < H; ++h) hm |= (unsigned long long)(hs[tid * H + h] > 0.f) << h;
+                    // (!(v <= 0): v > 0 or NaN - torch's ReLU backward hands the gradient of a NaN activation on)
+                    for (int t = 0; t < T; ++t) zm |= (unsigned long long)!(zs[tid * T + t] <= 0.f) << t;
+                    for (int h = 0; h < H; ++h) hm |= (unsigned long long)!(hs[tid * H + h] <= 0.f) << h;
                     zmask[pi] = zm;
                     hmask[pi] = hm;
                 }
@@ -216,13 +217,13 @@ __global__ __launch_bounds__(TP_THREADS) void pairs_kernel(
             __syncthreads();
             for (int e = tid; e < nb * H; e += TP_THREADS) {
                 const int jl = e / H, h = e - jl * H;
-                dhs[e] = hs[e] > 0.f ? dls[jl] * w2[h] : 0.f;
+                dhs[e] = !(hs[e] <= 0.f) ? dls[jl] * w2[h] : 0.f;
             }
             __syncthreads();
             for (int e = tid; e < nb * T; e += TP_THREADS) {
                 const int jl = e / T, t = e - jl * T;
                 float a = 0.f;
-                if (zs[e] > 0.f) {
+                if (!(zs[e] <= 0.f)) {
                     const float* dr = dhs + jl * H;
                     for (int h = 0; h < H; ++h) a = fmaf(w1[h * T1 + t], dr[h], a);
                 }

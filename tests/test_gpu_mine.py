@@ -130,10 +130,13 @@ def test_class_boundaries_nan_and_short_rows(eng, world):
     rxz[6:10] = rng.uniform(-1.0, 1.0, size=(4, 2))
     rows[11] = float("nan")
     score = eng.score_all_pairs(rows, cols).cpu().numpy()
+    # the NaN graphs really are NaN in the matrix (not scored like a healthy graph upstream)
+    assert np.isnan(score[11]).all() and np.isnan(score[:, 7]).all()
     for k in (1, 4, 16):
         for positives in (False, True):
             got = eng.score_mine(rows, cols, cxz, k=k, positives=positives, row_self=torch.arange(r, dtype=torch.int32) + 120,
                                  row_pose=rxz)
+            assert (got[1][11] == -1).all() and (got[1] != 7).all()    # ... and absent from the lists
             want = _reference(score, cxz, k, positives, row_self=np.arange(r) + 120, row_xz=rxz)
             _same(got, want, ("edges", k, positives))
             assert (got[1][5] == -1).all()                             # the NaN row pose: nothing qualifies

@@ -129,6 +129,8 @@ def test_duplicates_nan_and_empty(eng):
     cols[250] = float("nan")
     rows[3] = float("nan")
     score = eng.score_all_pairs(rows, cols)
+    # the NaN graphs really are NaN in the matrix (not scored like a healthy graph upstream)
+    assert torch.isnan(score[3]).all() and torch.isnan(score[:, 250]).all()
     for r in (0, 17):
         thr = float(score[r, 7])
         for window in (-1, 10):
@@ -137,6 +139,8 @@ def test_duplicates_nan_and_empty(eng):
     assert not torch.isnan(eng.score_above(rows, cols, -INF)[2]).any()
     want = _check(eng, rows, cols, -INF, score=score)
     assert want[0].numel() == int((~torch.isnan(score)).sum())     # every pair with a non-NaN score
+    assert want[0].numel() == 39 * 299                             # = every pair of two healthy graphs, counted from the plant
+    assert (want[0] != 3).all() and (want[1] != 250).all()
     # empty shapes: R = 0, M = 0
     for r, m in ((0, 50), (5, 0), (0, 0)):
         got = eng.score_above(rows[:r].contiguous(), cols[:m].contiguous(), 0.5, window=3)

@@ -106,6 +106,10 @@ def test_ties_nan_and_short_rows(eng):
         got = score.gather(1, i.clamp(min=0).long())
         assert not torch.isnan(v).any() and not torch.isnan(got[i >= 0]).any()   # a NaN score ranks last: never reported
         assert torch.equal(got[i >= 0], v[i >= 0])
+        # the NaN graphs really are NaN in the matrix (not scored like a healthy graph upstream), and absent from the lists
+        assert torch.isnan(score[3]).all() and torch.isnan(score[:, 250]).all()
+        assert (i[3] == -1).all() and (v[3] == -float("inf")).all()
+        assert (i != 250).all()
     # fewer than k eligible columns -> (-inf, -1) in the remaining slots
     few = _pooled(6, 9)
     for k in (4, 16):

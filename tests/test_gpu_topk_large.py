@@ -143,6 +143,16 @@ def test_rows_with_fewer_eligible_columns_than_k(eng):
     _check_resident(eng, score, (1, 17, 290, 299, 300, 301, 4096), _modes(20, 300, 6), "short rows")
     v, i = eng.topk_rows_large(score, k=4096, window=50)
     assert (i[3] == -1).all() and (v[3] == -float("inf")).all()
+    # the same from pooled vectors: the NaN graphs really are NaN in the matrix, and absent from the lists
+    rows, cols = _pooled(40, 32, 3.0, 5), _pooled(300, 32, 3.0, 6)
+    cols[250] = float("nan")
+    rows[3] = float("nan")
+    pscore = eng.score_all_pairs(rows, cols)
+    assert torch.isnan(pscore[3]).all() and torch.isnan(pscore[:, 250]).all()
+    for k in (17, 300):
+        v, i = eng.score_topk_large(rows, cols, k=k)
+        assert (i[3] == -1).all() and (v[3] == -float("inf")).all()
+        assert (i != 250).all()
     # no column at all
     v, i = eng.topk_rows_large(torch.empty(3, 0, device="cuda"), k=20)
     assert (i == -1).all() and (v == -float("inf")).all()

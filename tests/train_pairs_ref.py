@@ -28,6 +28,15 @@ def pair_weights(cls, w_neg, w_pos, dtype):
     return (cls == 0).to(dtype) * w_neg + (cls == 1).to(dtype) * w_pos
 
 
+def _bce_sum(pred, y, w):
+    """Fn.binary_cross_entropy(pred, y, weight=w, reduction="sum"), written out for a pred that holds a NaN: torch's CPU
+    kernel refuses one ("all elements of input should be between 0 and 1"), its formula - the logs clamped at -100 by
+    torch.clamp, which keeps a NaN, times the weight - hands it on, as its GPU kernel does."""
+    if bool(torch.isnan(pred).any()):
+        return -(w * (y * torch.log(pred).clamp(min=-100.0) + (1.0 - y) * torch.log1p(-pred).clamp(min=-100.0))).sum()
+    return Fn.binary_cross_entropy(pred, y, weight=w, reduction="sum")
+
+
 def ref_pairs_loss(rep, cls, p, w_neg=1.0, w_pos=1.0, chunk=128, backward=False):
     """-> (loss = sum w l / sum w, pred [G,G], wsum).  backward=True also runs loss.backward() chunk by chunk (the
     gradients land in rep.grad and the parameters' .grad; the returned loss is then detached)."""
@@ -41,7 +50,7 @@ def ref_pairs_loss(rep, cls, p, w_neg=1.0, w_pos=1.0, chunk=128, backward=False)
     for r0 in range(0, g, chunk):
         rows = slice(r0, min(r0 + chunk, g))
         pred = pairs_pred(rep, p, rows)
-        part = Fn.binary_cross_entropy(pred, y[rows], weight=w[rows], reduction="sum") * scale
+        part = _bce_sum(pred, y[rows], w[rows]) * scale
         if backward:
             part.backward()
             part = part.detach()
