@@ -30,7 +30,7 @@
  *   - every entry point that takes a handle runs on the handle's device and
  *     restores the caller's current device before it returns; the handle-free
  *     entry points (sgpr_knn, sgpr_graph_feature, sgpr_attention_pool,
- *     sgpr_ntn) run on the caller's current device.
+ *     sgpr_ntn, sgpr_verify_pairs) run on the caller's current device.
  */
 #ifndef SGPR_H
 #define SGPR_H
@@ -652,6 +652,59 @@ int sgpr_ntn(const float* d_weight, const float* d_weight_block, const float* d_
  * d_weight_block [T,2F], d_bias [T], d_e1 / d_e2 [B,F] -> d_out [B,T]); plain fp32. */
 int sgpr_ntn_any(const float* d_weight, const float* d_weight_block, const float* d_bias, const float* d_e1,
                  const float* d_e2, int64_t B, int F, int T, float* d_out, void* stream);
+
+/* ---- geometric verification of loop-closure candidates --------------------------------------------
+ * Planar consensus between the labelled centres of two graphs: is the pair one place, and what is the closure edge.
+ * The reference has no such stage.  Pair p verifies row graph d_idx_a[p] of d_centers_a [GA,N,3] / d_labels_a [GA,N]
+ * against column graph d_idx_b[p] of d_centers_b / d_labels_b [GB,...] - the packed arrays sgpr_embed reads, sensor frame
+ * x forward, y left, z up; a slot with label < 0 is padding.  Every float32 operation below is rounded on its own (no
+ * fused multiply-add; division and sqrt correctly rounded), so a record is reproducible bit for bit.
+ *   hypothesis  h = (i, i', j, j'), i < i' real slots of A, j != j' real slots of B, la[i] == lb[j], la[i'] == lb[j'];
+ *               u = a[i'].xy - a[i].xy, v = b[j'].xy - b[j].xy, lu = sqrt(ux ux + uy uy), lv alike; admissible iff
+ *               lu >= min_base, lv > 0 and |lu - lv| <= tau_edge
+ *   coarse      den = lu lv, c = (ux vx + uy vy) / den, s = (ux vy - uy vx) / den, ma = 0.5 (a[i].xy + a[i'].xy), mb
+ *               alike, tx = mb.x - (c ma.x - s ma.y), ty = mb.y - (s ma.x + c ma.y)
+ *   inlier      node p of A with some q of B: la[p] == lb[q], |a[p].z - b[q].z| <= tau_z and, px = (c a[p].x - s a[p].y)
+ *               + tx, py = (s a[p].x + c a[p].y) + ty, dx = px - b[q].x, dy = py - b[q].y: dx dx + dy dy <= tau_in tau_in
+ *               (that product formed once in float32)
+ *   best        the admissible hypothesis with the most inliers, ties to the lowest (i, i', j, j'): independent of the
+ *               evaluation order
+ *   cap         base pairs (i, i') ascend lexicographically; before one is started, max_hyp admissible hypotheses already
+ *               evaluated stop the enumeration with SGPR_VERIFY_TRUNCATED; `hypotheses` = the number evaluated
+ *   refined     one least-squares step in float64 (every operation rounded on its own, sums sequential over the inliers
+ *               p ascending) on the matches q(p) = the qualifying q with the smallest dx dx + dy dy, ties to the lowest
+ *               q: ca, cb the means, D = sum(ax~ bx~ + ay~ by~), X = sum(ax~ by~ - ay~ bx~) over the centred
+ *               coordinates, nrm = sqrt(D D + X X), c = D / nrm, s = X / nrm, tx = cb.x - (c ca.x - s ca.y), ty = cb.y -
+ *               (s ca.x + c ca.y); fewer than 2 inliers or nrm == 0: the coarse transform widened.  rmse = sqrt(sum r^2 /
+ *               n) over the matches under it (NaN without a match); inliers_refined = the inlier count under the refined
+ *               transform rounded to float32.
+ * Flags: SGPR_VERIFY_NO_HYPOTHESIS (none admissible) and SGPR_VERIFY_NONFINITE (a real node of either graph has a NaN
+ * or infinite coordinate; the pair is not evaluated) leave inliers 0, base -1, hypotheses 0 and NaN transforms / rmse;
+ * an index outside its graph set, negative included (the -1 padding of a top-k list), gives an all-zero record with
+ * SGPR_VERIFY_INVALID_INDEX and touches nothing else.  Every byte of every record is written; results depend on the
+ * arguments alone.  Checked before the device is touched: a NULL pointer (P > 0), P < 0, GA or GB < 0, a negative or
+ * NaN tolerance or max_hyp < 1 give SGPR_E_INVALID, N outside 1..SGPR_VERIFY_MAX_NODES SGPR_E_NODES; P == 0 succeeds
+ * without a launch.  One workgroup per pair, no workspace, no atomics on global memory; work per pair is about
+ * hypotheses x same-label correspondences, and a single base pair adds at most nB^2 hypotheses past the cap.
+ * Handle-free; runs on the caller's current device, asynchronous on `stream`. */
+typedef struct sgpr_verify_result {   /* 88 bytes */
+    int32_t inliers, inliers_refined;
+    int32_t base[4];                  /* i, i', j, j' (slot indices) */
+    uint32_t hypotheses, flags;
+    float coarse[4];                  /* c, s, tx, ty */
+    double refined[4];
+    double rmse;
+} sgpr_verify_result;
+#define SGPR_VERIFY_MAX_NODES 256
+#define SGPR_VERIFY_INVALID_INDEX 1
+#define SGPR_VERIFY_NO_HYPOTHESIS 2
+#define SGPR_VERIFY_TRUNCATED 4
+#define SGPR_VERIFY_NONFINITE 8
+int sgpr_verify_pairs(const float* d_centers_a, const int32_t* d_labels_a, int GA,
+                      const float* d_centers_b, const int32_t* d_labels_b, int GB, int N,
+                      const int32_t* d_idx_a, const int32_t* d_idx_b, int64_t P,
+                      float tau_edge, float tau_in, float tau_z, float min_base, int max_hyp,
+                      sgpr_verify_result* d_out, void* stream);
 
 /* ---- training: one EdgeConv block with BatchNorm in train mode ---------------------------
  * Replaces, for training, get_graph_feature -> Conv2d 1x1 -> BatchNorm2d (batch statistics) -> LeakyReLU(0.2) -> max

@@ -2255,6 +2255,34 @@ int sgpr_ntn(const float* d_weight, const float* d_weight_block, const float* d_
     return launch_ntn(d_weight, d_weight_block, d_bias, d_e1, d_e2, B, d_out, static_cast<hipStream_t>(stream));
 }
 
+int sgpr_verify_pairs(const float* d_centers_a, const int32_t* d_labels_a, int GA, const float* d_centers_b,
+                      const int32_t* d_labels_b, int GB, int N, const int32_t* d_idx_a, const int32_t* d_idx_b, int64_t P,
+                      float tau_edge, float tau_in, float tau_z, float min_base, int max_hyp, sgpr_verify_result* d_out,
+                      void* stream) {
+    static_assert(sizeof(sgpr_verify_result) == 88, "sgpr_verify_result is 88 bytes without padding");
+    if (P < 0 || GA < 0 || GB < 0) {
+        set_error("sgpr_verify_pairs: negative count");
+        return SGPR_E_INVALID;
+    }
+    // (a NaN fails every >= test)
+    if (!(tau_edge >= 0.f) || !(tau_in >= 0.f) || !(tau_z >= 0.f) || !(min_base >= 0.f) || max_hyp < 1) {
+        set_error("sgpr_verify_pairs: tolerances must be >= 0 and not NaN, max_hyp >= 1");
+        return SGPR_E_INVALID;
+    }
+    if (N < 1 || N > SGPR_VERIFY_MAX_NODES) {
+        set_error("sgpr_verify_pairs: N " + std::to_string(N) + " outside [1, " + std::to_string(SGPR_VERIFY_MAX_NODES) + "]");
+        return SGPR_E_NODES;
+    }
+    // (an empty list may come with NULL: the data pointer of an empty torch tensor)
+    if (P > 0 && (!d_idx_a || !d_idx_b || !d_out || !d_centers_a || !d_labels_a || !d_centers_b || !d_labels_b)) {
+        set_error("sgpr_verify_pairs: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (P == 0) return SGPR_OK;
+    return launch_verify_pairs(d_centers_a, d_labels_a, GA, d_centers_b, d_labels_b, GB, N, d_idx_a, d_idx_b, P, tau_edge,
+                               tau_in, tau_z, min_base, max_hyp, d_out, static_cast<hipStream_t>(stream));
+}
+
 size_t sgpr_cluster_workspace_bytes(int P) { return P < 0 ? 0 : cluster_ws_bytes(P); }
 
 int sgpr_cluster_scan(const float* d_points, int point_stride, const uint32_t* d_labels, int P, int max_nodes,

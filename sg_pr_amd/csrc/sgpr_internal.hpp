@@ -398,6 +398,11 @@ int launch_knn(const float* x, int B, int C, int N, int k, int64_t* idx, hipStre
 int launch_graph_feature(const float* x, const int64_t* idx, int B, int C, int N, int k, float* out, hipStream_t stream);
 int launch_attention_pool(const float* w, const float* emb, int B, int N, float* rep, float* att, hipStream_t stream);
 
+// geometric verification of P candidate pairs, one workgroup each (sgpr_verify.hip); arguments already checked
+int launch_verify_pairs(const float* ca, const int32_t* la, int GA, const float* cb, const int32_t* lb, int GB, int N,
+                        const int32_t* ia, const int32_t* ib, int64_t P, float tau_edge, float tau_in, float tau_z,
+                        float min_base, int max_hyp, sgpr_verify_result* out, hipStream_t stream);
+
 size_t size_order_ws_bytes(int G);
 int launch_size_order(const float* centers, const int32_t* labels, const long long* rag_off, int G, int N, int k,
                       int num_labels, int32_t* order, int32_t* info, void* ws, hipStream_t stream);

@@ -55,7 +55,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_score_seq_positives_workspace_bytes", "sgpr_score_seq_positives",
                "sgpr_score_seq_threshold_counts_workspace_bytes", "sgpr_score_seq_threshold_counts",
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
-               "sgpr_attention_pool_any", "sgpr_ntn_any",
+               "sgpr_attention_pool_any", "sgpr_ntn_any", "sgpr_verify_pairs",
                "sgpr_edgeconv_train_workspace_bytes", "sgpr_edgeconv_train_forward", "sgpr_edgeconv_train_backward",
                "sgpr_pairs_train_workspace_bytes", "sgpr_pairs_train_forward", "sgpr_pairs_train_backward",
                "sgpr_cluster_workspace_bytes", "sgpr_cluster_scan", "sgpr_graph_edges",
@@ -256,6 +256,9 @@ def load_library():
     lib.sgpr_attention_pool_any.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.sgpr_ntn_any.restype = i32
     lib.sgpr_ntn_any.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]
+    lib.sgpr_verify_pairs.restype = i32
+    f32 = ctypes.c_float
+    lib.sgpr_verify_pairs.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, i64, f32, f32, f32, f32, i32, vp, vp]
     lib.sgpr_edgeconv_train_workspace_bytes.restype = sz
     lib.sgpr_edgeconv_train_workspace_bytes.argtypes = [i32, i32]
     lib.sgpr_edgeconv_train_forward.restype = i32
@@ -1547,6 +1550,60 @@ def ntn(weight, weight_block, bias, e1, e2):
     with torch.cuda.device(e1.device):
         _raise_if(lib, lib.sgpr_ntn(_ptr(w), _ptr(wb), _ptr(bs), _ptr(e1), _ptr(e2), b, _ptr(out), _stream_of(e1)))
     return out[:, :t]
+
+
+# struct sgpr_verify_result of include/sgpr.h (88 bytes, no padding) and its flag bits
+VERIFY_RESULT = np.dtype([("inliers", "<i4"), ("inliers_refined", "<i4"), ("base", "<i4", (4,)), ("hypotheses", "<u4"),
+                          ("flags", "<u4"), ("coarse", "<f4", (4,)), ("refined", "<f8", (4,)), ("rmse", "<f8")])
+VERIFY_MAX_NODES = 256
+VERIFY_INVALID_INDEX, VERIFY_NO_HYPOTHESIS, VERIFY_TRUNCATED, VERIFY_NONFINITE = 1, 2, 4, 8
+
+
+def _verify_graphs(centers, labels, device, name):
+    c = torch.as_tensor(centers).to(device=device, dtype=torch.float32).contiguous()
+    lab = torch.as_tensor(labels).to(device=device, dtype=torch.int32).contiguous()
+    if c.dim() != 3 or c.shape[2] != 3 or tuple(lab.shape) != tuple(c.shape[:2]):
+        raise ValueError("%s: centers [G, N, 3] and labels [G, N]" % name)
+    return c, lab
+
+
+def verify_pairs(centers_a, labels_a, centers_b, labels_b, idx_a, idx_b, tau_edge=0.5, tau_inlier=0.6, tau_z=1.0,
+                 min_base=5.0, max_hyp=65536, device=None):
+    """sgpr_verify_pairs: geometric verification of the candidate pairs (idx_a[p], idx_b[p]) - planar consensus between
+    the labelled centres of row graph idx_a[p] of (centers_a [GA,N,3], labels_a [GA,N]) and column graph idx_b[p] of
+    (centers_b, labels_b).  Returns a dict of device tensors, one per field of the record (inliers, inliers_refined i32
+    [P]; base i32 [P,4]; hypotheses i64 [P]; flags i32 [P]; coarse f32 [P,4]; refined f64 [P,4]; rmse f64 [P]), plus
+    yaw = atan2(s, c) of the refined transform (f64 [P], radians) and record, the raw bytes u8 [P,88]
+    (VERIFY_RESULT).  An index outside its graph set (-1: a padding slot of a top-k list) gives a zeroed record with
+    VERIFY_INVALID_INDEX.  Asynchronous on the current stream."""
+    lib = load_library()
+    if device is None:
+        device = next((t.device for t in (centers_a, centers_b, idx_a, idx_b) if isinstance(t, torch.Tensor) and t.is_cuda),
+                      torch.device("cuda", torch.cuda.current_device()))
+    ca, la = _verify_graphs(centers_a, labels_a, device, "row graphs")
+    cb, lb = _verify_graphs(centers_b, labels_b, device, "column graphs")
+    if ca.shape[1] != cb.shape[1]:
+        raise ValueError("verify_pairs: both graph sets must have the same number of slots per graph")
+    ia = torch.as_tensor(idx_a).to(device=device, dtype=torch.int32).contiguous().view(-1)
+    ib = torch.as_tensor(idx_b).to(device=device, dtype=torch.int32).contiguous().view(-1)
+    if ia.numel() != ib.numel():
+        raise ValueError("verify_pairs: idx_a and idx_b must have the same length")
+    p = ia.numel()
+    rec = torch.empty(p, VERIFY_RESULT.itemsize, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _raise_if(lib, lib.sgpr_verify_pairs(_ptr(ca), _ptr(la), ca.shape[0], _ptr(cb), _ptr(lb), cb.shape[0], ca.shape[1],
+                                             _ptr(ia), _ptr(ib), p, float(tau_edge), float(tau_inlier), float(tau_z),
+                                             float(min_base), int(max_hyp), _ptr(rec), _stream_of(rec)))
+    return verify_fields(rec)
+
+
+def verify_fields(rec):
+    """The fields of sgpr_verify_result records (u8 [P,88] on any device) as tensors + yaw of the refined transform."""
+    i32, f32v, f64v = rec.view(torch.int32), rec.view(torch.float32), rec.view(torch.float64)
+    refined = f64v[:, 6:10]
+    return {"inliers": i32[:, 0], "inliers_refined": i32[:, 1], "base": i32[:, 2:6],
+            "hypotheses": i32[:, 6].to(torch.int64) & 0xffffffff, "flags": i32[:, 7], "coarse": f32v[:, 8:12],
+            "refined": refined, "rmse": f64v[:, 10], "yaw": torch.atan2(refined[:, 1], refined[:, 0]), "record": rec}
 
 
 def cluster_scan(points, labels, max_nodes=1024, want_point_node=False):

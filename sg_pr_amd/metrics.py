@@ -408,3 +408,36 @@ def precision_recall_at(rows, cols, pose_xz, p_thresh=3.0, n_thresh=20.0, window
     precision = tp / (tp + fp) if tp + fp else 0.0
     recall = tp / positives if positives else 0.0
     return precision, recall
+
+
+def closure_pose_errors(results, rows, cols, poses):
+    """Yaw and translation error of verified closures (engine.verify_pairs / SG.verify_closures) against ground-truth
+    poses.  results: the dict of fields (or anything with "refined" [..., 4] = c, s, tx, ty and "flags"), rows / cols:
+    the row and column frame of every pair, same leading shape; poses [M, 12]: KITTI 3x4 rows as synth.world_sequence
+    and the graph store hold them - x = p[3], z = p[11], and the sensor's x axis (forward; y is left) points along
+    (p[0], p[2]) in the world's (x, z) plane.  The refined transform maps a point of the row scan into the column scan:
+    b = R(yaw) a + t, so the truth is yaw = heading(row) - heading(col), t = R(-heading(col)) (xz(row) - xz(col)).
+    A pair without a transform (flags INVALID_INDEX / NO_HYPOTHESIS / NONFINITE) gets NaN errors.
+    -> dict: yaw_deg, trans_m (float64 numpy, the pairs' shape), median_yaw_deg, median_trans_m (NaN-ignoring; NaN when
+    no pair has a transform)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+    ref = host(results["refined"]).astype(np.float64)
+    flags = host(results["flags"]).astype(np.int64)
+    rows, cols = host(rows).astype(np.int64), host(cols).astype(np.int64)
+    poses = np.asarray(host(poses), dtype=np.float64).reshape(-1, 12)
+    ok = ((flags & (1 | 2 | 8)) == 0) & (rows >= 0) & (cols >= 0)
+    r, c = np.where(ok, rows, 0), np.where(ok, cols, 0)
+    head = np.arctan2(poses[:, 2], poses[:, 0])
+    dx, dz = poses[r, 3] - poses[c, 3], poses[r, 11] - poses[c, 11]
+    cb, sb = np.cos(head[c]), np.sin(head[c])
+    tx, ty = cb * dx + sb * dz, -sb * dx + cb * dz
+    yaw = np.arctan2(ref[..., 1], ref[..., 0])
+    dyaw = yaw - (head[r] - head[c])
+    dyaw = np.abs((dyaw + np.pi) % (2.0 * np.pi) - np.pi)
+    yaw_deg = np.where(ok, np.degrees(dyaw), np.nan)
+    trans = np.where(ok, np.hypot(ref[..., 2] - tx, ref[..., 3] - ty), np.nan)
+    some = bool(np.isfinite(yaw_deg).any())
+    return {"yaw_deg": yaw_deg, "trans_m": trans,
+            "median_yaw_deg": float(np.nanmedian(yaw_deg)) if some else float("nan"),
+            "median_trans_m": float(np.nanmedian(trans)) if some else float("nan")}

@@ -17,6 +17,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
 
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
+                                            [--verify] [--min-inliers I]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -29,7 +30,12 @@ sequence-matched score (the mean along the diagonal of the last L frames of both
 --seq-reverse: forward diagonals only (off), reverse only (on) or the larger of both, the default) and the file adds
 seq_len and dirs [M,K] (0 forward, 1 reverse).  With --threshold and --seq-len L > 1 also `<seq>_seq_above.npz`: every
 pair whose sequence-matched score is >= T (rows, cols, scores, dirs, precision, recall, seq_len; Engine.score_seq_above);
-`<seq>_above.npz` stays the single-scan result.
+`<seq>_above.npz` stays the single-scan result.  With --verify the retrieved lists are verified geometrically on the
+packed graphs (SG.verify_closures: planar consensus of the labelled centres, engine.verify_pairs): `<seq>_verify.npz` holds
+per list slot inliers, inliers_refined, flags, refined [M,K,4] (c, s, tx, ty: row scan -> column scan), yaw, rmse, the
+re-ranked lists indices_ranked (refined inliers descending, then score, then column) and accept (inliers_refined >=
+--min-inliers, default 12); printed are recall@1 before and after re-ranking, the precision of the accepted closures
+and the median yaw / translation error of the accepted true closures against the poses.
 """
 import argparse
 import hashlib
@@ -206,6 +212,10 @@ def main(argv=None):
                     help="rank the sequence-matched score: the mean along the last L frames of both trajectories (1..32)")
     ap.add_argument("--seq-reverse", choices=("off", "on", "both"), default="both",
                     help="with --seq-len: forward diagonals only (off), reverse only (on) or the larger of both")
+    ap.add_argument("--verify", action="store_true",
+                    help="verify the retrieved lists geometrically, re-rank them by inliers and write <seq>_verify.npz")
+    ap.add_argument("--min-inliers", type=int, default=12, metavar="I",
+                    help="with --verify: accept a closure with at least I refined inliers")
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if not 1 <= opt.seq_len <= _engine.Engine.SEQ_MAX_LEN:
         ap.error("--seq-len must lie in 1..%d" % _engine.Engine.SEQ_MAX_LEN)
@@ -248,6 +258,15 @@ def main(argv=None):
             print("sequence", sequence, "recall@%g%% (N = %d) %.4f" % (opt.recall_percent, extra["recall_percent_n"],
                                                                        extra["recall_percent"]))
         results[sequence] = recall
+        if opt.verify:
+            report = verify_lists(trainer.model, seq, vals, idx, opt.min_inliers, float(args.p_thresh), window=opt.window,
+                                  causal=opt.causal)
+            np.savez(os.path.join(args.output_path, sequence + "_verify.npz"), frame=np.arange(m), **report)
+            print("sequence", sequence, "verified", int(report["verified"]), "candidates, recall@1 %.4f -> %.4f re-ranked,"
+                  % (recall[0], report["recall_ranked"][0]), "accepted", int(report["accept"].sum()),
+                  "(>= %d inliers) precision %.4f," % (opt.min_inliers, report["precision"]),
+                  "accepted true closures %d: median yaw error %.3f deg, median translation error %.3f m"
+                  % (int(report["true_accepted"]), report["median_yaw_deg"], report["median_trans_m"]))
         if opt.threshold is not None:
             rows, cols, scores, _ = db.query_ids_above(torch.arange(m), opt.threshold, window=opt.window,
                                                        causal=opt.causal)
@@ -274,6 +293,35 @@ def main(argv=None):
             print("sequence", sequence, "hard pairs k", opt.hard, "frames with a negative above their best positive",
                   int(hard["neg_above_pos"].sum()), "(exact: %d frames of %d)" % (int(hard["exact"].sum()), m))
     return results
+
+
+def verify_lists(model, seq, values, indices, min_inliers, p_thresh, window=-1, causal=False):
+    """Geometric verification of retrieved lists (values / indices [M,K] of the frames of `seq` against themselves) ->
+    dict of numpy arrays: the per-slot fields, indices_ranked, accept, recall_ranked [K] (recall@1..K of the re-ranked
+    lists), precision of the accepted closures (metrics.precision_recall_at's classes), true_accepted = the accepted
+    closures within p_thresh and the median yaw / translation error of those (metrics.closure_pose_errors; 0 when there
+    is none)."""
+    ver = model.verify_closures(seq.centers, seq.labels, indices, values=values, min_inliers=min_inliers)
+    idx = torch.as_tensor(indices).to(ver["accept"].device)
+    m, k = idx.shape
+    rows = torch.arange(m, device=idx.device)[:, None].expand(m, k)
+    acc = ver["accept"]
+    arows, acols = rows[acc], idx[acc].long()
+    precision = metrics.precision_recall_at(arows, acols, seq.poses, p_thresh=p_thresh, window=window, causal=causal)[0]
+    err = metrics.closure_pose_errors({"refined": ver["refined"][acc], "flags": ver["flags"][acc]}, arows, acols, seq.poses)
+    from .allpairs import pose_xz
+    xz = pose_xz(seq.poses).to(device=idx.device, dtype=torch.float64)
+    true = (((xz[arows] - xz[acols]) ** 2).sum(dim=1) <= p_thresh * p_thresh).cpu().numpy()
+    yaw, trans = err["yaw_deg"][true], err["trans_m"][true]
+    out = {name: ver[name].cpu().numpy() for name in ("inliers", "inliers_refined", "flags", "refined", "yaw", "rmse",
+                                                      "indices_ranked", "accept")}
+    out.update({"recall_ranked": metrics.recall_at_n(ver["indices_ranked"], seq.poses, p_thresh=p_thresh, window=window,
+                                                     causal=causal),
+                "verified": np.int64(int((idx >= 0).sum())), "precision": np.float64(precision),
+                "true_accepted": np.int64(int(true.sum())),
+                "median_yaw_deg": np.float64(np.median(yaw) if yaw.size else 0.0),
+                "median_trans_m": np.float64(np.median(trans) if trans.size else 0.0)})
+    return out
 
 
 def hard_pairs_of(db, poses, k, p_thresh, window=-1, causal=False):

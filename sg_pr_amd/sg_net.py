@@ -158,6 +158,39 @@ class SG(torch.nn.Module):
         return self.engine().score_topk(pooled_rows, pooled_cols, k=k, window=window, row0=row0, causal=causal,
                                         row_self=row_self)
 
+    def verify_closures(self, centers, labels, indices, values=None, min_inliers=None, col_centers=None, col_labels=None,
+                        **tolerances):
+        """Geometric verification of candidate lists (engine.verify_pairs): indices [R,k] as every
+        loop_closures* call returns them - row r lists column graphs for row graph r of (centers [R,N,3], labels [R,N]);
+        the columns index (col_centers, col_labels), by default the row graphs themselves.  A -1 padding slot is
+        skipped: its fields are zero and its flags VERIFY_INVALID_INDEX.
+        -> dict of device tensors: every field of engine.verify_pairs shaped [R,k,...]; order i64 [R,k] = the slots of
+        each row re-ranked by (refined inliers descending, score descending, column ascending; padding last; values
+        None: all scores equal) and indices_ranked = the columns in that order; with min_inliers also accept bool
+        [R,k] = inliers_refined >= min_inliers (never a padding slot).  tolerances: tau_edge, tau_inlier, tau_z,
+        min_base, max_hyp."""
+        dev = self.engine().device
+        idx = torch.as_tensor(indices).to(device=dev, dtype=torch.int32)
+        if idx.dim() != 2:
+            raise ValueError("verify_closures: indices must be [R, k]")
+        r, k = idx.shape
+        rows = torch.arange(r, dtype=torch.int32, device=dev).repeat_interleave(k)
+        cc, cl = (centers, labels) if col_centers is None else (col_centers, col_labels)
+        flat = _engine.verify_pairs(centers, labels, cc, cl, rows, idx.reshape(-1), device=dev, **tolerances)
+        out = {name: t.reshape((r, k) + tuple(t.shape[1:])) for name, t in flat.items()}
+        valid = idx >= 0
+        order = torch.argsort(torch.where(valid, idx, torch.full_like(idx, 0x7fffffff)), dim=1, stable=True)
+        if values is not None:
+            score = torch.as_tensor(values).to(device=dev, dtype=torch.float32).reshape(r, k)
+            order = order.gather(1, torch.argsort(-score.gather(1, order), dim=1, stable=True))
+        inl = torch.where(valid, out["inliers_refined"], torch.full_like(idx, -1))
+        order = order.gather(1, torch.argsort(-inl.gather(1, order), dim=1, stable=True))
+        out["order"] = order
+        out["indices_ranked"] = idx.gather(1, order)
+        if min_inliers is not None:
+            out["accept"] = valid & (out["inliers_refined"] >= int(min_inliers))
+        return out
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming
