@@ -437,6 +437,47 @@ int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R,
                         float* d_values, int32_t* d_indices, unsigned char* d_dirs, void* d_workspace,
                         size_t workspace_bytes, void* stream);
 
+/* Distinct-place loop closures: per-row score peaks within a scan radius.  A trajectory revisits a place over many
+ * consecutive scans, so the k best columns of a row are mostly one place seen k times.  With X the ranked score (S of
+ * sgpr_score_all_pairs, or Q above), a column QUALIFIES for row r iff it is eligible (sgpr_score_topk's rule: window,
+ * SGPR_TOPK_CAUSAL, self_r = d_row_self[r] or row0 + r) and X[r, c] is neither NaN nor -inf (+inf qualifies);
+ * qualifying columns are ordered as sgpr_topk_rows_large lists them (value descending by IEEE comparison, -0.0 ties
+ * +0.0, then column ascending).  For a radius rho in 0..SGPR_PEAK_MAX_RADIUS:
+ *     column c is a PEAK of row r iff it qualifies and it comes first, in that order, among the qualifying columns c'
+ *     with |c' - c| <= rho.
+ * - Two peaks of a row are more than rho columns apart; the best qualifying column of a row is always a peak; rho = 0
+ *   makes every qualifying column a peak.
+ * - A column that does not qualify (ineligible, NaN, -inf) neither is a peak nor suppresses anything.  A causal query
+ *   that knows only the columns c < self_r therefore gets the lists of the offline call.  The first eligible column
+ *   beside an excluded window can be a peak of a slope that rises into the window: choose rho <= window.
+ * - On a plateau of equal values longer than rho only its first column is a peak ("first in its neighbourhood", not
+ *   "not beaten by a peak").
+ * - Each row is independent of every other row, and nothing depends on an evaluation order.
+ * - sgpr_peak_filter: a resident block d_score [R][ld] -> d_out [R][ldo] (ld, ldo >= M): X[r, c] (the stored bits) at
+ *   a peak, -inf elsewhere; every entry of [R][M] is written, nothing beyond column M.  Out of place: d_out overlapping
+ *   d_score is undefined.  No workspace.  One workgroup per strip of SGPR_PEAK_STRIP columns of a row (sgpr_peak.hip,
+ *   DESIGN.md §20).  An entry of d_row_self outside [0, M) only moves the window; the selections report it.
+ * - sgpr_score_peak_topk: sgpr_score_seq_topk's arguments and rules (a direction flag is required, the first ctx rows
+ *   are context only, d_dirs may be NULL, every handle, row blocks of at most 64 MB, the f16-range question answered
+ *   once per call) plus `radius`: for every row r >= ctx the k (1..SGPR_TOPK_LARGE_MAX) best PEAKS of Q (L = 1: of S
+ *   itself) in list order, (-inf, -1) in the slots past the last peak.  Each block is scored, filtered along the
+ *   diagonals (L > 1), peak-filtered into a P block and selected from it; the workspace is sgpr_score_seq_topk's plus
+ *   that P block, never R * M.  radius = 0 returns the bits of sgpr_score_seq_topk.
+ * Arguments are checked before the device is touched: sgpr_score_seq_topk's, and a radius outside
+ * 0..SGPR_PEAK_MAX_RADIUS gives SGPR_E_INVALID; a workspace below the _workspace_bytes answer SGPR_E_WORKSPACE (which is
+ * 0 for invalid arguments).  R == ctx or M == 0 writes padding lists without scoring.  Results depend on the arguments
+ * alone.  Asynchronous on `stream`. */
+#define SGPR_PEAK_MAX_RADIUS 1024
+#define SGPR_PEAK_STRIP 1024
+int sgpr_peak_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, const int32_t* d_row_self,
+                     int row0, int window, int flags, int radius, float* d_out, int64_t ldo, void* stream);
+size_t sgpr_score_peak_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int radius,
+                                            int flags);
+int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L, int radius, int k,
+                         float* d_values, int32_t* d_indices, unsigned char* d_dirs, void* d_workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* Hard-pair mining without the R x M matrix: for every row r the k (1..16) hardest pose-labelled pairs (r, c) of the
  * rectangle d_pooled_rows [R] x d_pooled_cols [M].
  * - Column c is eligible for row r iff it is for sgpr_score_topk (window, SGPR_TOPK_CAUSAL, self_r = d_row_self[r] or

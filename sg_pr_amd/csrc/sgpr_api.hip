@@ -1486,6 +1486,119 @@ int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R,
                             workspace_bytes, stream, select, crng, L - 1);
 }
 
+// ---- sgpr_peak_filter / sgpr_score_peak_topk: per-row score peaks within a scan radius (sgpr_peak.hip) on a resident
+//      block, and on sgpr_score_seq_topk's row blocks: score, diagonal filter (L > 1), peak filter into a P block, the
+//      large-k selection on P.  Rows are independent, so the peak step needs no context rows of its own
+static bool peak_radius_ok(const char* fn, int radius) {
+    if (radius < 0 || radius > SGPR_PEAK_MAX_RADIUS) {
+        set_error(std::string(fn) + ": the radius must lie in 0.." + std::to_string(SGPR_PEAK_MAX_RADIUS));
+        return false;
+    }
+    return true;
+}
+
+int sgpr_peak_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, const int32_t* d_row_self,
+                     int row0, int window, int flags, int radius, float* d_out, int64_t ldo, void* stream) {
+    if (!h || R < 0 || M < 0 || ld < M || ldo < M || window < -1) {
+        set_error("sgpr_peak_filter: NULL handle, negative size, leading dimension below M or window below -1");
+        return SGPR_E_INVALID;
+    }
+    if (flags & ~SGPR_TOPK_CAUSAL) {
+        set_error("sgpr_peak_filter: unknown flag bits " + std::to_string(flags & ~SGPR_TOPK_CAUSAL));
+        return SGPR_E_INVALID;
+    }
+    if (!peak_radius_ok("sgpr_peak_filter", radius) || !row0_ok("sgpr_peak_filter", row0, R)) return SGPR_E_INVALID;
+    if (R > 0 && M > 0 && (!d_score || !d_out)) {          // (an empty result needs no buffers)
+        set_error("sgpr_peak_filter: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (R == 0 || M == 0) return SGPR_OK;
+    DeviceGuard guard(h->device);
+    return launch_peak_filter(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, radius,
+                              d_out, ldo, static_cast<hipStream_t>(stream));
+}
+
+// head of sgpr_score_peak_topk: the call's f16 range (a float4) | the selection's workspace for one block | P block
+// [rb][M] | L > 1: Q block [rb][M] | L > 1, both directions: dir block [rb][M]
+static size_t peak_head_bytes(int R, int M, int L, int flags) {
+    const size_t rb = (size_t)score_block_rows(R, M, L - 1);
+    return 256 + a256(select_ws_bytes((int)rb, M)) + a256(rb * M * sizeof(float)) +
+           (L > 1 ? a256(rb * M * sizeof(float)) + (seq_both(flags) ? a256(rb * M) : 0) : 0);
+}
+
+size_t sgpr_score_peak_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int radius,
+                                            int flags) {
+    if (!h || R < 0 || M < 0 || k < 1 || k > SGPR_TOPK_LARGE_MAX || L < 1 || L > SGPR_SEQ_MAX_LEN || ctx < 0 || ctx > R ||
+        radius < 0 || radius > SGPR_PEAK_MAX_RADIUS || (flags & ~kSeqFlags) ||
+        !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
+        return 0;
+    if (R == ctx || M == 0) return 0;
+    return row_blocks_ws_bytes(h, R, M, peak_head_bytes(R, M, L, flags), L - 1);
+}
+
+int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L, int radius, int k,
+                         float* d_values, int32_t* d_indices, unsigned char* d_dirs, void* d_workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!h || R < 0 || M < 0) {
+        set_error("sgpr_score_peak_topk: NULL handle or negative count");
+        return SGPR_E_INVALID;
+    }
+    if (!seq_args_ok("sgpr_score_peak_topk", R, ctx, L, flags, kSeqFlags)) return SGPR_E_INVALID;
+    if (!peak_radius_ok("sgpr_score_peak_topk", radius)) return SGPR_E_INVALID;
+    if ((R > ctx && (!d_values || !d_indices)) || (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols))) {
+        set_error("sgpr_score_peak_topk: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (!topk_large_args_ok("sgpr_score_peak_topk", R, k, flags & SGPR_TOPK_CAUSAL, row0)) return SGPR_E_INVALID;
+    if (!workspace_ok("sgpr_score_peak_topk", sgpr_score_peak_topk_workspace_bytes(h, R, M, ctx, L, k, radius, flags),
+                      d_workspace, workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    if (R == ctx) return SGPR_OK;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_dir = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0) {
+        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, window,
+                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
+        if (rc != SGPR_OK || !d_dirs) return rc;
+        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_dir, d_dirs, s);
+    }
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    int clean_rows = 0;                                   // histogram rows the selection before left clear
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0), no = r0 + n - first;
+        float* p = reinterpret_cast<float*>(head + 256 + sel_bytes);
+        const float* x = block + (size_t)(first - r0) * M;   // L = 1: the ranked score is S itself (S * rcp[1] is S)
+        unsigned char* dir = nullptr;
+        int rc;
+        if (L > 1) {
+            float* q = reinterpret_cast<float*>(head + 256 + sel_bytes + blk_bytes);
+            dir = seq_both(flags) ? head + 256 + sel_bytes + 2 * blk_bytes : nullptr;
+            rc = launch_seq_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, q, M, dir, M, s);
+            if (rc != SGPR_OK) return rc;
+            x = q;
+        }
+        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
+        rc = launch_peak_filter(x, no, M, M, rs, row0 + first, window, causal, radius, p, M, s);
+        if (rc != SGPR_OK) return rc;
+        const size_t o = (size_t)(first - ctx) * k;
+        rc = launch_select_rows(p, no, M, M, rs, row0 + first, window, causal, k, d_values + o, d_indices + o, head + 256,
+                                select_group_rows(no) <= clean_rows, h->d_status, s);
+        clean_rows = select_group_rows(no);
+        if (rc != SGPR_OK || !d_dirs) return rc;
+        // (L = 1, both directions: the two sums are one number and forward wins the tie - direction 0, as fixed_dir says)
+        return launch_seq_dirs(d_indices + o, no, k, dir, M, fixed_dir, d_dirs + o, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, peak_head_bytes(R, M, L, flags), d_workspace,
+                            workspace_bytes, stream, select, crng, L - 1);
+}
+
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks
 //      and sgpr_mine_rows' kernel on the others) with the pose-class condition of the mined pairs
 static const int kMineFlags = SGPR_TOPK_CAUSAL | SGPR_MINE_NEGATIVES | SGPR_MINE_POSITIVES;

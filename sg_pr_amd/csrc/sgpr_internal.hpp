@@ -318,6 +318,10 @@ int launch_seq_filter(const float* score, int R, int M, int64_t ld, int ctx, int
 // out [n][k] = dir [n][ld] at the selected columns idx [n][k] (dir == nullptr: `fixed`); 0 where idx is -1
 int launch_seq_dirs(const int32_t* idx, int n, int k, const unsigned char* dir, int64_t ld, int fixed,
                     unsigned char* out, hipStream_t stream);
+// the peak filter of a resident n x M block (sgpr_peak.hip): out [n][ldo] = score at a peak within `radius` columns, -inf
+// elsewhere; eligibility as launch_select_rows (row_self [n] / row0 belong to the block's row 0)
+int launch_peak_filter(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
+                       int causal, int radius, float* out, int64_t ldo, hipStream_t stream);
 // sgpr_score_mine on the production handle (positives: SGPR_MINE_POSITIVES, else the negatives) and its selection on a
 // resident block (sgpr_mine_rows, the chunked path of the other handles; sgpr_metrics.hip)
 size_t score_mine_ws_bytes(const sgpr_handle* h, int R, int M, int k);

@@ -46,6 +46,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_topk_rows_large_workspace_bytes", "sgpr_topk_rows_large",
                "sgpr_score_topk_large_workspace_bytes", "sgpr_score_topk_large",
                "sgpr_seq_filter", "sgpr_score_seq_topk_workspace_bytes", "sgpr_score_seq_topk",
+               "sgpr_peak_filter", "sgpr_score_peak_topk_workspace_bytes", "sgpr_score_peak_topk",
                "sgpr_score_mine_workspace_bytes", "sgpr_score_mine", "sgpr_mine_rows_workspace_bytes", "sgpr_mine_rows",
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
                "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
@@ -196,6 +197,13 @@ def load_library():
     lib.sgpr_score_seq_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]
     lib.sgpr_score_seq_topk.restype = i32
     lib.sgpr_score_seq_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.sgpr_peak_filter.restype = i32
+    lib.sgpr_peak_filter.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, i32, vp, i64, vp]
+    lib.sgpr_score_peak_topk_workspace_bytes.restype = sz
+    lib.sgpr_score_peak_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32]
+    lib.sgpr_score_peak_topk.restype = i32
+    lib.sgpr_score_peak_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz,
+                                         vp]
     lib.sgpr_score_mine_workspace_bytes.restype = sz
     lib.sgpr_score_mine_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
     lib.sgpr_score_mine.restype = i32
@@ -1075,6 +1083,66 @@ class Engine:
         rc = self.lib.sgpr_score_seq_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
                                           int(window), flags, int(seq_len), int(k), _ptr(vals), _ptr(idx), _ptr(dirs),
                                           _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        return vals, idx, dirs
+
+    PEAK_MAX_RADIUS = 1024   # SGPR_PEAK_MAX_RADIUS of include/sgpr.h
+    PEAK_STRIP = 1024        # SGPR_PEAK_STRIP: columns a workgroup of the peak filter owns
+
+    def peak_filter(self, score, radius, window=-1, row0=0, causal=False, row_self=None, out=None):
+        """sgpr_peak_filter: a resident matrix [R, M] -> P f32 [R, M]: the score at a PEAK - a qualifying column
+        (score_topk's eligibility: window, causal, row_self / row0; neither NaN nor -inf) that comes first, by (value
+        descending, column ascending), among the qualifying columns at most `radius` away - and -inf elsewhere.
+        A row-strided view (unit column stride) is read in place.  out: a device tensor [R, M] to write into (row
+        stride >= M, unit column stride; it must not overlap score)."""
+        if not isinstance(score, torch.Tensor):
+            score = torch.as_tensor(score)
+        if score.dim() != 2:
+            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
+        if score.device != self.device or score.dtype != torch.float32:
+            score = score.to(device=self.device, dtype=torch.float32)
+        r, m = score.shape
+        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
+            score = score.contiguous()
+        rs = self._row_self(row_self, r)
+        if out is None:
+            out = torch.empty(r, m, dtype=torch.float32, device=self.device)
+        elif (out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (r, m)
+              or (m > 1 and out.stride(1) != 1) or (r > 1 and out.stride(0) < m)):
+            raise ValueError("out must be a float32 device tensor [%d, %d] with unit column stride" % (r, m))
+        rc = self.lib.sgpr_peak_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m, _ptr(rs),
+                                       int(row0), int(window), self.TOPK_CAUSAL if causal else 0, int(radius),
+                                       _ptr(out), max(out.stride(0), m) if r > 1 else m, self._stream())
+        self._check(rc)
+        return out
+
+    def score_peak_topk_workspace_bytes(self, r, m, radius, seq_len=1, k=1, causal=False, context=0, reverse=False):
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        return int(self.lib.sgpr_score_peak_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
+                                                                 int(k), int(radius), flags))
+
+    def score_peak_topk(self, pooled_rows, pooled_cols, radius, seq_len=1, k=1, window=-1, row0=0, causal=False,
+                        row_self=None, context=0, reverse=False):
+        """sgpr_score_peak_topk: distinct-place loop closures - the k best peaks (peak_filter's definition, within
+        `radius` columns) of the sequence-matched score (seq_len = 1: of the score itself) for rows context .. R-1 ->
+        (values f32 [R - context, k], indices i32, dirs u8), (-inf, -1, 0) past the last peak.  score_seq_topk's
+        arguments and rules; radius = 0 returns its bits.  Choose radius <= window: the first eligible column beside
+        an excluded window can be a peak of a slope that rises into the window."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        ro = max(r - int(context), 0)
+        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
+        dirs = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        ws_bytes = self.lib.sgpr_score_peak_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len), int(k),
+                                                                 int(radius), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_score_peak_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
+                                           int(window), flags, int(seq_len), int(radius), int(k), _ptr(vals),
+                                           _ptr(idx), _ptr(dirs), _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         return vals, idx, dirs
 

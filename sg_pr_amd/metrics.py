@@ -359,6 +359,22 @@ def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1
     return (hits / counted).cpu().numpy() if counted else np.zeros(kk)
 
 
+def places_per_list(indices, radius):
+    """Mean number of distinct places in a candidate list: the listed columns (>= 0) of a row, sorted, fall into groups
+    whose neighbours are at most `radius` apart - one place seen several times; averaged over the lists that are not
+    empty (0 when all are).  indices [M, K] as every loop-closure call returns them."""
+    import torch
+    idx = torch.as_tensor(indices).long()
+    if idx.numel() == 0:
+        return 0.0
+    srt = torch.sort(torch.where(idx >= 0, idx, torch.full_like(idx, -1)), dim=1).values     # padding first
+    listed = srt >= 0
+    gaps = (srt[:, 1:] - srt[:, :-1] > int(radius)) & listed[:, :-1] & listed[:, 1:]
+    places = gaps.sum(dim=1) + 1
+    some = listed.any(dim=1)
+    return float(places[some].double().mean()) if bool(some.any()) else 0.0
+
+
 def recall_percent_n(num_frames, percent=1.0):
     """Candidates per query of recall@percent (PointNetVLAD): N = max(1, round(M' * percent / 100)), M' database frames."""
     return max(1, int(round(num_frames * float(percent) / 100.0)))

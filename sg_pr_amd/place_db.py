@@ -17,7 +17,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
 
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
-                                            [--verify] [--min-inliers I]
+                                            [--verify] [--min-inliers I] [--distinct RHO]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -35,7 +35,13 @@ packed graphs (SG.verify_closures: planar consensus of the labelled centres, eng
 per list slot inliers, inliers_refined, flags, refined [M,K,4] (c, s, tx, ty: row scan -> column scan), yaw, rmse, the
 re-ranked lists indices_ranked (refined inliers descending, then score, then column) and accept (inliers_refined >=
 --min-inliers, default 12); printed are recall@1 before and after re-ranking, the precision of the accepted closures
-and the median yaw / translation error of the accepted true closures against the poses.
+and the median yaw / translation error of the accepted true closures against the poses.  With --distinct RHO
+(0..1024) the K best distinct places are retrieved as well - the peaks of the ranked score within RHO frames
+(engine.Engine.score_peak_topk; --seq-len still chooses the score; choose RHO <= --window):
+`<seq>_distinct.npz` holds frame, indices [M,K], scores [M,K], recall, radius (and seq_len, dirs); printed are
+recall@1 and recall@K of the distinct lists beside the plain ones and the mean number of places per list (groups of
+listed frames at most RHO apart) of both; with --verify the distinct lists are verified too (`<seq>_distinct_verify.npz`)
+and the number of pairs verified in each mode is printed.
 """
 import argparse
 import hashlib
@@ -95,39 +101,58 @@ class PlaceDatabase:
         """Embed packed graphs (centers [g,N,3], labels [g,N]) and append them -> their ids (int64 [g])."""
         return self.append_pooled(self._embed(centers, labels))
 
-    def query(self, centers, labels, k=1, window=-1, causal=False):
+    def query(self, centers, labels, k=1, window=-1, causal=False, distinct=None):
         """The k best members for graphs that are NOT in the database, taken as frames len(db), len(db) + 1, ...
-        -> (scores f32 [g,k], ids i32 [g,k]) on the device."""
+        -> (scores f32 [g,k], ids i32 [g,k]) on the device.  distinct=rho: the k best distinct places - score peaks
+        within rho members (engine.Engine.score_peak_topk; the members are one trajectory, choose rho <= window).
+        A causal query fed one scan at a time returns the lists of one offline causal call."""
+        if distinct is not None:
+            return self.eng.score_peak_topk(self._embed(centers, labels), self.pooled, int(distinct), k=k, window=window,
+                                            row0=self.n, causal=causal)[:2]
         return self.eng.score_topk(self._embed(centers, labels), self.pooled, k=k, window=window, row0=self.n,
                                    causal=causal)
 
-    def query_ids(self, ids, k=1, window=-1, causal=False):
-        """The k best members for members `ids` (their own id is their frame: row_self = ids)."""
+    def query_ids(self, ids, k=1, window=-1, causal=False, distinct=None):
+        """The k best members for members `ids` (their own id is their frame: row_self = ids).  distinct=rho: the k
+        best distinct places (query)."""
         ids = torch.as_tensor(ids, dtype=torch.int64).to(self._buf.device)
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n):
             raise IndexError("query_ids: ids must lie in [0, %d)" % self.n)
         rows = self.pooled.index_select(0, ids)
+        if distinct is not None:
+            return self.eng.score_peak_topk(rows, self.pooled, int(distinct), k=k, window=window, causal=causal,
+                                            row_self=ids.to(torch.int32))[:2]
         return self.eng.score_topk(rows, self.pooled, k=k, window=window, causal=causal,
                                    row_self=ids.to(torch.int32))
 
-    def query_seq(self, centers, labels, seq_len, k=1, window=-1, causal=False, reverse="both", pooled=None):
+    def query_seq(self, centers, labels, seq_len, k=1, window=-1, causal=False, reverse="both", pooled=None,
+                  distinct=None):
         """Sequence-matched query for graphs that are NOT in the database, taken as the next frames len(db),
         len(db) + 1, ... of the trajectory the members form (or, pooled=, their already embedded vectors): the k best
         members by the score averaged along the last seq_len frames (engine.Engine.score_seq_topk), the database's last
-        seq_len - 1 members serving as context rows -> (scores f32 [g,k], ids i32 [g,k], dirs u8 [g,k])."""
+        seq_len - 1 members serving as context rows -> (scores f32 [g,k], ids i32 [g,k], dirs u8 [g,k]).
+        distinct=rho: the k best peaks of that score within rho members (engine.Engine.score_peak_topk)."""
         new = self._embed(centers, labels) if pooled is None else self.eng._pooled(pooled, "pooled")
         ctx = min(int(seq_len) - 1, self.n)
         rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
+        if distinct is not None:
+            return self.eng.score_peak_topk(rows, self.pooled, int(distinct), seq_len=int(seq_len), k=k, window=window,
+                                            row0=self.n - ctx, causal=causal, context=ctx, reverse=reverse)
         return self.eng.score_seq_topk(rows, self.pooled, int(seq_len), k=k, window=window, row0=self.n - ctx,
                                        causal=causal, context=ctx, reverse=reverse)
 
-    def query_ids_seq(self, first, count, seq_len, k=1, window=-1, causal=False, reverse="both"):
+    def query_ids_seq(self, first, count, seq_len, k=1, window=-1, causal=False, reverse="both", distinct=None):
         """Sequence-matched lists for the run of members first .. first + count - 1 (their ids are their frames), the
-        up to seq_len - 1 members before `first` serving as context rows -> (scores, ids, dirs) [count, k]."""
+        up to seq_len - 1 members before `first` serving as context rows -> (scores, ids, dirs) [count, k].
+        distinct=rho: the k best peaks of that score within rho members."""
         first, count = int(first), int(count)
         if first < 0 or count < 0 or first + count > self.n:
             raise IndexError("query_ids_seq: first .. first + count must lie in [0, %d]" % self.n)
         ctx = min(int(seq_len) - 1, first)
+        if distinct is not None:
+            return self.eng.score_peak_topk(self._buf[first - ctx:first + count], self.pooled, int(distinct),
+                                            seq_len=int(seq_len), k=k, window=window, row0=first - ctx, causal=causal,
+                                            context=ctx, reverse=reverse)
         return self.eng.score_seq_topk(self._buf[first - ctx:first + count], self.pooled, int(seq_len), k=k,
                                        window=window, row0=first - ctx, causal=causal, context=ctx, reverse=reverse)
 
@@ -216,7 +241,11 @@ def main(argv=None):
                     help="verify the retrieved lists geometrically, re-rank them by inliers and write <seq>_verify.npz")
     ap.add_argument("--min-inliers", type=int, default=12, metavar="I",
                     help="with --verify: accept a closure with at least I refined inliers")
+    ap.add_argument("--distinct", type=int, default=None, metavar="RHO",
+                    help="also retrieve the K best distinct places: score peaks within RHO frames (0..1024)")
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if opt.distinct is not None and not 0 <= opt.distinct <= _engine.Engine.PEAK_MAX_RADIUS:
+        ap.error("--distinct must lie in 0..%d" % _engine.Engine.PEAK_MAX_RADIUS)
     if not 1 <= opt.seq_len <= _engine.Engine.SEQ_MAX_LEN:
         ap.error("--seq-len must lie in 1..%d" % _engine.Engine.SEQ_MAX_LEN)
     args = sgpr_args()
@@ -267,6 +296,32 @@ def main(argv=None):
                   "(>= %d inliers) precision %.4f," % (opt.min_inliers, report["precision"]),
                   "accepted true closures %d: median yaw error %.3f deg, median translation error %.3f m"
                   % (int(report["true_accepted"]), report["median_yaw_deg"], report["median_trans_m"]))
+        if opt.distinct is not None:
+            if opt.seq_len > 1:
+                dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
+                                                      reverse={"off": False, "on": True, "both": "both"}[opt.seq_reverse],
+                                                      distinct=opt.distinct)
+                dextra = {"seq_len": np.int64(opt.seq_len), "dirs": ddirs.cpu().numpy()}
+            else:
+                dvals, didx = db.query_ids(torch.arange(m), k=k, window=opt.window, causal=opt.causal,
+                                           distinct=opt.distinct)
+                dextra = {}
+            drecall = metrics.recall_at_n(didx, seq.poses, p_thresh=float(args.p_thresh), window=opt.window,
+                                          causal=opt.causal)
+            np.savez(os.path.join(args.output_path, sequence + "_distinct.npz"), frame=np.arange(m),
+                     indices=didx.cpu().numpy(), scores=dvals.cpu().numpy(), recall=drecall,
+                     radius=np.int64(opt.distinct), **dextra)
+            print("sequence", sequence, "distinct radius", opt.distinct, "recall@1 %.4f (plain %.4f)" % (drecall[0], recall[0]),
+                  "recall@%d %.4f (plain %.4f)" % (k, drecall[-1], recall[-1]),
+                  "places per list %.3f (plain %.3f)" % (metrics.places_per_list(didx, opt.distinct),
+                                                         metrics.places_per_list(idx, opt.distinct)))
+            if opt.verify:
+                dreport = verify_lists(trainer.model, seq, dvals, didx, opt.min_inliers, float(args.p_thresh),
+                                       window=opt.window, causal=opt.causal)
+                np.savez(os.path.join(args.output_path, sequence + "_distinct_verify.npz"), frame=np.arange(m), **dreport)
+                print("sequence", sequence, "pairs verified: plain", int(report["verified"]), "distinct",
+                      int(dreport["verified"]), "recall@1 re-ranked %.4f (plain %.4f)"
+                      % (dreport["recall_ranked"][0], report["recall_ranked"][0]))
         if opt.threshold is not None:
             rows, cols, scores, _ = db.query_ids_above(torch.arange(m), opt.threshold, window=opt.window,
                                                        causal=opt.causal)

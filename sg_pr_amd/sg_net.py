@@ -147,11 +147,20 @@ class SG(torch.nn.Module):
         return self.engine().score_all_pairs(pooled_rows, pooled_cols, out=out)
 
     def loop_closures(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None, seq_len=1,
-                      seq_reverse="both"):
+                      seq_reverse="both", distinct=None):
         """The k best columns per row of pooled_rows x pooled_cols without forming the matrix (engine.Engine.score_topk)
         -> (values f32 [R,k], indices i32 [R,k]) on the device.  seq_len > 1: rows and columns are consecutive scans and
         the lists rank the sequence-matched score (engine.Engine.score_seq_topk; seq_reverse False / True / "both")
-        -> (values, indices, dirs u8 [R,k])."""
+        -> (values, indices, dirs u8 [R,k]).  distinct=rho (0..1024): rows and columns are consecutive scans and the
+        lists hold distinct places - the k best PEAKS of the ranked score, a peak being the first column, by (value
+        descending, column ascending), among the qualifying columns at most rho away (engine.Engine.score_peak_topk,
+        DESIGN.md §20; k up to 4096, choose rho <= window); seq_len still chooses the score and the shape of the
+        result.  distinct=None: the plain lists."""
+        if distinct is not None:
+            out = self.engine().score_peak_topk(pooled_rows, pooled_cols, int(distinct), seq_len=int(seq_len), k=k,
+                                                window=window, row0=row0, causal=causal, row_self=row_self,
+                                                reverse=seq_reverse if int(seq_len) != 1 else False)
+            return out if int(seq_len) != 1 else out[:2]
         if int(seq_len) != 1:
             return self.engine().score_seq_topk(pooled_rows, pooled_cols, int(seq_len), k=k, window=window, row0=row0,
                                                 causal=causal, row_self=row_self, reverse=seq_reverse)
