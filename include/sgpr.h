@@ -478,6 +478,50 @@ int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                          float* d_values, int32_t* d_indices, unsigned char* d_dirs, void* d_workspace,
                          size_t workspace_bytes, void* stream);
 
+/* Speed-tolerant sequence matching: the diagonal mean of sgpr_seq_filter, maximised over a set of paths.  Scans are
+ * sampled in time, not in distance: a revisit driven at another speed, or matched against a keyframe-thinned map, is a
+ * line of slope p/q != 1, on which the unit diagonal averages one true score with L - 1 unrelated ones.
+ * A PATH is off[0..L-1], int32, with off[0] = 0, non-decreasing, off[L-1] <= SGPR_SEQ_PATH_MAX_OFFSET: the column
+ * distance walked back after d row steps.  A call takes n_paths paths, 1..SGPR_SEQ_MAX_PATHS, as a HOST array
+ * h_offsets [n_paths][L]; the array is copied into the launch and is free to reuse after the call returns.
+ * For path p and sigma = +1 (SGPR_SEQ_FORWARD) or -1 (SGPR_SEQ_REVERSE):
+ *     D_p(r, c)    = { d in 0..L-1 : r - d >= 0 and 0 <= c - sigma off_p[d] < M }     (a prefix: off is monotone)
+ *     Q_{p,sigma}  = (S[r, c] + S[r-1, c - sigma off_p[1]] + ...) * rcp[|D_p|],       rcp[n] = (float)(1.0 / n)
+ * plain fp32 additions in ascending d starting from the d = 0 term, one fp32 multiplication, nothing fused; terms are
+ * never masked and never replaced by zero.  The result is a fold over the candidates in this order: forward paths
+ * 0..n_paths-1, then reverse paths 0..n_paths-1 (directions not asked for are skipped).  `best` starts as the first
+ * candidate; a later x replaces it iff x > best or best is NaN; code (u8) = direction bit | path << 1 of the winner.
+ * With the single path off[d] = d this is sgpr_seq_filter bit for bit and code is its dir.  Duplicate paths are allowed
+ * and change nothing.  Everything else is sgpr_seq_filter's: the context rows ctx, eligibility on the end point only,
+ * NaN / inf propagation, 1 <= L <= SGPR_SEQ_MAX_LEN.
+ * - window >= L - 1 + the largest offset keeps the self diagonal out of every sum of an eligible end point.
+ * - A streaming place database (rows arrive one at a time, columns are the frames stored so far) gets the offline lists
+ *   iff window >= the largest offset; otherwise a reverse sum of an eligible column reaches a frame not stored yet.
+ * - sgpr_seq_path_filter: a resident matrix d_score [R][ld] -> d_out [R - ctx][ldo] and, unless NULL, d_code u8
+ *   [R - ctx][ldo].  Out of place.  No workspace.  One workgroup per tile of 32 rows x 256 columns with a halo of the
+ *   call's largest offset (sgpr_seq_path.hip).
+ * - sgpr_score_path_topk: sgpr_score_peak_topk's structure (row blocks with L - 1 context rows, the f16-range question
+ *   answered once per call, every handle) with the path filter in place of the diagonal filter; the peak step runs only
+ *   when radius > 0.  d_codes u8 [R - ctx][k] (or NULL): the code of each listed entry, 0 in a padding slot.  With the
+ *   unit path the lists are the bits of sgpr_score_seq_topk (radius 0) / sgpr_score_peak_topk (radius > 0) and the
+ *   workspace equals theirs; with n_paths > 1 and one direction it grows by one code block of the block's rows x M
+ *   bytes.  Never R * M.
+ * Arguments are checked before the device is touched: those of the calls above, and n_paths outside
+ * 1..SGPR_SEQ_MAX_PATHS, a NULL table, off[p][0] != 0, a decreasing step or an offset above SGPR_SEQ_PATH_MAX_OFFSET give
+ * SGPR_E_INVALID with a message naming the fault (the workspace answer is 0 for invalid arguments).  R == ctx or M == 0
+ * writes padding lists without scoring.  Results depend on the arguments alone.  Asynchronous on `stream`. */
+#define SGPR_SEQ_MAX_PATHS 16
+#define SGPR_SEQ_PATH_MAX_OFFSET 64
+int sgpr_seq_path_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx, int L, int flags,
+                         const int32_t* h_offsets, int n_paths, float* d_out, int64_t ldo, unsigned char* d_code,
+                         void* stream);
+size_t sgpr_score_path_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int k,
+                                            int radius, int flags);
+int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
+                         const int32_t* h_offsets, int n_paths, int radius, int k, float* d_values, int32_t* d_indices,
+                         unsigned char* d_codes, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Hard-pair mining without the R x M matrix: for every row r the k (1..16) hardest pose-labelled pairs (r, c) of the
  * rectangle d_pooled_rows [R] x d_pooled_cols [M].
  * - Column c is eligible for row r iff it is for sgpr_score_topk (window, SGPR_TOPK_CAUSAL, self_r = d_row_self[r] or

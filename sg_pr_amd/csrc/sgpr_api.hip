@@ -1599,6 +1599,147 @@ int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                             workspace_bytes, stream, select, crng, L - 1);
 }
 
+// ---- sgpr_seq_path_filter / sgpr_score_path_topk: the path-set score filter (sgpr_seq_path.hip) on a resident matrix,
+//      and on sgpr_score_peak_topk's row blocks in place of the diagonal filter (the peak step only when radius > 0)
+static bool seq_paths_ok(const char* fn, const int32_t* h_offsets, int n_paths, int L) {
+    if (n_paths < 1 || n_paths > SGPR_SEQ_MAX_PATHS) {
+        set_error(std::string(fn) + ": n_paths must lie in 1.." + std::to_string(SGPR_SEQ_MAX_PATHS));
+        return false;
+    }
+    if (!h_offsets) {
+        set_error(std::string(fn) + ": NULL path table");
+        return false;
+    }
+    for (int p = 0; p < n_paths; ++p) {
+        const int32_t* off = h_offsets + (size_t)p * L;
+        if (off[0] != 0) {
+            set_error(std::string(fn) + ": path " + std::to_string(p) + " does not start at offset 0");
+            return false;
+        }
+        for (int d = 1; d < L; ++d)
+            if (off[d] < off[d - 1]) {
+                set_error(std::string(fn) + ": path " + std::to_string(p) + " has a decreasing step at d = " +
+                          std::to_string(d));
+                return false;
+            }
+        if (off[L - 1] > SGPR_SEQ_PATH_MAX_OFFSET) {
+            set_error(std::string(fn) + ": path " + std::to_string(p) + " has an offset above " +
+                      std::to_string(SGPR_SEQ_PATH_MAX_OFFSET));
+            return false;
+        }
+    }
+    return true;
+}
+
+int sgpr_seq_path_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx, int L, int flags,
+                         const int32_t* h_offsets, int n_paths, float* d_out, int64_t ldo, unsigned char* d_code,
+                         void* stream) {
+    if (!h || R < 0 || M < 0 || ld < M || ldo < M) {
+        set_error("sgpr_seq_path_filter: NULL handle, negative size or leading dimension below M");
+        return SGPR_E_INVALID;
+    }
+    if (!seq_args_ok("sgpr_seq_path_filter", R, ctx, L, flags, SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)) return SGPR_E_INVALID;
+    if (!seq_paths_ok("sgpr_seq_path_filter", h_offsets, n_paths, L)) return SGPR_E_INVALID;
+    if (R > ctx && M > 0 && (!d_score || !d_out)) {       // (an empty result needs no buffers)
+        set_error("sgpr_seq_path_filter: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (R == ctx || M == 0) return SGPR_OK;
+    DeviceGuard guard(h->device);
+    return launch_seq_path_filter(d_score, R, M, ld, ctx, L, flags, h_offsets, n_paths, d_out, ldo, d_code, ldo,
+                                  static_cast<hipStream_t>(stream));
+}
+
+// head of sgpr_score_path_topk: sgpr_score_seq_topk's (radius 0) or sgpr_score_peak_topk's (radius > 0), their dir block
+// holding the codes; one direction and several paths: a code block [rb][M] behind it
+static size_t path_head_bytes(int R, int M, int L, int n_paths, int radius, int flags) {
+    const size_t rb = (size_t)score_block_rows(R, M, L - 1);
+    return (radius > 0 ? peak_head_bytes(R, M, L, flags) : seq_head_bytes(R, M, L, flags)) +
+           (n_paths > 1 && !seq_both(flags) ? a256(rb * M) : 0);
+}
+
+size_t sgpr_score_path_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int k,
+                                            int radius, int flags) {
+    if (!h || R < 0 || M < 0 || k < 1 || k > SGPR_TOPK_LARGE_MAX || L < 1 || L > SGPR_SEQ_MAX_LEN || ctx < 0 || ctx > R ||
+        n_paths < 1 || n_paths > SGPR_SEQ_MAX_PATHS || radius < 0 || radius > SGPR_PEAK_MAX_RADIUS ||
+        (flags & ~kSeqFlags) || !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
+        return 0;
+    if (R == ctx || M == 0) return 0;
+    return row_blocks_ws_bytes(h, R, M, path_head_bytes(R, M, L, n_paths, radius, flags), L - 1);
+}
+
+int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                         int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
+                         const int32_t* h_offsets, int n_paths, int radius, int k, float* d_values, int32_t* d_indices,
+                         unsigned char* d_codes, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!h || R < 0 || M < 0) {
+        set_error("sgpr_score_path_topk: NULL handle or negative count");
+        return SGPR_E_INVALID;
+    }
+    if (!seq_args_ok("sgpr_score_path_topk", R, ctx, L, flags, kSeqFlags)) return SGPR_E_INVALID;
+    if (!seq_paths_ok("sgpr_score_path_topk", h_offsets, n_paths, L)) return SGPR_E_INVALID;
+    if (!peak_radius_ok("sgpr_score_path_topk", radius)) return SGPR_E_INVALID;
+    if ((R > ctx && (!d_values || !d_indices)) || (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols))) {
+        set_error("sgpr_score_path_topk: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (!topk_large_args_ok("sgpr_score_path_topk", R, k, flags & SGPR_TOPK_CAUSAL, row0)) return SGPR_E_INVALID;
+    if (!workspace_ok("sgpr_score_path_topk",
+                      sgpr_score_path_topk_workspace_bytes(h, R, M, ctx, L, n_paths, k, radius, flags), d_workspace,
+                      workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    if (R == ctx) return SGPR_OK;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_code = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0) {
+        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, window,
+                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
+        if (rc != SGPR_OK || !d_codes) return rc;
+        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_code, d_codes, s);
+    }
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
+    // radius > 0: P block, then (L > 1) the Q block; radius 0: the Q block alone.  The code block follows the Q block.
+    const bool filter = radius == 0 || L > 1, want_code = filter && (seq_both(flags) || n_paths > 1);
+    const size_t q_at = 256 + sel_bytes + (radius > 0 ? blk_bytes : 0);
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    int clean_rows = 0;                                   // histogram rows the selection before left clear
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0), no = r0 + n - first;
+        const float* x = block + (size_t)(first - r0) * M;   // L = 1 before the peak step: every candidate is S itself
+        unsigned char* code = want_code ? head + q_at + blk_bytes : nullptr;
+        int rc;
+        if (filter) {
+            float* q = reinterpret_cast<float*>(head + q_at);
+            rc = launch_seq_path_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, h_offsets, n_paths, q,
+                                        M, code, M, s);
+            if (rc != SGPR_OK) return rc;
+            x = q;
+        }
+        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
+        if (radius > 0) {
+            float* p = reinterpret_cast<float*>(head + 256 + sel_bytes);
+            rc = launch_peak_filter(x, no, M, M, rs, row0 + first, window, causal, radius, p, M, s);
+            if (rc != SGPR_OK) return rc;
+            x = p;
+        }
+        const size_t o = (size_t)(first - ctx) * k;
+        rc = launch_select_rows(x, no, M, M, rs, row0 + first, window, causal, k, d_values + o, d_indices + o, head + 256,
+                                select_group_rows(no) <= clean_rows, h->d_status, s);
+        clean_rows = select_group_rows(no);
+        if (rc != SGPR_OK || !d_codes) return rc;
+        // (no code block: one candidate, or L = 1 where all candidates are one number and the first one keeps a listed,
+        //  hence non-NaN, entry - path 0 of the first direction asked for)
+        return launch_seq_dirs(d_indices + o, no, k, code, M, fixed_code, d_codes + o, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, path_head_bytes(R, M, L, n_paths, radius, flags),
+                            d_workspace, workspace_bytes, stream, select, crng, L - 1);
+}
+
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks
 //      and sgpr_mine_rows' kernel on the others) with the pose-class condition of the mined pairs
 static const int kMineFlags = SGPR_TOPK_CAUSAL | SGPR_MINE_NEGATIVES | SGPR_MINE_POSITIVES;

@@ -318,6 +318,11 @@ int launch_seq_filter(const float* score, int R, int M, int64_t ld, int ctx, int
 // out [n][k] = dir [n][ld] at the selected columns idx [n][k] (dir == nullptr: `fixed`); 0 where idx is -1
 int launch_seq_dirs(const int32_t* idx, int n, int k, const unsigned char* dir, int64_t ld, int fixed,
                     unsigned char* out, hipStream_t stream);
+// the path-set score filter of a resident R x M matrix (sgpr_seq_path.hip): launch_seq_filter's arguments with a host
+// table offsets [n_paths][L] (already checked; copied into the launch) and the winner's code (direction bit | path << 1)
+// into code [R - ctx][ldc] (or nullptr)
+int launch_seq_path_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
+                           int n_paths, float* out, int64_t ldo, unsigned char* code, int64_t ldc, hipStream_t stream);
 // the peak filter of a resident n x M block (sgpr_peak.hip): out [n][ldo] = score at a peak within `radius` columns, -inf
 // elsewhere; eligibility as launch_select_rows (row_self [n] / row0 belong to the block's row 0)
 int launch_peak_filter(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,

@@ -6,6 +6,7 @@ There is NO CPU fallback: a missing library or a non-GPU tensor raises.
 """
 import ctypes
 import os
+from fractions import Fraction
 import threading
 
 import numpy as np
@@ -47,6 +48,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_score_topk_large_workspace_bytes", "sgpr_score_topk_large",
                "sgpr_seq_filter", "sgpr_score_seq_topk_workspace_bytes", "sgpr_score_seq_topk",
                "sgpr_peak_filter", "sgpr_score_peak_topk_workspace_bytes", "sgpr_score_peak_topk",
+               "sgpr_seq_path_filter", "sgpr_score_path_topk_workspace_bytes", "sgpr_score_path_topk",
                "sgpr_score_mine_workspace_bytes", "sgpr_score_mine", "sgpr_mine_rows_workspace_bytes", "sgpr_mine_rows",
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
                "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
@@ -66,6 +68,60 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
 
 # struct sgpr_rank_group of include/sgpr.h
 RANK_GROUP = np.dtype([("value", "<f4", (8,)), ("pairs", "<u4", (8,))])
+
+
+SEQ_MAX_PATHS = 16          # SGPR_SEQ_MAX_PATHS of include/sgpr.h
+SEQ_PATH_MAX_OFFSET = 64    # SGPR_SEQ_PATH_MAX_OFFSET
+
+
+def _slope(s):
+    """(p, q) of a slope given as a pair, a Fraction, an int or a string like "3/2"; p >= 0, q >= 1, in lowest terms"""
+    if isinstance(s, str):
+        s = Fraction(s.strip())
+    elif isinstance(s, (tuple, list)):
+        if len(s) != 2:
+            raise ValueError("a slope pair is (p, q), got %r" % (s,))
+        s = Fraction(int(s[0]), int(s[1]))
+    else:
+        s = Fraction(s)
+    if s < 0:
+        raise ValueError("a slope must not be negative, got %s" % s)
+    return s.numerator, s.denominator
+
+
+def seq_paths(seq_len, slopes):
+    """The path table of Engine.seq_path_filter / score_path_topk for a set of slopes: int32 [P, seq_len].
+    A slope p/q (a (p, q) pair, a Fraction or a string like "3/2") means p columns per q rows; it gives one path per
+    phase j in 0..q-1, off[d] = (d p + j) // q.  Paths are de-duplicated in order.  ValueError past SEQ_MAX_PATHS paths
+    or past offset SEQ_PATH_MAX_OFFSET."""
+    seq_len = int(seq_len)
+    if seq_len < 1 or seq_len > Engine.SEQ_MAX_LEN:
+        raise ValueError("seq_len must lie in 1..%d, got %d" % (Engine.SEQ_MAX_LEN, seq_len))
+    paths = []
+    for s in slopes:
+        p, q = _slope(s)
+        for j in range(q):
+            off = tuple((d * p + j) // q for d in range(seq_len))
+            if off[-1] > SEQ_PATH_MAX_OFFSET:
+                raise ValueError("slope %d/%d walks %d columns back in %d scans: more than %d"
+                                 % (p, q, off[-1], seq_len, SEQ_PATH_MAX_OFFSET))
+            if off not in paths:
+                paths.append(off)
+    if not paths:
+        raise ValueError("no slopes given")
+    if len(paths) > SEQ_MAX_PATHS:
+        raise ValueError("%d distinct paths: more than %d" % (len(paths), SEQ_MAX_PATHS))
+    return np.asarray(paths, dtype=np.int32).reshape(len(paths), seq_len)
+
+
+def _path_table(paths, seq_len):
+    """a host int32 [P, seq_len] C-contiguous array of a path table (the library checks its contents)"""
+    if isinstance(paths, torch.Tensor):
+        paths = paths.cpu().numpy()
+    t = np.ascontiguousarray(np.asarray(paths, dtype=np.int32))
+    if t.ndim != 2 or t.shape[1] != int(seq_len):
+        raise ValueError("paths must be [P, %d], got %s" % (int(seq_len), tuple(t.shape)))
+    return t
 
 
 class SgprError(RuntimeError):
@@ -197,6 +253,13 @@ def load_library():
     lib.sgpr_score_seq_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]
     lib.sgpr_score_seq_topk.restype = i32
     lib.sgpr_score_seq_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    lib.sgpr_seq_path_filter.restype = i32
+    lib.sgpr_seq_path_filter.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, i32, vp, i64, vp, vp]
+    lib.sgpr_score_path_topk_workspace_bytes.restype = sz
+    lib.sgpr_score_path_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32]
+    lib.sgpr_score_path_topk.restype = i32
+    lib.sgpr_score_path_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp,
+                                         vp, sz, vp]
     lib.sgpr_peak_filter.restype = i32
     lib.sgpr_peak_filter.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, i32, vp, i64, vp]
     lib.sgpr_score_peak_topk_workspace_bytes.restype = sz
@@ -1085,6 +1148,75 @@ class Engine:
                                           _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         return vals, idx, dirs
+
+    SEQ_MAX_PATHS = SEQ_MAX_PATHS
+    SEQ_PATH_MAX_OFFSET = SEQ_PATH_MAX_OFFSET
+
+    def seq_path_filter(self, score, seq_len, paths, context=0, reverse=False, want_code=False, out=None, out_code=None):
+        """sgpr_seq_path_filter: seq_filter maximised over a set of paths (int32 [P, seq_len], see seq_paths) -> Q f32
+        [R - context, M] (and, want_code, the winner's code u8: direction bit | path << 1).  The single path
+        off[d] = d gives seq_filter's bits.  out / out_code as seq_filter's out / out_dir."""
+        if not isinstance(score, torch.Tensor):
+            score = torch.as_tensor(score)
+        if score.dim() != 2:
+            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
+        if score.device != self.device or score.dtype != torch.float32:
+            score = score.to(device=self.device, dtype=torch.float32)
+        table = _path_table(paths, seq_len)
+        r, m = score.shape
+        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
+            score = score.contiguous()
+        ro = max(r - int(context), 0)
+        if out is None:
+            out = torch.empty(ro, m, dtype=torch.float32, device=self.device)
+        if out_code is None and want_code:
+            out_code = torch.empty(ro, m, dtype=torch.uint8, device=self.device)
+        ldo = m
+        for t, dt, name in ((out, torch.float32, "out"), (out_code, torch.uint8, "out_code")):
+            if t is None:
+                continue
+            if t.device != self.device or t.dtype != dt or tuple(t.shape) != (ro, m) or (m > 1 and t.stride(1) != 1):
+                raise ValueError("%s must be a %s device tensor [%d, %d] with unit column stride" % (name, dt, ro, m))
+            if ro > 1:
+                ldo = max(ldo, t.stride(0))
+        if ro > 1 and out_code is not None and max(out.stride(0), m) != max(out_code.stride(0), m):
+            raise ValueError("out and out_code must share one row stride")
+        rc = self.lib.sgpr_seq_path_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m,
+                                           int(context), int(seq_len), self._seq_flags(reverse), table.ctypes.data,
+                                           table.shape[0], _ptr(out), ldo, _ptr(out_code), self._stream())
+        self._check(rc)
+        return (out, out_code) if (want_code or out_code is not None) else out
+
+    def score_path_topk_workspace_bytes(self, r, m, seq_len, n_paths, k=1, radius=0, causal=False, context=0,
+                                        reverse="both"):
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        return int(self.lib.sgpr_score_path_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
+                                                                 int(n_paths), int(k), int(radius), flags))
+
+    def score_path_topk(self, pooled_rows, pooled_cols, seq_len, paths, k=1, radius=0, window=-1, row0=0, causal=False,
+                        row_self=None, context=0, reverse="both"):
+        """sgpr_score_path_topk: score_seq_topk's (radius 0) or score_peak_topk's (radius > 0) lists of the path-set
+        score (seq_path_filter of the rectangle, never formed beyond 64 MB row blocks) for rows context .. R-1 ->
+        (values f32 [R - context, k], indices i32, codes u8: direction bit | path << 1, 0 in a padding slot)."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        table = _path_table(paths, seq_len)
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        ro = max(r - int(context), 0)
+        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
+        codes = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        ws_bytes = self.lib.sgpr_score_path_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len),
+                                                                 table.shape[0], int(k), int(radius), flags)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_score_path_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
+                                           int(window), flags, int(seq_len), table.ctypes.data, table.shape[0],
+                                           int(radius), int(k), _ptr(vals), _ptr(idx), _ptr(codes), _ptr(ws), ws_bytes,
+                                           self._stream())
+        self._check(rc)
+        return vals, idx, codes
 
     PEAK_MAX_RADIUS = 1024   # SGPR_PEAK_MAX_RADIUS of include/sgpr.h
     PEAK_STRIP = 1024        # SGPR_PEAK_STRIP: columns a workgroup of the peak filter owns

@@ -17,7 +17,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
 
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
-                                            [--verify] [--min-inliers I] [--distinct RHO]
+                                            [--verify] [--min-inliers I] [--distinct RHO] [--seq-slopes S,S,...]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -41,7 +41,11 @@ and the median yaw / translation error of the accepted true closures against the
 `<seq>_distinct.npz` holds frame, indices [M,K], scores [M,K], recall, radius (and seq_len, dirs); printed are
 recall@1 and recall@K of the distinct lists beside the plain ones and the mean number of places per list (groups of
 listed frames at most RHO apart) of both; with --verify the distinct lists are verified too (`<seq>_distinct_verify.npz`)
-and the number of pairs verified in each mode is printed.
+and the number of pairs verified in each mode is printed.  With --seq-len L > 1 and --seq-slopes 1,1/2,2/3,3/2,2 the
+speed-tolerant lists are retrieved as well - the best mean over the paths of these slopes (engine.seq_paths,
+engine.Engine.score_path_topk; --distinct composes): `<seq>_slopes.npz` holds frame, indices [M,K],
+scores [M,K], codes [M,K] (direction bit | path << 1), paths [P,L], recall, seq_len (and radius); printed are
+recall@1 and recall@K beside the unit-slope lists and the share of listed entries per path.
 """
 import argparse
 import hashlib
@@ -125,30 +129,46 @@ class PlaceDatabase:
         return self.eng.score_topk(rows, self.pooled, k=k, window=window, causal=causal,
                                    row_self=ids.to(torch.int32))
 
+    def _paths(self, seq_len, slopes):
+        return _engine.seq_paths(int(seq_len), slopes)
+
     def query_seq(self, centers, labels, seq_len, k=1, window=-1, causal=False, reverse="both", pooled=None,
-                  distinct=None):
+                  distinct=None, slopes=None):
         """Sequence-matched query for graphs that are NOT in the database, taken as the next frames len(db),
         len(db) + 1, ... of the trajectory the members form (or, pooled=, their already embedded vectors): the k best
         members by the score averaged along the last seq_len frames (engine.Engine.score_seq_topk), the database's last
         seq_len - 1 members serving as context rows -> (scores f32 [g,k], ids i32 [g,k], dirs u8 [g,k]).
-        distinct=rho: the k best peaks of that score within rho members (engine.Engine.score_peak_topk)."""
+        distinct=rho: the k best peaks of that score within rho members (engine.Engine.score_peak_topk).
+        slopes (e.g. ("1", "1/2", "2")): the best mean over the paths of these slopes (engine.seq_paths,
+        engine.Engine.score_path_topk) -> (scores, ids, codes u8: direction bit | path << 1).  Fed one scan at a time
+        (causal) it returns the lists of one offline call iff window >= the paths' largest offset."""
         new = self._embed(centers, labels) if pooled is None else self.eng._pooled(pooled, "pooled")
         ctx = min(int(seq_len) - 1, self.n)
         rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
+        if slopes is not None:
+            return self.eng.score_path_topk(rows, self.pooled, int(seq_len), self._paths(seq_len, slopes), k=k,
+                                            radius=0 if distinct is None else int(distinct), window=window,
+                                            row0=self.n - ctx, causal=causal, context=ctx, reverse=reverse)
         if distinct is not None:
             return self.eng.score_peak_topk(rows, self.pooled, int(distinct), seq_len=int(seq_len), k=k, window=window,
                                             row0=self.n - ctx, causal=causal, context=ctx, reverse=reverse)
         return self.eng.score_seq_topk(rows, self.pooled, int(seq_len), k=k, window=window, row0=self.n - ctx,
                                        causal=causal, context=ctx, reverse=reverse)
 
-    def query_ids_seq(self, first, count, seq_len, k=1, window=-1, causal=False, reverse="both", distinct=None):
+    def query_ids_seq(self, first, count, seq_len, k=1, window=-1, causal=False, reverse="both", distinct=None,
+                      slopes=None):
         """Sequence-matched lists for the run of members first .. first + count - 1 (their ids are their frames), the
         up to seq_len - 1 members before `first` serving as context rows -> (scores, ids, dirs) [count, k].
-        distinct=rho: the k best peaks of that score within rho members."""
+        distinct=rho: the k best peaks of that score within rho members.  slopes: query_seq's -> (scores, ids, codes)."""
         first, count = int(first), int(count)
         if first < 0 or count < 0 or first + count > self.n:
             raise IndexError("query_ids_seq: first .. first + count must lie in [0, %d]" % self.n)
         ctx = min(int(seq_len) - 1, first)
+        if slopes is not None:
+            return self.eng.score_path_topk(self._buf[first - ctx:first + count], self.pooled, int(seq_len),
+                                            self._paths(seq_len, slopes), k=k,
+                                            radius=0 if distinct is None else int(distinct), window=window,
+                                            row0=first - ctx, causal=causal, context=ctx, reverse=reverse)
         if distinct is not None:
             return self.eng.score_peak_topk(self._buf[first - ctx:first + count], self.pooled, int(distinct),
                                             seq_len=int(seq_len), k=k, window=window, row0=first - ctx, causal=causal,
@@ -243,7 +263,19 @@ def main(argv=None):
                     help="with --verify: accept a closure with at least I refined inliers")
     ap.add_argument("--distinct", type=int, default=None, metavar="RHO",
                     help="also retrieve the K best distinct places: score peaks within RHO frames (0..1024)")
+    ap.add_argument("--seq-slopes", default=None, metavar="S,S,...",
+                    help="with --seq-len: also retrieve the lists of the best mean over paths of these slopes, e.g. "
+                         "1,1/2,2/3,3/2,2; writes <seq>_slopes.npz")
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    paths = None
+    if opt.seq_slopes is not None:
+        if opt.seq_len < 2:
+            ap.error("--seq-slopes needs --seq-len L > 1")
+        try:
+            slopes = [t for t in opt.seq_slopes.split(",") if t.strip()]
+            paths = _engine.seq_paths(opt.seq_len, slopes)
+        except (ValueError, ZeroDivisionError) as e:
+            ap.error("--seq-slopes: %s" % e)
     if opt.distinct is not None and not 0 <= opt.distinct <= _engine.Engine.PEAK_MAX_RADIUS:
         ap.error("--distinct must lie in 0..%d" % _engine.Engine.PEAK_MAX_RADIUS)
     if not 1 <= opt.seq_len <= _engine.Engine.SEQ_MAX_LEN:
@@ -322,6 +354,25 @@ def main(argv=None):
                 print("sequence", sequence, "pairs verified: plain", int(report["verified"]), "distinct",
                       int(dreport["verified"]), "recall@1 re-ranked %.4f (plain %.4f)"
                       % (dreport["recall_ranked"][0], report["recall_ranked"][0]))
+        if paths is not None:
+            svals, sidx, scodes = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
+                                                   reverse={"off": False, "on": True, "both": "both"}[opt.seq_reverse],
+                                                   distinct=opt.distinct, slopes=slopes)
+            srecall = metrics.recall_at_n(sidx, seq.poses, p_thresh=float(args.p_thresh), window=opt.window,
+                                          causal=opt.causal)
+            sextra = {} if opt.distinct is None else {"radius": np.int64(opt.distinct)}
+            codes = scodes.cpu().numpy()
+            np.savez(os.path.join(args.output_path, sequence + "_slopes.npz"), frame=np.arange(m),
+                     indices=sidx.cpu().numpy(), scores=svals.cpu().numpy(), codes=codes, paths=paths, recall=srecall,
+                     seq_len=np.int64(opt.seq_len), **sextra)
+            listed = (sidx >= 0).cpu().numpy()
+            share = np.bincount(codes[listed] >> 1, minlength=paths.shape[0]) / max(int(listed.sum()), 1)
+            # the unit-slope lists beside them: the distinct ones when --distinct is given
+            urecall = drecall if opt.distinct is not None else recall
+            print("sequence", sequence, "slopes", opt.seq_slopes, "paths", paths.shape[0],
+                  "recall@1 %.4f (unit slope %.4f)" % (srecall[0], urecall[0]),
+                  "recall@%d %.4f (unit slope %.4f)" % (k, srecall[-1], urecall[-1]),
+                  "share of listed entries per path", " ".join("%.3f" % x for x in share))
         if opt.threshold is not None:
             rows, cols, scores, _ = db.query_ids_above(torch.arange(m), opt.threshold, window=opt.window,
                                                        causal=opt.causal)

@@ -147,7 +147,7 @@ class SG(torch.nn.Module):
         return self.engine().score_all_pairs(pooled_rows, pooled_cols, out=out)
 
     def loop_closures(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None, seq_len=1,
-                      seq_reverse="both", distinct=None):
+                      seq_reverse="both", distinct=None, seq_slopes=None):
         """The k best columns per row of pooled_rows x pooled_cols without forming the matrix (engine.Engine.score_topk)
         -> (values f32 [R,k], indices i32 [R,k]) on the device.  seq_len > 1: rows and columns are consecutive scans and
         the lists rank the sequence-matched score (engine.Engine.score_seq_topk; seq_reverse False / True / "both")
@@ -155,7 +155,17 @@ class SG(torch.nn.Module):
         lists hold distinct places - the k best PEAKS of the ranked score, a peak being the first column, by (value
         descending, column ascending), among the qualifying columns at most rho away (engine.Engine.score_peak_topk,
         DESIGN.md §20; k up to 4096, choose rho <= window); seq_len still chooses the score and the shape of the
-        result.  distinct=None: the plain lists."""
+        result.  distinct=None: the plain lists.  seq_slopes (with seq_len > 1; e.g. ("1", "1/2", "2/3", "3/2", "2")): the
+        score is the best mean over a set of paths of these slopes - a revisit driven at another speed
+        (engine.seq_paths, engine.Engine.score_path_topk) -> (values, indices, codes u8 [R,k]: direction
+        bit | path << 1); it composes with distinct.  seq_slopes=None: the unit diagonal, exactly as before."""
+        if seq_slopes is not None:
+            if int(seq_len) == 1:
+                raise ValueError("loop_closures: seq_slopes needs seq_len > 1")
+            return self.engine().score_path_topk(pooled_rows, pooled_cols, int(seq_len),
+                                                 _engine.seq_paths(int(seq_len), seq_slopes), k=k,
+                                                 radius=0 if distinct is None else int(distinct), window=window, row0=row0,
+                                                 causal=causal, row_self=row_self, reverse=seq_reverse)
         if distinct is not None:
             out = self.engine().score_peak_topk(pooled_rows, pooled_cols, int(distinct), seq_len=int(seq_len), k=k,
                                                 window=window, row0=row0, causal=causal, row_self=row_self,
