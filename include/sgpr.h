@@ -868,6 +868,13 @@ int sgpr_pairs_train_backward(const float* d_dloss, const float* d_wsum, const f
  *             sizes - PCL leaves that last order unspecified); d_point_node [P] i32 = node of each point or -1 (may be
  *             NULL); d_num_nodes [1] i32 = number of nodes found (may exceed max_nodes: then only the first max_nodes are
  *             written; -1 if more than 8192 clusters qualified).
+ * Non-finite coordinates: an axis of a node's centre is NaN iff some point of its cluster has a NaN or an infinity on
+ * that axis; the other axes are the mean over all its points, as for a finite cluster.  Only a (class, instance) group
+ * can hold such a point: under Euclidean clustering a point with a non-finite coordinate is in range of nothing, a
+ * cluster of one below every minimum size, so its d_point_node is -1 and the nodes around it are unchanged (as are
+ * road / parking, which never form nodes).  The remission column (index 3) is never read.
+ * Limits: coordinates within +-110 km (|x| * 2^24 must stay far below 2^63); at most 32 768 distinct (class, instance
+ * id) pairs in one scan - the pair table has 65 536 slots and its insertion does not terminate once the table is full.
  * Results do not depend on execution order (integer fixed-point centroid sums, lowest-index roots).  Handle-free; runs
  * on the caller's current device. */
 size_t sgpr_cluster_workspace_bytes(int P);
@@ -877,9 +884,10 @@ int sgpr_cluster_scan(const float* d_points, int point_stride, const uint32_t* d
 
 /* The edge rule of gen_graphs (gen_label_graph.py:367-385) for the n nodes of sgpr_cluster_scan: d_min_dis [n,n] f64 =
  * for i != j the distance between the point of cluster i and the point of cluster j that lie nearest to the midpoint of
- * the two centres (0 on the diagonal); the caller keeps the pairs i < j with distance <= 5 m as edges of weight
- * 1 - d/5.  The scorer never reads edges (utils.py:21-38 loads nodes, centers and pose only); this serves writers of
- * the reference's graph JSON.  d_workspace: n*n*4 bytes. */
+ * the two centres (0 on the diagonal; NaN off the diagonal in the row and column of a node that has a NaN centre or
+ * that no point of d_point_node carries - NaN <= 5 is false, so such a node gets no edge); the caller keeps the
+ * pairs i < j with distance <= 5 m as edges of weight 1 - d/5.  The scorer never reads edges (utils.py:21-38 loads
+ * nodes, centers and pose only); this serves writers of the reference's graph JSON.  d_workspace: n*n*4 bytes. */
 int sgpr_graph_edges(const float* d_points, int point_stride, const int32_t* d_point_node, int P, int n,
                      const double* d_centers, double* d_min_dis, void* d_workspace, size_t workspace_bytes, void* stream);
 

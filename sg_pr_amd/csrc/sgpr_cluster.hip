@@ -95,7 +95,8 @@ struct ClusterWs {
     int* parent;                   // [P] union-find forest; after flatten: the root (lowest index) of the point's cluster
     int* next;                     // [P] linked list of the point's cell
     int* size;                     // [P] points per root
-    long long* sum;                // [P][3] fixed-point coordinate sums per root
+    long long* sum;                // [P][3] fixed-point coordinate sums per root (finite addends only)
+    int* nonfinite;                // [P] per root, bit a: some point of the cluster has a NaN / inf on axis a
     int* node_of_root;             // [P] node index of a selected root, else -1
     unsigned long long* cell_key;  // [H] cell hash table
     int* cell_head;                // [H]
@@ -168,6 +169,9 @@ __device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
 // cells are a hair wider than the tolerance, so that two points in range can never end up two cells apart through the
 // rounding of the division
 __device__ __forceinline__ int cell_coord(float v, float tol) { return (int)floorf(v / (tol * 1.0001f)); }
+// a point with a NaN / inf coordinate is in range of nothing (every comparison with it is false): a singleton that
+// never enters the cell table, so no non-finite value reaches cell_coord's int conversion
+__device__ __forceinline__ bool finite3(const float* q) { return isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]); }
 
 __global__ __launch_bounds__(CL_THREADS) void cluster_init_kernel(ClusterWs w, const unsigned* __restrict__ label, int P) {
     const int p = blockIdx.x * CL_THREADS + threadIdx.x;
@@ -177,6 +181,7 @@ __global__ __launch_bounds__(CL_THREADS) void cluster_init_kernel(ClusterWs w, c
     w.cls[p] = c;
     w.parent[p] = p;
     w.size[p] = 0;
+    w.nonfinite[p] = 0;
     w.sum[3 * (size_t)p + 0] = 0;
     w.sum[3 * (size_t)p + 1] = 0;
     w.sum[3 * (size_t)p + 2] = 0;
@@ -195,10 +200,19 @@ __global__ __launch_bounds__(CL_THREADS) void cluster_link_kernel(ClusterWs w, c
     } else {
         const float tol = class_tolerance(c);
         const float* q = pts + (size_t)p * stride;
+        if (!finite3(q)) return;
         const unsigned s = table_insert(w.cell_key, w.H - 1, cell_key_of(c, cell_coord(q[0], tol), cell_coord(q[1], tol),
                                                                          cell_coord(q[2], tol)));
         w.next[p] = atomicExch(&w.cell_head[s], p);
     }
+}
+
+// (ex^2 + ey^2) + ez^2 with every operation rounded on its own, in the oracle's order.  The pragma is what keeps it
+// so: __fmul_rn / __fadd_rn are a plain * and + to the compiler, which fused one product into the sum under hipcc's
+// default -ffp-contract=fast-honor-pragmas and moved the decision for distances within an ulp of the tolerance
+__device__ __forceinline__ float dist2_rn(float ex, float ey, float ez) {
+#pragma clang fp contract(off)
+    return (ex * ex + ey * ey) + ez * ez;
 }
 
 __global__ __launch_bounds__(CL_THREADS) void cluster_union_kernel(ClusterWs w, const float* __restrict__ pts, int stride,
@@ -215,6 +229,7 @@ __global__ __launch_bounds__(CL_THREADS) void cluster_union_kernel(ClusterWs w, 
     const float tol = class_tolerance(c);
     const float tol2 = tol * tol;
     const float* q = pts + (size_t)p * stride;
+    if (!finite3(q)) return;
     const float x = q[0], y = q[1], z = q[2];
     const int ix = cell_coord(x, tol), iy = cell_coord(y, tol), iz = cell_coord(z, tol);
     for (int dz = -1; dz <= 1; ++dz)
@@ -226,8 +241,7 @@ __global__ __launch_bounds__(CL_THREADS) void cluster_union_kernel(ClusterWs w, 
                     if (o >= p) continue;                       // every unordered pair once
                     const float* r = pts + (size_t)o * stride;
                     const float ex = x - r[0], ey = y - r[1], ez = z - r[2];
-                    // (dx^2 + dy^2) + dz^2 with individually rounded operations (no contraction): the oracle's order
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
+                    const float d2 = dist2_rn(ex, ey, ez);
                     if (d2 < tol2) uf_unite(w.parent, p, o);    // FLANN's radius search: strictly below
                 }
             }
@@ -247,9 +261,14 @@ __global__ __launch_bounds__(CL_THREADS) void cluster_flatten_kernel(ClusterWs w
     atomicAdd(&w.size[r], 1);
     const float* q = pts + (size_t)p * stride;
     const double k = 16777216.0;                                // 2^24: centimetre-free fixed point, order-independent sums
-    atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)r + 0]), (unsigned long long)llrint((double)q[0] * k));
-    atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)r + 1]), (unsigned long long)llrint((double)q[1] * k));
-    atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)r + 2]), (unsigned long long)llrint((double)q[2] * k));
+    int bad = 0;                                                // llrint of a NaN / inf is undefined: flag the axis instead
+    for (int a = 0; a < 3; ++a) {
+        if (isfinite(q[a]))
+            atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)r + a]), (unsigned long long)llrint((double)q[a] * k));
+        else
+            bad |= 1 << a;
+    }
+    if (bad) atomicOr(&w.nonfinite[r], bad);
 }
 
 __global__ __launch_bounds__(CL_THREADS) void cluster_collect_kernel(ClusterWs w, const unsigned* __restrict__ label, int P) {
@@ -286,9 +305,9 @@ __global__ __launch_bounds__(CL_THREADS) void cluster_rank_kernel(ClusterWs w, i
     }
     if (rank >= max_nodes) return;
     const double inv = 1.0 / (16777216.0 * (double)me.w);
-    centers[3 * rank + 0] = (double)w.sum[3 * (size_t)me.z + 0] * inv;
-    centers[3 * rank + 1] = (double)w.sum[3 * (size_t)me.z + 1] * inv;
-    centers[3 * rank + 2] = (double)w.sum[3 * (size_t)me.z + 2] * inv;
+    const int bad = w.nonfinite[me.z];                          // NaN in, NaN out - per axis, like the reference's mean
+    for (int a = 0; a < 3; ++a)
+        centers[3 * rank + a] = (bad >> a) & 1 ? (double)NAN : (double)w.sum[3 * (size_t)me.z + a] * inv;
     node_labels[rank] = node_class(me.x);
     node_sizes[rank] = me.w;
     w.node_of_root[me.z] = rank;
@@ -338,7 +357,8 @@ __global__ __launch_bounds__(CL_THREADS) void graph_nearest_kernel(const float* 
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) near[(size_t)i * n + j] = bi[0];
+    // no point of node i at a distance below +inf (NaN centre, or a node index that no point carries): -1
+    if (threadIdx.x == 0) near[(size_t)i * n + j] = bi[0] == 0x7fffffff ? -1 : bi[0];
 }
 
 __global__ __launch_bounds__(CL_THREADS) void graph_min_dis_kernel(const float* __restrict__ pts, int stride, int n,
@@ -348,8 +368,13 @@ __global__ __launch_bounds__(CL_THREADS) void graph_min_dis_kernel(const float* 
     const int i = e / n, j = e - i * n;
     double d = 0.0;
     if (i != j) {
-        const float* a = pts + (size_t)near[(size_t)i * n + j] * stride;
-        const float* b = pts + (size_t)near[(size_t)j * n + i] * stride;
+        const int na = near[(size_t)i * n + j], nb = near[(size_t)j * n + i];
+        if (na < 0 || nb < 0) {
+            min_dis[e] = (double)NAN;
+            return;
+        }
+        const float* a = pts + (size_t)na * stride;
+        const float* b = pts + (size_t)nb * stride;
         const double dx = (double)a[0] - (double)b[0], dy = (double)a[1] - (double)b[1], dz = (double)a[2] - (double)b[2];
         d = sqrt((dx * dx + dy * dy) + dz * dz);
     }
@@ -378,7 +403,7 @@ static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 size_t cluster_ws_bytes(int P) {
     const size_t p = (size_t)P, h = table_slots(P);
-    return align256(p * 4) * 5 + align256(p * 24) + align256(h * 8) + align256(h * 4) + align256((size_t)CL_INST_SLOTS * 8) +
+    return align256(p * 4) * 6 + align256(p * 24) + align256(h * 8) + align256(h * 4) + align256((size_t)CL_INST_SLOTS * 8) +
            align256((size_t)CL_INST_SLOTS * 4) + 256 + 256 + align256((size_t)CL_MAX_CAND * sizeof(int4));
 }
 
@@ -399,6 +424,7 @@ int launch_cluster_scan(const float* pts, int stride, const uint32_t* label, int
     w.next = reinterpret_cast<int*>(take(p * 4));
     w.size = reinterpret_cast<int*>(take(p * 4));
     w.node_of_root = reinterpret_cast<int*>(take(p * 4));
+    w.nonfinite = reinterpret_cast<int*>(take(p * 4));
     w.sum = reinterpret_cast<long long*>(take(p * 24));
     w.cell_key = reinterpret_cast<unsigned long long*>(take((size_t)w.H * 8));
     w.cell_head = reinterpret_cast<int*>(take((size_t)w.H * 4));

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import cluster_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -31,6 +33,10 @@ def test_scan_to_nodes_matches_oracle(go, seed, scale):
     np.testing.assert_array_equal(sc.node_sizes.cpu().numpy(), [int((inst == i).sum()) for i in node_inst])
     # centres: the oracle averages float64 copies of the float32 coordinates; the kernel sums 2^-24 m fixed point
     np.testing.assert_allclose(np.array(got["centers"]), np.array(want["centers"]), rtol=0, atol=1e-6)
+    # ... and that makes them reproducible bit for bit: the exact reference (tests/cluster_ref.py)
+    exact = cluster_ref.cluster_ref(pts, lab)
+    np.testing.assert_array_equal(sc.centers.cpu().numpy().view(np.int64), exact["centers"].view(np.int64))
+    np.testing.assert_array_equal(sc.point_node.cpu().numpy(), exact["point_node"])
     # the reference's intermediate cluster array, up to the order of the rows inside a cluster
     got_cl = glg.gen_labels(pts, lab)
     assert got_cl.shape == want_cl.shape
