@@ -746,7 +746,8 @@ int sgpr_ntn_any(const float* d_weight, const float* d_weight_block, const float
  * fused multiply-add; division and sqrt correctly rounded), so a record is reproducible bit for bit.
  *   hypothesis  h = (i, i', j, j'), i < i' real slots of A, j != j' real slots of B, la[i] == lb[j], la[i'] == lb[j'];
  *               u = a[i'].xy - a[i].xy, v = b[j'].xy - b[j].xy, lu = sqrt(ux ux + uy uy), lv alike; admissible iff
- *               lu >= min_base, lv > 0 and |lu - lv| <= tau_edge
+ *               lu >= min_base, lu lv > 0 (the float32 product den below: neither length is zero and the product does not
+ *               underflow, so c and s are never 0 / 0) and |lu - lv| <= tau_edge
  *   coarse      den = lu lv, c = (ux vx + uy vy) / den, s = (ux vy - uy vx) / den, ma = 0.5 (a[i].xy + a[i'].xy), mb
  *               alike, tx = mb.x - (c ma.x - s ma.y), ty = mb.y - (s ma.x + c ma.y)
  *   inlier      node p of A with some q of B: la[p] == lb[q], |a[p].z - b[q].z| <= tau_z and, px = (c a[p].x - s a[p].y)
@@ -767,9 +768,13 @@ int sgpr_ntn_any(const float* d_weight, const float* d_weight_block, const float
  * or infinite coordinate; the pair is not evaluated) leave inliers 0, base -1, hypotheses 0 and NaN transforms / rmse;
  * an index outside its graph set, negative included (the -1 padding of a top-k list), gives an all-zero record with
  * SGPR_VERIFY_INVALID_INDEX and touches nothing else.  Every byte of every record is written; results depend on the
- * arguments alone.  Checked before the device is touched: a NULL pointer (P > 0), P < 0, GA or GB < 0, a negative or
- * NaN tolerance or max_hyp < 1 give SGPR_E_INVALID, N outside 1..SGPR_VERIFY_MAX_NODES SGPR_E_NODES; P == 0 succeeds
- * without a launch.  One workgroup per pair, no workspace, no atomics on global memory; work per pair is about
+ * arguments alone.  With finite coordinates whose differences, squares and sums stay inside float32, flags == 0 comes
+ * with a finite coarse and refined transform.  Finite coordinates beyond that (|x| of about 1e19 and more) pass the
+ * input check and are evaluated by the same arithmetic: lu or lv may be +inf (|inf - inf| is NaN: inadmissible; a finite
+ * length beside +inf is admissible only at tau_edge = +inf, with den = +inf and c = s = +-0 or NaN), so a record with
+ * flags == 0 may then carry a transform that is no rotation or is NaN.  Callers keep coordinates in sensor range.
+ * Checked before the device is touched: a NULL pointer (P > 0), P < 0, GA or GB < 0, a negative or NaN tolerance or
+ * max_hyp < 1 give SGPR_E_INVALID, N outside 1..SGPR_VERIFY_MAX_NODES SGPR_E_NODES; P == 0 succeeds without a launch.  One workgroup per pair, no workspace, no atomics on global memory; work per pair is about
  * hypotheses x same-label correspondences, and a single base pair adds at most nB^2 hypotheses past the cap.
  * Handle-free; runs on the caller's current device, asynchronous on `stream`. */
 typedef struct sgpr_verify_result {   /* 88 bytes */

@@ -2,7 +2,7 @@
 // centres of two graphs.  DESIGN.md §19.
 //
 //   hypothesis  h = (i, i', j, j'): two nodes of A and two same-labelled nodes of B whose planar distances agree
-//               (lu >= min_base, lv > 0, |lu - lv| <= tau_edge) fix a rotation about z and a translation in the plane
+//               (lu >= min_base, lu lv > 0, |lu - lv| <= tau_edge) fix a rotation about z and a translation in the plane
 //   inl(h)      = nodes p of A with a same-label node q of B within tau_z in height and tau_in in the plane after h
 //   result      = the hypothesis with the most inliers (ties: the lowest (i, i', j, j')), one float64 least-squares step
 //
@@ -235,7 +235,8 @@ __global__ __launch_bounds__(VF_T) void verify_kernel(const VerifyArgs g) {
                     const float4 b0 = B[j0], b1 = B[j1];
                     const float vx = b1.x - b0.x, vy = b1.y - b0.y;
                     const float lv = sqrtf(vx * vx + vy * vy);
-                    adm = j0 != j1 && lv > 0.f && fabsf(lu - lv) <= g.tau_edge;
+                    // (den = lu lv > 0: no zero length, no underflowing product - c and s are never 0 / 0)
+                    adm = j0 != j1 && lu * lv > 0.f && fabsf(lu - lv) <= g.tau_edge;
                 }
                 const unsigned long long bal = __ballot(adm);
                 if (lane == 0) wcnt[par][wave] = __popcll(bal);
