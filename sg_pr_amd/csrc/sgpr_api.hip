@@ -1,11 +1,12 @@
-// C-ABI entry points of libsgpr_hip.so (declared in include/sgpr.h) and the host-side
-// weight preparation: eval-mode BatchNorm folding + kernel-ready layout.
+// C-ABI entry points of libsgpr_hip.so (declared in include/sgpr.h).  The host-side weight preparation (eval-mode
+// BatchNorm folding + kernel-ready layouts) is sgpr_model.hpp; sgpr_create uploads what it packs.
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <atomic>
 #include <exception>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -57,117 +58,6 @@ static bool row0_ok(const char* fn, int row0, int R) {
     return true;
 }
 
-// The kernels are written for {12, 64, 64, 32, 16, 16}.  A SMALLER architecture is served exactly by the same kernels:
-// its tensors are embedded into the built shapes with zero weights (and neutral BatchNorm statistics) for the channels
-// it does not have - a channel whose weights are all zero stays 0 through conv / BN / LeakyReLU, adds 0 to every
-// distance, every sum and every maximum partner, and a zero tensor / bottleneck neuron contributes 0 to the score.
-static bool dims_supported(const sgpr_dims* d) {
-    return d && d->num_labels >= 1 && d->num_labels <= kLabels && d->filters_1 >= 1 && d->filters_1 <= kF1 &&
-           d->filters_2 >= 1 && d->filters_2 <= kF2 && d->filters_3 >= 1 && d->filters_3 <= kF3 &&
-           d->tensor_neurons >= 1 && d->tensor_neurons <= kT && d->bottle_neck_neurons >= 1 && d->bottle_neck_neurons <= kB;
-}
-static bool dims_full(const sgpr_dims* d) {
-    return d->num_labels == kLabels && d->filters_1 == kF1 && d->filters_2 == kF2 && d->filters_3 == kF3 &&
-           d->tensor_neurons == kT && d->bottle_neck_neurons == kB;
-}
-
-// what the any-shape kernels (sgpr_generic.hip) serve
-static bool dims_generic(const sgpr_dims* d) {
-    return d && d->num_labels >= 1 && d->num_labels <= SGPR_GENERIC_MAX_LABELS && d->filters_1 >= 1 &&
-           d->filters_1 <= SGPR_GENERIC_MAX_FILTERS && d->filters_2 >= 1 && d->filters_2 <= SGPR_GENERIC_MAX_FILTERS &&
-           d->filters_3 >= 1 && d->filters_3 <= SGPR_GENERIC_MAX_F3 && d->tensor_neurons >= 1 &&
-           d->tensor_neurons <= SGPR_GENERIC_MAX_T && d->bottle_neck_neurons >= 1 && d->bottle_neck_neurons <= SGPR_GENERIC_MAX_T;
-}
-
-struct BlockShape {
-    int cout, cin2;
-};
-
-static void block_shapes(const sgpr_dims* d, BlockShape out[7]) {
-    // order of the blob: s_conv1, f_conv1, s_conv2, f_conv2, s_conv3, f_conv3, conv_end (sg_net.py:50-76)
-    out[0] = {d->filters_1, 6};
-    out[1] = {d->filters_1, 2 * d->num_labels};
-    out[2] = {d->filters_2, 2 * d->filters_1};
-    out[3] = {d->filters_2, 2 * d->filters_1};
-    out[4] = {d->filters_3, 2 * d->filters_2};
-    out[5] = {d->filters_3, 2 * d->filters_2};
-    out[6] = {d->filters_3, 2 * d->filters_3};
-}
-
-static size_t weights_count(const sgpr_dims* d);
-// the blob of a smaller architecture `d` scattered into the built architecture's blob layout
-static std::vector<float> pad_blob(const float* src, const sgpr_dims* d) {
-    const sgpr_dims full = {kLabels, kF1, kF2, kF3, kT, kB};
-    BlockShape bs[7], bf[7];
-    block_shapes(d, bs);
-    block_shapes(&full, bf);
-    std::vector<float> out(weights_count(&full), 0.f);
-    float* dst = out.data();
-    for (int b = 0; b < 7; ++b) {
-        const int co = bs[b].cout, ci = bs[b].cin2 / 2, CO = bf[b].cout, CI = bf[b].cin2 / 2;
-        // weight [cout][2 cin]: the (x_j - x_i) half and the x_i half keep their places in the wider halves (conv_end:
-        // the xyz3 half and the sem3 half of cat(xyz3, sem3))
-        for (int c = 0; c < co; ++c)
-            for (int i = 0; i < ci; ++i) {
-                dst[(size_t)c * 2 * CI + i] = src[(size_t)c * 2 * ci + i];
-                dst[(size_t)c * 2 * CI + CI + i] = src[(size_t)c * 2 * ci + ci + i];
-            }
-        src += (size_t)co * 2 * ci;
-        dst += (size_t)CO * 2 * CI;
-        const float neutral[4] = {1.f, 0.f, 0.f, 1.f};          // gamma, beta, running_mean, running_var
-        for (int v = 0; v < 4; ++v) {
-            for (int c = 0; c < CO; ++c) dst[c] = c < co ? src[c] : neutral[v];
-            src += co;
-            dst += CO;
-        }
-    }
-    const int f = d->filters_3, t = d->tensor_neurons, bn = d->bottle_neck_neurons;
-    for (int i = 0; i < f; ++i)                                  // attention.weight_matrix [F3][F3]
-        for (int j = 0; j < f; ++j) dst[(size_t)i * kF3 + j] = src[(size_t)i * f + j];
-    src += (size_t)f * f;
-    dst += (size_t)kF3 * kF3;
-    for (int i = 0; i < f; ++i)                                  // tensor_network.weight_matrix [F3][F3][T]
-        for (int j = 0; j < f; ++j)
-            for (int q = 0; q < t; ++q) dst[((size_t)i * kF3 + j) * kT + q] = src[((size_t)i * f + j) * t + q];
-    src += (size_t)f * f * t;
-    dst += (size_t)kF3 * kF3 * kT;
-    for (int q = 0; q < t; ++q)                                  // weight_matrix_block [T][2 F3]
-        for (int j = 0; j < f; ++j) {
-            dst[(size_t)q * 2 * kF3 + j] = src[(size_t)q * 2 * f + j];
-            dst[(size_t)q * 2 * kF3 + kF3 + j] = src[(size_t)q * 2 * f + f + j];
-        }
-    src += (size_t)t * 2 * f;
-    dst += (size_t)kT * 2 * kF3;
-    for (int q = 0; q < t; ++q) dst[q] = src[q];                 // tensor_network.bias [T]
-    src += t;
-    dst += kT;
-    for (int o = 0; o < bn; ++o)                                 // fully_connected_first.weight [B][T]
-        for (int q = 0; q < t; ++q) dst[(size_t)o * kT + q] = src[(size_t)o * t + q];
-    src += (size_t)bn * t;
-    dst += (size_t)kB * kT;
-    for (int o = 0; o < bn; ++o) dst[o] = src[o];                // fully_connected_first.bias [B]
-    src += bn;
-    dst += kB;
-    for (int o = 0; o < bn; ++o) dst[o] = src[o];                // scoring_layer.weight [1][B]
-    src += bn;
-    dst += kB;
-    dst[0] = src[0];                                             // scoring_layer.bias
-    return out;
-}
-
-static size_t weights_count(const sgpr_dims* d) {
-    BlockShape bs[7];
-    block_shapes(d, bs);
-    size_t n = 0;
-    for (int b = 0; b < 7; ++b) n += (size_t)bs[b].cout * bs[b].cin2 + 4 * (size_t)bs[b].cout;
-    const size_t f = d->filters_3, t = d->tensor_neurons, bn = d->bottle_neck_neurons;
-    n += f * f;                  // attention.weight_matrix
-    n += f * f * t + t * 2 * f + t;  // tensor_network
-    n += bn * t + bn;            // fully_connected_first
-    n += bn + 1;                 // scoring_layer
-    return n;
-}
-
 }  // namespace sgpr
 
 using namespace sgpr;
@@ -180,206 +70,8 @@ int sgpr_abi_version(void) { return SGPR_ABI_VERSION; }
 
 const char* sgpr_last_error(void) { return g_last_error.c_str(); }
 
-// w = hi + mid + lo with three round-to-nearest-even bf16 terms (exact to 24 bits)
-static unsigned short bf16_rne_host(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-static float bf16_to_float_host(unsigned short h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-static void split3_host(float w, unsigned short (&pl)[3]) {
-    pl[0] = bf16_rne_host(w);
-    float r = w - bf16_to_float_host(pl[0]);
-    pl[1] = bf16_rne_host(r);
-    r -= bf16_to_float_host(pl[1]);
-    pl[2] = bf16_rne_host(r);
-}
-
-#ifndef SGPR_WIDE_EMBED
-#define SGPR_WIDE_EMBED 1     // any-shape handles inside sgpr_wide.hip's limits embed on the matrix cores (0: A/B builds, plain fp32 only)
-#endif
-// The any-shape model of a blob (GenericModel): BatchNorm folded in double precision at the model's own dimensions,
-// uploaded as one allocation.  Blob order: s_conv1, f_conv1, s_conv2, f_conv2, s_conv3, f_conv3, conv_end, tail tensors.
-static int build_generic_model(const float* weights, const sgpr_dims* d, sgpr_handle* h) {
-    BlockShape bs[7];
-    block_shapes(d, bs);
-    std::vector<float> host;
-    size_t off_wa[6], off_wb[6], off_tb[6], off_wend = 0, off_tend = 0;
-    const float* src = weights;
-    GenericModel& m = h->gm;
-    memset(&m, 0, sizeof(m));
-    m.L = d->num_labels; m.f1 = d->filters_1; m.f2 = d->filters_2; m.f3 = d->filters_3;
-    m.T = d->tensor_neurons; m.B = d->bottle_neck_neurons;
-    m.cmax = std::max(std::max(3, m.L), std::max(m.f1, std::max(m.f2, m.f3)));
-    for (int b = 0; b < 7; ++b) {
-        const int cout = bs[b].cout, cin2 = bs[b].cin2, cin = cin2 / 2;
-        const float* W = src;
-        const float* gamma = W + (size_t)cout * cin2;
-        const float* beta = gamma + cout;
-        const float* mean = beta + cout;
-        const float* var = mean + cout;
-        src = var + cout;
-        if (b < 6) {
-            // blob order alternates the branches (s1, f1, s2, f2, s3, f3); the model keeps xyz layers 0..2, semantic 3..5
-            const int l6 = (b & 1) * 3 + (b >> 1);
-            m.cin[l6] = cin;
-            m.cout[l6] = cout;
-            const int cout8 = (cout + 7) & ~7;                      // [cin][cout8]: see GenericModel
-            off_wa[l6] = host.size();
-            host.resize(host.size() + (size_t)cout8 * cin, 0.f);
-            off_wb[l6] = host.size();
-            host.resize(host.size() + (size_t)cout8 * cin, 0.f);
-            off_tb[l6] = host.size();
-            host.resize(host.size() + cout8, 0.f);
-            for (int c = 0; c < cout; ++c) {
-                const double s = (double)gamma[c] / std::sqrt((double)var[c] + 1e-5);
-                for (int i = 0; i < cin; ++i) {
-                    const double w1 = W[(size_t)c * cin2 + i], w2 = W[(size_t)c * cin2 + cin + i];
-                    host[off_wa[l6] + (size_t)i * cout8 + c] = (float)(s * w1);            // acts on x_j
-                    host[off_wb[l6] + (size_t)i * cout8 + c] = (float)(s * (w2 - w1));     // acts on x_i
-                }
-                host[off_tb[l6] + c] = (float)((double)beta[c] - (double)mean[c] * s);
-            }
-        } else {
-            const int cout8 = (cout + 7) & ~7;
-            off_wend = host.size();
-            host.resize(host.size() + (size_t)cout8 * cin2, 0.f);
-            off_tend = host.size();
-            host.resize(host.size() + cout8, 0.f);
-            for (int c = 0; c < cout; ++c) {
-                const double s = (double)gamma[c] / std::sqrt((double)var[c] + 1e-5);
-                for (int i = 0; i < cin2; ++i) host[off_wend + (size_t)i * cout8 + c] = (float)(s * W[(size_t)c * cin2 + i]);
-                host[off_tend + c] = (float)((double)beta[c] - (double)mean[c] * s);
-            }
-        }
-    }
-    const size_t f = m.f3, t = m.T, bn = m.B;
-    const size_t off_tail = host.size();
-    const size_t n_tail = f * f + f * f * t + t * 2 * f + t + bn * t + bn + bn + 1;
-    host.insert(host.end(), src, src + n_tail);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_gblob), host.size() * sizeof(float));
-    if (e != hipSuccess) return hip_fail(e, "sgpr_create: any-shape model");
-    e = hipMemcpy(h->d_gblob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail(e, "sgpr_create: any-shape model upload");
-    const float* dv = h->d_gblob;
-    for (int l = 0; l < 6; ++l) {
-        m.wa[l] = dv + off_wa[l];
-        m.wb[l] = dv + off_wb[l];
-        m.tb[l] = dv + off_tb[l];
-    }
-    m.w_end = dv + off_wend;
-    m.t_end = dv + off_tend;
-    const float* q = dv + off_tail;
-    m.att_w = q;    q += f * f;
-    m.ntn_w = q;    q += f * f * t;
-    m.ntn_wb = q;   q += t * 2 * f;
-    m.ntn_bias = q; q += t;
-    m.fc1_w = q;    q += bn * t;
-    m.fc1_b = q;    q += bn;
-    m.fc2_w = q;    q += bn;
-    m.fc2_b = q;
-    {
-        const float* fc1 = host.data() + off_tail + (f * f + f * f * t + t * 2 * f + t);   // (the host copy of m.fc1_w ...)
-        const HeadRange hr = head_range(fc1, fc1 + bn * t + bn, (int)bn, (int)t);         // (... and of m.fc2_w)
-        m.head_scale = hr.scale;
-        m.head_nl2e = hr.nl2e;
-        m.head_f16 = hr.f16_ok;
-    }
-    // ---- the matrix-core form of the same folded weights (WideModel, sgpr_wide.hip) for moderately larger architectures:
-    //      widths padded to 32 with zeros, two f16 planes (w = hi + lo, 22 bits) in MFMA operand order.  Only for an
-    //      any-shape handle (the built shape runs on the tuned kernels) inside the limits and the f16 range.
-    WideModel& wm = h->wm;
-    memset(&wm, 0, sizeof(wm));
-    h->d_wblob = nullptr;
-    float wmax = 0.f;
-    for (size_t i = 0; i < off_tail; ++i) wmax = std::max(wmax, fabsf(host[i]));
-    if (h->generic_only && m.L <= SGPR_WIDE_MAX_LABELS && m.f1 <= SGPR_WIDE_MAX_FILTERS && m.f2 <= SGPR_WIDE_MAX_FILTERS &&
-        m.f3 <= SGPR_WIDE_MAX_F3 && wmax < 60000.f && SGPR_WIDE_EMBED) {
-        auto p32 = [](int v) { return (v + 31) & ~31; };
-        std::vector<unsigned short> planes;
-        std::vector<float> tbs;
-        size_t off_wh[7], off_tbp[7];
-        auto put = [&planes](float v, size_t at_hi, size_t at_lo) {
-            const _Float16 hi = (_Float16)v;
-            const _Float16 lo = (_Float16)(v - (float)hi);
-            memcpy(&planes[at_hi], &hi, 2);
-            memcpy(&planes[at_lo], &lo, 2);
-        };
-        for (int l = 0; l < 6; ++l) {
-            const int cin = m.cin[l], cout = m.cout[l], cout8 = (cout + 7) & ~7;
-            const int cinP = p32(cin), coutP = p32(cout), nct = 2 * coutP / 16, ks = cinP / 32;
-            wm.cinP[l] = cinP;
-            wm.coutP[l] = coutP;
-            off_wh[l] = planes.size();
-            planes.resize(planes.size() + (size_t)nct * ks * 2 * 512, 0);
-            off_tbp[l] = tbs.size();
-            tbs.resize(tbs.size() + coutP, 0.f);
-            for (int c = 0; c < cout; ++c) tbs[off_tbp[l] + c] = host[off_tb[l] + c];
-            for (int ct = 0; ct < nct; ++ct)
-                for (int st = 0; st < ks; ++st)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e8 = 0; e8 < 8; ++e8) {
-                            const int row = ct * 16 + (lane & 15), ch = 32 * st + 8 * (lane >> 4) + e8;
-                            const bool brow = row >= coutP;                         // b rows follow the a rows
-                            const int oc = brow ? row - coutP : row;
-                            float v = 0.f;
-                            if (oc < cout && ch < cin) v = host[(brow ? off_wb[l] : off_wa[l]) + (size_t)ch * cout8 + oc];
-                            const size_t base = off_wh[l] + ((size_t)(ct * ks + st) * 2) * 512 + (size_t)lane * 8 + e8;
-                            put(v, base, base + 512);
-                        }
-        }
-        {   // conv_end on cat(xyz3 [F3P], sem3 [F3P]): input channel F3P + c is the reference's f3 + c
-            const int f3 = m.f3, F3P = p32(f3), f8 = (f3 + 7) & ~7, nct = F3P / 16, ks = 2 * F3P / 32;
-            wm.F3P = F3P;
-            off_wh[6] = planes.size();
-            planes.resize(planes.size() + (size_t)nct * ks * 2 * 512, 0);
-            off_tbp[6] = tbs.size();
-            tbs.resize(tbs.size() + F3P, 0.f);
-            for (int c = 0; c < f3; ++c) tbs[off_tbp[6] + c] = host[off_tend + c];
-            for (int ct = 0; ct < nct; ++ct)
-                for (int st = 0; st < ks; ++st)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e8 = 0; e8 < 8; ++e8) {
-                            const int oc = ct * 16 + (lane & 15), ch = 32 * st + 8 * (lane >> 4) + e8;
-                            const int half = ch >= F3P ? 1 : 0, c = ch - half * F3P;
-                            float v = 0.f;
-                            if (oc < f3 && c < f3) v = host[off_wend + (size_t)(half * f3 + c) * f8 + oc];
-                            const size_t base = off_wh[6] + ((size_t)(ct * ks + st) * 2) * 512 + (size_t)lane * 8 + e8;
-                            put(v, base, base + 512);
-                        }
-        }
-        const size_t plane_bytes = (planes.size() * 2 + 255) & ~(size_t)255;
-        e = hipMalloc(&h->d_wblob, plane_bytes + tbs.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(h->d_wblob, planes.data(), planes.size() * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(static_cast<char*>(h->d_wblob) + plane_bytes, tbs.data(), tbs.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (h->d_wblob) (void)hipFree(h->d_wblob);
-            h->d_wblob = nullptr;
-            return hip_fail(e, "sgpr_create: matrix-core form of the any-shape model");
-        }
-        const unsigned short* pv = static_cast<const unsigned short*>(h->d_wblob);
-        const float* tv = reinterpret_cast<const float*>(static_cast<const char*>(h->d_wblob) + plane_bytes);
-        for (int l = 0; l < 6; ++l) {
-            wm.wh[l] = pv + off_wh[l];
-            wm.tbp[l] = tv + off_tbp[l];
-        }
-        wm.wh_end = pv + off_wh[6];
-        wm.tbp_end = tv + off_tbp[6];
-        wm.att_w = m.att_w;
-        wm.L = m.L;
-        wm.f3 = m.f3;
-        wm.ok = 1;
-    }
-    return SGPR_OK;
-}
-
+// Every layout is packed on the host first (sgpr_model.hpp); what follows only uploads the buffers and turns their
+// offsets into pointers.  A half-built handle is owned by `owner`: every failure path frees it through sgpr_destroy.
 int sgpr_create(const float* weights, size_t n_floats, const sgpr_dims* dims, int device, sgpr_handle** out) {
     if (!weights || !dims || !out) {
         set_error("sgpr_create: NULL argument");
@@ -395,170 +87,14 @@ int sgpr_create(const float* weights, size_t n_floats, const sgpr_dims* dims, in
                   std::to_string(weights_count(dims)));
         return SGPR_E_BLOB;
     }
-    if (!dims_supported(dims)) {
-        // larger than the shape the tuned kernels are built for {labels 12, filters 64/64/32, tensor 16, bottleneck 16}:
-        // the handle runs every call on the any-shape kernels (sgpr_generic.hip)
-        DeviceGuard guard(device);
-        sgpr_handle* h = new sgpr_handle();
-        memset(static_cast<void*>(h), 0, sizeof(*h));
-        h->device = device;
-        h->dims = *dims;
-        h->generic_only = 1;
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, device);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_status), sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemset(h->d_status, 0, sizeof(int32_t));
-        int rc = e == hipSuccess ? build_generic_model(weights, dims, h) : hip_fail(e, "sgpr_create");
-        if (rc != SGPR_OK) {
-            if (h->d_status) (void)hipFree(h->d_status);
-            if (h->d_gblob) (void)hipFree(h->d_gblob);
-            delete h;
-            return rc;
-        }
-        h->num_cus = prop.multiProcessorCount;
-        *out = h;
-        return SGPR_OK;
-    }
-    const float* user_weights = weights;
-    const sgpr_dims user_dims = *dims;
-    const sgpr_dims full_dims = {kLabels, kF1, kF2, kF3, kT, kB};
-    std::vector<float> padded;
-    if (!dims_full(dims)) {                  // a smaller architecture inside the built one (dims_supported)
-        padded = pad_blob(weights, dims);
-        weights = padded.data();
-        n_floats = padded.size();
-        dims = &full_dims;
-    }
-    BlockShape bs[7];
-    block_shapes(dims, bs);
-
-    // ---- fold BN (double precision) and lay out: 6 EdgeConv layers + conv_end + tail tensors
-    std::vector<float> packed;
-    size_t off_wf[7], off_tb[7];
-    int kp_of[7];
-    const float* src = weights;
-    for (int b = 0; b < 7; ++b) {
-        const int cout = bs[b].cout, cin2 = bs[b].cin2;
-        const float* W = src;
-        const float* gamma = W + (size_t)cout * cin2;
-        const float* beta = gamma + cout;
-        const float* mean = beta + cout;
-        const float* var = mean + cout;
-        src = var + cout;
-        if (b < 6) {
-            const int cin = cin2 / 2;
-            const int kp = cin <= kKPad ? kKPad : cin;
-            kp_of[b] = kp;
-            off_wf[b] = packed.size();
-            packed.resize(packed.size() + (size_t)2 * cout * kp, 0.f);
-            float* wf = packed.data() + off_wf[b];
-            for (int c = 0; c < cout; ++c) {
-                const double s = (double)gamma[c] / sqrt((double)var[c] + 1e-5);
-                for (int i = 0; i < cin; ++i) {
-                    const double w1 = W[(size_t)c * cin2 + i];        // multiplies (x_j - x_i)   dgcnn.py:47
-                    const double w2 = W[(size_t)c * cin2 + cin + i];  // multiplies x_i
-                    wf[(size_t)c * kp + i] = (float)(s * w1);
-                    wf[(size_t)(cout + c) * kp + i] = (float)(s * (w2 - w1));
-                }
-            }
-        } else {
-            kp_of[b] = cin2;
-            off_wf[b] = packed.size();
-            packed.resize(packed.size() + (size_t)cout * cin2, 0.f);
-            float* wf = packed.data() + off_wf[b];
-            for (int c = 0; c < cout; ++c) {
-                const double s = (double)gamma[c] / sqrt((double)var[c] + 1e-5);
-                for (int i = 0; i < cin2; ++i) wf[(size_t)c * cin2 + i] = (float)(s * W[(size_t)c * cin2 + i]);
-            }
-        }
-        off_tb[b] = packed.size();
-        packed.resize(packed.size() + cout, 0.f);
-        float* tb = packed.data() + off_tb[b];
-        for (int c = 0; c < cout; ++c) {
-            const double s = (double)gamma[c] / sqrt((double)var[c] + 1e-5);
-            tb[c] = (float)((double)beta[c] - (double)mean[c] * s);
-        }
-    }
-    const size_t f = kF3, t = kT, bn = kB;
-    auto append = [&](size_t n) {
-        size_t o = packed.size();
-        packed.insert(packed.end(), src, src + n);
-        src += n;
-        return o;
-    };
-    const size_t o_att = append(f * f);
-    const size_t o_ntw = append(f * f * t);
-    const size_t o_ntb = append(t * 2 * f);
-    const size_t o_ntbias = append(t);
-    const size_t o_fc1w = append(bn * t);
-    const size_t o_fc1b = append(bn);
-    const size_t o_fc2w = append(bn);
-    const size_t o_fc2b = append(1);
-    while (packed.size() % 4) packed.push_back(0.f);
-    const size_t o_ntwt = packed.size();      // NTN weight re-ordered [i][t][j] for the all-pairs prep kernel
-    packed.resize(packed.size() + f * f * t);
-    for (size_t i = 0; i < f; ++i)
-        for (size_t tt = 0; tt < t; ++tt)
-            for (size_t j = 0; j < f; ++j) packed[o_ntwt + (i * t + tt) * f + j] = packed[o_ntw + i * (f * t) + j * t + tt];
-    // ---- bf16 three-plane copies of the seven folded weight matrices, in MFMA operand order (sgpr_internal.hpp)
-    size_t off_wb[7];
-    for (int b = 0; b < 7; ++b) {
-        const int rows = b < 6 ? 2 * bs[b].cout : bs[b].cout, kp = kp_of[b];
-        const int nks = kp == 64 ? 2 : 1, nct = rows / 16;
-        std::vector<unsigned short> wb((size_t)nct * nks * 3 * 512, 0);
-        const float* wf = packed.data() + off_wf[b];
-        for (int ct = 0; ct < nct; ++ct)
-            for (int st = 0; st < nks; ++st)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int l15 = lane & 15, lq = lane >> 4;
-                        int kk;
-                        if (nks == 2) kk = 32 * st + 8 * lq + j;
-                        else kk = j < 4 ? 4 * lq + j : -1;
-                        unsigned short pl[3] = {0, 0, 0};
-                        if (kk >= 0 && kk < kp) split3_host(wf[(size_t)(ct * 16 + l15) * kp + kk], pl);
-                        for (int q = 0; q < 3; ++q) wb[(((size_t)(ct * nks + st) * 3 + q) * 64 + lane) * 8 + j] = pl[q];
-                    }
-        off_wb[b] = packed.size();
-        packed.resize(packed.size() + wb.size() / 2);
-        memcpy(packed.data() + off_wb[b], wb.data(), wb.size() * sizeof(unsigned short));
-    }
-
-    // ---- the same seven matrices as two f16 planes (w = hi + lo), [column tile][k-step][plane][lane][8]
-    size_t off_wh[7];
-    bool f16_ok = true;
-    for (int b = 0; b < 7; ++b) {
-        const int rows = b < 6 ? 2 * bs[b].cout : bs[b].cout, kp = kp_of[b];
-        const int nks = kp == 64 ? 2 : 1, nct = rows / 16;
-        std::vector<unsigned short> wh((size_t)nct * nks * 2 * 512, 0);
-        const float* wf = packed.data() + off_wf[b];
-        for (int ct = 0; ct < nct; ++ct)
-            for (int st = 0; st < nks; ++st)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int l15 = lane & 15, lq = lane >> 4;
-                        int kk;
-                        if (nks == 2) kk = 32 * st + 8 * lq + j;
-                        else kk = j < 4 ? 4 * lq + j : -1;
-                        unsigned short pl[2] = {0, 0};
-                        if (kk >= 0 && kk < kp) {
-                            const float v = wf[(size_t)(ct * 16 + l15) * kp + kk];
-                            if (!(fabsf(v) < 60000.f)) f16_ok = false;
-                            const _Float16 hi = (_Float16)v;
-                            const _Float16 lo = (_Float16)(v - (float)hi);
-                            memcpy(&pl[0], &hi, 2);
-                            memcpy(&pl[1], &lo, 2);
-                        }
-                        for (int q = 0; q < 2; ++q) wh[(((size_t)(ct * nks + st) * 2 + q) * 64 + lane) * 8 + j] = pl[q];
-                    }
-        off_wh[b] = packed.size();
-        packed.resize(packed.size() + wh.size() / 2);
-        memcpy(packed.data() + off_wh[b], wh.data(), wh.size() * sizeof(unsigned short));
-    }
-
-    while (packed.size() % 4) packed.push_back(0.f);
-    const size_t o_semtab = packed.size();      // graph-independent tables of the super-node branch + the largest value in them
-    packed.resize(packed.size() + kSemTableFloats + 4, 0.f);
+    // larger than the shape the tuned kernels are built for {labels 12, filters 64/64/32, tensor 16, bottleneck 16}:
+    // the handle runs every call on the any-shape kernels (sgpr_generic.hip); else the any-shape model of the same
+    // checkpoint serves node_num / K beyond the tuned kernels' limits
+    const bool generic_only = !dims_supported(dims);
+    const FoldedNet net = fold_model(weights, dims);
+    const PackedBuilt pb = generic_only ? PackedBuilt() : pack_built(net);
+    const PackedGeneric pg = pack_generic(net);
+    const PackedWide pw = pack_wide(net, generic_only);
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -568,96 +104,129 @@ int sgpr_create(const float* weights, size_t n_floats, const sgpr_dims* dims, in
         return SGPR_E_INVALID;
     }
     DeviceGuard guard(device);   // the caller's current device is restored on return
-    sgpr_handle* h = new sgpr_handle();
-    memset(h, 0, sizeof(*h));
+    struct Destroy {
+        void operator()(sgpr_handle* p) const { sgpr_destroy(p); }
+    };
+    std::unique_ptr<sgpr_handle, Destroy> owner(new sgpr_handle());
+    sgpr_handle* h = owner.get();
+    memset(static_cast<void*>(h), 0, sizeof(*h));
     h->device = device;
-    h->dims = user_dims;            // (what the caller loaded; the kernels run on the built shapes)
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-        h->num_cus = cus;
-    }
-    h->blob_floats = packed.size();
-    e = hipMalloc(reinterpret_cast<void**>(&h->d_blob), packed.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_status), sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(h->d_blob, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+    h->dims = *dims;             // (what the caller loaded; the tuned kernels run on the built shapes)
+    h->generic_only = generic_only ? 1 : 0;
+    if (hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->num_cus <= 0)
+        h->num_cus = 256;
+
+    auto upload = [&e](void* dst, const void* src, size_t bytes) {
+        if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+    };
+    e = hipMalloc(reinterpret_cast<void**>(&h->d_status), sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(h->d_status, 0, sizeof(int32_t));
-    if (e != hipSuccess) {
-        if (h->d_blob) (void)hipFree(h->d_blob);
-        if (h->d_status) (void)hipFree(h->d_status);
-        delete h;
-        return hip_fail(e, "sgpr_create: device allocation / upload");
+    if (e == hipSuccess && !generic_only) e = hipMalloc(reinterpret_cast<void**>(&h->d_blob), pb.blob.size() * sizeof(float));
+    if (!generic_only) upload(h->d_blob, pb.blob.data(), pb.blob.size() * sizeof(float));
+    if (e != hipSuccess) return hip_fail(e, "sgpr_create: device allocation / upload");
+    e = hipMalloc(reinterpret_cast<void**>(&h->d_gblob), pg.blob.size() * sizeof(float));
+    upload(h->d_gblob, pg.blob.data(), pg.blob.size() * sizeof(float));
+    if (e != hipSuccess) return hip_fail(e, "sgpr_create: any-shape model");
+    if (pw.ok) {
+        e = hipMalloc(&h->d_wblob, pw.plane_bytes + pw.tbs.size() * sizeof(float));
+        upload(h->d_wblob, pw.planes.data(), pw.planes.size() * sizeof(unsigned short));
+        upload(static_cast<char*>(h->d_wblob) + pw.plane_bytes, pw.tbs.data(), pw.tbs.size() * sizeof(float));
+        if (e != hipSuccess) return hip_fail(e, "sgpr_create: matrix-core form of the any-shape model");
     }
-    // blob order is s1,f1,s2,f2,s3,f3 ; kernel order is f1,f2,f3,s1,s2,s3 (the semantic branch runs first: its 12
-    // input registers per thread die after the first staging, the 3 xyz registers wait for the second)
-    static const int blob_of_layer[6] = {1, 3, 5, 0, 2, 4};
+
+    GenericModel& m = h->gm;
+    m.L = dims->num_labels; m.f1 = dims->filters_1; m.f2 = dims->filters_2; m.f3 = dims->filters_3;
+    m.T = dims->tensor_neurons; m.B = dims->bottle_neck_neurons;
+    m.cmax = pg.cmax;
+    const float* gv = h->d_gblob;
     for (int l = 0; l < 6; ++l) {
-        const int b = blob_of_layer[l];
-        h->w.wf[l] = h->d_blob + off_wf[b];
-        h->w.tb[l] = h->d_blob + off_tb[b];
-        h->w.wb[l] = reinterpret_cast<const unsigned short*>(h->d_blob + off_wb[b]);
-        h->w.wh[l] = reinterpret_cast<const unsigned short*>(h->d_blob + off_wh[b]);
-        h->w.kp[l] = kp_of[b];
-        h->w.cout[l] = bs[b].cout;
+        m.cin[l] = pg.cin[l];
+        m.cout[l] = pg.cout[l];
+        m.wa[l] = gv + pg.off_wa[l];
+        m.wb[l] = gv + pg.off_wb[l];
+        m.tb[l] = gv + pg.off_tb[l];
     }
-    h->w.wf_end = h->d_blob + off_wf[6];
-    h->w.tb_end = h->d_blob + off_tb[6];
-    h->w.wb_end = reinterpret_cast<const unsigned short*>(h->d_blob + off_wb[6]);
-    h->w.wh_end = reinterpret_cast<const unsigned short*>(h->d_blob + off_wh[6]);
-    h->f16_weights = f16_ok ? 1 : 0;
-    h->w.att_w = h->d_blob + o_att;
-    h->w.ntn_w = h->d_blob + o_ntw;
-    h->w.ntn_wt = h->d_blob + o_ntwt;
-    h->w.ntn_wb = h->d_blob + o_ntb;
-    h->w.ntn_bias = h->d_blob + o_ntbias;
-    h->w.fc1_w = h->d_blob + o_fc1w;
-    h->w.fc1_b = h->d_blob + o_fc1b;
-    h->w.fc2_w = h->d_blob + o_fc2w;
-    h->w.fc2_b = h->d_blob + o_fc2b;
-    {
-        const HeadRange hr = head_range(packed.data() + o_fc1w, packed.data() + o_fc2w, (int)bn, (int)t);
-        h->w.head_scale = hr.scale;
-        h->w.head_nl2e = hr.nl2e;
-        h->head_f16 = hr.f16_ok;
+    m.w_end = gv + pg.off_wend;
+    m.t_end = gv + pg.off_tend;
+    m.att_w = gv + pg.off_tail[kAttW];
+    m.ntn_w = gv + pg.off_tail[kNtnW];
+    m.ntn_wb = gv + pg.off_tail[kNtnWb];
+    m.ntn_bias = gv + pg.off_tail[kNtnBias];
+    m.fc1_w = gv + pg.off_tail[kFc1W];
+    m.fc1_b = gv + pg.off_tail[kFc1B];
+    m.fc2_w = gv + pg.off_tail[kFc2W];
+    m.fc2_b = gv + pg.off_tail[kFc2B];
+    m.head_scale = pg.head.scale;
+    m.head_nl2e = pg.head.nl2e;
+    m.head_f16 = pg.head.f16_ok;
+
+    if (pw.ok) {
+        WideModel& wm = h->wm;
+        const unsigned short* pv = static_cast<const unsigned short*>(h->d_wblob);
+        const float* tv = reinterpret_cast<const float*>(static_cast<const char*>(h->d_wblob) + pw.plane_bytes);
+        for (int l = 0; l < 6; ++l) {
+            wm.cinP[l] = pw.cinP[l];
+            wm.coutP[l] = pw.coutP[l];
+            wm.wh[l] = pv + pw.off_wh[l];
+            wm.tbp[l] = tv + pw.off_tbp[l];
+        }
+        wm.wh_end = pv + pw.off_wh[6];
+        wm.tbp_end = tv + pw.off_tbp[6];
+        wm.F3P = pw.F3P;
+        wm.att_w = m.att_w;
+        wm.L = m.L;
+        wm.f3 = m.f3;
+        wm.ok = 1;
     }
-    h->w.sem_g = h->w.sem_xx = h->w.sem_a2 = h->w.sem_b2 = nullptr;
-    if (f16_ok) {
+    if (generic_only) {
+        *out = owner.release();
+        return SGPR_OK;
+    }
+
+    h->blob_floats = pb.blob.size();
+    DevWeights& w = h->w;
+    for (int l = 0; l < 6; ++l) {
+        w.wf[l] = h->d_blob + pb.off_wf[l];
+        w.tb[l] = h->d_blob + pb.off_tb[l];
+        w.wb[l] = reinterpret_cast<const unsigned short*>(h->d_blob + pb.off_wb[l]);
+        w.wh[l] = reinterpret_cast<const unsigned short*>(h->d_blob + pb.off_wh[l]);
+        w.kp[l] = pb.kp[l];
+        w.cout[l] = pb.cout[l];
+    }
+    w.wf_end = h->d_blob + pb.off_wf[6];
+    w.tb_end = h->d_blob + pb.off_tb[6];
+    w.wb_end = reinterpret_cast<const unsigned short*>(h->d_blob + pb.off_wb[6]);
+    w.wh_end = reinterpret_cast<const unsigned short*>(h->d_blob + pb.off_wh[6]);
+    w.att_w = h->d_blob + pb.off_tail[kAttW];
+    w.ntn_w = h->d_blob + pb.off_tail[kNtnW];
+    w.ntn_wt = h->d_blob + pb.off_ntwt;
+    w.ntn_wb = h->d_blob + pb.off_tail[kNtnWb];
+    w.ntn_bias = h->d_blob + pb.off_tail[kNtnBias];
+    w.fc1_w = h->d_blob + pb.off_tail[kFc1W];
+    w.fc1_b = h->d_blob + pb.off_tail[kFc1B];
+    w.fc2_w = h->d_blob + pb.off_tail[kFc2W];
+    w.fc2_b = h->d_blob + pb.off_tail[kFc2B];
+    w.head_scale = pb.head.scale;
+    w.head_nl2e = pb.head.nl2e;
+    h->head_f16 = pb.head.f16_ok;
+    h->f16_weights = pb.f16_ok ? 1 : 0;
+    if (pb.f16_ok) {
         // the graph-independent part of the super-node branch, by the kernels' own instructions (bit-identical to the
         // per-graph path); skipped when a layer-1 output leaves the f16 range (the per-graph path then flags the graph)
-        float* tab = h->d_blob + o_semtab;
+        float* tab = h->d_blob + pb.off_semtab;
         float vmax = INFINITY;
-        int rc = launch_sem_tables(h->w, tab, tab + kSemTableFloats, nullptr);
-        if (rc == SGPR_OK) {
-            e = hipMemcpy(&vmax, tab + kSemTableFloats, sizeof(float), hipMemcpyDeviceToHost);   // (synchronises)
-            if (e != hipSuccess) rc = hip_fail(e, "sgpr_create: super-node tables");
-        }
-        if (rc != SGPR_OK) {
-            (void)hipFree(h->d_blob);
-            (void)hipFree(h->d_status);
-            delete h;
-            return rc;
-        }
+        const int rc = launch_sem_tables(w, tab, tab + kSemTableFloats, nullptr);
+        if (rc != SGPR_OK) return rc;
+        e = hipMemcpy(&vmax, tab + kSemTableFloats, sizeof(float), hipMemcpyDeviceToHost);   // (synchronises)
+        if (e != hipSuccess) return hip_fail(e, "sgpr_create: super-node tables");
         if (vmax < 60000.f) {
-            h->w.sem_g = tab;
-            h->w.sem_xx = tab + 4 * 256;
-            h->w.sem_a2 = h->w.sem_xx + 32;
-            h->w.sem_b2 = h->w.sem_a2 + 2 * 16 * 64;
+            w.sem_g = tab;
+            w.sem_xx = tab + 4 * 256;
+            w.sem_a2 = w.sem_xx + 32;
+            w.sem_b2 = w.sem_a2 + 2 * 16 * 64;
         }
     }
-    // the any-shape model of the same checkpoint: serves node_num / K beyond the tuned kernels' limits
-    h->generic_only = 0;
-    h->d_gblob = nullptr;
-    {
-        const int rc = build_generic_model(user_weights, &user_dims, h);
-        if (rc != SGPR_OK) {
-            (void)hipFree(h->d_blob);
-            (void)hipFree(h->d_status);
-            if (h->d_gblob) (void)hipFree(h->d_gblob);      // (allocated, then its upload failed)
-            delete h;
-            return rc;
-        }
-    }
-    *out = h;
+    *out = owner.release();
     return SGPR_OK;
 }
 

@@ -7,50 +7,17 @@
 #include <string>
 
 #include "sgpr.h"
+#include "sgpr_model.hpp"
 
 namespace sgpr {
 
-// Architecture the kernels are written for (every shipped checkpoint; sgpr.h).
-constexpr int kLabels = 12;
-constexpr int kF1 = 64, kF2 = 64, kF3 = 32;
-constexpr int kT = 16;   // tensor_neurons
-constexpr int kB = 16;   // bottle_neck_neurons
-constexpr int kKPad = 16;  // layer-1 inputs (3 / 12 channels) are zero-padded to one MFMA k-block
+// (shape constants, dims predicates, head_range and the host-side packer: sgpr_model.hpp)
 
 // Device-resident, kernel-ready weights (all pointers into one allocation).
 //   EdgeConv layer l (order: s_conv1, s_conv2, s_conv3, f_conv1, f_conv2, f_conv3):
 //     wf[l] : [2*cout][kp] row-major.  rows [0,cout)      = s * W[:, :C]          (acts on x_j)
 //                                      rows [cout,2cout)  = s * (W[:, C:] - W[:, :C])  (acts on x_i)
 //     tb[l] : [cout] = beta - mean * s,  s = gamma / sqrt(var + 1e-5)   (eval BatchNorm folded)
-// The scoring head's fold v[o][t] = fc2_w[o] fc1_w[o][t] (fp32, as every tail forms it) is cut into two f16 planes by
-// the matrix-core tails.  A plane pair keeps 22 significant bits only where the low plane is normal (|v| >= 2^-3); below
-// that the low plane's step is a fixed 2^-24.  The tails therefore cut 2^k v, k >= 0 the largest power that keeps
-// max |2^k v| below 2^15 (k <= 64), scale b1 by the same factor and undo it in the sigmoid's constant: exp2(z' (-log2 e
-// 2^-k) + ...) with z' = 2^k z is the unscaled product exactly.  f16_ok = 0: max |v| reaches 60000, no f16 plane can hold
-// the fold and the handle's tails run at fp32's range (the bf16 instance / the plain-fp32 kernel).
-struct HeadRange {
-    float scale, nl2e;
-    int f16_ok;
-};
-inline HeadRange head_range(const float* fc1_w, const float* fc2_w, int B, int T) {
-    float vmax = 0.f;
-    bool finite = true;
-    for (int o = 0; o < B; ++o)
-        for (int t = 0; t < T; ++t) {
-            const float v = fabsf(fc2_w[o] * fc1_w[(size_t)o * T + t]);
-            if (!(v <= 3.0e38f)) finite = false;
-            vmax = v > vmax ? v : vmax;
-        }
-    HeadRange r;
-    r.f16_ok = finite && vmax < 60000.f;
-    int k = 0;
-    if (r.f16_ok && vmax > 0.f)
-        while (k < 64 && ldexpf(vmax, k + 1) < 32768.f) ++k;
-    r.scale = ldexpf(1.f, k);
-    r.nl2e = ldexpf(-1.4426950408889634f, -k);
-    return r;
-}
-
 struct DevWeights {
     const float* wf[6];             // folded fp32 weights [2*cout][kp] (a rows, then b rows); host-side source of wb
     // the same weights as three bf16 planes (w = hi + mid + lo, exact to 24 bits) in MFMA operand order:
@@ -86,16 +53,10 @@ struct DevWeights {
     const float* sem_a2;  // [2][16][64]    layer 2's per-node term a = W1' x1
     const float* sem_b2;  // [2][16][64]    ... and b = (W2 - W1)' x1 + t
 };
-constexpr int kSemTableFloats = 4 * 256 + 32 + 2 * 2 * 16 * 64;
 
 // Any-shape model (sgpr_generic.hip): the folded fp32 weights at the model's own dimensions, for what the tuned kernels
 // are not built for - architectures beyond the built shape, node_num > SGPR_MAX_NODES, K > SGPR_MAX_K.
-#define SGPR_GENERIC_MAX_LABELS SGPR_ANY_MAX_LABELS
-#define SGPR_GENERIC_MAX_FILTERS SGPR_ANY_MAX_FILTERS
-#define SGPR_GENERIC_MAX_F3 SGPR_ANY_MAX_FILTERS_3
-#define SGPR_GENERIC_MAX_T SGPR_ANY_MAX_NEURONS          // tensor neurons and bottleneck neurons
-#define SGPR_GENERIC_MAX_NODES SGPR_ANY_MAX_NODES
-#define SGPR_GENERIC_MAX_K SGPR_ANY_MAX_K
+// (limits: SGPR_GENERIC_MAX_*, sgpr_model.hpp)
 struct GenericModel {
     int L, f1, f2, f3, T, B, cmax;      // cmax: widest activation row (max of 3, L, f1, f2, f3)
     int cin[6], cout[6];                // EdgeConv blocks: xyz branch (s_conv1..3), then the semantic branch (f_conv1..3)
@@ -121,10 +82,7 @@ struct GenericModel {
 // Matrix-core form of a GenericModel for MODERATELY larger architectures (sgpr_wide.hip): labels <= 32, filters_1 / 2 <= 128,
 // filters_3 <= 64; every width padded to a multiple of 32 with zero weights (exact: a padded channel is lrelu(0 + 0) = 0
 // and meets zero weights in the next layer).  Weights as two f16 planes in MFMA operand order, like DevWeights::wh.
-#define SGPR_WIDE_MAX_LABELS 32
-#define SGPR_WIDE_MAX_FILTERS 128
-#define SGPR_WIDE_MAX_F3 64
-#define SGPR_WIDE_MAX_NODES 112
+// (limits: SGPR_WIDE_MAX_*, sgpr_model.hpp)
 struct WideModel {
     int ok;                                // 0: this architecture / these weights are not served (limits, f16 range)
     int L, f3, F3P;                        // F3P = filters_3 padded

@@ -1845,6 +1845,30 @@ def test_f1_max_bit_pattern_bins_at_their_edges(eng):
     check(sc, lab, "rare positives")
 
 
+def test_create_refuses_a_device_beyond_the_count(oracle_sd):
+    """sgpr_create checks `device` against hipGetDeviceCount before it touches a device, for both kinds of handle: a
+    built-shape blob and an any-shape-only blob, device == count -> SGPR_E_INVALID naming the device, no handle, and the
+    caller's current device as it was."""
+    import ctypes
+    from sg_pr_amd import engine
+    lib = engine.load_library()
+    with open("/proc/self/maps") as f:
+        hip_path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    hip = ctypes.CDLL(hip_path)                   # (the runtime the library itself is linked to)
+    count, before, after = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    assert hip.hipGetDeviceCount(ctypes.byref(count)) == 0 and count.value >= 1
+    assert hip.hipGetDevice(ctypes.byref(before)) == 0
+    wide = engine.SgprDims(12, 64, 64, 64, 16, 16)                      # larger than the built shape: any-shape only
+    n_wide = lib.sgpr_weights_count(ctypes.byref(wide))
+    for dims, blob in ((engine.default_dims(), engine.blob_from_state_dict(oracle_sd)),
+                       (wide, np.full(n_wide, 0.25, dtype=np.float32))):
+        h = ctypes.c_void_p()
+        rc = lib.sgpr_create(blob.ctypes.data_as(ctypes.c_void_p), blob.size, ctypes.byref(dims), count.value, ctypes.byref(h))
+        assert rc == -1 and h.value is None                             # SGPR_E_INVALID
+        assert lib.sgpr_last_error() == b"sgpr_create: device %d of %d" % (count.value, count.value)
+        assert hip.hipGetDevice(ctypes.byref(after)) == 0 and after.value == before.value
+
+
 def test_smaller_architectures_run_on_the_built_kernels(oracle):
     """parser_sg.py:12-18 exposes filters_1/2/3, tensor_neurons and bottle_neck_neurons; the label count is a model
     argument (sg_net.py:40-76).  Every architecture no larger than the built one {12, 64, 64, 32, 16, 16} in any of the six
