@@ -522,6 +522,57 @@ int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                          const int32_t* h_offsets, int n_paths, int radius, int k, float* d_values, int32_t* d_indices,
                          unsigned char* d_codes, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-session maps: the path-set mean above where the rows and the columns are SEVERAL trajectories (sessions: a map
+ * recorded on earlier drives, then the current drive), stacked in time order.  Every call above takes the columns for one
+ * trajectory; on a stacked map its index window hides the true matches of a session that starts where the one before
+ * ended, and its diagonals average across the seam.  Here sums and the window stop at session boundaries.
+ * A SESSION TABLE is a HOST array starts[0..n-1], int32: starts[0] = 0, non-decreasing (a repeated value is an empty
+ * session), every value <= R (row table) or <= M (column table), n in 1..SGPR_SESSION_MAX; NULL with n = 0 means one
+ * session.  The arrays are copied into the launch and are free to reuse after the call returns.
+ *     sess(x) = the largest j with starts[j] <= x; an index below 0 counts as session 0 (an index at or past the end
+ *               falls, by the same rule, into the last session)
+ *     lo(x), hi(x) = the first and the last index of session sess(x): starts[j] and starts[j + 1] - 1 (the last session
+ *               ends at R - 1 / M - 1)
+ * For path p (sgpr_seq_path_filter's table; NULL with n_paths = 0 is the unit diagonal off[d] = d) and sigma = +1 / -1:
+ *     D_p(r, c)    = { d in 0..L-1 : r - d >= lo_row(r) and lo_col(c) <= c - sigma off_p[d] <= hi_col(c) }   (a prefix)
+ *     Q_{p,sigma}  = (S[r, c] + S[r-1, c - sigma off_p[1]] + ...) * rcp[|D_p|]
+ * Additions, the multiplication, the fold over the candidates, `code`, the context rows and NaN / inf propagation are
+ * sgpr_seq_path_filter's, bit for bit.
+ * SESSION WINDOW: with window >= 0, column c is excluded for row r iff sess_col(c) == sess_col(self_r) and
+ * |c - self_r| <= window, self_r = d_row_self[r] (device, [R]: context rows have entries too) or, d_row_self NULL,
+ * row0 + r.  Columns of other sessions are never window-excluded; terms are never masked.  SGPR_TOPK_CAUSAL keeps its
+ * meaning, c < self_r: sessions are stacked in time order, so every earlier session is visible.
+ * Identities: (1) one row session, one column session, window = -1: sgpr_seq_path_filter's bits and codes; (2) one
+ * session each, any window: the pooled call's lists are sgpr_score_path_topk's with radius = 0; (3) window = -1: the
+ * block Q[rows of row session i, columns of column session j] is sgpr_seq_path_filter run on that sub-matrix alone, a row
+ * session's context rows being the rows of that session before the block.
+ * - sgpr_session_filter: a resident matrix d_score [R][ld] -> d_out [R - ctx][ldo] and, unless NULL, d_code u8
+ *   [R - ctx][ldo]; an excluded end point gets -inf with code 0.  Out of place.  No workspace.  The causal flag is not
+ *   accepted (the pooled call hands it to its selection).  sgpr_seq_path_filter's tile and halo (sgpr_session.hip,
+ *   DESIGN.md §22).
+ * - sgpr_score_session_topk: sgpr_score_path_topk's arguments without `radius`, plus the two tables, and its structure
+ *   (row blocks with L - 1 context rows, the f16-range question answered once per call, every handle): the session filter
+ *   in place of the path filter with the row table shifted per block, then the large-k selection without a window (an
+ *   excluded end point is -inf and never listed).  The workspace equals sgpr_score_path_topk_workspace_bytes at
+ *   radius = 0 (n_paths = 0 counting as one path).
+ * Arguments are checked before the device is touched: those of sgpr_seq_path_filter / sgpr_score_path_topk, a window
+ * below -1, and a table that does not start at 0, decreases, has an entry past its limit, n outside
+ * 0..SGPR_SESSION_MAX, NULL with n > 0 (or a table with n = 0), a path table with n_paths = 0 give SGPR_E_INVALID with a
+ * message naming the fault (the workspace answer is 0 for invalid arguments).  R == ctx or M == 0 writes padding lists
+ * without scoring.  Results depend on the arguments alone.  Asynchronous on `stream`. */
+#define SGPR_SESSION_MAX 64
+int sgpr_session_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx, int L, int flags,
+                        const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts, int n_row_sessions,
+                        const int32_t* h_col_starts, int n_col_sessions, const int32_t* d_row_self, int row0, int window,
+                        float* d_out, int64_t ldo, unsigned char* d_code, void* stream);
+size_t sgpr_score_session_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int k,
+                                               int flags, int n_row_sessions, int n_col_sessions);
+int sgpr_score_session_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                            int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
+                            const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts, int n_row_sessions,
+                            const int32_t* h_col_starts, int n_col_sessions, int k, float* d_values, int32_t* d_indices,
+                            unsigned char* d_codes, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Hard-pair mining without the R x M matrix: for every row r the k (1..16) hardest pose-labelled pairs (r, c) of the
  * rectangle d_pooled_rows [R] x d_pooled_cols [M].
  * - Column c is eligible for row r iff it is for sgpr_score_topk (window, SGPR_TOPK_CAUSAL, self_r = d_row_self[r] or

@@ -1309,6 +1309,148 @@ int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                             d_workspace, workspace_bytes, stream, select, crng, L - 1);
 }
 
+// ---- sgpr_session_filter / sgpr_score_session_topk: the session-aware path-set filter (sgpr_session.hip) on a resident
+//      matrix, and on sgpr_score_path_topk's row blocks (radius 0) with the row table shifted per block; the window is the
+//      filter's, so the selection runs without one
+static bool session_paths_ok(const char* fn, const int32_t* h_offsets, int n_paths, int L) {
+    if (n_paths == 0 && !h_offsets) return true;          // the unit diagonal
+    if (n_paths == 0) {
+        set_error(std::string(fn) + ": a path table with n_paths = 0");
+        return false;
+    }
+    return seq_paths_ok(fn, h_offsets, n_paths, L);
+}
+
+static bool session_table_ok(const char* fn, const char* which, const int32_t* starts, int n, int limit) {
+    if (n < 0 || n > SGPR_SESSION_MAX) {
+        set_error(std::string(fn) + ": the number of " + which + " sessions must lie in 0.." +
+                  std::to_string(SGPR_SESSION_MAX));
+        return false;
+    }
+    if (!starts || n == 0) {
+        if (!starts && n == 0) return true;               // one session
+        set_error(std::string(fn) + (starts ? ": a " : ": NULL ") + which + " session table with n = " + std::to_string(n));
+        return false;
+    }
+    if (starts[0] != 0) {
+        set_error(std::string(fn) + ": the " + which + " session table does not start at 0");
+        return false;
+    }
+    for (int j = 1; j < n; ++j)
+        if (starts[j] < starts[j - 1]) {
+            set_error(std::string(fn) + ": the " + which + " session table has a decreasing entry at " + std::to_string(j));
+            return false;
+        }
+    if (starts[n - 1] > limit) {
+        set_error(std::string(fn) + ": the " + which + " session table has an entry past " + std::to_string(limit));
+        return false;
+    }
+    return true;
+}
+
+int sgpr_session_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx, int L, int flags,
+                        const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts, int n_row_sessions,
+                        const int32_t* h_col_starts, int n_col_sessions, const int32_t* d_row_self, int row0, int window,
+                        float* d_out, int64_t ldo, unsigned char* d_code, void* stream) {
+    const char* fn = "sgpr_session_filter";
+    if (!h || R < 0 || M < 0 || ld < M || ldo < M || window < -1) {
+        set_error("sgpr_session_filter: NULL handle, negative size, leading dimension below M or window below -1");
+        return SGPR_E_INVALID;
+    }
+    if (!seq_args_ok(fn, R, ctx, L, flags, SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)) return SGPR_E_INVALID;
+    if (!session_paths_ok(fn, h_offsets, n_paths, L)) return SGPR_E_INVALID;
+    if (!session_table_ok(fn, "row", h_row_starts, n_row_sessions, R) ||
+        !session_table_ok(fn, "column", h_col_starts, n_col_sessions, M) || !row0_ok(fn, row0, R))
+        return SGPR_E_INVALID;
+    if (R > ctx && M > 0 && (!d_score || !d_out)) {       // (an empty result needs no buffers)
+        set_error("sgpr_session_filter: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (R == ctx || M == 0) return SGPR_OK;
+    DeviceGuard guard(h->device);
+    return launch_session_filter(d_score, R, M, ld, ctx, L, flags, h_offsets, n_paths, h_row_starts, n_row_sessions,
+                                 h_col_starts, n_col_sessions, d_row_self, row0, window, d_out, ldo, d_code, ldo,
+                                 static_cast<hipStream_t>(stream));
+}
+
+size_t sgpr_score_session_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int k,
+                                               int flags, int n_row_sessions, int n_col_sessions) {
+    if (n_paths < 0 || n_row_sessions < 0 || n_row_sessions > SGPR_SESSION_MAX || n_col_sessions < 0 ||
+        n_col_sessions > SGPR_SESSION_MAX)
+        return 0;
+    return sgpr_score_path_topk_workspace_bytes(h, R, M, ctx, L, std::max(n_paths, 1), k, 0, flags);
+}
+
+int sgpr_score_session_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                            int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
+                            const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts, int n_row_sessions,
+                            const int32_t* h_col_starts, int n_col_sessions, int k, float* d_values, int32_t* d_indices,
+                            unsigned char* d_codes, void* d_workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "sgpr_score_session_topk";
+    if (!h || R < 0 || M < 0 || window < -1) {
+        set_error("sgpr_score_session_topk: NULL handle, negative count or window below -1");
+        return SGPR_E_INVALID;
+    }
+    if (!seq_args_ok(fn, R, ctx, L, flags, kSeqFlags)) return SGPR_E_INVALID;
+    if (!session_paths_ok(fn, h_offsets, n_paths, L)) return SGPR_E_INVALID;
+    if (!session_table_ok(fn, "row", h_row_starts, n_row_sessions, R) ||
+        !session_table_ok(fn, "column", h_col_starts, n_col_sessions, M))
+        return SGPR_E_INVALID;
+    if ((R > ctx && (!d_values || !d_indices)) || (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols))) {
+        set_error("sgpr_score_session_topk: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    if (!topk_large_args_ok(fn, R, k, flags & SGPR_TOPK_CAUSAL, row0)) return SGPR_E_INVALID;
+    if (!workspace_ok(fn, sgpr_score_session_topk_workspace_bytes(h, R, M, ctx, L, n_paths, k, flags, n_row_sessions,
+                                                                  n_col_sessions),
+                      d_workspace, workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    if (R == ctx) return SGPR_OK;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_code = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
+    const int np = std::max(n_paths, 1), seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE);
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0) {
+        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, -1,
+                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
+        if (rc != SGPR_OK || !d_codes) return rc;
+        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_code, d_codes, s);
+    }
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
+    const bool want_code = seq_both(flags) || np > 1;     // the code block follows the Q block (path_head_bytes)
+    const size_t q_at = 256 + sel_bytes;
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    int clean_rows = 0;                                   // histogram rows the selection before left clear
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0), no = r0 + n - first, base = r0 - c;
+        float* q = reinterpret_cast<float*>(head + q_at);
+        unsigned char* code = want_code ? head + q_at + blk_bytes : nullptr;
+        // the filter's rectangle is rows base .. r0 + n - 1: the row table moves with it.  A session that starts before
+        // `base` starts at the rectangle's row 0 - where it matters (base > 0) every output row has its L - 1 rows
+        // inside the rectangle, and a depth of L is a depth of L from either start
+        int32_t local[SGPR_SESSION_MAX];
+        for (int j = 0; j < n_row_sessions; ++j)
+            local[j] = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)h_row_starts[j] - base, 0), c + n);
+        int rc = launch_session_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, seq_flags, h_offsets, np,
+                                       h_row_starts ? local : nullptr, n_row_sessions, h_col_starts, n_col_sessions,
+                                       d_row_self ? d_row_self + base : nullptr, row0 + base, window, q, M, code, M, s);
+        if (rc != SGPR_OK) return rc;
+        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
+        const size_t o = (size_t)(first - ctx) * k;
+        rc = launch_select_rows(q, no, M, M, rs, row0 + first, -1, causal, k, d_values + o, d_indices + o, head + 256,
+                                select_group_rows(no) <= clean_rows, h->d_status, s);
+        clean_rows = select_group_rows(no);
+        if (rc != SGPR_OK || !d_codes) return rc;
+        return launch_seq_dirs(d_indices + o, no, k, code, M, fixed_code, d_codes + o, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, path_head_bytes(R, M, L, np, 0, flags), d_workspace,
+                            workspace_bytes, stream, select, crng, L - 1);
+}
+
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks
 //      and sgpr_mine_rows' kernel on the others) with the pose-class condition of the mined pairs
 static const int kMineFlags = SGPR_TOPK_CAUSAL | SGPR_MINE_NEGATIVES | SGPR_MINE_POSITIVES;

@@ -281,6 +281,13 @@ int launch_seq_dirs(const int32_t* idx, int n, int k, const unsigned char* dir, 
 // into code [R - ctx][ldc] (or nullptr)
 int launch_seq_path_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
                            int n_paths, float* out, int64_t ldo, unsigned char* code, int64_t ldc, hipStream_t stream);
+// the session-aware path-set filter of a resident R x M matrix (sgpr_session.hip): launch_seq_path_filter's arguments
+// (offsets == nullptr: the unit diagonal) with host session tables (already checked; nullptr: one session; copied into
+// the launch) and the session window on the end point (row_self [R] / row0 belong to the matrix's row 0; window < 0: none)
+int launch_session_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
+                          int n_paths, const int32_t* row_starts, int n_row, const int32_t* col_starts, int n_col,
+                          const int32_t* row_self, int row0, int window, float* out, int64_t ldo, unsigned char* code,
+                          int64_t ldc, hipStream_t stream);
 // the peak filter of a resident n x M block (sgpr_peak.hip): out [n][ldo] = score at a peak within `radius` columns, -inf
 // elsewhere; eligibility as launch_select_rows (row_self [n] / row0 belong to the block's row 0)
 int launch_peak_filter(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,

@@ -49,6 +49,7 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_seq_filter", "sgpr_score_seq_topk_workspace_bytes", "sgpr_score_seq_topk",
                "sgpr_peak_filter", "sgpr_score_peak_topk_workspace_bytes", "sgpr_score_peak_topk",
                "sgpr_seq_path_filter", "sgpr_score_path_topk_workspace_bytes", "sgpr_score_path_topk",
+               "sgpr_session_filter", "sgpr_score_session_topk_workspace_bytes", "sgpr_score_session_topk",
                "sgpr_score_mine_workspace_bytes", "sgpr_score_mine", "sgpr_mine_rows_workspace_bytes", "sgpr_mine_rows",
                "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
                "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
@@ -121,6 +122,21 @@ def _path_table(paths, seq_len):
     t = np.ascontiguousarray(np.asarray(paths, dtype=np.int32))
     if t.ndim != 2 or t.shape[1] != int(seq_len):
         raise ValueError("paths must be [P, %d], got %s" % (int(seq_len), tuple(t.shape)))
+    return t
+
+
+SESSION_MAX = 64            # SGPR_SESSION_MAX of include/sgpr.h
+
+
+def _session_table(starts):
+    """a host int32 C-contiguous array of session starts, or None (the library checks its contents)"""
+    if starts is None:
+        return None
+    if isinstance(starts, torch.Tensor):
+        starts = starts.cpu().numpy()
+    t = np.ascontiguousarray(np.asarray(starts, dtype=np.int32))
+    if t.ndim != 1 or t.shape[0] < 1:
+        raise ValueError("a session table is a 1-d array of at least one start, got shape %s" % (tuple(t.shape),))
     return t
 
 
@@ -260,6 +276,14 @@ def load_library():
     lib.sgpr_score_path_topk.restype = i32
     lib.sgpr_score_path_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp,
                                          vp, sz, vp]
+    lib.sgpr_session_filter.restype = i32
+    lib.sgpr_session_filter.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp,
+                                        i64, vp, vp]
+    lib.sgpr_score_session_topk_workspace_bytes.restype = sz
+    lib.sgpr_score_session_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32]
+    lib.sgpr_score_session_topk.restype = i32
+    lib.sgpr_score_session_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32,
+                                            i32, vp, vp, vp, vp, sz, vp]
     lib.sgpr_peak_filter.restype = i32
     lib.sgpr_peak_filter.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, i32, vp, i64, vp]
     lib.sgpr_score_peak_topk_workspace_bytes.restype = sz
@@ -1218,7 +1242,91 @@ class Engine:
         self._check(rc)
         return vals, idx, codes
 
-    PEAK_MAX_RADIUS = 1024   # SGPR_PEAK_MAX_RADIUS of include/sgpr.h
+    SESSION_MAX = SESSION_MAX
+
+    def session_filter(self, score, seq_len, paths=None, row_sessions=None, col_sessions=None, window=-1, row0=0,
+                       row_self=None, context=0, reverse=False, want_code=False, out=None, out_code=None):
+        """sgpr_session_filter: seq_path_filter on a stacked multi-session matrix.  row_sessions / col_sessions: the
+        first row / column of every session (int32, starting at 0, non-decreasing; None: one session).  Sums stop at the
+        edges of the end point's own row and column session; with window >= 0 column c is excluded (-inf, code 0) for
+        row r iff it lies in the session of self_r (row_self[r] or row0 + r) and |c - self_r| <= window.  paths None: the
+        unit diagonal.  -> Q f32 [R - context, M] (and, want_code, the code u8).  out / out_code as seq_filter's."""
+        if not isinstance(score, torch.Tensor):
+            score = torch.as_tensor(score)
+        if score.dim() != 2:
+            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
+        if score.device != self.device or score.dtype != torch.float32:
+            score = score.to(device=self.device, dtype=torch.float32)
+        table = None if paths is None else _path_table(paths, seq_len)
+        rt, ct = _session_table(row_sessions), _session_table(col_sessions)
+        r, m = score.shape
+        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
+            score = score.contiguous()
+        rs = self._row_self(row_self, r)
+        ro = max(r - int(context), 0)
+        if out is None:
+            out = torch.empty(ro, m, dtype=torch.float32, device=self.device)
+        if out_code is None and want_code:
+            out_code = torch.empty(ro, m, dtype=torch.uint8, device=self.device)
+        ldo = m
+        for t, dt, name in ((out, torch.float32, "out"), (out_code, torch.uint8, "out_code")):
+            if t is None:
+                continue
+            if t.device != self.device or t.dtype != dt or tuple(t.shape) != (ro, m) or (m > 1 and t.stride(1) != 1):
+                raise ValueError("%s must be a %s device tensor [%d, %d] with unit column stride" % (name, dt, ro, m))
+            if ro > 1:
+                ldo = max(ldo, t.stride(0))
+        if ro > 1 and out_code is not None and max(out.stride(0), m) != max(out_code.stride(0), m):
+            raise ValueError("out and out_code must share one row stride")
+        rc = self.lib.sgpr_session_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m,
+                                          int(context), int(seq_len), self._seq_flags(reverse),
+                                          None if table is None else table.ctypes.data,
+                                          0 if table is None else table.shape[0],
+                                          None if rt is None else rt.ctypes.data, 0 if rt is None else rt.shape[0],
+                                          None if ct is None else ct.ctypes.data, 0 if ct is None else ct.shape[0],
+                                          _ptr(rs), int(row0), int(window), _ptr(out), ldo, _ptr(out_code),
+                                          self._stream())
+        self._check(rc)
+        return (out, out_code) if (want_code or out_code is not None) else out
+
+    def score_session_topk_workspace_bytes(self, r, m, seq_len, n_paths=0, k=1, causal=False, context=0, reverse="both",
+                                           n_row_sessions=0, n_col_sessions=0):
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        return int(self.lib.sgpr_score_session_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
+                                                                    int(n_paths), int(k), flags, int(n_row_sessions),
+                                                                    int(n_col_sessions)))
+
+    def score_session_topk(self, pooled_rows, pooled_cols, seq_len, paths=None, row_sessions=None, col_sessions=None, k=1,
+                           window=-1, row0=0, causal=False, row_self=None, context=0, reverse="both"):
+        """sgpr_score_session_topk: score_path_topk's lists (radius 0) of the session-aware score (session_filter of
+        the rectangle, never formed beyond 64 MB row blocks) for rows context .. R-1 -> (values f32 [R - context, k],
+        indices i32, codes u8).  row_sessions counts over all R rows, the context rows included."""
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        table = None if paths is None else _path_table(paths, seq_len)
+        rt, ct = _session_table(row_sessions), _session_table(col_sessions)
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        ro = max(r - int(context), 0)
+        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
+        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
+        codes = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        n_paths = 0 if table is None else table.shape[0]
+        n_row, n_col = (0 if rt is None else rt.shape[0]), (0 if ct is None else ct.shape[0])
+        ws_bytes = self.lib.sgpr_score_session_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len), n_paths,
+                                                                    int(k), flags, n_row, n_col)
+        ws = self._ws(ws_bytes)
+        rc = self.lib.sgpr_score_session_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
+                                              int(window), flags, int(seq_len),
+                                              None if table is None else table.ctypes.data, n_paths,
+                                              None if rt is None else rt.ctypes.data, n_row,
+                                              None if ct is None else ct.ctypes.data, n_col, int(k), _ptr(vals),
+                                              _ptr(idx), _ptr(codes), _ptr(ws), ws_bytes, self._stream())
+        self._check(rc)
+        return vals, idx, codes
+
+    PEAK_MAX_RADIUS = 1024  # SGPR_PEAK_MAX_RADIUS of include/sgpr.h
     PEAK_STRIP = 1024        # SGPR_PEAK_STRIP: columns a workgroup of the peak filter owns
 
     def peak_filter(self, score, radius, window=-1, row0=0, causal=False, row_self=None, out=None):

@@ -324,11 +324,14 @@ def counts_of(score, gt):
     return pos, count_fn
 
 
-def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1024):
+def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1024, col_starts=None, row_mask=None):
     """Recall@1..K of loop-closure candidates (sgpr_score_topk's indices [M,K] of query frames 0..M-1 against frames
     0..M'-1; -1 = no candidate).  A query counts only if some frame it was allowed to match (|c - r| > window, window < 0:
     no window; causal: c < r) lies within p_thresh of it; it is a hit at N if one of its first N indices does.
     pose_xz: [M', 2] (or [M', 12] KITTI rows).  Plain torch on the indices' device, chunked by rows (not a hot path).
+    col_starts (the first frame of every session of a multi-session map, sgpr_session_filter's table): the allowed-match
+    rule uses the session window - a frame of another session than the query's is never window-excluded.
+    row_mask (bool [M]): only these queries are counted.
     -> float64 numpy [K]: hits at N / counted queries (0 when no query counts)."""
     import torch
     from .allpairs import pose_xz as _xz
@@ -337,6 +340,9 @@ def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1
     xz = _xz(pose_xz).to(dev)
     m, kk = idx.shape
     cols = torch.arange(xz.shape[0], device=dev)
+    if col_starts is not None:
+        starts = torch.as_tensor(np.asarray(col_starts, dtype=np.int64), device=dev)
+        col_sess = torch.searchsorted(starts, cols, right=True) - 1
     hits = torch.zeros(kk, dtype=torch.float64, device=dev)
     counted = 0
     for lo in range(0, m, chunk):
@@ -344,11 +350,16 @@ def recall_at_n(indices, pose_xz, p_thresh=3.0, window=50, causal=False, chunk=1
         rows = torch.arange(lo, hi, device=dev)
         near = torch.cdist(xz[lo:hi], xz) <= p_thresh                        # [n, M']
         ok = torch.ones_like(near)
-        if window >= 0:
+        if window >= 0 and col_starts is not None:
+            row_sess = torch.searchsorted(starts, rows, right=True) - 1
+            ok &= ((cols[None, :] - rows[:, None]).abs() > window) | (col_sess[None, :] != row_sess[:, None])
+        elif window >= 0:
             ok &= (cols[None, :] - rows[:, None]).abs() > window
         if causal:
             ok &= cols[None, :] < rows[:, None]
         valid = (near & ok).any(dim=1)                                       # queries with a revisit to find
+        if row_mask is not None:
+            valid &= torch.as_tensor(np.asarray(row_mask, dtype=bool)[lo:hi], device=dev)
         ix = idx[lo:hi].long()
         got = torch.zeros(ix.shape, dtype=torch.bool, device=dev)
         has = ix >= 0

@@ -18,6 +18,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
                                             [--verify] [--min-inliers I] [--distinct RHO] [--seq-slopes S,S,...]
+                                            [--sessions N]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -45,7 +46,15 @@ and the number of pairs verified in each mode is printed.  With --seq-len L > 1 
 speed-tolerant lists are retrieved as well - the best mean over the paths of these slopes (engine.seq_paths,
 engine.Engine.score_path_topk; --distinct composes): `<seq>_slopes.npz` holds frame, indices [M,K],
 scores [M,K], codes [M,K] (direction bit | path << 1), paths [P,L], recall, seq_len (and radius); printed are
-recall@1 and recall@K beside the unit-slope lists and the share of listed entries per path.
+recall@1 and recall@K beside the unit-slope lists and the share of listed entries per path.  With --sessions N
+(2..64) the sequence is also taken as a multi-session map: N consecutive near-equal sessions, session j starting at frame
+(j * M) // N, stored with new_session() between them and queried through the session call (sums and the window stop at
+session boundaries, engine.Engine.score_session_topk; --seq-len and --seq-slopes choose the score):
+`<seq>_sessions.npz` holds frame, indices [M,K], scores [M,K], codes [M,K], session_starts, recall, recall_head,
+recall_one_trajectory, recall_head_one_trajectory (and seq_len); printed are recall@1 and recall@K beside the
+one-trajectory lists, and the same pair for the head rows alone - the frames fewer than --window scans after the start
+of a session that has a predecessor.  All four are counted under the session rule for an allowed match
+(metrics.recall_at_n with col_starts), so the two lists are judged on the same queries.
 """
 import argparse
 import hashlib
@@ -72,6 +81,35 @@ class PlaceDatabase:
         self.k = int(model.args.K)
         self._buf = torch.empty(max(int(capacity), 1), self.eng.pw, dtype=torch.float32, device=self.eng.device)
         self.n = 0
+        self._starts = [0]                                   # the first member of every session (new_session)
+
+    @property
+    def session_starts(self):
+        """The first member id of every session, int32 [sessions] (one session: [0])."""
+        return np.asarray(self._starts, dtype=np.int32)
+
+    @property
+    def _multi(self):
+        return len(self._starts) > 1
+
+    def new_session(self):
+        """The members added from now on belong to a new session: a map recorded on an earlier drive ends here.  From
+        the second session on every query goes through the session call (engine.Engine.score_session_topk, DESIGN.md
+        §22): sums stop at session boundaries and the window excludes members of the query's own session only.
+        A session without members is not opened twice.  -> the index of the current session."""
+        if self.n > self._starts[-1]:
+            if len(self._starts) >= _engine.SESSION_MAX:
+                raise ValueError("new_session: more than %d sessions" % _engine.SESSION_MAX)
+            self._starts.append(self.n)
+        return len(self._starts) - 1
+
+    def _no_sessions(self, what):
+        if self._multi:
+            raise NotImplementedError("%s is not available on a database with more than one session" % what)
+
+    def _session_rows(self, base, count):
+        """the row table of members base .. base + count - 1 (a session that starts before `base` starts at row 0)"""
+        return np.clip(self.session_starts.astype(np.int64) - base, 0, count).astype(np.int32)
 
     def __len__(self):
         return self.n
@@ -110,6 +148,12 @@ class PlaceDatabase:
         -> (scores f32 [g,k], ids i32 [g,k]) on the device.  distinct=rho: the k best distinct places - score peaks
         within rho members (engine.Engine.score_peak_topk; the members are one trajectory, choose rho <= window).
         A causal query fed one scan at a time returns the lists of one offline causal call."""
+        if self._multi:
+            if distinct is not None:
+                self._no_sessions("distinct=")
+            return self.eng.score_session_topk(self._embed(centers, labels), self.pooled, 1, k=k, window=window,
+                                               row0=self.n, causal=causal, col_sessions=self.session_starts,
+                                               reverse=False)[:2]
         if distinct is not None:
             return self.eng.score_peak_topk(self._embed(centers, labels), self.pooled, int(distinct), k=k, window=window,
                                             row0=self.n, causal=causal)[:2]
@@ -123,6 +167,12 @@ class PlaceDatabase:
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n):
             raise IndexError("query_ids: ids must lie in [0, %d)" % self.n)
         rows = self.pooled.index_select(0, ids)
+        if self._multi:
+            if distinct is not None:
+                self._no_sessions("distinct=")
+            return self.eng.score_session_topk(rows, self.pooled, 1, k=k, window=window, causal=causal,
+                                               row_self=ids.to(torch.int32), col_sessions=self.session_starts,
+                                               reverse=False)[:2]
         if distinct is not None:
             return self.eng.score_peak_topk(rows, self.pooled, int(distinct), k=k, window=window, causal=causal,
                                             row_self=ids.to(torch.int32))[:2]
@@ -143,6 +193,15 @@ class PlaceDatabase:
         engine.Engine.score_path_topk) -> (scores, ids, codes u8: direction bit | path << 1).  Fed one scan at a time
         (causal) it returns the lists of one offline call iff window >= the paths' largest offset."""
         new = self._embed(centers, labels) if pooled is None else self.eng._pooled(pooled, "pooled")
+        if self._multi:                                      # context rows: members of the current session only
+            if distinct is not None:
+                self._no_sessions("distinct=")
+            ctx = min(int(seq_len) - 1, self.n - self._starts[-1])
+            rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
+            return self.eng.score_session_topk(rows, self.pooled, int(seq_len),
+                                               None if slopes is None else self._paths(seq_len, slopes),
+                                               col_sessions=self.session_starts, k=k, window=window, row0=self.n - ctx,
+                                               causal=causal, context=ctx, reverse=reverse)
         ctx = min(int(seq_len) - 1, self.n)
         rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
         if slopes is not None:
@@ -164,6 +223,14 @@ class PlaceDatabase:
         if first < 0 or count < 0 or first + count > self.n:
             raise IndexError("query_ids_seq: first .. first + count must lie in [0, %d]" % self.n)
         ctx = min(int(seq_len) - 1, first)
+        if self._multi:
+            if distinct is not None:
+                self._no_sessions("distinct=")
+            return self.eng.score_session_topk(self._buf[first - ctx:first + count], self.pooled, int(seq_len),
+                                               None if slopes is None else self._paths(seq_len, slopes),
+                                               row_sessions=self._session_rows(first - ctx, ctx + count),
+                                               col_sessions=self.session_starts, k=k, window=window, row0=first - ctx,
+                                               causal=causal, context=ctx, reverse=reverse)
         if slopes is not None:
             return self.eng.score_path_topk(self._buf[first - ctx:first + count], self.pooled, int(seq_len),
                                             self._paths(seq_len, slopes), k=k,
@@ -179,6 +246,7 @@ class PlaceDatabase:
     def query_ids_hard(self, ids, poses, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1, causal=False):
         """The k hardest negatives (positives=True: positives) of stored members ids among all members
         (Engine.score_mine with row_self = ids); poses [len, 12] or [len, 2] of every member."""
+        self._no_sessions("query_ids_hard")
         ids = torch.as_tensor(ids, dtype=torch.int64, device=self.eng.device)
         rows = self.pooled.index_select(0, ids)
         return self.eng.score_mine(rows, self.pooled, poses, k=k, positives=positives, d_pos=d_pos, d_neg=d_neg,
@@ -187,11 +255,13 @@ class PlaceDatabase:
     def query_above(self, centers, labels, threshold, window=-1, causal=False):
         """Every member scoring >= threshold for graphs that are NOT in the database (frames len(db), len(db) + 1, ...)
         -> (rows i32 [n], ids i32 [n], scores f32 [n], row_ptr i64 [g+1]) on the device (engine.Engine.score_above)."""
+        self._no_sessions("query_above")
         return self.eng.score_above(self._embed(centers, labels), self.pooled, threshold, window=window, row0=self.n,
                                     causal=causal)
 
     def query_ids_above(self, ids, threshold, window=-1, causal=False):
         """Every member scoring >= threshold for members `ids` (row_self = ids)."""
+        self._no_sessions("query_ids_above")
         ids = torch.as_tensor(ids, dtype=torch.int64).to(self._buf.device)
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n):
             raise IndexError("query_ids_above: ids must lie in [0, %d)" % self.n)
@@ -204,6 +274,7 @@ class PlaceDatabase:
         instead of ranked: every member whose sequence-matched score is >= threshold (engine.Engine.score_seq_above)
         -> (rows i32 [n], ids i32 [n], scores f32 [n], dirs u8 [n], row_ptr i64 [g+1]).  Fed one scan at a time it
         returns the pairs of one offline call, under query_seq's condition (causal, window >= seq_len - 1)."""
+        self._no_sessions("query_seq_above")
         new = self._embed(centers, labels) if pooled is None else self.eng._pooled(pooled, "pooled")
         ctx = min(int(seq_len) - 1, self.n)
         rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
@@ -213,6 +284,7 @@ class PlaceDatabase:
     def query_ids_seq_above(self, first, count, seq_len, threshold, window=-1, causal=False, reverse="both"):
         """Every member whose sequence-matched score is >= threshold for the run of members first .. first + count - 1
         (rows counted from `first`), the up to seq_len - 1 members before it serving as context rows."""
+        self._no_sessions("query_ids_seq_above")
         first, count = int(first), int(count)
         if first < 0 or count < 0 or first + count > self.n:
             raise IndexError("query_ids_seq_above: first .. first + count must lie in [0, %d]" % self.n)
@@ -222,12 +294,15 @@ class PlaceDatabase:
 
     def save(self, path):
         dims = np.array([getattr(self.eng.dims, f) for f in _DIMS], dtype=np.int64)
-        np.savez(path, pooled=self.pooled.cpu().numpy(), dims=dims, weights_sha256=np.array(weights_sha256(self.model)))
+        extra = {"session_starts": self.session_starts} if self._multi else {}
+        np.savez(path, pooled=self.pooled.cpu().numpy(), dims=dims, weights_sha256=np.array(weights_sha256(self.model)),
+                 **extra)
 
     @classmethod
     def load(cls, path, model):
         with np.load(path, allow_pickle=False) as z:
             pooled, dims, sha = z["pooled"], z["dims"], str(z["weights_sha256"])
+            starts = z["session_starts"] if "session_starts" in z.files else None
         if sha != weights_sha256(model):
             raise ValueError("%s was built with another checkpoint (weights sha256 %s...)" % (path, sha[:12]))
         db = cls(model, capacity=max(pooled.shape[0], 1))
@@ -235,6 +310,12 @@ class PlaceDatabase:
         if not np.array_equal(have, dims) or pooled.shape[1] != db.eng.pw:
             raise ValueError("%s holds vectors of another architecture (dims %s)" % (path, dims.tolist()))
         db.append_pooled(torch.from_numpy(pooled))
+        if starts is not None:
+            starts = [int(v) for v in starts]
+            if (not starts or starts[0] != 0 or any(b <= a for a, b in zip(starts, starts[1:])) or starts[-1] > db.n
+                    or len(starts) > _engine.SESSION_MAX):
+                raise ValueError("%s holds a broken session table %s" % (path, starts))
+            db._starts = starts
         return db
 
 
@@ -266,7 +347,14 @@ def main(argv=None):
     ap.add_argument("--seq-slopes", default=None, metavar="S,S,...",
                     help="with --seq-len: also retrieve the lists of the best mean over paths of these slopes, e.g. "
                          "1,1/2,2/3,3/2,2; writes <seq>_slopes.npz")
+    ap.add_argument("--sessions", type=int, default=None, metavar="N",
+                    help="also retrieve with the sequence split into N consecutive sessions (2..%d); writes "
+                         "<seq>_sessions.npz" % _engine.SESSION_MAX)
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if opt.sessions is not None and not 2 <= opt.sessions <= _engine.SESSION_MAX:
+        ap.error("--sessions must lie in 2..%d" % _engine.SESSION_MAX)
+    if opt.sessions is not None and opt.distinct is not None:
+        ap.error("--sessions does not compose with --distinct")
     paths = None
     if opt.seq_slopes is not None:
         if opt.seq_len < 2:
@@ -373,6 +461,18 @@ def main(argv=None):
                   "recall@1 %.4f (unit slope %.4f)" % (srecall[0], urecall[0]),
                   "recall@%d %.4f (unit slope %.4f)" % (k, srecall[-1], urecall[-1]),
                   "share of listed entries per path", " ".join("%.3f" % x for x in share))
+        if opt.sessions is not None:
+            report = session_lists(db, seq.poses, opt.sessions, idx, k=k, window=opt.window, causal=opt.causal,
+                                   seq_len=opt.seq_len, p_thresh=float(args.p_thresh),
+                                   reverse={"off": False, "on": True, "both": "both"}[opt.seq_reverse],
+                                   slopes=slopes if paths is not None else None)
+            np.savez(os.path.join(args.output_path, sequence + "_sessions.npz"), frame=np.arange(m),
+                     **report, **({"seq_len": np.int64(opt.seq_len)} if opt.seq_len > 1 else {}))
+            for name, what in (("recall", "all rows"), ("recall_head", "head rows (%d)" % int(report["head_rows"]))):
+                one = report[name + "_one_trajectory"]
+                print("sequence", sequence, "sessions", opt.sessions, what,
+                      "recall@1 %.4f (one trajectory %.4f)" % (report[name][0], one[0]),
+                      "recall@%d %.4f (one trajectory %.4f)" % (k, report[name][-1], one[-1]))
         if opt.threshold is not None:
             rows, cols, scores, _ = db.query_ids_above(torch.arange(m), opt.threshold, window=opt.window,
                                                        causal=opt.causal)
@@ -399,6 +499,39 @@ def main(argv=None):
             print("sequence", sequence, "hard pairs k", opt.hard, "frames with a negative above their best positive",
                   int(hard["neg_above_pos"].sum()), "(exact: %d frames of %d)" % (int(hard["exact"].sum()), m))
     return results
+
+
+def session_lists(db, poses, sessions, one_idx, k=1, window=50, causal=False, seq_len=1, p_thresh=3.0, reverse="both",
+                  slopes=None):
+    """The members of `db` taken as `sessions` consecutive near-equal sessions (session j starts at (j * M) // sessions)
+    and retrieved through the session call; one_idx: the one-trajectory lists to judge beside them -> dict of numpy
+    arrays: indices, scores, codes, session_starts, recall / recall_head (head rows: fewer than `window` scans after
+    the start of a session with a predecessor) and the same two of one_idx, all under the session rule, head_rows."""
+    m = len(db)
+    sdb = PlaceDatabase(db.model, capacity=max(m, 1))
+    bounds = [(j * m) // int(sessions) for j in range(int(sessions))] + [m]
+    for a, b in zip(bounds, bounds[1:]):
+        sdb.new_session()
+        sdb.append_pooled(db.pooled[a:b])
+    starts = sdb.session_starts
+    if seq_len > 1:
+        vals, idx, codes = sdb.query_ids_seq(0, m, seq_len, k=k, window=window, causal=causal, reverse=reverse,
+                                             slopes=slopes)
+        codes = codes.cpu().numpy()
+    else:
+        vals, idx = sdb.query_ids(torch.arange(m), k=k, window=window, causal=causal)
+        codes = np.zeros(tuple(idx.shape), dtype=np.uint8)
+    frames = np.arange(m)
+    head = np.zeros(m, dtype=bool)
+    for s0 in starts[1:]:
+        head |= (frames >= s0) & (frames < s0 + max(int(window), 0))
+    kw = dict(p_thresh=p_thresh, window=window, causal=causal, col_starts=starts)
+    return {"indices": idx.cpu().numpy(), "scores": vals.cpu().numpy(), "codes": codes, "session_starts": starts,
+            "recall": metrics.recall_at_n(idx, poses, **kw),
+            "recall_head": metrics.recall_at_n(idx, poses, row_mask=head, **kw),
+            "recall_one_trajectory": metrics.recall_at_n(one_idx, poses, **kw),
+            "recall_head_one_trajectory": metrics.recall_at_n(one_idx, poses, row_mask=head, **kw),
+            "head_rows": np.int64(int(head.sum()))}
 
 
 def verify_lists(model, seq, values, indices, min_inliers, p_thresh, window=-1, causal=False):

@@ -147,7 +147,7 @@ class SG(torch.nn.Module):
         return self.engine().score_all_pairs(pooled_rows, pooled_cols, out=out)
 
     def loop_closures(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None, seq_len=1,
-                      seq_reverse="both", distinct=None, seq_slopes=None):
+                      seq_reverse="both", distinct=None, seq_slopes=None, row_sessions=None, col_sessions=None):
         """The k best columns per row of pooled_rows x pooled_cols without forming the matrix (engine.Engine.score_topk)
         -> (values f32 [R,k], indices i32 [R,k]) on the device.  seq_len > 1: rows and columns are consecutive scans and
         the lists rank the sequence-matched score (engine.Engine.score_seq_topk; seq_reverse False / True / "both")
@@ -158,7 +158,20 @@ class SG(torch.nn.Module):
         result.  distinct=None: the plain lists.  seq_slopes (with seq_len > 1; e.g. ("1", "1/2", "2/3", "3/2", "2")): the
         score is the best mean over a set of paths of these slopes - a revisit driven at another speed
         (engine.seq_paths, engine.Engine.score_path_topk) -> (values, indices, codes u8 [R,k]: direction
-        bit | path << 1); it composes with distinct.  seq_slopes=None: the unit diagonal, exactly as before."""
+        bit | path << 1); it composes with distinct.  seq_slopes=None: the unit diagonal, exactly as before.
+        row_sessions / col_sessions (the first row / column of every session of a stacked multi-session map; either may
+        be None: one session): sums and the window stop at session boundaries (engine.Engine.score_session_topk,
+        DESIGN.md §22) -> (values, indices, codes), for every seq_len; not with distinct.  Both None: exactly as before."""
+        if row_sessions is not None or col_sessions is not None:
+            if distinct is not None:
+                raise ValueError("loop_closures: distinct is not available with session tables")
+            if seq_slopes is not None and int(seq_len) == 1:
+                raise ValueError("loop_closures: seq_slopes needs seq_len > 1")
+            paths = None if seq_slopes is None else _engine.seq_paths(int(seq_len), seq_slopes)
+            return self.engine().score_session_topk(pooled_rows, pooled_cols, int(seq_len), paths,
+                                                    row_sessions=row_sessions, col_sessions=col_sessions, k=k,
+                                                    window=window, row0=row0, causal=causal, row_self=row_self,
+                                                    reverse=seq_reverse)
         if seq_slopes is not None:
             if int(seq_len) == 1:
                 raise ValueError("loop_closures: seq_slopes needs seq_len > 1")
