@@ -745,6 +745,56 @@ int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_
                                     const unsigned long long* d_at_least, unsigned long long* d_out, void* d_workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* Thresholded closures on multi-session maps: the range retrieval of sgpr_seq_rows_above / sgpr_score_seq_above on the
+ * session-aware path-set score of sgpr_session_filter, with a MINIMUM TERM COUNT.  One session with the unit path is
+ * sgpr_seq_rows_above's score, one session with a path table is sgpr_seq_path_filter's.
+ * - S, the session tables, sess / lo / hi, D_p(r, c) and Q_{p,sigma} are sgpr_session_filter's, bit for bit: the fp32
+ *   additions in ascending d, the one multiplication by rcp[|D_p|], the context rows and the session window on the end
+ *   point.
+ * - MINIMUM TERM COUNT: min_terms lies in 1..L.  A candidate (p, sigma) takes part in the fold only when
+ *   |D_p(r, c)| >= min_terms.  The fold is sgpr_seq_path_filter's - paths in ascending p within a direction, forward
+ *   before reverse, q > best || best != best - run over the participating candidates in that order, the first of them
+ *   initialising it; `code` is the winner's, direction bit | p << 1.  An end point with no participating candidate is
+ *   NOT ELIGIBLE: never listed and never counted, not even at threshold = -inf.  With min_terms = 1 every candidate
+ *   participates (d = 0 is always in D) and Q and code are sgpr_session_filter's bits.
+ * - ELIGIBILITY: a pair (r, c) with ctx <= r < R is eligible when (1) it is not excluded by the session window
+ *   (window >= 0, sess_col(c) == sess_col(self_r) and |c - self_r| <= window), (2) under SGPR_TOPK_CAUSAL, c < self_r,
+ *   and (3) at least one candidate reaches min_terms; self_r = d_row_self[r] (device, [R]: context rows have entries
+ *   too) or row0 + r.  A pair is selected when it is eligible and Q >= threshold.  A NaN Q never qualifies; a NaN
+ *   threshold is SGPR_E_INVALID.
+ * - OUTPUT: sgpr_seq_rows_above's exactly.  Row-major (r, then c ascending); d_rows holds r - ctx, d_values the bits of
+ *   Q, d_codes (u8, may be NULL) the winner's code; d_row_ptr (int64 [R - ctx + 1], may be NULL) and *d_count are exact
+ *   also when `capacity` cuts the output; capacity = 0 with NULL arrays counts only; two calls return identical bytes.
+ *   ctx == R, R == 0 and M == 0 are valid empty calls.  A d_row_self entry outside [0, M) is reported by
+ *   sgpr_check_status (the bit sgpr_rows_above raises).
+ * - sgpr_session_rows_above: a resident matrix d_score [R][ld].  Two passes of sgpr_session_filter's tile kernel with
+ *   sgpr_seq_rows_above's range-select epilogue (sgpr_session_above.hip): no Q or code block exists.
+ *   Its workspace equals sgpr_seq_rows_above_workspace_bytes.
+ * - sgpr_score_session_above: the rectangle d_pooled_rows [R] x d_pooled_cols [M], every handle: sgpr_score_seq_above's
+ *   row blocks (L - 1 context rows, the f16-range question answered once per call, positions continuing on the device
+ *   across blocks) with the row table shifted per block as sgpr_score_session_topk shifts it.  Its workspace equals
+ *   sgpr_score_seq_above_workspace_bytes at equal R, M, ctx, L, flags: the paths' halo lives in LDS.
+ * Arguments are checked before the device is touched: those of sgpr_score_session_topk (paths, tables, window below -1),
+ * those of sgpr_score_seq_above, and min_terms outside 1..L give SGPR_E_INVALID with a message naming the fault (the
+ * workspace answer is 0 for invalid arguments), a workspace below the query SGPR_E_WORKSPACE.  Results depend on the
+ * arguments alone.  Asynchronous on `stream`. */
+size_t sgpr_session_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx);
+int sgpr_session_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx,
+                            const int32_t* d_row_self, int row0, int window, int flags, int L, const int32_t* h_offsets,
+                            int n_paths, const int32_t* h_row_starts, int n_row_sessions, const int32_t* h_col_starts,
+                            int n_col_sessions, int min_terms, float threshold, int32_t* d_rows, int32_t* d_cols,
+                            float* d_values, unsigned char* d_codes, int64_t capacity, int64_t* d_row_ptr,
+                            unsigned long long* d_count, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t sgpr_score_session_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int flags,
+                                                int n_row_sessions, int n_col_sessions);
+int sgpr_score_session_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                             int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
+                             const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts, int n_row_sessions,
+                             const int32_t* h_col_starts, int n_col_sessions, int min_terms, float threshold,
+                             int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_codes, int64_t capacity,
+                             int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* LDS bytes per workgroup the embed kernel uses for (N, k) on this handle; 0 if unsupported. */
 size_t sgpr_embed_lds_bytes(const sgpr_handle* h, int N, int k);
 

@@ -1725,6 +1725,120 @@ int sgpr_score_seq_above(const sgpr_handle* h, const float* d_pooled_rows, int R
                             workspace_bytes, stream, select, crng, L - 1);
 }
 
+// ---- sgpr_session_rows_above / sgpr_score_session_above: the range selection on the session-aware path-set score with a
+//      minimum term count (session_above_kernel, sgpr_session_above.hip) on a resident matrix, and on
+//      sgpr_score_seq_above's row blocks with the row table shifted per block as sgpr_score_session_topk shifts it
+static bool session_above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int ctx, int row0, int window,
+                                  int flags, int L, const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts,
+                                  int n_row_sessions, const int32_t* h_col_starts, int n_col_sessions, int min_terms,
+                                  float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity,
+                                  unsigned long long* d_count) {
+    if (!seq_above_args_ok(fn, h, R, M, ctx, row0, flags, L, threshold, d_rows, d_cols, d_values, capacity, d_count))
+        return false;
+    if (window < -1) {
+        set_error(std::string(fn) + ": window below -1");
+        return false;
+    }
+    if (!session_paths_ok(fn, h_offsets, n_paths, L)) return false;
+    if (!session_table_ok(fn, "row", h_row_starts, n_row_sessions, R) ||
+        !session_table_ok(fn, "column", h_col_starts, n_col_sessions, M))
+        return false;
+    if (min_terms < 1 || min_terms > L) {
+        set_error(std::string(fn) + ": min_terms must lie in 1..L, got " + std::to_string(min_terms));
+        return false;
+    }
+    return true;
+}
+
+size_t sgpr_session_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx) {
+    return sgpr_seq_rows_above_workspace_bytes(h, R, M, ctx);
+}
+
+int sgpr_session_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx,
+                            const int32_t* d_row_self, int row0, int window, int flags, int L, const int32_t* h_offsets,
+                            int n_paths, const int32_t* h_row_starts, int n_row_sessions, const int32_t* h_col_starts,
+                            int n_col_sessions, int min_terms, float threshold, int32_t* d_rows, int32_t* d_cols,
+                            float* d_values, unsigned char* d_codes, int64_t capacity, int64_t* d_row_ptr,
+                            unsigned long long* d_count, void* d_workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "sgpr_session_rows_above";
+    if (!session_above_args_ok(fn, h, R, M, ctx, row0, window, flags, L, h_offsets, n_paths, h_row_starts, n_row_sessions,
+                               h_col_starts, n_col_sessions, min_terms, threshold, d_rows, d_cols, d_values, capacity,
+                               d_count))
+        return SGPR_E_INVALID;
+    if (ld < M || (R > ctx && M > 0 && !d_score)) {
+        set_error("sgpr_session_rows_above: NULL score or ld < M");
+        return SGPR_E_INVALID;
+    }
+    if (!workspace_ok(fn, sgpr_session_rows_above_workspace_bytes(h, R, M, ctx), d_workspace, workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
+    unsigned char* ws = static_cast<unsigned char*>(d_workspace);
+    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(ws + seq_above_ws_bytes(R - ctx, M));
+    return launch_session_above(d_score, R, M, ld, ctx, L, flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE), h_offsets,
+                                n_paths, h_row_starts, n_row_sessions, h_col_starts, n_col_sessions, d_row_self, row0,
+                                window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, min_terms, threshold, d_rows, d_cols, d_values,
+                                d_codes, capacity, rp, 0, d_count, 0, ws, h->d_status, s);
+}
+
+size_t sgpr_score_session_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int flags,
+                                                int n_row_sessions, int n_col_sessions) {
+    if (n_paths < 0 || n_paths > SGPR_SEQ_MAX_PATHS || n_row_sessions < 0 || n_row_sessions > SGPR_SESSION_MAX ||
+        n_col_sessions < 0 || n_col_sessions > SGPR_SESSION_MAX)
+        return 0;
+    return sgpr_score_seq_above_workspace_bytes(h, R, M, ctx, L, flags);   // (the halo lives in LDS, not here)
+}
+
+int sgpr_score_session_above(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                             int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
+                             const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts, int n_row_sessions,
+                             const int32_t* h_col_starts, int n_col_sessions, int min_terms, float threshold,
+                             int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_codes, int64_t capacity,
+                             int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
+                             void* stream) {
+    const char* fn = "sgpr_score_session_above";
+    if (!session_above_args_ok(fn, h, R, M, ctx, row0, window, flags, L, h_offsets, n_paths, h_row_starts, n_row_sessions,
+                               h_col_starts, n_col_sessions, min_terms, threshold, d_rows, d_cols, d_values, capacity,
+                               d_count))
+        return SGPR_E_INVALID;
+    if (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols)) {
+        set_error("sgpr_score_session_above: NULL pooled vectors");
+        return SGPR_E_INVALID;
+    }
+    if (!workspace_ok(fn, sgpr_score_session_above_workspace_bytes(h, R, M, ctx, L, n_paths, flags, n_row_sessions,
+                                                                   n_col_sessions),
+                      d_workspace, workspace_bytes))
+        return SGPR_E_WORKSPACE;
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE);
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = seq_above_ws_bytes(rb, M);
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0), base = r0 - c;
+        int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(head + 256 + sel_bytes);
+        // the rectangle is rows base .. r0 + n - 1 and the row table moves with it (sgpr_score_session_topk's shift): a
+        // session that starts before `base` starts at the rectangle's row 0, and where that matters (base > 0) every
+        // output row has its L - 1 rows inside the rectangle - a depth of L from either start, so min_terms sees the same
+        int32_t local[SGPR_SESSION_MAX];
+        for (int j = 0; j < n_row_sessions; ++j)
+            local[j] = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)h_row_starts[j] - base, 0), c + n);
+        return launch_session_above(block - (size_t)c * M, c + n, M, M, c + first - r0, L, seq_flags, h_offsets, n_paths,
+                                    h_row_starts ? local : nullptr, n_row_sessions, h_col_starts, n_col_sessions,
+                                    d_row_self ? d_row_self + base : nullptr, row0 + base, window, causal, min_terms,
+                                    threshold, d_rows, d_cols, d_values, d_codes, capacity, rp + (first - ctx),
+                                    first - ctx, d_count, first > ctx ? 1 : 0, head + 256, h->d_status, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_above_head_bytes(R, M, ctx, L), d_workspace,
+                            workspace_bytes, stream, select, crng, L - 1);
+}
+
 // ---- sgpr_score_positives / sgpr_score_threshold_counts: the fused evaluation epilogues on the production handle; the
 //      other handles score bounded row blocks with their own tail and run the matrix kernels on each block, row0
 //      advancing, the blocks' results added up on the device

@@ -324,6 +324,17 @@ int launch_seq_above(const float* score, int R, int M, int64_t ld, int ctx, int 
                      int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
                      unsigned char* odirs, int64_t cap, int64_t* row_ptr, int rout0, unsigned long long* count,
                      int accumulate, void* ws, int32_t* status, hipStream_t stream);
+// seq_above_rowscan_kernel on its own (sgpr_seq.hip): seg [n][nseg] -> exclusive offsets in place, cnt [n] = row totals
+int launch_seq_above_rowscan(int32_t* seg, int n, int nseg, int32_t* cnt, hipStream_t stream);
+// launch_seq_above on the session-aware path-set score with a minimum term count (sgpr_session_above.hip; sgpr_session_rows_above
+// and each row block of sgpr_score_session_above): launch_session_filter's paths, tables and session window, codes in
+// place of directions.  ws: seq_above_ws_bytes(R - ctx, M)
+int launch_session_above(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
+                         int n_paths, const int32_t* row_starts, int n_row, const int32_t* col_starts, int n_col,
+                         const int32_t* row_self, int row0, int window, int causal, int min_terms, float thr,
+                         int32_t* orows, int32_t* ocols, float* ovals, unsigned char* ocodes, int64_t cap,
+                         int64_t* row_ptr, int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status,
+                         hipStream_t stream);
 // the fused evaluation epilogues of the all-pairs tail (production handle): T >= 0 the threshold counts (count == NULL,
 // d_out [T + 3]), T < 0 the positives (out [cap], count [2]); the chunked path of the other handles adds block counts up
 size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T);

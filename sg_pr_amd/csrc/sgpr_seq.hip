@@ -242,6 +242,12 @@ __global__ __launch_bounds__(256) void seq_above_rowscan_kernel(int32_t* __restr
     if (lane == 0) cnt[o] = run;
 }
 
+int launch_seq_above_rowscan(int32_t* seg, int n, int nseg, int32_t* cnt, hipStream_t s) {
+    hipLaunchKernelGGL(seq_above_rowscan_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, seg, n, nseg, cnt);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "seq_above_rowscan_kernel launch");
+}
+
 static size_t seq_a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // seg [n][ceil(M / 64)] i32 | cnt [n] i32
@@ -302,9 +308,8 @@ int launch_seq_above(const float* score, int R, int M, int64_t ld, int ctx, int 
     hipLaunchKernelGGL(seq_above_kernel<1>, dim3((unsigned)(tx * ty)), dim3(SEQ_TC), lds, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "seq_above_kernel launch (pass 1)");
-    hipLaunchKernelGGL(seq_above_rowscan_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, a.seg, n, a.nseg, cnt);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "seq_above_rowscan_kernel launch");
+    rc = launch_seq_above_rowscan(a.seg, n, a.nseg, cnt, s);
+    if (rc != SGPR_OK) return rc;
     rc = launch_above_scan(cnt, n, row_ptr, count, accumulate, s);
     if (rc != SGPR_OK || cap == 0) return rc;              // (capacity 0: count only)
     hipLaunchKernelGGL(seq_above_kernel<2>, dim3((unsigned)(tx * ty)), dim3(SEQ_TC), lds, s, a);

@@ -58,6 +58,8 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_score_seq_above_workspace_bytes", "sgpr_score_seq_above",
                "sgpr_score_seq_positives_workspace_bytes", "sgpr_score_seq_positives",
                "sgpr_score_seq_threshold_counts_workspace_bytes", "sgpr_score_seq_threshold_counts",
+               "sgpr_session_rows_above_workspace_bytes", "sgpr_session_rows_above",
+               "sgpr_score_session_above_workspace_bytes", "sgpr_score_session_above",
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
                "sgpr_attention_pool_any", "sgpr_ntn_any", "sgpr_verify_pairs",
                "sgpr_edgeconv_train_workspace_bytes", "sgpr_edgeconv_train_forward", "sgpr_edgeconv_train_backward",
@@ -338,6 +340,16 @@ def load_library():
     lib.sgpr_score_seq_threshold_counts.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, dbl, dbl, vp, i64, vp,
                                                     i32, vp, i32, vp, vp, vp, sz, vp]
     lib.sgpr_embed_lds_bytes.restype = sz
+    lib.sgpr_session_rows_above_workspace_bytes.restype = sz
+    lib.sgpr_session_rows_above_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.sgpr_session_rows_above.restype = i32
+    lib.sgpr_session_rows_above.argtypes = [vp, vp, i32, i32, i64, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32,
+                                            i32, f32, vp, vp, vp, vp, i64, vp, vp, vp, sz, vp]
+    lib.sgpr_score_session_above_workspace_bytes.restype = sz
+    lib.sgpr_score_session_above_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32]
+    lib.sgpr_score_session_above.restype = i32
+    lib.sgpr_score_session_above.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32,
+                                             i32, f32, vp, vp, vp, vp, i64, vp, vp, vp, sz, vp]
     lib.sgpr_embed_lds_bytes.argtypes = [vp, i32, i32]
     lib.sgpr_knn.restype = i32
     lib.sgpr_knn.argtypes = [vp, i32, i32, i32, i32, vp, vp]
@@ -1644,6 +1656,84 @@ class Engine:
                                                  _ptr(out_c), _ptr(out_v), _ptr(out_d), cap, _ptr(row_ptr), _ptr(count),
                                                  _ptr(ws), ws_bytes, self._stream())
         return self._seq_above(r, m, context, capacity, call, want_dirs)
+
+    # ------------------------------------------------------------------ ... and on the session-aware path-set score
+    def session_rows_above_workspace_bytes(self, r, m, context=0):
+        return int(self.lib.sgpr_session_rows_above_workspace_bytes(self._h, int(r), int(m), int(context)))
+
+    def score_session_above_workspace_bytes(self, r, m, seq_len, n_paths=0, causal=False, context=0, reverse="both",
+                                            n_row_sessions=0, n_col_sessions=0):
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        return int(self.lib.sgpr_score_session_above_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
+                                                                     int(n_paths), flags, int(n_row_sessions),
+                                                                     int(n_col_sessions)))
+
+    @staticmethod
+    def _session_tables(paths, seq_len, row_sessions, col_sessions):
+        """(path table pointer, n_paths, row table pointer, n, column table pointer, n) and the arrays that own them"""
+        table = None if paths is None else _path_table(paths, seq_len)
+        rt, ct = _session_table(row_sessions), _session_table(col_sessions)
+        args = []
+        for t in (table, rt, ct):
+            args += [None, 0] if t is None else [t.ctypes.data, t.shape[0]]
+        return args, (table, rt, ct)
+
+    def session_rows_above(self, score, seq_len, threshold, paths=None, row_sessions=None, col_sessions=None, min_terms=1,
+                           window=-1, row0=0, causal=False, row_self=None, context=0, reverse="both", capacity=None,
+                           want_codes=True):
+        """seq_rows_above on the session-aware path-set score of a resident matrix score [R, M]
+        (sgpr_session_rows_above): every eligible pair of rows context .. R-1 whose session_filter value, folded over
+        the candidates with at least `min_terms` terms, is >= threshold -> (rows i32 [n] counted from `context`, cols
+        i32 [n], values f32 [n], codes u8 [n] (direction bit | path << 1; None for want_codes=False), row_ptr i64
+        [R - context + 1]), row-major.  paths / row_sessions / col_sessions / window as session_filter's; an end point
+        none of whose candidates has min_terms terms is never listed; capacity as in score_above."""
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
+                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
+            score = self._dev(score, torch.float32, "score")
+        r, m = score.shape
+        ld = max(score.stride(0), m)
+        rs = self._row_self(row_self, r)
+        tables, keep = self._session_tables(paths, seq_len, row_sessions, col_sessions)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        ws_bytes = self.lib.sgpr_session_rows_above_workspace_bytes(self._h, r, m, int(context))
+        ws = self._ws(ws_bytes)
+
+        def call(cap, out_r, out_c, out_v, out_d, row_ptr, count):
+            return self.lib.sgpr_session_rows_above(self._h, _ptr(score), r, m, ld, int(context), _ptr(rs), int(row0),
+                                                    int(window), flags, int(seq_len), *tables, int(min_terms),
+                                                    float(threshold), _ptr(out_r), _ptr(out_c), _ptr(out_v),
+                                                    _ptr(out_d), cap, _ptr(row_ptr), _ptr(count), _ptr(ws), ws_bytes,
+                                                    self._stream())
+        return self._seq_above(r, m, context, capacity, call, want_codes)
+
+    def score_session_above(self, pooled_rows, pooled_cols, seq_len, threshold, paths=None, row_sessions=None,
+                            col_sessions=None, min_terms=1, window=-1, row0=0, causal=False, row_self=None, context=0,
+                            reverse="both", capacity=None, want_codes=True):
+        """session_rows_above on the rectangle pooled_rows x pooled_cols without forming it (sgpr_score_session_above):
+        score_seq_above's row blocks with the row table moving with each block; neither the filtered scores nor their
+        codes are ever stored -> (rows, cols, values, codes, row_ptr).  row_sessions counts over all R rows, the
+        context rows included."""
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        rows = self._pooled(pooled_rows, "pooled_rows")
+        cols = self._pooled(pooled_cols, "pooled_cols")
+        r, m = rows.shape[0], cols.shape[0]
+        rs = self._row_self(row_self, r)
+        tables, keep = self._session_tables(paths, seq_len, row_sessions, col_sessions)
+        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        ws_bytes = self.lib.sgpr_score_session_above_workspace_bytes(self._h, r, m, int(context), int(seq_len), tables[1],
+                                                                     flags, tables[3], tables[5])
+        ws = self._ws(ws_bytes)
+
+        def call(cap, out_r, out_c, out_v, out_d, row_ptr, count):
+            return self.lib.sgpr_score_session_above(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs),
+                                                     int(row0), int(window), flags, int(seq_len), *tables, int(min_terms),
+                                                     float(threshold), _ptr(out_r), _ptr(out_c), _ptr(out_v),
+                                                     _ptr(out_d), cap, _ptr(row_ptr), _ptr(count), _ptr(ws), ws_bytes,
+                                                     self._stream())
+        return self._seq_above(r, m, context, capacity, call, want_codes)
 
     def score_seq_positives_workspace_bytes(self, r, m, seq_len, context=0, reverse="both"):
         return int(self.lib.sgpr_score_seq_positives_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),

@@ -403,13 +403,16 @@ def recall_at_percent(indices, pose_xz, percent=1.0, p_thresh=3.0, window=50, ca
     return float(recall_at_n(idx[:, :n], pose_xz, p_thresh=p_thresh, window=window, causal=causal)[n - 1]), n
 
 
-def precision_recall_at(rows, cols, pose_xz, p_thresh=3.0, n_thresh=20.0, window=50, causal=False, chunk=None):
+def precision_recall_at(rows, cols, pose_xz, p_thresh=3.0, n_thresh=20.0, window=50, causal=False, chunk=None,
+                        col_starts=None):
     """Precision and recall of a list of accepted pairs (sgpr_score_above's rows / cols of query frames 0..M-1 against
     frames 0..M-1, M = len(pose_xz)) under the repository's pair classes: distance <= p_thresh positive, >= n_thresh
     negative, in between not counted.  precision = positives / (positives + negatives) among the pairs; recall =
     positives among the pairs / every eligible positive pair (|c - r| > window, window < 0: no window; causal: c < r),
     counted with plain torch on the poses, chunked by rows (not a hot path).  Distances are compared squared, in float64.
-    pose_xz: [M, 2] (or [M, 12] KITTI rows).  -> (precision, recall) floats, 0 where the denominator is 0."""
+    pose_xz: [M, 2] (or [M, 12] KITTI rows).  col_starts (the first frame of every session of a multi-session map):
+    the eligible positives follow the session window, as recall_at_n's - a frame of another session than the query's is
+    never window-excluded.  -> (precision, recall) floats, 0 where the denominator is 0."""
     import torch
     from .allpairs import pose_xz as _xz
     rows = torch.as_tensor(rows).long()
@@ -422,12 +425,17 @@ def precision_recall_at(rows, cols, pose_xz, p_thresh=3.0, n_thresh=20.0, window
     fp = int((d2 >= n2).sum())
     chunk = chunk or max(1, (1 << 24) // max(m, 1))
     allc = torch.arange(m, device=xz.device)
+    if col_starts is not None:
+        starts = torch.as_tensor(np.asarray(col_starts, dtype=np.int64), device=xz.device)
+        col_sess = torch.searchsorted(starts, allc, right=True) - 1
     positives = 0
     for lo in range(0, m, chunk):
         hi = min(m, lo + chunk)
         r = torch.arange(lo, hi, device=xz.device)
         near = ((xz[lo:hi, None, :] - xz[None, :, :]) ** 2).sum(dim=2) <= p2
-        if window >= 0:
+        if window >= 0 and col_starts is not None:
+            near &= ((allc[None, :] - r[:, None]).abs() > window) | (col_sess[None, :] != col_sess[lo:hi, None])
+        elif window >= 0:
             near &= (allc[None, :] - r[:, None]).abs() > window
         if causal:
             near &= allc[None, :] < r[:, None]

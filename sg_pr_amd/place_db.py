@@ -105,7 +105,8 @@ class PlaceDatabase:
 
     def _no_sessions(self, what):
         if self._multi:
-            raise NotImplementedError("%s is not available on a database with more than one session" % what)
+            hint = " (query_closures / query_ids_closures threshold a multi-session map)" if what.endswith("_above") else ""
+            raise NotImplementedError("%s is not available on a database with more than one session%s" % (what, hint))
 
     def _session_rows(self, base, count):
         """the row table of members base .. base + count - 1 (a session that starts before `base` starts at row 0)"""
@@ -292,6 +293,39 @@ class PlaceDatabase:
         return self.eng.score_seq_above(self._buf[first - ctx:first + count], self.pooled, int(seq_len), threshold,
                                         window=window, row0=first - ctx, causal=causal, context=ctx, reverse=reverse)
 
+    def query_closures(self, centers, labels, threshold, seq_len=1, slopes=None, min_terms=1, window=-1, causal=False,
+                       reverse="both", pooled=None):
+        """Every member that new scans (NOT in the database: frames len(db), len(db) + 1, ... of the current session,
+        or, pooled=, their embedded vectors) are a closure of, on a map of any number of sessions
+        (engine.Engine.score_session_above): the session-aware path-set score - sums and the window stop at session
+        seams - folded over the candidates with at least `min_terms` terms, >= threshold.  The context rows are the up
+        to seq_len - 1 last members of the current session, as in query_seq; slopes as there (None: the unit path).
+        -> (rows i32 [n], ids i32 [n], scores f32 [n], codes u8 [n]: direction bit | path << 1, row_ptr i64 [g+1]).
+        Fed one scan at a time it returns the pairs of one offline query_ids_closures call, under query_seq's
+        condition (causal, window >= the paths' largest offset)."""
+        new = self._embed(centers, labels) if pooled is None else self.eng._pooled(pooled, "pooled")
+        ctx = min(int(seq_len) - 1, self.n - self._starts[-1])
+        rows = torch.cat((self._buf[self.n - ctx:self.n], new)) if ctx > 0 else new
+        return self.eng.score_session_above(rows, self.pooled, int(seq_len), threshold,
+                                            None if slopes is None else self._paths(seq_len, slopes),
+                                            col_sessions=self.session_starts, min_terms=int(min_terms), window=window,
+                                            row0=self.n - ctx, causal=causal, context=ctx, reverse=reverse)
+
+    def query_ids_closures(self, first, count, threshold, seq_len=1, slopes=None, min_terms=1, window=-1, causal=False,
+                           reverse="both"):
+        """query_closures for the run of members first .. first + count - 1 (their ids are their frames; rows counted
+        from `first`), the up to seq_len - 1 members before `first` serving as context rows; sums stop at the session
+        seams among them."""
+        first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > self.n:
+            raise IndexError("query_ids_closures: first .. first + count must lie in [0, %d]" % self.n)
+        ctx = min(int(seq_len) - 1, first)
+        return self.eng.score_session_above(self._buf[first - ctx:first + count], self.pooled, int(seq_len), threshold,
+                                            None if slopes is None else self._paths(seq_len, slopes),
+                                            row_sessions=self._session_rows(first - ctx, ctx + count),
+                                            col_sessions=self.session_starts, min_terms=int(min_terms), window=window,
+                                            row0=first - ctx, causal=causal, context=ctx, reverse=reverse)
+
     def save(self, path):
         dims = np.array([getattr(self.eng.dims, f) for f in _DIMS], dtype=np.int64)
         extra = {"session_starts": self.session_starts} if self._multi else {}
@@ -350,7 +384,14 @@ def main(argv=None):
     ap.add_argument("--sessions", type=int, default=None, metavar="N",
                     help="also retrieve with the sequence split into N consecutive sessions (2..%d); writes "
                          "<seq>_sessions.npz" % _engine.SESSION_MAX)
+    ap.add_argument("--min-terms", type=int, default=None, metavar="K",
+                    help="with --threshold and --sessions or --seq-slopes: a path mean counts only with at least K terms "
+                         "(1..--seq-len; default 1)")
     opt = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if opt.min_terms is not None and opt.threshold is None:
+        ap.error("--min-terms needs --threshold")
+    if opt.min_terms is not None and not 1 <= opt.min_terms <= max(opt.seq_len, 1):
+        ap.error("--min-terms must lie in 1..--seq-len")
     if opt.sessions is not None and not 2 <= opt.sessions <= _engine.SESSION_MAX:
         ap.error("--sessions must lie in 2..%d" % _engine.SESSION_MAX)
     if opt.sessions is not None and opt.distinct is not None:
@@ -493,6 +534,15 @@ def main(argv=None):
                      recall=rec, seq_len=np.int64(opt.seq_len))
             print("sequence", sequence, "sequence length", opt.seq_len, "threshold", opt.threshold, "pairs", rows.numel(),
                   "precision %.4f recall %.4f" % (precision, rec))
+        if opt.threshold is not None and (opt.sessions is not None or paths is not None):
+            report = session_closures(db, seq.poses, opt.sessions or 1, opt.threshold, window=opt.window,
+                                      causal=opt.causal, seq_len=opt.seq_len, p_thresh=float(args.p_thresh),
+                                      reverse={"off": False, "on": True, "both": "both"}[opt.seq_reverse],
+                                      slopes=slopes if paths is not None else None, min_terms=opt.min_terms or 1)
+            np.savez(os.path.join(args.output_path, sequence + "_session_above.npz"), **report)
+            print("sequence", sequence, "sessions", opt.sessions or 1, "sequence length", opt.seq_len, "min terms",
+                  opt.min_terms or 1, "threshold", opt.threshold, "pairs", report["rows"].size,
+                  "precision %.4f recall %.4f" % (report["precision"], report["recall"]))
         if opt.hard is not None:
             hard = hard_pairs_of(db, seq.poses, opt.hard, float(args.p_thresh), window=opt.window, causal=opt.causal)
             np.savez(os.path.join(args.output_path, sequence + "_hard.npz"), frame=np.arange(m), **hard)
@@ -532,6 +582,29 @@ def session_lists(db, poses, sessions, one_idx, k=1, window=50, causal=False, se
             "recall_one_trajectory": metrics.recall_at_n(one_idx, poses, **kw),
             "recall_head_one_trajectory": metrics.recall_at_n(one_idx, poses, row_mask=head, **kw),
             "head_rows": np.int64(int(head.sum()))}
+
+
+def session_closures(db, poses, sessions, threshold, window=50, causal=False, seq_len=1, p_thresh=3.0, reverse="both",
+                     slopes=None, min_terms=1):
+    """The members of `db` taken as `sessions` consecutive near-equal sessions (session_lists' split) and thresholded
+    through PlaceDatabase.query_ids_closures -> dict of numpy arrays: rows, cols, scores, codes, row_ptr,
+    session_starts, seq_len, min_terms, precision and recall (metrics.precision_recall_at under the session rule)."""
+    m = len(db)
+    sdb = PlaceDatabase(db.model, capacity=max(m, 1))
+    bounds = [(j * m) // int(sessions) for j in range(int(sessions))] + [m]
+    for a, b in zip(bounds, bounds[1:]):
+        sdb.new_session()
+        sdb.append_pooled(db.pooled[a:b])
+    starts = sdb.session_starts
+    rows, cols, scores, codes, row_ptr = sdb.query_ids_closures(0, m, threshold, seq_len=seq_len, slopes=slopes,
+                                                                min_terms=min_terms, window=window, causal=causal,
+                                                                reverse=reverse)
+    precision, rec = metrics.precision_recall_at(rows, cols, poses, p_thresh=p_thresh, window=window, causal=causal,
+                                                 col_starts=starts)
+    return {"rows": rows.cpu().numpy(), "cols": cols.cpu().numpy(), "scores": scores.cpu().numpy(),
+            "codes": codes.cpu().numpy(), "row_ptr": row_ptr.cpu().numpy(), "session_starts": starts,
+            "seq_len": np.int64(seq_len), "min_terms": np.int64(min_terms), "precision": np.float64(precision),
+            "recall": np.float64(rec)}
 
 
 def verify_lists(model, seq, values, indices, min_inliers, p_thresh, window=-1, causal=False):

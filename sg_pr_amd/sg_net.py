@@ -232,11 +232,21 @@ class SG(torch.nn.Module):
                                         row_pose=row_pose)
 
     def loop_closures_above(self, pooled_rows, pooled_cols, threshold, window=-1, row0=0, causal=False, row_self=None,
-                            capacity=None, seq_len=1, seq_reverse="both"):
+                            capacity=None, seq_len=1, seq_reverse="both", seq_slopes=None, row_sessions=None,
+                            col_sessions=None, min_terms=1):
         """Every pair of pooled_rows x pooled_cols scoring >= threshold, without forming the matrix
         (engine.Engine.score_above) -> (rows i32 [n], cols i32 [n], values f32 [n], row_ptr i64 [R+1]) on the device.
         seq_len > 1: rows and columns are consecutive scans and the sequence-matched score is thresholded
-        (engine.Engine.score_seq_above; seq_reverse False / True / "both") -> (rows, cols, values, dirs u8 [n], row_ptr)."""
+        (engine.Engine.score_seq_above; seq_reverse False / True / "both") -> (rows, cols, values, dirs u8 [n], row_ptr).
+        seq_slopes (engine.seq_paths' slopes), row_sessions / col_sessions (the first row / column of every session of a
+        stacked multi-session map) or min_terms > 1: the session-aware path-set score, folded over the candidates with
+        at least min_terms terms (engine.Engine.score_session_above) -> (rows, cols, values, codes u8 [n], row_ptr)."""
+        if seq_slopes is not None or row_sessions is not None or col_sessions is not None or int(min_terms) != 1:
+            paths = None if seq_slopes is None else _engine.seq_paths(int(seq_len), seq_slopes)
+            return self.engine().score_session_above(pooled_rows, pooled_cols, int(seq_len), threshold, paths,
+                                                     row_sessions=row_sessions, col_sessions=col_sessions,
+                                                     min_terms=int(min_terms), window=window, row0=row0, causal=causal,
+                                                     row_self=row_self, reverse=seq_reverse, capacity=capacity)
         if int(seq_len) != 1:
             return self.engine().score_seq_above(pooled_rows, pooled_cols, int(seq_len), threshold, window=window,
                                                  row0=row0, causal=causal, row_self=row_self, reverse=seq_reverse,
