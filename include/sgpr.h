@@ -30,7 +30,7 @@
  *   - every entry point that takes a handle runs on the handle's device and
  *     restores the caller's current device before it returns; the handle-free
  *     entry points (sgpr_knn, sgpr_graph_feature, sgpr_attention_pool,
- *     sgpr_ntn, sgpr_verify_pairs) run on the caller's current device.
+ *     sgpr_ntn, sgpr_verify_pairs, sgpr_closure_consistency, sgpr_consistent_set) run on the caller's current device.
  */
 #ifndef SGPR_H
 #define SGPR_H
@@ -896,6 +896,56 @@ int sgpr_verify_pairs(const float* d_centers_a, const int32_t* d_labels_a, int G
                       const int32_t* d_idx_a, const int32_t* d_idx_b, int64_t P,
                       float tau_edge, float tau_in, float tau_z, float min_base, int max_hyp,
                       sgpr_verify_result* d_out, void* stream);
+
+/* ---- pairwise-consistent loop closures ---------------------------------------------------------------
+ * Which of C verified closures agree with one another through the odometry of the drives, and a large set that agrees
+ * pair by pair.  The reference has no such stage.  An SE(2) element E = (c, s, x, y) acts as p -> R p + t with
+ * R = [[c, -s], [s, c]]; all arithmetic is float64 and every operation is rounded on its own (no fused multiply-add;
+ * sqrt correctly rounded), so every output is reproducible bit for bit.
+ *   compose(A, B) (B first): c = A.c B.c - A.s B.s, s = A.s B.c + A.c B.s, x = (A.c B.x - A.s B.y) + A.x,
+ *               y = (A.s B.x + A.c B.y) + A.y;  inverse(A): c = A.c, s = -A.s, x = -(A.c A.x + A.s A.y),
+ *               y = A.s A.x - A.c A.y
+ *   closure p   d_rows[p], d_cols[p]: scan indices into d_Xr [MR,4] / d_Xc [MC,4], the planar odometry (each pose maps a
+ *               point of that scan into its session's own frame; sessions may live in unrelated frames); d_T [C,4]: the
+ *               `refined` field of sgpr_verify_pairs (a point of the row scan into the column scan); d_group[p]: the
+ *               problem the closure belongs to (row session x column session).  Rp = Xr[rows[p]], Cp = Xc[cols[p]],
+ *               G_p = compose(compose(Cp, T_p), inverse(Rp)), H_p = compose(inverse(T_p), inverse(Cp))
+ *   void        rows[p] or cols[p] outside its table, group[p] outside [0, n_groups), or any of the 12 doubles read is
+ *               not finite: a zero row and column, degree 0
+ *   pair        p < q of one group, neither void: D = compose(compose(H_q, G_p), R_q), dx = R_q.x - R_p.x,
+ *               dy = R_q.y - R_p.y, lever = sqrt(dx dx + dy dy), tau = max_trans + lever_gain lever; consistent iff
+ *               D.c >= min_cos and D.x D.x + D.y D.y <= tau tau.  min_cos is a cosine, formed by the caller.
+ *   d_adj       uint64 [C][ceil(C/64)]: bit q & 63 of word q >> 6 of row p = the test on (min(p,q), max(p,q)) - symmetric
+ *               by construction; 0 on the diagonal, across groups and at bit positions >= C.  Every word is written.
+ *   d_degree    int32 [C] = popcount of row p.
+ *   workspace   sgpr_closure_consistency_workspace_bytes(C) = roundup(4 C, 256) + 96 C bytes, any contents.  After the
+ *               call its first C int32 hold the members: group[p] of every closure that is not void, -1 of a void one -
+ *               the d_group to hand to sgpr_consistent_set.
+ * sgpr_consistent_set: the greedy clique of every group g on ANY bit matrix of that layout (symmetric or not).  cand =
+ * the closures with d_group[p] == g; while cand is not empty: d(v) = popcount(row_v & cand & ~bit v) for every v in cand,
+ * v* = the largest d, ties to the lowest index, d_rank[v*] = the number chosen before it in g, cand &= row_v* & ~bit v*.
+ * Bits at or beyond C and diagonal bits are ignored, so the loop ends after at most |group| rounds whatever the matrix
+ * holds.  d_rank int32 [C] (-1: not selected, d_group[p] outside [0, n_groups) included), d_group_size int32 [n_groups] =
+ * the size of each clique.  Workspace: sgpr_consistent_set_workspace_bytes(C) = roundup(4 C, 256) bytes, any contents.
+ * One workgroup per group; it keeps the counts up to date from what leaves cand (the same integers as recounting):
+ * n ceil(C/64) word operations to start, then per round (candidates left) x (words in which cand lost a bit) - about
+ * n^2 / 2 in all for a complete group of n closures - and three barriers per round.
+ * Checked before the device is touched, each with a message naming the fault (and the workspace queries answer 0): a
+ * NULL pointer with C > 0, C < 0 or > SGPR_CONSISTENCY_MAX_CLOSURES, MR or MC < 0, n_groups outside
+ * 1..SGPR_CONSISTENCY_MAX_GROUPS, a negative or NaN max_trans or lever_gain, a NaN min_cos: SGPR_E_INVALID; a missing or
+ * short workspace: SGPR_E_WORKSPACE.  C == 0 succeeds without a launch (d_group_size, if given, is zeroed).  Every
+ * output byte is written; no atomics on global memory; results depend on the arguments alone.  Handle-free; both run on
+ * the caller's current device, asynchronous on `stream`. */
+#define SGPR_CONSISTENCY_MAX_CLOSURES 16384
+#define SGPR_CONSISTENCY_MAX_GROUPS 4096
+size_t sgpr_closure_consistency_workspace_bytes(int C);
+int sgpr_closure_consistency(const int32_t* d_rows, const int32_t* d_cols, const double* d_T, int C, const double* d_Xr,
+                             int MR, const double* d_Xc, int MC, const int32_t* d_group, int n_groups, double max_trans,
+                             double min_cos, double lever_gain, uint64_t* d_adj, int32_t* d_degree, void* d_workspace,
+                             size_t workspace_bytes, void* stream);
+size_t sgpr_consistent_set_workspace_bytes(int C);
+int sgpr_consistent_set(const uint64_t* d_adj, int C, const int32_t* d_group, int n_groups, int32_t* d_rank,
+                        int32_t* d_group_size, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training: one EdgeConv block with BatchNorm in train mode ---------------------------
  * Replaces, for training, get_graph_feature -> Conv2d 1x1 -> BatchNorm2d (batch statistics) -> LeakyReLU(0.2) -> max

@@ -2362,6 +2362,86 @@ int sgpr_verify_pairs(const float* d_centers_a, const int32_t* d_labels_a, int G
                                tau_in, tau_z, min_base, max_hyp, d_out, static_cast<hipStream_t>(stream));
 }
 
+static bool consistency_counts_ok(const char* fn, int C, int n_groups) {
+    if (C < 0 || C > SGPR_CONSISTENCY_MAX_CLOSURES) {
+        set_error(std::string(fn) + ": C " + std::to_string(C) + " outside [0, " +
+                  std::to_string(SGPR_CONSISTENCY_MAX_CLOSURES) + "]");
+        return false;
+    }
+    if (n_groups < 1 || n_groups > SGPR_CONSISTENCY_MAX_GROUPS) {
+        set_error(std::string(fn) + ": n_groups " + std::to_string(n_groups) + " outside [1, " +
+                  std::to_string(SGPR_CONSISTENCY_MAX_GROUPS) + "]");
+        return false;
+    }
+    return true;
+}
+
+size_t sgpr_closure_consistency_workspace_bytes(int C) {
+    return (C < 0 || C > SGPR_CONSISTENCY_MAX_CLOSURES) ? 0 : closure_consistency_ws_bytes(C);
+}
+
+size_t sgpr_consistent_set_workspace_bytes(int C) {
+    return (C < 0 || C > SGPR_CONSISTENCY_MAX_CLOSURES) ? 0 : consistent_set_ws_bytes(C);
+}
+
+int sgpr_closure_consistency(const int32_t* d_rows, const int32_t* d_cols, const double* d_T, int C, const double* d_Xr,
+                             int MR, const double* d_Xc, int MC, const int32_t* d_group, int n_groups, double max_trans,
+                             double min_cos, double lever_gain, uint64_t* d_adj, int32_t* d_degree, void* d_workspace,
+                             size_t workspace_bytes, void* stream) {
+    if (!consistency_counts_ok("sgpr_closure_consistency", C, n_groups)) return SGPR_E_INVALID;
+    if (MR < 0 || MC < 0) {
+        set_error("sgpr_closure_consistency: negative pose table size");
+        return SGPR_E_INVALID;
+    }
+    // (a NaN fails every comparison)
+    if (!(max_trans >= 0.0) || !(lever_gain >= 0.0)) {
+        set_error("sgpr_closure_consistency: max_trans and lever_gain must be >= 0 and not NaN");
+        return SGPR_E_INVALID;
+    }
+    if (min_cos != min_cos) {
+        set_error("sgpr_closure_consistency: min_cos is NaN");
+        return SGPR_E_INVALID;
+    }
+    if (C == 0) return SGPR_OK;
+    // (an empty pose table may come with NULL: every closure is then void)
+    if (!d_rows || !d_cols || !d_T || !d_group || !d_adj || !d_degree || (MR > 0 && !d_Xr) || (MC > 0 && !d_Xc)) {
+        set_error("sgpr_closure_consistency: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = closure_consistency_ws_bytes(C);
+    if (!d_workspace || workspace_bytes < need) {
+        set_error("sgpr_closure_consistency: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    return launch_closure_consistency(d_rows, d_cols, d_T, C, d_Xr, MR, d_Xc, MC, d_group, n_groups, max_trans, min_cos,
+                                      lever_gain, reinterpret_cast<unsigned long long*>(d_adj), d_degree, d_workspace,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int sgpr_consistent_set(const uint64_t* d_adj, int C, const int32_t* d_group, int n_groups, int32_t* d_rank,
+                        int32_t* d_group_size, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!consistency_counts_ok("sgpr_consistent_set", C, n_groups)) return SGPR_E_INVALID;
+    if (C == 0) {
+        if (d_group_size) {
+            const hipError_t e = hipMemsetAsync(d_group_size, 0, (size_t)n_groups * sizeof(int32_t),
+                                                static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return hip_fail(e, "sgpr_consistent_set: clearing d_group_size");
+        }
+        return SGPR_OK;
+    }
+    if (!d_adj || !d_group || !d_rank || !d_group_size) {
+        set_error("sgpr_consistent_set: NULL argument");
+        return SGPR_E_INVALID;
+    }
+    const size_t need = consistent_set_ws_bytes(C);
+    if (!d_workspace || workspace_bytes < need) {
+        set_error("sgpr_consistent_set: workspace of " + std::to_string(need) + " bytes required");
+        return SGPR_E_WORKSPACE;
+    }
+    return launch_consistent_set(reinterpret_cast<const unsigned long long*>(d_adj), C, d_group, n_groups, d_rank,
+                                 d_group_size, d_workspace, static_cast<hipStream_t>(stream));
+}
+
 size_t sgpr_cluster_workspace_bytes(int P) { return P < 0 ? 0 : cluster_ws_bytes(P); }
 
 int sgpr_cluster_scan(const float* d_points, int point_stride, const uint32_t* d_labels, int P, int max_nodes,

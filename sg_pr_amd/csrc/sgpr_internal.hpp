@@ -388,6 +388,16 @@ int launch_verify_pairs(const float* ca, const int32_t* la, int GA, const float*
                         const int32_t* ia, const int32_t* ib, int64_t P, float tau_edge, float tau_in, float tau_z,
                         float min_base, int max_hyp, sgpr_verify_result* out, hipStream_t stream);
 
+// pairwise consistency of C closures and the greedy clique of every group (sgpr_consistency.hip); arguments already checked
+size_t closure_consistency_ws_bytes(int C);
+size_t consistent_set_ws_bytes(int C);
+int launch_closure_consistency(const int32_t* rows, const int32_t* cols, const double* T, int C, const double* Xr, int MR,
+                               const double* Xc, int MC, const int32_t* group, int n_groups, double max_trans,
+                               double min_cos, double lever_gain, unsigned long long* adj, int32_t* degree, void* ws,
+                               hipStream_t stream);
+int launch_consistent_set(const unsigned long long* adj, int C, const int32_t* group, int n_groups, int32_t* rank,
+                          int32_t* group_size, void* ws, hipStream_t stream);
+
 size_t size_order_ws_bytes(int G);
 int launch_size_order(const float* centers, const int32_t* labels, const long long* rag_off, int G, int N, int k,
                       int num_labels, int32_t* order, int32_t* info, void* ws, hipStream_t stream);

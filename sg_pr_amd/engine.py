@@ -62,6 +62,8 @@ ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled
                "sgpr_score_session_above_workspace_bytes", "sgpr_score_session_above",
                "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
                "sgpr_attention_pool_any", "sgpr_ntn_any", "sgpr_verify_pairs",
+               "sgpr_closure_consistency_workspace_bytes", "sgpr_closure_consistency",
+               "sgpr_consistent_set_workspace_bytes", "sgpr_consistent_set",
                "sgpr_edgeconv_train_workspace_bytes", "sgpr_edgeconv_train_forward", "sgpr_edgeconv_train_backward",
                "sgpr_pairs_train_workspace_bytes", "sgpr_pairs_train_forward", "sgpr_pairs_train_backward",
                "sgpr_cluster_workspace_bytes", "sgpr_cluster_scan", "sgpr_graph_edges",
@@ -366,6 +368,15 @@ def load_library():
     lib.sgpr_verify_pairs.restype = i32
     f32 = ctypes.c_float
     lib.sgpr_verify_pairs.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, i64, f32, f32, f32, f32, i32, vp, vp]
+    dbl = ctypes.c_double
+    lib.sgpr_closure_consistency_workspace_bytes.restype = sz
+    lib.sgpr_closure_consistency_workspace_bytes.argtypes = [i32]
+    lib.sgpr_closure_consistency.restype = i32
+    lib.sgpr_closure_consistency.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, dbl, dbl, dbl, vp, vp, vp, sz, vp]
+    lib.sgpr_consistent_set_workspace_bytes.restype = sz
+    lib.sgpr_consistent_set_workspace_bytes.argtypes = [i32]
+    lib.sgpr_consistent_set.restype = i32
+    lib.sgpr_consistent_set.argtypes = [vp, i32, vp, i32, vp, vp, vp, sz, vp]
     lib.sgpr_edgeconv_train_workspace_bytes.restype = sz
     lib.sgpr_edgeconv_train_workspace_bytes.argtypes = [i32, i32]
     lib.sgpr_edgeconv_train_forward.restype = i32
@@ -2002,6 +2013,66 @@ def verify_fields(rec):
     return {"inliers": i32[:, 0], "inliers_refined": i32[:, 1], "base": i32[:, 2:6],
             "hypotheses": i32[:, 6].to(torch.int64) & 0xffffffff, "flags": i32[:, 7], "coarse": f32v[:, 8:12],
             "refined": refined, "rmse": f64v[:, 10], "yaw": torch.atan2(refined[:, 1], refined[:, 0]), "record": rec}
+
+
+CONSISTENCY_MAX_CLOSURES = 16384     # SGPR_CONSISTENCY_MAX_CLOSURES of include/sgpr.h
+CONSISTENCY_MAX_GROUPS = 4096        # SGPR_CONSISTENCY_MAX_GROUPS
+
+
+def _on(t, device, dtype):
+    return torch.as_tensor(t).to(device=device, dtype=dtype).contiguous()
+
+
+def closure_consistency(rows, cols, T, Xr, Xc, group, n_groups, max_trans, min_cos, lever_gain, device=None):
+    """sgpr_closure_consistency: which of the C closures (rows[p], cols[p], T[p] f64 [C,4] = the refined
+    transform of verify_pairs) agree pair by pair through the planar odometry Xr [MR,4] / Xc [MC,4] (c, s, x, y; f64),
+    within a group (group i32 [C], 0..n_groups-1).  min_cos is the cosine of the yaw tolerance.
+    -> (adj i64 [C, ceil(C/64)]: bit q & 63 of word q >> 6 of row p, degree i32 [C], members i32 [C] = the group of every
+    closure that is not void, -1 of a void one: what consistent_set takes).  Device tensors, asynchronous on the current
+    stream."""
+    lib = load_library()
+    if device is None:
+        device = next((t.device for t in (T, rows, cols, Xr, Xc, group) if isinstance(t, torch.Tensor) and t.is_cuda),
+                      torch.device("cuda", torch.cuda.current_device()))
+    r, c, g = (_on(t, device, torch.int32).view(-1) for t in (rows, cols, group))
+    t = _on(T, device, torch.float64).view(-1, 4)
+    xr, xc = _on(Xr, device, torch.float64).view(-1, 4), _on(Xc, device, torch.float64).view(-1, 4)
+    n = r.numel()
+    if c.numel() != n or g.numel() != n or t.shape[0] != n:
+        raise ValueError("closure_consistency: rows, cols, group and T must describe the same number of closures")
+    adj = torch.empty(n, (n + 63) // 64, dtype=torch.int64, device=device)
+    degree = torch.empty(n, dtype=torch.int32, device=device)
+    need = int(lib.sgpr_closure_consistency_workspace_bytes(n)) if 0 <= n <= CONSISTENCY_MAX_CLOSURES else 0
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _raise_if(lib, lib.sgpr_closure_consistency(_ptr(r), _ptr(c), _ptr(t), n, _ptr(xr), xr.shape[0], _ptr(xc),
+                                                    xc.shape[0], _ptr(g), int(n_groups), float(max_trans), float(min_cos),
+                                                    float(lever_gain), _ptr(adj), _ptr(degree), _ptr(ws), need,
+                                                    _stream_of(adj)))
+    return adj, degree, ws[:4 * n].view(torch.int32)
+
+
+def consistent_set(adj, group, n_groups, device=None):
+    """sgpr_consistent_set: the greedy clique of every group on a bit matrix adj i64 [C, ceil(C/64)] (closure_consistency's,
+    or any other: diagonal bits and bits beyond C are ignored) -> (rank i32 [C]: the order in which the closure was chosen
+    within its group, -1 = not selected; group_size i32 [n_groups]).  group i32 [C]: outside 0..n_groups-1 = in no group.
+    Device tensors, asynchronous on the current stream."""
+    lib = load_library()
+    if device is None:
+        device = adj.device if isinstance(adj, torch.Tensor) and adj.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    g = _on(group, device, torch.int32).view(-1)
+    n = g.numel()
+    a = _on(adj, device, torch.int64)
+    if a.numel() != n * ((n + 63) // 64):
+        raise ValueError("consistent_set: adj must be [C, ceil(C/64)] for the C entries of group")
+    rank = torch.empty(n, dtype=torch.int32, device=device)
+    size = torch.empty(max(int(n_groups), 0), dtype=torch.int32, device=device)
+    need = int(lib.sgpr_consistent_set_workspace_bytes(n)) if 0 <= n <= CONSISTENCY_MAX_CLOSURES else 0
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _raise_if(lib, lib.sgpr_consistent_set(_ptr(a), n, _ptr(g), int(n_groups), _ptr(rank), _ptr(size), _ptr(ws), need,
+                                               _stream_of(rank)))
+    return rank, size
 
 
 def cluster_scan(points, labels, max_nodes=1024, want_point_node=False):

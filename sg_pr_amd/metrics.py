@@ -445,6 +445,16 @@ def precision_recall_at(rows, cols, pose_xz, p_thresh=3.0, n_thresh=20.0, window
     return precision, recall
 
 
+def planar_odometry(poses12):
+    """KITTI 3x4 pose rows [M, 12] (synth.world_sequence, the graph store) -> float64 [M, 4] planar poses (c, s, x, y)
+    under the conventions of closure_pose_errors: heading = atan2(p[2], p[0]), x = p[3], y = p[11].  Each maps a point of
+    its scan (x forward, y left) into the sequence's own frame, so the true closure of a pair is
+    inverse(X[col]) o X[row] - what SG.consistent_closures and engine.closure_consistency take as odometry."""
+    p = np.asarray(poses12.detach().cpu().numpy() if hasattr(poses12, "detach") else poses12, dtype=np.float64).reshape(-1, 12)
+    head = np.arctan2(p[:, 2], p[:, 0])
+    return np.ascontiguousarray(np.stack((np.cos(head), np.sin(head), p[:, 3], p[:, 11]), axis=1))
+
+
 def closure_pose_errors(results, rows, cols, poses):
     """Yaw and translation error of verified closures (engine.verify_pairs / SG.verify_closures) against ground-truth
     poses.  results: the dict of fields (or anything with "refined" [..., 4] = c, s, tx, ty and "flags"), rows / cols:

@@ -17,7 +17,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
 
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
-                                            [--verify] [--min-inliers I] [--distinct RHO] [--seq-slopes S,S,...]
+                                            [--verify] [--min-inliers I] [--consistent] [--distinct RHO] [--seq-slopes S,S,...]
                                             [--sessions N]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
@@ -54,9 +54,14 @@ session boundaries, engine.Engine.score_session_topk; --seq-len 
 recall_one_trajectory, recall_head_one_trajectory (and seq_len); printed are recall@1 and recall@K beside the
 one-trajectory lists, and the same pair for the head rows alone - the frames fewer than --window scans after the start
 of a session that has a predecessor.  All four are counted under the session rule for an allowed match
-(metrics.recall_at_n with col_starts), so the two lists are judged on the same queries.
+(metrics.recall_at_n with col_starts), so the two lists are judged on the same queries.  With --verify --consistent
+[--max-trans M] [--max-yaw-deg D] [--lever-gain G] [--min-clique N] the accepted closures are also checked against one
+another through the poses (SG.consistent_closures; with --sessions N within each pair of sessions):
+`<seq>_consistent.npz` holds rows, cols, refined, consistent, rank, degree, group_size, session_starts and the counts;
+printed are the number and the precision of the accepted closures before and after the selection.
 """
 import argparse
+import math
 import hashlib
 import os
 
@@ -376,6 +381,17 @@ def main(argv=None):
                     help="verify the retrieved lists geometrically, re-rank them by inliers and write <seq>_verify.npz")
     ap.add_argument("--min-inliers", type=int, default=12, metavar="I",
                     help="with --verify: accept a closure with at least I refined inliers")
+    ap.add_argument("--consistent", action="store_true",
+                    help="with --verify: keep the accepted closures that agree pair by pair through the poses "
+                         "(with --sessions N: within each pair of sessions) and write <seq>_consistent.npz")
+    ap.add_argument("--max-trans", type=float, default=1.0, metavar="M",
+                    help="with --consistent: translation tolerance of a pair of closures, metres")
+    ap.add_argument("--max-yaw-deg", type=float, default=math.degrees(0.06), metavar="D",
+                    help="with --consistent: yaw tolerance of a pair of closures, degrees")
+    ap.add_argument("--lever-gain", type=float, default=0.04, metavar="G",
+                    help="with --consistent: extra translation tolerance per metre between the two row scans")
+    ap.add_argument("--min-clique", type=int, default=3, metavar="N",
+                    help="with --consistent: a group whose consistent set is smaller than N accepts nothing")
     ap.add_argument("--distinct", type=int, default=None, metavar="RHO",
                     help="also retrieve the K best distinct places: score peaks within RHO frames (0..1024)")
     ap.add_argument("--seq-slopes", default=None, metavar="S,S,...",
@@ -392,6 +408,10 @@ def main(argv=None):
         ap.error("--min-terms needs --threshold")
     if opt.min_terms is not None and not 1 <= opt.min_terms <= max(opt.seq_len, 1):
         ap.error("--min-terms must lie in 1..--seq-len")
+    if opt.consistent and not opt.verify:
+        ap.error("--consistent needs --verify")
+    if opt.consistent and (opt.max_trans < 0 or opt.lever_gain < 0 or not 0 <= opt.max_yaw_deg <= 180):
+        ap.error("--max-trans and --lever-gain must be >= 0, --max-yaw-deg in 0..180")
     if opt.sessions is not None and not 2 <= opt.sessions <= _engine.SESSION_MAX:
         ap.error("--sessions must lie in 2..%d" % _engine.SESSION_MAX)
     if opt.sessions is not None and opt.distinct is not None:
@@ -457,6 +477,16 @@ def main(argv=None):
                   "(>= %d inliers) precision %.4f," % (opt.min_inliers, report["precision"]),
                   "accepted true closures %d: median yaw error %.3f deg, median translation error %.3f m"
                   % (int(report["true_accepted"]), report["median_yaw_deg"], report["median_trans_m"]))
+        if opt.consistent:
+            creport = consistent_lists(trainer.model, seq, vals, idx, opt.min_inliers, float(args.p_thresh),
+                                       window=opt.window, causal=opt.causal, sessions=opt.sessions,
+                                       max_trans=opt.max_trans, max_yaw=math.radians(opt.max_yaw_deg),
+                                       lever_gain=opt.lever_gain, min_clique=opt.min_clique)
+            np.savez(os.path.join(args.output_path, sequence + "_consistent.npz"), **creport)
+            print("sequence", sequence, "sessions", opt.sessions or 1, "accepted", int(creport["accepted"]),
+                  "precision %.4f" % creport["precision_accepted"], "-> pairwise consistent",
+                  int(creport["consistent_count"]), "precision %.4f" % creport["precision_consistent"],
+                  "(largest set %d)" % int(creport["group_size"].max()))
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
@@ -634,6 +664,40 @@ def verify_lists(model, seq, values, indices, min_inliers, p_thresh, window=-1, 
                 "median_yaw_deg": np.float64(np.median(yaw) if yaw.size else 0.0),
                 "median_trans_m": np.float64(np.median(trans) if trans.size else 0.0)})
     return out
+
+
+def consistent_lists(model, seq, values, indices, min_inliers, p_thresh, window=-1, causal=False, sessions=None,
+                     max_trans=1.0, max_yaw=0.06, lever_gain=0.04, min_clique=3):
+    """verify_lists' accepted closures, then the pairwise-consistent ones among them (SG.consistent_closures with the
+    sequence's poses as odometry; sessions N: the frames taken as N consecutive near-equal sessions - session_lists'
+    split - and closures compared only within one pair of sessions).  At most engine.CONSISTENCY_MAX_CLOSURES accepted
+    closures enter the selection: beyond that the ones with the most refined inliers (ties to the earlier slot).
+    -> dict of numpy arrays: rows, cols, refined of the closures that entered, consistent bool, rank, degree (one per
+    closure), group_size, session_starts, accepted / consistent (counts), precision_accepted / precision_consistent
+    (metrics.precision_recall_at's classes)."""
+    ver = model.verify_closures(seq.centers, seq.labels, indices, values=values, min_inliers=min_inliers)
+    idx = torch.as_tensor(indices).to(ver["accept"].device)
+    m, k = idx.shape
+    rows = torch.arange(m, device=idx.device)[:, None].expand(m, k)
+    acc = ver["accept"]
+    arows, acols = rows[acc], idx[acc].long()
+    refined, flags, inl = ver["refined"][acc], ver["flags"][acc], ver["inliers_refined"][acc]
+    if arows.numel() > _engine.CONSISTENCY_MAX_CLOSURES:
+        keep = torch.argsort(-inl.long(), stable=True)[:_engine.CONSISTENCY_MAX_CLOSURES].sort().values
+        arows, acols, refined, flags = arows[keep], acols[keep], refined[keep], flags[keep]
+    starts = None if sessions is None else np.asarray([(j * m) // int(sessions) for j in range(int(sessions))], np.int32)
+    sel = model.consistent_closures({"refined": refined, "flags": flags}, arows, acols, seq.poses, row_sessions=starts,
+                                    col_sessions=starts, max_trans=max_trans, max_yaw=max_yaw, lever_gain=lever_gain,
+                                    min_clique=min_clique)
+    ok = sel["accept"]
+    kw = dict(p_thresh=p_thresh, window=window, causal=causal)
+    return {"rows": arows.cpu().numpy(), "cols": acols.cpu().numpy(), "refined": refined.cpu().numpy(),
+            "consistent": ok.cpu().numpy(), "rank": sel["rank"].cpu().numpy(), "degree": sel["degree"].cpu().numpy(),
+            "group_size": sel["group_size"].cpu().numpy(),
+            "session_starts": np.zeros(1, np.int32) if starts is None else starts,
+            "accepted": np.int64(arows.numel()), "consistent_count": np.int64(int(ok.sum())),
+            "precision_accepted": np.float64(metrics.precision_recall_at(arows, acols, seq.poses, **kw)[0]),
+            "precision_consistent": np.float64(metrics.precision_recall_at(arows[ok], acols[ok], seq.poses, **kw)[0])}
 
 
 def hard_pairs_of(db, poses, k, p_thresh, window=-1, causal=False):

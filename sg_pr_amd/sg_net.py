@@ -223,6 +223,60 @@ class SG(torch.nn.Module):
             out["accept"] = valid & (out["inliers_refined"] >= int(min_inliers))
         return out
 
+    def consistent_closures(self, verified, rows, cols, row_poses, col_poses=None, row_sessions=None, col_sessions=None,
+                            max_trans=1.0, max_yaw=0.06, lever_gain=0.04, min_clique=3):
+        """Pairwise-consistent closures (engine.closure_consistency + engine.consistent_set): of the
+        verified closures, per pair of sessions, a largest-by-greedy set whose members agree with one another through the
+        odometry - going out over one closure and back over another returns to the start within max_trans + lever_gain x
+        (distance between the two row scans) metres and max_yaw radians.
+        verified: the dict of verify_closures / engine.verify_pairs ("refined", "flags", and "accept" when it was made
+        with min_inliers); rows / cols: the row and column scan of every closure, same shape as the records (at most
+        engine.CONSISTENCY_MAX_CLOSURES in all); row_poses / col_poses: KITTI 3x4 pose rows [M,12] (metrics.planar_odometry
+        makes them planar) or planar poses [M,4]; col_poses None: the row poses.  row_sessions / col_sessions: the first
+        scan of every session of a stacked map (None: one session); closures are only compared within one (row session,
+        column session) group.  A closure is void - never selected, consistent with nothing - if its flags carry
+        INVALID_INDEX, NO_HYPOTHESIS or NONFINITE or it is not accepted; a group whose set is smaller than min_clique
+        accepts nothing.
+        -> dict of device tensors shaped like rows: accept bool, rank i32 (the order chosen within the group, -1 = not),
+        degree i32 (closures of its group it agrees with); group_size i32 [row sessions x column sessions]."""
+        import math
+        from . import metrics
+        dev = self.engine().device
+        r = torch.as_tensor(rows).to(device=dev, dtype=torch.int64)
+        shape = tuple(r.shape)
+        r = r.reshape(-1)
+        c = torch.as_tensor(cols).to(device=dev, dtype=torch.int64).reshape(-1)
+        flags = torch.as_tensor(verified["flags"]).to(device=dev, dtype=torch.int64).reshape(-1)
+        refined = torch.as_tensor(verified["refined"]).to(device=dev, dtype=torch.float64).reshape(-1, 4)
+        if c.numel() != r.numel() or flags.numel() != r.numel() or refined.shape[0] != r.numel():
+            raise ValueError("consistent_closures: rows, cols and the verified records must have the same shape")
+
+        def planar(p):
+            p = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+            p = p.reshape(p.shape[0], -1)
+            return torch.as_tensor(np.asarray(p, dtype=np.float64) if p.shape[1] == 4 else metrics.planar_odometry(p),
+                                   device=dev)
+
+        def starts(t):
+            t = [0] if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else t)
+            return torch.as_tensor(np.asarray(t, dtype=np.int64).reshape(-1), device=dev)
+
+        xr = planar(row_poses)
+        xc = xr if col_poses is None else planar(col_poses)
+        rs, cs = starts(row_sessions), starts(col_sessions)
+        n_groups = int(rs.numel() * cs.numel())
+        void = (flags & (_engine.VERIFY_INVALID_INDEX | _engine.VERIFY_NO_HYPOTHESIS | _engine.VERIFY_NONFINITE)) != 0
+        if "accept" in verified:
+            void |= ~torch.as_tensor(verified["accept"]).to(device=dev, dtype=torch.bool).reshape(-1)
+        group = (torch.searchsorted(rs, r, right=True) - 1) * cs.numel() + (torch.searchsorted(cs, c, right=True) - 1)
+        group = torch.where(void | (r < 0) | (c < 0), torch.full_like(group, -1), group)
+        adj, degree, members = _engine.closure_consistency(r, c, refined, xr, xc, group, n_groups, max_trans,
+                                                           math.cos(float(max_yaw)), lever_gain, device=dev)
+        rank, size = _engine.consistent_set(adj, members, n_groups, device=dev)
+        big = size[members.clamp(min=0).to(torch.int64)] >= int(min_clique)
+        return {"accept": ((rank >= 0) & big).reshape(shape), "rank": rank.reshape(shape),
+                "degree": degree.reshape(shape), "group_size": size}
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming

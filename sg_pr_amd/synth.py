@@ -152,6 +152,67 @@ def world_sequence(num_graphs=4541, node_num=100, seed=0, sensor_range=50.0, cen
     return centers, labels, n_real, poses
 
 
+def _se2_compose(a, b):
+    """a o b (b first) on planar poses [..., 4] = (c, s, x, y)"""
+    return np.stack((a[..., 0] * b[..., 0] - a[..., 1] * b[..., 1], a[..., 1] * b[..., 0] + a[..., 0] * b[..., 1],
+                     a[..., 0] * b[..., 2] - a[..., 1] * b[..., 3] + a[..., 2],
+                     a[..., 1] * b[..., 2] + a[..., 0] * b[..., 3] + a[..., 3]), axis=-1)
+
+
+def _se2_inverse(a):
+    return np.stack((a[..., 0], -a[..., 1], -(a[..., 0] * a[..., 2] + a[..., 1] * a[..., 3]),
+                     a[..., 1] * a[..., 2] - a[..., 0] * a[..., 3]), axis=-1)
+
+
+def _se2(yaw, x, y):
+    yaw, x, y = np.broadcast_arrays(np.asarray(yaw, dtype=np.float64), x, y)
+    return np.stack((np.cos(yaw), np.sin(yaw), x, y), axis=-1).astype(np.float64)
+
+
+def closure_world(seed, scans=600, closures=400, outlier_frac=0.5, alias=30, noise_t=0.15, noise_yaw=0.01):
+    """A planted set of loop closures between two drives, for the pairwise-consistency stage.
+
+    Two drives of one planar random-walk trajectory (1 m per scan): the second is offset by N(0, 0.5) m per scan and its
+    odometry is expressed in a frame of its own, rotated by 1.1 rad and shifted by (40, -25) - the two sessions' frames
+    are unrelated, as in a multi-session map.  A closure pairs a row scan of drive 1 with a column scan of drive 2 and
+    carries T, a point of the row scan into the column scan.  True closures pair scans within +-2 indices and carry the
+    true transform perturbed by N(0, noise_yaw) rad and N(0, noise_t) m; outliers pair random scans with random
+    transforms; `alias` of the outliers are rebuilt to agree on ONE wrong alignment of the two frames (a perceptually
+    aliased place: consistent with each other, inconsistent with the truth), with the same noise.
+    -> dict: rows, cols int32 [C]; T float64 [C,4] (c, s, tx, ty); Xr, Xc float64 [scans,4] planar odometry (c, s, x,
+    y); planted bool [C] (a true closure); aliased bool [C].  Closures are shuffled.  numpy only."""
+    rng = np.random.default_rng(seed + 15485863)
+    S, C = int(scans), int(closures)
+    heading = np.cumsum(rng.normal(0.0, 0.05, size=S))
+    xy = np.cumsum(np.stack([np.cos(heading), np.sin(heading)], axis=1), axis=0)
+    X1 = _se2(heading, xy[:, 0], xy[:, 1])
+    xy2 = xy + rng.normal(0.0, 0.5, size=(S, 2))
+    X2 = _se2(heading + rng.normal(0.0, 0.03, size=S), xy2[:, 0], xy2[:, 1])        # drive 2 in drive 1's frame
+    frame = _se2(1.1, 40.0, -25.0)
+    Xc = _se2_compose(frame, X2)
+    n_out = min(C, int(round(float(outlier_frac) * C)))
+    n_alias = min(int(alias), n_out)
+    planted = np.zeros(C, dtype=bool)
+    planted[n_out:] = True
+    aliased = np.zeros(C, dtype=bool)
+    aliased[:n_alias] = True
+    rows = rng.integers(0, S, size=C)
+    cols = np.where(planted, np.clip(rows + rng.integers(-2, 3, size=C), 0, S - 1), rng.integers(0, S, size=C))
+
+    def noisy(t):
+        return _se2_compose(_se2(rng.normal(0.0, noise_yaw, size=C), rng.normal(0.0, noise_t, size=C),
+                                 rng.normal(0.0, noise_t, size=C)), t)
+
+    truth = noisy(_se2_compose(_se2_inverse(X2[cols]), X1[rows]))
+    wrong = _se2_compose(_se2(0.4, 15.0, -8.0), X1[rows])                            # ... if the frames were aligned so
+    fake = noisy(_se2_compose(_se2_inverse(X2[cols]), wrong))
+    rand = _se2(rng.uniform(-np.pi, np.pi, size=C), rng.uniform(-30.0, 30.0, size=C), rng.uniform(-30.0, 30.0, size=C))
+    T = np.where(planted[:, None], truth, np.where(aliased[:, None], fake, rand))
+    perm = rng.permutation(C)
+    return {"rows": rows[perm].astype(np.int32), "cols": cols[perm].astype(np.int32),
+            "T": np.ascontiguousarray(T[perm]), "Xr": X1, "Xc": Xc, "planted": planted[perm], "aliased": aliased[perm]}
+
+
 def dense_features(centers, labels, num_labels=NUM_LABELS):
     """Packed (centers, labels) -> the reference's dense `B x (3+L) x N` float32
     tensor (sg_net.py:274-298): xyz rows then a one-hot block, all-zero for -1."""
