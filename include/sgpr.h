@@ -499,7 +499,7 @@ int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
  *   iff window >= the largest offset; otherwise a reverse sum of an eligible column reaches a frame not stored yet.
  * - sgpr_seq_path_filter: a resident matrix d_score [R][ld] -> d_out [R - ctx][ldo] and, unless NULL, d_code u8
  *   [R - ctx][ldo].  Out of place.  No workspace.  One workgroup per tile of 32 rows x 256 columns with a halo of the
- *   call's largest offset (sgpr_seq_path.hip).
+ *   call's largest offset (seq_path_kernel in sgpr_seq.hip).
  * - sgpr_score_path_topk: sgpr_score_peak_topk's structure (row blocks with L - 1 context rows, the f16-range question
  *   answered once per call, every handle) with the path filter in place of the diagonal filter; the peak step runs only
  *   when radius > 0.  d_codes u8 [R - ctx][k] (or NULL): the code of each listed entry, 0 in a padding slot.  With the
@@ -548,7 +548,7 @@ int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
  * session's context rows being the rows of that session before the block.
  * - sgpr_session_filter: a resident matrix d_score [R][ld] -> d_out [R - ctx][ldo] and, unless NULL, d_code u8
  *   [R - ctx][ldo]; an excluded end point gets -inf with code 0.  Out of place.  No workspace.  The causal flag is not
- *   accepted (the pooled call hands it to its selection).  sgpr_seq_path_filter's tile and halo (sgpr_session.hip,
+ *   accepted (the pooled call hands it to its selection).  sgpr_seq_path_filter's tile and halo (session_kernel in sgpr_seq.hip,
  *   DESIGN.md §22).
  * - sgpr_score_session_topk: sgpr_score_path_topk's arguments without `radius`, plus the two tables, and its structure
  *   (row blocks with L - 1 context rows, the f16-range question answered once per call, every handle): the session filter
@@ -768,7 +768,7 @@ int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_
  *   ctx == R, R == 0 and M == 0 are valid empty calls.  A d_row_self entry outside [0, M) is reported by
  *   sgpr_check_status (the bit sgpr_rows_above raises).
  * - sgpr_session_rows_above: a resident matrix d_score [R][ld].  Two passes of sgpr_session_filter's tile kernel with
- *   sgpr_seq_rows_above's range-select epilogue (sgpr_session_above.hip): no Q or code block exists.
+ *   sgpr_seq_rows_above's range-select epilogue (session_above_kernel in sgpr_seq.hip): no Q or code block exists.
  *   Its workspace equals sgpr_seq_rows_above_workspace_bytes.
  * - sgpr_score_session_above: the rectangle d_pooled_rows [R] x d_pooled_cols [M], every handle: sgpr_score_seq_above's
  *   row blocks (L - 1 context rows, the f16-range question answered once per call, positions continuing on the device

@@ -944,7 +944,7 @@ int sgpr_score_topk_large(const sgpr_handle* h, const float* d_pooled_rows, int 
                             workspace_bytes, stream, select, crng);
 }
 
-// ---- sgpr_seq_filter / sgpr_score_seq_topk: the diagonal score filter (sgpr_seq.hip) on a resident matrix, and on
+// ---- sgpr_seq_filter / sgpr_score_seq_topk: the diagonal score filter (seq_filter_kernel; the family: sgpr_seq.hip) on a resident matrix, and on
 //      row blocks that carry their last L - 1 rows over as the next block's context, each selected by the large-k selection
 static const int kSeqFlags = SGPR_TOPK_CAUSAL | SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE;
 
@@ -986,11 +986,144 @@ int sgpr_seq_filter(const sgpr_handle* h, const float* d_score, int R, int M, in
 
 static bool seq_both(int flags) { return (flags & SGPR_SEQ_FORWARD) && (flags & SGPR_SEQ_REVERSE); }
 
-// head of sgpr_score_seq_topk: the call's f16 range (a float4) | the selection's workspace for one block | Q block
-// [rb][M] | dir block [rb][M] (both directions)
-static size_t seq_head_bytes(int R, int M, int L, int flags) {
-    const size_t rb = (size_t)score_block_rows(R, M, L - 1);
-    return 256 + a256(select_ws_bytes((int)rb, M)) + a256(rb * M * sizeof(float)) + (seq_both(flags) ? a256(rb * M) : 0);
+// ---- the ranking pipeline of sgpr_score_seq_topk, _peak_topk, _path_topk and _session_topk.  Row blocks that carry their
+//      last L - 1 rows over as the next block's context, each going through: score block -> [diagonal / path / session
+//      filter into a Q block] -> [peak filter into a P block] -> the large-k selection -> the directions / codes of the
+//      selected columns.
+enum RankFilter { kRankNone, kRankDiagonal, kRankPaths, kRankSessions };
+
+struct RankStages {
+    RankFilter filter;     // kRankNone: the ranked score is S itself (L = 1 before a peak step: S * rcp[1] is S)
+    bool peak;             // the peak step runs: a P block sits in front of the Q block
+    bool code_block;       // the filter writes a dir / code block behind the Q block
+    bool code_room;        // the head has room for that block
+    bool filter_window;    // the window is the filter's (sessions): the selection runs without one
+    int L, radius;
+    const int32_t* offsets;   // kRankPaths, kRankSessions (nullptr: the unit diagonal)
+    int n_paths;
+    const int32_t* row_starts;   // kRankSessions (nullptr: one session)
+    int n_row;
+    const int32_t* col_starts;
+    int n_col;
+};
+
+// sgpr_score_seq_topk: the diagonal filter at every L; a dir block when both directions are asked for
+static RankStages seq_stages(int L, int flags) {
+    return {kRankDiagonal, false, seq_both(flags), seq_both(flags), false, L, 0, nullptr, 0, nullptr, 0, nullptr, 0};
+}
+
+// sgpr_score_peak_topk: the peak step at every radius, the diagonal filter when L > 1 (L = 1, both directions: the two
+// sums are one number and forward wins the tie - direction 0, no dir block)
+static RankStages peak_stages(int L, int radius, int flags) {
+    const bool dir = L > 1 && seq_both(flags);
+    return {L > 1 ? kRankDiagonal : kRankNone, true, dir, dir, false, L, radius, nullptr, 0, nullptr, 0, nullptr, 0};
+}
+
+// sgpr_score_path_topk: the peak step only when radius > 0, the path filter unless L = 1 comes before a peak step (every
+// candidate is S itself).  Codes: both directions or several paths; one direction and several paths keep their room
+// in the head even where no filter runs
+static RankStages path_stages(int L, const int32_t* offsets, int n_paths, int radius, int flags) {
+    const bool filter = radius == 0 || L > 1;
+    return {filter ? kRankPaths : kRankNone, radius > 0, filter && (seq_both(flags) || n_paths > 1),
+            seq_both(flags) ? filter : n_paths > 1, false, L, radius, offsets, n_paths, nullptr, 0, nullptr, 0};
+}
+
+// sgpr_score_session_topk: sgpr_score_path_topk's at radius 0 with the session filter, which applies the window itself
+static RankStages session_stages(int L, const int32_t* offsets, int n_paths, const int32_t* row_starts, int n_row,
+                                 const int32_t* col_starts, int n_col, int flags) {
+    RankStages st = path_stages(L, offsets, std::max(n_paths, 1), 0, flags);
+    st.filter = kRankSessions;
+    st.filter_window = true;
+    st.row_starts = row_starts;
+    st.n_row = n_row;
+    st.col_starts = col_starts;
+    st.n_col = n_col;
+    return st;
+}
+
+// the pipeline's head: the call's f16 range (a float4) | the selection's workspace for one block | [P block [rb][M]] |
+// [Q block [rb][M]] | [dir / code block [rb][M] u8]
+static size_t rank_head_bytes(int R, int M, const RankStages& st) {
+    const size_t rb = (size_t)score_block_rows(R, M, st.L - 1), blk = a256(rb * M * sizeof(float));
+    return 256 + a256(select_ws_bytes((int)rb, M)) + (st.peak ? blk : 0) + (st.filter != kRankNone ? blk : 0) +
+           (st.code_room ? a256(rb * M) : 0);
+}
+
+// the row-session table of the rectangle that starts at the call's row `base` and has `rows` rows (nullptr stays
+// nullptr: one session).  A session that starts before `base` starts at the rectangle's row 0 - where it matters
+// (base > 0) every output row has its L - 1 rows inside the rectangle, and a depth of L is a depth of L from either start
+static const int32_t* shift_row_table(const int32_t* starts, int n, int base, int rows, int32_t* local) {
+    if (!starts) return nullptr;
+    for (int j = 0; j < n; ++j) local[j] = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)starts[j] - base, 0), rows);
+    return local;
+}
+
+// arguments and workspace already checked, R > ctx.  Without a code block the listed code is the first direction asked
+// for, path 0: one candidate, or L = 1 where all candidates are one number and the first one keeps a listed, hence
+// non-NaN, entry (forward wins the tie)
+static int rank_row_blocks(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                           int ctx, const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
+                           int32_t* d_indices, unsigned char* d_codes, const RankStages& st, void* d_workspace,
+                           size_t workspace_bytes, void* stream) {
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_code = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
+    const int seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE), L = st.L;
+    const int sel_window = st.filter_window ? -1 : window;
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0) {
+        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx,
+                                          sel_window, causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
+        if (rc != SGPR_OK || !d_codes) return rc;
+        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_code, d_codes, s);
+    }
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
+    const size_t p_at = 256 + sel_bytes, q_at = p_at + (st.peak ? blk_bytes : 0);
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    int clean_rows = 0;                                   // histogram rows the selection before left clear
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        const int c = std::min(L - 1, r0), no = r0 + n - first, base = r0 - c;
+        // the rectangle the filter sees starts c rows before r0: global row 0, or L - 1 rows back (no sum reaches further)
+        const float* rect = block - (size_t)c * M;
+        const float* x = block + (size_t)(first - r0) * M;
+        float* q = reinterpret_cast<float*>(head + q_at);
+        unsigned char* code = st.code_block ? head + q_at + blk_bytes : nullptr;
+        int rc = SGPR_OK;
+        if (st.filter == kRankDiagonal) {
+            rc = launch_seq_filter(rect, c + n, M, M, first - base, L, seq_flags, q, M, code, M, s);
+        } else if (st.filter == kRankPaths) {
+            rc = launch_seq_path_filter(rect, c + n, M, M, first - base, L, seq_flags, st.offsets, st.n_paths, q, M, code, M,
+                                        s);
+        } else if (st.filter == kRankSessions) {          // row_self / row0 and the row table move with the rectangle
+            int32_t local[SGPR_SESSION_MAX];
+            rc = launch_session_filter(rect, c + n, M, M, first - base, L, seq_flags, st.offsets, st.n_paths,
+                                       shift_row_table(st.row_starts, st.n_row, base, c + n, local), st.n_row,
+                                       st.col_starts, st.n_col, d_row_self ? d_row_self + base : nullptr, row0 + base,
+                                       window, q, M, code, M, s);
+        }
+        if (rc != SGPR_OK) return rc;
+        if (st.filter != kRankNone) x = q;
+        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
+        if (st.peak) {                                    // (rows are independent: no context rows of its own)
+            float* p = reinterpret_cast<float*>(head + p_at);
+            rc = launch_peak_filter(x, no, M, M, rs, row0 + first, window, causal, st.radius, p, M, s);
+            if (rc != SGPR_OK) return rc;
+            x = p;
+        }
+        const size_t o = (size_t)(first - ctx) * k;
+        rc = launch_select_rows(x, no, M, M, rs, row0 + first, sel_window, causal, k, d_values + o, d_indices + o,
+                                head + 256, select_group_rows(no) <= clean_rows, h->d_status, s);
+        // (the first block's outputs start at ctx: the block after it may select more rows, whose histograms reach into
+        //  what this one used for its state and counts)
+        clean_rows = select_group_rows(no);
+        if (rc != SGPR_OK || !d_codes) return rc;
+        return launch_seq_dirs(d_indices + o, no, k, code, M, fixed_code, d_codes + o, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, rank_head_bytes(R, M, st), d_workspace, workspace_bytes,
+                            stream, select, crng, L - 1);
 }
 
 size_t sgpr_score_seq_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int flags) {
@@ -998,7 +1131,7 @@ size_t sgpr_score_seq_topk_workspace_bytes(const sgpr_handle* h, int R, int M, i
         (flags & ~kSeqFlags) || !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
         return 0;
     if (R == ctx || M == 0) return 0;
-    return row_blocks_ws_bytes(h, R, M, seq_head_bytes(R, M, L, flags), L - 1);
+    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, seq_stages(L, flags)), L - 1);
 }
 
 int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1019,40 +1152,8 @@ int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R,
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_dir = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0) {
-        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, window,
-                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
-        if (rc != SGPR_OK || !d_dirs) return rc;
-        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_dir, d_dirs, s);
-    }
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), q_bytes = a256((size_t)rb * M * sizeof(float));
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
-    int clean_rows = 0;                                   // histogram rows the selection before left clear
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0), no = r0 + n - first;
-        float* q = reinterpret_cast<float*>(head + 256 + sel_bytes);
-        unsigned char* dir = seq_both(flags) ? head + 256 + sel_bytes + q_bytes : nullptr;
-        // the rectangle the filter sees starts c rows before r0: global row 0, or L - 1 rows back (no sum reaches further)
-        int rc = launch_seq_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, q, M, dir, M, s);
-        if (rc != SGPR_OK) return rc;
-        const size_t o = (size_t)(first - ctx) * k;
-        rc = launch_select_rows(q, no, M, M, d_row_self ? d_row_self + first : nullptr, row0 + first, window, causal, k,
-                                d_values + o, d_indices + o, head + 256, select_group_rows(no) <= clean_rows, h->d_status, s);
-        // (the first block's outputs start at ctx: the block after it may select more rows, whose histograms reach into
-        //  what this one used for its state and counts)
-        clean_rows = select_group_rows(no);
-        if (rc != SGPR_OK || !d_dirs) return rc;
-        return launch_seq_dirs(d_indices + o, no, k, dir, M, fixed_dir, d_dirs + o, s);
-    };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_head_bytes(R, M, L, flags), d_workspace,
-                            workspace_bytes, stream, select, crng, L - 1);
+    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
+                           d_indices, d_dirs, seq_stages(L, flags), d_workspace, workspace_bytes, stream);
 }
 
 // ---- sgpr_peak_filter / sgpr_score_peak_topk: per-row score peaks within a scan radius (sgpr_peak.hip) on a resident
@@ -1087,14 +1188,6 @@ int sgpr_peak_filter(const sgpr_handle* h, const float* d_score, int R, int M, i
                               d_out, ldo, static_cast<hipStream_t>(stream));
 }
 
-// head of sgpr_score_peak_topk: the call's f16 range (a float4) | the selection's workspace for one block | P block
-// [rb][M] | L > 1: Q block [rb][M] | L > 1, both directions: dir block [rb][M]
-static size_t peak_head_bytes(int R, int M, int L, int flags) {
-    const size_t rb = (size_t)score_block_rows(R, M, L - 1);
-    return 256 + a256(select_ws_bytes((int)rb, M)) + a256(rb * M * sizeof(float)) +
-           (L > 1 ? a256(rb * M * sizeof(float)) + (seq_both(flags) ? a256(rb * M) : 0) : 0);
-}
-
 size_t sgpr_score_peak_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int radius,
                                             int flags) {
     if (!h || R < 0 || M < 0 || k < 1 || k > SGPR_TOPK_LARGE_MAX || L < 1 || L > SGPR_SEQ_MAX_LEN || ctx < 0 || ctx > R ||
@@ -1102,7 +1195,7 @@ size_t sgpr_score_peak_topk_workspace_bytes(const sgpr_handle* h, int R, int M, 
         !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
         return 0;
     if (R == ctx || M == 0) return 0;
-    return row_blocks_ws_bytes(h, R, M, peak_head_bytes(R, M, L, flags), L - 1);
+    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, peak_stages(L, radius, flags)), L - 1);
 }
 
 int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1124,51 +1217,11 @@ int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                       d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_dir = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0) {
-        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, window,
-                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
-        if (rc != SGPR_OK || !d_dirs) return rc;
-        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_dir, d_dirs, s);
-    }
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
-    int clean_rows = 0;                                   // histogram rows the selection before left clear
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0), no = r0 + n - first;
-        float* p = reinterpret_cast<float*>(head + 256 + sel_bytes);
-        const float* x = block + (size_t)(first - r0) * M;   // L = 1: the ranked score is S itself (S * rcp[1] is S)
-        unsigned char* dir = nullptr;
-        int rc;
-        if (L > 1) {
-            float* q = reinterpret_cast<float*>(head + 256 + sel_bytes + blk_bytes);
-            dir = seq_both(flags) ? head + 256 + sel_bytes + 2 * blk_bytes : nullptr;
-            rc = launch_seq_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, q, M, dir, M, s);
-            if (rc != SGPR_OK) return rc;
-            x = q;
-        }
-        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
-        rc = launch_peak_filter(x, no, M, M, rs, row0 + first, window, causal, radius, p, M, s);
-        if (rc != SGPR_OK) return rc;
-        const size_t o = (size_t)(first - ctx) * k;
-        rc = launch_select_rows(p, no, M, M, rs, row0 + first, window, causal, k, d_values + o, d_indices + o, head + 256,
-                                select_group_rows(no) <= clean_rows, h->d_status, s);
-        clean_rows = select_group_rows(no);
-        if (rc != SGPR_OK || !d_dirs) return rc;
-        // (L = 1, both directions: the two sums are one number and forward wins the tie - direction 0, as fixed_dir says)
-        return launch_seq_dirs(d_indices + o, no, k, dir, M, fixed_dir, d_dirs + o, s);
-    };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, peak_head_bytes(R, M, L, flags), d_workspace,
-                            workspace_bytes, stream, select, crng, L - 1);
+    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
+                           d_indices, d_dirs, peak_stages(L, radius, flags), d_workspace, workspace_bytes, stream);
 }
 
-// ---- sgpr_seq_path_filter / sgpr_score_path_topk: the path-set score filter (sgpr_seq_path.hip) on a resident matrix,
+// ---- sgpr_seq_path_filter / sgpr_score_path_topk: the path-set score filter (seq_path_kernel) on a resident matrix,
 //      and on sgpr_score_peak_topk's row blocks in place of the diagonal filter (the peak step only when radius > 0)
 static bool seq_paths_ok(const char* fn, const int32_t* h_offsets, int n_paths, int L) {
     if (n_paths < 1 || n_paths > SGPR_SEQ_MAX_PATHS) {
@@ -1219,14 +1272,6 @@ int sgpr_seq_path_filter(const sgpr_handle* h, const float* d_score, int R, int 
                                   static_cast<hipStream_t>(stream));
 }
 
-// head of sgpr_score_path_topk: sgpr_score_seq_topk's (radius 0) or sgpr_score_peak_topk's (radius > 0), their dir block
-// holding the codes; one direction and several paths: a code block [rb][M] behind it
-static size_t path_head_bytes(int R, int M, int L, int n_paths, int radius, int flags) {
-    const size_t rb = (size_t)score_block_rows(R, M, L - 1);
-    return (radius > 0 ? peak_head_bytes(R, M, L, flags) : seq_head_bytes(R, M, L, flags)) +
-           (n_paths > 1 && !seq_both(flags) ? a256(rb * M) : 0);
-}
-
 size_t sgpr_score_path_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int k,
                                             int radius, int flags) {
     if (!h || R < 0 || M < 0 || k < 1 || k > SGPR_TOPK_LARGE_MAX || L < 1 || L > SGPR_SEQ_MAX_LEN || ctx < 0 || ctx > R ||
@@ -1234,7 +1279,7 @@ size_t sgpr_score_path_topk_workspace_bytes(const sgpr_handle* h, int R, int M, 
         (flags & ~kSeqFlags) || !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
         return 0;
     if (R == ctx || M == 0) return 0;
-    return row_blocks_ws_bytes(h, R, M, path_head_bytes(R, M, L, n_paths, radius, flags), L - 1);
+    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, path_stages(L, nullptr, n_paths, radius, flags)), L - 1);
 }
 
 int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1258,58 +1303,12 @@ int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_code = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0) {
-        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, window,
-                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
-        if (rc != SGPR_OK || !d_codes) return rc;
-        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_code, d_codes, s);
-    }
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
-    // radius > 0: P block, then (L > 1) the Q block; radius 0: the Q block alone.  The code block follows the Q block.
-    const bool filter = radius == 0 || L > 1, want_code = filter && (seq_both(flags) || n_paths > 1);
-    const size_t q_at = 256 + sel_bytes + (radius > 0 ? blk_bytes : 0);
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
-    int clean_rows = 0;                                   // histogram rows the selection before left clear
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0), no = r0 + n - first;
-        const float* x = block + (size_t)(first - r0) * M;   // L = 1 before the peak step: every candidate is S itself
-        unsigned char* code = want_code ? head + q_at + blk_bytes : nullptr;
-        int rc;
-        if (filter) {
-            float* q = reinterpret_cast<float*>(head + q_at);
-            rc = launch_seq_path_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, h_offsets, n_paths, q,
-                                        M, code, M, s);
-            if (rc != SGPR_OK) return rc;
-            x = q;
-        }
-        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
-        if (radius > 0) {
-            float* p = reinterpret_cast<float*>(head + 256 + sel_bytes);
-            rc = launch_peak_filter(x, no, M, M, rs, row0 + first, window, causal, radius, p, M, s);
-            if (rc != SGPR_OK) return rc;
-            x = p;
-        }
-        const size_t o = (size_t)(first - ctx) * k;
-        rc = launch_select_rows(x, no, M, M, rs, row0 + first, window, causal, k, d_values + o, d_indices + o, head + 256,
-                                select_group_rows(no) <= clean_rows, h->d_status, s);
-        clean_rows = select_group_rows(no);
-        if (rc != SGPR_OK || !d_codes) return rc;
-        // (no code block: one candidate, or L = 1 where all candidates are one number and the first one keeps a listed,
-        //  hence non-NaN, entry - path 0 of the first direction asked for)
-        return launch_seq_dirs(d_indices + o, no, k, code, M, fixed_code, d_codes + o, s);
-    };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, path_head_bytes(R, M, L, n_paths, radius, flags),
-                            d_workspace, workspace_bytes, stream, select, crng, L - 1);
+    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
+                           d_indices, d_codes, path_stages(L, h_offsets, n_paths, radius, flags), d_workspace,
+                           workspace_bytes, stream);
 }
 
-// ---- sgpr_session_filter / sgpr_score_session_topk: the session-aware path-set filter (sgpr_session.hip) on a resident
+// ---- sgpr_session_filter / sgpr_score_session_topk: the session-aware path-set filter (session_kernel) on a resident
 //      matrix, and on sgpr_score_path_topk's row blocks (radius 0) with the row table shifted per block; the window is the
 //      filter's, so the selection runs without one
 static bool session_paths_ok(const char* fn, const int32_t* h_offsets, int n_paths, int L) {
@@ -1406,49 +1405,10 @@ int sgpr_score_session_topk(const sgpr_handle* h, const float* d_pooled_rows, in
                       d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_code = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
-    const int np = std::max(n_paths, 1), seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE);
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0) {
-        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx, -1,
-                                          causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
-        if (rc != SGPR_OK || !d_codes) return rc;
-        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_code, d_codes, s);
-    }
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
-    const bool want_code = seq_both(flags) || np > 1;     // the code block follows the Q block (path_head_bytes)
-    const size_t q_at = 256 + sel_bytes;
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
-    int clean_rows = 0;                                   // histogram rows the selection before left clear
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0), no = r0 + n - first, base = r0 - c;
-        float* q = reinterpret_cast<float*>(head + q_at);
-        unsigned char* code = want_code ? head + q_at + blk_bytes : nullptr;
-        // the filter's rectangle is rows base .. r0 + n - 1: the row table moves with it.  A session that starts before
-        // `base` starts at the rectangle's row 0 - where it matters (base > 0) every output row has its L - 1 rows
-        // inside the rectangle, and a depth of L is a depth of L from either start
-        int32_t local[SGPR_SESSION_MAX];
-        for (int j = 0; j < n_row_sessions; ++j)
-            local[j] = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)h_row_starts[j] - base, 0), c + n);
-        int rc = launch_session_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, seq_flags, h_offsets, np,
-                                       h_row_starts ? local : nullptr, n_row_sessions, h_col_starts, n_col_sessions,
-                                       d_row_self ? d_row_self + base : nullptr, row0 + base, window, q, M, code, M, s);
-        if (rc != SGPR_OK) return rc;
-        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
-        const size_t o = (size_t)(first - ctx) * k;
-        rc = launch_select_rows(q, no, M, M, rs, row0 + first, -1, causal, k, d_values + o, d_indices + o, head + 256,
-                                select_group_rows(no) <= clean_rows, h->d_status, s);
-        clean_rows = select_group_rows(no);
-        if (rc != SGPR_OK || !d_codes) return rc;
-        return launch_seq_dirs(d_indices + o, no, k, code, M, fixed_code, d_codes + o, s);
-    };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, path_head_bytes(R, M, L, np, 0, flags), d_workspace,
-                            workspace_bytes, stream, select, crng, L - 1);
+    const RankStages st = session_stages(L, h_offsets, n_paths, h_row_starts, n_row_sessions, h_col_starts,
+                                         n_col_sessions, flags);
+    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
+                           d_indices, d_codes, st, d_workspace, workspace_bytes, stream);
 }
 
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks
@@ -1681,6 +1641,56 @@ static size_t seq_above_head_bytes(int R, int M, int ctx, int L) {
     return 256 + seq_above_ws_bytes(score_block_rows(R, M, L - 1), M) + a256((size_t)(R - ctx + 1) * 8);
 }
 
+struct RangeSessions {     // what sgpr_score_session_above adds to sgpr_score_seq_above
+    const int32_t* offsets;
+    int n_paths;
+    const int32_t* row_starts;
+    int n_row;
+    const int32_t* col_starts;
+    int n_col;
+    int min_terms;
+};
+
+// the range pipeline of sgpr_score_seq_above (ss == nullptr: seq_above_kernel) and sgpr_score_session_above
+// (session_above_kernel) on the ranking pipeline's row blocks with context - no Q or code block.  Arguments and
+// workspace already checked
+static int range_row_blocks(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
+                            int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
+                            const RangeSessions* ss, float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values,
+                            unsigned char* d_codes, int64_t capacity, int64_t* d_row_ptr, unsigned long long* d_count,
+                            void* d_workspace, size_t workspace_bytes, void* stream) {
+    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE);
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
+    const int rb = score_block_rows(R, M, L - 1);
+    const size_t sel_bytes = seq_above_ws_bytes(rb, M);
+    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
+                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
+        const int first = std::max(r0, ctx);              // the block's first output row
+        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
+        // the rectangle starts c rows before r0 (the ranking pipeline's): its row 0 is row `base` of the call, and
+        // row_self / row0 and the row table move with it (a depth of L from either start, so min_terms sees the same)
+        const int c = std::min(L - 1, r0), base = r0 - c, o = first - ctx;
+        const float* rect = block - (size_t)c * M;
+        const int32_t* rs = d_row_self ? d_row_self + base : nullptr;
+        int64_t* rp = (d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(head + 256 + sel_bytes)) + o;
+        if (!ss)
+            return launch_seq_above(rect, c + n, M, M, first - base, L, seq_flags, rs, row0 + base, window, causal,
+                                    threshold, d_rows, d_cols, d_values, d_codes, capacity, rp, o, d_count, o > 0 ? 1 : 0,
+                                    head + 256, h->d_status, s);
+        int32_t local[SGPR_SESSION_MAX];
+        return launch_session_above(rect, c + n, M, M, first - base, L, seq_flags, ss->offsets, ss->n_paths,
+                                    shift_row_table(ss->row_starts, ss->n_row, base, c + n, local), ss->n_row,
+                                    ss->col_starts, ss->n_col, rs, row0 + base, window, causal, ss->min_terms, threshold,
+                                    d_rows, d_cols, d_values, d_codes, capacity, rp, o, d_count, o > 0 ? 1 : 0, head + 256,
+                                    h->d_status, s);
+    };
+    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_above_head_bytes(R, M, ctx, L), d_workspace,
+                            workspace_bytes, stream, select, crng, L - 1);
+}
+
 size_t sgpr_score_seq_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags) {
     if (!seq_query_ok(h, R, M, ctx, L, flags)) return 0;
     if (R == ctx || M == 0) return 0;
@@ -1702,31 +1712,13 @@ int sgpr_score_seq_above(const sgpr_handle* h, const float* d_pooled_rows, int R
     if (!workspace_ok("sgpr_score_seq_above", sgpr_score_seq_above_workspace_bytes(h, R, M, ctx, L, flags), d_workspace,
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t sel_bytes = seq_above_ws_bytes(rb, M);
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0);
-        int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(head + 256 + sel_bytes);
-        // the rectangle starts c rows before r0 (sgpr_score_seq_topk's): its row 0 is row r0 - c of the call
-        return launch_seq_above(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags,
-                                d_row_self ? d_row_self + (r0 - c) : nullptr, row0 + (r0 - c), window, causal, threshold,
-                                d_rows, d_cols, d_values, d_dirs, capacity, rp + (first - ctx), first - ctx, d_count,
-                                first > ctx ? 1 : 0, head + 256, h->d_status, s);
-    };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_above_head_bytes(R, M, ctx, L), d_workspace,
-                            workspace_bytes, stream, select, crng, L - 1);
+    return range_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, L, nullptr,
+                            threshold, d_rows, d_cols, d_values, d_dirs, capacity, d_row_ptr, d_count, d_workspace,
+                            workspace_bytes, stream);
 }
 
 // ---- sgpr_session_rows_above / sgpr_score_session_above: the range selection on the session-aware path-set score with a
-//      minimum term count (session_above_kernel, sgpr_session_above.hip) on a resident matrix, and on
+//      minimum term count (session_above_kernel) on a resident matrix, and on
 //      sgpr_score_seq_above's row blocks with the row table shifted per block as sgpr_score_session_topk shifts it
 static bool session_above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int ctx, int row0, int window,
                                   int flags, int L, const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts,
@@ -1810,33 +1802,10 @@ int sgpr_score_session_above(const sgpr_handle* h, const float* d_pooled_rows, i
                                                                    n_col_sessions),
                       d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE);
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t sel_bytes = seq_above_ws_bytes(rb, M);
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0), base = r0 - c;
-        int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(head + 256 + sel_bytes);
-        // the rectangle is rows base .. r0 + n - 1 and the row table moves with it (sgpr_score_session_topk's shift): a
-        // session that starts before `base` starts at the rectangle's row 0, and where that matters (base > 0) every
-        // output row has its L - 1 rows inside the rectangle - a depth of L from either start, so min_terms sees the same
-        int32_t local[SGPR_SESSION_MAX];
-        for (int j = 0; j < n_row_sessions; ++j)
-            local[j] = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)h_row_starts[j] - base, 0), c + n);
-        return launch_session_above(block - (size_t)c * M, c + n, M, M, c + first - r0, L, seq_flags, h_offsets, n_paths,
-                                    h_row_starts ? local : nullptr, n_row_sessions, h_col_starts, n_col_sessions,
-                                    d_row_self ? d_row_self + base : nullptr, row0 + base, window, causal, min_terms,
-                                    threshold, d_rows, d_cols, d_values, d_codes, capacity, rp + (first - ctx),
-                                    first - ctx, d_count, first > ctx ? 1 : 0, head + 256, h->d_status, s);
-    };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_above_head_bytes(R, M, ctx, L), d_workspace,
-                            workspace_bytes, stream, select, crng, L - 1);
+    const RangeSessions ss = {h_offsets, n_paths, h_row_starts, n_row_sessions, h_col_starts, n_col_sessions, min_terms};
+    return range_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, L, &ss, threshold,
+                            d_rows, d_cols, d_values, d_codes, capacity, d_row_ptr, d_count, d_workspace, workspace_bytes,
+                            stream);
 }
 
 // ---- sgpr_score_positives / sgpr_score_threshold_counts: the fused evaluation epilogues on the production handle; the

@@ -276,12 +276,12 @@ int launch_seq_filter(const float* score, int R, int M, int64_t ld, int ctx, int
 // out [n][k] = dir [n][ld] at the selected columns idx [n][k] (dir == nullptr: `fixed`); 0 where idx is -1
 int launch_seq_dirs(const int32_t* idx, int n, int k, const unsigned char* dir, int64_t ld, int fixed,
                     unsigned char* out, hipStream_t stream);
-// the path-set score filter of a resident R x M matrix (sgpr_seq_path.hip): launch_seq_filter's arguments with a host
+// the path-set score filter of a resident R x M matrix (seq_path_kernel, sgpr_seq.hip): launch_seq_filter's arguments with a host
 // table offsets [n_paths][L] (already checked; copied into the launch) and the winner's code (direction bit | path << 1)
 // into code [R - ctx][ldc] (or nullptr)
 int launch_seq_path_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
                            int n_paths, float* out, int64_t ldo, unsigned char* code, int64_t ldc, hipStream_t stream);
-// the session-aware path-set filter of a resident R x M matrix (sgpr_session.hip): launch_seq_path_filter's arguments
+// the session-aware path-set filter of a resident R x M matrix (session_kernel, sgpr_seq.hip): launch_seq_path_filter's arguments
 // (offsets == nullptr: the unit diagonal) with host session tables (already checked; nullptr: one session; copied into
 // the launch) and the session window on the end point (row_self [R] / row0 belong to the matrix's row 0; window < 0: none)
 int launch_session_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
@@ -326,7 +326,7 @@ int launch_seq_above(const float* score, int R, int M, int64_t ld, int ctx, int 
                      int accumulate, void* ws, int32_t* status, hipStream_t stream);
 // seq_above_rowscan_kernel on its own (sgpr_seq.hip): seg [n][nseg] -> exclusive offsets in place, cnt [n] = row totals
 int launch_seq_above_rowscan(int32_t* seg, int n, int nseg, int32_t* cnt, hipStream_t stream);
-// launch_seq_above on the session-aware path-set score with a minimum term count (sgpr_session_above.hip; sgpr_session_rows_above
+// launch_seq_above on the session-aware path-set score with a minimum term count (session_above_kernel, sgpr_seq.hip; sgpr_session_rows_above
 // and each row block of sgpr_score_session_above): launch_session_filter's paths, tables and session window, codes in
 // place of directions.  ws: seq_above_ws_bytes(R - ctx, M)
 int launch_session_above(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,

@@ -23,7 +23,7 @@ from test_seq_paths_host import PLANTED_SLOPES, planted_figures
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TR, TC = 32, 256                  # seq_path_kernel's tile (sgpr_seq_path.hip): output rows x columns
+TR, TC = 32, 256                  # seq_path_kernel's tile (SEQ_TR, SEQ_TC of sgpr_seq.hip): output rows x columns
 
 
 @pytest.fixture(scope="module")

@@ -19,7 +19,7 @@ from test_session_host import planted_figures
 
 pytestmark = pytest.mark.gpu
 
-TR, TC = 32, 256                  # session_kernel's tile (sgpr_session.hip): output rows x columns
+TR, TC = 32, 256                  # session_kernel's tile (SEQ_TR, SEQ_TC of sgpr_seq.hip): output rows x columns
 
 
 @pytest.fixture(scope="module")

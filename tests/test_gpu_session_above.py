@@ -23,7 +23,7 @@ from test_gpu_session import _row_tables, _tab
 pytestmark = pytest.mark.gpu
 
 INF = float("inf")
-TR, TC = 32, 256                  # session_above_kernel's tile (sgpr_session_above.hip): output rows x columns
+TR, TC = 32, 256                  # session_above_kernel's tile (SEQ_TR, SEQ_TC of sgpr_seq.hip): output rows x columns
 
 
 @pytest.fixture(scope="module")
