@@ -6,7 +6,9 @@ sha256 of every source, header and the compiler flags is stored next to each obj
 (`*.srchash`); an artefact is reused only while its recorded hash equals the hash of what is on disk now.
 `force=True` (or SGPR_FORCE_BUILD=1 in the environment) recompiles everything from scratch.
 """
+import collections
 import concurrent.futures
+import ctypes
 import hashlib
 import os
 import re
@@ -56,10 +58,61 @@ def source_hash():
     return _hash_of([os.path.join(CSRC, s) for s in _sources()] + HEADERS)
 
 
+HeaderAbi = collections.namedtuple("HeaderAbi", "functions constants errors")
+_VALUE_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+                "double": ctypes.c_double}
+_RETURN_TYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
+
+
+def parse_header(text):
+    """What a C header in the style of include/sgpr.h declares -> HeaderAbi(functions, constants, errors):
+    functions [(name, restype, argtypes)] in ctypes terms, one per `ret sgpr_name(args);` - every pointer parameter is
+    c_void_p, values are int / int64_t / size_t / float / double, returns int / size_t / void / const char*;
+    constants {name: value} of the `#define SGPR_* <integer>` lines; errors {name: value} of the SGPR_OK / SGPR_E_*
+    enum.  Only that style is read: comments, preprocessor lines, struct typedefs and the extern "C" brace are dropped.
+    A declaration with any other type raises ImportError naming it (ctypes would otherwise pass it as an int)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {m.group(1): int(m.group(2), 0)
+                 for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(SGPR_\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    errors = {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}\s*;", text, re.S):
+        for name, value in re.findall(r"(SGPR_\w+)\s*=\s*(-?\d+)", body):
+            errors[name] = int(value)
+    text = re.sub(r"\benum\s*\{.*?\}\s*;|\btypedef\s+struct\s+\w+\s*(\{.*?\})?\s*\w+\s*;|\bextern\s+\"C\"\s*\{", " ", text,
+                  flags=re.S)
+    functions = []
+    for decl in text.split(";"):
+        decl = " ".join(decl.split()).strip("} ")                      # (the closing brace of extern "C")
+        if not decl:
+            continue
+        m = re.fullmatch(r"(.+?) ?\b(sgpr_\w+) ?\((.*)\)", decl)
+        if m is None or m.group(1) not in _RETURN_TYPES:
+            raise ImportError("C header: cannot bind `%s`: not `int | size_t | void | const char* sgpr_name(...)`" % decl)
+        argtypes = []
+        for param in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            words = param.replace("*", " * ").split()
+            kind = " ".join(w for w in words[:-1] if w != "const")   # (the last word is the parameter's name)
+            if "*" in words[:-1]:
+                argtypes.append(ctypes.c_void_p)
+            elif kind in _VALUE_TYPES:
+                argtypes.append(_VALUE_TYPES[kind])
+            else:
+                raise ImportError("C header: cannot bind `%s`: parameter `%s` is neither a pointer nor one of %s"
+                                  % (decl, param.strip(), ", ".join(_VALUE_TYPES)))
+        functions.append((m.group(2), _RETURN_TYPES[m.group(1)], argtypes))
+    return HeaderAbi(functions, constants, errors)
+
+
+def header_abi():
+    """parse_header of include/sgpr.h: the one declaration the Python binding follows."""
+    with open(HEADERS[0]) as f:
+        return parse_header(f.read())
+
+
 def header_abi_version():
     """SGPR_ABI_VERSION of include/sgpr.h - what a loaded library must answer from sgpr_abi_version()."""
-    with open(HEADERS[0]) as f:
-        return int(re.search(r"#define\s+SGPR_ABI_VERSION\s+(\d+)", f.read()).group(1))
+    return header_abi().constants["SGPR_ABI_VERSION"]
 
 
 def _recorded(path):

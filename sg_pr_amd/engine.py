@@ -14,9 +14,13 @@ import torch
 
 from . import _build
 
+# include/sgpr.h is the one declaration of the C-ABI: its functions, limits, flag bits and error codes are read from it
+_ABI = _build.header_abi()
+_C = _ABI.constants
+
 NUM_LABELS = 12
 F3 = 32
-MAX_NODES = 256     # SGPR_MAX_NODES of include/sgpr.h: node_num of the tuned kernels (beyond: the any-shape kernels)
+MAX_NODES = _C["SGPR_MAX_NODES"]     # node_num of the tuned kernels (beyond: the any-shape kernels)
 
 # order of the fp32 tensors in the weights blob (include/sgpr.h, sgpr_weights_count)
 _CONV_BLOCKS = ["dgcnn_s_conv1", "dgcnn_f_conv1", "dgcnn_s_conv2", "dgcnn_f_conv2",
@@ -28,55 +32,19 @@ BLOB_KEYS += ["attention.weight_matrix", "tensor_network.weight_matrix", "tensor
               "tensor_network.bias", "fully_connected_first.weight", "fully_connected_first.bias",
               "scoring_layer.weight", "scoring_layer.bias"]
 
-SGPR_OK = 0
-ERROR_NAMES = {-1: "SGPR_E_INVALID", -2: "SGPR_E_DIMS", -3: "SGPR_E_NODES", -4: "SGPR_E_K", -5: "SGPR_E_LABEL",
-               -6: "SGPR_E_HIP", -7: "SGPR_E_WORKSPACE", -8: "SGPR_E_BLOB"}
+SGPR_OK = _ABI.errors["SGPR_OK"]
+ERROR_NAMES = {code: name for name, code in _ABI.errors.items() if code != SGPR_OK}
 
 # every symbol include/sgpr.h declares (tests check the library exports all of them)
-ABI_SYMBOLS = ["sgpr_weights_count", "sgpr_create", "sgpr_destroy", "sgpr_pooled_width", "sgpr_is_any_shape",
-               "sgpr_embed_workspace_bytes", "sgpr_embed",
-               "sgpr_embed_capped", "sgpr_embed_ordered", "sgpr_embed_ragged",
-               "sgpr_size_order_workspace_bytes", "sgpr_size_order",
-               "sgpr_embed_dense", "sgpr_embed_debug", "sgpr_score_pairs", "sgpr_pair_plan_ints", "sgpr_pair_plan",
-               "sgpr_score_pair_list_workspace_bytes", "sgpr_score_pair_list", "sgpr_score_all_pairs_workspace_bytes",
-               "sgpr_score_all_pairs", "sgpr_score_all_pairs_multi_workspace_bytes", "sgpr_score_all_pairs_multi",
-               "sgpr_forward_workspace_bytes", "sgpr_forward_dense", "sgpr_check_status",
-               "sgpr_pair_positives", "sgpr_pair_threshold_counts_workspace_bytes", "sgpr_pair_threshold_counts",
-               "sgpr_f1_max_workspace_bytes", "sgpr_f1_max", "sgpr_topk_rows",
-               "sgpr_score_topk_workspace_bytes", "sgpr_score_topk",
-               "sgpr_topk_rows_large_workspace_bytes", "sgpr_topk_rows_large",
-               "sgpr_score_topk_large_workspace_bytes", "sgpr_score_topk_large",
-               "sgpr_seq_filter", "sgpr_score_seq_topk_workspace_bytes", "sgpr_score_seq_topk",
-               "sgpr_peak_filter", "sgpr_score_peak_topk_workspace_bytes", "sgpr_score_peak_topk",
-               "sgpr_seq_path_filter", "sgpr_score_path_topk_workspace_bytes", "sgpr_score_path_topk",
-               "sgpr_session_filter", "sgpr_score_session_topk_workspace_bytes", "sgpr_score_session_topk",
-               "sgpr_score_mine_workspace_bytes", "sgpr_score_mine", "sgpr_mine_rows_workspace_bytes", "sgpr_mine_rows",
-               "sgpr_score_above_workspace_bytes", "sgpr_score_above", "sgpr_rows_above_workspace_bytes",
-               "sgpr_rows_above", "sgpr_score_positives_workspace_bytes", "sgpr_score_positives",
-               "sgpr_score_threshold_counts_workspace_bytes", "sgpr_score_threshold_counts",
-               "sgpr_seq_rows_above_workspace_bytes", "sgpr_seq_rows_above",
-               "sgpr_score_seq_above_workspace_bytes", "sgpr_score_seq_above",
-               "sgpr_score_seq_positives_workspace_bytes", "sgpr_score_seq_positives",
-               "sgpr_score_seq_threshold_counts_workspace_bytes", "sgpr_score_seq_threshold_counts",
-               "sgpr_session_rows_above_workspace_bytes", "sgpr_session_rows_above",
-               "sgpr_score_session_above_workspace_bytes", "sgpr_score_session_above",
-               "sgpr_embed_lds_bytes", "sgpr_knn", "sgpr_graph_feature", "sgpr_attention_pool", "sgpr_ntn",
-               "sgpr_attention_pool_any", "sgpr_ntn_any", "sgpr_verify_pairs",
-               "sgpr_closure_consistency_workspace_bytes", "sgpr_closure_consistency",
-               "sgpr_consistent_set_workspace_bytes", "sgpr_consistent_set",
-               "sgpr_edgeconv_train_workspace_bytes", "sgpr_edgeconv_train_forward", "sgpr_edgeconv_train_backward",
-               "sgpr_pairs_train_workspace_bytes", "sgpr_pairs_train_forward", "sgpr_pairs_train_backward",
-               "sgpr_cluster_workspace_bytes", "sgpr_cluster_scan", "sgpr_graph_edges",
-               "sgpr_debug_set_profile_buffer", "sgpr_debug_set_skip_mask", "sgpr_debug_uses_f16_planes", "sgpr_last_error",
-               "sgpr_abi_version"]
+ABI_SYMBOLS = [name for name, _, _ in _ABI.functions]
 
 
 # struct sgpr_rank_group of include/sgpr.h
 RANK_GROUP = np.dtype([("value", "<f4", (8,)), ("pairs", "<u4", (8,))])
 
 
-SEQ_MAX_PATHS = 16          # SGPR_SEQ_MAX_PATHS of include/sgpr.h
-SEQ_PATH_MAX_OFFSET = 64    # SGPR_SEQ_PATH_MAX_OFFSET
+SEQ_MAX_PATHS = _C["SGPR_SEQ_MAX_PATHS"]
+SEQ_PATH_MAX_OFFSET = _C["SGPR_SEQ_PATH_MAX_OFFSET"]
 
 
 def _slope(s):
@@ -129,7 +97,7 @@ def _path_table(paths, seq_len):
     return t
 
 
-SESSION_MAX = 64            # SGPR_SESSION_MAX of include/sgpr.h
+SESSION_MAX = _C["SGPR_SESSION_MAX"]
 
 
 def _session_table(starts):
@@ -175,12 +143,11 @@ def load_library():
         raise ImportError("HIP engine %s is not built; run `python -m sg_pr_amd._build` "
                           "(there is no CPU fallback)" % path)
     lib = ctypes.CDLL(path)
-    vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
     # first thing: a library built from other sources than the header this binding follows must say so before any
     # missing symbol raises an AttributeError
     want = _build.header_abi_version()
     try:
-        lib.sgpr_abi_version.restype = i32
+        lib.sgpr_abi_version.restype = ctypes.c_int
         lib.sgpr_abi_version.argtypes = []
         have = lib.sgpr_abi_version()
     except AttributeError:
@@ -188,221 +155,10 @@ def load_library():
     if have != want:
         raise ImportError("%s reports C-ABI version %s, include/sgpr.h declares %d: rebuild it "
                           "(`python -m sg_pr_amd._build --force`)" % (path, have, want))
-    lib.sgpr_weights_count.restype = sz
-    lib.sgpr_weights_count.argtypes = [ctypes.POINTER(SgprDims)]
-    lib.sgpr_create.restype = i32
-    lib.sgpr_create.argtypes = [vp, sz, ctypes.POINTER(SgprDims), i32, ctypes.POINTER(vp)]
-    lib.sgpr_destroy.restype = None
-    lib.sgpr_destroy.argtypes = [vp]
-    lib.sgpr_pooled_width.restype = i32
-    lib.sgpr_pooled_width.argtypes = [vp]
-    lib.sgpr_is_any_shape.restype = i32
-    lib.sgpr_is_any_shape.argtypes = [vp]
-    lib.sgpr_embed_workspace_bytes.restype = sz
-    lib.sgpr_embed_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    lib.sgpr_embed.restype = i32
-    lib.sgpr_embed.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_embed_capped.restype = i32
-    lib.sgpr_embed_capped.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_embed_ordered.restype = i32
-    lib.sgpr_embed_ordered.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_embed_ragged.restype = i32
-    lib.sgpr_embed_ragged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_size_order_workspace_bytes.restype = sz
-    lib.sgpr_size_order_workspace_bytes.argtypes = [i32]
-    lib.sgpr_size_order.restype = i32
-    lib.sgpr_size_order.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_embed_dense.restype = i32
-    lib.sgpr_embed_dense.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_embed_debug.restype = i32
-    lib.sgpr_embed_debug.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_score_pairs.restype = i32
-    lib.sgpr_score_pairs.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
-    lib.sgpr_pair_plan_ints.restype = sz
-    lib.sgpr_pair_plan_ints.argtypes = [i64, i32]
-    lib.sgpr_pair_plan.restype = i32
-    lib.sgpr_pair_plan.argtypes = [vp, vp, i64, i32, i32, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(i32),
-                                   ctypes.POINTER(i32)]
-    lib.sgpr_score_pair_list_workspace_bytes.restype = sz
-    lib.sgpr_score_pair_list_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.sgpr_score_pair_list.restype = i32
-    lib.sgpr_score_pair_list.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, sz, vp]
-    lib.sgpr_score_all_pairs_workspace_bytes.restype = sz
-    lib.sgpr_score_all_pairs_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.sgpr_score_all_pairs.restype = i32
-    lib.sgpr_score_all_pairs.argtypes = [vp, vp, i32, vp, i32, vp, i64, vp, sz, vp]
-    lib.sgpr_score_all_pairs_multi_workspace_bytes.restype = sz
-    lib.sgpr_score_all_pairs_multi_workspace_bytes.argtypes = [vp, i32, vp]
-    lib.sgpr_score_all_pairs_multi.restype = i32
-    lib.sgpr_score_all_pairs_multi.argtypes = [vp, i32, vp, vp, sz, vp]
-    lib.sgpr_forward_workspace_bytes.restype = sz
-    lib.sgpr_forward_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    lib.sgpr_forward_dense.restype = i32
-    lib.sgpr_forward_dense.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_check_status.restype = i32
-    lib.sgpr_check_status.argtypes = [vp, vp]
-    dbl = ctypes.c_double
-    lib.sgpr_pair_positives.restype = i32
-    lib.sgpr_pair_positives.argtypes = [vp, vp, i32, i32, i64, i32, vp, dbl, dbl, vp, i64, vp, i64, vp, vp]
-    lib.sgpr_pair_threshold_counts.restype = i32
-    lib.sgpr_pair_threshold_counts_workspace_bytes.restype = sz
-    lib.sgpr_pair_threshold_counts_workspace_bytes.argtypes = [vp, i32]
-    lib.sgpr_pair_threshold_counts.argtypes = [vp, vp, i32, i32, i64, i32, vp, dbl, dbl, vp, i64, vp, i32, vp, i32, vp, vp, vp, sz,
-                                               vp]
-    lib.sgpr_f1_max_workspace_bytes.restype = sz
-    lib.sgpr_f1_max_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.sgpr_f1_max.restype = i32
-    lib.sgpr_f1_max.argtypes = [vp, vp, i32, i32, i64, i32, vp, dbl, dbl, vp, i64, vp, vp, sz, vp]
-    lib.sgpr_topk_rows.restype = i32
-    lib.sgpr_topk_rows.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, vp, vp]
-    lib.sgpr_score_topk_workspace_bytes.restype = sz
-    lib.sgpr_score_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
-    lib.sgpr_score_topk.restype = i32
-    lib.sgpr_score_topk.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_topk_rows_large_workspace_bytes.restype = sz
-    lib.sgpr_topk_rows_large_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
-    lib.sgpr_topk_rows_large.restype = i32
-    lib.sgpr_topk_rows_large.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_score_topk_large_workspace_bytes.restype = sz
-    lib.sgpr_score_topk_large_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
-    lib.sgpr_score_topk_large.restype = i32
-    lib.sgpr_score_topk_large.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_seq_filter.restype = i32
-    lib.sgpr_seq_filter.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, i64, vp, vp]
-    lib.sgpr_score_seq_topk_workspace_bytes.restype = sz
-    lib.sgpr_score_seq_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]
-    lib.sgpr_score_seq_topk.restype = i32
-    lib.sgpr_score_seq_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_seq_path_filter.restype = i32
-    lib.sgpr_seq_path_filter.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, i32, vp, i64, vp, vp]
-    lib.sgpr_score_path_topk_workspace_bytes.restype = sz
-    lib.sgpr_score_path_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32]
-    lib.sgpr_score_path_topk.restype = i32
-    lib.sgpr_score_path_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp,
-                                         vp, sz, vp]
-    lib.sgpr_session_filter.restype = i32
-    lib.sgpr_session_filter.argtypes = [vp, vp, i32, i32, i64, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp,
-                                        i64, vp, vp]
-    lib.sgpr_score_session_topk_workspace_bytes.restype = sz
-    lib.sgpr_score_session_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32]
-    lib.sgpr_score_session_topk.restype = i32
-    lib.sgpr_score_session_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32,
-                                            i32, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_peak_filter.restype = i32
-    lib.sgpr_peak_filter.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, i32, vp, i64, vp]
-    lib.sgpr_score_peak_topk_workspace_bytes.restype = sz
-    lib.sgpr_score_peak_topk_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32]
-    lib.sgpr_score_peak_topk.restype = i32
-    lib.sgpr_score_peak_topk.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz,
-                                         vp]
-    lib.sgpr_score_mine_workspace_bytes.restype = sz
-    lib.sgpr_score_mine_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
-    lib.sgpr_score_mine.restype = i32
-    lib.sgpr_score_mine.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_mine_rows_workspace_bytes.restype = sz
-    lib.sgpr_mine_rows_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
-    lib.sgpr_mine_rows.restype = i32
-    lib.sgpr_mine_rows.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, sz, vp]
-    f32 = ctypes.c_float
-    lib.sgpr_score_above_workspace_bytes.restype = sz
-    lib.sgpr_score_above_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    lib.sgpr_score_above.restype = i32
-    lib.sgpr_score_above.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
-    lib.sgpr_rows_above_workspace_bytes.restype = sz
-    lib.sgpr_rows_above_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.sgpr_rows_above.restype = i32
-    lib.sgpr_rows_above.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, i32, f32, vp, vp, vp, i64, vp, vp, vp, sz, vp]
-    lib.sgpr_score_positives_workspace_bytes.restype = sz
-    lib.sgpr_score_positives_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.sgpr_score_positives.restype = i32
-    lib.sgpr_score_positives.argtypes = [vp, vp, i32, vp, i32, i32, vp, dbl, dbl, vp, i64, vp, i64, vp, vp, sz, vp]
-    lib.sgpr_score_threshold_counts_workspace_bytes.restype = sz
-    lib.sgpr_score_threshold_counts_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    lib.sgpr_score_threshold_counts.restype = i32
-    lib.sgpr_score_threshold_counts.argtypes = [vp, vp, i32, vp, i32, i32, vp, dbl, dbl, vp, i64, vp, i32, vp, i32, vp, vp,
-                                                vp, sz, vp]
-    lib.sgpr_seq_rows_above_workspace_bytes.restype = sz
-    lib.sgpr_seq_rows_above_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    lib.sgpr_seq_rows_above.restype = i32
-    lib.sgpr_seq_rows_above.argtypes = [vp, vp, i32, i32, i64, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp,
-                                        vp, vp, sz, vp]
-    lib.sgpr_score_seq_above_workspace_bytes.restype = sz
-    lib.sgpr_score_seq_above_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32]
-    lib.sgpr_score_seq_above.restype = i32
-    lib.sgpr_score_seq_above.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp,
-                                         vp, vp, sz, vp]
-    lib.sgpr_score_seq_positives_workspace_bytes.restype = sz
-    lib.sgpr_score_seq_positives_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32]
-    lib.sgpr_score_seq_positives.restype = i32
-    lib.sgpr_score_seq_positives.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, dbl, dbl, vp, i64, vp, i64, vp,
-                                             vp, sz, vp]
-    lib.sgpr_score_seq_threshold_counts_workspace_bytes.restype = sz
-    lib.sgpr_score_seq_threshold_counts_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]
-    lib.sgpr_score_seq_threshold_counts.restype = i32
-    lib.sgpr_score_seq_threshold_counts.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, dbl, dbl, vp, i64, vp,
-                                                    i32, vp, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_embed_lds_bytes.restype = sz
-    lib.sgpr_session_rows_above_workspace_bytes.restype = sz
-    lib.sgpr_session_rows_above_workspace_bytes.argtypes = [vp, i32, i32, i32]
-    lib.sgpr_session_rows_above.restype = i32
-    lib.sgpr_session_rows_above.argtypes = [vp, vp, i32, i32, i64, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32,
-                                            i32, f32, vp, vp, vp, vp, i64, vp, vp, vp, sz, vp]
-    lib.sgpr_score_session_above_workspace_bytes.restype = sz
-    lib.sgpr_score_session_above_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32]
-    lib.sgpr_score_session_above.restype = i32
-    lib.sgpr_score_session_above.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32,
-                                             i32, f32, vp, vp, vp, vp, i64, vp, vp, vp, sz, vp]
-    lib.sgpr_embed_lds_bytes.argtypes = [vp, i32, i32]
-    lib.sgpr_knn.restype = i32
-    lib.sgpr_knn.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.sgpr_graph_feature.restype = i32
-    lib.sgpr_graph_feature.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.sgpr_attention_pool.restype = i32
-    lib.sgpr_attention_pool.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    lib.sgpr_ntn.restype = i32
-    lib.sgpr_ntn.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
-    lib.sgpr_attention_pool_any.restype = i32
-    lib.sgpr_attention_pool_any.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    lib.sgpr_ntn_any.restype = i32
-    lib.sgpr_ntn_any.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]
-    lib.sgpr_verify_pairs.restype = i32
-    f32 = ctypes.c_float
-    lib.sgpr_verify_pairs.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, i64, f32, f32, f32, f32, i32, vp, vp]
-    dbl = ctypes.c_double
-    lib.sgpr_closure_consistency_workspace_bytes.restype = sz
-    lib.sgpr_closure_consistency_workspace_bytes.argtypes = [i32]
-    lib.sgpr_closure_consistency.restype = i32
-    lib.sgpr_closure_consistency.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, dbl, dbl, dbl, vp, vp, vp, sz, vp]
-    lib.sgpr_consistent_set_workspace_bytes.restype = sz
-    lib.sgpr_consistent_set_workspace_bytes.argtypes = [i32]
-    lib.sgpr_consistent_set.restype = i32
-    lib.sgpr_consistent_set.argtypes = [vp, i32, vp, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_edgeconv_train_workspace_bytes.restype = sz
-    lib.sgpr_edgeconv_train_workspace_bytes.argtypes = [i32, i32]
-    lib.sgpr_edgeconv_train_forward.restype = i32
-    lib.sgpr_edgeconv_train_forward.argtypes = [vp] * 5 + [i32] * 4 + [ctypes.c_float] + [vp] * 6 + [sz, vp]
-    lib.sgpr_edgeconv_train_backward.restype = i32
-    lib.sgpr_edgeconv_train_backward.argtypes = [vp] * 10 + [i32] * 4 + [ctypes.c_float] + [vp] * 5 + [sz, vp]
-    lib.sgpr_pairs_train_workspace_bytes.restype = sz
-    lib.sgpr_pairs_train_workspace_bytes.argtypes = [i32] * 4
-    lib.sgpr_pairs_train_forward.restype = i32
-    lib.sgpr_pairs_train_forward.argtypes = [vp] * 9 + [ctypes.c_float] * 2 + [i32] * 4 + [vp] * 4 + [sz, vp]
-    lib.sgpr_pairs_train_backward.restype = i32
-    lib.sgpr_pairs_train_backward.argtypes = [vp] * 12 + [ctypes.c_float] * 2 + [i32] * 4 + [vp] * 9 + [sz, vp]
-    lib.sgpr_cluster_workspace_bytes.restype = sz
-    lib.sgpr_cluster_workspace_bytes.argtypes = [i32]
-    lib.sgpr_cluster_scan.restype = i32
-    lib.sgpr_cluster_scan.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.sgpr_graph_edges.restype = i32
-    lib.sgpr_graph_edges.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, sz, vp]
-    lib.sgpr_debug_set_skip_mask.restype = None
-    lib.sgpr_debug_set_skip_mask.argtypes = [vp, i32]
-    lib.sgpr_debug_uses_f16_planes.restype = i32
-    lib.sgpr_debug_uses_f16_planes.argtypes = [vp]
-    lib.sgpr_debug_set_profile_buffer.restype = None
-    lib.sgpr_debug_set_profile_buffer.argtypes = [vp, vp]
-    lib.sgpr_last_error.restype = ctypes.c_char_p
-    lib.sgpr_last_error.argtypes = []
+    # the signatures are the header's (_build.parse_header): there is no table of them in Python
+    for name, restype, argtypes in _ABI.functions:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -427,6 +183,28 @@ def blob_from_state_dict(sd):
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+_UNSET = object()      # "argument not passed" where None is a value
+
+
+def _check(rc):
+    if rc != SGPR_OK:
+        raise SgprError(rc, load_library().sgpr_last_error().decode())
+
+
+def _stream(device):
+    """the stream current on `device`, as the C-ABI takes it"""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _on(t, device, dtype):
+    """t (a tensor or anything torch.as_tensor takes) on `device`, of `dtype`, contiguous; as it is where it is all that"""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+    if t.device != device or t.dtype != dtype or not t.is_contiguous():
+        t = t.to(device=device, dtype=dtype).contiguous()
+    return t
 
 
 class Engine:
@@ -477,19 +255,13 @@ class Engine:
             pass
 
     # ------------------------------------------------------------------ helpers
-    def _check(self, rc):
-        if rc != SGPR_OK:
-            raise SgprError(rc, self.lib.sgpr_last_error().decode())
+    _check = staticmethod(_check)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _stream(self.device)
 
     def _dev(self, t, dtype, name):
-        if not isinstance(t, torch.Tensor):
-            t = torch.as_tensor(t)
-        if t.device != self.device or t.dtype != dtype or not t.is_contiguous():
-            t = t.to(device=self.device, dtype=dtype).contiguous()
-        return t
+        return _on(t, self.device, dtype)
 
     def _pooled(self, t, name):
         """a pooled-vector argument on the device, fp32, contiguous - and of THIS handle's row width: the kernels read
@@ -857,7 +629,7 @@ class Engine:
         self._check(rc)
         return score
 
-    MAX_PAIR_JOBS = 8
+    MAX_PAIR_JOBS = _C["SGPR_MAX_PAIR_JOBS"]
 
     def score_all_pairs_multi(self, jobs):
         """Several independent rectangles with one pair of launches (sgpr_score_all_pairs_multi).  jobs: list of
@@ -883,99 +655,105 @@ class Engine:
         return outs
 
     # ------------------------------------------------------------------ consumers of the score matrix
-    def _truth(self, score, row0, pose_xz, gt):
+    def _matrix(self, score, name="score", rank2=False):
+        """A resident-matrix argument -> (tensor, R, M, ld).  A float32 2-D tensor on this device with unit column stride
+        and a row stride >= M (any strides where there is at most one row / column to step over) is read in place;
+        anything else - a host array, another dtype or device, a column-strided or transposed view - is converted once.
+        rank2: refuse anything but two dimensions with a ValueError before converting."""
         if not isinstance(score, torch.Tensor):
             score = torch.as_tensor(score)
-        if score.device != self.device or score.dtype != torch.float32 or score.dim() != 2 or score.stride(1) != 1:
-            score = score.to(device=self.device, dtype=torch.float32).contiguous()      # (row-strided views pass as they are)
+        if rank2 and score.dim() != 2:
+            raise ValueError("%s must be [R, M], got %s" % (name, tuple(score.shape),))
+        if not (score.device == self.device and score.dtype == torch.float32 and score.dim() == 2
+                and (score.shape[1] <= 1 or score.stride(1) == 1)
+                and (score.shape[0] <= 1 or score.stride(0) >= score.shape[1])):
+            score = score.to(device=self.device, dtype=torch.float32).contiguous()
         r, m = score.shape
-        if pose_xz is not None:
-            pose_xz = self._dev(pose_xz, torch.float64, "pose_xz")
-            assert pose_xz.shape[1] == 2 and pose_xz.shape[0] >= max(m, row0 + r)
-            gt = None
-        elif gt is not None:
-            gt = self._dev(gt, torch.int8, "gt")
-            assert gt.shape == (r, m)
-        else:
-            raise ValueError("the pair consumers need poses or explicit labels")
-        return score, r, m, pose_xz, gt
+        return score, r, m, max(score.stride(0), m) if r > 1 else m
 
-    def pair_positives(self, score, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None):
-        """Scores of the positive pairs of a rectangle that stays on the device (sgpr_pair_positives): float32 device
-        tensor (unordered) and the number of positives skipped for a negative / NaN score."""
-        score, r, m, pose_xz, gt = self._truth(score, row0, pose_xz, gt)
-        count = torch.empty(2, dtype=torch.int64, device=self.device)
-        # one launch when the list fits the first guess (positives are rare: loop closures), a second one sized exactly
-        # otherwise
-        cap = min(r * m, 1 << 20)
-        while True:
-            out = torch.empty(cap, dtype=torch.float32, device=self.device)
-            rc = self.lib.sgpr_pair_positives(self._h, _ptr(score), r, m, score.stride(0), int(row0), _ptr(pose_xz),
-                                              float(d_pos), float(d_neg), _ptr(gt), m, _ptr(out) if cap else None, cap,
-                                              _ptr(count), self._stream())
-            self._check(rc)
-            n, bad = (int(v) for v in count.tolist())
-            if n <= cap:
-                return out[:n], bad
-            cap = n
-
-    def pair_threshold_counts(self, score, thresholds, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None, rank=None):
-        """One streaming pass over a score rectangle (sgpr_pair_threshold_counts): negatives by threshold bucket.
-        thresholds: ascending float32 (<= 8191).  rank = (values, step, above) additionally ranks every negative among
-        all distinct positive values (see include/sgpr.h).  Returns (counts int64 [T+1], skipped, rank_sum or None)."""
-        score, r, m, pose_xz, gt = self._truth(score, row0, pose_xz, gt)
-        thr = self._dev(torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float32)), torch.float32, "thresholds")
-        t = int(thr.numel())
-        out = torch.empty(t + 3, dtype=torch.int64, device=self.device)
-        ws_bytes = self.lib.sgpr_pair_threshold_counts_workspace_bytes(self._h, t)
-        ws = self._ws(ws_bytes)
-        table, at_least, gpt = self._rank_table(rank, t)
-        rc = self.lib.sgpr_pair_threshold_counts(self._h, _ptr(score), r, m, score.stride(0), int(row0), _ptr(pose_xz),
-                                                 float(d_pos), float(d_neg), _ptr(gt), m, _ptr(thr), t, _ptr(table), gpt,
-                                                 _ptr(at_least), _ptr(out), _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        h = out.cpu().numpy()
-        rank_sum = int(h[t + 2].astype(np.uint64)) if rank is not None else None
-        return h[:t + 1].copy(), int(h[t + 1]), rank_sum
-
-    def _rank_table(self, rank, t):
-        """rank = (values, step, above) -> (sgpr_rank_group table, at_least, groups per threshold) on the device"""
-        if rank is None:
-            return None, None, 0
-        vals, step, above = rank
-        vals = np.asarray(vals, dtype=np.float32)
-        above = np.asarray(above, dtype=np.int64)
-        u, step = int(vals.size), int(step)
-        assert above.size == u + 1 and t == -(-u // step) and int(above[0]) < 2 ** 32
-        gpt = -(-step // 8)
-        # values / pair counts of threshold q's bucket = entries q * step .. (q + 1) * step, padded to gpt * 8
-        pad = t * step - u
-        v2 = np.concatenate((vals, np.full(pad, np.inf, dtype=np.float32))).reshape(t, step)
-        m2 = np.concatenate((above[:-1] - above[1:], np.zeros(pad, dtype=np.int64))).reshape(t, step)
-        v3 = np.full((t, gpt * 8), np.inf, dtype=np.float32)
-        m3 = np.zeros((t, gpt * 8), dtype=np.uint32)
-        v3[:, :step] = v2
-        m3[:, :step] = m2
-        ent = np.zeros((t, gpt), dtype=RANK_GROUP)
-        ent["value"] = v3.reshape(t, gpt, 8)
-        ent["pairs"] = m3.reshape(t, gpt, 8)
-        table = torch.from_numpy(ent.view(np.uint8).reshape(-1)).to(self.device)
-        at_least = torch.from_numpy(np.ascontiguousarray(above[:-1][::step])).to(self.device)
-        return table, at_least, gpt
-
-    # ------------------------------------------------------------------ the same consumers without the matrix
-    MAX_POOLED_THRESHOLDS = 2047     # SGPR_SCORE_COUNT_MAX_THRESHOLDS of include/sgpr.h
-
-    def _pooled_truth(self, r, m, row0, pose_xz, gt):
+    def _truth(self, r, m, row0, pose_xz, gt, context=0):
+        """the ground truth of the pair consumers -> (pose_xz f64 [>= max(M, row0 + R), 2], None) or, without poses,
+        (None, gt i8 [R - context, M]) on the device"""
         if pose_xz is not None:
             pose_xz = self._dev(pose_xz, torch.float64, "pose_xz")
             assert pose_xz.dim() == 2 and pose_xz.shape[1] == 2 and pose_xz.shape[0] >= max(m, row0 + r)
             return pose_xz, None
         if gt is not None:
             gt = self._dev(gt, torch.int8, "gt")
-            assert gt.shape == (r, m)
+            assert gt.shape == (max(r - int(context), 0), m)
             return None, gt
         raise ValueError("the pair consumers need poses or explicit labels")
+
+    def _positives(self, fn, head, cap, tail=()):
+        """a positives list fn(*head, out, capacity, count, *tail, stream): one launch when the list fits the first guess
+        (positives are rare: loop closures), a second one sized exactly otherwise -> (scores f32 [n], skipped)"""
+        count = torch.empty(2, dtype=torch.int64, device=self.device)
+        while True:
+            out = torch.empty(cap, dtype=torch.float32, device=self.device)
+            self._check(fn(*head, _ptr(out) if cap else None, cap, _ptr(count), *tail, self._stream()))
+            n, bad = (int(v) for v in count.tolist())
+            if n <= cap:
+                return out[:n], bad
+            cap = n
+
+    def _threshold_counts(self, fn, head, thresholds, rank, workspace_bytes):
+        """a counting pass fn(*head, thresholds, T, rank table, groups per threshold, at_least, out, workspace,
+        workspace_bytes, stream), its workspace sized by workspace_bytes(T) -> (counts int64 [T+1], skipped, rank_sum or
+        None).  rank = (values, step, above) becomes the sgpr_rank_group table and at_least on the device."""
+        thr = self._dev(torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float32)), torch.float32, "thresholds")
+        t = int(thr.numel())
+        out = torch.empty(t + 3, dtype=torch.int64, device=self.device)
+        ws_bytes = workspace_bytes(t)
+        ws = self._ws(ws_bytes)
+        table, at_least, gpt = None, None, 0
+        if rank is not None:
+            vals, step, above = rank
+            vals = np.asarray(vals, dtype=np.float32)
+            above = np.asarray(above, dtype=np.int64)
+            u, step = int(vals.size), int(step)
+            assert above.size == u + 1 and t == -(-u // step) and int(above[0]) < 2 ** 32
+            gpt = -(-step // 8)
+            # values / pair counts of threshold q's bucket = entries q * step .. (q + 1) * step, padded to gpt * 8
+            pad = t * step - u
+            v2 = np.concatenate((vals, np.full(pad, np.inf, dtype=np.float32))).reshape(t, step)
+            m2 = np.concatenate((above[:-1] - above[1:], np.zeros(pad, dtype=np.int64))).reshape(t, step)
+            v3 = np.full((t, gpt * 8), np.inf, dtype=np.float32)
+            m3 = np.zeros((t, gpt * 8), dtype=np.uint32)
+            v3[:, :step] = v2
+            m3[:, :step] = m2
+            ent = np.zeros((t, gpt), dtype=RANK_GROUP)
+            ent["value"] = v3.reshape(t, gpt, 8)
+            ent["pairs"] = m3.reshape(t, gpt, 8)
+            table = torch.from_numpy(ent.view(np.uint8).reshape(-1)).to(self.device)
+            at_least = torch.from_numpy(np.ascontiguousarray(above[:-1][::step])).to(self.device)
+        self._check(fn(*head, _ptr(thr), t, _ptr(table), gpt, _ptr(at_least), _ptr(out), _ptr(ws), ws_bytes,
+                       self._stream()))
+        h = out.cpu().numpy()
+        rank_sum = int(h[t + 2].astype(np.uint64)) if rank is not None else None
+        return h[:t + 1].copy(), int(h[t + 1]), rank_sum
+
+    def pair_positives(self, score, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None):
+        """Scores of the positive pairs of a rectangle that stays on the device (sgpr_pair_positives): float32 device
+        tensor (unordered) and the number of positives skipped for a negative / NaN score."""
+        score, r, m, ld = self._matrix(score)
+        pose_xz, gt = self._truth(r, m, row0, pose_xz, gt)
+        return self._positives(self.lib.sgpr_pair_positives,
+                               (self._h, _ptr(score), r, m, ld, int(row0), _ptr(pose_xz), float(d_pos), float(d_neg),
+                                _ptr(gt), m), min(r * m, 1 << 20))
+
+    def pair_threshold_counts(self, score, thresholds, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None, rank=None):
+        """One streaming pass over a score rectangle (sgpr_pair_threshold_counts): negatives by threshold bucket.
+        thresholds: ascending float32 (<= 8191).  rank = (values, step, above) additionally ranks every negative among
+        all distinct positive values (see include/sgpr.h).  Returns (counts int64 [T+1], skipped, rank_sum or None)."""
+        score, r, m, ld = self._matrix(score)
+        pose_xz, gt = self._truth(r, m, row0, pose_xz, gt)
+        return self._threshold_counts(self.lib.sgpr_pair_threshold_counts,
+                                      (self._h, _ptr(score), r, m, ld, int(row0), _ptr(pose_xz), float(d_pos),
+                                       float(d_neg), _ptr(gt), m), thresholds, rank,
+                                      lambda t: self.lib.sgpr_pair_threshold_counts_workspace_bytes(self._h, t))
+
+    # ------------------------------------------------------------------ the same consumers without the matrix
+    MAX_POOLED_THRESHOLDS = _C["SGPR_SCORE_COUNT_MAX_THRESHOLDS"]
 
     def score_positives_workspace_bytes(self, r, m):
         return int(self.lib.sgpr_score_positives_workspace_bytes(self._h, int(r), int(m)))
@@ -990,21 +768,12 @@ class Engine:
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
-        pose_xz, gt = self._pooled_truth(r, m, row0, pose_xz, gt)
+        pose_xz, gt = self._truth(r, m, row0, pose_xz, gt)
         ws_bytes = self.score_positives_workspace_bytes(r, m)
         ws = self._ws(ws_bytes)
-        count = torch.empty(2, dtype=torch.int64, device=self.device)
-        cap = min(r * m, 1 << 20)
-        while True:
-            out = torch.empty(cap, dtype=torch.float32, device=self.device)
-            rc = self.lib.sgpr_score_positives(self._h, _ptr(rows), r, _ptr(cols), m, int(row0), _ptr(pose_xz),
-                                               float(d_pos), float(d_neg), _ptr(gt), m, _ptr(out) if cap else None, cap,
-                                               _ptr(count), _ptr(ws), ws_bytes, self._stream())
-            self._check(rc)
-            n, bad = (int(v) for v in count.tolist())
-            if n <= cap:
-                return out[:n], bad
-            cap = n
+        return self._positives(self.lib.sgpr_score_positives,
+                               (self._h, _ptr(rows), r, _ptr(cols), m, int(row0), _ptr(pose_xz), float(d_pos),
+                                float(d_neg), _ptr(gt), m), min(r * m, 1 << 20), (_ptr(ws), ws_bytes))
 
     def score_threshold_counts(self, pooled_rows, pooled_cols, thresholds, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0,
                                gt=None, rank=None):
@@ -1014,30 +783,22 @@ class Engine:
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
-        pose_xz, gt = self._pooled_truth(r, m, row0, pose_xz, gt)
-        thr = self._dev(torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float32)), torch.float32, "thresholds")
-        t = int(thr.numel())
-        out = torch.empty(t + 3, dtype=torch.int64, device=self.device)
-        ws_bytes = self.score_threshold_counts_workspace_bytes(r, m, t)
-        ws = self._ws(ws_bytes)
-        table, at_least, gpt = self._rank_table(rank, t)
-        rc = self.lib.sgpr_score_threshold_counts(self._h, _ptr(rows), r, _ptr(cols), m, int(row0), _ptr(pose_xz),
-                                                  float(d_pos), float(d_neg), _ptr(gt), m, _ptr(thr), t, _ptr(table), gpt,
-                                                  _ptr(at_least), _ptr(out), _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        h = out.cpu().numpy()
-        rank_sum = int(h[t + 2].astype(np.uint64)) if rank is not None else None
-        return h[:t + 1].copy(), int(h[t + 1]), rank_sum
+        pose_xz, gt = self._truth(r, m, row0, pose_xz, gt)
+        return self._threshold_counts(self.lib.sgpr_score_threshold_counts,
+                                      (self._h, _ptr(rows), r, _ptr(cols), m, int(row0), _ptr(pose_xz), float(d_pos),
+                                       float(d_neg), _ptr(gt), m), thresholds, rank,
+                                      lambda t: self.score_threshold_counts_workspace_bytes(r, m, t))
 
     def f1_max(self, score, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None):
         """F1-max of a score rectangle in ONE engine call (sgpr_f1_max): every step on the device, one 64-byte copy
         at the end.  Returns the raw result vector (numpy float64 [8], see include/sgpr.h): [0] F1-max, [1] status (0 ok,
         1 = use the multi-call path, 2 = negative / NaN scores), [2] positives, [3] negatives, [4] passes."""
-        score, r, m, pose_xz, gt = self._truth(score, row0, pose_xz, gt)
+        score, r, m, ld = self._matrix(score)
+        pose_xz, gt = self._truth(r, m, row0, pose_xz, gt)
         res = torch.empty(8, dtype=torch.float64, device=self.device)
         ws_bytes = self.lib.sgpr_f1_max_workspace_bytes(self._h, r, m)
         ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_f1_max(self._h, _ptr(score), r, m, score.stride(0), int(row0), _ptr(pose_xz), float(d_pos),
+        rc = self.lib.sgpr_f1_max(self._h, _ptr(score), r, m, ld, int(row0), _ptr(pose_xz), float(d_pos),
                                   float(d_neg), _ptr(gt), m, _ptr(res), _ptr(ws), ws_bytes, self._stream())
         self._check(rc)
         # (the 64 bytes land in a pinned buffer of this engine and thread: a pageable copy is staged by the runtime, and a
@@ -1049,22 +810,7 @@ class Engine:
         torch.cuda.current_stream(self.device).synchronize()
         return host.numpy().copy()
 
-    def topk_rows(self, score, k=1, row0=0, window=-1, causal=False, row_self=None):
-        """Best k columns per row outside |col - (row0 + row)| <= window -> (values f32 [R,k], indices i32 [R,k]).
-        k in {1, 4, 8, 16} without causal / row_self: sgpr_topk_rows; any other k in 1..4096 (or the causal rule, or a
-        row_self table, as score_topk takes them): topk_rows_large."""
-        if int(k) in (1, 4, 8, 16) and not causal and row_self is None:
-            score = self._dev(score, torch.float32, "score")
-            r, m = score.shape
-            assert score.stride(1) == 1
-            vals = torch.empty(r, k, dtype=torch.float32, device=self.device)
-            idx = torch.empty(r, k, dtype=torch.int32, device=self.device)
-            rc = self.lib.sgpr_topk_rows(self._h, _ptr(score), r, m, score.stride(0), int(row0), int(window), int(k),
-                                         _ptr(vals), _ptr(idx), self._stream())
-            self._check(rc)
-            return vals, idx
-        return self.topk_rows_large(score, k=k, row0=row0, window=window, causal=causal, row_self=row_self)
-
+    # ------------------------------------------------------------------ ranked lists
     def _row_self(self, row_self, r):
         if row_self is None:
             return None
@@ -1073,35 +819,62 @@ class Engine:
             raise ValueError("row_self must be [%d], got %s" % (r, tuple(rs.shape)))
         return rs
 
+    def _flags(self, causal=False, reverse=_UNSET, positives=_UNSET):
+        """The flags word of an entry point and of its *_workspace_bytes twin.  causal: TOPK_CAUSAL.  reverse (the
+        sequence family alone passes it): False (forward diagonals c - r = const), True (reverse, c + r = const) or
+        "both" (the larger).  positives (the mining calls alone pass it): MINE_POSITIVES or MINE_NEGATIVES."""
+        flags = self.TOPK_CAUSAL if causal else 0
+        if isinstance(reverse, str):
+            if reverse != "both":
+                raise ValueError('reverse must be False, True or "both", got %r' % (reverse,))
+            flags |= self.SEQ_FORWARD | self.SEQ_REVERSE
+        elif reverse is not _UNSET:
+            flags |= self.SEQ_REVERSE if reverse else self.SEQ_FORWARD
+        if positives is not _UNSET:
+            flags |= self.MINE_POSITIVES if positives else self.MINE_NEGATIVES
+        return flags
+
+    def _ranked(self, fn, head, ro, k, ws_bytes, codes=False):
+        """a ranked-list entry point fn(*head, k, values, indices, [codes,] workspace, workspace_bytes, stream) ->
+        (values f32 [ro, k], indices i32 [ro, k]) and, codes, the direction / path codes u8 [ro, k]"""
+        outs = [torch.empty(ro, int(k), dtype=dt, device=self.device)
+                for dt in (torch.float32, torch.int32, torch.uint8)[:3 if codes else 2]]
+        ws = self._ws(ws_bytes)
+        self._check(fn(*head, int(k), *[_ptr(t) for t in outs], _ptr(ws), ws_bytes, self._stream()))
+        return tuple(outs)
+
+    def topk_rows(self, score, k=1, row0=0, window=-1, causal=False, row_self=None):
+        """Best k columns per row outside |col - (row0 + row)| <= window -> (values f32 [R,k], indices i32 [R,k]).
+        k in {1, 4, 8, 16} without causal / row_self: sgpr_topk_rows; any other k in 1..4096 (or the causal rule, or a
+        row_self table, as score_topk takes them): topk_rows_large."""
+        if int(k) in (1, 4, 8, 16) and not causal and row_self is None:
+            score, r, m, ld = self._matrix(score)
+            vals = torch.empty(r, k, dtype=torch.float32, device=self.device)
+            idx = torch.empty(r, k, dtype=torch.int32, device=self.device)
+            rc = self.lib.sgpr_topk_rows(self._h, _ptr(score), r, m, ld, int(row0), int(window), int(k),
+                                         _ptr(vals), _ptr(idx), self._stream())
+            self._check(rc)
+            return vals, idx
+        return self.topk_rows_large(score, k=k, row0=row0, window=window, causal=causal, row_self=row_self)
+
     def topk_rows_large_workspace_bytes(self, r, m, k, causal=False):
-        return int(self.lib.sgpr_topk_rows_large_workspace_bytes(self._h, int(r), int(m), int(k),
-                                                                 self.TOPK_CAUSAL if causal else 0))
+        return int(self.lib.sgpr_topk_rows_large_workspace_bytes(self._h, int(r), int(m), int(k), self._flags(causal)))
 
     def topk_rows_large(self, score, k=1, row0=0, window=-1, causal=False, row_self=None):
         """sgpr_topk_rows_large: the best k (1..4096) eligible columns per row of a resident matrix (score_topk's rules:
         window, causal, row_self) -> (values f32 [R,k], indices i32 [R,k]); (-inf, -1) past the last eligible column."""
-        score = self._dev(score, torch.float32, "score")
-        r, m = score.shape
-        if score.stride(1) != 1:
-            score = score.contiguous()
+        score, r, m, ld = self._matrix(score)
         rs = self._row_self(row_self, r)
-        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
-        flags = self.TOPK_CAUSAL if causal else 0
+        flags = self._flags(causal)
         ws_bytes = self.lib.sgpr_topk_rows_large_workspace_bytes(self._h, r, m, int(k), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_topk_rows_large(self._h, _ptr(score), r, m, max(score.stride(0), m), _ptr(rs), int(row0),
-                                           int(window), flags, int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes,
-                                           self._stream())
-        self._check(rc)
-        return vals, idx
+        return self._ranked(self.lib.sgpr_topk_rows_large,
+                            (self._h, _ptr(score), r, m, ld, _ptr(rs), int(row0), int(window), flags), r, k, ws_bytes)
 
-    TOPK_CAUSAL = 1     # SGPR_TOPK_CAUSAL of include/sgpr.h
-    TOPK_LARGE_MAX = 4096   # SGPR_TOPK_LARGE_MAX
+    TOPK_CAUSAL = _C["SGPR_TOPK_CAUSAL"]
+    TOPK_LARGE_MAX = _C["SGPR_TOPK_LARGE_MAX"]
 
     def score_topk_large_workspace_bytes(self, r, m, k, causal=False):
-        return int(self.lib.sgpr_score_topk_large_workspace_bytes(self._h, int(r), int(m), int(k),
-                                                                  self.TOPK_CAUSAL if causal else 0))
+        return int(self.lib.sgpr_score_topk_large_workspace_bytes(self._h, int(r), int(m), int(k), self._flags(causal)))
 
     def score_topk_large(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None):
         """sgpr_score_topk_large: score_topk's lists for k in 1..4096, the rectangle scored in row blocks of at most
@@ -1110,27 +883,36 @@ class Engine:
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
-        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
-        flags = self.TOPK_CAUSAL if causal else 0
+        flags = self._flags(causal)
         ws_bytes = self.lib.sgpr_score_topk_large_workspace_bytes(self._h, r, m, int(k), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_score_topk_large(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window),
-                                            flags, int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        return vals, idx
+        return self._ranked(self.lib.sgpr_score_topk_large,
+                            (self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window), flags), r, k,
+                            ws_bytes)
 
-    SEQ_FORWARD = 2     # SGPR_SEQ_FORWARD of include/sgpr.h
-    SEQ_REVERSE = 4     # SGPR_SEQ_REVERSE
-    SEQ_MAX_LEN = 32    # SGPR_SEQ_MAX_LEN
+    SEQ_FORWARD = _C["SGPR_SEQ_FORWARD"]
+    SEQ_REVERSE = _C["SGPR_SEQ_REVERSE"]
+    SEQ_MAX_LEN = _C["SGPR_SEQ_MAX_LEN"]
 
-    def _seq_flags(self, reverse):
-        """reverse: False (forward diagonals c - r = const), True (reverse, c + r = const) or "both" (the larger)"""
-        if isinstance(reverse, str):
-            if reverse != "both":
-                raise ValueError('reverse must be False, True or "both", got %r' % (reverse,))
-            return self.SEQ_FORWARD | self.SEQ_REVERSE
-        return self.SEQ_REVERSE if reverse else self.SEQ_FORWARD
+    def _filter_outputs(self, ro, m, out, second=None, second_name=None, want_second=False):
+        """The outputs of a filter -> (out f32 [ro, m], second u8 [ro, m] or None, their common row stride).  Given
+        tensors are checked - this device, dtype, shape, unit column stride, one row stride >= m shared by both - and
+        missing ones allocated (the second one only when wanted)."""
+        if out is None:
+            out = torch.empty(ro, m, dtype=torch.float32, device=self.device)
+        if second is None and want_second:
+            second = torch.empty(ro, m, dtype=torch.uint8, device=self.device)
+        ldo = m
+        for t, dt, name in ((out, torch.float32, "out"), (second, torch.uint8, second_name)):
+            if t is None:
+                continue
+            if (t.device != self.device or t.dtype != dt or tuple(t.shape) != (ro, m) or (m > 1 and t.stride(1) != 1)
+                    or (ro > 1 and t.stride(0) < m)):
+                raise ValueError("%s must be a %s device tensor [%d, %d] with unit column stride" % (name, dt, ro, m))
+            if ro > 1:
+                ldo = max(ldo, t.stride(0))
+        if ro > 1 and second is not None and out.stride(0) != second.stride(0):
+            raise ValueError("out and %s must share one row stride" % second_name)
+        return out, second, ldo
 
     def seq_filter(self, score, seq_len, context=0, reverse=False, want_dir=False, out=None, out_dir=None):
         """sgpr_seq_filter: the mean of a resident matrix along the diagonal of up to seq_len entries that ends in
@@ -1138,40 +920,16 @@ class Engine:
         the direction taken, u8: 0 forward, 1 reverse).  fp32 sums in a fixed order: bit-reproducible (include/sgpr.h).
         A row-strided view (unit column stride) is read in place.  out / out_dir: device tensors [R - context, M] to
         write into, with one common row stride >= M and unit column stride (they must not overlap score)."""
-        if not isinstance(score, torch.Tensor):
-            score = torch.as_tensor(score)
-        if score.dim() != 2:
-            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
-        if score.device != self.device or score.dtype != torch.float32:
-            score = score.to(device=self.device, dtype=torch.float32)
-        r, m = score.shape
-        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
-            score = score.contiguous()
-        ro = max(r - int(context), 0)
-        if out is None:
-            out = torch.empty(ro, m, dtype=torch.float32, device=self.device)
-        if out_dir is None and want_dir:
-            out_dir = torch.empty(ro, m, dtype=torch.uint8, device=self.device)
-        ldo = m
-        for t, dt, name in ((out, torch.float32, "out"), (out_dir, torch.uint8, "out_dir")):
-            if t is None:
-                continue
-            if t.device != self.device or t.dtype != dt or tuple(t.shape) != (ro, m) or (m > 1 and t.stride(1) != 1):
-                raise ValueError("%s must be a %s device tensor [%d, %d] with unit column stride" % (name, dt, ro, m))
-            if ro > 1:
-                ldo = max(ldo, t.stride(0))
-        if ro > 1 and out_dir is not None and max(out.stride(0), m) != max(out_dir.stride(0), m):
-            raise ValueError("out and out_dir must share one row stride")
-        rc = self.lib.sgpr_seq_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m, int(context),
-                                      int(seq_len), self._seq_flags(reverse), _ptr(out), ldo, _ptr(out_dir),
-                                      self._stream())
+        score, r, m, ld = self._matrix(score, rank2=True)
+        out, out_dir, ldo = self._filter_outputs(max(r - int(context), 0), m, out, out_dir, "out_dir", want_dir)
+        rc = self.lib.sgpr_seq_filter(self._h, _ptr(score), r, m, ld, int(context), int(seq_len),
+                                      self._flags(reverse=reverse), _ptr(out), ldo, _ptr(out_dir), self._stream())
         self._check(rc)
-        return (out, out_dir) if (want_dir or out_dir is not None) else out
+        return out if out_dir is None else (out, out_dir)
 
     def score_seq_topk_workspace_bytes(self, r, m, seq_len, k=1, causal=False, context=0, reverse="both"):
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
         return int(self.lib.sgpr_score_seq_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
-                                                                int(k), flags))
+                                                                int(k), self._flags(causal, reverse)))
 
     def score_seq_topk(self, pooled_rows, pooled_cols, seq_len, k=1, window=-1, row0=0, causal=False, row_self=None,
                        context=0, reverse="both"):
@@ -1183,18 +941,11 @@ class Engine:
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
-        ro = max(r - int(context), 0)
-        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
-        dirs = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         ws_bytes = self.lib.sgpr_score_seq_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len), int(k), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_score_seq_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
-                                          int(window), flags, int(seq_len), int(k), _ptr(vals), _ptr(idx), _ptr(dirs),
-                                          _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        return vals, idx, dirs
+        return self._ranked(self.lib.sgpr_score_seq_topk,
+                            (self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0), int(window), flags,
+                             int(seq_len)), max(r - int(context), 0), k, ws_bytes, codes=True)
 
     SEQ_MAX_PATHS = SEQ_MAX_PATHS
     SEQ_PATH_MAX_OFFSET = SEQ_PATH_MAX_OFFSET
@@ -1203,42 +954,20 @@ class Engine:
         """sgpr_seq_path_filter: seq_filter maximised over a set of paths (int32 [P, seq_len], see seq_paths) -> Q f32
         [R - context, M] (and, want_code, the winner's code u8: direction bit | path << 1).  The single path
         off[d] = d gives seq_filter's bits.  out / out_code as seq_filter's out / out_dir."""
-        if not isinstance(score, torch.Tensor):
-            score = torch.as_tensor(score)
-        if score.dim() != 2:
-            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
-        if score.device != self.device or score.dtype != torch.float32:
-            score = score.to(device=self.device, dtype=torch.float32)
+        score, r, m, ld = self._matrix(score, rank2=True)
         table = _path_table(paths, seq_len)
-        r, m = score.shape
-        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
-            score = score.contiguous()
-        ro = max(r - int(context), 0)
-        if out is None:
-            out = torch.empty(ro, m, dtype=torch.float32, device=self.device)
-        if out_code is None and want_code:
-            out_code = torch.empty(ro, m, dtype=torch.uint8, device=self.device)
-        ldo = m
-        for t, dt, name in ((out, torch.float32, "out"), (out_code, torch.uint8, "out_code")):
-            if t is None:
-                continue
-            if t.device != self.device or t.dtype != dt or tuple(t.shape) != (ro, m) or (m > 1 and t.stride(1) != 1):
-                raise ValueError("%s must be a %s device tensor [%d, %d] with unit column stride" % (name, dt, ro, m))
-            if ro > 1:
-                ldo = max(ldo, t.stride(0))
-        if ro > 1 and out_code is not None and max(out.stride(0), m) != max(out_code.stride(0), m):
-            raise ValueError("out and out_code must share one row stride")
-        rc = self.lib.sgpr_seq_path_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m,
-                                           int(context), int(seq_len), self._seq_flags(reverse), table.ctypes.data,
-                                           table.shape[0], _ptr(out), ldo, _ptr(out_code), self._stream())
+        out, out_code, ldo = self._filter_outputs(max(r - int(context), 0), m, out, out_code, "out_code", want_code)
+        rc = self.lib.sgpr_seq_path_filter(self._h, _ptr(score), r, m, ld, int(context), int(seq_len),
+                                           self._flags(reverse=reverse), table.ctypes.data, table.shape[0], _ptr(out),
+                                           ldo, _ptr(out_code), self._stream())
         self._check(rc)
-        return (out, out_code) if (want_code or out_code is not None) else out
+        return out if out_code is None else (out, out_code)
 
     def score_path_topk_workspace_bytes(self, r, m, seq_len, n_paths, k=1, radius=0, causal=False, context=0,
                                         reverse="both"):
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
         return int(self.lib.sgpr_score_path_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
-                                                                 int(n_paths), int(k), int(radius), flags))
+                                                                 int(n_paths), int(k), int(radius),
+                                                                 self._flags(causal, reverse)))
 
     def score_path_topk(self, pooled_rows, pooled_cols, seq_len, paths, k=1, radius=0, window=-1, row0=0, causal=False,
                         row_self=None, context=0, reverse="both"):
@@ -1250,22 +979,25 @@ class Engine:
         table = _path_table(paths, seq_len)
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
-        ro = max(r - int(context), 0)
-        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
-        codes = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         ws_bytes = self.lib.sgpr_score_path_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len),
                                                                  table.shape[0], int(k), int(radius), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_score_path_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
-                                           int(window), flags, int(seq_len), table.ctypes.data, table.shape[0],
-                                           int(radius), int(k), _ptr(vals), _ptr(idx), _ptr(codes), _ptr(ws), ws_bytes,
-                                           self._stream())
-        self._check(rc)
-        return vals, idx, codes
+        return self._ranked(self.lib.sgpr_score_path_topk,
+                            (self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0), int(window), flags,
+                             int(seq_len), table.ctypes.data, table.shape[0], int(radius)),
+                            max(r - int(context), 0), k, ws_bytes, codes=True)
 
     SESSION_MAX = SESSION_MAX
+
+    @staticmethod
+    def _session_tables(paths, seq_len, row_sessions, col_sessions):
+        """(path table pointer, n_paths, row table pointer, n, column table pointer, n) and the arrays that own them"""
+        table = None if paths is None else _path_table(paths, seq_len)
+        rt, ct = _session_table(row_sessions), _session_table(col_sessions)
+        args = []
+        for t in (table, rt, ct):
+            args += [None, 0] if t is None else [t.ctypes.data, t.shape[0]]
+        return args, (table, rt, ct)
 
     def session_filter(self, score, seq_len, paths=None, row_sessions=None, col_sessions=None, window=-1, row0=0,
                        row_self=None, context=0, reverse=False, want_code=False, out=None, out_code=None):
@@ -1274,50 +1006,21 @@ class Engine:
         edges of the end point's own row and column session; with window >= 0 column c is excluded (-inf, code 0) for
         row r iff it lies in the session of self_r (row_self[r] or row0 + r) and |c - self_r| <= window.  paths None: the
         unit diagonal.  -> Q f32 [R - context, M] (and, want_code, the code u8).  out / out_code as seq_filter's."""
-        if not isinstance(score, torch.Tensor):
-            score = torch.as_tensor(score)
-        if score.dim() != 2:
-            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
-        if score.device != self.device or score.dtype != torch.float32:
-            score = score.to(device=self.device, dtype=torch.float32)
-        table = None if paths is None else _path_table(paths, seq_len)
-        rt, ct = _session_table(row_sessions), _session_table(col_sessions)
-        r, m = score.shape
-        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
-            score = score.contiguous()
+        score, r, m, ld = self._matrix(score, rank2=True)
+        tables, keep = self._session_tables(paths, seq_len, row_sessions, col_sessions)
         rs = self._row_self(row_self, r)
-        ro = max(r - int(context), 0)
-        if out is None:
-            out = torch.empty(ro, m, dtype=torch.float32, device=self.device)
-        if out_code is None and want_code:
-            out_code = torch.empty(ro, m, dtype=torch.uint8, device=self.device)
-        ldo = m
-        for t, dt, name in ((out, torch.float32, "out"), (out_code, torch.uint8, "out_code")):
-            if t is None:
-                continue
-            if t.device != self.device or t.dtype != dt or tuple(t.shape) != (ro, m) or (m > 1 and t.stride(1) != 1):
-                raise ValueError("%s must be a %s device tensor [%d, %d] with unit column stride" % (name, dt, ro, m))
-            if ro > 1:
-                ldo = max(ldo, t.stride(0))
-        if ro > 1 and out_code is not None and max(out.stride(0), m) != max(out_code.stride(0), m):
-            raise ValueError("out and out_code must share one row stride")
-        rc = self.lib.sgpr_session_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m,
-                                          int(context), int(seq_len), self._seq_flags(reverse),
-                                          None if table is None else table.ctypes.data,
-                                          0 if table is None else table.shape[0],
-                                          None if rt is None else rt.ctypes.data, 0 if rt is None else rt.shape[0],
-                                          None if ct is None else ct.ctypes.data, 0 if ct is None else ct.shape[0],
-                                          _ptr(rs), int(row0), int(window), _ptr(out), ldo, _ptr(out_code),
-                                          self._stream())
+        out, out_code, ldo = self._filter_outputs(max(r - int(context), 0), m, out, out_code, "out_code", want_code)
+        rc = self.lib.sgpr_session_filter(self._h, _ptr(score), r, m, ld, int(context), int(seq_len),
+                                          self._flags(reverse=reverse), *tables, _ptr(rs), int(row0), int(window),
+                                          _ptr(out), ldo, _ptr(out_code), self._stream())
         self._check(rc)
-        return (out, out_code) if (want_code or out_code is not None) else out
+        return out if out_code is None else (out, out_code)
 
     def score_session_topk_workspace_bytes(self, r, m, seq_len, n_paths=0, k=1, causal=False, context=0, reverse="both",
                                            n_row_sessions=0, n_col_sessions=0):
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
         return int(self.lib.sgpr_score_session_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
-                                                                    int(n_paths), int(k), flags, int(n_row_sessions),
-                                                                    int(n_col_sessions)))
+                                                                    int(n_paths), int(k), self._flags(causal, reverse),
+                                                                    int(n_row_sessions), int(n_col_sessions)))
 
     def score_session_topk(self, pooled_rows, pooled_cols, seq_len, paths=None, row_sessions=None, col_sessions=None, k=1,
                            window=-1, row0=0, causal=False, row_self=None, context=0, reverse="both"):
@@ -1326,31 +1029,18 @@ class Engine:
         indices i32, codes u8).  row_sessions counts over all R rows, the context rows included."""
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
-        table = None if paths is None else _path_table(paths, seq_len)
-        rt, ct = _session_table(row_sessions), _session_table(col_sessions)
+        tables, keep = self._session_tables(paths, seq_len, row_sessions, col_sessions)
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
-        ro = max(r - int(context), 0)
-        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
-        codes = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
-        n_paths = 0 if table is None else table.shape[0]
-        n_row, n_col = (0 if rt is None else rt.shape[0]), (0 if ct is None else ct.shape[0])
-        ws_bytes = self.lib.sgpr_score_session_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len), n_paths,
-                                                                    int(k), flags, n_row, n_col)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_score_session_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
-                                              int(window), flags, int(seq_len),
-                                              None if table is None else table.ctypes.data, n_paths,
-                                              None if rt is None else rt.ctypes.data, n_row,
-                                              None if ct is None else ct.ctypes.data, n_col, int(k), _ptr(vals),
-                                              _ptr(idx), _ptr(codes), _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        return vals, idx, codes
+        flags = self._flags(causal, reverse)
+        ws_bytes = self.lib.sgpr_score_session_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len), tables[1],
+                                                                    int(k), flags, tables[3], tables[5])
+        return self._ranked(self.lib.sgpr_score_session_topk,
+                            (self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0), int(window), flags,
+                             int(seq_len), *tables), max(r - int(context), 0), k, ws_bytes, codes=True)
 
-    PEAK_MAX_RADIUS = 1024  # SGPR_PEAK_MAX_RADIUS of include/sgpr.h
-    PEAK_STRIP = 1024        # SGPR_PEAK_STRIP: columns a workgroup of the peak filter owns
+    PEAK_MAX_RADIUS = _C["SGPR_PEAK_MAX_RADIUS"]
+    PEAK_STRIP = _C["SGPR_PEAK_STRIP"]           # columns a workgroup of the peak filter owns
 
     def peak_filter(self, score, radius, window=-1, row0=0, causal=False, row_self=None, out=None):
         """sgpr_peak_filter: a resident matrix [R, M] -> P f32 [R, M]: the score at a PEAK - a qualifying column
@@ -1358,31 +1048,17 @@ class Engine:
         descending, column ascending), among the qualifying columns at most `radius` away - and -inf elsewhere.
         A row-strided view (unit column stride) is read in place.  out: a device tensor [R, M] to write into (row
         stride >= M, unit column stride; it must not overlap score)."""
-        if not isinstance(score, torch.Tensor):
-            score = torch.as_tensor(score)
-        if score.dim() != 2:
-            raise ValueError("score must be [R, M], got %s" % (tuple(score.shape),))
-        if score.device != self.device or score.dtype != torch.float32:
-            score = score.to(device=self.device, dtype=torch.float32)
-        r, m = score.shape
-        if r > 1 and m and (score.stride(1) != 1 or score.stride(0) < m):
-            score = score.contiguous()
+        score, r, m, ld = self._matrix(score, rank2=True)
         rs = self._row_self(row_self, r)
-        if out is None:
-            out = torch.empty(r, m, dtype=torch.float32, device=self.device)
-        elif (out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (r, m)
-              or (m > 1 and out.stride(1) != 1) or (r > 1 and out.stride(0) < m)):
-            raise ValueError("out must be a float32 device tensor [%d, %d] with unit column stride" % (r, m))
-        rc = self.lib.sgpr_peak_filter(self._h, _ptr(score), r, m, max(score.stride(0), m) if r > 1 else m, _ptr(rs),
-                                       int(row0), int(window), self.TOPK_CAUSAL if causal else 0, int(radius),
-                                       _ptr(out), max(out.stride(0), m) if r > 1 else m, self._stream())
+        out, _, ldo = self._filter_outputs(r, m, out)
+        rc = self.lib.sgpr_peak_filter(self._h, _ptr(score), r, m, ld, _ptr(rs), int(row0), int(window),
+                                       self._flags(causal), int(radius), _ptr(out), ldo, self._stream())
         self._check(rc)
         return out
 
     def score_peak_topk_workspace_bytes(self, r, m, radius, seq_len=1, k=1, causal=False, context=0, reverse=False):
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
         return int(self.lib.sgpr_score_peak_topk_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
-                                                                 int(k), int(radius), flags))
+                                                                 int(k), int(radius), self._flags(causal, reverse)))
 
     def score_peak_topk(self, pooled_rows, pooled_cols, radius, seq_len=1, k=1, window=-1, row0=0, causal=False,
                         row_self=None, context=0, reverse=False):
@@ -1395,23 +1071,15 @@ class Engine:
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
-        ro = max(r - int(context), 0)
-        vals = torch.empty(ro, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(ro, int(k), dtype=torch.int32, device=self.device)
-        dirs = torch.empty(ro, int(k), dtype=torch.uint8, device=self.device)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         ws_bytes = self.lib.sgpr_score_peak_topk_workspace_bytes(self._h, r, m, int(context), int(seq_len), int(k),
                                                                  int(radius), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_score_peak_topk(self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0),
-                                           int(window), flags, int(seq_len), int(radius), int(k), _ptr(vals),
-                                           _ptr(idx), _ptr(dirs), _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        return vals, idx, dirs
+        return self._ranked(self.lib.sgpr_score_peak_topk,
+                            (self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0), int(window), flags,
+                             int(seq_len), int(radius)), max(r - int(context), 0), k, ws_bytes, codes=True)
 
     def score_topk_workspace_bytes(self, r, m, k=1, causal=False):
-        return int(self.lib.sgpr_score_topk_workspace_bytes(self._h, int(r), int(m), int(k),
-                                                            self.TOPK_CAUSAL if causal else 0))
+        return int(self.lib.sgpr_score_topk_workspace_bytes(self._h, int(r), int(m), int(k), self._flags(causal)))
 
     def score_topk(self, pooled_rows, pooled_cols, k=1, window=-1, row0=0, causal=False, row_self=None):
         """Best k columns per row of the rectangle pooled_rows x pooled_cols without forming it (sgpr_score_topk):
@@ -1424,26 +1092,15 @@ class Engine:
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
-        rs = None
-        if row_self is not None:
-            rs = self._dev(row_self, torch.int32, "row_self")
-            if rs.shape != (r,):
-                raise ValueError("row_self must be [%d], got %s" % (r, tuple(rs.shape)))
-        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
-        flags = self.TOPK_CAUSAL if causal else 0
+        rs = self._row_self(row_self, r)
+        flags = self._flags(causal)
         ws_bytes = self.lib.sgpr_score_topk_workspace_bytes(self._h, r, m, int(k), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_score_topk(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window), flags,
-                                      int(k), _ptr(vals), _ptr(idx), _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        return vals, idx
+        return self._ranked(self.lib.sgpr_score_topk,
+                            (self._h, _ptr(rows), r, _ptr(cols), m, _ptr(rs), int(row0), int(window), flags), r, k,
+                            ws_bytes)
 
-    MINE_NEGATIVES = 2  # SGPR_MINE_NEGATIVES of include/sgpr.h
-    MINE_POSITIVES = 4  # SGPR_MINE_POSITIVES
-
-    def _mine_flags(self, positives, causal):
-        return (self.MINE_POSITIVES if positives else self.MINE_NEGATIVES) | (self.TOPK_CAUSAL if causal else 0)
+    MINE_NEGATIVES = _C["SGPR_MINE_NEGATIVES"]
+    MINE_POSITIVES = _C["SGPR_MINE_POSITIVES"]
 
     def _mine_poses(self, col_pose, row_pose, r, m):
         """[.,12] KITTI or [.,2] planar poses -> float64 (x, z) device tensors ([m,2] columns, [r,2] rows or None)"""
@@ -1459,7 +1116,7 @@ class Engine:
 
     def score_mine_workspace_bytes(self, r, m, k=1, positives=False, causal=False):
         return int(self.lib.sgpr_score_mine_workspace_bytes(self._h, int(r), int(m), int(k),
-                                                            self._mine_flags(positives, causal)))
+                                                            self._flags(causal, positives=positives)))
 
     def score_mine(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
@@ -1475,41 +1132,27 @@ class Engine:
         r, m = rows.shape[0], cols.shape[0]
         cp, rp = self._mine_poses(col_pose, row_pose, r, m)
         rs = self._row_self(row_self, r)
-        flags = self._mine_flags(positives, causal)
-        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
+        flags = self._flags(causal, positives=positives)
         ws_bytes = self.lib.sgpr_score_mine_workspace_bytes(self._h, r, m, int(k), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_score_mine(self._h, _ptr(rows), r, _ptr(cols), m, _ptr(cp), _ptr(rp), _ptr(rs), int(row0),
-                                      int(window), flags, float(d_pos), float(d_neg), int(k), _ptr(vals), _ptr(idx),
-                                      _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        return vals, idx
+        return self._ranked(self.lib.sgpr_score_mine,
+                            (self._h, _ptr(rows), r, _ptr(cols), m, _ptr(cp), _ptr(rp), _ptr(rs), int(row0), int(window),
+                             flags, float(d_pos), float(d_neg)), r, k, ws_bytes)
 
     def mine_rows(self, score, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1, row0=0, causal=False,
                   row_self=None, row_pose=None):
         """score_mine's selection on a resident matrix score [R, M] (sgpr_mine_rows; any row stride >= M with unit
         column stride is read in place) -> (values f32 [R,k], indices i32 [R,k])."""
-        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
-                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
-            score = self._dev(score, torch.float32, "score")
-        r, m = score.shape
-        ld = max(score.stride(0), m)
+        score, r, m, ld = self._matrix(score)
         cp, rp = self._mine_poses(col_pose, row_pose, r, m)
         rs = self._row_self(row_self, r)
-        flags = self._mine_flags(positives, causal)
-        vals = torch.empty(r, int(k), dtype=torch.float32, device=self.device)
-        idx = torch.empty(r, int(k), dtype=torch.int32, device=self.device)
+        flags = self._flags(causal, positives=positives)
         ws_bytes = self.lib.sgpr_mine_rows_workspace_bytes(self._h, r, m, int(k), flags)
-        ws = self._ws(ws_bytes)
-        rc = self.lib.sgpr_mine_rows(self._h, _ptr(score), r, m, ld, _ptr(cp), _ptr(rp), _ptr(rs), int(row0),
-                                     int(window), flags, float(d_pos), float(d_neg), int(k), _ptr(vals), _ptr(idx),
-                                     _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        return vals, idx
+        return self._ranked(self.lib.sgpr_mine_rows,
+                            (self._h, _ptr(score), r, m, ld, _ptr(cp), _ptr(rp), _ptr(rs), int(row0), int(window), flags,
+                             float(d_pos), float(d_neg)), r, k, ws_bytes)
 
     def score_above_workspace_bytes(self, r, m, causal=False):
-        return int(self.lib.sgpr_score_above_workspace_bytes(self._h, int(r), int(m), self.TOPK_CAUSAL if causal else 0))
+        return int(self.lib.sgpr_score_above_workspace_bytes(self._h, int(r), int(m), self._flags(causal)))
 
     def rows_above_workspace_bytes(self, r, m):
         return int(self.lib.sgpr_rows_above_workspace_bytes(self._h, int(r), int(m)))
@@ -1541,14 +1184,6 @@ class Engine:
             out_r, out_c, out_v, row_ptr, count = run(n)
         return out_r[:n], out_c[:n], out_v[:n], row_ptr
 
-    def _row_self(self, row_self, r):
-        if row_self is None:
-            return None
-        rs = self._dev(row_self, torch.int32, "row_self")
-        if rs.shape != (r,):
-            raise ValueError("row_self must be [%d], got %s" % (r, tuple(rs.shape)))
-        return rs
-
     def score_above(self, pooled_rows, pooled_cols, threshold, window=-1, row0=0, causal=False, row_self=None,
                     capacity=None):
         """Every pair (r, c) of the rectangle pooled_rows x pooled_cols with score >= threshold, without forming the
@@ -1566,7 +1201,7 @@ class Engine:
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
-        flags = self.TOPK_CAUSAL if causal else 0
+        flags = self._flags(causal)
         ws_bytes = self.lib.sgpr_score_above_workspace_bytes(self._h, r, m, flags)
         ws = self._ws(ws_bytes)
 
@@ -1581,13 +1216,9 @@ class Engine:
         column stride is read in place) -> (rows, cols, values, row_ptr), with score_above's rules and capacity."""
         if threshold != threshold:
             raise ValueError("threshold is NaN")
-        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
-                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
-            score = self._dev(score, torch.float32, "score")
-        r, m = score.shape
-        ld = max(score.stride(0), m)
+        score, r, m, ld = self._matrix(score)
         rs = self._row_self(row_self, r)
-        flags = self.TOPK_CAUSAL if causal else 0
+        flags = self._flags(causal)
         ws_bytes = self.lib.sgpr_rows_above_workspace_bytes(self._h, r, m)
         ws = self._ws(ws_bytes)
 
@@ -1602,7 +1233,7 @@ class Engine:
         return int(self.lib.sgpr_seq_rows_above_workspace_bytes(self._h, int(r), int(m), int(context)))
 
     def score_seq_above_workspace_bytes(self, r, m, seq_len, causal=False, context=0, reverse="both"):
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         return int(self.lib.sgpr_score_seq_above_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
                                                                  flags))
 
@@ -1629,13 +1260,9 @@ class Engine:
         capacity as in score_above.  The filtered matrix is never written."""
         if threshold != threshold:
             raise ValueError("threshold is NaN")
-        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
-                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
-            score = self._dev(score, torch.float32, "score")
-        r, m = score.shape
-        ld = max(score.stride(0), m)
+        score, r, m, ld = self._matrix(score)
         rs = self._row_self(row_self, r)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         ws_bytes = self.lib.sgpr_seq_rows_above_workspace_bytes(self._h, r, m, int(context))
         ws = self._ws(ws_bytes)
 
@@ -1657,7 +1284,7 @@ class Engine:
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         ws_bytes = self.lib.sgpr_score_seq_above_workspace_bytes(self._h, r, m, int(context), int(seq_len), flags)
         ws = self._ws(ws_bytes)
 
@@ -1674,20 +1301,10 @@ class Engine:
 
     def score_session_above_workspace_bytes(self, r, m, seq_len, n_paths=0, causal=False, context=0, reverse="both",
                                             n_row_sessions=0, n_col_sessions=0):
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         return int(self.lib.sgpr_score_session_above_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
                                                                      int(n_paths), flags, int(n_row_sessions),
                                                                      int(n_col_sessions)))
-
-    @staticmethod
-    def _session_tables(paths, seq_len, row_sessions, col_sessions):
-        """(path table pointer, n_paths, row table pointer, n, column table pointer, n) and the arrays that own them"""
-        table = None if paths is None else _path_table(paths, seq_len)
-        rt, ct = _session_table(row_sessions), _session_table(col_sessions)
-        args = []
-        for t in (table, rt, ct):
-            args += [None, 0] if t is None else [t.ctypes.data, t.shape[0]]
-        return args, (table, rt, ct)
 
     def session_rows_above(self, score, seq_len, threshold, paths=None, row_sessions=None, col_sessions=None, min_terms=1,
                            window=-1, row0=0, causal=False, row_self=None, context=0, reverse="both", capacity=None,
@@ -1700,14 +1317,10 @@ class Engine:
         none of whose candidates has min_terms terms is never listed; capacity as in score_above."""
         if threshold != threshold:
             raise ValueError("threshold is NaN")
-        if not (isinstance(score, torch.Tensor) and score.device == self.device and score.dtype == torch.float32 and
-                score.dim() == 2 and score.stride(1) == 1 and score.stride(0) >= score.shape[1]):
-            score = self._dev(score, torch.float32, "score")
-        r, m = score.shape
-        ld = max(score.stride(0), m)
+        score, r, m, ld = self._matrix(score)
         rs = self._row_self(row_self, r)
         tables, keep = self._session_tables(paths, seq_len, row_sessions, col_sessions)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         ws_bytes = self.lib.sgpr_session_rows_above_workspace_bytes(self._h, r, m, int(context))
         ws = self._ws(ws_bytes)
 
@@ -1733,7 +1346,7 @@ class Engine:
         r, m = rows.shape[0], cols.shape[0]
         rs = self._row_self(row_self, r)
         tables, keep = self._session_tables(paths, seq_len, row_sessions, col_sessions)
-        flags = self._seq_flags(reverse) | (self.TOPK_CAUSAL if causal else 0)
+        flags = self._flags(causal, reverse)
         ws_bytes = self.lib.sgpr_score_session_above_workspace_bytes(self._h, r, m, int(context), int(seq_len), tables[1],
                                                                      flags, tables[3], tables[5])
         ws = self._ws(ws_bytes)
@@ -1748,19 +1361,11 @@ class Engine:
 
     def score_seq_positives_workspace_bytes(self, r, m, seq_len, context=0, reverse="both"):
         return int(self.lib.sgpr_score_seq_positives_workspace_bytes(self._h, int(r), int(m), int(context), int(seq_len),
-                                                                     self._seq_flags(reverse)))
+                                                                     self._flags(reverse=reverse)))
 
     def score_seq_threshold_counts_workspace_bytes(self, r, m, seq_len, t, context=0, reverse="both"):
         return int(self.lib.sgpr_score_seq_threshold_counts_workspace_bytes(self._h, int(r), int(m), int(context),
-                                                                            int(seq_len), self._seq_flags(reverse), int(t)))
-
-    def _seq_truth(self, r, m, context, row0, pose_xz, gt):
-        ro = max(r - int(context), 0)
-        if pose_xz is None and gt is not None:
-            gt = self._dev(gt, torch.int8, "gt")
-            assert gt.shape == (ro, m)
-            return None, gt
-        return self._pooled_truth(r, m, row0, pose_xz, gt)
+                                                                            int(seq_len), self._flags(reverse=reverse), int(t)))
 
     def score_seq_positives(self, pooled_rows, pooled_cols, seq_len, row0=0, pose_xz=None, d_pos=3.0, d_neg=20.0, gt=None,
                             context=0, reverse="both"):
@@ -1771,23 +1376,14 @@ class Engine:
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
-        pose_xz, gt = self._seq_truth(r, m, context, row0, pose_xz, gt)
-        flags = self._seq_flags(reverse)
+        pose_xz, gt = self._truth(r, m, row0, pose_xz, gt, context)
+        flags = self._flags(reverse=reverse)
         ws_bytes = self.lib.sgpr_score_seq_positives_workspace_bytes(self._h, r, m, int(context), int(seq_len), flags)
         ws = self._ws(ws_bytes)
-        count = torch.empty(2, dtype=torch.int64, device=self.device)
-        cap = min(max(r - int(context), 0) * m, 1 << 20)
-        while True:
-            out = torch.empty(cap, dtype=torch.float32, device=self.device)
-            rc = self.lib.sgpr_score_seq_positives(self._h, _ptr(rows), r, _ptr(cols), m, int(context), int(seq_len),
-                                                   flags, int(row0), _ptr(pose_xz), float(d_pos), float(d_neg), _ptr(gt),
-                                                   m, _ptr(out) if cap else None, cap, _ptr(count), _ptr(ws), ws_bytes,
-                                                   self._stream())
-            self._check(rc)
-            n, bad = (int(v) for v in count.tolist())
-            if n <= cap:
-                return out[:n], bad
-            cap = n
+        return self._positives(self.lib.sgpr_score_seq_positives,
+                               (self._h, _ptr(rows), r, _ptr(cols), m, int(context), int(seq_len), flags, int(row0),
+                                _ptr(pose_xz), float(d_pos), float(d_neg), _ptr(gt), m),
+                               min(max(r - int(context), 0) * m, 1 << 20), (_ptr(ws), ws_bytes))
 
     def score_seq_threshold_counts(self, pooled_rows, pooled_cols, seq_len, thresholds, row0=0, pose_xz=None, d_pos=3.0,
                                    d_neg=20.0, gt=None, rank=None, context=0, reverse="both"):
@@ -1797,23 +1393,13 @@ class Engine:
         rows = self._pooled(pooled_rows, "pooled_rows")
         cols = self._pooled(pooled_cols, "pooled_cols")
         r, m = rows.shape[0], cols.shape[0]
-        pose_xz, gt = self._seq_truth(r, m, context, row0, pose_xz, gt)
-        thr = self._dev(torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float32)), torch.float32, "thresholds")
-        t = int(thr.numel())
-        out = torch.empty(t + 3, dtype=torch.int64, device=self.device)
-        flags = self._seq_flags(reverse)
-        ws_bytes = self.lib.sgpr_score_seq_threshold_counts_workspace_bytes(self._h, r, m, int(context), int(seq_len),
-                                                                            flags, t)
-        ws = self._ws(ws_bytes)
-        table, at_least, gpt = self._rank_table(rank, t)
-        rc = self.lib.sgpr_score_seq_threshold_counts(self._h, _ptr(rows), r, _ptr(cols), m, int(context), int(seq_len),
-                                                      flags, int(row0), _ptr(pose_xz), float(d_pos), float(d_neg),
-                                                      _ptr(gt), m, _ptr(thr), t, _ptr(table), gpt, _ptr(at_least),
-                                                      _ptr(out), _ptr(ws), ws_bytes, self._stream())
-        self._check(rc)
-        h = out.cpu().numpy()
-        rank_sum = int(h[t + 2].astype(np.uint64)) if rank is not None else None
-        return h[:t + 1].copy(), int(h[t + 1]), rank_sum
+        pose_xz, gt = self._truth(r, m, row0, pose_xz, gt, context)
+        flags = self._flags(reverse=reverse)
+        return self._threshold_counts(self.lib.sgpr_score_seq_threshold_counts,
+                                      (self._h, _ptr(rows), r, _ptr(cols), m, int(context), int(seq_len), flags, int(row0),
+                                       _ptr(pose_xz), float(d_pos), float(d_neg), _ptr(gt), m), thresholds, rank,
+                                      lambda t: self.lib.sgpr_score_seq_threshold_counts_workspace_bytes(
+                                          self._h, r, m, int(context), int(seq_len), flags, t))
 
     def forward_dense(self, features_1, features_2, k, want_att=True):
         """Drop-in SG.forward on dense [B,3+L,N] inputs -> (score [B], att1 [B,N], att2 [B,N])."""
@@ -1853,8 +1439,7 @@ class PairPlan:
         rc = lib.sgpr_pair_plan(i1.ctypes.data_as(ctypes.c_void_p), i2.ctypes.data_as(ctypes.c_void_p), self.P,
                                 self.num_rows, self.num_cols, words.ctypes.data_as(ctypes.c_void_p), words.size,
                                 ctypes.byref(used), ctypes.byref(nr), ctypes.byref(ni))
-        if rc != SGPR_OK:
-            raise SgprError(rc, lib.sgpr_last_error().decode())
+        _check(rc)
         self.n_rows, self.n_items = int(nr.value), int(ni.value)
         self.host_words = words[:int(used.value)]
         self.words = torch.from_numpy(self.host_words.copy()).to(engine.device)
@@ -1864,16 +1449,7 @@ class PairPlan:
 def _gpu_f32(t, name):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError("%s must be a tensor on the MI355X (there is no CPU fallback)" % name)
-    return t.detach().to(torch.float32).contiguous()
-
-
-def _raise_if(lib, rc):
-    if rc != SGPR_OK:
-        raise SgprError(rc, lib.sgpr_last_error().decode())
-
-
-def _stream_of(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    return _on(t.detach(), t.device, torch.float32)
 
 
 def knn(x, k):
@@ -1883,7 +1459,7 @@ def knn(x, k):
     b, c, n = x.shape
     idx = torch.empty(b, n, int(k), dtype=torch.int64, device=x.device)
     with torch.cuda.device(x.device):
-        _raise_if(lib, lib.sgpr_knn(_ptr(x), b, c, n, int(k), _ptr(idx), _stream_of(x)))
+        _check(lib.sgpr_knn(_ptr(x), b, c, n, int(k), _ptr(idx), _stream(x.device)))
     return idx
 
 
@@ -1898,7 +1474,7 @@ def graph_feature(x, idx):
     k = idx.shape[2]
     out = torch.empty(b, 2 * c, n, k, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _raise_if(lib, lib.sgpr_graph_feature(_ptr(x), _ptr(idx), b, c, n, k, _ptr(out), _stream_of(x)))
+        _check(lib.sgpr_graph_feature(_ptr(x), _ptr(idx), b, c, n, k, _ptr(out), _stream(x.device)))
     return out
 
 
@@ -1918,7 +1494,7 @@ def attention_pool(weight, emb):
         rep = torch.empty(b, f, dtype=torch.float32, device=emb.device)
         att = torch.empty(b, n, dtype=torch.float32, device=emb.device)
         with torch.cuda.device(emb.device):
-            _raise_if(lib, lib.sgpr_attention_pool_any(_ptr(weight), _ptr(emb), b, n, f, _ptr(rep), _ptr(att), _stream_of(emb)))
+            _check(lib.sgpr_attention_pool_any(_ptr(weight), _ptr(emb), b, n, f, _ptr(rep), _ptr(att), _stream(emb.device)))
         return rep, att
     if f < F3:          # a smaller width is the built one with zero channels (exactly: zeros add nothing to any sum)
         emb = torch.nn.functional.pad(emb, (0, F3 - f))
@@ -1926,7 +1502,7 @@ def attention_pool(weight, emb):
     rep = torch.empty(b, F3, dtype=torch.float32, device=emb.device)
     att = torch.empty(b, n, dtype=torch.float32, device=emb.device)
     with torch.cuda.device(emb.device):
-        _raise_if(lib, lib.sgpr_attention_pool(_ptr(weight), _ptr(emb), b, n, _ptr(rep), _ptr(att), _stream_of(emb)))
+        _check(lib.sgpr_attention_pool(_ptr(weight), _ptr(emb), b, n, _ptr(rep), _ptr(att), _stream(emb.device)))
     return rep[:, :f], att
 
 
@@ -1946,8 +1522,8 @@ def ntn(weight, weight_block, bias, e1, e2):
     if f > F3 or t > 16:   # wider than the built module: the any-width kernel (plain fp32)
         out = torch.empty(b, t, dtype=torch.float32, device=e1.device)
         with torch.cuda.device(e1.device):
-            _raise_if(lib, lib.sgpr_ntn_any(_ptr(w.contiguous()), _ptr(wb.contiguous()), _ptr(bs.contiguous()), _ptr(e1),
-                                            _ptr(e2), b, f, t, _ptr(out), _stream_of(e1)))
+            _check(lib.sgpr_ntn_any(_ptr(w.contiguous()), _ptr(wb.contiguous()), _ptr(bs.contiguous()), _ptr(e1),
+                                    _ptr(e2), b, f, t, _ptr(out), _stream(e1.device)))
         return out
     if f < F3 or t < 16:   # a smaller module is the built one with zero weights for what it does not have
         pad = torch.nn.functional.pad
@@ -1957,20 +1533,20 @@ def ntn(weight, weight_block, bias, e1, e2):
         bs = pad(bs, (0, 16 - t)).contiguous()
     out = torch.empty(b, 16, dtype=torch.float32, device=e1.device)
     with torch.cuda.device(e1.device):
-        _raise_if(lib, lib.sgpr_ntn(_ptr(w), _ptr(wb), _ptr(bs), _ptr(e1), _ptr(e2), b, _ptr(out), _stream_of(e1)))
+        _check(lib.sgpr_ntn(_ptr(w), _ptr(wb), _ptr(bs), _ptr(e1), _ptr(e2), b, _ptr(out), _stream(e1.device)))
     return out[:, :t]
 
 
 # struct sgpr_verify_result of include/sgpr.h (88 bytes, no padding) and its flag bits
 VERIFY_RESULT = np.dtype([("inliers", "<i4"), ("inliers_refined", "<i4"), ("base", "<i4", (4,)), ("hypotheses", "<u4"),
                           ("flags", "<u4"), ("coarse", "<f4", (4,)), ("refined", "<f8", (4,)), ("rmse", "<f8")])
-VERIFY_MAX_NODES = 256
-VERIFY_INVALID_INDEX, VERIFY_NO_HYPOTHESIS, VERIFY_TRUNCATED, VERIFY_NONFINITE = 1, 2, 4, 8
+VERIFY_MAX_NODES = _C["SGPR_VERIFY_MAX_NODES"]
+VERIFY_INVALID_INDEX, VERIFY_NO_HYPOTHESIS, VERIFY_TRUNCATED, VERIFY_NONFINITE = (
+    _C["SGPR_VERIFY_" + name] for name in ("INVALID_INDEX", "NO_HYPOTHESIS", "TRUNCATED", "NONFINITE"))
 
 
 def _verify_graphs(centers, labels, device, name):
-    c = torch.as_tensor(centers).to(device=device, dtype=torch.float32).contiguous()
-    lab = torch.as_tensor(labels).to(device=device, dtype=torch.int32).contiguous()
+    c, lab = _on(centers, device, torch.float32), _on(labels, device, torch.int32)
     if c.dim() != 3 or c.shape[2] != 3 or tuple(lab.shape) != tuple(c.shape[:2]):
         raise ValueError("%s: centers [G, N, 3] and labels [G, N]" % name)
     return c, lab
@@ -1993,16 +1569,15 @@ def verify_pairs(centers_a, labels_a, centers_b, labels_b, idx_a, idx_b, tau_edg
     cb, lb = _verify_graphs(centers_b, labels_b, device, "column graphs")
     if ca.shape[1] != cb.shape[1]:
         raise ValueError("verify_pairs: both graph sets must have the same number of slots per graph")
-    ia = torch.as_tensor(idx_a).to(device=device, dtype=torch.int32).contiguous().view(-1)
-    ib = torch.as_tensor(idx_b).to(device=device, dtype=torch.int32).contiguous().view(-1)
+    ia, ib = _on(idx_a, device, torch.int32).view(-1), _on(idx_b, device, torch.int32).view(-1)
     if ia.numel() != ib.numel():
         raise ValueError("verify_pairs: idx_a and idx_b must have the same length")
     p = ia.numel()
     rec = torch.empty(p, VERIFY_RESULT.itemsize, dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        _raise_if(lib, lib.sgpr_verify_pairs(_ptr(ca), _ptr(la), ca.shape[0], _ptr(cb), _ptr(lb), cb.shape[0], ca.shape[1],
-                                             _ptr(ia), _ptr(ib), p, float(tau_edge), float(tau_inlier), float(tau_z),
-                                             float(min_base), int(max_hyp), _ptr(rec), _stream_of(rec)))
+        _check(lib.sgpr_verify_pairs(_ptr(ca), _ptr(la), ca.shape[0], _ptr(cb), _ptr(lb), cb.shape[0], ca.shape[1],
+                                     _ptr(ia), _ptr(ib), p, float(tau_edge), float(tau_inlier), float(tau_z),
+                                     float(min_base), int(max_hyp), _ptr(rec), _stream(rec.device)))
     return verify_fields(rec)
 
 
@@ -2015,12 +1590,8 @@ def verify_fields(rec):
             "refined": refined, "rmse": f64v[:, 10], "yaw": torch.atan2(refined[:, 1], refined[:, 0]), "record": rec}
 
 
-CONSISTENCY_MAX_CLOSURES = 16384     # SGPR_CONSISTENCY_MAX_CLOSURES of include/sgpr.h
-CONSISTENCY_MAX_GROUPS = 4096        # SGPR_CONSISTENCY_MAX_GROUPS
-
-
-def _on(t, device, dtype):
-    return torch.as_tensor(t).to(device=device, dtype=dtype).contiguous()
+CONSISTENCY_MAX_CLOSURES = _C["SGPR_CONSISTENCY_MAX_CLOSURES"]
+CONSISTENCY_MAX_GROUPS = _C["SGPR_CONSISTENCY_MAX_GROUPS"]
 
 
 def closure_consistency(rows, cols, T, Xr, Xc, group, n_groups, max_trans, min_cos, lever_gain, device=None):
@@ -2045,10 +1616,10 @@ def closure_consistency(rows, cols, T, Xr, Xc, group, n_groups, max_trans, min_c
     need = int(lib.sgpr_closure_consistency_workspace_bytes(n)) if 0 <= n <= CONSISTENCY_MAX_CLOSURES else 0
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        _raise_if(lib, lib.sgpr_closure_consistency(_ptr(r), _ptr(c), _ptr(t), n, _ptr(xr), xr.shape[0], _ptr(xc),
-                                                    xc.shape[0], _ptr(g), int(n_groups), float(max_trans), float(min_cos),
-                                                    float(lever_gain), _ptr(adj), _ptr(degree), _ptr(ws), need,
-                                                    _stream_of(adj)))
+        _check(lib.sgpr_closure_consistency(_ptr(r), _ptr(c), _ptr(t), n, _ptr(xr), xr.shape[0], _ptr(xc),
+                                            xc.shape[0], _ptr(g), int(n_groups), float(max_trans), float(min_cos),
+                                            float(lever_gain), _ptr(adj), _ptr(degree), _ptr(ws), need,
+                                            _stream(adj.device)))
     return adj, degree, ws[:4 * n].view(torch.int32)
 
 
@@ -2070,8 +1641,8 @@ def consistent_set(adj, group, n_groups, device=None):
     need = int(lib.sgpr_consistent_set_workspace_bytes(n)) if 0 <= n <= CONSISTENCY_MAX_CLOSURES else 0
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        _raise_if(lib, lib.sgpr_consistent_set(_ptr(a), n, _ptr(g), int(n_groups), _ptr(rank), _ptr(size), _ptr(ws), need,
-                                               _stream_of(rank)))
+        _check(lib.sgpr_consistent_set(_ptr(a), n, _ptr(g), int(n_groups), _ptr(rank), _ptr(size), _ptr(ws), need,
+                                       _stream(rank.device)))
     return rank, size
 
 
@@ -2079,9 +1650,7 @@ def cluster_scan(points, labels, max_nodes=1024, want_point_node=False):
     """sgpr_cluster_scan: points [P, >=3] f32 and raw labels [P] (u32 bit pattern) on the GPU ->
     (centers float64 [n,3], node labels int32 [n], cluster sizes int32 [n], point -> node int32 [P] or None)."""
     lib = load_library()
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        raise RuntimeError("points must be a tensor on the MI355X (there is no CPU fallback)")
-    points = points.detach().to(torch.float32).contiguous()
+    points = _gpu_f32(points, "points")
     p, stride = points.shape
     labels = labels.to(points.device).contiguous()
     if labels.dtype not in (torch.int32, torch.uint32) or labels.numel() != p:
@@ -2095,8 +1664,8 @@ def cluster_scan(points, labels, max_nodes=1024, want_point_node=False):
     ws_bytes = lib.sgpr_cluster_workspace_bytes(p)
     ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _raise_if(lib, lib.sgpr_cluster_scan(_ptr(points), stride, _ptr(labels), p, max_nodes, _ptr(centers), _ptr(nlab),
-                                             _ptr(nsize), _ptr(pnode), _ptr(count), _ptr(ws), ws_bytes, _stream_of(points)))
+        _check(lib.sgpr_cluster_scan(_ptr(points), stride, _ptr(labels), p, max_nodes, _ptr(centers), _ptr(nlab),
+                                     _ptr(nsize), _ptr(pnode), _ptr(count), _ptr(ws), ws_bytes, _stream(points.device)))
     n = int(count.item())
     if n < 0 or n > max_nodes:
         raise SgprError(-3, "scan produced %s nodes, more than max_nodes=%d" % ("> 8192" if n < 0 else n, max_nodes))
@@ -2117,6 +1686,6 @@ def graph_edges(points, point_node, centers):
     centers = centers.to(device=dev, dtype=torch.float64).contiguous()
     point_node = point_node.to(device=dev, dtype=torch.int32).contiguous()
     with torch.cuda.device(dev):
-        _raise_if(lib, lib.sgpr_graph_edges(_ptr(points), stride, _ptr(point_node), p, n, _ptr(centers), _ptr(out), _ptr(ws),
-                                            n * n * 4, _stream_of(points)))
+        _check(lib.sgpr_graph_edges(_ptr(points), stride, _ptr(point_node), p, n, _ptr(centers), _ptr(out), _ptr(ws),
+                                    n * n * 4, _stream(points.device)))
     return out
