@@ -486,3 +486,32 @@ def closure_pose_errors(results, rows, cols, poses):
     return {"yaw_deg": yaw_deg, "trans_m": trans,
             "median_yaw_deg": float(np.nanmedian(yaw_deg)) if some else float("nan"),
             "median_trans_m": float(np.nanmedian(trans)) if some else float("nan")}
+
+
+def trajectory_error(est, truth, starts=None):
+    """RMS position error (m) of estimated planar poses against the truth after ONE rigid planar alignment (rotation +
+    translation, closed form: the least-squares fit of the positions).  est, truth: [M, 4] planar poses (c, s, x, y) or
+    [M, 2] positions.  starts = None -> a float for the whole map (a merged multi-session map is only right when its
+    sessions share one frame); starts = a session table -> float64 [S], every session aligned on its own (NaN for an
+    empty one)."""
+    def xy(a):
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float64)
+        a = a.reshape(-1, a.shape[-1])
+        return a[:, -2] + 1j * a[:, -1]
+
+    def one(a, b):
+        if a.size == 0:
+            return float("nan")
+        a, b = a - a.mean(), b - b.mean()
+        rot = np.vdot(a, b)
+        rot = rot / abs(rot) if abs(rot) > 0 else 1.0
+        return float(np.sqrt(np.mean(np.abs(rot * a - b) ** 2)))
+
+    a, b = xy(est), xy(truth)
+    if a.shape != b.shape:
+        raise ValueError("trajectory_error: est and truth must hold the same number of poses")
+    if starts is None:
+        return one(a, b)
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    ends = np.append(starts[1:], a.size)
+    return np.array([one(a[s:e], b[s:e]) for s, e in zip(starts, ends)], dtype=np.float64)

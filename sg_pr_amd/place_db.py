@@ -18,7 +18,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
                                             [--verify] [--min-inliers I] [--consistent] [--distinct RHO] [--seq-slopes S,S,...]
-                                            [--sessions N]
+                                            [--sessions N] [--optimize] [--save-poses FILE]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -58,7 +58,11 @@ of a session that has a predecessor.  All four are counted under the session rul
 [--max-trans M] [--max-yaw-deg D] [--lever-gain G] [--min-clique N] the accepted closures are also checked against one
 another through the poses (SG.consistent_closures; with --sessions N within each pair of sessions):
 `<seq>_consistent.npz` holds rows, cols, refined, consistent, rank, degree, group_size, session_starts and the counts;
-printed are the number and the precision of the accepted closures before and after the selection.
+printed are the number and the precision of the accepted closures before and after the selection.  With --optimize
+[--save-poses FILE] on top of that the planar pose graph of the map - the sequence's poses as odometry, the consistent
+closures as loop edges, the first scan fixed - is relaxed on the device (SG.optimize_map, posegraph.optimize, DESIGN.md
+§25): printed are the closures and scans that took part, the trajectory error of the map against the poses before and
+after (metrics.trajectory_error) and the iterations of the two stages; FILE gets the optimised poses [M,4] (.npy).
 """
 import argparse
 import math
@@ -384,6 +388,11 @@ def main(argv=None):
     ap.add_argument("--consistent", action="store_true",
                     help="with --verify: keep the accepted closures that agree pair by pair through the poses "
                          "(with --sessions N: within each pair of sessions) and write <seq>_consistent.npz")
+    ap.add_argument("--optimize", action="store_true",
+                    help="with --consistent: relax the planar pose graph of the map over the consistent closures "
+                         "(DESIGN.md §25) and print the trajectory error before and after")
+    ap.add_argument("--save-poses", default=None, metavar="FILE",
+                    help="with --optimize: write the optimised planar poses [M,4] (c, s, x, y) to FILE (.npy)")
     ap.add_argument("--max-trans", type=float, default=1.0, metavar="M",
                     help="with --consistent: translation tolerance of a pair of closures, metres")
     ap.add_argument("--max-yaw-deg", type=float, default=math.degrees(0.06), metavar="D",
@@ -410,6 +419,10 @@ def main(argv=None):
         ap.error("--min-terms must lie in 1..--seq-len")
     if opt.consistent and not opt.verify:
         ap.error("--consistent needs --verify")
+    if opt.optimize and not opt.consistent:
+        ap.error("--optimize needs --consistent")
+    if opt.save_poses is not None and not opt.optimize:
+        ap.error("--save-poses needs --optimize")
     if opt.consistent and (opt.max_trans < 0 or opt.lever_gain < 0 or not 0 <= opt.max_yaw_deg <= 180):
         ap.error("--max-trans and --lever-gain must be >= 0, --max-yaw-deg in 0..180")
     if opt.sessions is not None and not 2 <= opt.sessions <= _engine.SESSION_MAX:
@@ -487,6 +500,19 @@ def main(argv=None):
                   "precision %.4f" % creport["precision_accepted"], "-> pairwise consistent",
                   int(creport["consistent_count"]), "precision %.4f" % creport["precision_consistent"],
                   "(largest set %d)" % int(creport["group_size"].max()))
+        if opt.optimize:
+            X = metrics.planar_odometry(seq.poses)
+            sel = {"accept": creport["consistent"]}
+            out, info = trainer.model.optimize_map(sel, {"refined": creport["refined"]}, creport["rows"], creport["cols"], X,
+                                                   sessions=creport["session_starts"])
+            out = out.cpu().numpy()
+            print("sequence", sequence, "pose graph over", info["live_closures"], "closures,", info["free_scans"],
+                  "free scans in", info["active_sessions"], "sessions: trajectory error %.4f m -> %.4f m,"
+                  % (metrics.trajectory_error(X, X), metrics.trajectory_error(out, X)),
+                  "iterations %d + %d (%s, %s)" % (info["iterations"] + info["stop"]))
+            if opt.save_poses is not None:
+                with open(opt.save_poses, "wb") as f:
+                    np.save(f, out)
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,

@@ -277,6 +277,50 @@ class SG(torch.nn.Module):
         return {"accept": ((rank >= 0) & big).reshape(shape), "rank": rank.reshape(shape),
                 "degree": degree.reshape(shape), "group_size": size}
 
+    def optimize_map(self, consistent, verified, rows, cols, poses, sessions=None, row_poses=None, row_sessions=None,
+                     weight=None, **solver):
+        """One map in one frame (posegraph.optimize): the closures consistent_closures accepted become the
+        loop edges of a planar pose graph over the odometry of the map, and a two-stage linear solve spreads the drift
+        over the loops and places every session that a closure ties to the first one.
+        consistent: the dict of consistent_closures (its "accept") or a bool mask shaped like rows; verified: the dict of
+        verify_closures / engine.verify_pairs ("refined"); rows / cols: the row and column scan of every closure.  poses
+        / sessions: the column scans' poses (KITTI rows [M,12] or planar [M,4]) and session table.  row_poses None: the
+        rows index the same map; otherwise the row scans are a separate set, joined to the map behind the column scans
+        as extra sessions (row_sessions: its own session table, None = one).  The first scan of the first session is
+        fixed.  solver: weight, w_odo, w_clo, max_iters, rel_tol of posegraph.optimize.
+        -> (planar poses f64 [M (+ MR), 4] device tensor in the frame of the first session, info dict with
+        "session_starts" of the stacked map added)."""
+        from . import metrics, posegraph
+        dev = self.engine().device
+
+        def planar(p):
+            p = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+            p = p.reshape(p.shape[0], -1)
+            return np.asarray(p, dtype=np.float64) if p.shape[1] == 4 else metrics.planar_odometry(p)
+
+        def table(t):
+            t = [0] if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else t)
+            return np.asarray(t, dtype=np.int64).reshape(-1)
+
+        X, starts = planar(poses), table(sessions)
+        r = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).reshape(-1)
+        c = torch.as_tensor(cols).to(device=dev, dtype=torch.int64).reshape(-1)
+        if row_poses is not None:
+            r = torch.where(r >= 0, r + X.shape[0], r)
+            starts = np.concatenate((starts, table(row_sessions) + X.shape[0]))
+            X = np.concatenate((X, planar(row_poses)))
+        acc = consistent["accept"] if isinstance(consistent, dict) else consistent
+        acc = torch.as_tensor(acc).to(device=dev, dtype=torch.bool).reshape(-1)
+        refined = torch.as_tensor(verified["refined"]).to(device=dev, dtype=torch.float64).reshape(-1, 4)
+        if not (acc.numel() == r.numel() == c.numel() == refined.shape[0]):
+            raise ValueError("optimize_map: the selection, the verified records, rows and cols must have the same shape")
+        if weight is not None:
+            weight = torch.as_tensor(weight).to(device=dev, dtype=torch.float64).reshape(-1)[acc]
+        out, info = posegraph.optimize(X, r[acc].to(torch.int32), c[acc].to(torch.int32), refined[acc], starts=starts,
+                                       weight=weight, device=dev, **solver)
+        info["session_starts"] = starts.astype(np.int32)
+        return out, info
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming

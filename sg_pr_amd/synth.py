@@ -169,6 +169,13 @@ def _se2(yaw, x, y):
     return np.stack((np.cos(yaw), np.sin(yaw), x, y), axis=-1).astype(np.float64)
 
 
+def _random_walk(rng, S):
+    """the planar trajectory of closure_world and drift_world: 1 m per scan, the heading a random walk of 0.05 rad"""
+    heading = np.cumsum(rng.normal(0.0, 0.05, size=S))
+    xy = np.cumsum(np.stack([np.cos(heading), np.sin(heading)], axis=1), axis=0)
+    return heading, xy
+
+
 def closure_world(seed, scans=600, closures=400, outlier_frac=0.5, alias=30, noise_t=0.15, noise_yaw=0.01):
     """A planted set of loop closures between two drives, for the pairwise-consistency stage.
 
@@ -183,8 +190,7 @@ def closure_world(seed, scans=600, closures=400, outlier_frac=0.5, alias=30, noi
     y); planted bool [C] (a true closure); aliased bool [C].  Closures are shuffled.  numpy only."""
     rng = np.random.default_rng(seed + 15485863)
     S, C = int(scans), int(closures)
-    heading = np.cumsum(rng.normal(0.0, 0.05, size=S))
-    xy = np.cumsum(np.stack([np.cos(heading), np.sin(heading)], axis=1), axis=0)
+    heading, xy = _random_walk(rng, S)
     X1 = _se2(heading, xy[:, 0], xy[:, 1])
     xy2 = xy + rng.normal(0.0, 0.5, size=(S, 2))
     X2 = _se2(heading + rng.normal(0.0, 0.03, size=S), xy2[:, 0], xy2[:, 1])        # drive 2 in drive 1's frame
@@ -211,6 +217,44 @@ def closure_world(seed, scans=600, closures=400, outlier_frac=0.5, alias=30, noi
     perm = rng.permutation(C)
     return {"rows": rows[perm].astype(np.int32), "cols": cols[perm].astype(np.int32),
             "T": np.ascontiguousarray(T[perm]), "Xr": X1, "Xc": Xc, "planted": planted[perm], "aliased": aliased[perm]}
+
+
+def drift_world(seed, scans=300, sessions=2, closures=120, noise_t=0.15, noise_yaw=0.01, odo_yaw=0.004, odo_t=0.03):
+    """A multi-session map with drifting odometry and true loop closures, for the pose-graph stage.
+
+    `sessions` drives of closure_world's trajectory (1 m per scan), each jittered by N(0, 0.5) m and N(0, 0.03) rad.
+    The odometry of a drive is integrated from its true relative motions, each perturbed by N(0, odo_yaw) rad and
+    N(0, odo_t) m, starting in a frame of its own (drive d: rotated by 1.1 d rad, shifted by (40 d, -25 d)) - so every
+    drive drifts and the frames are unrelated.  A closure joins a scan of one drive to a scan within +-2 indices of a
+    different drive and carries T, a point of scan rows[p] into scan cols[p], with closure_world's noise.
+    -> dict: truth, odom float64 [sessions * scans, 4] planar poses (c, s, x, y) of the stacked map; starts int32
+    [sessions]; rows, cols int32 [C] (indices into the stacked map); T float64 [C,4].  numpy only."""
+    rng = np.random.default_rng(seed + 32452843)
+    S, D, C = int(scans), int(sessions), int(closures)
+    heading, xy = _random_walk(rng, S)
+    truth, odom = [], []
+    for d in range(D):
+        xyd = xy + rng.normal(0.0, 0.5, size=(S, 2))
+        Xt = _se2(heading + rng.normal(0.0, 0.03, size=S), xyd[:, 0], xyd[:, 1])
+        rel = _se2_compose(_se2_inverse(Xt[:-1]), Xt[1:])
+        rel = _se2_compose(rel, _se2(rng.normal(0.0, odo_yaw, size=S - 1), rng.normal(0.0, odo_t, size=S - 1),
+                                     rng.normal(0.0, odo_t, size=S - 1)))
+        Xo = np.empty((S, 4), dtype=np.float64)
+        Xo[0] = _se2_compose(_se2(1.1 * d, 40.0 * d, -25.0 * d), Xt[0])
+        for k in range(S - 1):
+            Xo[k + 1] = _se2_compose(Xo[k], rel[k])
+        truth.append(Xt)
+        odom.append(Xo)
+    truth, odom = np.concatenate(truth), np.concatenate(odom)
+    a = rng.integers(0, D, size=C)
+    b = (a + rng.integers(1, max(D, 2), size=C)) % D if D > 1 else a
+    i = rng.integers(0, S, size=C)
+    j = np.clip(i + rng.integers(-2, 3, size=C), 0, S - 1)
+    rows, cols = a * S + i, b * S + j
+    T = _se2_compose(_se2(rng.normal(0.0, noise_yaw, size=C), rng.normal(0.0, noise_t, size=C),
+                          rng.normal(0.0, noise_t, size=C)), _se2_compose(_se2_inverse(truth[cols]), truth[rows]))
+    return {"truth": truth, "odom": odom, "starts": (np.arange(D) * S).astype(np.int32), "rows": rows.astype(np.int32),
+            "cols": cols.astype(np.int32), "T": np.ascontiguousarray(T)}
 
 
 def dense_features(centers, labels, num_labels=NUM_LABELS):
