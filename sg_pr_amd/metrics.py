@@ -515,3 +515,20 @@ def trajectory_error(est, truth, starts=None):
     starts = np.asarray(starts, dtype=np.int64).reshape(-1)
     ends = np.append(starts[1:], a.size)
     return np.array([one(a[s:e], b[s:e]) for s, e in zip(starts, ends)], dtype=np.float64)
+
+
+def localization_errors(pose, truth):
+    """Translation and yaw error of localised scans (localize.localize / SG.localize) against the true
+    poses.  pose, truth: planar poses [Q, 4] (c, s, x, y) in one frame; a query without a pose holds NaN and gets NaN
+    errors.  -> dict: trans_m, yaw_deg (float64 numpy [Q]; the yaw error is the absolute angle between the two headings),
+    median_trans_m, median_yaw_deg (NaN-ignoring; NaN when no query has a pose)."""
+    def host(t):
+        return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64).reshape(-1, 4)
+    p, t = host(pose), host(truth)
+    if p.shape != t.shape:
+        raise ValueError("localization_errors: pose and truth must hold the same number of poses")
+    trans = np.hypot(p[:, 2] - t[:, 2], p[:, 3] - t[:, 3])
+    yaw = np.degrees(np.abs(np.arctan2(p[:, 1] * t[:, 0] - p[:, 0] * t[:, 1], p[:, 0] * t[:, 0] + p[:, 1] * t[:, 1])))
+    some = bool(np.isfinite(trans).any())
+    return {"trans_m": trans, "yaw_deg": yaw, "median_trans_m": float(np.nanmedian(trans)) if some else float("nan"),
+            "median_yaw_deg": float(np.nanmedian(yaw)) if some else float("nan")}

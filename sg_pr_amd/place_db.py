@@ -63,6 +63,14 @@ printed are the number and the precision of the accepted closures before and aft
 closures as loop edges, the first scan fixed - is relaxed on the device (SG.optimize_map, posegraph.optimize, DESIGN.md
 §25): printed are the closures and scans that took part, the trajectory error of the map against the poses before and
 after (metrics.trajectory_error) and the iterations of the two stages; FILE gets the optimised poses [M,4] (.npy).
+With --verify --localize [--loc-len L] [--min-support S] [--loc-max-trans M] [--loc-max-yaw-deg D] every scan is
+localised in the sequence's own planar ground-truth poses from the candidates its list retrieved (SG.localize,
+localize.localize; the window already keeps a scan's neighbours out of its list): the verified candidates
+of the scan and of the L - 1 scans before it, carried forward by the poses as odometry, vote on its pose, and it counts as
+localised with a support of at least S.  `<seq>_localize.npz` holds pose [M,4], support, live, winner, flags, spread,
+accept, trans_m, yaw_deg, the records that went in (indices, refined, verify_flags, verify_accept) and the parameters;
+printed are the share localised and the median and 95th-percentile translation and yaw error, and beside them the same
+numbers for the best verified candidate taken alone.
 """
 import argparse
 import math
@@ -393,6 +401,17 @@ def main(argv=None):
                          "(DESIGN.md §25) and print the trajectory error before and after")
     ap.add_argument("--save-poses", default=None, metavar="FILE",
                     help="with --optimize: write the optimised planar poses [M,4] (c, s, x, y) to FILE (.npy)")
+    ap.add_argument("--localize", action="store_true",
+                    help="with --verify: localise every scan in the sequence's poses from its verified candidates "
+                         "(DESIGN.md §26) and write <seq>_localize.npz")
+    ap.add_argument("--loc-len", type=int, default=1, metavar="L",
+                    help="with --localize: the candidates of the last L scans vote, carried forward by the odometry (1..16)")
+    ap.add_argument("--min-support", type=int, default=3, metavar="S",
+                    help="with --localize: a scan is localised when S hypotheses agree")
+    ap.add_argument("--loc-max-trans", type=float, default=1.0, metavar="M",
+                    help="with --localize: translation tolerance of two hypotheses, metres")
+    ap.add_argument("--loc-max-yaw-deg", type=float, default=math.degrees(0.1), metavar="D",
+                    help="with --localize: yaw tolerance of two hypotheses, degrees")
     ap.add_argument("--max-trans", type=float, default=1.0, metavar="M",
                     help="with --consistent: translation tolerance of a pair of closures, metres")
     ap.add_argument("--max-yaw-deg", type=float, default=math.degrees(0.06), metavar="D",
@@ -425,6 +444,11 @@ def main(argv=None):
         ap.error("--save-poses needs --optimize")
     if opt.consistent and (opt.max_trans < 0 or opt.lever_gain < 0 or not 0 <= opt.max_yaw_deg <= 180):
         ap.error("--max-trans and --lever-gain must be >= 0, --max-yaw-deg in 0..180")
+    if opt.localize and not opt.verify:
+        ap.error("--localize needs --verify")
+    from .localize import MAX_LEN as loc_max_len
+    if opt.localize and not (1 <= opt.loc_len <= loc_max_len and opt.loc_max_trans >= 0 and 0 <= opt.loc_max_yaw_deg <= 180):
+        ap.error("--loc-len must lie in 1..%d, --loc-max-trans must be >= 0, --loc-max-yaw-deg in 0..180" % loc_max_len)
     if opt.sessions is not None and not 2 <= opt.sessions <= _engine.SESSION_MAX:
         ap.error("--sessions must lie in 2..%d" % _engine.SESSION_MAX)
     if opt.sessions is not None and opt.distinct is not None:
@@ -513,6 +537,18 @@ def main(argv=None):
             if opt.save_poses is not None:
                 with open(opt.save_poses, "wb") as f:
                     np.save(f, out)
+        if opt.localize:
+            lreport = localize_lists(trainer.model, seq, vals, idx, opt.min_inliers, seq_len=opt.loc_len,
+                                     min_support=opt.min_support, max_trans=opt.loc_max_trans,
+                                     max_yaw=math.radians(opt.loc_max_yaw_deg))
+            np.savez(os.path.join(args.output_path, sequence + "_localize.npz"), frame=np.arange(m), **lreport)
+            print("sequence", sequence, "localised %.4f of %d scans (last %d scans, support >= %d):"
+                  % (lreport["localized"], m, opt.loc_len, opt.min_support),
+                  "translation error median %.3f m, 95%% %.3f m; yaw error median %.3f deg, 95%% %.3f deg;"
+                  % tuple(lreport[n] for n in ("median_trans_m", "p95_trans_m", "median_yaw_deg", "p95_yaw_deg")),
+                  "best verified candidate alone: %.4f, median %.3f m, 95%% %.3f m; median %.3f deg, 95%% %.3f deg"
+                  % tuple(lreport["single_" + n] for n in ("localized", "median_trans_m", "p95_trans_m", "median_yaw_deg",
+                                                           "p95_yaw_deg")))
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
@@ -689,6 +725,50 @@ def verify_lists(model, seq, values, indices, min_inliers, p_thresh, window=-1, 
                 "true_accepted": np.int64(int(true.sum())),
                 "median_yaw_deg": np.float64(np.median(yaw) if yaw.size else 0.0),
                 "median_trans_m": np.float64(np.median(trans) if trans.size else 0.0)})
+    return out
+
+
+def localize_lists(model, seq, values, indices, min_inliers, seq_len=1, min_support=3, max_trans=1.0, max_yaw=0.1):
+    """Every frame of `seq` localised in the sequence's own planar poses from the candidates its list retrieved (values /
+    indices [M,K], at most localize.MAX_K columns of them): verified as verify_lists does, then SG.localize with the
+    poses as the map and as the query drive's odometry.  Beside it the best verified candidate taken alone: the first
+    slot of the re-ranked list, when it is accepted.
+    -> dict of numpy arrays: pose [M,4], support, live, winner, flags, spread, accept (support >= min_support), trans_m,
+    yaw_deg [M] (metrics.localization_errors against the poses; NaN where not accepted), localized (the share accepted),
+    median / p95 of both errors over the accepted; single_pose, single_accept and the same five figures with the prefix
+    single_; what went in: indices, refined, verify_flags, verify_accept, seq_len, min_support, max_trans, max_yaw."""
+    from . import localize as _localize
+    from .synth import _se2_compose
+    idx = torch.as_tensor(indices)[:, :_localize.MAX_K]
+    vals = None if values is None else torch.as_tensor(values)[:, :_localize.MAX_K]
+    ver = model.verify_closures(seq.centers, seq.labels, idx, values=vals, min_inliers=min_inliers)
+    X = metrics.planar_odometry(seq.poses)
+    loc = model.localize(ver, idx, X, query_poses=X, seq_len=seq_len, min_support=min_support, max_trans=max_trans,
+                         max_yaw=max_yaw)
+    out = {name: loc[name].cpu().numpy() for name in ("pose", "support", "live", "winner", "flags", "spread", "accept")}
+    idx_h, refined = idx.cpu().numpy(), ver["refined"].cpu().numpy()
+    best = ver["order"][:, :1].cpu().numpy()
+    single_ok = np.take_along_axis(ver["accept"].cpu().numpy(), best, axis=1)[:, 0]
+    col = np.take_along_axis(idx_h, best, axis=1)[:, 0]
+    single = _se2_compose(X[np.where(single_ok, col, 0)], np.take_along_axis(refined, best[:, :, None], axis=1)[:, 0])
+    single[~single_ok] = np.nan
+
+    def figures(pose, ok, prefix):
+        err = metrics.localization_errors(np.where(ok[:, None], pose, np.nan), X)
+        t, y = err["trans_m"][ok], err["yaw_deg"][ok]
+        rep = {prefix + "localized": np.float64(ok.mean() if ok.size else 0.0)}
+        for name, v in (("trans_m", t), ("yaw_deg", y)):
+            rep[prefix + "median_" + name] = np.float64(np.median(v) if v.size else float("nan"))
+            rep[prefix + "p95_" + name] = np.float64(np.percentile(v, 95) if v.size else float("nan"))
+        return err, rep
+
+    err, rep = figures(out["pose"], out["accept"], "")
+    out.update(rep)
+    out.update({"trans_m": err["trans_m"], "yaw_deg": err["yaw_deg"], "single_pose": single, "single_accept": single_ok})
+    out.update(figures(single, single_ok, "single_")[1])
+    out.update({"indices": idx_h, "refined": refined, "verify_flags": ver["flags"].cpu().numpy(),
+                "verify_accept": ver["accept"].cpu().numpy(), "seq_len": np.int64(seq_len),
+                "min_support": np.int64(min_support), "max_trans": np.float64(max_trans), "max_yaw": np.float64(max_yaw)})
     return out
 
 

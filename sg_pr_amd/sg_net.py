@@ -19,6 +19,14 @@ from .layers_batch import AttentionModule, TenorNetworkModule
 from .utils import process_pair, load_paires, read_graph, pose_distance  # noqa: F401  (reference: `from utils import *`)
 
 
+def _planar(p):
+    """poses as optimize_map and localize take them - KITTI rows [M,12] or planar [M,4] - as planar float64 [M,4] on the host"""
+    from . import metrics
+    p = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+    p = p.reshape(p.shape[0], -1)
+    return np.asarray(p, dtype=np.float64) if p.shape[1] == 4 else metrics.planar_odometry(p)
+
+
 class SG(torch.nn.Module):
     """Pair scorer with the reference's constructor, parameter names and forward contract.
 
@@ -290,25 +298,20 @@ class SG(torch.nn.Module):
         fixed.  solver: weight, w_odo, w_clo, max_iters, rel_tol of posegraph.optimize.
         -> (planar poses f64 [M (+ MR), 4] device tensor in the frame of the first session, info dict with
         "session_starts" of the stacked map added)."""
-        from . import metrics, posegraph
+        from . import posegraph
         dev = self.engine().device
-
-        def planar(p):
-            p = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
-            p = p.reshape(p.shape[0], -1)
-            return np.asarray(p, dtype=np.float64) if p.shape[1] == 4 else metrics.planar_odometry(p)
 
         def table(t):
             t = [0] if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else t)
             return np.asarray(t, dtype=np.int64).reshape(-1)
 
-        X, starts = planar(poses), table(sessions)
+        X, starts = _planar(poses), table(sessions)
         r = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).reshape(-1)
         c = torch.as_tensor(cols).to(device=dev, dtype=torch.int64).reshape(-1)
         if row_poses is not None:
             r = torch.where(r >= 0, r + X.shape[0], r)
             starts = np.concatenate((starts, table(row_sessions) + X.shape[0]))
-            X = np.concatenate((X, planar(row_poses)))
+            X = np.concatenate((X, _planar(row_poses)))
         acc = consistent["accept"] if isinstance(consistent, dict) else consistent
         acc = torch.as_tensor(acc).to(device=dev, dtype=torch.bool).reshape(-1)
         refined = torch.as_tensor(verified["refined"]).to(device=dev, dtype=torch.float64).reshape(-1, 4)
@@ -320,6 +323,37 @@ class SG(torch.nn.Module):
                                        weight=weight, device=dev, **solver)
         info["session_starts"] = starts.astype(np.int32)
         return out, info
+
+    def localize(self, verified, cols, map_poses, query_poses=None, query_sessions=None, seq_len=1, min_support=3,
+                 max_trans=1.0, max_yaw=0.1):
+        """Where is every query scan in the map (localize.localize): every verified candidate of the last
+        seq_len scans of a query's session, carried forward by the query drive's own odometry, is a hypothesis of the
+        query's pose in the map; the answer is the mean of the largest set of hypotheses that agrees with one of them
+        within max_trans metres and max_yaw radians, accepted when that set has min_support members.
+        verified: the dict of verify_closures ("refined", "flags", and "accept" when it was made with min_inliers) with
+        the queries as rows, shaped [Q,k]; cols [Q,k]: the candidate map scans (-1 = padding).  map_poses: the poses of
+        the map scans in the map frame - KITTI rows [M,12] (metrics.planar_odometry makes them planar) or planar [M,4],
+        e.g. what optimize_map returned.  query_poses: the odometry of the query drive in any frame of its own (needed
+        for seq_len > 1), query_sessions its session table (None: one session).  A candidate is void if its flags carry
+        INVALID_INDEX, NO_HYPOTHESIS or NONFINITE or it is not accepted.
+        -> dict of device tensors: pose f64 [Q,4] (c, s, x, y; NaN without a live hypothesis), support, live, winner,
+        flags i32 [Q], spread f64 [Q], accept bool [Q]."""
+        from . import localize as _localize
+        dev = self.engine().device
+        c = torch.as_tensor(cols).to(device=dev, dtype=torch.int32)
+        if c.dim() != 2:
+            raise ValueError("localize: cols must be [Q, k]")
+        flags = torch.as_tensor(verified["flags"]).to(device=dev, dtype=torch.int64).reshape(c.shape)
+        refined = torch.as_tensor(verified["refined"]).to(device=dev, dtype=torch.float64).reshape(tuple(c.shape) + (4,))
+        void = (flags & (_engine.VERIFY_INVALID_INDEX | _engine.VERIFY_NO_HYPOTHESIS | _engine.VERIFY_NONFINITE)) != 0
+        if "accept" in verified:
+            void |= ~torch.as_tensor(verified["accept"]).to(device=dev, dtype=torch.bool).reshape(c.shape)
+        if int(seq_len) > 1 and query_poses is None:
+            raise ValueError("localize: seq_len > 1 needs the query drive's odometry (query_poses)")
+        odo = None if query_poses is None else _planar(query_poses)
+        return _localize.localize(_planar(map_poses), c, refined, accept=~void, odo=odo, starts=query_sessions,
+                                  seq_len=int(seq_len), max_trans=max_trans, max_yaw=max_yaw, device=dev,
+                                  min_support=int(min_support))
 
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):

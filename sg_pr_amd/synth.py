@@ -257,6 +257,59 @@ def drift_world(seed, scans=300, sessions=2, closures=120, noise_t=0.15, noise_y
             "cols": cols.astype(np.int32), "T": np.ascontiguousarray(T)}
 
 
+def localize_world(seed, map_scans=600, queries=200, k=8, true_frac=0.4, alias_frac=0.25, alias=4, noise_t=0.15,
+                   noise_yaw=0.01, odo_yaw=0.004, odo_t=0.03):
+    """A map, a query drive and candidate lists with planted truths and aliases, for the localisation stage (DESIGN.md
+    §26).
+
+    The map is closure_world's trajectory (1 m per scan) with its true poses.  The queries re-drive a random stretch of
+    it, jittered by N(0, 0.5) m and N(0, 0.03) rad; their odometry is integrated from the true relative motions, each
+    perturbed by N(0, odo_yaw) rad and N(0, odo_t) m, in a frame of its own (rotated by 1.1 rad, shifted by (40, -25)),
+    as in drift_world.  Every query has k candidates (col, T: a point of the query scan into map scan col).  A candidate
+    is true with probability true_frac: its column lies within +-2 of the query's map index and T is the true transform
+    perturbed by N(0, noise_yaw) rad and N(0, noise_t) m, as in closure_world.  The rest are random columns with random
+    transforms (+-30 m, any yaw).  In a share alias_frac of the queries the first `alias` false candidates are rebuilt
+    to agree on ONE wrong pose, drawn per query anywhere in the map's bounding box, with the same noise: they agree with
+    one another within a scan, and, not moving with the odometry, with nothing across scans.
+    -> dict: map float64 [map_scans,4]; truth, odom float64 [queries,4] (c, s, x, y); index int32 [queries] (the map
+    scan each query re-drives); cols int32 [queries,k]; T float64 [queries,k,4]; planted, aliased bool [queries,k].
+    numpy only."""
+    rng = np.random.default_rng(seed + 49979687)
+    M, Q, K = int(map_scans), int(queries), int(k)
+    heading, xy = _random_walk(rng, M)
+    world = _se2(heading, xy[:, 0], xy[:, 1])
+    index = int(rng.integers(0, M - Q + 1)) + np.arange(Q)
+    xyq = xy[index] + rng.normal(0.0, 0.5, size=(Q, 2))
+    truth = _se2(heading[index] + rng.normal(0.0, 0.03, size=Q), xyq[:, 0], xyq[:, 1])
+    rel = _se2_compose(_se2_inverse(truth[:-1]), truth[1:])
+    rel = _se2_compose(rel, _se2(rng.normal(0.0, odo_yaw, size=Q - 1), rng.normal(0.0, odo_t, size=Q - 1),
+                                 rng.normal(0.0, odo_t, size=Q - 1)))
+    odom = np.empty((Q, 4), dtype=np.float64)
+    odom[0] = _se2_compose(_se2(1.1, 40.0, -25.0), truth[0])
+    for i in range(Q - 1):
+        odom[i + 1] = _se2_compose(odom[i], rel[i])
+    planted = rng.random((Q, K)) < float(true_frac)
+    near = np.clip(index[:, None] + rng.integers(-2, 3, size=(Q, K)), 0, M - 1)
+    cols = np.where(planted, near, rng.integers(0, M, size=(Q, K)))
+    false_rank = np.cumsum(~planted, axis=1) - 1                               # 0, 1, ... over a query's false candidates
+    aliased = (~planted) & (false_rank < int(alias)) & (rng.random(Q) < float(alias_frac))[:, None]
+    lo, hi = xy.min(0), xy.max(0)
+    wrong = _se2(rng.uniform(-np.pi, np.pi, size=Q), rng.uniform(lo[0], hi[0], size=Q), rng.uniform(lo[1], hi[1], size=Q))
+
+    def noisy(t):
+        return _se2_compose(_se2(rng.normal(0.0, noise_yaw, size=(Q, K)), rng.normal(0.0, noise_t, size=(Q, K)),
+                                 rng.normal(0.0, noise_t, size=(Q, K))), t)
+
+    to_col = _se2_inverse(world[cols])
+    true_T = noisy(_se2_compose(to_col, truth[:, None, :]))
+    fake_T = noisy(_se2_compose(to_col, wrong[:, None, :]))
+    rand_T = _se2(rng.uniform(-np.pi, np.pi, size=(Q, K)), rng.uniform(-30.0, 30.0, size=(Q, K)),
+                  rng.uniform(-30.0, 30.0, size=(Q, K)))
+    T = np.where(planted[..., None], true_T, np.where(aliased[..., None], fake_T, rand_T))
+    return {"map": world, "truth": truth, "odom": odom, "index": index.astype(np.int32), "cols": cols.astype(np.int32),
+            "T": np.ascontiguousarray(T), "planted": planted, "aliased": aliased}
+
+
 def dense_features(centers, labels, num_labels=NUM_LABELS):
     """Packed (centers, labels) -> the reference's dense `B x (3+L) x N` float32
     tensor (sg_net.py:274-298): xyz rows then a one-hot block, all-zero for -1."""
