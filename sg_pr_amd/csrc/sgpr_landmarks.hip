@@ -1,0 +1,510 @@
+// The semantic landmark map (sgpr_landmark_map; include/sgpr_landmarks.h): every node of every scan of
+// a map goes into the map frame, nodes of one label within that label's radius link, and the connected components of
+// the link graph are the landmarks.  sgpr_cluster.hip's scheme for one scan's points, across a whole map: a cell table,
+// a lock-free union-find whose roots are lowest indices, fixed-point integer sums - here in float64, with a radius per
+// label, sessions and spreads.  HBM-bound integer / pointer work, no matrix cores.
+//
+//   lm_transform_kernel   one thread per node: the map point, live or dead; a live node enters the open-addressing cell
+//                         table (key: a hash of (label, ix, iy)) and is pushed on its cell's linked list.
+//   lm_union_kernel       one thread per live node: the lower-indexed nodes on the lists of its 9 neighbouring cells are
+//                         tested with the header's rule and united.  The larger root is hooked under the smaller by a
+//                         CAS, so a component's root is its LOWEST NODE INDEX whatever the execution order.
+//   lm_flatten_kernel     the forest is final: every live node finds its root and adds its count, its three fixed-point
+//                         coordinates and its session bit to the root (integer atomics: any order, same sums).  Each
+//                         workgroup counts its roots and its live nodes.
+//   lm_scan_kernel        one workgroup: exclusive prefix sum of the per-workgroup root counts; d_num.
+//   lm_record_kernel      the id of a root = roots before it = its workgroup's prefix + its rank inside the workgroup;
+//                         records of ids below max_landmarks are written.
+//   lm_spread_kernel      second pass: every live node gets its landmark id and adds its capped squared distance to
+//                         the centre (recomputed from the root's sums: the same expression, the same bits).
+//   lm_finish_kernel      spread of every recorded landmark.
+//
+// TERMINATION.  The cell table has at least 2 G N slots and every key in it belongs to some node, so it is never more
+// than half full: insertion and lookup always reach their key or an empty slot.  The cell lists are complete before
+// the kernel that walks them starts.  The only loop that depends on another workgroup is uf_unite's CAS retry, and a
+// failed CAS means that another thread's CAS succeeded (lock-free: some thread always makes progress, and a root's
+// parent only ever decreases).  Nothing waits on a flag, a counter or a lock.
+//
+// VISIBILITY.  Per-XCD L2s are not coherent with one another and a CU's L1 is never refreshed by other CUs' stores.
+// The forest is rewritten by other CUs while it is read, so it is read and written with agent-scope relaxed atomics
+// (served past L1/L2 where the agent's coherence point is) and hooked with device-scope CAS, as in sgpr_cluster.hip.
+// Everything else is handed from one kernel to the next on one stream.  No floating-point atomics, no inline assembly,
+// plain vector stores.
+//
+// Cells are a linked list per cell; the cell-sorted layout (count, scan, scatter, a wave per cell with the cell in LDS)
+// is not built.
+#include <math.h>
+
+#include <cmath>
+#include <string>
+
+#include "sgpr_internal.hpp"
+#include "sgpr_landmarks.h"
+
+namespace sgpr {
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int LM_THREADS = 256;
+constexpr int LM_SCAN_THREADS = 1024;
+constexpr unsigned long long LM_EMPTY = ~0ull;
+constexpr double LM_FIX = 16777216.0;          // 2^24
+constexpr double LM_LIMIT = 137438953472.0;    // 2^37
+constexpr double LM_D2_CAP = 1048576.0;        // 2^20
+constexpr double LM_MIN_CELL = 0.5;
+
+struct LmWs {
+    double* m;                     // [P][3] map point
+    int* lab;                      // [P] label of a live node, -1 of a dead one
+    int* parent;                   // [P] union-find forest
+    int* next;                     // [P] linked list of the node's cell; after flatten: the node's root
+    int* cnt;                      // [P] members per root
+    int* id;                       // [P] landmark id of a root
+    long long* sum;                // [P][3] fixed-point coordinate sums per root
+    unsigned long long* q;         // [P] fixed-point sum of squared distances per root
+    unsigned long long* sess;      // [P] session mask per root
+    unsigned long long* cell_key;  // [H]
+    int* cell_head;                // [H]
+    int* blk_roots;                // [B] roots per workgroup; after the scan: roots before the workgroup
+    int* blk_live;                 // [B] live nodes per workgroup
+    unsigned long long hmask;      // H - 1 (H a power of two)
+};
+
+struct LmArgs {
+    const float* centers;
+    const int32_t* labels;
+    const double* poses;
+    double* lm_center;
+    int32_t* lm_label;
+    int32_t* lm_count;
+    int32_t* lm_first;
+    unsigned long long* lm_sessions;
+    double* lm_spread;
+    int32_t* node_landmark;
+    int32_t* num;
+    int P, N, n_labels, n_sessions, max_landmarks, B;
+    double tau_z;
+    double radius[SGPR_LANDMARK_MAX_LABELS];
+    int32_t starts[SGPR_SESSION_MAX];
+};
+
+__device__ __forceinline__ unsigned long long lm_mix64(unsigned long long k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
+// Cell width of a label: a hair wider than its radius, and never below LM_MIN_CELL.
+//
+// Two nodes in range are never two cells apart.  Let a >= b be one coordinate of two nodes that link, w the width.
+// The rule gives fl(dx dx) <= fl(r r) up to the roundings of the products and the sum, i.e. |dx| <= r (1 + 2^-50), and
+// dx = fl(a - b), so a - b <= r (1 + 2^-49).  w >= r 1.001 (1 - 2^-52), so (a - b) / w < 1 - 9e-4.  Both quotients are
+// rounded: |a|, |b| <= 2^37 and w >= 0.5 bound them by 2^38 and each rounding error by 2^-53 2^38 = 2^-15, together
+// 6.2e-5.  So fl(a / w) - fl(b / w) < 1, and floor() of two numbers less than 1 apart differs by at most 1 (division
+// by a positive w is monotone, so the difference is not negative either).  |quotient| <= 2^38 fits a long long.
+// A width above the radius only adds candidates; the pair test is the header's, exact.  r = +inf: w = inf, every
+// quotient is +-0, one cell.
+__device__ __forceinline__ double lm_cell_width(double r) { return fmax(r * 1.001, LM_MIN_CELL); }
+__device__ __forceinline__ long long lm_cell_coord(double v, double w) { return (long long)floor(v / w); }
+
+// The key is a HASH of (label, ix, iy), not a packing: 2 x 39 bits of cell coordinate and 6 of label do not fit.  Two
+// cells with one key share a list, and one list may be met twice among the 9 neighbours; the pair test compares the
+// labels and the distance itself and uniting is idempotent, so a collision costs time and never an answer.
+__device__ __forceinline__ unsigned long long lm_cell_key(int label, long long ix, long long iy) {
+    unsigned long long k = lm_mix64((unsigned long long)ix + 0x9e3779b97f4a7c15ull * (unsigned long long)(label + 1));
+    k = lm_mix64(k ^ ((unsigned long long)iy * 0xd6e8feb86659fd93ull));
+    return k == LM_EMPTY ? 0ull : k;
+}
+
+// slot of `key`, inserting it when absent.  Terminates: see TERMINATION above
+__device__ __forceinline__ unsigned long long lm_table_insert(unsigned long long* keys, unsigned long long mask,
+                                                              unsigned long long key) {
+    unsigned long long s = lm_mix64(key) & mask;
+    while (true) {
+        const unsigned long long old = atomicCAS(&keys[s], LM_EMPTY, key);
+        if (old == LM_EMPTY || old == key) return s;
+        s = (s + 1) & mask;
+    }
+}
+// slot of `key`, or LM_EMPTY when absent (the table is complete: built by an earlier kernel)
+__device__ __forceinline__ unsigned long long lm_table_find(const unsigned long long* keys, unsigned long long mask,
+                                                            unsigned long long key) {
+    unsigned long long s = lm_mix64(key) & mask;
+    while (true) {
+        const unsigned long long k = keys[s];
+        if (k == key) return s;
+        if (k == LM_EMPTY) return LM_EMPTY;
+        s = (s + 1) & mask;
+    }
+}
+
+__device__ __forceinline__ int ld_parent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_parent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int uf_find(int* parent, int x) {
+    int p = ld_parent(parent + x);
+    while (p != x) {                       // path halving: only ever replaces a pointer by an ancestor
+        const int gp = ld_parent(parent + p);
+        if (gp != p) st_parent(parent + x, gp);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+__device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
+    while (true) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        if (atomicCAS(&parent[hi], hi, lo) == hi) return;      // hook the larger root under the smaller
+    }
+}
+
+__device__ __forceinline__ bool lm_in_limit(double v) { return isfinite(v) && fabs(v) <= LM_LIMIT; }
+
+__global__ __launch_bounds__(LM_THREADS) void lm_transform_kernel(const LmWs w, const LmArgs a) {
+    const int p = blockIdx.x * LM_THREADS + threadIdx.x;
+    if (p >= a.P) return;
+    const int g = p / a.N;
+    const int l = a.labels[p];
+    const double x = (double)a.centers[3 * (size_t)p], y = (double)a.centers[3 * (size_t)p + 1],
+                 z = (double)a.centers[3 * (size_t)p + 2];
+    const double c = a.poses[4 * (size_t)g], s = a.poses[4 * (size_t)g + 1], X = a.poses[4 * (size_t)g + 2],
+                 Y = a.poses[4 * (size_t)g + 3];
+    const double mx = (c * x - s * y) + X, my = (s * x + c * y) + Y, mz = z;
+    bool live = l >= 0 && l < a.n_labels;
+    const double r = live ? a.radius[l] : 0.0;
+    live = live && r > 0.0 && isfinite(c) && isfinite(s) && isfinite(X) && isfinite(Y) && lm_in_limit(mx) &&
+           lm_in_limit(my) && lm_in_limit(mz);
+    w.m[3 * (size_t)p] = mx;
+    w.m[3 * (size_t)p + 1] = my;
+    w.m[3 * (size_t)p + 2] = mz;
+    w.lab[p] = live ? l : -1;
+    w.parent[p] = p;
+    w.cnt[p] = 0;
+    w.id[p] = -1;
+    w.sum[3 * (size_t)p] = 0;
+    w.sum[3 * (size_t)p + 1] = 0;
+    w.sum[3 * (size_t)p + 2] = 0;
+    w.q[p] = 0ull;
+    w.sess[p] = 0ull;
+    if (!live) {
+        w.next[p] = -1;
+        a.node_landmark[p] = -1;
+        return;
+    }
+    const double cw = lm_cell_width(r);
+    const unsigned long long slot = lm_table_insert(w.cell_key, w.hmask, lm_cell_key(l, lm_cell_coord(mx, cw), lm_cell_coord(my, cw)));
+    w.next[p] = atomicExch(&w.cell_head[slot], p);
+}
+
+__global__ __launch_bounds__(LM_THREADS) void lm_union_kernel(const LmWs w, const LmArgs a) {
+    const int p = blockIdx.x * LM_THREADS + threadIdx.x;
+    if (p >= a.P) return;
+    const int l = w.lab[p];
+    if (l < 0) return;
+    const double r = a.radius[l], r2 = r * r, tau_z = a.tau_z;
+    const double cw = lm_cell_width(r);
+    const double mx = w.m[3 * (size_t)p], my = w.m[3 * (size_t)p + 1], mz = w.m[3 * (size_t)p + 2];
+    const long long ix = lm_cell_coord(mx, cw), iy = lm_cell_coord(my, cw);
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const unsigned long long slot = lm_table_find(w.cell_key, w.hmask, lm_cell_key(l, ix + dx, iy + dy));
+            if (slot == LM_EMPTY) continue;
+            for (int o = w.cell_head[slot]; o >= 0; o = w.next[o]) {
+                if (o >= p || w.lab[o] != l) continue;          // every unordered pair once; (a shared list: see lm_cell_key)
+                const double ex = mx - w.m[3 * (size_t)o], ey = my - w.m[3 * (size_t)o + 1];
+                const double d2 = ex * ex + ey * ey;
+                if (d2 <= r2 && fabs(mz - w.m[3 * (size_t)o + 2]) <= tau_z) uf_unite(w.parent, p, o);
+            }
+        }
+}
+
+// the sum of v over the workgroup, valid in thread 0
+__device__ __forceinline__ int lm_block_sum(int v, int* wsum) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int t = 0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < LM_THREADS / 64; ++i) t += wsum[i];
+    __syncthreads();
+    return t;
+}
+
+__global__ __launch_bounds__(LM_THREADS) void lm_flatten_kernel(const LmWs w, const LmArgs a) {
+    __shared__ int wsum[LM_THREADS / 64];
+    const int p = blockIdx.x * LM_THREADS + threadIdx.x;
+    const bool live = p < a.P && w.lab[p] >= 0;
+    int root = -1;
+    if (live) {
+        root = p;
+        while (true) {                                          // the forest is final: reads past L1
+            const int up = ld_parent(w.parent + root);
+            if (up == root) break;
+            root = up;
+        }
+        w.next[p] = root;                                       // (the cell lists are dead) the node's root
+        const int g = p / a.N;
+        int sess = 0;
+        for (int j = 1; j < a.n_sessions; ++j) sess = a.starts[j] <= g ? j : sess;
+        atomicAdd(&w.cnt[root], 1);
+        for (int k = 0; k < 3; ++k)
+            atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)root + k]),
+                      (unsigned long long)llrint(w.m[3 * (size_t)p + k] * LM_FIX));
+        atomicOr(&w.sess[root], 1ull << sess);
+    }
+    const int roots = lm_block_sum(live && root == p ? 1 : 0, wsum);
+    const int lives = lm_block_sum(live ? 1 : 0, wsum);
+    if (threadIdx.x == 0) {
+        w.blk_roots[blockIdx.x] = roots;
+        w.blk_live[blockIdx.x] = lives;
+    }
+}
+
+__global__ __launch_bounds__(LM_SCAN_THREADS) void lm_scan_kernel(const LmWs w, const LmArgs a) {
+    __shared__ int part[LM_SCAN_THREADS];
+    __shared__ int live_part[LM_SCAN_THREADS];
+    const int t = threadIdx.x;
+    const int seg = (a.B + LM_SCAN_THREADS - 1) / LM_SCAN_THREADS;
+    const int lo = min(t * seg, a.B), hi = min(lo + seg, a.B);
+    int s = 0, lv = 0;
+    for (int i = lo; i < hi; ++i) {
+        s += w.blk_roots[i];
+        lv += w.blk_live[i];
+    }
+    part[t] = s;
+    live_part[t] = lv;
+    __syncthreads();
+    for (int off = 1; off < LM_SCAN_THREADS; off <<= 1) {       // inclusive scan of the segment sums
+        const int u = t >= off ? part[t - off] : 0, v = t >= off ? live_part[t - off] : 0;
+        __syncthreads();
+        part[t] += u;
+        live_part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - s;
+    for (int i = lo; i < hi; ++i) {
+        const int c = w.blk_roots[i];
+        w.blk_roots[i] = run;
+        run += c;
+    }
+    if (t == LM_SCAN_THREADS - 1) {
+        a.num[0] = part[t];
+        a.num[1] = live_part[t];
+    }
+}
+
+__device__ __forceinline__ double lm_center(const LmWs& w, int root, int k, double cnt) {
+    return (double)w.sum[3 * (size_t)root + k] / (cnt * LM_FIX);
+}
+
+__global__ __launch_bounds__(LM_THREADS) void lm_record_kernel(const LmWs w, const LmArgs a) {
+    __shared__ int wcount[LM_THREADS / 64];
+    const int p = blockIdx.x * LM_THREADS + threadIdx.x;
+    const bool root = p < a.P && w.lab[p] >= 0 && w.next[p] == p;
+    const unsigned long long ball = __ballot(root);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wcount[wave] = __popcll(ball);
+    __syncthreads();
+    if (!root) return;
+    int id = w.blk_roots[blockIdx.x] + __popcll(ball & ((1ull << lane) - 1ull));
+    for (int v = 0; v < wave; ++v) id += wcount[v];
+    w.id[p] = id;
+    if (id >= a.max_landmarks) return;
+    const int n = w.cnt[p];
+    const double cnt = (double)n;
+    for (int k = 0; k < 3; ++k) a.lm_center[3 * (size_t)id + k] = lm_center(w, p, k, cnt);
+    a.lm_label[id] = w.lab[p];
+    a.lm_count[id] = n;
+    a.lm_first[id] = p;
+    a.lm_sessions[id] = w.sess[p];
+}
+
+__global__ __launch_bounds__(LM_THREADS) void lm_spread_kernel(const LmWs w, const LmArgs a) {
+    const int p = blockIdx.x * LM_THREADS + threadIdx.x;
+    if (p >= a.P || w.lab[p] < 0) return;
+    const int root = w.next[p];
+    a.node_landmark[p] = w.id[root];
+    const double cnt = (double)w.cnt[root];
+    const double ex = w.m[3 * (size_t)p] - lm_center(w, root, 0, cnt), ey = w.m[3 * (size_t)p + 1] - lm_center(w, root, 1, cnt);
+    const double d2 = ex * ex + ey * ey;
+    atomicAdd(&w.q[root], (unsigned long long)llrint(fmin(d2, LM_D2_CAP) * LM_FIX));
+}
+
+__global__ __launch_bounds__(LM_THREADS) void lm_finish_kernel(const LmWs w, const LmArgs a) {
+    const int p = blockIdx.x * LM_THREADS + threadIdx.x;
+    if (p >= a.P || w.lab[p] < 0 || w.next[p] != p) return;
+    const int id = w.id[p];
+    if (id >= a.max_landmarks) return;
+    a.lm_spread[id] = sqrt((double)w.q[p] / ((double)w.cnt[p] * LM_FIX));
+}
+
+size_t lm_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+unsigned long long lm_table_slots(size_t P) {
+    unsigned long long h = 1024;
+    while (h < 2ull * P) h <<= 1;
+    return h;
+}
+
+size_t lm_ws_bytes(size_t P) {
+    const size_t h = (size_t)lm_table_slots(P), b = (P + LM_THREADS - 1) / LM_THREADS;
+    return lm_align(P * 24) * 2 + lm_align(P * 4) * 5 + lm_align(P * 8) * 2 + lm_align(h * 8) + lm_align(h * 4) +
+           lm_align(b * 4) * 2;
+}
+
+bool lm_size_ok(int G, int N) { return G >= 0 && N >= 0 && (long long)G * (long long)N <= 0x7fffffffll; }
+
+}  // namespace
+}  // namespace sgpr
+
+using namespace sgpr;
+
+extern "C" {
+
+size_t sgpr_landmark_workspace_bytes(int G, int N) {
+    if (!lm_size_ok(G, N) || G == 0 || N == 0) return 0;
+    return lm_ws_bytes((size_t)G * (size_t)N);
+}
+
+int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, int N, const double* d_poses,
+                      const int32_t* h_starts, int n_sessions, const double* h_radius, int n_labels, double tau_z,
+                      int max_landmarks, double* d_lm_center, int32_t* d_lm_label, int32_t* d_lm_count,
+                      int32_t* d_lm_first, uint64_t* d_lm_sessions, double* d_lm_spread, int32_t* d_node_landmark,
+                      int32_t* d_num, void* d_workspace, size_t workspace_bytes, void* stream) {
+    const std::string fn = "sgpr_landmark_map";
+    if (G < 0 || N < 0 || max_landmarks < 0) {
+        set_error(fn + ": " + (G < 0 ? "G " + std::to_string(G) : N < 0 ? "N " + std::to_string(N)
+                                                                         : "max_landmarks " + std::to_string(max_landmarks)) +
+                  " is negative");
+        return SGPR_E_INVALID;
+    }
+    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
+        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
+        return SGPR_E_INVALID;
+    }
+    if (!h_radius) {
+        set_error(fn + ": NULL h_radius");
+        return SGPR_E_INVALID;
+    }
+    for (int l = 0; l < n_labels; ++l)
+        if (!(h_radius[l] >= 0.0)) {
+            set_error(fn + ": radius of label " + std::to_string(l) + " is negative or NaN");
+            return SGPR_E_INVALID;
+        }
+    if (!(tau_z >= 0.0)) {
+        set_error(fn + ": tau_z is negative or NaN");
+        return SGPR_E_INVALID;
+    }
+    // the session table, under the rules of sgpr.h
+    if (n_sessions < 0 || n_sessions > SGPR_SESSION_MAX) {
+        set_error(fn + ": the number of sessions must lie in 0.." + std::to_string(SGPR_SESSION_MAX));
+        return SGPR_E_INVALID;
+    }
+    if ((h_starts == nullptr) != (n_sessions == 0)) {
+        set_error(fn + (h_starts ? ": a" : ": NULL") + " session table with n = " + std::to_string(n_sessions));
+        return SGPR_E_INVALID;
+    }
+    if (n_sessions > 0) {
+        if (h_starts[0] != 0) {
+            set_error(fn + ": the session table does not start at 0");
+            return SGPR_E_INVALID;
+        }
+        for (int j = 1; j < n_sessions; ++j)
+            if (h_starts[j] < h_starts[j - 1]) {
+                set_error(fn + ": the session table has a decreasing entry at " + std::to_string(j));
+                return SGPR_E_INVALID;
+            }
+        if (h_starts[n_sessions - 1] > G) {
+            set_error(fn + ": the session table has an entry past " + std::to_string(G));
+            return SGPR_E_INVALID;
+        }
+    }
+    if (!lm_size_ok(G, N)) {
+        set_error(fn + ": G N = " + std::to_string((long long)G * N) + " exceeds the int32 node index");
+        return SGPR_E_INVALID;
+    }
+    if (G == 0 || N == 0) return SGPR_OK;
+    const bool records = d_lm_center && d_lm_label && d_lm_count && d_lm_first && d_lm_sessions && d_lm_spread;
+    if (!d_centers || !d_labels || !d_poses || (!records && max_landmarks > 0) || !d_node_landmark || !d_num || !d_workspace) {
+        set_error(fn + ": NULL argument");
+        return SGPR_E_INVALID;
+    }
+    const size_t P = (size_t)G * (size_t)N;
+    const size_t need = lm_ws_bytes(P);
+    if (workspace_bytes < need) {
+        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
+        return SGPR_E_INVALID;
+    }
+
+    unsigned char* b = static_cast<unsigned char*>(d_workspace);
+    auto take = [&](size_t bytes) {
+        unsigned char* r = b;
+        b += lm_align(bytes);
+        return r;
+    };
+    LmWs w;
+    const size_t H = (size_t)lm_table_slots(P);
+    const int B = (int)((P + LM_THREADS - 1) / LM_THREADS);
+    w.hmask = H - 1;
+    w.m = reinterpret_cast<double*>(take(P * 24));
+    w.sum = reinterpret_cast<long long*>(take(P * 24));
+    w.lab = reinterpret_cast<int*>(take(P * 4));
+    w.parent = reinterpret_cast<int*>(take(P * 4));
+    w.next = reinterpret_cast<int*>(take(P * 4));
+    w.cnt = reinterpret_cast<int*>(take(P * 4));
+    w.id = reinterpret_cast<int*>(take(P * 4));
+    w.q = reinterpret_cast<unsigned long long*>(take(P * 8));
+    w.sess = reinterpret_cast<unsigned long long*>(take(P * 8));
+    w.cell_key = reinterpret_cast<unsigned long long*>(take(H * 8));
+    w.cell_head = reinterpret_cast<int*>(take(H * 4));
+    w.blk_roots = reinterpret_cast<int*>(take((size_t)B * 4));
+    w.blk_live = reinterpret_cast<int*>(take((size_t)B * 4));
+
+    LmArgs a = {};
+    a.centers = d_centers;
+    a.labels = d_labels;
+    a.poses = d_poses;
+    a.lm_center = d_lm_center;
+    a.lm_label = d_lm_label;
+    a.lm_count = d_lm_count;
+    a.lm_first = d_lm_first;
+    a.lm_sessions = reinterpret_cast<unsigned long long*>(d_lm_sessions);
+    a.lm_spread = d_lm_spread;
+    a.node_landmark = d_node_landmark;
+    a.num = d_num;
+    a.P = (int)P;
+    a.N = N;
+    a.n_labels = n_labels;
+    a.max_landmarks = max_landmarks;
+    a.B = B;
+    a.tau_z = tau_z;
+    for (int l = 0; l < n_labels; ++l) a.radius[l] = h_radius[l];
+    a.n_sessions = n_sessions > 0 ? n_sessions : 1;
+    for (int s = 0; s < a.n_sessions; ++s) a.starts[s] = n_sessions > 0 ? h_starts[s] : 0;
+
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    // cell_key | cell_head: empty keys, list ends (-1)
+    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, lm_align(H * 8) + lm_align(H * 4), s);
+    if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_map: memset");
+    const dim3 grid(B), block(LM_THREADS);
+    hipLaunchKernelGGL(lm_transform_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_union_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_flatten_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_scan_kernel, dim3(1), dim3(LM_SCAN_THREADS), 0, s, w, a);
+    hipLaunchKernelGGL(lm_record_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_spread_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_finish_kernel, grid, block, 0, s, w, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_map: launch");
+    return SGPR_OK;
+}
+
+}  // extern "C"

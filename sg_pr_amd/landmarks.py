@@ -1,0 +1,182 @@
+"""The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h).
+
+The entry points are declared in the fourth public header; this module parses it with _build.parse_header and sets the
+signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import _build, engine, synth
+
+HEADER = os.path.join(_build.REPO, "include", "sgpr_landmarks.h")
+with open(HEADER) as _f:
+    _ABI = _build.parse_header(_f.read())
+_C = _ABI.constants
+
+ABI_SYMBOLS = [name for name, _, _ in _ABI.functions]
+MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
+DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
+DEFAULT_MAX_LANDMARKS = 1 << 22          # the default capacity is G N, capped here; build() re-runs past it
+_CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L float64 matrix alive
+
+_lib = None
+
+
+def load_library():
+    """engine.load_library() with the signatures of include/sgpr_landmarks.h set on it"""
+    global _lib
+    if _lib is None:
+        lib = engine.load_library()
+        for name, restype, argtypes in _ABI.functions:
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise ImportError("%s does not export %s: rebuild it (`python -m sg_pr_amd._build --force`)"
+                                  % (_build.LIB_PATH, name))
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = lib
+    return _lib
+
+
+def workspace_bytes(G, N):
+    return int(load_library().sgpr_landmark_workspace_bytes(int(G), int(N)))
+
+
+def _radius_table(radius):
+    r = np.atleast_1d(np.asarray(DEFAULT_RADIUS if radius is None else radius, dtype=np.float64))
+    if r.ndim != 1:
+        raise ValueError("landmarks: radius is a scalar or one value per label")
+    if r.size == 1:
+        r = np.full(synth.NUM_LABELS, r[0], dtype=np.float64)
+    return np.ascontiguousarray(r)
+
+
+def build_async(centers, labels, poses, starts=None, radius=None, tau_z=DEFAULT_TAU_Z, max_landmarks=None, workspace=None,
+                device=None):
+    """sgpr_landmark_map without reading anything back -> dict of device tensors, asynchronous on the current stream:
+    center f64 [max_landmarks,3], label, count, first i32 [max_landmarks], sessions i64 [max_landmarks] (the bits of the
+    uint64 mask), spread f64 [max_landmarks], node_landmark i32 [G,N], num i32 [2] = (landmarks found, live nodes).
+    Only the first min(num[0], max_landmarks) records are written.  workspace: a uint8 device tensor of at least
+    workspace_bytes(G, N) to reuse (None: one is allocated)."""
+    lib = load_library()
+    if device is None:
+        device = next((t.device for t in (centers, labels, poses) if isinstance(t, torch.Tensor) and t.is_cuda),
+                      torch.device("cuda", torch.cuda.current_device()))
+    lab = engine._on(labels, device, torch.int32)
+    if lab.dim() != 2:
+        raise ValueError("landmarks: labels must be [G, N]")
+    g, n = lab.shape
+    cen = engine._on(centers, device, torch.float32)
+    if cen.numel() != g * n * 3:
+        raise ValueError("landmarks: centers must be [G, N, 3]")
+    x = engine._on(poses, device, torch.float64)
+    if x.numel() != g * 4:
+        raise ValueError("landmarks: poses must hold one planar pose (c, s, x, y) per scan")
+    table = engine._session_table(starts)
+    rad = _radius_table(radius)
+    cap = min(g * n, DEFAULT_MAX_LANDMARKS) if max_landmarks is None else int(max_landmarks)
+    rows = max(cap, 0)
+    out = {"center": torch.empty(rows, 3, dtype=torch.float64, device=device),
+           "label": torch.empty(rows, dtype=torch.int32, device=device),
+           "count": torch.empty(rows, dtype=torch.int32, device=device),
+           "first": torch.empty(rows, dtype=torch.int32, device=device),
+           "sessions": torch.empty(rows, dtype=torch.int64, device=device),
+           "spread": torch.empty(rows, dtype=torch.float64, device=device),
+           "node_landmark": torch.empty(g, n, dtype=torch.int32, device=device),
+           "num": torch.zeros(2, dtype=torch.int32, device=device)}       # (G N == 0: the call writes nothing)
+    need = workspace_bytes(g, n)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_map(
+            engine._ptr(cen), engine._ptr(lab), g, n, engine._ptr(x),
+            None if table is None else table.ctypes.data, 0 if table is None else table.shape[0],
+            rad.ctypes.data, rad.shape[0], float(tau_z), cap, engine._ptr(out["center"]), engine._ptr(out["label"]),
+            engine._ptr(out["count"]), engine._ptr(out["first"]), engine._ptr(out["sessions"]),
+            engine._ptr(out["spread"]), engine._ptr(out["node_landmark"]), engine._ptr(out["num"]),
+            engine._ptr(workspace), workspace.numel(), engine._stream(device)))
+    return out
+
+
+def build(centers, labels, poses, starts=None, radius=None, tau_z=DEFAULT_TAU_Z, max_landmarks=None, workspace=None,
+          device=None):
+    """The landmark map of G scans.  centers f32 [G,N,3], labels i32 [G,N]: the packed node arrays (label -1 =
+    padding); poses [G,4]: planar (c, s, x, y), a scan point into the map frame; starts: the session table of the scans
+    (None: one session); radius: the link radius in metres, a scalar (for every label of synth.NUM_LABELS) or one value
+    per label (0 = the label takes no part); tau_z: the height tolerance.  Nodes of one label within the radius link;
+    a landmark is a connected component, numbered by its lowest node g N + n.
+    -> dict of device tensors trimmed to the landmarks found: center f64 [L,3], label, count, first i32 [L], sessions
+    i64 [L] (bit j = seen by session j), spread f64 [L] (planar RMS distance of the observations to the centre, m),
+    node_landmark i32 [G,N] (-1 = dead node); num_landmarks, live_nodes int.  If max_landmarks (default G N, capped at
+    DEFAULT_MAX_LANDMARKS) was too small the call is repeated once with the reported count."""
+    kw = dict(starts=starts, radius=radius, tau_z=tau_z, workspace=workspace, device=device)
+    out = build_async(centers, labels, poses, max_landmarks=max_landmarks, **kw)
+    found, live = (int(v) for v in out["num"].tolist())
+    if found > out["label"].shape[0]:
+        out = build_async(centers, labels, poses, max_landmarks=found, **kw)
+    res = {k: out[k][:found] for k in ("center", "label", "count", "first", "sessions", "spread")}
+    res["node_landmark"] = out["node_landmark"]
+    res["num_landmarks"], res["live_nodes"] = found, live
+    return res
+
+
+def _popcount64(words):
+    w = torch.as_tensor(words).to(torch.int64)
+    n = torch.zeros_like(w)
+    for b in range(64):
+        n += (w >> b) & 1
+    return n
+
+
+def select(lm, min_count=1, min_sessions=1):
+    """mask bool [L] of the landmarks with at least min_count observations, seen by at least min_sessions sessions"""
+    count = torch.as_tensor(lm["count"])
+    return (count >= int(min_count)) & (_popcount64(lm["sessions"]).to(count.device) >= int(min_sessions))
+
+
+def virtual_scans(lm, poses, sensor_range=50.0, node_num=100, keep=None):
+    """What a scan at each of `poses` [Q,4] (planar, sensor into map) would hold if it saw the landmarks themselves:
+    the kept landmarks (keep: a mask as select makes it; None: all) within sensor_range of the pose (planar), in the
+    sensor frame - inverse(pose) applied to the centre, z unchanged - the nearest node_num of them (ties to the lower
+    landmark id), listed label-ascending (stable), padded with centre 0 / label -1: the layout synth.world_sequence
+    makes and verify_pairs / embed read.  -> (centers f32 [Q,node_num,3], labels i32 [Q,node_num]) on lm's device."""
+    center = torch.as_tensor(lm["center"])
+    dev = center.device
+    center = center.to(torch.float64).reshape(-1, 3)
+    label = torch.as_tensor(lm["label"]).to(device=dev, dtype=torch.int64).reshape(-1)
+    if keep is not None:
+        idx = torch.nonzero(torch.as_tensor(keep).to(device=dev, dtype=torch.bool).reshape(-1)).reshape(-1)
+        center, label = center[idx], label[idx]                 # (ascending: ties still go to the lower id)
+    X = engine._on(poses, dev, torch.float64).reshape(-1, 4)
+    q, n_lm, nn = X.shape[0], center.shape[0], int(node_num)
+    out_c = torch.zeros(q, nn, 3, dtype=torch.float32, device=dev)
+    out_l = torch.full((q, nn), -1, dtype=torch.int32, device=dev)
+    if q == 0 or n_lm == 0 or nn == 0:
+        return out_c, out_l
+    k = min(nn, n_lm)
+    step = max(1, _CHUNK_BYTES // (8 * n_lm))
+    r2 = float(sensor_range) * float(sensor_range)
+    big = 1 << 20
+    for lo in range(0, q, step):
+        P = X[lo:lo + step]
+        dx = center[None, :, 0] - P[:, None, 2]
+        dy = center[None, :, 1] - P[:, None, 3]
+        d2 = dx * dx + dy * dy
+        d2 = torch.where(d2 <= r2, d2, torch.full_like(d2, float("inf")))
+        # nearest first, ties to the lower id: a stable sort of the distances
+        dist, near = torch.sort(d2, dim=1, stable=True)
+        dist, near = dist[:, :k], near[:, :k]
+        seen = torch.isfinite(dist)
+        lab = torch.where(seen, label[near], torch.full_like(near, big))
+        order = torch.argsort(lab, dim=1, stable=True)          # label-ascending, unseen last
+        near, seen, lab = near.gather(1, order), seen.gather(1, order), lab.gather(1, order)
+        ex, ey = dx.gather(1, near), dy.gather(1, near)
+        c, s = P[:, None, 0], P[:, None, 1]
+        pts = torch.stack((c * ex + s * ey, c * ey - s * ex, center[:, 2][near]), dim=-1)     # R^T (centre - t)
+        out_c[lo:lo + step, :k] = torch.where(seen[..., None], pts, torch.zeros_like(pts)).to(torch.float32)
+        out_l[lo:lo + step, :k] = torch.where(seen, lab, torch.full_like(lab, -1)).to(torch.int32)
+    return out_c, out_l

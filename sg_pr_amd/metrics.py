@@ -532,3 +532,27 @@ def localization_errors(pose, truth):
     some = bool(np.isfinite(trans).any())
     return {"trans_m": trans, "yaw_deg": yaw, "median_trans_m": float(np.nanmedian(trans)) if some else float("nan"),
             "median_yaw_deg": float(np.nanmedian(yaw)) if some else float("nan")}
+
+
+def map_sharpness(lm, min_count=2):
+    """A map-quality number that needs no ground truth: how tightly the observations of the landmarks
+    of landmarks.build / SG.landmark_map sit on them.  lm: its dict ("count", "spread", "sessions").
+    -> dict: sharpness = sqrt(sum count spread^2 / sum count) over the landmarks with count >= min_count, in metres (NaN
+    without one); landmarks = how many those are; shared = the share of them seen by at least 2 sessions; single = the
+    share of ALL landmarks with one observation.  Drift smears the observations of an object (sharpness rises) until
+    they no longer link and the object splits into one landmark per session (shared falls, the count rises)."""
+    def host(t):
+        return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t).reshape(-1)
+    count = host(lm["count"]).astype(np.int64)
+    spread = host(lm["spread"]).astype(np.float64)
+    words = host(lm["sessions"]).astype(np.int64).view(np.uint64)
+    seen_by = np.zeros(words.shape, dtype=np.int64)
+    for b in range(64):
+        seen_by += ((words >> np.uint64(b)) & np.uint64(1)).astype(np.int64)
+    big = count >= int(min_count)
+    n = int(big.sum())
+    w = count[big].astype(np.float64)
+    return {"sharpness": float(np.sqrt(np.sum(w * spread[big] ** 2) / np.sum(w))) if n else float("nan"),
+            "landmarks": n,
+            "shared": float(np.mean(seen_by[big] >= 2)) if n else float("nan"),
+            "single": float(np.mean(count == 1)) if count.size else float("nan")}

@@ -71,6 +71,13 @@ localised with a support of at least S.  `<seq>_localize.npz` holds pose [M,4], 
 accept, trans_m, yaw_deg, the records that went in (indices, refined, verify_flags, verify_accept) and the parameters;
 printed are the share localised and the median and 95th-percentile translation and yaw error, and beside them the same
 numbers for the best verified candidate taken alone.
+With --landmarks [--lm-radius R] [--lm-tau-z Z] [--lm-min-sessions S] the nodes of every scan are fused into a landmark
+map (SG.landmark_map, landmarks.build) on the poses the run ends with - the optimised ones after
+--optimize, the sequence's own otherwise - with the sessions of --consistent --sessions N.  `<seq>_landmarks.npz` holds
+center, label, count, first, sessions, spread per landmark, node_landmark [M,N], keep (seen by at least S sessions), the
+poses and the parameters; printed are the landmarks with two or more observations, their sharpness, the share seen by
+two or more sessions and the share of single observations (metrics.map_sharpness), and after --optimize the same four
+on the poses before optimisation.
 """
 import argparse
 import math
@@ -412,6 +419,15 @@ def main(argv=None):
                     help="with --localize: translation tolerance of two hypotheses, metres")
     ap.add_argument("--loc-max-yaw-deg", type=float, default=math.degrees(0.1), metavar="D",
                     help="with --localize: yaw tolerance of two hypotheses, degrees")
+    ap.add_argument("--landmarks", action="store_true",
+                    help="fuse the nodes of every scan into a landmark map (DESIGN.md §27) on the poses the run ends "
+                         "with - the optimised ones after --optimize - and write <seq>_landmarks.npz")
+    ap.add_argument("--lm-radius", type=float, default=0.75, metavar="R",
+                    help="with --landmarks: nodes of one label within R metres of one another are one landmark")
+    ap.add_argument("--lm-tau-z", type=float, default=0.75, metavar="Z",
+                    help="with --landmarks: ... and within Z metres in height")
+    ap.add_argument("--lm-min-sessions", type=int, default=1, metavar="S",
+                    help="with --landmarks: report the landmarks seen by at least S sessions as kept (1..64)")
     ap.add_argument("--max-trans", type=float, default=1.0, metavar="M",
                     help="with --consistent: translation tolerance of a pair of closures, metres")
     ap.add_argument("--max-yaw-deg", type=float, default=math.degrees(0.06), metavar="D",
@@ -444,6 +460,8 @@ def main(argv=None):
         ap.error("--save-poses needs --optimize")
     if opt.consistent and (opt.max_trans < 0 or opt.lever_gain < 0 or not 0 <= opt.max_yaw_deg <= 180):
         ap.error("--max-trans and --lever-gain must be >= 0, --max-yaw-deg in 0..180")
+    if opt.landmarks and not (opt.lm_radius > 0 and opt.lm_tau_z >= 0 and 1 <= opt.lm_min_sessions <= _engine.SESSION_MAX):
+        ap.error("--lm-radius must be > 0, --lm-tau-z >= 0, --lm-min-sessions in 1..%d" % _engine.SESSION_MAX)
     if opt.localize and not opt.verify:
         ap.error("--localize needs --verify")
     from .localize import MAX_LEN as loc_max_len
@@ -537,6 +555,19 @@ def main(argv=None):
             if opt.save_poses is not None:
                 with open(opt.save_poses, "wb") as f:
                     np.save(f, out)
+        if opt.landmarks:
+            starts = creport["session_starts"] if opt.consistent else None
+            mreport = landmark_lists(trainer.model, seq, out if opt.optimize else None, sessions=starts,
+                                     before=opt.optimize, radius=opt.lm_radius, tau_z=opt.lm_tau_z,
+                                     min_sessions=opt.lm_min_sessions)
+            np.savez(os.path.join(args.output_path, sequence + "_landmarks.npz"), **mreport)
+            line = "landmarks %d sharpness %.4f m shared %.4f single %.4f" % tuple(
+                mreport[n] for n in ("landmarks", "sharpness", "shared", "single"))
+            if opt.optimize:
+                line += " (before optimisation: landmarks %d sharpness %.4f m shared %.4f single %.4f)" % tuple(
+                    mreport["before_" + n] for n in ("landmarks", "sharpness", "shared", "single"))
+            print("sequence", sequence, "landmark map of", int(mreport["live_nodes"]), "nodes:", line + ",",
+                  int(mreport["keep"].sum()), "seen by >= %d sessions" % opt.lm_min_sessions)
         if opt.localize:
             lreport = localize_lists(trainer.model, seq, vals, idx, opt.min_inliers, seq_len=opt.loc_len,
                                      min_support=opt.min_support, max_trans=opt.loc_max_trans,
@@ -769,6 +800,29 @@ def localize_lists(model, seq, values, indices, min_inliers, seq_len=1, min_supp
     out.update({"indices": idx_h, "refined": refined, "verify_flags": ver["flags"].cpu().numpy(),
                 "verify_accept": ver["accept"].cpu().numpy(), "seq_len": np.int64(seq_len),
                 "min_support": np.int64(min_support), "max_trans": np.float64(max_trans), "max_yaw": np.float64(max_yaw)})
+    return out
+
+
+def landmark_lists(model, seq, poses=None, sessions=None, before=False, radius=0.75, tau_z=0.75, min_sessions=1):
+    """The landmark map of `seq` (SG.landmark_map) on planar `poses` [M,4] - None: the sequence's own - with `sessions`
+    as the session table of its frames (None: one session).  before: also the figures of the map on the sequence's own
+    poses, to set an optimised map against.
+    -> dict of numpy arrays: center, label, count, first, sessions, spread per landmark, node_landmark [M,N], keep (the
+    landmarks seen by at least min_sessions sessions), live_nodes, poses, radius, tau_z, min_sessions, the four figures of
+    metrics.map_sharpness (landmarks, sharpness, shared, single) and, with before, the same four with the prefix before_."""
+    from . import landmarks as _landmarks
+    own = metrics.planar_odometry(seq.poses)
+    X = own if poses is None else np.asarray(poses, dtype=np.float64).reshape(-1, 4)
+    lm = model.landmark_map(seq.centers, seq.labels, X, sessions=sessions, radius=radius, tau_z=tau_z)
+    out = {name: lm[name].cpu().numpy() for name in ("center", "label", "count", "first", "sessions", "spread",
+                                                     "node_landmark")}
+    out["keep"] = _landmarks.select(lm, min_sessions=min_sessions).cpu().numpy()
+    out.update({"live_nodes": np.int64(lm["live_nodes"]), "poses": X, "radius": np.float64(radius),
+                "tau_z": np.float64(tau_z), "min_sessions": np.int64(min_sessions)})
+    out.update(metrics.map_sharpness(lm))
+    if before:
+        first = model.landmark_map(seq.centers, seq.labels, own, sessions=sessions, radius=radius, tau_z=tau_z)
+        out.update({"before_" + k: v for k, v in metrics.map_sharpness(first).items()})
     return out
 
 

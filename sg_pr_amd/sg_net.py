@@ -355,6 +355,18 @@ class SG(torch.nn.Module):
                                   seq_len=int(seq_len), max_trans=max_trans, max_yaw=max_yaw, device=dev,
                                   min_support=int(min_support))
 
+    def landmark_map(self, centers, labels, poses, sessions=None, **kw):
+        """The semantic landmark map (landmarks.build): the nodes of every scan of the map, put into the
+        map frame by the scan's pose and fused - nodes of one label within a radius of one another are one landmark.
+        centers [M,N,3], labels [M,N]: the packed node arrays of the map scans; poses: KITTI rows [M,12] or planar
+        [M,4], e.g. what optimize_map returned; sessions: the session table of the scans (None: one session).
+        kw: radius, tau_z, max_landmarks, workspace of landmarks.build.
+        -> its dict: center, label, count, first, sessions, spread per landmark, node_landmark [M,N], num_landmarks,
+        live_nodes."""
+        from . import landmarks as _landmarks
+        x = poses if isinstance(poses, torch.Tensor) and poses.dim() == 2 and poses.shape[1] == 4 else _planar(poses)
+        return _landmarks.build(centers, labels, x, starts=sessions, device=self.engine().device, **kw)
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming

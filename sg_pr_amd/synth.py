@@ -394,3 +394,81 @@ def labelled_scan(seed=0, scale=1.0):
     perm = rng.permutation(len(labels))
     points = np.concatenate((xyz, rng.random((len(labels), 1))), axis=1).astype(np.float32)[perm]
     return np.ascontiguousarray(points), np.ascontiguousarray(labels[perm])
+
+
+def landmark_world(seed, scans=100, sessions=3, transient_frac=0.15, closures=120, node_num=100, sensor_range=50.0,
+                   center_noise=0.15, dropout=0.12, density=0.0062, region=60.0, mix_alpha=3.0, odo_yaw=0.004, odo_t=0.03):
+    """One world seen by several drives, with the identity of every node kept: for the landmark map.
+
+    world_sequence's world and rendering (landmarks uniform over the trajectories' bounding box + sensor_range, a label
+    mix per region, heights in [-2, 1]; a scan sees the landmarks within sensor_range in its sensor frame, each dropped
+    with probability `dropout` and jittered by N(0, center_noise) m, the nearest node_num - 40 kept, listed
+    label-ascending), driven `sessions` times along closure_world's trajectory (1 m per scan) with drift_world's jitter
+    of N(0, 0.5) m and N(0, 0.03) rad per scan.  A share `transient_frac` of the landmarks exists during ONE drive only
+    (a parked car).  The odometry of a drive is integrated from its true relative motions perturbed by N(0, odo_yaw) rad
+    and N(0, odo_t) m in a frame of its own (drive d: rotated by 1.1 d rad, shifted by (40 d, -25 d)), as in drift_world.
+    True closures join a scan of one drive to a scan within +-2 indices of another drive.
+    -> dict: centers f32 [M,N,3], labels i32 [M,N] (M = sessions * scans, -1 = padding); truth, odom f64 [M,4] planar
+    poses (c, s, x, y), a scan point into the map frame; starts i32 [sessions]; node_id i32 [M,N], the true landmark of
+    every node (-1 = padding); transient_session i32 [landmarks], the one drive a transient exists in (-1 = permanent);
+    land_xy f64 [landmarks,2], land_label i32 [landmarks]; rows, cols i32 [closures].  numpy only."""
+    rng = np.random.default_rng(seed + 67867967)
+    S, D, C = int(scans), int(sessions), int(closures)
+    heading, xy = _random_walk(rng, S)
+    drives = []
+    for d in range(D):
+        xyd = xy + rng.normal(0.0, 0.5, size=(S, 2))
+        drives.append((heading + rng.normal(0.0, 0.03, size=S), xyd))
+    all_xy = np.concatenate([x for _, x in drives])
+    lo, hi = all_xy.min(0) - sensor_range, all_xy.max(0) + sensor_range
+    n_land = max(int(density * float(np.prod(hi - lo))), 1)
+    land_xy = rng.uniform(lo, hi, size=(n_land, 2))
+    land_h = rng.uniform(-2.0, 1.0, size=n_land)
+    reg = np.floor((land_xy - lo) / region).astype(np.int64)
+    nreg = reg.max(0) + 1
+    mix = rng.dirichlet(_KITTI_LABEL_P * mix_alpha + 1e-3, size=int(nreg[0] * nreg[1]))
+    cum = np.cumsum(mix[reg[:, 0] * nreg[1] + reg[:, 1]], axis=1)
+    land_lab = np.minimum((rng.random(n_land)[:, None] > cum).sum(1), NUM_LABELS - 1)
+    transient = np.where(rng.random(n_land) < float(transient_frac), rng.integers(0, max(D, 1), size=n_land), -1)
+    max_real = max(node_num - 40, 1)
+    M = D * S
+    centers = np.zeros((M, node_num, 3), dtype=np.float32)
+    labels = -np.ones((M, node_num), dtype=np.int32)
+    node_id = -np.ones((M, node_num), dtype=np.int32)
+    truth, odom = [], []
+    for d, (hd, xyd) in enumerate(drives):
+        exists = (transient < 0) | (transient == d)
+        for t in range(S):
+            dl = land_xy - xyd[t]
+            r2 = (dl * dl).sum(1)
+            seen = np.flatnonzero((r2 <= sensor_range * sensor_range) & exists)
+            seen = seen[rng.random(seen.size) >= dropout]
+            if seen.size > max_real:
+                seen = seen[np.argsort(r2[seen], kind="stable")[:max_real]]
+            c, s = np.cos(hd[t]), np.sin(hd[t])
+            fwd = dl[seen, 0] * c + dl[seen, 1] * s
+            left = -dl[seen, 0] * s + dl[seen, 1] * c
+            pts = np.stack([fwd, left, land_h[seen]], axis=1) + rng.normal(0.0, center_noise, size=(seen.size, 3))
+            order = np.argsort(land_lab[seen], kind="stable")
+            n, g = seen.size, d * S + t
+            centers[g, :n] = pts[order]
+            labels[g, :n] = land_lab[seen][order]
+            node_id[g, :n] = seen[order]
+        Xt = _se2(hd, xyd[:, 0], xyd[:, 1])
+        rel = _se2_compose(_se2_inverse(Xt[:-1]), Xt[1:])
+        rel = _se2_compose(rel, _se2(rng.normal(0.0, odo_yaw, size=S - 1), rng.normal(0.0, odo_t, size=S - 1),
+                                     rng.normal(0.0, odo_t, size=S - 1)))
+        Xo = np.empty((S, 4), dtype=np.float64)
+        Xo[0] = _se2_compose(_se2(1.1 * d, 40.0 * d, -25.0 * d), Xt[0])
+        for k in range(S - 1):
+            Xo[k + 1] = _se2_compose(Xo[k], rel[k])
+        truth.append(Xt)
+        odom.append(Xo)
+    a = rng.integers(0, D, size=C)
+    b = (a + rng.integers(1, max(D, 2), size=C)) % D if D > 1 else a
+    i = rng.integers(0, S, size=C)
+    j = np.clip(i + rng.integers(-2, 3, size=C), 0, S - 1)
+    return {"centers": centers, "labels": labels, "truth": np.concatenate(truth), "odom": np.concatenate(odom),
+            "starts": (np.arange(D) * S).astype(np.int32), "node_id": node_id,
+            "transient_session": transient.astype(np.int32), "land_xy": land_xy, "land_label": land_lab.astype(np.int32),
+            "rows": (a * S + i).astype(np.int32), "cols": (b * S + j).astype(np.int32)}
