@@ -1,6 +1,6 @@
 """Build libsgpr_hip.so (the C-ABI in include/sgpr.h) for gfx950 with hipcc, in-tree.
 
-Every HIP source is compiled to its own object (in parallel) and the objects are linked into
+Every HIP source is compiled to its own object (up to MAX_COMPILERS at once) and the objects are linked into
 sg_pr_amd/lib/libsgpr_hip.so.  Staleness is decided by CONTENT, never by timestamps or by where the code runs: the
 sha256 of every source, header and the compiler flags is stored next to each object and next to the library
 (`*.srchash`); an artefact is reused only while its recorded hash equals the hash of what is on disk now.
@@ -26,8 +26,10 @@ SOURCES = ["sgpr_embed.hip", "sgpr_score.hip", "sgpr_metrics.hip", "sgpr_modules
            "sgpr_seq.hip", "sgpr_peak.hip", "sgpr_verify.hip", "sgpr_consistency.hip", "sgpr_api.hip", "sgpr_posegraph.hip",
            "sgpr_localize.hip", "sgpr_landmarks.hip"]
 HEADERS = [os.path.join(REPO, "include", "sgpr.h"), os.path.join(CSRC, "sgpr_internal.hpp"),
-           os.path.join(CSRC, "sgpr_model.hpp"), os.path.join(REPO, "include", "sgpr_localize.h"),
-           os.path.join(REPO, "include", "sgpr_landmarks.h"), os.path.join(REPO, "include", "sgpr_posegraph.h")]
+           os.path.join(CSRC, "sgpr_model.hpp"), os.path.join(CSRC, "sgpr_map.hpp"),
+           os.path.join(REPO, "include", "sgpr_localize.h"), os.path.join(REPO, "include", "sgpr_landmarks.h"),
+           os.path.join(REPO, "include", "sgpr_posegraph.h")]
+MAX_COMPILERS = 16     # compilers at once: one per source, up to this many
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed"]
 
 
@@ -153,7 +155,7 @@ def build_library(force=False, verbose=False):
         return obj
 
     total = source_hash()
-    with concurrent.futures.ThreadPoolExecutor(max_workers=len(_sources())) as pool:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(_sources()), MAX_COMPILERS)) as pool:
         objs = list(pool.map(compile_one, _sources()))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB_PATH + ".tmp"]
     if verbose:

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "sgpr_internal.hpp"
+#include "sgpr_map.hpp"
 
 namespace sgpr {
 
@@ -1318,33 +1319,6 @@ static bool session_paths_ok(const char* fn, const int32_t* h_offsets, int n_pat
         return false;
     }
     return seq_paths_ok(fn, h_offsets, n_paths, L);
-}
-
-static bool session_table_ok(const char* fn, const char* which, const int32_t* starts, int n, int limit) {
-    if (n < 0 || n > SGPR_SESSION_MAX) {
-        set_error(std::string(fn) + ": the number of " + which + " sessions must lie in 0.." +
-                  std::to_string(SGPR_SESSION_MAX));
-        return false;
-    }
-    if (!starts || n == 0) {
-        if (!starts && n == 0) return true;               // one session
-        set_error(std::string(fn) + (starts ? ": a " : ": NULL ") + which + " session table with n = " + std::to_string(n));
-        return false;
-    }
-    if (starts[0] != 0) {
-        set_error(std::string(fn) + ": the " + which + " session table does not start at 0");
-        return false;
-    }
-    for (int j = 1; j < n; ++j)
-        if (starts[j] < starts[j - 1]) {
-            set_error(std::string(fn) + ": the " + which + " session table has a decreasing entry at " + std::to_string(j));
-            return false;
-        }
-    if (starts[n - 1] > limit) {
-        set_error(std::string(fn) + ": the " + which + " session table has an entry past " + std::to_string(limit));
-        return false;
-    }
-    return true;
 }
 
 int sgpr_session_filter(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int ctx, int L, int flags,

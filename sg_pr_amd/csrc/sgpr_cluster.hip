@@ -20,13 +20,13 @@
 #include <math.h>
 
 #include "sgpr_internal.hpp"
+#include "sgpr_map.hpp"
 
 namespace sgpr {
 
 constexpr int CL_THREADS = 256;
 constexpr int CL_MAX_CAND = 8192;          // clusters that may qualify as nodes in one scan
-constexpr int CL_INST_SLOTS = 1 << 16;     // (class, instance) hash table
-constexpr unsigned long long CL_EMPTY = ~0ull;
+constexpr unsigned CL_INST_SLOTS = 1u << 16;   // (class, instance) hash table
 constexpr int CL_NCLASS = 20;
 constexpr int CL_MAX_CLUSTER = 50000;      // gen_label_graph.py:305
 
@@ -108,64 +108,11 @@ struct ClusterWs {
     unsigned H;                    // cell table slots (power of two)
 };
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
 __device__ __forceinline__ unsigned long long cell_key_of(int c, int ix, int iy, int iz) {
     // 19 bits per axis (offset binary), 5 bits of class
     return ((unsigned long long)c << 57) | ((unsigned long long)((ix + (1 << 18)) & 0x7ffff) << 38) |
            ((unsigned long long)((iy + (1 << 18)) & 0x7ffff) << 19) | (unsigned long long)((iz + (1 << 18)) & 0x7ffff);
 }
-// slot of `key`, inserting it when absent
-__device__ __forceinline__ unsigned table_insert(unsigned long long* keys, unsigned mask, unsigned long long key) {
-    unsigned s = (unsigned)mix64(key) & mask;
-    while (true) {
-        const unsigned long long old = atomicCAS(&keys[s], CL_EMPTY, key);
-        if (old == CL_EMPTY || old == key) return s;
-        s = (s + 1) & mask;
-    }
-}
-// slot of `key`, or ~0u when absent (table complete: built by an earlier kernel)
-__device__ __forceinline__ unsigned table_find(const unsigned long long* keys, unsigned mask, unsigned long long key) {
-    unsigned s = (unsigned)mix64(key) & mask;
-    while (true) {
-        const unsigned long long k = keys[s];
-        if (k == key) return s;
-        if (k == CL_EMPTY) return ~0u;
-        s = (s + 1) & mask;
-    }
-}
-
-// agent-scope relaxed accesses: the forest is rewritten by other CUs while it is read (a CU's L1 is never refreshed by
-// other CUs' stores), so its loads must be served by L2
-__device__ __forceinline__ int ld_parent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_parent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(int* parent, int x) {
-    int p = ld_parent(parent + x);
-    while (p != x) {                       // path halving: only ever replaces a pointer by an ancestor
-        const int gp = ld_parent(parent + p);
-        if (gp != p) st_parent(parent + x, gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-__device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        const int hi = a > b ? a : b, lo = a > b ? b : a;
-        if (atomicCAS(&parent[hi], hi, lo) == hi) return;      // hook the larger root under the smaller
-    }
-}
-
 // cells are a hair wider than the tolerance, so that two points in range can never end up two cells apart through the
 // rounding of the division
 __device__ __forceinline__ int cell_coord(float v, float tol) { return (int)floorf(v / (tol * 1.0001f)); }
@@ -251,12 +198,7 @@ __global__ __launch_bounds__(CL_THREADS) void cluster_flatten_kernel(ClusterWs w
     const int p = blockIdx.x * CL_THREADS + threadIdx.x;
     if (p >= P) return;
     if (class_mode(w.cls[p]) != 2) return;
-    int r = p;
-    while (true) {                                              // the forest is final: plain reads through L2
-        const int up = ld_parent(w.parent + r);
-        if (up == r) break;
-        r = up;
-    }
+    const int r = uf_root_final(w.parent, p);
     w.next[p] = r;                                              // (the cell lists are dead) the point's root
     atomicAdd(&w.size[r], 1);
     const float* q = pts + (size_t)p * stride;
@@ -393,14 +335,6 @@ int launch_graph_edges(const float* pts, int stride, const int32_t* point_node, 
     return SGPR_OK;
 }
 
-static unsigned table_slots(int P) {
-    unsigned h = 1024;
-    while (h < 2u * (unsigned)P) h <<= 1;
-    return h;
-}
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 size_t cluster_ws_bytes(int P) {
     const size_t p = (size_t)P, h = table_slots(P);
     return align256(p * 4) * 6 + align256(p * 24) + align256(h * 8) + align256(h * 4) + align256((size_t)CL_INST_SLOTS * 8) +
@@ -410,29 +344,24 @@ size_t cluster_ws_bytes(int P) {
 int launch_cluster_scan(const float* pts, int stride, const uint32_t* label, int P, int max_nodes, double* centers,
                         int32_t* node_labels, int32_t* node_sizes, int32_t* point_node, int32_t* num_nodes, void* ws,
                         hipStream_t stream) {
-    unsigned char* b = static_cast<unsigned char*>(ws);
-    auto take = [&](size_t bytes) {
-        unsigned char* r = b;
-        b += align256(bytes);
-        return r;
-    };
+    Carver ws_at{static_cast<unsigned char*>(ws)};
     ClusterWs w;
     const size_t p = (size_t)P;
-    w.H = table_slots(P);
-    w.cls = reinterpret_cast<int*>(take(p * 4));
-    w.parent = reinterpret_cast<int*>(take(p * 4));
-    w.next = reinterpret_cast<int*>(take(p * 4));
-    w.size = reinterpret_cast<int*>(take(p * 4));
-    w.node_of_root = reinterpret_cast<int*>(take(p * 4));
-    w.nonfinite = reinterpret_cast<int*>(take(p * 4));
-    w.sum = reinterpret_cast<long long*>(take(p * 24));
-    w.cell_key = reinterpret_cast<unsigned long long*>(take((size_t)w.H * 8));
-    w.cell_head = reinterpret_cast<int*>(take((size_t)w.H * 4));
-    w.inst_key = reinterpret_cast<unsigned long long*>(take((size_t)CL_INST_SLOTS * 8));
-    w.inst_min = reinterpret_cast<int*>(take((size_t)CL_INST_SLOTS * 4));
-    w.class_inst = reinterpret_cast<int*>(take(256));
-    w.count = reinterpret_cast<int*>(take(256));
-    w.cand = reinterpret_cast<int4*>(take((size_t)CL_MAX_CAND * sizeof(int4)));
+    w.H = (unsigned)table_slots(p);
+    w.cls = ws_at.take<int>(p);
+    w.parent = ws_at.take<int>(p);
+    w.next = ws_at.take<int>(p);
+    w.size = ws_at.take<int>(p);
+    w.node_of_root = ws_at.take<int>(p);
+    w.nonfinite = ws_at.take<int>(p);
+    w.sum = ws_at.take<long long>(3 * p);
+    w.cell_key = ws_at.take<unsigned long long>(w.H);
+    w.cell_head = ws_at.take<int>(w.H);
+    w.inst_key = ws_at.take<unsigned long long>(CL_INST_SLOTS);
+    w.inst_min = ws_at.take<int>(CL_INST_SLOTS);
+    w.class_inst = ws_at.take<int>(64);            // (256 bytes each: one memset clears the flags and the counters)
+    w.count = ws_at.take<int>(64);
+    w.cand = ws_at.take<int4>(CL_MAX_CAND);
     hipError_t e = hipMemsetAsync(w.node_of_root, 0xff, p * 4, stream);
     // cell_key | cell_head: empty keys, list ends (-1)
     if (e == hipSuccess) e = hipMemsetAsync(w.cell_key, 0xff, align256((size_t)w.H * 8) + align256((size_t)w.H * 4), stream);

@@ -15,6 +15,7 @@
 // correctly rounded one), so the bit matrix is reproducible bit for bit (tests/consistency_ref.py).  Plain vector
 // stores only; no atomics on global memory.
 #include "sgpr_internal.hpp"
+#include "sgpr_map.hpp"
 
 namespace sgpr {
 
@@ -26,47 +27,6 @@ constexpr int CC_T = 256;        // threads of the prep and pair kernels
 constexpr int CC_ROWS = 8;       // rows of the bit matrix per workgroup of the pair kernel
 constexpr int CS_T = 1024;       // threads of the clique kernel
 constexpr int CS_WAVES = CS_T / 64;
-
-struct Se2 {
-    double c, s, x, y;
-};
-
-__device__ __forceinline__ Se2 se2_compose(const Se2& a, const Se2& b) {
-    Se2 r;
-    r.c = a.c * b.c - a.s * b.s;
-    r.s = a.s * b.c + a.c * b.s;
-    r.x = (a.c * b.x - a.s * b.y) + a.x;
-    r.y = (a.s * b.x + a.c * b.y) + a.y;
-    return r;
-}
-
-__device__ __forceinline__ Se2 se2_inverse(const Se2& a) {
-    Se2 r;
-    r.c = a.c;
-    r.s = -a.s;
-    r.x = -(a.c * a.x + a.s * a.y);
-    r.y = a.s * a.x - a.c * a.y;
-    return r;
-}
-
-__device__ __forceinline__ Se2 se2_load(const double* p) {
-    const double2 lo = *reinterpret_cast<const double2*>(p), hi = *reinterpret_cast<const double2*>(p + 2);
-    Se2 r;
-    r.c = lo.x;
-    r.s = lo.y;
-    r.x = hi.x;
-    r.y = hi.y;
-    return r;
-}
-
-__device__ __forceinline__ void se2_store(double* p, const Se2& v) {
-    *reinterpret_cast<double2*>(p) = make_double2(v.c, v.s);
-    *reinterpret_cast<double2*>(p + 2) = make_double2(v.x, v.y);
-}
-
-__device__ __forceinline__ bool se2_finite(const Se2& v) {
-    return isfinite(v.c) && isfinite(v.s) && isfinite(v.x) && isfinite(v.y);
-}
 
 // the workspace of sgpr_closure_consistency: members i32 [C] first (what the header promises), then G, H, R f64 [C][4]
 struct CcWs {

@@ -19,15 +19,9 @@
 //                         the centre (recomputed from the root's sums: the same expression, the same bits).
 //   lm_finish_kernel      spread of every recorded landmark.
 //
-// TERMINATION.  The cell table has at least 2 G N slots and every key in it belongs to some node, so it is never more
-// than half full: insertion and lookup always reach their key or an empty slot.  The cell lists are complete before
-// the kernel that walks them starts.  The only loop that depends on another workgroup is uf_unite's CAS retry, and a
-// failed CAS means that another thread's CAS succeeded (lock-free: some thread always makes progress, and a root's
-// parent only ever decreases).  Nothing waits on a flag, a counter or a lock.
-//
-// VISIBILITY.  Per-XCD L2s are not coherent with one another and a CU's L1 is never refreshed by other CUs' stores.
-// The forest is rewritten by other CUs while it is read, so it is read and written with agent-scope relaxed atomics
-// (served past L1/L2 where the agent's coherence point is) and hooked with device-scope CAS, as in sgpr_cluster.hip.
+// The cell table and the union-find are sgpr_map.hpp's, with their SIZING, VISIBILITY and TERMINATION arguments: the
+// table has table_slots(G N) slots and every key in it belongs to some node; the cell lists are complete before the
+// kernel that walks them starts; the forest is the only memory another workgroup rewrites while it is read.
 // Everything else is handed from one kernel to the next on one stream.  No floating-point atomics, no inline assembly,
 // plain vector stores.
 //
@@ -40,6 +34,7 @@
 
 #include "sgpr_internal.hpp"
 #include "sgpr_landmarks.h"
+#include "sgpr_map.hpp"
 
 namespace sgpr {
 
@@ -49,7 +44,6 @@ namespace {
 
 constexpr int LM_THREADS = 256;
 constexpr int LM_SCAN_THREADS = 1024;
-constexpr unsigned long long LM_EMPTY = ~0ull;
 constexpr double LM_FIX = 16777216.0;          // 2^24
 constexpr double LM_LIMIT = 137438953472.0;    // 2^37
 constexpr double LM_D2_CAP = 1048576.0;        // 2^20
@@ -90,15 +84,6 @@ struct LmArgs {
     int32_t starts[SGPR_SESSION_MAX];
 };
 
-__device__ __forceinline__ unsigned long long lm_mix64(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-
 // Cell width of a label: a hair wider than its radius, and never below LM_MIN_CELL.
 //
 // Two nodes in range are never two cells apart.  Let a >= b be one coordinate of two nodes that link, w the width.
@@ -116,54 +101,9 @@ __device__ __forceinline__ long long lm_cell_coord(double v, double w) { return 
 // cells with one key share a list, and one list may be met twice among the 9 neighbours; the pair test compares the
 // labels and the distance itself and uniting is idempotent, so a collision costs time and never an answer.
 __device__ __forceinline__ unsigned long long lm_cell_key(int label, long long ix, long long iy) {
-    unsigned long long k = lm_mix64((unsigned long long)ix + 0x9e3779b97f4a7c15ull * (unsigned long long)(label + 1));
-    k = lm_mix64(k ^ ((unsigned long long)iy * 0xd6e8feb86659fd93ull));
-    return k == LM_EMPTY ? 0ull : k;
-}
-
-// slot of `key`, inserting it when absent.  Terminates: see TERMINATION above
-__device__ __forceinline__ unsigned long long lm_table_insert(unsigned long long* keys, unsigned long long mask,
-                                                              unsigned long long key) {
-    unsigned long long s = lm_mix64(key) & mask;
-    while (true) {
-        const unsigned long long old = atomicCAS(&keys[s], LM_EMPTY, key);
-        if (old == LM_EMPTY || old == key) return s;
-        s = (s + 1) & mask;
-    }
-}
-// slot of `key`, or LM_EMPTY when absent (the table is complete: built by an earlier kernel)
-__device__ __forceinline__ unsigned long long lm_table_find(const unsigned long long* keys, unsigned long long mask,
-                                                            unsigned long long key) {
-    unsigned long long s = lm_mix64(key) & mask;
-    while (true) {
-        const unsigned long long k = keys[s];
-        if (k == key) return s;
-        if (k == LM_EMPTY) return LM_EMPTY;
-        s = (s + 1) & mask;
-    }
-}
-
-__device__ __forceinline__ int ld_parent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_parent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(int* parent, int x) {
-    int p = ld_parent(parent + x);
-    while (p != x) {                       // path halving: only ever replaces a pointer by an ancestor
-        const int gp = ld_parent(parent + p);
-        if (gp != p) st_parent(parent + x, gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-__device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        const int hi = a > b ? a : b, lo = a > b ? b : a;
-        if (atomicCAS(&parent[hi], hi, lo) == hi) return;      // hook the larger root under the smaller
-    }
+    unsigned long long k = mix64((unsigned long long)ix + 0x9e3779b97f4a7c15ull * (unsigned long long)(label + 1));
+    k = mix64(k ^ ((unsigned long long)iy * 0xd6e8feb86659fd93ull));
+    return k == TABLE_EMPTY ? 0ull : k;
 }
 
 __device__ __forceinline__ bool lm_in_limit(double v) { return isfinite(v) && fabs(v) <= LM_LIMIT; }
@@ -200,7 +140,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_transform_kernel(const LmWs w, 
         return;
     }
     const double cw = lm_cell_width(r);
-    const unsigned long long slot = lm_table_insert(w.cell_key, w.hmask, lm_cell_key(l, lm_cell_coord(mx, cw), lm_cell_coord(my, cw)));
+    const unsigned long long slot = table_insert(w.cell_key, w.hmask, lm_cell_key(l, lm_cell_coord(mx, cw), lm_cell_coord(my, cw)));
     w.next[p] = atomicExch(&w.cell_head[slot], p);
 }
 
@@ -215,8 +155,8 @@ __global__ __launch_bounds__(LM_THREADS) void lm_union_kernel(const LmWs w, cons
     const long long ix = lm_cell_coord(mx, cw), iy = lm_cell_coord(my, cw);
     for (int dy = -1; dy <= 1; ++dy)
         for (int dx = -1; dx <= 1; ++dx) {
-            const unsigned long long slot = lm_table_find(w.cell_key, w.hmask, lm_cell_key(l, ix + dx, iy + dy));
-            if (slot == LM_EMPTY) continue;
+            const unsigned long long slot = table_find(w.cell_key, w.hmask, lm_cell_key(l, ix + dx, iy + dy));
+            if (slot == TABLE_EMPTY) continue;
             for (int o = w.cell_head[slot]; o >= 0; o = w.next[o]) {
                 if (o >= p || w.lab[o] != l) continue;          // every unordered pair once; (a shared list: see lm_cell_key)
                 const double ex = mx - w.m[3 * (size_t)o], ey = my - w.m[3 * (size_t)o + 1];
@@ -244,16 +184,10 @@ __global__ __launch_bounds__(LM_THREADS) void lm_flatten_kernel(const LmWs w, co
     const bool live = p < a.P && w.lab[p] >= 0;
     int root = -1;
     if (live) {
-        root = p;
-        while (true) {                                          // the forest is final: reads past L1
-            const int up = ld_parent(w.parent + root);
-            if (up == root) break;
-            root = up;
-        }
+        root = uf_root_final(w.parent, p);
         w.next[p] = root;                                       // (the cell lists are dead) the node's root
         const int g = p / a.N;
-        int sess = 0;
-        for (int j = 1; j < a.n_sessions; ++j) sess = a.starts[j] <= g ? j : sess;
+        const int sess = session_of(a.starts, a.n_sessions, g);
         atomicAdd(&w.cnt[root], 1);
         for (int k = 0; k < 3; ++k)
             atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)root + k]),
@@ -346,18 +280,10 @@ __global__ __launch_bounds__(LM_THREADS) void lm_finish_kernel(const LmWs w, con
     a.lm_spread[id] = sqrt((double)w.q[p] / ((double)w.cnt[p] * LM_FIX));
 }
 
-size_t lm_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-unsigned long long lm_table_slots(size_t P) {
-    unsigned long long h = 1024;
-    while (h < 2ull * P) h <<= 1;
-    return h;
-}
-
 size_t lm_ws_bytes(size_t P) {
-    const size_t h = (size_t)lm_table_slots(P), b = (P + LM_THREADS - 1) / LM_THREADS;
-    return lm_align(P * 24) * 2 + lm_align(P * 4) * 5 + lm_align(P * 8) * 2 + lm_align(h * 8) + lm_align(h * 4) +
-           lm_align(b * 4) * 2;
+    const size_t h = table_slots(P), b = (P + LM_THREADS - 1) / LM_THREADS;
+    return align256(P * 24) * 2 + align256(P * 4) * 5 + align256(P * 8) * 2 + align256(h * 8) + align256(h * 4) +
+           align256(b * 4) * 2;
 }
 
 bool lm_size_ok(int G, int N) { return G >= 0 && N >= 0 && (long long)G * (long long)N <= 0x7fffffffll; }
@@ -403,30 +329,7 @@ int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, in
         set_error(fn + ": tau_z is negative or NaN");
         return SGPR_E_INVALID;
     }
-    // the session table, under the rules of sgpr.h
-    if (n_sessions < 0 || n_sessions > SGPR_SESSION_MAX) {
-        set_error(fn + ": the number of sessions must lie in 0.." + std::to_string(SGPR_SESSION_MAX));
-        return SGPR_E_INVALID;
-    }
-    if ((h_starts == nullptr) != (n_sessions == 0)) {
-        set_error(fn + (h_starts ? ": a" : ": NULL") + " session table with n = " + std::to_string(n_sessions));
-        return SGPR_E_INVALID;
-    }
-    if (n_sessions > 0) {
-        if (h_starts[0] != 0) {
-            set_error(fn + ": the session table does not start at 0");
-            return SGPR_E_INVALID;
-        }
-        for (int j = 1; j < n_sessions; ++j)
-            if (h_starts[j] < h_starts[j - 1]) {
-                set_error(fn + ": the session table has a decreasing entry at " + std::to_string(j));
-                return SGPR_E_INVALID;
-            }
-        if (h_starts[n_sessions - 1] > G) {
-            set_error(fn + ": the session table has an entry past " + std::to_string(G));
-            return SGPR_E_INVALID;
-        }
-    }
+    if (!session_table_ok(fn.c_str(), "", h_starts, n_sessions, G)) return SGPR_E_INVALID;
     if (!lm_size_ok(G, N)) {
         set_error(fn + ": G N = " + std::to_string((long long)G * N) + " exceeds the int32 node index");
         return SGPR_E_INVALID;
@@ -444,29 +347,24 @@ int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, in
         return SGPR_E_INVALID;
     }
 
-    unsigned char* b = static_cast<unsigned char*>(d_workspace);
-    auto take = [&](size_t bytes) {
-        unsigned char* r = b;
-        b += lm_align(bytes);
-        return r;
-    };
+    Carver ws{static_cast<unsigned char*>(d_workspace)};
     LmWs w;
-    const size_t H = (size_t)lm_table_slots(P);
+    const size_t H = table_slots(P);
     const int B = (int)((P + LM_THREADS - 1) / LM_THREADS);
     w.hmask = H - 1;
-    w.m = reinterpret_cast<double*>(take(P * 24));
-    w.sum = reinterpret_cast<long long*>(take(P * 24));
-    w.lab = reinterpret_cast<int*>(take(P * 4));
-    w.parent = reinterpret_cast<int*>(take(P * 4));
-    w.next = reinterpret_cast<int*>(take(P * 4));
-    w.cnt = reinterpret_cast<int*>(take(P * 4));
-    w.id = reinterpret_cast<int*>(take(P * 4));
-    w.q = reinterpret_cast<unsigned long long*>(take(P * 8));
-    w.sess = reinterpret_cast<unsigned long long*>(take(P * 8));
-    w.cell_key = reinterpret_cast<unsigned long long*>(take(H * 8));
-    w.cell_head = reinterpret_cast<int*>(take(H * 4));
-    w.blk_roots = reinterpret_cast<int*>(take((size_t)B * 4));
-    w.blk_live = reinterpret_cast<int*>(take((size_t)B * 4));
+    w.m = ws.take<double>(3 * P);
+    w.sum = ws.take<long long>(3 * P);
+    w.lab = ws.take<int>(P);
+    w.parent = ws.take<int>(P);
+    w.next = ws.take<int>(P);
+    w.cnt = ws.take<int>(P);
+    w.id = ws.take<int>(P);
+    w.q = ws.take<unsigned long long>(P);
+    w.sess = ws.take<unsigned long long>(P);
+    w.cell_key = ws.take<unsigned long long>(H);
+    w.cell_head = ws.take<int>(H);
+    w.blk_roots = ws.take<int>(B);
+    w.blk_live = ws.take<int>(B);
 
     LmArgs a = {};
     a.centers = d_centers;
@@ -487,12 +385,11 @@ int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, in
     a.B = B;
     a.tau_z = tau_z;
     for (int l = 0; l < n_labels; ++l) a.radius[l] = h_radius[l];
-    a.n_sessions = n_sessions > 0 ? n_sessions : 1;
-    for (int s = 0; s < a.n_sessions; ++s) a.starts[s] = n_sessions > 0 ? h_starts[s] : 0;
+    fill_session_table(a.starts, &a.n_sessions, h_starts, n_sessions);
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     // cell_key | cell_head: empty keys, list ends (-1)
-    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, lm_align(H * 8) + lm_align(H * 4), s);
+    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, align256(H * 8) + align256(H * 4), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_map: memset");
     const dim3 grid(B), block(LM_THREADS);
     hipLaunchKernelGGL(lm_transform_kernel, grid, block, 0, s, w, a);

@@ -22,43 +22,13 @@
 
 #include "sgpr_internal.hpp"
 #include "sgpr_localize.h"
+#include "sgpr_map.hpp"
 
 namespace sgpr {
 
 #pragma clang fp contract(off)
 
 namespace {
-
-struct Se2 {
-    double c, s, x, y;
-};
-
-__device__ __forceinline__ Se2 se2_compose(const Se2& a, const Se2& b) {
-    Se2 r;
-    r.c = a.c * b.c - a.s * b.s;
-    r.s = a.s * b.c + a.c * b.s;
-    r.x = (a.c * b.x - a.s * b.y) + a.x;
-    r.y = (a.s * b.x + a.c * b.y) + a.y;
-    return r;
-}
-
-__device__ __forceinline__ Se2 se2_inverse(const Se2& a) {
-    Se2 r;
-    r.c = a.c;
-    r.s = -a.s;
-    r.x = -(a.c * a.x + a.s * a.y);
-    r.y = a.s * a.x - a.c * a.y;
-    return r;
-}
-
-__device__ __forceinline__ Se2 se2_load(const double* p) {
-    const double2 lo = *reinterpret_cast<const double2*>(p), hi = *reinterpret_cast<const double2*>(p + 2);
-    return Se2{lo.x, lo.y, hi.x, hi.y};
-}
-
-__device__ __forceinline__ bool se2_finite(const Se2& v) {
-    return isfinite(v.c) && isfinite(v.s) && isfinite(v.x) && isfinite(v.y);
-}
 
 struct LocArgs {
     const double* map;
@@ -120,7 +90,7 @@ __global__ __launch_bounds__(T) void loc_kernel(const LocArgs a) {
     int P2 = 1;
     while (P2 < LK) P2 <<= 1;
 
-    // the first query of i's session: sess(i) = the largest j with starts[j] <= i
+    // the first query of i's session: session_of's rule (sgpr_map.hpp), keeping the start and not the index
     int lo = 0;
     for (int j = 1; j < a.n_sessions; ++j) lo = a.starts[j] <= i ? a.starts[j] : lo;
     const int nl = min(a.L, i - lo + 1);         // scans of the window; slots at or past nl K are dead
@@ -270,30 +240,7 @@ int sgpr_localize_scans(const double* d_map, int M, const int32_t* d_cols, const
         set_error(fn + ": L " + std::to_string(L) + " outside [1, " + std::to_string(SGPR_LOCALIZE_MAX_LEN) + "]");
         return SGPR_E_INVALID;
     }
-    // the session table, under the rules of sgpr.h
-    if (n_sessions < 0 || n_sessions > SGPR_SESSION_MAX) {
-        set_error(fn + ": the number of sessions must lie in 0.." + std::to_string(SGPR_SESSION_MAX));
-        return SGPR_E_INVALID;
-    }
-    if ((h_starts == nullptr) != (n_sessions == 0)) {
-        set_error(fn + (h_starts ? ": a" : ": NULL") + " session table with n = " + std::to_string(n_sessions));
-        return SGPR_E_INVALID;
-    }
-    if (n_sessions > 0) {
-        if (h_starts[0] != 0) {
-            set_error(fn + ": the session table does not start at 0");
-            return SGPR_E_INVALID;
-        }
-        for (int j = 1; j < n_sessions; ++j)
-            if (h_starts[j] < h_starts[j - 1]) {
-                set_error(fn + ": the session table has a decreasing entry at " + std::to_string(j));
-                return SGPR_E_INVALID;
-            }
-        if (h_starts[n_sessions - 1] > Q) {
-            set_error(fn + ": the session table has an entry past " + std::to_string(Q));
-            return SGPR_E_INVALID;
-        }
-    }
+    if (!session_table_ok(fn.c_str(), "", h_starts, n_sessions, Q)) return SGPR_E_INVALID;
     if (!(max_trans >= 0.0)) {
         set_error(fn + ": max_trans is negative or NaN");
         return SGPR_E_INVALID;
@@ -321,8 +268,7 @@ int sgpr_localize_scans(const double* d_map, int M, const int32_t* d_cols, const
     a.L = L;
     a.max_trans = max_trans;
     a.min_cos = min_cos;
-    a.n_sessions = n_sessions > 0 ? n_sessions : 1;
-    for (int s = 0; s < a.n_sessions; ++s) a.starts[s] = n_sessions > 0 ? h_starts[s] : 0;
+    fill_session_table(a.starts, &a.n_sessions, h_starts, n_sessions);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int slots = L * K;
     if (slots <= 64) return loc_launch<64>(a, Q, s);

@@ -22,6 +22,7 @@
 #include <string>
 
 #include "sgpr_internal.hpp"
+#include "sgpr_map.hpp"
 #include "sgpr_posegraph.h"
 
 namespace sgpr {
@@ -76,34 +77,23 @@ size_t pg_ws_bytes(int M, int C) { return 8192 + (size_t)192 * M + (size_t)64 * 
 
 // carve the workspace (every array 256-byte aligned from the base); returns the bytes used
 size_t pg_carve(PgArgs& a, void* ws) {
-    char* base = static_cast<char*>(ws);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += (bytes + 255) / 256 * 256;
-        return p;
-    };
+    unsigned char* base = static_cast<unsigned char*>(ws);
+    Carver c{base};
     const size_t M = a.M, C = a.C, NS = pg_segment_cap(a.M) * PG_SEG;
-    for (c64** v : {&a.g, &a.t, &a.r, &a.p, &a.Ap, &a.zv, &a.ozr, &a.ozt}) *v = reinterpret_cast<c64*>(take(M * 16));
-    a.diag = reinterpret_cast<double*>(take(M * 8));
-    for (int32_t** v : {&a.pos, &a.slot, &a.cntH, &a.cntT}) *v = reinterpret_cast<int32_t*>(take(M * 4));
-    for (int32_t** v : {&a.offH, &a.offT}) *v = reinterpret_cast<int32_t*>(take((M + 1) * 4));
-    a.free = reinterpret_cast<uint8_t*>(take(M));
-    for (c64** v : {&a.czr, &a.czt}) *v = reinterpret_cast<c64*>(take(C * 16));
-    for (double** v : {&a.cwr, &a.cwt}) *v = reinterpret_cast<double*>(take(C * 8));
-    for (int32_t** v : {&a.listH, &a.listT}) *v = reinterpret_cast<int32_t*>(take(C * 4));
-    a.live = reinterpret_cast<uint8_t*>(take(C));
-    a.Y = reinterpret_cast<c64*>(take(NS * 16));
-    a.L = reinterpret_cast<c64*>(take(NS * 16));
-    a.PIV = reinterpret_cast<double*>(take(NS * 8));
-    a.CPL = reinterpret_cast<uint8_t*>(take(NS));
-    return off;
-}
-
-__device__ __forceinline__ int pg_session_of(const PgArgs& a, int k) {
-    int s = 0;
-    for (int j = 1; j < a.n_sessions; ++j) s = a.starts[j] <= k ? j : s;
-    return s;
+    for (c64** v : {&a.g, &a.t, &a.r, &a.p, &a.Ap, &a.zv, &a.ozr, &a.ozt}) *v = c.take<c64>(M);
+    a.diag = c.take<double>(M);
+    for (int32_t** v : {&a.pos, &a.slot, &a.cntH, &a.cntT}) *v = c.take<int32_t>(M);
+    for (int32_t** v : {&a.offH, &a.offT}) *v = c.take<int32_t>(M + 1);
+    a.free = c.take<uint8_t>(M);
+    for (c64** v : {&a.czr, &a.czt}) *v = c.take<c64>(C);
+    for (double** v : {&a.cwr, &a.cwt}) *v = c.take<double>(C);
+    for (int32_t** v : {&a.listH, &a.listT}) *v = c.take<int32_t>(C);
+    a.live = c.take<uint8_t>(C);
+    a.Y = c.take<c64>(NS);
+    a.L = c.take<c64>(NS);
+    a.PIV = c.take<double>(NS);
+    a.CPL = c.take<uint8_t>(NS);
+    return (size_t)(c.p - base);
 }
 
 // ascending heap sort of n distinct ints (a closure list; usually a handful)
@@ -428,7 +418,7 @@ __global__ __launch_bounds__(PG_T) void pg_solve_kernel(const PgArgs a) {
             const double c = a.X[(size_t)k * 4], s = a.X[(size_t)k * 4 + 1], x = a.X[(size_t)k * 4 + 2],
                          y = a.X[(size_t)k * 4 + 3];
             if (!(isfinite(c) && isfinite(s) && isfinite(x) && isfinite(y)) || c * c + s * s == 0.0) bad = true;
-            const int ss = pg_session_of(a, k), pos = k - a.starts[ss];
+            const int ss = session_of(a.starts, a.n_sessions, k), pos = k - a.starts[ss];
             a.pos[k] = pos;
             a.slot[k] = (pos % PG_SEG) * NS + a.segbase[ss] + pos / PG_SEG;
             a.cntH[k] = 0;
@@ -479,7 +469,7 @@ __global__ __launch_bounds__(PG_T) void pg_solve_kernel(const PgArgs a) {
             a.cwt[p] = a.w_clo[1] * wm;
             atomicAdd(&a.cntH[r], 1);
             atomicAdd(&a.cntT[c], 1);
-            const int sr = pg_session_of(a, r), sc = pg_session_of(a, c);
+            const int sr = session_of(a.starts, a.n_sessions, r), sc = session_of(a.starts, a.n_sessions, c);
             atomicOr(&sh.adj[sr], 1ull << sc);
             atomicOr(&sh.adj[sc], 1ull << sr);
         }
@@ -528,7 +518,7 @@ __global__ __launch_bounds__(PG_T) void pg_solve_kernel(const PgArgs a) {
             runH += a.cntH[k];
             runT += a.cntT[k];
             const bool fixed = a.fixed ? a.fixed[k] != 0 : k == 0;
-            const bool fr = ((active >> pg_session_of(a, k)) & 1ull) && !fixed;
+            const bool fr = ((active >> session_of(a.starts, a.n_sessions, k)) & 1ull) && !fixed;
             a.free[k] = fr ? 1 : 0;
             nfree += fr ? 1 : 0;
         }
@@ -641,30 +631,7 @@ int sgpr_posegraph_optimize(const double* d_X, int M, const int32_t* h_starts, i
                   std::to_string(SGPR_POSEGRAPH_MAX_ITERS) + "]");
         return SGPR_E_INVALID;
     }
-    // the session table, under the rules of sgpr.h
-    if (n_sessions < 0 || n_sessions > SGPR_SESSION_MAX) {
-        set_error(fn + ": the number of sessions must lie in 0.." + std::to_string(SGPR_SESSION_MAX));
-        return SGPR_E_INVALID;
-    }
-    if ((h_starts == nullptr) != (n_sessions == 0)) {
-        set_error(fn + (h_starts ? ": a" : ": NULL") + " session table with n = " + std::to_string(n_sessions));
-        return SGPR_E_INVALID;
-    }
-    if (n_sessions > 0) {
-        if (h_starts[0] != 0) {
-            set_error(fn + ": the session table does not start at 0");
-            return SGPR_E_INVALID;
-        }
-        for (int j = 1; j < n_sessions; ++j)
-            if (h_starts[j] < h_starts[j - 1]) {
-                set_error(fn + ": the session table has a decreasing entry at " + std::to_string(j));
-                return SGPR_E_INVALID;
-            }
-        if (h_starts[n_sessions - 1] > M) {
-            set_error(fn + ": the session table has an entry past " + std::to_string(M));
-            return SGPR_E_INVALID;
-        }
-    }
+    if (!session_table_ok(fn.c_str(), "", h_starts, n_sessions, M)) return SGPR_E_INVALID;
     for (double w : {w_odo_rot, w_odo_trans, w_clo_rot, w_clo_trans})
         if (!(w > 0.0) || !std::isfinite(w)) {
             set_error(fn + ": every weight must be finite and positive");
@@ -702,8 +669,7 @@ int sgpr_posegraph_optimize(const double* d_X, int M, const int32_t* h_starts, i
     a.w_clo[0] = w_clo_rot;
     a.w_clo[1] = w_clo_trans;
     a.rel_tol = rel_tol;
-    a.n_sessions = n_sessions > 0 ? n_sessions : 1;
-    for (int s = 0; s < a.n_sessions; ++s) a.starts[s] = n_sessions > 0 ? h_starts[s] : 0;
+    fill_session_table(a.starts, &a.n_sessions, h_starts, n_sessions);
     a.starts[a.n_sessions] = M;
     a.segbase[0] = 0;
     for (int s = 0; s < a.n_sessions; ++s)

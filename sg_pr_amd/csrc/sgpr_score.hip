@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "sgpr_internal.hpp"
+#include "sgpr_map.hpp"
 
 namespace sgpr {
 
@@ -1986,7 +1987,6 @@ int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const
     return SGPR_OK;
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 size_t score_all_pairs_multi_ws_bytes(int n, const sgpr_pairs_job* jobs) {
     size_t total = 0;

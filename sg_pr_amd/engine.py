@@ -5,6 +5,7 @@ for device memory and streams only: tensors are handed over as raw pointers.
 There is NO CPU fallback: a missing library or a non-GPU tensor raises.
 """
 import ctypes
+import functools
 import os
 from fractions import Fraction
 import threading
@@ -112,6 +113,11 @@ def _session_table(starts):
     return t
 
 
+def _table_args(t):
+    """(pointer, n) of an optional host table (_session_table, _path_table) as the C-ABI takes it; None: (NULL, 0)"""
+    return (None, 0) if t is None else (t.ctypes.data, t.shape[0])
+
+
 class SgprError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("%s (%d): %s" % (ERROR_NAMES.get(code, "SGPR_E_?"), code, message))
@@ -163,6 +169,28 @@ def load_library():
     return lib
 
 
+@functools.lru_cache(maxsize=None)
+def public_header(file_name):
+    """_build.parse_header of include/<file_name>: what one of the further public headers declares (needs no library)"""
+    with open(os.path.join(_build.REPO, "include", file_name)) as f:
+        return _build.parse_header(f.read())
+
+
+@functools.lru_cache(maxsize=None)
+def bind_header(file_name):
+    """public_header(file_name) with its functions' signatures set on the one library load_library() returns -> the
+    HeaderAbi.  A library that lacks one of the functions was built from other sources: ImportError."""
+    abi, lib = public_header(file_name), load_library()
+    for name, restype, argtypes in abi.functions:
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError("%s does not export %s: rebuild it (`python -m sg_pr_amd._build --force`)"
+                              % (_build.LIB_PATH, name))
+        fn.restype, fn.argtypes = restype, argtypes
+    return abi
+
+
 def default_dims():
     return SgprDims(NUM_LABELS, 64, 64, 32, 16, 16)
 
@@ -196,6 +224,12 @@ def _check(rc):
 def _stream(device):
     """the stream current on `device`, as the C-ABI takes it"""
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _device_of(*tensors):
+    """the device of the first CUDA tensor among the arguments, else the current device"""
+    return next((t.device for t in tensors if isinstance(t, torch.Tensor) and t.is_cuda),
+                torch.device("cuda", torch.cuda.current_device()))
 
 
 def _on(t, device, dtype):
@@ -958,7 +992,7 @@ class Engine:
         table = _path_table(paths, seq_len)
         out, out_code, ldo = self._filter_outputs(max(r - int(context), 0), m, out, out_code, "out_code", want_code)
         rc = self.lib.sgpr_seq_path_filter(self._h, _ptr(score), r, m, ld, int(context), int(seq_len),
-                                           self._flags(reverse=reverse), table.ctypes.data, table.shape[0], _ptr(out),
+                                           self._flags(reverse=reverse), *_table_args(table), _ptr(out),
                                            ldo, _ptr(out_code), self._stream())
         self._check(rc)
         return out if out_code is None else (out, out_code)
@@ -984,7 +1018,7 @@ class Engine:
                                                                  table.shape[0], int(k), int(radius), flags)
         return self._ranked(self.lib.sgpr_score_path_topk,
                             (self._h, _ptr(rows), r, _ptr(cols), m, int(context), _ptr(rs), int(row0), int(window), flags,
-                             int(seq_len), table.ctypes.data, table.shape[0], int(radius)),
+                             int(seq_len), *_table_args(table), int(radius)),
                             max(r - int(context), 0), k, ws_bytes, codes=True)
 
     SESSION_MAX = SESSION_MAX
@@ -994,10 +1028,7 @@ class Engine:
         """(path table pointer, n_paths, row table pointer, n, column table pointer, n) and the arrays that own them"""
         table = None if paths is None else _path_table(paths, seq_len)
         rt, ct = _session_table(row_sessions), _session_table(col_sessions)
-        args = []
-        for t in (table, rt, ct):
-            args += [None, 0] if t is None else [t.ctypes.data, t.shape[0]]
-        return args, (table, rt, ct)
+        return [*_table_args(table), *_table_args(rt), *_table_args(ct)], (table, rt, ct)
 
     def session_filter(self, score, seq_len, paths=None, row_sessions=None, col_sessions=None, window=-1, row0=0,
                        row_self=None, context=0, reverse=False, want_code=False, out=None, out_code=None):
@@ -1563,8 +1594,7 @@ def verify_pairs(centers_a, labels_a, centers_b, labels_b, idx_a, idx_b, tau_edg
     VERIFY_INVALID_INDEX.  Asynchronous on the current stream."""
     lib = load_library()
     if device is None:
-        device = next((t.device for t in (centers_a, centers_b, idx_a, idx_b) if isinstance(t, torch.Tensor) and t.is_cuda),
-                      torch.device("cuda", torch.cuda.current_device()))
+        device = _device_of(centers_a, centers_b, idx_a, idx_b)
     ca, la = _verify_graphs(centers_a, labels_a, device, "row graphs")
     cb, lb = _verify_graphs(centers_b, labels_b, device, "column graphs")
     if ca.shape[1] != cb.shape[1]:
@@ -1603,8 +1633,7 @@ def closure_consistency(rows, cols, T, Xr, Xc, group, n_groups, max_trans, min_c
     stream."""
     lib = load_library()
     if device is None:
-        device = next((t.device for t in (T, rows, cols, Xr, Xc, group) if isinstance(t, torch.Tensor) and t.is_cuda),
-                      torch.device("cuda", torch.cuda.current_device()))
+        device = _device_of(T, rows, cols, Xr, Xc, group)
     r, c, g = (_on(t, device, torch.int32).view(-1) for t in (rows, cols, group))
     t = _on(T, device, torch.float64).view(-1, 4)
     xr, xc = _on(Xr, device, torch.float64).view(-1, 4), _on(Xc, device, torch.float64).view(-1, 4)

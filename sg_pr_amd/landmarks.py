@@ -1,6 +1,6 @@
 """The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h).
 
-The entry points are declared in the fourth public header; this module parses it with _build.parse_header and sets the
+The entry points are declared in the fourth public header; this module has engine.bind_header parse it and set the
 signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -11,8 +11,7 @@ import torch
 from . import _build, engine, synth
 
 HEADER = os.path.join(_build.REPO, "include", "sgpr_landmarks.h")
-with open(HEADER) as _f:
-    _ABI = _build.parse_header(_f.read())
+_ABI = engine.public_header(os.path.basename(HEADER))
 _C = _ABI.constants
 
 ABI_SYMBOLS = [name for name, _, _ in _ABI.functions]
@@ -21,23 +20,11 @@ DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
 DEFAULT_MAX_LANDMARKS = 1 << 22          # the default capacity is G N, capped here; build() re-runs past it
 _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L float64 matrix alive
 
-_lib = None
-
 
 def load_library():
     """engine.load_library() with the signatures of include/sgpr_landmarks.h set on it"""
-    global _lib
-    if _lib is None:
-        lib = engine.load_library()
-        for name, restype, argtypes in _ABI.functions:
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise ImportError("%s does not export %s: rebuild it (`python -m sg_pr_amd._build --force`)"
-                                  % (_build.LIB_PATH, name))
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = lib
-    return _lib
+    engine.bind_header(os.path.basename(HEADER))
+    return engine.load_library()
 
 
 def workspace_bytes(G, N):
@@ -62,8 +49,7 @@ def build_async(centers, labels, poses, starts=None, radius=None, tau_z=DEFAULT_
     workspace_bytes(G, N) to reuse (None: one is allocated)."""
     lib = load_library()
     if device is None:
-        device = next((t.device for t in (centers, labels, poses) if isinstance(t, torch.Tensor) and t.is_cuda),
-                      torch.device("cuda", torch.cuda.current_device()))
+        device = engine._device_of(centers, labels, poses)
     lab = engine._on(labels, device, torch.int32)
     if lab.dim() != 2:
         raise ValueError("landmarks: labels must be [G, N]")
@@ -94,7 +80,7 @@ def build_async(centers, labels, poses, starts=None, radius=None, tau_z=DEFAULT_
     with torch.cuda.device(device):
         engine._check(lib.sgpr_landmark_map(
             engine._ptr(cen), engine._ptr(lab), g, n, engine._ptr(x),
-            None if table is None else table.ctypes.data, 0 if table is None else table.shape[0],
+            *engine._table_args(table),
             rad.ctypes.data, rad.shape[0], float(tau_z), cap, engine._ptr(out["center"]), engine._ptr(out["label"]),
             engine._ptr(out["count"]), engine._ptr(out["first"]), engine._ptr(out["sessions"]),
             engine._ptr(out["spread"]), engine._ptr(out["node_landmark"]), engine._ptr(out["num"]),

@@ -1,6 +1,6 @@
 """Localise scans in the map: pose consensus over verified candidates (include/sgpr_localize.h).
 
-The entry point is declared in the third public header; this module parses it with _build.parse_header and sets the
+The entry point is declared in the third public header; this module has engine.bind_header parse it and set the
 signature on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import math
@@ -11,31 +11,18 @@ import torch
 from . import _build, engine
 
 HEADER = os.path.join(_build.REPO, "include", "sgpr_localize.h")
-with open(HEADER) as _f:
-    _ABI = _build.parse_header(_f.read())
+_ABI = engine.public_header(os.path.basename(HEADER))
 _C = _ABI.constants
 
 ABI_SYMBOLS = [name for name, _, _ in _ABI.functions]
 MAX_K, MAX_LEN = _C["SGPR_LOCALIZE_MAX_K"], _C["SGPR_LOCALIZE_MAX_LEN"]
 NO_HYPOTHESIS, DEGENERATE = _C["SGPR_LOCALIZE_NO_HYPOTHESIS"], _C["SGPR_LOCALIZE_DEGENERATE"]
 
-_lib = None
-
 
 def load_library():
     """engine.load_library() with the signatures of include/sgpr_localize.h set on it"""
-    global _lib
-    if _lib is None:
-        lib = engine.load_library()
-        for name, restype, argtypes in _ABI.functions:
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise ImportError("%s does not export %s: rebuild it (`python -m sg_pr_amd._build --force`)"
-                                  % (_build.LIB_PATH, name))
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = lib
-    return _lib
+    engine.bind_header(os.path.basename(HEADER))
+    return engine.load_library()
 
 
 def localize_async(map_poses, cols, T, accept=None, odo=None, starts=None, seq_len=1, max_trans=1.0, max_yaw=0.1,
@@ -44,8 +31,7 @@ def localize_async(map_poses, cols, T, accept=None, odo=None, starts=None, seq_l
     winner slot, flags), spread f64 [Q]) device tensors, asynchronous on the current stream."""
     lib = load_library()
     if device is None:
-        device = next((t.device for t in (map_poses, T, cols, odo) if isinstance(t, torch.Tensor) and t.is_cuda),
-                      torch.device("cuda", torch.cuda.current_device()))
+        device = engine._device_of(map_poses, T, cols, odo)
     x = engine._on(map_poses, device, torch.float64).view(-1, 4)
     c = engine._on(cols, device, torch.int32)
     if c.dim() != 2:
@@ -70,7 +56,7 @@ def localize_async(map_poses, cols, T, accept=None, odo=None, starts=None, seq_l
     with torch.cuda.device(device):
         engine._check(lib.sgpr_localize_scans(
             engine._ptr(x), m, engine._ptr(c), engine._ptr(t), engine._ptr(acc), q, k, engine._ptr(od),
-            None if table is None else table.ctypes.data, 0 if table is None else table.shape[0], int(seq_len),
+            *engine._table_args(table), int(seq_len),
             float(max_trans), math.cos(float(max_yaw)), engine._ptr(pose), engine._ptr(stat), engine._ptr(spread),
             engine._stream(device)))
     return pose, stat, spread

@@ -1,6 +1,6 @@
 """Planar pose-graph relaxation over accepted loop closures (include/sgpr_posegraph.h).
 
-The entry points are declared in the second public header; this module parses it with _build.parse_header and sets the
+The entry points are declared in the second public header; this module has engine.bind_header parse it and set the
 signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -11,8 +11,7 @@ import torch
 from . import _build, engine
 
 HEADER = os.path.join(_build.REPO, "include", "sgpr_posegraph.h")
-with open(HEADER) as _f:
-    _ABI = _build.parse_header(_f.read())
+_ABI = engine.public_header(os.path.basename(HEADER))
 _C = _ABI.constants
 
 ABI_SYMBOLS = [name for name, _, _ in _ABI.functions]
@@ -24,23 +23,11 @@ STOP_NAMES = {CONVERGED: "converged", STOP_MAX_ITERS: "max_iters", BREAKDOWN: "b
 # 1 / sigma^2 of synth.drift_world's odometry steps (0.004 rad, 0.03 m) and closures (0.01 rad, 0.15 m)
 W_ODO, W_CLO = (62500.0, 1100.0), (10000.0, 44.0)
 
-_lib = None
-
 
 def load_library():
     """engine.load_library() with the signatures of include/sgpr_posegraph.h set on it"""
-    global _lib
-    if _lib is None:
-        lib = engine.load_library()
-        for name, restype, argtypes in _ABI.functions:
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise ImportError("%s does not export %s: rebuild it (`python -m sg_pr_amd._build --force`)"
-                                  % (_build.LIB_PATH, name))
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = lib
-    return _lib
+    engine.bind_header(os.path.basename(HEADER))
+    return engine.load_library()
 
 
 def workspace_bytes(m, c):
@@ -63,8 +50,7 @@ def optimize_async(X, rows, cols, T, starts=None, fixed=None, weight=None, w_odo
     tensors, asynchronous on the current stream.  workspace: a uint8 device tensor to carve (any contents), or None."""
     lib = load_library()
     if device is None:
-        device = next((t.device for t in (X, T, rows, cols) if isinstance(t, torch.Tensor) and t.is_cuda),
-                      torch.device("cuda", torch.cuda.current_device()))
+        device = engine._device_of(X, T, rows, cols)
     x = engine._on(X, device, torch.float64).view(-1, 4)
     r, c = (engine._on(t, device, torch.int32).view(-1) for t in (rows, cols))
     t = engine._on(T, device, torch.float64).view(-1, 4)
@@ -85,7 +71,7 @@ def optimize_async(X, rows, cols, T, starts=None, fixed=None, weight=None, w_odo
     ws = workspace if workspace is not None else torch.empty(max(need, 16), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
         engine._check(lib.sgpr_posegraph_optimize(
-            engine._ptr(x), m, None if table is None else table.ctypes.data, 0 if table is None else table.shape[0],
+            engine._ptr(x), m, *engine._table_args(table),
             engine._ptr(r), engine._ptr(c), engine._ptr(t), engine._ptr(wgt), n, engine._ptr(fx), float(w_odo[0]),
             float(w_odo[1]), float(w_clo[0]), float(w_clo[1]), int(max_iters), float(rel_tol), engine._ptr(out),
             engine._ptr(info), engine._ptr(resid), engine._ptr(ws), ws.numel(), engine._stream(device)))

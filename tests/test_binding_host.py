@@ -1,10 +1,12 @@
 """The Python binding follows include/sgpr.h and nothing else (no GPU): the header parser on a literal text, the ctypes
 signatures it gives the loaded library - a set of functions that together use every parameter and return type of the
 header, written out here as literals -, every declared function bound, and the limits / flag bits / error codes the
-binding mirrors pinned to their values."""
+binding mirrors pinned to their values.  Last, the one session-table check behind the entry points of all four headers:
+the same bad table gets the same answer from each."""
 import ctypes
 import os
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,3 +130,55 @@ def test_mirrored_constants_have_the_header_values():
     assert engine.ERROR_NAMES == {-1: "SGPR_E_INVALID", -2: "SGPR_E_DIMS", -3: "SGPR_E_NODES", -4: "SGPR_E_K",
                                   -5: "SGPR_E_LABEL", -6: "SGPR_E_HIP", -7: "SGPR_E_WORKSPACE", -8: "SGPR_E_BLOB"}
     assert all(isinstance(v, int) for v in (E.TOPK_CAUSAL, engine.MAX_NODES, engine.VERIFY_NONFINITE))
+
+
+# (table or None, n or None = its length, limit, a word of the message) - every fault of a session table
+BAD_SESSION_TABLES = {
+    "null_with_n_2": (None, 2, 8, "NULL"),
+    "table_with_n_0": ([0, 4], 0, 8, "with n = 0"),
+    "n_minus_1": ([0, 4], -1, 8, "0..64"),
+    "n_65": ([0] * 65, 65, 8, "0..64"),
+    "first_entry_1": ([1, 4], None, 8, "start at 0"),
+    "decreasing": ([0, 5, 4], None, 8, "decreasing entry at 2"),
+    "past_the_limit": ([0, 4, 9], None, 8, "past 8"),
+    "limit_0": ([0, 1], None, 0, "past 0"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(BAD_SESSION_TABLES))
+def test_one_session_table_check_behind_every_header(case):
+    """sgpr_session_filter (its row table), sgpr_posegraph_optimize, sgpr_localize_scans and sgpr_landmark_map refuse a
+    bad session table with the same code and, after the function's name and apart from the word "row", the same text.
+    Wild device pointers: had the device been touched, the call would have failed otherwise or crashed."""
+    from sg_pr_amd import engine, landmarks, localize, posegraph
+    lib = engine.load_library()
+    assert posegraph.load_library() is lib and localize.load_library() is lib and landmarks.load_library() is lib
+    values, n, limit, word = BAD_SESSION_TABLES[case]
+    table = None if values is None else np.ascontiguousarray(values, dtype=np.int32)
+    t = None if table is None else ctypes.c_void_p(table.ctypes.data)
+    n = len(values) if n is None else n
+    g = ctypes.c_void_p(0xdead0000)                 # never dereferenced
+    zeroed = ctypes.create_string_buffer(1 << 16)   # a zeroed handle: plain fields only, no device state behind it
+    radius = np.full(12, 0.75)
+    calls = {
+        "sgpr_session_filter": lambda: lib.sgpr_session_filter(
+            ctypes.cast(zeroed, ctypes.c_void_p), g, limit, 300, 300, 0, 8, 2, None, 0, t, n, None, 0, None, 0, -1, g, 300,
+            None, None),
+        "sgpr_posegraph_optimize": lambda: lib.sgpr_posegraph_optimize(
+            g, limit, t, n, g, g, g, None, 5, None, 1.0, 1.0, 1.0, 1.0, 10, 1e-9, g, g, g, g, 1 << 40, None),
+        "sgpr_localize_scans": lambda: lib.sgpr_localize_scans(
+            g, 20, g, g, g, limit, 4, g, t, n, 2, 1.0, 0.9, g, g, g, None),
+        "sgpr_landmark_map": lambda: lib.sgpr_landmark_map(
+            g, g, limit, 10, g, t, n, radius.ctypes.data, 12, 0.75, 80, g, g, g, g, g, g, g, g, g, 1 << 40, None),
+    }
+    texts = {}
+    for fn, call in calls.items():
+        assert call() == -1, fn                      # SGPR_E_INVALID
+        message = lib.sgpr_last_error().decode()
+        assert message.startswith(fn + ": "), message
+        texts[fn] = message[len(fn) + 2:]
+    row = texts.pop("sgpr_session_filter")
+    assert word in row and "row " in row and "  " not in row, row
+    for fn, text in texts.items():
+        assert text == row.replace("row ", "", 1), (fn, text, row)
+        assert "  " not in text and word in text, (fn, text)
