@@ -739,7 +739,9 @@ __device__ __forceinline__ void emit_bits(unsigned take, int jbase, int pitchA, 
 // Exact k-smallest selection for the rows of one key chunk.
 // P consecutive lanes share a row; lane `part` owns candidates [part*seg, (part+1)*seg), seg <= CAP.
 // Result: nbr[i][0..k) = (float offset of the A row of) the k nearest candidates of row i under the
-// total order (key ascending, index ascending) - written as an unordered set.
+// total order (key ascending, index ascending) - written as an unordered set.  (The unit of an entry belongs to the
+// instance: float offsets here, in select_bisect and in select_owned_big; BYTE offsets in select_owned, whose instances
+// read them back through gather_max1 / gather_max2<true> - embed_graph's kOwned ties the writer to the reader.)
 // CAPX = candidates a lane may own: CAP in general, 16 in lean plans (NP <= 64 and >= 4 lanes per row whenever a row
 // has more than 16 candidates), which drops the 32- and 64-candidate paths and their registers from that instance.
 // KEEP = list entries that matter (k <= KEEP <= KP): the sorted lists carry +inf beyond it, and every comparator,
@@ -1073,11 +1075,13 @@ __device__ __forceinline__ f32x4 tile16_swapped(const FragT<FMT> (&a)[2], const 
 // candidate index of bit u of a lane's mask: tile u >> 2, lane group lq, element u & 3
 __device__ __forceinline__ int owned_cand(int u, int lq) { return 16 * (u >> 2) + 4 * lq + (u & 3); }
 
-__device__ __forceinline__ void emit_owned(unsigned take, int lq, int pitchA, unsigned short* __restrict__ out, int& pos) {
+// stride: what an entry counts per candidate row, in the unit of the instance's neighbour entries - select_owned passes
+// the row pitch of A in BYTES (its reader: gather_max1 / gather_max2<true>), select_owned_big the pitch in floats
+__device__ __forceinline__ void emit_owned(unsigned take, int lq, int stride, unsigned short* __restrict__ out, int& pos) {
     while (take) {
         const int u = __ffs(take) - 1;
         take &= take - 1;
-        out[pos++] = (unsigned short)(owned_cand(u, lq) * pitchA);
+        out[pos++] = (unsigned short)(owned_cand(u, lq) * stride);
     }
 }
 
@@ -1088,11 +1092,15 @@ __device__ __forceinline__ void select_owned(const EmbedPlan& p, const int n, co
                                              const unsigned char* __restrict__ X, const float* __restrict__ xx,
                                              unsigned short* __restrict__ nbr, const int wave, const bool coord) {
     constexpr int K = 10, KP = 16, XR = xrow<FMT>();
+    // The neighbour entries of these instances are BYTE offsets of the candidate's row in A (at most 63 rows x 272 bytes:
+    // sixteen bits hold them), not float offsets: the gather's address is then base + entry, and a vector add takes either
+    // half of the word the entries were read in as its operand - one instruction per neighbour, not mask + shift-add.
+    const int pitchB = 4 * p.pitchA;
     if (wave >= nrt) return;                         // no rows of the graph in this wave's tile
     const int lane = phase_tid() & 63, l15 = lane & 15, lq = lane >> 4;
     const int i = 16 * wave + l15;
     const bool active = i < n;
-    // the representative of >= K identical trailing slots (select_phase): its key, picked up while its tile goes by
+    // the representative of >= K identical trailing slots (select_phase): its key is read from the lane's keys below
     const int jr = n - 1, tr = jr >> 4, rr = jr & 3, lqr = (jr >> 2) & 3;
     float d[16], krep_part = 0.f;
     if (coord) {
@@ -1108,7 +1116,6 @@ __device__ __forceinline__ void select_owned(const EmbedPlan& p, const int n, co
                     const float t = fmaf(2.f, dot, -cj.w);
                     key[r] = __fsub_rn(ci.w, t);     // (+inf for an empty slot: its |x|^2 is)
                 }
-                if (tj == tr) krep_part = rr == 0 ? key[0] : (rr == 1 ? key[1] : (rr == 2 ? key[2] : key[3]));
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) d[4 * tj + r] = key[r];
@@ -1125,16 +1132,21 @@ __device__ __forceinline__ void select_owned(const EmbedPlan& p, const int n, co
                 const f32x4 g = tj >= wave ? tile16_swapped<FMT>(a, b) : tile16<4, FMT>(a, b);
                 const int jb = 16 * tj + 4 * lq;
                 const float4 xj = *reinterpret_cast<const float4*>(xx + jb);
-                key[0] = fmaf(-2.f, g[0], jb + 0 < n ? xj.x : INFINITY);
-                key[1] = fmaf(-2.f, g[1], jb + 1 < n ? xj.y : INFINITY);
-                key[2] = fmaf(-2.f, g[2], jb + 2 < n ? xj.z : INFINITY);
-                key[3] = fmaf(-2.f, g[3], jb + 3 < n ? xj.w : INFINITY);
-                if (tj == tr) krep_part = rr == 0 ? key[0] : (rr == 1 ? key[1] : (rr == 2 ? key[2] : key[3]));
+                // (xx is +inf for the slots the graph does not have - staging and gather epilogue of embed_graph - so an
+                //  empty slot's key is +inf without an index test per key)
+                key[0] = fmaf(-2.f, g[0], xj.x);
+                key[1] = fmaf(-2.f, g[1], xj.y);
+                key[2] = fmaf(-2.f, g[2], xj.z);
+                key[3] = fmaf(-2.f, g[3], xj.w);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) d[4 * tj + r] = key[r];
         }
     }
+    // the representative's key is element 4 tr + rr of the keys of its lane group: ONE indexed register move (the index is
+    // wave-uniform, the sixteen keys sit in consecutive registers) - picked up tile by tile, "is this the tile, which of its
+    // four" was a chain of scalar branches and spilled condition masks in every tile of every layer
+    if (one_rep) krep_part = d[4 * tr + rr];
     // ---- this lane's K smallest (ascending), then the butterfly over the row's four lanes (16 and 32 lanes away)
     float L[KP];
     list_from_32<KP, K, 0, 16>(d, 4 * nrt, L);
@@ -1161,9 +1173,13 @@ __device__ __forceinline__ void select_owned(const EmbedPlan& p, const int n, co
             tau = krep;
             dup_cut = true;
         }
-        if (active) {
-            const unsigned short rep = (unsigned short)(jr * p.pitchA);
-            for (int q = lq; q < K; q += 4) out[q] = rep;
+        // the row's list starts out as K copies of the representative (the emission below overwrites its head): three of the
+        // row's lanes store four entries each - entries 10 and 11 are padding of the 16-entry row, which nothing reads - in
+        // one predicated 8-byte store instead of a strided loop of sixteen-bit stores under three exec masks
+        static_assert(K <= 12, "three lanes x four entries");
+        if (active && lq < 3) {
+            const unsigned rep2 = (unsigned)(jr * pitchB) * 0x10001u;
+            *reinterpret_cast<uint2*>(out + 4 * lq) = make_uint2(rep2, rep2);
         }
     }
     // ---- the common case: exactly K keys at or below tau (or the representative's cut) -> one mask, a prefix, emission
@@ -1183,7 +1199,7 @@ __device__ __forceinline__ void select_owned(const EmbedPlan& p, const int n, co
     if (__ballot(active && !(dup_cut || total_le == K)) == 0ull) {
         if (active) {
             int pos = incl - n_le;
-            emit_owned(le, lq, p.pitchA, out, pos);
+            emit_owned(le, lq, pitchB, out, pos);
         }
         return;
     }
@@ -1219,7 +1235,7 @@ __device__ __forceinline__ void select_owned(const EmbedPlan& p, const int n, co
     for (int q = 0; q < 4; ++q) pk[q] = (unsigned)__shfl((int)mine, 16 * q + l15);
     if (active) {
         int pos = less_incl - n_less;
-        emit_owned(lt, lq, p.pitchA, out, pos);
+        emit_owned(lt, lq, pitchB, out, pos);
         int before = 0;                              // ties in the tiles before the current one
 #pragma unroll 1
         for (int tj = 0; tj < 4; ++tj) {             // (rolled: this path is rare, the instance's code size is not)
@@ -1240,7 +1256,7 @@ __device__ __forceinline__ void select_owned(const EmbedPlan& p, const int n, co
                 bits ^= low;
             }
             int tpos = total_less + min(start, T);
-            emit_owned(keep << (4 * tj), lq, p.pitchA, out, tpos);
+            emit_owned(keep << (4 * tj), lq, pitchB, out, tpos);
             before += all;
         }
     }
@@ -1969,6 +1985,14 @@ __device__ __forceinline__ void nbr_pair(const unsigned short* __restrict__ nw, 
 #endif
 }
 
+// BYTES: a neighbour entry is the byte offset of its row in A (the lean production instances: select_owned), else the float offset
+template <bool BYTES>
+__device__ __forceinline__ float4 nbr_row(const float* __restrict__ A4, int a) {
+    if constexpr (BYTES) return *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(A4) + a);
+    return *reinterpret_cast<const float4*>(A4 + a);
+}
+
+template <bool BYTES = false>
 __device__ __forceinline__ void gather_max2(const float* __restrict__ A4, const unsigned short* __restrict__ nwa,
                                             const unsigned short* __restrict__ nwb, int k, float4& ma, float4& mb) {
     ma = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
@@ -1980,10 +2004,10 @@ __device__ __forceinline__ void gather_max2(const float* __restrict__ A4, const 
         int a0, a1, b0, b1;
         nbr_pair(nwa, q, odd, a0, a1);
         nbr_pair(nwb, q, odd, b0, b1);
-        const float4 va0 = *reinterpret_cast<const float4*>(A4 + a0);
-        const float4 va1 = *reinterpret_cast<const float4*>(A4 + a1);
-        const float4 vb0 = *reinterpret_cast<const float4*>(A4 + b0);
-        const float4 vb1 = *reinterpret_cast<const float4*>(A4 + b1);
+        const float4 va0 = nbr_row<BYTES>(A4, a0);
+        const float4 va1 = nbr_row<BYTES>(A4, a1);
+        const float4 vb0 = nbr_row<BYTES>(A4, b0);
+        const float4 vb1 = nbr_row<BYTES>(A4, b1);
         ma.x = max3(ma.x, va0.x, va1.x);
         ma.y = max3(ma.y, va0.y, va1.y);
         ma.z = max3(ma.z, va0.z, va1.z);
@@ -1996,6 +2020,7 @@ __device__ __forceinline__ void gather_max2(const float* __restrict__ A4, const 
 }
 
 // one row (the last, unpaired group of a wave)
+template <bool BYTES = false>
 __device__ __forceinline__ void gather_max1(const float* __restrict__ A4, const unsigned short* __restrict__ nwa, int k, float4& ma) {
     ma = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
     const int kw = (k + 1) >> 1;
@@ -2004,8 +2029,8 @@ __device__ __forceinline__ void gather_max1(const float* __restrict__ A4, const 
         const bool odd = 2 * q + 1 < k;
         int a0, a1;
         nbr_pair(nwa, q, odd, a0, a1);
-        const float4 va0 = *reinterpret_cast<const float4*>(A4 + a0);
-        const float4 va1 = *reinterpret_cast<const float4*>(A4 + a1);
+        const float4 va0 = nbr_row<BYTES>(A4, a0);
+        const float4 va1 = nbr_row<BYTES>(A4, a1);
         ma.x = max3(ma.x, va0.x, va1.x);
         ma.y = max3(ma.y, va0.y, va1.y);
         ma.z = max3(ma.z, va0.z, va1.z);
@@ -2334,11 +2359,22 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
     if constexpr (LEAN != 0) lean_fixed_layout(plan_local, DBG == 0, LEAN);
     const EmbedPlan& p = plan_local;
     float vmax = 0.f;                                    // FMT_H2: largest magnitude stored into the f16 planes
+    // lean production instances: keys in registers, selection by the wave that owns the rows (select_owned).  Their squared
+    // norms carry +inf for the slots [N, NP) the graph does not have, like the big instance's (OwnedKeys / select_owned rank
+    // those slots last without an index test)
+    constexpr bool kOwned = SGPR_OWNED_SELECT != 0 && LEAN != 0 && DBG == 0 && FMT == FMT_H2 && KC == 10;
     const int NT = LEAN != 0 ? kLeanNT : (int)blockDim.x, NW = NT >> 6;   // 64 .. 512 threads (EmbedPlan::nt); lean: a constant
     unsigned char* X = smem + p.offX;                    // [NP][XROW]: bf16 planes (or fp32 rows) / in-place fp32 b
     constexpr int XROW = xrow<FMT>();
     float* A = reinterpret_cast<float*>(smem + p.offA);
     float* D = reinterpret_cast<float*>(smem + p.offD);
+    // squared norms of the rows of X.  INVARIANT of the kOwned instances (and of BIG): whenever a non-coordinate layer's
+    // selection runs, xx[j] = +inf for EVERY slot j in [N, NP) - select_owned tests no index, an absent slot is kept out of
+    // the neighbour sets by its key alone.  Whoever fills xx for such a layer writes all of [0, NP): (1) the generic
+    // staging of layer 0 (rows [0, NP)); (2) the gather epilogue of a layer with want_norm - its row groups cover
+    // [0, nq), nq = N rounded up to the group, the padded rows inside a group get +inf; (3) the zero-fill loop behind that
+    // gather covers [nq, NP).  A new writer of xx must do the same.  (The gather ablation, skip & 8, leaves xx stale:
+    // its results are timing only, like every ablation's.)
     float* xx = reinterpret_cast<float*>(smem + p.offXX);
     float* red = reinterpret_cast<float*>(smem + p.offRed);
     unsigned short* nbr = reinterpret_cast<unsigned short*>(smem + p.offIdx);
@@ -2473,25 +2509,41 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
             for (int c = 0; c < kLabels; ++c) ref[3 + c] = sem[c];
         }
         __syncthreads();
-        bool same = tid < NS && fx == ref[0] && fy == ref[1] && fz == ref[2];
+        // (the 15 values in four 16-byte reads, and `&` on the comparisons, not `&&`: a short-circuit chain compiles to an LDS
+        //  read, a wait and a branch around the rest per channel)
+        // (`pro` starts on a 16-byte boundary in every plan: red = the start of the dynamic LDS, offRed = offX = 0 in
+        //  lean_fixed_layout, plan_layout and plan_big; A = offA, a sum of multiples of 16.  The sixteenth float of the
+        //  record is read and never written or used.)
+        static_assert(kLabels == 12, "the last slot's record is four float4");
+        float refv[16];
 #pragma unroll
-        for (int c = 0; c < kLabels; ++c) same = same && (sem[c] == ref[3 + c]);
-        const unsigned long long differs = __ballot(tid < NS && !same);
-        const unsigned long long neg = __ballot(tid < NS && mylab < 0), not_pad = __ballot(tid < NS && mylab != -1);
-        unsigned long long lab_mine = 0ull;                 // lane c < 12 keeps the ballot of label c
-#pragma unroll
-        for (int c = 0; c < kLabels; ++c) {
-            const unsigned long long mk = __ballot(tid < NS && mylab == c);
-            lab_mine = lane == c ? mk : lab_mine;
+        for (int q = 0; q < 4; ++q) {
+            const float4 r4 = reinterpret_cast<const float4*>(ref)[q];
+            refv[4 * q] = r4.x, refv[4 * q + 1] = r4.y, refv[4 * q + 2] = r4.z, refv[4 * q + 3] = r4.w;
         }
+        bool same = (tid < NS) & (fx == refv[0]) & (fy == refv[1]) & (fz == refv[2]);
+#pragma unroll
+        for (int c = 0; c < kLabels; ++c) same = same & (sem[c] == refv[3 + c]);
+        // (every wave is whole here: the ballot of a comparison IS the comparison's lane mask - __ballot takes an int and
+        //  rebuilds the mask from it, two more vector instructions per ballot; and the twelve wave-uniform label masks go
+        //  to the LDS from lane 0 beside the other three, not through "lane c keeps mask c": a comparison of the lane id and
+        //  two selects per label)
+        const bool slot = tid < NS;
+        const unsigned long long differs = __builtin_amdgcn_ballot_w64(slot & !same);
+        const unsigned long long neg = __builtin_amdgcn_ballot_w64(slot & (mylab < 0));
+        const unsigned long long not_pad = __builtin_amdgcn_ballot_w64(slot & (mylab != -1));
+        unsigned long long lab_mask[kLabels];               // slots of this wave that carry label c
+#pragma unroll
+        for (int c = 0; c < kLabels; ++c) lab_mask[c] = __builtin_amdgcn_ballot_w64(slot & (mylab == c));
         // (slots sit in the first NS / 64 <= 8 waves; the big instance runs up to 16)
         const int NWI = NW < 8 ? NW : 8;
         if (lane == 0 && wave < NWI) {
             wmax[wave] = differs ? wave * 64 + 63 - __clzll((long long)differs) : -1;
             negm[wave] = neg;
             nm1[wave] = not_pad;
+#pragma unroll
+            for (int c = 0; c < kLabels; ++c) labm[wave * kLabels + c] = lab_mask[c];
         }
-        if (lane < kLabels && wave < NWI) labm[wave * kLabels + lane] = lab_mine;
         __syncthreads();
         int last = -1;
 #pragma unroll
@@ -2499,12 +2551,15 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
         nd = last + 1;
         // (nd <= NS - 1: the last slot equals itself)  slots before the trailing run, per wave, as lane masks
         any_bad = ((nm1[nd >> 6] >> (nd & 63)) & 1ull) != 0ull;       // the run's first slot is not padding
+        // (lanes 12..63 count label 0 again and nobody reads their count: an index clamp, not an exec mask per wave slot;
+        //  `|`, not `||`: no branch per wave slot either)
+        const int ll = lane < kLabels ? lane : 0;
 #pragma unroll
         for (int q = 0; q < NWI; ++q) {
             const int nb = min(max(nd - 64 * q, 0), 64);
             const unsigned long long below = nb >= 64 ? ~0ull : ((1ull << nb) - 1ull);
-            any_bad = any_bad || (negm[q] & below) != 0ull;
-            if (lane < kLabels) my_label_count += __popcll(labm[q * kLabels + lane] & below);
+            any_bad = any_bad | ((negm[q] & below) != 0ull);
+            my_label_count += __popcll(labm[q * kLabels + ll] & below);
         }
         const int m = NS - nd;
         // m >= k copies: ONE representative slot is enough (a row can take at most k copies, and once a row
@@ -2663,7 +2718,7 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
             xstore<FMT>(xr, 4, live ? make_float4(sem[4], sem[5], sem[6], sem[7]) : z4, vmax);
             xstore<FMT>(xr, 8, live ? make_float4(sem[8], sem[9], sem[10], sem[11]) : z4, vmax);
             xzero<FMT>(xr, 12);
-            xx[tid] = live ? s : 0.f;
+            xx[tid] = live ? s : (kOwned ? INFINITY : 0.f);
         }
     }
     __syncthreads();
@@ -2702,7 +2757,6 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
         int32_t* dbg_knn = dbg_knn_all ? dbg_knn_all + ((size_t)g * 6 + Ldump) * NS * p.k : nullptr;
         // ---- kNN keys (Gram on MFMA) -> selection, one chunk of rows at a time (a single chunk, upper-triangular
         //      tiles mirrored, when the whole key matrix is resident)
-        constexpr bool kOwned = SGPR_OWNED_SELECT != 0 && LEAN != 0 && DBG == 0 && FMT == FMT_H2 && KC == 10;
         // the 64-row production instance (128 registers per lane at four workgroups per CU, ~90 in use): the weights of
         // this wave's first column tile of the layer's GEMMs are requested BEFORE the selection
         constexpr bool kWPre = SGPR_WPREFETCH != 0 && kOwned && LEAN == 64 && SGPR_LEAN_WAVES == 4;
@@ -2756,7 +2810,9 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
             // lean production instances: keys in registers, selection right behind them, no barrier until the GEMMs' own
             // (A is written only by the GEMM phase and nothing reads it here; b replaces X behind gemm_cols' barrier, which
             // every wave reaches after its selection)
-            select_owned<FMT>(p, N, nrt, one_rep, X, xx, nbr, wave, L == 3);
+            // (ablation bit 0, as on the other plans: no selection - only together with bit 3, the gather, which would
+            //  read the lists nobody wrote: mask 9 against mask 8 is what keys + Gram tiles + selection cost)
+            if (!(skip & 1) || !(skip & 8)) select_owned<FMT>(p, N, nrt, one_rep, X, xx, nbr, wave, L == 3);
         }
         for (int rc0 = 0; !kOwned && !BIG && rc0 < NP; rc0 += p.RC) {
             const int rows_chunk = min(p.RC, NP - rc0);
@@ -2852,9 +2908,9 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
                 const int ra = min(ia, N - 1), rb = TWO ? min(ib, N - 1) : ra;   // padded rows: compute a real row
                 float4 ma, mb;
                 if constexpr (TWO) {
-                    gather_max2(A + c4, nbr + ra * p.kpitch, nbr + rb * p.kpitch, k, ma, mb);
+                    gather_max2<kOwned>(A + c4, nbr + ra * p.kpitch, nbr + rb * p.kpitch, k, ma, mb);
                 } else {
-                    gather_max1(A + c4, nbr + ra * p.kpitch, k, ma);
+                    gather_max1<kOwned>(A + c4, nbr + ra * p.kpitch, k, ma);
                     mb = ma;
                 }
                 // padded rows (>= N) inside a partly real group simply keep a copy of row N-1: they are never candidates
@@ -2901,8 +2957,8 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
                     }
                     if (ggrp ? c4 == 0 : (lane & 15) == 0) {
                         // (big instance: +inf for the slots the graph does not have - OwnedKeys ranks them last without an index test)
-                        xx[ia] = (!BIG || ia < N) ? sa : INFINITY;
-                        if (TWO) xx[ib] = (!BIG || ib < N) ? sb : INFINITY;
+                        xx[ia] = (!(BIG || kOwned) || ia < N) ? sa : INFINITY;
+                        if (TWO) xx[ib] = (!(BIG || kOwned) || ib < N) ? sb : INFINITY;
                     }
                 }
             };
@@ -2938,8 +2994,10 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
             if (!BIG && L != 2 && !(skip & 8)) {
                 constexpr int QW = (FMT == FMT_BF3 ? 384 : 256) / 16;        // 16-byte pieces per row
                 const int nq = (N + rpw - 1) & ~(rpw - 1);
-                for (int e = tid; e < (NP - nq) * QW; e += NT)
+                for (int e = tid; e < (NP - nq) * QW; e += NT) {
                     *reinterpret_cast<uint4*>(X + (nq + e / QW) * XROW + (e % QW) * 16) = make_uint4(0u, 0u, 0u, 0u);
+                    if (kOwned && want_norm && e % QW == 0) xx[nq + e / QW] = INFINITY;
+                }
             }
         }
         __syncthreads();
@@ -3067,9 +3125,9 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
         float s = 0.f;
         for (int q = 0; q < NPART; ++q) s += red[q * 32 + tid];
         mean[tid] = s / (float)NS;
-    }
-    __syncthreads();
-    if (tid < 32) {
+        // (the 32 lanes that wrote the means are the 32 that read them, in one wave: the LDS keeps a wave's accesses in
+        //  program order, so no workgroup barrier stands between the two steps)
+        group_sync<true>();
         float gc = 0.f;
         if (SGPR_ATT_PREFETCH) {
 #pragma unroll
