@@ -1,7 +1,8 @@
-"""The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h).
+"""The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h),
+and the refinement of the poses on that map (include/sgpr_landmark_refine.h).
 
-The entry points are declared in the fourth public header; this module has engine.bind_header parse it and set the
-signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
+The entry points are declared in the fourth and fifth public headers; this module has engine.bind_header parse them and
+set the signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
 
@@ -15,6 +16,8 @@ _ABI = engine.public_header(os.path.basename(HEADER))
 _C = _ABI.constants
 
 ABI_SYMBOLS = [name for name, _, _ in _ABI.functions]
+REFINE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_refine.h")
+REFINE_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(REFINE_HEADER)).functions]
 MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
 DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
 DEFAULT_MAX_LANDMARKS = 1 << 22          # the default capacity is G N, capped here; build() re-runs past it
@@ -22,8 +25,10 @@ _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L floa
 
 
 def load_library():
-    """engine.load_library() with the signatures of include/sgpr_landmarks.h set on it"""
+    """engine.load_library() with the signatures of include/sgpr_landmarks.h and include/sgpr_landmark_refine.h set on
+    it"""
     engine.bind_header(os.path.basename(HEADER))
+    engine.bind_header(os.path.basename(REFINE_HEADER))
     return engine.load_library()
 
 
@@ -122,6 +127,76 @@ def select(lm, min_count=1, min_sessions=1):
     """mask bool [L] of the landmarks with at least min_count observations, seen by at least min_sessions sessions"""
     count = torch.as_tensor(lm["count"])
     return (count >= int(min_count)) & (_popcount64(lm["sessions"]).to(count.device) >= int(min_sessions))
+
+
+def refine_workspace_bytes(G, N, L):
+    return int(load_library().sgpr_landmark_refine_workspace_bytes(int(G), int(N), int(L)))
+
+
+def refine_async(centers, labels, poses, lm, use=None, fixed=None, iters=10, min_nodes=6, workspace=None, device=None):
+    """sgpr_landmark_refine without reading anything back -> dict of device tensors, asynchronous on the current stream:
+    poses f64 [G,4], cost f64 [iters+1], info i32 [4] = (used nodes and landmarks observed at the end, scans the last fit
+    re-fitted, free scans it kept).  centers f32 [G,N,3], labels i32 [G,N] (its shape is all that is read: the landmark
+    of a node decides), poses [G,4] planar; lm: the dict of build / build_async made on THOSE poses ("node_landmark",
+    and "count" for the number of landmarks); use: a mask over the landmarks (select makes one; None: all of them);
+    fixed: a mask over the scans that keep their pose (None: no scan).  workspace: a uint8 device tensor of at least
+    refine_workspace_bytes(G, N, L) to reuse."""
+    lib = load_library()
+    if device is None:
+        device = engine._device_of(centers, poses, lm["node_landmark"])
+    node = engine._on(lm["node_landmark"], device, torch.int32)
+    if node.dim() != 2 or tuple(node.shape) != tuple(torch.as_tensor(labels).shape):
+        raise ValueError("landmarks.refine: node_landmark and labels must be [G, N]")
+    g, n = node.shape
+    cen = engine._on(centers, device, torch.float32)
+    if cen.numel() != g * n * 3:
+        raise ValueError("landmarks.refine: centers must be [G, N, 3]")
+    x = engine._on(poses, device, torch.float64)
+    if x.numel() != g * 4:
+        raise ValueError("landmarks.refine: poses must hold one planar pose (c, s, x, y) per scan")
+    n_lm = int(torch.as_tensor(lm["count"]).shape[0])
+    if use is None:
+        mask = torch.ones(n_lm, dtype=torch.uint8, device=device)
+    else:
+        mask = engine._on(torch.as_tensor(use).reshape(-1) != 0, device, torch.bool).to(torch.uint8)
+        if mask.numel() != n_lm:
+            raise ValueError("landmarks.refine: use must hold one entry per landmark")
+    fix = None
+    if fixed is not None:
+        fix = engine._on(torch.as_tensor(fixed).reshape(-1) != 0, device, torch.bool).to(torch.uint8)
+        if fix.numel() != g:
+            raise ValueError("landmarks.refine: fixed must hold one entry per scan")
+    t = int(iters)
+    out = {"poses": torch.empty(g, 4, dtype=torch.float64, device=device),
+           "cost": torch.full((max(t, 0) + 1,), float("nan"), dtype=torch.float64, device=device),
+           "info": torch.zeros(4, dtype=torch.int32, device=device)}          # (G N == 0: the call writes nothing)
+    need = refine_workspace_bytes(g, n, n_lm)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks.refine: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_refine(
+            engine._ptr(cen), g, n, engine._ptr(x), engine._ptr(node), engine._ptr(mask), n_lm, engine._ptr(fix), t,
+            int(min_nodes), engine._ptr(out["poses"]), engine._ptr(out["cost"]), engine._ptr(out["info"]),
+            engine._ptr(workspace), workspace.numel(), engine._stream(device)))
+    if g * n == 0:
+        out["poses"].copy_(x.reshape(g, 4))
+    return out
+
+
+def refine(centers, labels, poses, lm, use=None, fixed=None, iters=10, min_nodes=6, workspace=None, device=None):
+    """Refine the planar poses of G scans on the landmark map `lm` that build made on them: `iters`
+    alternations of "a landmark's centre is the mean of its observations" and "every scan is re-fitted rigidly to the
+    centres of its nodes' landmarks", all scans of a step against the same centres.  Arguments as refine_async; a scan
+    with fewer than min_nodes nodes on the landmarks in use keeps its pose.
+    -> (poses f64 [G,4] on the device, info dict: cost (numpy float64 [iters+1], the RMS distance in metres of the
+    observations to their centres before every step and at the end), used_nodes, landmarks, refitted, kept)."""
+    out = refine_async(centers, labels, poses, lm, use=use, fixed=fixed, iters=iters, min_nodes=min_nodes,
+                       workspace=workspace, device=device)
+    used, seen, refit, kept = (int(v) for v in out["info"].tolist())
+    return out["poses"], {"cost": out["cost"].cpu().numpy(), "used_nodes": used, "landmarks": seen, "refitted": refit,
+                          "kept": kept}
 
 
 def virtual_scans(lm, poses, sensor_range=50.0, node_num=100, keep=None):

@@ -78,6 +78,11 @@ center, label, count, first, sessions, spread per landmark, node_landmark [M,N],
 poses and the parameters; printed are the landmarks with two or more observations, their sharpness, the share seen by
 two or more sessions and the share of single observations (metrics.map_sharpness), and after --optimize the same four
 on the poses before optimisation.
+With --landmarks --refine [--refine-rounds R] [--refine-iters T] the poses the run ends with are first refined on the map's
+own landmarks (SG.refine_map, landmarks.refine): R rounds (default 2) of landmark map, the landmarks with
+two or more observations, T alternations (default 10) of centre means and closed-form pose fits, the first scan fixed.
+Printed are landmarks, sharpness and shared before and after and the trajectory error against the sequence's own poses
+before and after; the landmark map above is then the one on the refined poses, and --save-poses FILE gets them.
 """
 import argparse
 import math
@@ -428,6 +433,13 @@ def main(argv=None):
                     help="with --landmarks: ... and within Z metres in height")
     ap.add_argument("--lm-min-sessions", type=int, default=1, metavar="S",
                     help="with --landmarks: report the landmarks seen by at least S sessions as kept (1..64)")
+    ap.add_argument("--refine", action="store_true",
+                    help="with --landmarks: refine the poses the run ends with on the map's own landmarks (DESIGN.md "
+                         "§29) before the landmark map is written; --save-poses then gets the refined poses")
+    ap.add_argument("--refine-rounds", type=int, default=2, metavar="R",
+                    help="with --refine: rounds of (landmark map, select, refine)")
+    ap.add_argument("--refine-iters", type=int, default=10, metavar="T",
+                    help="with --refine: alternations of centre means and pose fits per round")
     ap.add_argument("--max-trans", type=float, default=1.0, metavar="M",
                     help="with --consistent: translation tolerance of a pair of closures, metres")
     ap.add_argument("--max-yaw-deg", type=float, default=math.degrees(0.06), metavar="D",
@@ -456,7 +468,11 @@ def main(argv=None):
         ap.error("--consistent needs --verify")
     if opt.optimize and not opt.consistent:
         ap.error("--optimize needs --consistent")
-    if opt.save_poses is not None and not opt.optimize:
+    if opt.refine and not opt.landmarks:
+        ap.error("--refine needs --landmarks")
+    if opt.refine and not (opt.refine_rounds >= 1 and opt.refine_iters >= 0):
+        ap.error("--refine-rounds must be >= 1, --refine-iters >= 0")
+    if opt.save_poses is not None and not (opt.optimize or opt.refine):
         ap.error("--save-poses needs --optimize")
     if opt.consistent and (opt.max_trans < 0 or opt.lever_gain < 0 or not 0 <= opt.max_yaw_deg <= 180):
         ap.error("--max-trans and --lever-gain must be >= 0, --max-yaw-deg in 0..180")
@@ -557,7 +573,20 @@ def main(argv=None):
                     np.save(f, out)
         if opt.landmarks:
             starts = creport["session_starts"] if opt.consistent else None
-            mreport = landmark_lists(trainer.model, seq, out if opt.optimize else None, sessions=starts,
+            if opt.refine:
+                rreport = refine_lists(trainer.model, seq, out if opt.optimize else None, sessions=starts,
+                                       rounds=opt.refine_rounds, iters=opt.refine_iters, radius=opt.lm_radius,
+                                       tau_z=opt.lm_tau_z)
+                out = rreport["poses"]
+                print("sequence", sequence, "refined on its landmarks, %d x %d iterations:" % (opt.refine_rounds, opt.refine_iters),
+                      "landmarks %d -> %d, sharpness %.4f m -> %.4f m, shared %.4f -> %.4f,"
+                      % tuple(rreport[a + n] for n in ("landmarks", "sharpness", "shared") for a in ("before_", "")),
+                      "trajectory error %.4f m -> %.4f m," % (rreport["before_trajectory_error"], rreport["trajectory_error"]),
+                      "%d of %d scans re-fitted" % (int(rreport["refitted"]), m))
+                if opt.save_poses is not None:
+                    with open(opt.save_poses, "wb") as f:
+                        np.save(f, out)
+            mreport = landmark_lists(trainer.model, seq, out if opt.optimize or opt.refine else None, sessions=starts,
                                      before=opt.optimize, radius=opt.lm_radius, tau_z=opt.lm_tau_z,
                                      min_sessions=opt.lm_min_sessions)
             np.savez(os.path.join(args.output_path, sequence + "_landmarks.npz"), **mreport)
@@ -800,6 +829,26 @@ def localize_lists(model, seq, values, indices, min_inliers, seq_len=1, min_supp
     out.update({"indices": idx_h, "refined": refined, "verify_flags": ver["flags"].cpu().numpy(),
                 "verify_accept": ver["accept"].cpu().numpy(), "seq_len": np.int64(seq_len),
                 "min_support": np.int64(min_support), "max_trans": np.float64(max_trans), "max_yaw": np.float64(max_yaw)})
+    return out
+
+
+def refine_lists(model, seq, poses=None, sessions=None, rounds=2, iters=10, radius=0.75, tau_z=0.75):
+    """The planar `poses` [M,4] of `seq` - None: the sequence's own - refined on the map's landmarks (SG.refine_map) with
+    `sessions` as the session table of its frames.
+    -> dict: poses f64 [M,4] (numpy), cost [rounds, iters+1], refitted (scans the last fit moved), the figures landmarks,
+    sharpness, shared (metrics.map_sharpness) and trajectory_error (metrics.trajectory_error against the sequence's own
+    poses) of the refined map, and the same four with the prefix before_."""
+    own = metrics.planar_odometry(seq.poses)
+    X = own if poses is None else np.asarray(poses, dtype=np.float64).reshape(-1, 4)
+    kw = dict(sessions=sessions, radius=radius, tau_z=tau_z)
+    first = metrics.map_sharpness(model.landmark_map(seq.centers, seq.labels, X, **kw))
+    Y, lm, costs = model.refine_map(seq.centers, seq.labels, X, rounds=rounds, iters=iters, **kw)
+    Y = Y.cpu().numpy()
+    out = {"poses": Y, "cost": np.stack(costs), "refitted": np.int64((Y != X).any(axis=1).sum()),
+           "trajectory_error": metrics.trajectory_error(Y, own), "before_trajectory_error": metrics.trajectory_error(X, own)}
+    last = metrics.map_sharpness(lm)
+    out.update({n: last[n] for n in ("landmarks", "sharpness", "shared")})
+    out.update({"before_" + n: first[n] for n in ("landmarks", "sharpness", "shared")})
     return out
 
 

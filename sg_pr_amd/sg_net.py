@@ -367,6 +367,33 @@ class SG(torch.nn.Module):
         x = poses if isinstance(poses, torch.Tensor) and poses.dim() == 2 and poses.shape[1] == 4 else _planar(poses)
         return _landmarks.build(centers, labels, x, starts=sessions, device=self.engine().device, **kw)
 
+    def refine_map(self, centers, labels, poses, sessions=None, rounds=2, iters=10, min_count=2, min_sessions=1,
+                   fixed=None, min_nodes=6, **landmark_kw):
+        """Refine the poses of a map on its own landmarks (landmarks.refine): `rounds` times, the landmark
+        map is built on the current poses (landmark_map), the landmarks with at least min_count observations from at
+        least min_sessions sessions are selected (landmarks.select), and `iters` alternations of centre means and
+        closed-form pose fits move every scan onto them; a final landmark map is built on the result.  Re-associating
+        between the rounds lets landmarks that drift had merged or split come right.
+        centers [M,N,3], labels [M,N]; poses: KITTI rows [M,12] or planar [M,4], e.g. what optimize_map returned;
+        sessions: the session table of the scans (None: one session); fixed: a mask over the scans that keep their pose
+        (None: the first scan of the first session); landmark_kw: radius, tau_z of landmarks.build.
+        -> (planar poses f64 [M,4] device tensor, the dict of landmark_map on them, [numpy cost array per round])."""
+        from . import landmarks as _landmarks
+        dev = self.engine().device
+        x = poses if isinstance(poses, torch.Tensor) and poses.dim() == 2 and poses.shape[1] == 4 else _planar(poses)
+        x = _engine._on(x, dev, torch.float64)
+        if fixed is None:
+            fixed = torch.zeros(x.shape[0], dtype=torch.bool, device=dev)
+            fixed[:1] = True
+        costs = []
+        for _ in range(int(rounds)):
+            lm = _landmarks.build(centers, labels, x, starts=sessions, device=dev, **landmark_kw)
+            use = _landmarks.select(lm, min_count=min_count, min_sessions=min_sessions)
+            x, info = _landmarks.refine(centers, labels, x, lm, use=use, fixed=fixed, iters=iters, min_nodes=min_nodes,
+                                        device=dev)
+            costs.append(info["cost"])
+        return x, _landmarks.build(centers, labels, x, starts=sessions, device=dev, **landmark_kw), costs
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming
