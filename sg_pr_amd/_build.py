@@ -26,7 +26,7 @@ SOURCES = ["sgpr_embed.hip", "sgpr_score.hip", "sgpr_metrics.hip", "sgpr_modules
            "sgpr_seq.hip", "sgpr_peak.hip", "sgpr_verify.hip", "sgpr_consistency.hip", "sgpr_api.hip", "sgpr_posegraph.hip",
            "sgpr_localize.hip", "sgpr_landmarks.hip", "sgpr_landmark_refine.hip"]
 HEADERS = [os.path.join(REPO, "include", "sgpr.h"), os.path.join(CSRC, "sgpr_internal.hpp"),
-           os.path.join(CSRC, "sgpr_model.hpp"), os.path.join(CSRC, "sgpr_map.hpp"),
+           os.path.join(CSRC, "sgpr_model.hpp"), os.path.join(CSRC, "sgpr_map.hpp"), os.path.join(CSRC, "sgpr_eval.hpp"),
            os.path.join(REPO, "include", "sgpr_localize.h"), os.path.join(REPO, "include", "sgpr_landmarks.h"),
            os.path.join(REPO, "include", "sgpr_landmark_refine.h"), os.path.join(REPO, "include", "sgpr_posegraph.h")]
 MAX_COMPILERS = 16     # compilers at once: one per source, up to this many

@@ -1806,9 +1806,9 @@ static PairTruth eval_truth(int row0, const double* pose, double d_pos, double d
     return t;
 }
 
-// head of sgpr_score_threshold_counts' row-block path: the block's d_out [T + 3] u64 | its counting slabs
+// head of sgpr_score_threshold_counts' row-block path: the counting slabs (every block's counts fold into d_out)
 static size_t counts_head_bytes(const sgpr_handle* h, int T) {
-    return a256((size_t)(T + 3) * 8) + a256(sgpr_pair_threshold_counts_workspace_bytes(h, T));
+    return a256(sgpr_pair_threshold_counts_workspace_bytes(h, T));
 }
 
 size_t sgpr_score_positives_workspace_bytes(const sgpr_handle* h, int R, int M) {
@@ -1881,14 +1881,12 @@ int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows
                                  groups_per_threshold, d_at_least, d_out, d_workspace, s);
     hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_threshold_counts: memset");
-    const size_t part_bytes = a256((size_t)(T + 3) * 8), slab_bytes = sgpr_pair_threshold_counts_workspace_bytes(h, T);
     auto count = [&](const float* block, unsigned char* head, int r0, int n) {
-        unsigned long long* part = reinterpret_cast<unsigned long long*>(head);
-        const int rc = sgpr_pair_threshold_counts(h, block, n, M, M, row0 + r0, d_pose_xz, d_pos, d_neg,
-                                                  truth.gt ? truth.gt + (int64_t)r0 * ldg : nullptr, ldg, d_thresholds, T,
-                                                  d_rank, groups_per_threshold, d_at_least, part, head + part_bytes,
-                                                  slab_bytes, stream);
-        return rc != SGPR_OK ? rc : launch_eval_add(d_out, part, T + 3, s);
+        PairTruth tb = truth;
+        tb.row0 = row0 + r0;
+        if (tb.gt) tb.gt += (int64_t)r0 * ldg;
+        return launch_pair_counts_more(h, block, n, M, M, tb, d_thresholds, T, d_rank, groups_per_threshold, d_at_least,
+                                       d_out, reinterpret_cast<unsigned*>(head), 1, s);
     };
     return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, counts_head_bytes(h, T), d_workspace, workspace_bytes,
                             stream, count);
@@ -1917,7 +1915,7 @@ static bool seq_eval_query_ok(const sgpr_handle* h, int R, int M, int ctx, int L
     return seq_query_ok(h, R, M, ctx, L, flags) && !(flags & SGPR_TOPK_CAUSAL);
 }
 
-// head of the two calls: the call's f16 range (a float4) | Q block [rb][M] | (counts) the block's d_out and slabs
+// head of the two calls: the call's f16 range (a float4) | Q block [rb][M] | (counts) the counting slabs
 static size_t seq_eval_head_bytes(int R, int M, int L) {
     return 256 + a256((size_t)score_block_rows(R, M, L - 1) * M * sizeof(float));
 }
@@ -2014,15 +2012,13 @@ int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_
     hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_seq_threshold_counts: memset");
     if (R == ctx || M == 0) return SGPR_OK;
-    const signed char* gt = d_pose_xz ? nullptr : d_gt;
-    const size_t part_bytes = a256((size_t)(T + 3) * 8), slab_bytes = sgpr_pair_threshold_counts_workspace_bytes(h, T);
+    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
     auto count = [&](const float* q, unsigned char* tail, int first, int no) {
-        unsigned long long* part = reinterpret_cast<unsigned long long*>(tail);
-        const int rc = sgpr_pair_threshold_counts(h, q, no, M, M, row0 + first, d_pose_xz, d_pos, d_neg,
-                                                  gt ? gt + (int64_t)(first - ctx) * ldg : nullptr, ldg, d_thresholds, T,
-                                                  d_rank, groups_per_threshold, d_at_least, part, tail + part_bytes,
-                                                  slab_bytes, stream);
-        return rc != SGPR_OK ? rc : launch_eval_add(d_out, part, T + 3, s);
+        PairTruth tb = truth;
+        tb.row0 = row0 + first;
+        if (tb.gt) tb.gt += (int64_t)(first - ctx) * ldg;
+        return launch_pair_counts_more(h, q, no, M, M, tb, d_thresholds, T, d_rank, groups_per_threshold, d_at_least, d_out,
+                                       reinterpret_cast<unsigned*>(tail), 1, s);
     };
     return seq_eval_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags,
                            seq_eval_head_bytes(R, M, L) + counts_head_bytes(h, T), d_workspace, workspace_bytes, stream,

@@ -336,16 +336,21 @@ int launch_session_above(const float* score, int R, int M, int64_t ld, int ctx, 
                          int64_t* row_ptr, int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status,
                          hipStream_t stream);
 // the fused evaluation epilogues of the all-pairs tail (production handle): T >= 0 the threshold counts (count == NULL,
-// d_out [T + 3]), T < 0 the positives (out [cap], count [2]); the chunked path of the other handles adds block counts up
+// d_out [T + 3]), T < 0 the positives (out [cap], count [2])
 size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T);
 int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const PairTruth& truth,
                       float* out, int64_t cap, unsigned long long* count, const float* thr, int T,
                       const sgpr_rank_group* rank, int gpt, const unsigned long long* at_least, unsigned long long* d_out,
                       void* ws, hipStream_t stream);
-int launch_eval_add(unsigned long long* out, const unsigned long long* in, int n, hipStream_t stream);
 // sgpr_pair_positives' kernel without clearing d_count: the appends of a row block continue the list (sgpr_metrics.hip)
 int launch_pair_positives_more(const sgpr_handle* h, const float* score, int R, int M, int64_t ld, const PairTruth& truth,
                                float* out, int64_t cap, unsigned long long* count, hipStream_t stream);
+// ... and sgpr_pair_threshold_counts' two kernels without its argument checks; accumulate: d_out [T + 3] keeps what the
+// row blocks before this one left in it.  slabs: sgpr_pair_threshold_counts_workspace_bytes(h, T)
+int launch_pair_counts_more(const sgpr_handle* h, const float* score, int R, int M, int64_t ld, const PairTruth& truth,
+                            const float* thr, int T, const sgpr_rank_group* rank, int gpt,
+                            const unsigned long long* at_least, unsigned long long* d_out, unsigned* slabs,
+                            int accumulate, hipStream_t stream);
 size_t score_pair_list_ws_bytes(int NR, int M);
 int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float* cols, int M, const int32_t* plan,
                            int NR, int NI, int64_t P, float* score, void* ws, hipStream_t stream, bool exact = false);

@@ -13,12 +13,14 @@
 //        (sg_pr_amd/metrics.py).  HBM-bound integer work: coalesced 16-B reads, no global atomics inside the loop.
 //  * sgpr_topk_rows       - loop-closure candidates: for every query row the K best-scoring columns outside a temporal
 //                           exclusion window, deterministic (score descending, column ascending).
+// Here: the kernels that read a resident matrix, the slab fold kernel and the entry points.  The counting steps, the
+// slab layout and the K dispatch of the lists are sgpr_eval.hpp's, shared with the fused epilogues of sgpr_score.hip.
 #include <math.h>
 #include <string.h>
 
 #include <string>
 
-#include "sgpr_internal.hpp"
+#include "sgpr_eval.hpp"
 
 namespace sgpr {
 
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(256) void pair_positives_kernel(const PairScan a, f
                 float s = 0.f;
                 if (pos[q]) {
                     s = a.score[(int64_t)r * a.ld + cc[q]];
-                    if (__float_as_uint(s) > 0x7f800000u) {          // negative or NaN: its order is undefined
+                    if (ev_bad(s)) {
                         ++nbad;
                         pos[q] = false;
                     }
@@ -115,50 +117,29 @@ __global__ __launch_bounds__(256) void pair_positives_kernel(const PairScan a, f
 struct CountArgs {
     PairScan scan;
     const float* thr;                    // [T] ascending thresholds (scores of positive pairs)
-    int T, Tp;                           // Tp = the power of two above T (thresholds padded with +inf in LDS)
-    // optional exact ranking of every negative among ALL distinct positive values (ROC area): bucket b > 0 of the
-    // thresholds holds the values rank[(b - 1) * gpt .. b * gpt), eight per record, thr[b - 1] the first of them
-    const sgpr_rank_group* rank;         // [T * gpt]
-    const unsigned long long* at_least;  // [T]: positive pairs with a value >= thr[q]
-    int gpt;
-    unsigned* slabs;                     // [gridDim.x][slab_words]: T + 1 counters (padded to even) | bad (u64) | rank sum (u64)
-    int slab_words;
-    const int* dT;                       // optional: T lives on the device (sgpr_f1_max: the thresholds are picked by a kernel);
-                                         // *dT < 0 = nothing to count (the launch returns without touching the slabs)
+    ThrView th;                          // (tree and cnt are the kernel's own LDS; at_least arrives in global memory)
+    unsigned* slabs;                     // [gridDim.x][slab_words(T)]
 };
 
 // ---- (3) negatives by threshold bucket; bucket b = #{q : thr[q] <= s}, so FP(>= thr[q]) = sum of buckets b > q.
 //      rank sum = sum over negatives of 2 #{positive pairs > s} + #{positive pairs == s}  (= 2 P N AUC)
-__global__ __launch_bounds__(PC_THREADS) void pair_threshold_count_kernel(const CountArgs a_in) {
+//      (the counting itself: sgpr_eval.hpp, shared with the fused epilogue of sgpr_score.hip)
+__global__ __launch_bounds__(PC_THREADS) void pair_threshold_count_kernel(const CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
-    CountArgs a = a_in;
-    if (a.dT) {                          // thresholds picked on the device: their number, too
-        const int t = *a.dT;
-        if (t < 0) return;
-        a.T = t;
-        a.Tp = 1;
-        while (a.Tp <= t) a.Tp <<= 1;
-    }
-    float* thr = reinterpret_cast<float*>(pc_smem);                       // [Tp]
-    unsigned* cnt = reinterpret_cast<unsigned*>(thr + a.Tp);              // [T + 1]
-    unsigned long long* at_least_lds = reinterpret_cast<unsigned long long*>(cnt + ((a.T + 2) & ~1));   // [T] (ranking only)
-    if (a.rank)
-        for (int i = threadIdx.x; i < a.T; i += PC_THREADS) at_least_lds[i] = a.at_least[i];
-    // the thresholds as a complete binary search tree in breadth-first order (node 1 = root, children 2k / 2k + 1),
-    // padded with +inf: the probes of one level are neighbours in LDS.  In the sorted array the probes of the upper
-    // levels sit a power of two >= 32 words apart - all lanes of a wave in ONE bank, a 64-way conflict per step.
-    const int lg = 31 - __clz(a.Tp);
-    for (int node = threadIdx.x; node < a.Tp; node += PC_THREADS) {
-        float v = INFINITY;
-        if (node > 0) {
-            const int l = 31 - __clz(node), i = node - (1 << l);
-            const int idx = (((2 * i + 1) << (lg - 1 - l))) - 1;          // position of the node's key in sorted order
-            if (idx < a.T) v = a.thr[idx];
-        }
-        thr[node] = v;
-    }
-    for (int i = threadIdx.x; i <= a.T; i += PC_THREADS) cnt[i] = 0u;
+    __shared__ unsigned long long tail[2];
+    ThrView t = a.th;
+    const int lg = thr_levels(t.T);
+    float* tree = reinterpret_cast<float*>(pc_smem);                                        // [1 << lg]
+    unsigned* cnt = reinterpret_cast<unsigned*>(tree + (1 << lg));                          // [T + 1]
+    unsigned long long* atl = reinterpret_cast<unsigned long long*>(cnt + slab_counters(t.T));   // [T] (ranking only)
+    if (t.rank)
+        for (int i = threadIdx.x; i < t.T; i += PC_THREADS) atl[i] = t.at_least[i];
+    thr_build_tree(tree, lg, a.thr, t.T, threadIdx.x, PC_THREADS);
+    for (int i = threadIdx.x; i <= t.T; i += PC_THREADS) cnt[i] = 0u;
     __syncthreads();
+    t.tree = tree;
+    t.cnt = cnt;
+    t.at_least = atl;
     const PairScan& sc = a.scan;
     // items = (row, group of 4 columns), row-major; a workgroup owns a contiguous range of them and its threads walk
     // it with stride PC_THREADS (lanes along the row), carrying (row, group) along instead of dividing per item
@@ -196,127 +177,50 @@ __global__ __launch_bounds__(PC_THREADS) void pair_threshold_count_kernel(const 
         for (int q = 0; q < 4; ++q) {
             const bool inb = c0 + q < sc.M;            // (no early exit: the wave counts together below)
             neg[q] = inb && classify_pair(sc.truth, r, inb ? c0 + q : sc.M - 1, px, pz, lo2, hi2) == 0;
-            if (neg[q] && __float_as_uint(s[q]) > 0x7f800000u) {          // negative or NaN
+            if (neg[q] && ev_bad(s[q])) {
                 ++nbad;
                 neg[q] = false;
             }
         }
-        // four independent branch-free descents of the tree (LDS), interleaved: right whenever the key is <= s; the
-        // leaf reached is the number of thresholds <= s
-        int b[4] = {1, 1, 1, 1};
-        for (int lvl = 0; lvl < lg; ++lvl) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b[q] = 2 * b[q] + ((thr[b[q]] <= s[q]) ? 1 : 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) b[q] -= a.Tp;
-        if (a.rank) {
-            // the bucket's values (and how many pairs carry each) arrive in ONE round of independent 16-byte loads from
-            // the L2-resident table, two elements at a time: pairs above s = pairs from the bucket's first value on
-            // - pairs of the bucket's values <= s
-#pragma unroll
-            for (int q0 = 0; q0 < 4; q0 += 2) {
-                unsigned le[2] = {0u, 0u}, eq[2] = {0u, 0u};
-                for (int gi = 0; gi < a.gpt; ++gi) {
-                    float4 v[2][2];
-                    uint4 m[2][2];
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int bq = min(b[q0 + e], a.T);
-                        const uint4* rec = reinterpret_cast<const uint4*>(a.rank + (size_t)max(bq - 1, 0) * a.gpt + gi);
-                        v[e][0] = *reinterpret_cast<const float4*>(rec);
-                        v[e][1] = *reinterpret_cast<const float4*>(rec + 1);
-                        m[e][0] = rec[2];
-                        m[e][1] = rec[3];
-                    }
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const float x = s[q0 + e];
-                        const float vv[8] = {v[e][0].x, v[e][0].y, v[e][0].z, v[e][0].w, v[e][1].x, v[e][1].y, v[e][1].z, v[e][1].w};
-                        const unsigned mm[8] = {m[e][0].x, m[e][0].y, m[e][0].z, m[e][0].w, m[e][1].x, m[e][1].y, m[e][1].z, m[e][1].w};
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            le[e] += vv[i] <= x ? mm[i] : 0u;
-                            eq[e] += vv[i] == x ? mm[i] : 0u;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int bq = min(b[q0 + e], a.T);
-                    // b == 0: s lies below every positive value, all P = at_least[0] pairs rank above it
-                    const unsigned long long gt_s = bq > 0 ? at_least_lds[bq - 1] - le[e] : at_least_lds[0];
-                    rank2 += neg[q0 + e] ? 2ull * gt_s + (bq > 0 ? eq[e] : 0u) : 0ull;
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int bq = min(b[q], a.T);
-            // wave-aggregated counting: sigmoid scores of negatives pile up in a few buckets, and 64 lanes hitting one
-            // LDS counter serialise.  Up to three rounds take the bucket of the first waiting lane with ONE atomic for all
-            // the lanes that share it; whoever is left counts on its own.
-            int idx = neg[q] ? bq : -1;
-            unsigned long long todo = __ballot(idx >= 0);
-#pragma unroll 1
-            for (int round = 0; round < 3 && todo; ++round) {
-                const int leader = __ffsll((long long)todo) - 1;
-                const int lidx = __shfl(idx, leader);
-                const unsigned long long same = __ballot(idx == lidx);
-                if ((int)(threadIdx.x & 63) == leader) atomicAdd(&cnt[lidx], (unsigned)__popcll(same));
-                if (idx == lidx) idx = -1;
-                todo &= ~same;
-                if (__popcll(same) < 4) break;           // scattered buckets: the rounds would only add instructions
-            }
-            if (idx >= 0) atomicAdd(&cnt[idx], 1u);
-        }
+        thr_count4<2>(t, s, neg, rank2);
     }
-    // per-workgroup results go to the workgroup's own slab (no global atomics); slab_sum_kernel adds the slabs up
-    __shared__ unsigned long long tail[2];
-    if (threadIdx.x == 0) tail[0] = tail[1] = 0ull;
-    __syncthreads();
-    if (a.rank) {
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) rank2 += __shfl_xor(rank2, m);
-        if ((threadIdx.x & 63) == 0 && rank2) atomicAdd(&tail[1], rank2);
-    }
-    if (nbad) atomicAdd(&tail[0], (unsigned long long)nbad);
-    __syncthreads();
-    unsigned* slab = a.slabs + (size_t)blockIdx.x * a.slab_words;
-    for (int i = threadIdx.x; i <= a.T; i += PC_THREADS) slab[i] = cnt[i];
-    if (threadIdx.x < 2) reinterpret_cast<unsigned long long*>(slab + a.slab_words - 4)[threadIdx.x] = tail[threadIdx.x];
+    thr_close(t, tail, nbad, rank2, a.slabs + (size_t)blockIdx.x * slab_words(t.T), threadIdx.x, PC_THREADS);
 }
 
-// out[i] = sum over the slabs: 32 counters per workgroup, 32 threads per counter (each sums every 32nd slab: one round
-// of independent loads), 128-B coalesced reads
+// out[i] (+)= sum over the slabs: 32 counters per workgroup, 32 threads per counter (each sums every 32nd slab: one
+// round of independent loads), 128-B coalesced reads.  accumulate: the row blocks after the first add to what the blocks
+// before them left in out.
 // out_t (optional): the sums once more in the order the F1 plan kernel reads them - counter i = t * per + q of thread t
 // at [q * 1024 + t] (one coalesced load per q instead of 192-byte strides between the lanes)
-__global__ __launch_bounds__(1024) void slab_sum_kernel(const unsigned* __restrict__ slabs, int n_slabs, int slab_words, int T,
-                                                        unsigned long long* __restrict__ out, const int* __restrict__ dT = nullptr,
-                                                        unsigned long long* __restrict__ out_t = nullptr, int per = 1) {
+__global__ __launch_bounds__(1024) void slab_fold_kernel(const unsigned* __restrict__ slabs, int n_slabs, int words, int T,
+                                                         unsigned long long* __restrict__ out, int accumulate,
+                                                         unsigned long long* __restrict__ out_t, int per) {
     __shared__ unsigned long long part[32][33];
-    if (dT) {
-        T = *dT;
-        if (T < 0) return;
-    }
     const int b = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const int i = blockIdx.x * 32 + b;                  // counters 0..T, then T+1 = bad, T+2 = rank sum
     unsigned long long s = 0ull;
     if (i <= T) {
 #pragma unroll 8
-        for (int q = grp; q < n_slabs; q += 32) s += slabs[(size_t)q * slab_words + i];
+        for (int q = grp; q < n_slabs; q += 32) s += slabs[(size_t)q * words + i];
     } else if (i <= T + 2) {
-        for (int q = grp; q < n_slabs; q += 32)
-            s += reinterpret_cast<const unsigned long long*>(slabs + (size_t)q * slab_words + slab_words - 4)[i - T - 1];
+        for (int q = grp; q < n_slabs; q += 32) s += slab_tail(slabs + (size_t)q * words, words)[i - T - 1];
     }
     part[grp][b] = s;
     __syncthreads();
     if (grp == 0 && i <= T + 2) {
 #pragma unroll
         for (int q = 1; q < 32; ++q) s += part[q][b];
-        out[i] = s;
+        out[i] = accumulate ? out[i] + s : s;
         if (out_t && i <= T) out_t[(size_t)(i % per) * 1024 + i / per] = s;
     }
+}
+
+int launch_slab_fold(const unsigned* slabs, int n_slabs, int words, int T, unsigned long long* out, int accumulate,
+                     unsigned long long* out_t, int per, hipStream_t stream) {
+    hipLaunchKernelGGL(slab_fold_kernel, dim3((unsigned)((T + 3 + 31) / 32)), dim3(1024), 0, stream, slabs, n_slabs, words, T,
+                       out, accumulate, out_t, per);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, "slab_fold_kernel launch");
 }
 
 // ------------------------------------------------------------------ F1-max in one call (sgpr_f1_max)
@@ -328,7 +232,7 @@ __global__ __launch_bounds__(1024) void slab_sum_kernel(const unsigned* __restri
 //                          atomic (bin = f1_key(score): a monotone map of the bit pattern with 5 mantissa bits of
 //                          resolution in s below 1/2 and in 1 - s above - sigmoid scores crowd towards 1), a positive is
 //                          appended to the (short) list of positive scores
-//   .  slab_sum_kernel     the workgroups' histograms added up
+//   .  slab_fold_kernel    the workgroups' histograms added up
 //   P  f1_plan_kernel      (one workgroup) positives by bin; suffix sums give exact (TP, FP) at every bin edge - each an
 //                          attained point of the curve - and for the positives INSIDE bin b the bound F1(TP(>= edge b),
 //                          FP(>= edge b+1)); the bins whose bound beats the best edge value are the candidates: their
@@ -336,7 +240,7 @@ __global__ __launch_bounds__(1024) void slab_sum_kernel(const unsigned* __restri
 //                          with TP exact for each of them
 //   B  f1_refine_kernel    second streaming pass: a negative outside the candidate bins costs one bit test; inside, a
 //                          bisection among the thresholds and one LDS atomic
-//   .  slab_sum_kernel
+//   .  slab_fold_kernel
 //   F  f1_final            (the workgroup of pass B that finishes last) exact FP, hence exact F1, at every threshold; the
 //                          maximum with the edge values is exact.
 // Everything the steps decide lives in a control block on the device; the host reads 8 doubles at the end.  Rectangles
@@ -683,7 +587,7 @@ __global__ __launch_bounds__(F1_THREADS) void f1_scan_kernel(const PairScan sc, 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float x = cur.s[u][q];
-                const bool usable = __float_as_uint(x) <= 0x7f800000u;      // not negative, not NaN
+                const bool usable = !ev_bad(x);
                 if (cls[q] == 0) {
                     if (usable) atomicAdd(&hist[f1_key(x)], 1u);
                     else ++bad_neg;
@@ -830,8 +734,8 @@ __global__ __launch_bounds__(F1_THREADS) void f1_scan_kernel(const PairScan sc, 
         hist[i] = 0u;
     }
     if (tid == 0) {
-        reinterpret_cast<unsigned long long*>(slab + slab_words - 4)[0] = nbad_neg;
-        reinterpret_cast<unsigned long long*>(slab + slab_words - 4)[1] = 0ull;
+        slab_tail(slab, slab_words)[0] = nbad_neg;
+        slab_tail(slab, slab_words)[1] = 0ull;
     }
     F1A_STAMP(5)
     // The positives by bin, for the plan kernel: the workgroup's are counted in the (now free) histogram first and leave
@@ -936,7 +840,7 @@ constexpr int f1_max3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b
 constexpr int F1_PLAN_WORDS = (f1_max3(F1_NBP, F1_PER * F1_THREADS, 2 * F1_HASH + F1_SORT + 1) + 3) & ~3;   // (16-byte reads of what follows)
 __device__ __forceinline__ unsigned f1_hash(unsigned bits) { return (bits * 2654435761u) >> 19; }
 
-// ---- P: one workgroup.  negb [F1_NBP + 2] (uint64, from slab_sum_kernel; [F1_NBP] = negatives with unusable scores).
+// ---- P: one workgroup.  negb [F1_NBP + 2] (uint64, from slab_fold_kernel; [F1_NBP] = negatives with unusable scores).
 //      Out: ctrl, mark bits [F1_NBP / 32 + 1], thr [T2], info [T2], dT2; tpge / fpge [F1_NB + 1] = pairs in bins >= b.
 //      A single workgroup lives on latency: the bins' sums are scanned in registers (thread t owns 24 consecutive bins),
 //      every pass over the positives keeps eight independent loads in flight.
@@ -981,7 +885,7 @@ __global__ __launch_bounds__(F1_THREADS) void f1_plan_kernel(const unsigned long
         kspan[1] = -1;
     }
     // positives by bin: counted by pass A where it found them (one global atomic per positive pair; round 4 spent 14 us
-    // of this single workgroup on a pass over the list with LDS atomics); negatives by bin: slab_sum_kernel's sums.  Both
+    // of this single workgroup on a pass over the list with LDS atomics); negatives by bin: slab_fold_kernel's sums.  Both
     // arrive transposed ([q][thread]): 48 coalesced loads per thread (in the bins' own order - 96 / 192 bytes between
     // neighbouring lanes - the same loads took 8 us)
     unsigned ps[PER];
@@ -1372,7 +1276,7 @@ __global__ __launch_bounds__(F1_THREADS) void f1_refine_kernel(const PairScan sc
         const int r = qr[e], c = qc[e];
         const unsigned cb = cls_in[(size_t)r * cw + (c >> 2)];
         if (((cb >> (2 * (c & 3))) & 3u) != 0u) return;                // pass A's class: not a negative
-        if (__float_as_uint(x) > 0x7f800000u) return;
+        if (ev_bad(x)) return;
         const int b = f1_key(x);
         if (!((mark[b >> 5] >> (b & 31)) & 1u)) return;                // not in a candidate bin: nothing to settle
         int lo = 0, hi = T;                                            // thr[lo-1] <= x < thr[hi]
@@ -1527,28 +1431,14 @@ int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int
                          int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t s) {
     if (R == 0) return SGPR_OK;
     const dim3 grid((R + 3) / 4), block(256);
-    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;
-#define SGPR_TOPK_EXT(KK, C) hipLaunchKernelGGL((topk_rows_kernel<KK, true, C>), grid, block, 0, s, score, R, M, ld, row0, \
-                                                window, val, idx, row_self, k, status)
-    if (causal) {
-        switch (K) {
-            case 1: SGPR_TOPK_EXT(1, true); break;
-            case 4: SGPR_TOPK_EXT(4, true); break;
-            case 8: SGPR_TOPK_EXT(8, true); break;
-            default: SGPR_TOPK_EXT(16, true); break;
-        }
-    } else {
-        switch (K) {
-            case 1: SGPR_TOPK_EXT(1, false); break;
-            case 4: SGPR_TOPK_EXT(4, false); break;
-            case 8: SGPR_TOPK_EXT(8, false); break;
-            default: SGPR_TOPK_EXT(16, false); break;
-        }
-    }
-#undef SGPR_TOPK_EXT
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "topk_rows_kernel launch");
-    return SGPR_OK;
+    return launch_list_k(k, "topk_rows_kernel launch", [&](auto K) {
+        if (causal)
+            hipLaunchKernelGGL((topk_rows_kernel<K, true, true>), grid, block, 0, s, score, R, M, ld, row0, window, val, idx,
+                               row_self, k, status);
+        else
+            hipLaunchKernelGGL((topk_rows_kernel<K, true, false>), grid, block, 0, s, score, R, M, ld, row0, window, val, idx,
+                               row_self, k, status);
+    });
 }
 
 // ------------------------------------------------------------------ mined pairs per row (sgpr_mine_rows)
@@ -1654,27 +1544,18 @@ int launch_mine_rows(const float* score, int R, int M, int64_t ld, const int32_t
     t.d_pos = d_pos;
     t.d_neg = d_neg;
     const dim3 grid((R + 3) / 4), block(256);
-    const int K = k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;
-    const int sel = K * 4 + (positives ? 2 : 0) + (causal ? 1 : 0);
-#define SGPR_MINE_ROWS(KK, MM, C) \
-    case KK * 4 + (MM == 2 ? 2 : 0) + (C ? 1 : 0): \
-        hipLaunchKernelGGL((mine_rows_kernel<KK, MM, C>), grid, block, 0, s, score, R, M, ld, row_self, row0, window, t, \
-                           row_pose, k, val, idx, status); \
-        break;
-#define SGPR_MINE_ROWS_K(KK) SGPR_MINE_ROWS(KK, 1, false) SGPR_MINE_ROWS(KK, 1, true) SGPR_MINE_ROWS(KK, 2, false) \
-    SGPR_MINE_ROWS(KK, 2, true)
-    switch (sel) {
-        SGPR_MINE_ROWS_K(1)
-        SGPR_MINE_ROWS_K(4)
-        SGPR_MINE_ROWS_K(8)
-        SGPR_MINE_ROWS_K(16)
-        default: break;
-    }
-#undef SGPR_MINE_ROWS_K
-#undef SGPR_MINE_ROWS
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "mine_rows_kernel launch");
-    return SGPR_OK;
+    return launch_list_k(k, "mine_rows_kernel launch", [&](auto K) {
+        auto go = [&](auto mine, auto is_causal) {
+            hipLaunchKernelGGL((mine_rows_kernel<K, mine, is_causal>), grid, block, 0, s, score, R, M, ld, row_self, row0,
+                               window, t, row_pose, k, val, idx, status);
+        };
+        using Neg = std::integral_constant<int, 1>;
+        using Pos = std::integral_constant<int, 2>;
+        if (positives)
+            causal ? go(Pos(), std::true_type()) : go(Pos(), std::false_type());
+        else
+            causal ? go(Neg(), std::true_type()) : go(Neg(), std::false_type());
+    });
 }
 
 }  // namespace sgpr
@@ -1739,9 +1620,33 @@ int launch_pair_positives_more(const sgpr_handle* h, const float* score, int R, 
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SGPR_OK : hip_fail(e, "pair_positives_kernel launch");
 }
-}  // namespace sgpr
 
-static int slab_words(int T) { return ((T + 2) & ~1) + 4; }
+int launch_pair_counts_more(const sgpr_handle* h, const float* score, int R, int M, int64_t ld, const PairTruth& truth,
+                            const float* thr, int T, const sgpr_rank_group* rank, int gpt,
+                            const unsigned long long* at_least, unsigned long long* d_out, unsigned* slabs,
+                            int accumulate, hipStream_t stream) {
+    if ((int64_t)R * M == 0) return SGPR_OK;
+    CountArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scan = make_scan(score, R, M, ld, truth.row0, truth.pose, truth.d_pos, truth.d_neg, truth.gt, truth.ldg);
+    a.thr = thr;
+    a.th.T = T;
+    a.th.rank = rank;
+    a.th.at_least = at_least;
+    a.th.gpt = rank ? gpt : 0;
+    a.slabs = slabs;
+    static LdsLimitOnce once;
+    if (int rc = raise_lds_limit(&once, reinterpret_cast<const void*>(&pair_threshold_count_kernel), 144 * 1024,   // (+ 16 B of static LDS)
+                                 "pair_threshold_count_kernel"))
+        return rc;
+    const size_t lds = ((size_t)1 << thr_levels(T)) * sizeof(float) + (size_t)slab_counters(T) * sizeof(unsigned) +
+                       (rank ? (size_t)T * sizeof(unsigned long long) : 0);
+    hipLaunchKernelGGL(pair_threshold_count_kernel, dim3(h->num_cus), dim3(PC_THREADS), lds, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "pair_threshold_count_kernel launch");
+    return launch_slab_fold(slabs, h->num_cus, slab_words(T), T, d_out, accumulate, nullptr, 1, stream);
+}
+}  // namespace sgpr
 
 size_t sgpr_pair_threshold_counts_workspace_bytes(const sgpr_handle* h, int T) {
     if (!h || T < 0 || T > PC_MAX_THRESHOLDS) return 0;
@@ -1770,37 +1675,14 @@ int sgpr_pair_threshold_counts(const sgpr_handle* h, const float* d_score, int R
     }
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e;
     if ((int64_t)R * M == 0) {
-        e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
+        const hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
         if (e != hipSuccess) return hip_fail(e, "sgpr_pair_threshold_counts: memset");
         return SGPR_OK;
     }
-    CountArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scan = make_scan(d_score, R, M, ld, row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
-    a.thr = d_thresholds;
-    a.T = T;
-    a.Tp = 1;
-    while (a.Tp <= T) a.Tp <<= 1;
-    a.rank = d_rank;
-    a.at_least = d_at_least;
-    a.gpt = d_rank ? groups_per_threshold : 0;
-    a.slabs = static_cast<unsigned*>(d_workspace);
-    a.slab_words = slab_words(T);
-    static LdsLimitOnce once;
-    if (int rc = raise_lds_limit(&once, reinterpret_cast<const void*>(&pair_threshold_count_kernel), 144 * 1024,   // (+ 16 B of static LDS)
-                                 "pair_threshold_count_kernel"))
-        return rc;
-    const size_t lds = (size_t)a.Tp * sizeof(float) + (size_t)((T + 2) & ~1) * sizeof(unsigned) +
-                       (d_rank ? (size_t)T * sizeof(unsigned long long) : 0);
-    hipLaunchKernelGGL(pair_threshold_count_kernel, dim3(h->num_cus), dim3(PC_THREADS), lds, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "pair_threshold_count_kernel launch");
-    hipLaunchKernelGGL(slab_sum_kernel, dim3((T + 3 + 31) / 32), dim3(1024), 0, s, a.slabs, h->num_cus, a.slab_words, T, d_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "slab_sum_kernel launch");
-    return SGPR_OK;
+    const PairScan sc = make_scan(d_score, R, M, ld, row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
+    return launch_pair_counts_more(h, d_score, R, M, ld, sc.truth, d_thresholds, T, d_rank, groups_per_threshold, d_at_least,
+                                   d_out, static_cast<unsigned*>(d_workspace), 0, s);
 }
 
 // ---- sgpr_f1_max: workspace = header (counts, control block, device-side sizes) | negatives by bin | pairs from a bin on
@@ -1892,7 +1774,8 @@ int sgpr_f1_max(const sgpr_handle* h, const float* d_score, int R, int M, int64_
     }
     const PairScan sc = make_scan(d_score, R, M, ld, row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
     hipLaunchKernelGGL(f1_scan_kernel, dim3(L.slabs_a), dim3(F1_THREADS), lds_scan, s, sc, slabs, L.words_a, pos, L.cap, count, cls, posb);
-    hipLaunchKernelGGL(slab_sum_kernel, dim3((F1_NBP + 2 + 31) / 32), dim3(1024), 0, s, slabs, L.slabs_a, L.words_a, F1_NBP - 1, negb, nullptr, negb_t, F1_PER);
+    rc = launch_slab_fold(slabs, L.slabs_a, L.words_a, F1_NBP - 1, negb, 0, negb_t, F1_PER, s);
+    if (rc != SGPR_OK) return rc;                         // (a failed launch of the scan shows up here, too)
     hipLaunchKernelGGL(f1_plan_kernel, dim3(1), dim3(F1_THREADS), lds_plan, s, negb, pos, count, L.cap, tpge, fpge, mark, thr, info, dT2,
                        ctrl, reinterpret_cast<unsigned long long*>(ws + 128), posb, negb_t);
     hipLaunchKernelGGL(f1_refine_kernel, dim3(L.slabs_b), dim3(F1_THREADS), 0, s, sc, mark, thr, dT2, neg2, cls, info, ctrl,
@@ -1916,13 +1799,7 @@ int sgpr_topk_rows(const sgpr_handle* h, const float* d_score, int R, int M, int
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((R + 3) / 4), block(256);
-    switch (k) {
-        case 1: hipLaunchKernelGGL(topk_rows_kernel<1>, grid, block, 0, s, d_score, R, M, ld, row0, window, d_values, d_indices); break;
-        case 4: hipLaunchKernelGGL(topk_rows_kernel<4>, grid, block, 0, s, d_score, R, M, ld, row0, window, d_values, d_indices); break;
-        case 8: hipLaunchKernelGGL(topk_rows_kernel<8>, grid, block, 0, s, d_score, R, M, ld, row0, window, d_values, d_indices); break;
-        default: hipLaunchKernelGGL(topk_rows_kernel<16>, grid, block, 0, s, d_score, R, M, ld, row0, window, d_values, d_indices); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "topk_rows_kernel launch");
-    return SGPR_OK;
+    return launch_list_k(k, "topk_rows_kernel launch", [&](auto K) {
+        hipLaunchKernelGGL(topk_rows_kernel<K>, grid, block, 0, s, d_score, R, M, ld, row0, window, d_values, d_indices);
+    });
 }

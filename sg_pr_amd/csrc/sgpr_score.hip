@@ -11,13 +11,14 @@
 //                            two-plane f16 operands (x = hi + lo, 22 bits; three cross products per layer), layer 2
 //                            chained off the accumulator layout of layer 1; a wave keeps 4 row graphs in registers and
 //                            walks 64-column super-blocks; every store instruction writes 4 rows x 256 contiguous bytes.
+// The fused epilogues of that tail (top-k, range selection, mining, positives, threshold counts) follow; what the
+// counting one shares with the matrix consumers of sgpr_metrics.hip - the counting steps, the slab layout and its fold,
+// the K dispatch of the lists - is sgpr_eval.hpp's.
 #include <math.h>
 
 #include <string.h>
 
-#include <type_traits>
-
-#include "sgpr_internal.hpp"
+#include "sgpr_eval.hpp"
 #include "sgpr_map.hpp"
 
 namespace sgpr {
@@ -861,10 +862,9 @@ __device__ __forceinline__ long long ab_start(const AboveArgs& a, int rg, int nc
 //   TK_POS  every pair is labelled (classify_pair: float64 poses, or the explicit labels); the scores of the positive
 //           ones are appended to the output list (one ballot prefix and one global atomic per wave and super-block that
 //           holds any), positives with a negative / NaN score are counted instead.
-//   TK_CNT  every negative pair descends the threshold tree in LDS (breadth-first, padded with +inf), is optionally
-//           ranked among the positive values (the rank groups) and is counted with the wave-aggregated LDS atomics of
-//           pair_threshold_count_kernel into the workgroup's counters; a workgroup's counters go to its own slab at the
-//           end (no global atomic in the loop) and eval_fold_kernel adds the slabs up.
+//   TK_CNT  every negative pair is counted between the thresholds and optionally ranked among the positive values with
+//           sgpr_eval.hpp's steps - the ones pair_threshold_count_kernel takes on a resident matrix: tree in LDS,
+//           wave-aggregated LDS atomics, the workgroup's own slab at the end (no global atomic in the loop), one fold.
 // With poses, a work item is first tested as a whole: the bounding box of the wave's four row poses against the box of
 // the chunk's 256 column poses (eval_colbox_kernel), float64, the gap cut by 2^-40 of the largest magnitude and the
 // squared distance to clear the class boundary by 0.1 % - far beyond the roundings of utils.py:36's arithmetic.  An item
@@ -883,18 +883,12 @@ struct EvalArgs {
     float* out;                          // [cap] positive scores, appended
     long long cap;
     unsigned long long* count;           // [0] positives with a usable score, [1] positives with a negative / NaN one
-    // TK_CNT (LDS)
-    const float* tree;                   // [Tp] breadth-first threshold tree
-    unsigned* cnt;                       // [T + 1]
-    const unsigned long long* at_least;  // [T] (ranking only)
-    const sgpr_rank_group* rank;         // [T * gpt] or nullptr
-    int T, lg, gpt;
+    // TK_CNT
+    ThrView th;                          // the thresholds and the workgroup's counters (sgpr_eval.hpp)
     // per lane: labelled pairs skipped for a negative / NaN score, the rank sum
     unsigned nbad;
     unsigned long long rank2;
 };
-
-__device__ __forceinline__ bool ev_bad(float s) { return __float_as_uint(s) > 0x7f800000u; }   // negative or NaN
 
 // the pose box of the wave's four rows (lane group g: row r) - wave-uniform after the shuffles
 __device__ __forceinline__ void ev_row_box(double px, double pz, double (&bx)[4]) {
@@ -977,56 +971,7 @@ __device__ __forceinline__ void ev_cnt_push(EvalArgs& e, const float (&s)[4], in
         }
     }
     if (!__any(neg[0] || neg[1] || neg[2] || neg[3])) return;
-    // four interleaved descents of the tree: right whenever the key is <= s; the leaf is the number of thresholds <= s
-    const int Tp = 1 << e.lg;
-    int bq[4] = {1, 1, 1, 1};
-    for (int lvl = 0; lvl < e.lg; ++lvl) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) bq[q] = 2 * bq[q] + ((e.tree[bq[q]] <= s[q]) ? 1 : 0);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bq[q] = min(bq[q] - Tp, e.T);
-    if (e.rank) {
-        // pairs above s = pairs from the bucket's first value on - pairs of the bucket's values <= s
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            unsigned le = 0u, eq = 0u;
-            const sgpr_rank_group* g0 = e.rank + (size_t)max(bq[q] - 1, 0) * e.gpt;
-            for (int gi = 0; gi < e.gpt; ++gi) {
-                const uint4* rec = reinterpret_cast<const uint4*>(g0 + gi);
-                const float4 v0 = *reinterpret_cast<const float4*>(rec), v1 = *reinterpret_cast<const float4*>(rec + 1);
-                const uint4 m0 = rec[2], m1 = rec[3];
-                const float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                const unsigned mm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    le += vv[i] <= s[q] ? mm[i] : 0u;
-                    eq += vv[i] == s[q] ? mm[i] : 0u;
-                }
-            }
-            // bucket 0: s lies below every positive value, all P = at_least[0] pairs rank above it
-            const unsigned long long gt_s = bq[q] > 0 ? e.at_least[bq[q] - 1] - le : e.at_least[0];
-            e.rank2 += neg[q] ? 2ull * gt_s + (bq[q] > 0 ? eq : 0u) : 0ull;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        // wave-aggregated counting (pair_threshold_count_kernel's rule): up to three rounds take the bucket of the first
-        // waiting lane with one atomic for every lane that shares it; whoever is left counts on its own
-        int idx = neg[q] ? bq[q] : -1;
-        unsigned long long todo = __ballot(idx >= 0);
-#pragma unroll 1
-        for (int round = 0; round < 3 && todo; ++round) {
-            const int leader = __ffsll((long long)todo) - 1;
-            const int lidx = __shfl(idx, leader);
-            const unsigned long long same = __ballot(idx == lidx);
-            if ((int)(threadIdx.x & 63) == leader) atomicAdd(&e.cnt[lidx], (unsigned)__popcll(same));
-            if (idx == lidx) idx = -1;
-            todo &= ~same;
-            if (__popcll(same) < 4) break;
-        }
-        if (idx >= 0) atomicAdd(&e.cnt[idx], 1u);
-    }
+    thr_count4<1>(e.th, s, neg, e.rank2);
 }
 
 // ------------------------------------------------------------------ fused mining epilogue (sgpr_score_mine)
@@ -2068,22 +2013,6 @@ static TopkArgs topk_args(const sgpr_handle* h, int R, int M, const int32_t* row
     return TopkArgs{row_self, row0, window, causal, k, 0, val, idx, pval, pidx, h->d_status};
 }
 
-// launches launch(std::integral_constant<int, K>()) for the compiled list instance of k (the first k of its K = 1, 4, 8 or
-// 16 entries)
-template <class Launch>
-static int launch_list_k(int k, const char* what, Launch&& launch) {
-    if (k <= 1)
-        launch(std::integral_constant<int, 1>());
-    else if (k <= 4)
-        launch(std::integral_constant<int, 4>());
-    else if (k <= 8)
-        launch(std::integral_constant<int, 8>());
-    else
-        launch(std::integral_constant<int, 16>());
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, what);
-}
-
 int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
                       int row0, int window, int causal, int k, float* val, int32_t* idx, void* ws, hipStream_t stream) {
     if (R == 0) return SGPR_OK;
@@ -2328,32 +2257,22 @@ __global__ __launch_bounds__(256, OCC) void score_counts_kernel(const DevWeights
                                                                 const float* __restrict__ pcol, EvalArgs a,
                                                                 const float* __restrict__ thr,
                                                                 const unsigned long long* __restrict__ at_least,
-                                                                unsigned* __restrict__ slabs, int slab_words) {
+                                                                unsigned* __restrict__ slabs) {
     __shared__ float tree[EV_TP];
     __shared__ unsigned cnt[EV_TP];
     __shared__ unsigned long long atl[EV_MAX_T];
     __shared__ unsigned long long tail[2];
     const int tid = threadIdx.x, lane = tid & 63;
     const int l15 = lane & 15, g = lane >> 4;
-    // the thresholds as a complete binary search tree in breadth-first order (node 1 = root), padded with +inf
-    const int Tp = 1 << a.lg;
-    for (int node = tid; node < Tp; node += 256) {
-        float v = INFINITY;
-        if (node > 0) {
-            const int l = 31 - __clz(node), i = node - (1 << l);
-            const int idx = ((2 * i + 1) << (a.lg - 1 - l)) - 1;          // position of the node's key in sorted order
-            if (idx < a.T) v = thr[idx];
-        }
-        tree[node] = v;
-    }
-    for (int i = tid; i <= a.T; i += 256) cnt[i] = 0u;
-    if (a.rank)
-        for (int i = tid; i < a.T; i += 256) atl[i] = at_least[i];
-    if (tid < 2) tail[tid] = 0ull;
+    ThrView& t = a.th;
+    thr_build_tree(tree, thr_levels(t.T), thr, t.T, tid, 256);
+    for (int i = tid; i <= t.T; i += 256) cnt[i] = 0u;
+    if (t.rank)
+        for (int i = tid; i < t.T; i += 256) atl[i] = at_least[i];
     __syncthreads();
-    a.tree = tree;
-    a.cnt = cnt;
-    a.at_least = atl;
+    t.tree = tree;
+    t.cnt = cnt;
+    t.at_least = atl;
     a.nbad = 0u;
     a.rank2 = 0ull;
     float am = 0.f, um = 0.f, em = 0.f, l1 = 0.f;
@@ -2369,48 +2288,8 @@ __global__ __launch_bounds__(256, OCC) void score_counts_kernel(const DevWeights
         ap_items<NI, 0, true, TK_CNT>(w, k, true, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, nullptr, &a);
     else
         ap_items<NI, 0, false, TK_CNT>(w, k, mode != 0, R, M, Ab, Cb, ur, prow, pcol, nullptr, 0, it0, it1, nullptr, nullptr, &a);
-    unsigned long long r2 = a.rank2, nb = a.nbad;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        r2 += __shfl_xor(r2, m);
-        nb += __shfl_xor(nb, m);
-    }
-    __syncthreads();
-    if (lane == 0) {
-        if (nb) atomicAdd(&tail[0], nb);
-        if (r2) atomicAdd(&tail[1], r2);
-    }
-    __syncthreads();
-    unsigned* slab = slabs + (size_t)blockIdx.x * slab_words;
-    for (int i = tid; i <= a.T; i += 256) slab[i] = cnt[i];
-    if (tid < 2) reinterpret_cast<unsigned long long*>(slab + slab_words - 4)[tid] = tail[tid];
+    thr_close(t, tail, a.nbad, a.rank2, slabs + (size_t)blockIdx.x * slab_words(t.T), tid, 256);
 }
-
-// out[i] (+)= the sum over the slabs of counter i (0..T), then the skipped count and the rank sum (u64 words of the slab
-// tail): 32 counters per workgroup, 32 threads per counter, 128-B coalesced reads.  accumulate: the row blocks after
-// the first add to what the blocks before them left in out.
-__global__ __launch_bounds__(1024) void eval_fold_kernel(const unsigned* __restrict__ slabs, int n_slabs, int slab_words,
-                                                         int T, unsigned long long* __restrict__ out, int accumulate) {
-    __shared__ unsigned long long part[32][33];
-    const int b = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + b;
-    unsigned long long s = 0ull;
-    if (i <= T) {
-        for (int q = grp; q < n_slabs; q += 32) s += slabs[(size_t)q * slab_words + i];
-    } else if (i <= T + 2) {
-        for (int q = grp; q < n_slabs; q += 32)
-            s += reinterpret_cast<const unsigned long long*>(slabs + (size_t)q * slab_words + slab_words - 4)[i - T - 1];
-    }
-    part[grp][b] = s;
-    __syncthreads();
-    if (grp == 0 && i <= T + 2) {
-#pragma unroll
-        for (int q = 1; q < 32; ++q) s += part[q][b];
-        out[i] = accumulate ? out[i] + s : s;
-    }
-}
-
-static int eval_slab_words(int T) { return ((T + 2) & ~1) + 4; }
 
 static int eval_block_rows(const sgpr_handle* h, int R, int M) {
     const int64_t ncc = (M + AP_COLS - 1) / AP_COLS;
@@ -2427,7 +2306,7 @@ size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T) {
     const int rb = eval_block_rows(h, R, M);
     const size_t ncc = (size_t)(M + AP_COLS - 1) / AP_COLS;
     size_t b = align256(ncc * 4 * sizeof(double)) + align256(score_all_pairs_ws_bytes(rb, M));
-    if (T >= 0) b += align256((size_t)topk_grid(h, rb, M) * eval_slab_words(T) * sizeof(unsigned));
+    if (T >= 0) b += align256((size_t)topk_grid(h, rb, M) * slab_words(T) * sizeof(unsigned));
     return b + (rb < R ? 256 : 0);                        // (more than one block: the call's range, launch_call_range)
 }
 
@@ -2454,7 +2333,7 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
     double* cbox = reinterpret_cast<double*>(p);
     p += align256((size_t)ncc * 4 * sizeof(double));
     unsigned* slabs = nullptr;
-    const int sw = eval_slab_words(T < 0 ? 0 : T);
+    const int sw = slab_words(T < 0 ? 0 : T);
     if (counts) {
         slabs = reinterpret_cast<unsigned*>(p);
         p += align256((size_t)topk_grid(h, rb, M) * sw * sizeof(unsigned));
@@ -2472,12 +2351,9 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
     a.out = out;
     a.cap = cap;
     a.count = count;
-    a.rank = rank;
-    a.gpt = rank ? gpt : 0;
-    a.T = T < 0 ? 0 : T;
-    int lg = 0;
-    while ((1 << lg) <= a.T) ++lg;
-    a.lg = lg;
+    a.th.rank = rank;
+    a.th.gpt = rank ? gpt : 0;
+    a.th.T = T < 0 ? 0 : T;
     float* crng = nullptr;                                // more than one block: the f16 range of the whole rectangle
     if (rb < R) {
         crng = reinterpret_cast<float*>(p + align256(score_all_pairs_ws_bytes(rb, M)));
@@ -2505,13 +2381,11 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
             continue;
         }
         hipLaunchKernelGGL((score_counts_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, krng, knrng,
-                           brows, cols, a, thr, at_least, slabs, sw);
+                           brows, cols, a, thr, at_least, slabs);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "score_counts_kernel launch");
-        hipLaunchKernelGGL(eval_fold_kernel, dim3((unsigned)((T + 3 + 31) / 32)), dim3(1024), 0, stream, slabs, (int)grid, sw,
-                           T, d_out, r0 > 0 ? 1 : 0);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "eval_fold_kernel launch");
+        const int rc2 = launch_slab_fold(slabs, (int)grid, sw, T, d_out, r0 > 0 ? 1 : 0, nullptr, 1, stream);
+        if (rc2 != SGPR_OK) return rc2;
     }
     return SGPR_OK;
 }
@@ -2625,19 +2499,6 @@ int launch_score_mine(const sgpr_handle* h, const float* rows, int R, const floa
         else
             hipLaunchKernelGGL((topk_merge_kernel<K>), gm, bd, 0, stream, R, M, (int)grid, a);
     });
-}
-
-// out[i] += in[i] (the row blocks of the chunked counting path)
-__global__ __launch_bounds__(256) void eval_add_kernel(unsigned long long* __restrict__ out,
-                                                       const unsigned long long* __restrict__ in, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] += in[i];
-}
-
-int launch_eval_add(unsigned long long* out, const unsigned long long* in, int n, hipStream_t stream) {
-    hipLaunchKernelGGL(eval_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, out, in, n);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "eval_add_kernel launch");
 }
 
 // ------------------------------------------------------------------ grouped pair list (sgpr_score_pair_list)

@@ -2,6 +2,7 @@
 the symbols, the host-side argument checks, the workspace bounds, and what thresholding the sequence-matched score does
 to a planted revisit (tests/seq_above_ref.py).  CPU only."""
 import ctypes
+import struct
 
 import numpy as np
 import pytest
@@ -165,7 +166,15 @@ def test_score_seq_threshold_counts_argument_checks_touch_no_device(lib):
     assert fn(h, R, M, 7, 8, FWD, 2048) == 0 and fn(h, R, M, 7, 8, FWD, -1) == 0 and fn(None, R, M, 7, 8, FWD, T) == 0
     assert fn(h, R, M, 7, 33, FWD, T) == 0 and fn(h, R, M, -1, 8, FWD, T) == 0 and fn(h, R, M, 7, 8, CAUSAL, T) == 0
     assert fn(h, R, M, R, 8, FWD, T) == 0
-    assert fn(h, R, M, 7, 8, FWD, 2047) > need
+    # T enters through the counting slabs alone, one per CU (every block's counts fold straight into d_out)
+    assert fn(h, R, M, 7, 8, FWD, 2047) == need                                # (a zeroed handle has no CU)
+    cus = ctypes.create_string_buffer(1 << 16)
+    struct.pack_into("ii", cus, 0, 0, 256)                                     # sgpr_handle: device, num_cus
+    hc = ctypes.cast(cus, ctypes.c_void_p)
+
+    def slabs(t):
+        return (256 * ((((t + 2) & ~1) + 4) * 4) + 255) & ~255
+    assert fn(hc, R, M, 7, 8, FWD, 2047) - fn(hc, R, M, 7, 8, FWD, T) == slabs(2047) - slabs(T)
 
 
 @pytest.mark.parametrize("case", [(M_A, RB_A + 1, 8), (262144, 150, 32)], ids=["rb+1", "thin"])
