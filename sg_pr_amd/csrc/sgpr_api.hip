@@ -41,6 +41,11 @@ int hip_fail(hipError_t e, const char* what) {
     return SGPR_E_HIP;
 }
 
+int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SGPR_OK : hip_fail(e, what);
+}
+
 // the caller's workspace holds the `need` bytes entry point fn asks for (need 0: any pointer, NULL included)
 static bool workspace_ok(const char* fn, size_t need, const void* ws, size_t ws_bytes) {
     if (need > 0 && (!ws || ws_bytes < need)) {
@@ -764,16 +769,20 @@ static int score_block_rows(int R, int M, int ctx_rows = 0) {
     return (int)std::max<size_t>(1, std::min<size_t>((size_t)R, fresh));
 }
 
-static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // row-block path layout: score block [ctx_rows + rb][M] | the caller's head (head_bytes) | the block's all-pairs workspace
 static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t head_bytes, int ctx_rows = 0) {
     const int rb = score_block_rows(R, M, ctx_rows);
     return a256(((size_t)ctx_rows + rb) * M * sizeof(float)) + head_bytes + sgpr_score_all_pairs_workspace_bytes(h, rb, M);
 }
 
+// the caller's head of that layout (where the call's f16 range sits, if it has one)
+static unsigned char* row_blocks_head(void* ws, int R, int M, int ctx_rows = 0) {
+    const size_t rows = (size_t)ctx_rows + score_block_rows(R, M, ctx_rows);
+    return static_cast<unsigned char*>(ws) + a256(rows * M * sizeof(float));
+}
+
 // sgpr_score_all_pairs on rows [r0, r0 + n) of the rectangle, one block after the other, each followed by
-// consume(block, head, r0, n): block [n][M] (ld M), head the caller's region of the workspace.
+// consume(block, head, r0): block the n scored rows [n][M] (ld M), head the caller's region of the workspace.
 // The f16-range question is the whole rectangle's, as in sgpr_score_all_pairs on it: on an any-shape handle's matrix-core
 // tail a first pass preps every block into the all-pairs region, its TailHdr cleared once and accumulating the maxima of
 // all blocks, and no block's scoring clears it (the other handles' row blocks take the three-plane instance: no gate).
@@ -784,16 +793,15 @@ static size_t row_blocks_ws_bytes(const sgpr_handle* h, int R, int M, size_t hea
 // right in front of `block`.
 extern "C++" {   // (a template, inside the C-ABI block)
 template <class Consume>
-static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, size_t head_bytes,
-                            void* ws, size_t ws_bytes, void* stream, Consume&& consume, float* crng = nullptr,
-                            int ctx_rows = 0) {
-    const int rb = score_block_rows(R, M, ctx_rows), pw = pooled_width(h);
-    const size_t block_bytes = a256(((size_t)ctx_rows + rb) * M * sizeof(float));
+static int score_row_blocks(const sgpr_handle* h, const PooledRect& p, size_t head_bytes, void* ws, size_t ws_bytes,
+                            void* stream, Consume&& consume, float* crng = nullptr, int ctx_rows = 0) {
+    const int R = p.R, M = p.M, rb = score_block_rows(R, M, ctx_rows), pw = pooled_width(h);
+    const float *rows = p.rows, *cols = p.cols;
     float* carry = static_cast<float*>(ws);
     float* block = carry + (size_t)ctx_rows * M;
-    unsigned char* head = static_cast<unsigned char*>(ws) + block_bytes;
+    unsigned char* head = row_blocks_head(ws, R, M, ctx_rows);
     unsigned char* aws = head + head_bytes;
-    const size_t aws_bytes = ws_bytes - block_bytes - head_bytes;
+    const size_t aws_bytes = ws_bytes - (size_t)(aws - static_cast<unsigned char*>(ws));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool one_range = h->generic_only && wide_tail_serves(h) && rb < R;
     const bool call_range = crng && has_fused_epilogues(h) && rb < R;
@@ -815,7 +823,8 @@ static int score_row_blocks(const sgpr_handle* h, const float* rows, int R, cons
                  : call_range ? launch_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, s, false, crng)
                               : sgpr_score_all_pairs(h, rows + (size_t)r0 * pw, n, cols, M, block, M, aws, aws_bytes, stream);
         if (rc != SGPR_OK) return rc;
-        rc = consume(block, head, r0, n);
+        const ScoreBlock scored = {block, n, M, M};
+        rc = consume(scored, head, r0);
         if (rc != SGPR_OK) return rc;
         if (ctx_rows > 0 && r0 + n < R) {
             // rows [n, n + ctx_rows) of the buffer move to its front: one copy, or (a block shorter than the context:
@@ -858,17 +867,16 @@ int sgpr_score_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, con
     if (!workspace_ok("sgpr_score_topk", sgpr_score_topk_workspace_bytes(h, R, M, k, flags), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == 0) return SGPR_OK;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const Eligible elig = eligible(d_row_self, row0, window, flags);
+    const ListOut out = {d_values, d_indices, k, nullptr};
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0 || has_fused_epilogues(h))
-        return launch_score_topk(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, k, d_values,
-                                 d_indices, d_workspace, s);
-    auto select = [&](const float* block, unsigned char*, int r0, int n) {
-        return launch_topk_rows_ext(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, k,
-                                    d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
+    if (M == 0 || has_fused_epilogues(h)) return launch_score_topk(h, rect, elig, out, d_workspace, s);
+    auto select = [&](const ScoreBlock& block, unsigned char*, int r0) {
+        return launch_topk_rows_ext(block, elig.from(r0), out.at(r0), h->d_status, s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, 0, d_workspace, workspace_bytes, stream, select);
+    return score_row_blocks(h, rect, 0, d_workspace, workspace_bytes, stream, select);
 }
 
 // ---- sgpr_score_topk_large / sgpr_topk_rows_large: k up to SGPR_TOPK_LARGE_MAX through the large-k selection
@@ -905,9 +913,11 @@ int sgpr_topk_rows_large(const sgpr_handle* h, const float* d_score, int R, int 
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == 0) return SGPR_OK;
+    const ScoreBlock block = {d_score, R, M, ld};
+    const ListOut out = {d_values, d_indices, k, nullptr};
     DeviceGuard guard(h->device);
-    return launch_select_rows(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, k, d_values,
-                              d_indices, d_workspace, false, h->d_status, static_cast<hipStream_t>(stream));
+    return launch_select_rows(block, eligible(d_row_self, row0, window, flags), out, d_workspace, false, h->d_status,
+                              static_cast<hipStream_t>(stream));
 }
 
 size_t sgpr_score_topk_large_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
@@ -928,21 +938,17 @@ int sgpr_score_topk_large(const sgpr_handle* h, const float* d_pooled_rows, int 
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == 0) return SGPR_OK;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const Eligible elig = eligible(d_row_self, row0, window, flags);
+    const ListOut out = {d_values, d_indices, k, nullptr};
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0)
-        return launch_select_rows(nullptr, R, 0, 0, d_row_self, row0, window, causal, k, d_values, d_indices, nullptr, false,
-                                  h->d_status, s);
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256((size_t)score_block_rows(R, M) * M * sizeof(float)));
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        return launch_select_rows(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, k,
-                                  d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, head + 256, r0 > 0, h->d_status,
-                                  s);
+    if (M == 0) return launch_select_rows(ScoreBlock{nullptr, R, 0, 0}, elig, out, nullptr, false, h->d_status, s);
+    float* crng = reinterpret_cast<float*>(row_blocks_head(d_workspace, R, M));
+    auto select = [&](const ScoreBlock& block, unsigned char* head, int r0) {
+        return launch_select_rows(block, elig.from(r0), out.at(r0), head + 256, r0 > 0, h->d_status, s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, topk_large_head_bytes(R, M), d_workspace,
-                            workspace_bytes, stream, select, crng);
+    return score_row_blocks(h, rect, topk_large_head_bytes(R, M), d_workspace, workspace_bytes, stream, select, crng);
 }
 
 // ---- sgpr_seq_filter / sgpr_score_seq_topk: the diagonal score filter (seq_filter_kernel; the family: sgpr_seq.hip) on a resident matrix, and on
@@ -981,8 +987,10 @@ int sgpr_seq_filter(const sgpr_handle* h, const float* d_score, int R, int M, in
         return SGPR_E_INVALID;
     }
     if (R == ctx || M == 0) return SGPR_OK;
+    const ScoreBlock block = {d_score, R, M, ld};
+    const FilterOut out = {d_out, ldo, d_dir, ldo};
     DeviceGuard guard(h->device);
-    return launch_seq_filter(d_score, R, M, ld, ctx, L, flags, d_out, ldo, d_dir, ldo, static_cast<hipStream_t>(stream));
+    return launch_seq_filter(block, seq_spec(ctx, L, flags), out, static_cast<hipStream_t>(stream));
 }
 
 static bool seq_both(int flags) { return (flags & SGPR_SEQ_FORWARD) && (flags & SGPR_SEQ_REVERSE); }
@@ -996,135 +1004,142 @@ enum RankFilter { kRankNone, kRankDiagonal, kRankPaths, kRankSessions };
 struct RankStages {
     RankFilter filter;     // kRankNone: the ranked score is S itself (L = 1 before a peak step: S * rcp[1] is S)
     bool peak;             // the peak step runs: a P block sits in front of the Q block
+    int radius;
     bool code_block;       // the filter writes a dir / code block behind the Q block
     bool code_room;        // the head has room for that block
     bool filter_window;    // the window is the filter's (sessions): the selection runs without one
-    int L, radius;
-    const int32_t* offsets;   // kRankPaths, kRankSessions (nullptr: the unit diagonal)
-    int n_paths;
-    const int32_t* row_starts;   // kRankSessions (nullptr: one session)
-    int n_row;
-    const int32_t* col_starts;
-    int n_col;
 };
 
-// sgpr_score_seq_topk: the diagonal filter at every L; a dir block when both directions are asked for
-static RankStages seq_stages(int L, int flags) {
-    return {kRankDiagonal, false, seq_both(flags), seq_both(flags), false, L, 0, nullptr, 0, nullptr, 0, nullptr, 0};
+static RankStages rank_stages(RankFilter filter, bool peak, int radius, bool code_block, bool code_room) {
+    RankStages st;
+    st.filter = filter;
+    st.peak = peak;
+    st.radius = radius;
+    st.code_block = code_block;
+    st.code_room = code_room;
+    st.filter_window = false;
+    return st;
 }
+
+// sgpr_score_seq_topk: the diagonal filter at every L; a dir block when both directions are asked for
+static RankStages seq_stages(int flags) { return rank_stages(kRankDiagonal, false, 0, seq_both(flags), seq_both(flags)); }
 
 // sgpr_score_peak_topk: the peak step at every radius, the diagonal filter when L > 1 (L = 1, both directions: the two
 // sums are one number and forward wins the tie - direction 0, no dir block)
 static RankStages peak_stages(int L, int radius, int flags) {
     const bool dir = L > 1 && seq_both(flags);
-    return {L > 1 ? kRankDiagonal : kRankNone, true, dir, dir, false, L, radius, nullptr, 0, nullptr, 0, nullptr, 0};
+    return rank_stages(L > 1 ? kRankDiagonal : kRankNone, true, radius, dir, dir);
 }
 
 // sgpr_score_path_topk: the peak step only when radius > 0, the path filter unless L = 1 comes before a peak step (every
 // candidate is S itself).  Codes: both directions or several paths; one direction and several paths keep their room
 // in the head even where no filter runs
-static RankStages path_stages(int L, const int32_t* offsets, int n_paths, int radius, int flags) {
+static RankStages path_stages(int L, int n_paths, int radius, int flags) {
     const bool filter = radius == 0 || L > 1;
-    return {filter ? kRankPaths : kRankNone, radius > 0, filter && (seq_both(flags) || n_paths > 1),
-            seq_both(flags) ? filter : n_paths > 1, false, L, radius, offsets, n_paths, nullptr, 0, nullptr, 0};
+    return rank_stages(filter ? kRankPaths : kRankNone, radius > 0, radius, filter && (seq_both(flags) || n_paths > 1),
+                       seq_both(flags) ? filter : n_paths > 1);
 }
 
 // sgpr_score_session_topk: sgpr_score_path_topk's at radius 0 with the session filter, which applies the window itself
-static RankStages session_stages(int L, const int32_t* offsets, int n_paths, const int32_t* row_starts, int n_row,
-                                 const int32_t* col_starts, int n_col, int flags) {
-    RankStages st = path_stages(L, offsets, std::max(n_paths, 1), 0, flags);
+static RankStages session_stages(int L, int n_paths, int flags) {
+    RankStages st = path_stages(L, std::max(n_paths, 1), 0, flags);
     st.filter = kRankSessions;
     st.filter_window = true;
-    st.row_starts = row_starts;
-    st.n_row = n_row;
-    st.col_starts = col_starts;
-    st.n_col = n_col;
     return st;
 }
 
 // the pipeline's head: the call's f16 range (a float4) | the selection's workspace for one block | [P block [rb][M]] |
 // [Q block [rb][M]] | [dir / code block [rb][M] u8]
-static size_t rank_head_bytes(int R, int M, const RankStages& st) {
-    const size_t rb = (size_t)score_block_rows(R, M, st.L - 1), blk = a256(rb * M * sizeof(float));
+static size_t rank_head_bytes(int R, int M, int L, const RankStages& st) {
+    const size_t rb = (size_t)score_block_rows(R, M, L - 1), blk = a256(rb * M * sizeof(float));
     return 256 + a256(select_ws_bytes((int)rb, M)) + (st.peak ? blk : 0) + (st.filter != kRankNone ? blk : 0) +
            (st.code_room ? a256(rb * M) : 0);
 }
 
-// the row-session table of the rectangle that starts at the call's row `base` and has `rows` rows (nullptr stays
-// nullptr: one session).  A session that starts before `base` starts at the rectangle's row 0 - where it matters
-// (base > 0) every output row has its L - 1 rows inside the rectangle, and a depth of L is a depth of L from either start
-static const int32_t* shift_row_table(const int32_t* starts, int n, int base, int rows, int32_t* local) {
-    if (!starts) return nullptr;
-    for (int j = 0; j < n; ++j) local[j] = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)starts[j] - base, 0), rows);
-    return local;
-}
+// what a row block with context means to the ranking, range and evaluation pipelines: the block scored rows r0 ..
+// r0 + scored.R - 1 of the call, and min(L - 1, r0) rows of the block before sit right in front of them
+struct BlockView {
+    int first;         // the block's first output row (a row of the call)
+    int no;            // its output rows; <= 0: context rows only
+    int base;          // the call's row of the rectangle's row 0
+    ScoreBlock rect;   // what a filter sees: from global row 0, or L - 1 rows back (no sum reaches further)
+    BlockView(const ScoreBlock& scored, int r0, int ctx, int L) : rect(scored) {
+        const int c = std::min(L - 1, r0);
+        first = std::max(r0, ctx);
+        no = r0 + scored.R - first;
+        base = r0 - c;
+        rect.score -= (size_t)c * scored.M;
+        rect.R += c;
+    }
+};
+
+// the call's SeqSpec as the rectangle of a block sees it (shift_row_table): the context is what lies in front of the
+// first output row, and the row-session table moves with the rectangle (nullptr stays nullptr: one session).  A session
+// that starts before `base` starts at the rectangle's row 0 - where it matters (base > 0) every output row has its L - 1
+// rows inside the rectangle, and a depth of L is a depth of L from either start (so min_terms sees the same)
+struct ShiftedSeq : SeqSpec {
+    int32_t local[SGPR_SESSION_MAX];
+    ShiftedSeq(const SeqSpec& seq, const BlockView& v) : SeqSpec(seq) {
+        ctx = v.first - v.base;
+        if (!row_starts) return;
+        for (int j = 0; j < n_row; ++j)
+            local[j] = (int32_t)std::min<int64_t>(std::max<int64_t>((int64_t)seq.row_starts[j] - v.base, 0), v.rect.R);
+        row_starts = local;
+    }
+    ShiftedSeq(const ShiftedSeq&) = delete;
+};
 
 // arguments and workspace already checked, R > ctx.  Without a code block the listed code is the first direction asked
 // for, path 0: one candidate, or L = 1 where all candidates are one number and the first one keeps a listed, hence
 // non-NaN, entry (forward wins the tie)
-static int rank_row_blocks(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
-                           int ctx, const int32_t* d_row_self, int row0, int window, int flags, int k, float* d_values,
-                           int32_t* d_indices, unsigned char* d_codes, const RankStages& st, void* d_workspace,
-                           size_t workspace_bytes, void* stream) {
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, fixed_code = (flags & SGPR_SEQ_FORWARD) ? 0 : 1;
-    const int seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE), L = st.L;
-    const int sel_window = st.filter_window ? -1 : window;
+static int rank_row_blocks(const sgpr_handle* h, const PooledRect& p, const SeqSpec& seq, const Eligible& elig,
+                           const ListOut& out, const RankStages& st, void* d_workspace, size_t workspace_bytes,
+                           void* stream) {
+    const int R = p.R, M = p.M, ctx = seq.ctx, L = seq.L, fixed_code = (seq.dirs & SGPR_SEQ_FORWARD) ? 0 : 1;
+    const Eligible sel = st.filter_window ? elig.without_window() : elig;
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (M == 0) {
-        const int rc = launch_select_rows(nullptr, R - ctx, 0, 0, d_row_self ? d_row_self + ctx : nullptr, row0 + ctx,
-                                          sel_window, causal, k, d_values, d_indices, nullptr, false, h->d_status, s);
-        if (rc != SGPR_OK || !d_codes) return rc;
-        return launch_seq_dirs(d_indices, R - ctx, k, nullptr, 0, fixed_code, d_codes, s);
+        const ScoreBlock none = {nullptr, R - ctx, 0, 0};
+        const int rc = launch_select_rows(none, sel.from(ctx), out, nullptr, false, h->d_status, s);
+        if (rc != SGPR_OK || !out.codes) return rc;
+        return launch_seq_dirs(out.idx, R - ctx, out.k, nullptr, 0, fixed_code, out.codes, s);
     }
     const int rb = score_block_rows(R, M, L - 1);
     const size_t sel_bytes = a256(select_ws_bytes(rb, M)), blk_bytes = a256((size_t)rb * M * sizeof(float));
     const size_t p_at = 256 + sel_bytes, q_at = p_at + (st.peak ? blk_bytes : 0);
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+    float* crng = reinterpret_cast<float*>(row_blocks_head(d_workspace, R, M, L - 1));
     int clean_rows = 0;                                   // histogram rows the selection before left clear
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0), no = r0 + n - first, base = r0 - c;
-        // the rectangle the filter sees starts c rows before r0: global row 0, or L - 1 rows back (no sum reaches further)
-        const float* rect = block - (size_t)c * M;
-        const float* x = block + (size_t)(first - r0) * M;
-        float* q = reinterpret_cast<float*>(head + q_at);
+    auto select = [&](const ScoreBlock& scored, unsigned char* head, int r0) {
+        const BlockView v(scored, r0, ctx, L);
+        if (v.no <= 0) return (int)SGPR_OK;               // context rows only
+        const ShiftedSeq sq(seq, v);
         unsigned char* code = st.code_block ? head + q_at + blk_bytes : nullptr;
+        const FilterOut q = {reinterpret_cast<float*>(head + q_at), M, code, M};
         int rc = SGPR_OK;
-        if (st.filter == kRankDiagonal) {
-            rc = launch_seq_filter(rect, c + n, M, M, first - base, L, seq_flags, q, M, code, M, s);
-        } else if (st.filter == kRankPaths) {
-            rc = launch_seq_path_filter(rect, c + n, M, M, first - base, L, seq_flags, st.offsets, st.n_paths, q, M, code, M,
-                                        s);
-        } else if (st.filter == kRankSessions) {          // row_self / row0 and the row table move with the rectangle
-            int32_t local[SGPR_SESSION_MAX];
-            rc = launch_session_filter(rect, c + n, M, M, first - base, L, seq_flags, st.offsets, st.n_paths,
-                                       shift_row_table(st.row_starts, st.n_row, base, c + n, local), st.n_row,
-                                       st.col_starts, st.n_col, d_row_self ? d_row_self + base : nullptr, row0 + base,
-                                       window, q, M, code, M, s);
-        }
+        if (st.filter == kRankDiagonal)
+            rc = launch_seq_filter(v.rect, sq, q, s);
+        else if (st.filter == kRankPaths)
+            rc = launch_seq_path_filter(v.rect, sq, q, s);
+        else if (st.filter == kRankSessions)              // row_self / row0 and the row table move with the rectangle
+            rc = launch_session_filter(v.rect, sq, elig.from(v.base), q, s);
         if (rc != SGPR_OK) return rc;
-        if (st.filter != kRankNone) x = q;
-        const int32_t* rs = d_row_self ? d_row_self + first : nullptr;
+        ScoreBlock x = {st.filter != kRankNone ? q.out : scored.score + (size_t)(v.first - r0) * M, v.no, M, M};
         if (st.peak) {                                    // (rows are independent: no context rows of its own)
-            float* p = reinterpret_cast<float*>(head + p_at);
-            rc = launch_peak_filter(x, no, M, M, rs, row0 + first, window, causal, st.radius, p, M, s);
+            float* peaks = reinterpret_cast<float*>(head + p_at);
+            rc = launch_peak_filter(x, elig.from(v.first), st.radius, peaks, M, s);
             if (rc != SGPR_OK) return rc;
-            x = p;
+            x.score = peaks;
         }
-        const size_t o = (size_t)(first - ctx) * k;
-        rc = launch_select_rows(x, no, M, M, rs, row0 + first, sel_window, causal, k, d_values + o, d_indices + o,
-                                head + 256, select_group_rows(no) <= clean_rows, h->d_status, s);
+        const ListOut o = out.at(v.first - ctx);
+        rc = launch_select_rows(x, sel.from(v.first), o, head + 256, select_group_rows(v.no) <= clean_rows, h->d_status, s);
         // (the first block's outputs start at ctx: the block after it may select more rows, whose histograms reach into
         //  what this one used for its state and counts)
-        clean_rows = select_group_rows(no);
-        if (rc != SGPR_OK || !d_codes) return rc;
-        return launch_seq_dirs(d_indices + o, no, k, code, M, fixed_code, d_codes + o, s);
+        clean_rows = select_group_rows(v.no);
+        if (rc != SGPR_OK || !o.codes) return rc;
+        return launch_seq_dirs(o.idx, v.no, o.k, q.code, M, fixed_code, o.codes, s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, rank_head_bytes(R, M, st), d_workspace, workspace_bytes,
-                            stream, select, crng, L - 1);
+    return score_row_blocks(h, p, rank_head_bytes(R, M, L, st), d_workspace, workspace_bytes, stream, select, crng, L - 1);
 }
 
 size_t sgpr_score_seq_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int flags) {
@@ -1132,7 +1147,7 @@ size_t sgpr_score_seq_topk_workspace_bytes(const sgpr_handle* h, int R, int M, i
         (flags & ~kSeqFlags) || !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
         return 0;
     if (R == ctx || M == 0) return 0;
-    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, seq_stages(L, flags)), L - 1);
+    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, L, seq_stages(flags)), L - 1);
 }
 
 int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1153,8 +1168,10 @@ int sgpr_score_seq_topk(const sgpr_handle* h, const float* d_pooled_rows, int R,
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
-                           d_indices, d_dirs, seq_stages(L, flags), d_workspace, workspace_bytes, stream);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const ListOut out = {d_values, d_indices, k, d_dirs};
+    return rank_row_blocks(h, rect, seq_spec(ctx, L, flags), eligible(d_row_self, row0, window, flags), out,
+                           seq_stages(flags), d_workspace, workspace_bytes, stream);
 }
 
 // ---- sgpr_peak_filter / sgpr_score_peak_topk: per-row score peaks within a scan radius (sgpr_peak.hip) on a resident
@@ -1184,9 +1201,10 @@ int sgpr_peak_filter(const sgpr_handle* h, const float* d_score, int R, int M, i
         return SGPR_E_INVALID;
     }
     if (R == 0 || M == 0) return SGPR_OK;
+    const ScoreBlock block = {d_score, R, M, ld};
     DeviceGuard guard(h->device);
-    return launch_peak_filter(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, radius,
-                              d_out, ldo, static_cast<hipStream_t>(stream));
+    return launch_peak_filter(block, eligible(d_row_self, row0, window, flags), radius, d_out, ldo,
+                              static_cast<hipStream_t>(stream));
 }
 
 size_t sgpr_score_peak_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int k, int radius,
@@ -1196,7 +1214,7 @@ size_t sgpr_score_peak_topk_workspace_bytes(const sgpr_handle* h, int R, int M, 
         !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
         return 0;
     if (R == ctx || M == 0) return 0;
-    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, peak_stages(L, radius, flags)), L - 1);
+    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, L, peak_stages(L, radius, flags)), L - 1);
 }
 
 int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1218,8 +1236,10 @@ int sgpr_score_peak_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                       d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
-                           d_indices, d_dirs, peak_stages(L, radius, flags), d_workspace, workspace_bytes, stream);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const ListOut out = {d_values, d_indices, k, d_dirs};
+    return rank_row_blocks(h, rect, seq_spec(ctx, L, flags), eligible(d_row_self, row0, window, flags), out,
+                           peak_stages(L, radius, flags), d_workspace, workspace_bytes, stream);
 }
 
 // ---- sgpr_seq_path_filter / sgpr_score_path_topk: the path-set score filter (seq_path_kernel) on a resident matrix,
@@ -1268,8 +1288,10 @@ int sgpr_seq_path_filter(const sgpr_handle* h, const float* d_score, int R, int 
         return SGPR_E_INVALID;
     }
     if (R == ctx || M == 0) return SGPR_OK;
+    const ScoreBlock block = {d_score, R, M, ld};
+    const FilterOut out = {d_out, ldo, d_code, ldo};
     DeviceGuard guard(h->device);
-    return launch_seq_path_filter(d_score, R, M, ld, ctx, L, flags, h_offsets, n_paths, d_out, ldo, d_code, ldo,
+    return launch_seq_path_filter(block, seq_spec(ctx, L, flags).paths(h_offsets, n_paths), out,
                                   static_cast<hipStream_t>(stream));
 }
 
@@ -1280,7 +1302,7 @@ size_t sgpr_score_path_topk_workspace_bytes(const sgpr_handle* h, int R, int M, 
         (flags & ~kSeqFlags) || !(flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)))
         return 0;
     if (R == ctx || M == 0) return 0;
-    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, path_stages(L, nullptr, n_paths, radius, flags)), L - 1);
+    return row_blocks_ws_bytes(h, R, M, rank_head_bytes(R, M, L, path_stages(L, n_paths, radius, flags)), L - 1);
 }
 
 int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
@@ -1304,9 +1326,11 @@ int sgpr_score_path_topk(const sgpr_handle* h, const float* d_pooled_rows, int R
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
-                           d_indices, d_codes, path_stages(L, h_offsets, n_paths, radius, flags), d_workspace,
-                           workspace_bytes, stream);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const ListOut out = {d_values, d_indices, k, d_codes};
+    return rank_row_blocks(h, rect, seq_spec(ctx, L, flags).paths(h_offsets, n_paths),
+                           eligible(d_row_self, row0, window, flags), out, path_stages(L, n_paths, radius, flags),
+                           d_workspace, workspace_bytes, stream);
 }
 
 // ---- sgpr_session_filter / sgpr_score_session_topk: the session-aware path-set filter (session_kernel) on a resident
@@ -1340,10 +1364,12 @@ int sgpr_session_filter(const sgpr_handle* h, const float* d_score, int R, int M
         return SGPR_E_INVALID;
     }
     if (R == ctx || M == 0) return SGPR_OK;
+    const ScoreBlock block = {d_score, R, M, ld};
+    const SeqSpec seq = seq_spec(ctx, L, flags).paths(h_offsets, n_paths)
+                            .sessions(h_row_starts, n_row_sessions, h_col_starts, n_col_sessions);
+    const FilterOut out = {d_out, ldo, d_code, ldo};
     DeviceGuard guard(h->device);
-    return launch_session_filter(d_score, R, M, ld, ctx, L, flags, h_offsets, n_paths, h_row_starts, n_row_sessions,
-                                 h_col_starts, n_col_sessions, d_row_self, row0, window, d_out, ldo, d_code, ldo,
-                                 static_cast<hipStream_t>(stream));
+    return launch_session_filter(block, seq, eligible(d_row_self, row0, window, 0), out, static_cast<hipStream_t>(stream));
 }
 
 size_t sgpr_score_session_topk_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int k,
@@ -1379,10 +1405,12 @@ int sgpr_score_session_topk(const sgpr_handle* h, const float* d_pooled_rows, in
                       d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == ctx) return SGPR_OK;
-    const RankStages st = session_stages(L, h_offsets, n_paths, h_row_starts, n_row_sessions, h_col_starts,
-                                         n_col_sessions, flags);
-    return rank_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, k, d_values,
-                           d_indices, d_codes, st, d_workspace, workspace_bytes, stream);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const SeqSpec seq = seq_spec(ctx, L, flags).paths(h_offsets, n_paths)
+                            .sessions(h_row_starts, n_row_sessions, h_col_starts, n_col_sessions);
+    const ListOut out = {d_values, d_indices, k, d_codes};
+    return rank_row_blocks(h, rect, seq, eligible(d_row_self, row0, window, flags), out, session_stages(L, n_paths, flags),
+                           d_workspace, workspace_bytes, stream);
 }
 
 // ---- sgpr_score_mine / sgpr_mine_rows: sgpr_score_topk's split (fused on the production handle, 64 MB score blocks
@@ -1394,13 +1422,14 @@ static bool mine_flags_ok(int flags) {
     return !(flags & ~kMineFlags) && (mode == SGPR_MINE_NEGATIVES || mode == SGPR_MINE_POSITIVES);
 }
 
-static bool mine_args_ok(const char* fn, const sgpr_handle* h, int R, int M, const double* col_pose, int row0, int flags,
-                         double d_pos, double d_neg, int k, const float* d_values, const int32_t* d_indices) {
-    if (!h || R < 0 || M < 0 || !col_pose || !d_values || !d_indices) {
+static bool mine_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int row0, int flags, const MineSpec& mine,
+                         const ListOut& out) {
+    const double d_pos = mine.d_pos, d_neg = mine.d_neg;
+    if (!h || R < 0 || M < 0 || !mine.col_pose || !out.val || !out.idx) {
         set_error(std::string(fn) + ": NULL argument or negative count");
         return false;
     }
-    if (k < 1 || k > 16) {
+    if (out.k < 1 || out.k > 16) {
         set_error(std::string(fn) + ": k must lie in 1..16");
         return false;
     }
@@ -1428,8 +1457,9 @@ int sgpr_score_mine(const sgpr_handle* h, const float* d_pooled_rows, int R, con
                     const double* d_col_pose_xz, const double* d_row_pose_xz, const int32_t* d_row_self, int row0,
                     int window, int flags, double d_pos, double d_neg, int k, float* d_values, int32_t* d_indices,
                     void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!mine_args_ok("sgpr_score_mine", h, R, M, d_col_pose_xz, row0, flags, d_pos, d_neg, k, d_values, d_indices))
-        return SGPR_E_INVALID;
+    const MineSpec mine = mine_spec(flags, d_col_pose_xz, d_row_pose_xz, d_pos, d_neg);
+    const ListOut out = {d_values, d_indices, k, nullptr};
+    if (!mine_args_ok("sgpr_score_mine", h, R, M, row0, flags, mine, out)) return SGPR_E_INVALID;
     if (!d_pooled_rows || !d_pooled_cols) {
         set_error("sgpr_score_mine: NULL pooled array");
         return SGPR_E_INVALID;
@@ -1437,18 +1467,15 @@ int sgpr_score_mine(const sgpr_handle* h, const float* d_pooled_rows, int R, con
     if (!workspace_ok("sgpr_score_mine", sgpr_score_mine_workspace_bytes(h, R, M, k, flags), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
     if (R == 0) return SGPR_OK;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, positives = (flags & SGPR_MINE_POSITIVES) ? 1 : 0;
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const Eligible elig = eligible(d_row_self, row0, window, flags);
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0 || has_fused_epilogues(h))
-        return launch_score_mine(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, positives,
-                                 d_col_pose_xz, d_row_pose_xz, d_pos, d_neg, k, d_values, d_indices, d_workspace, s);
-    auto select = [&](const float* block, unsigned char*, int r0, int n) {
-        return launch_mine_rows(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, positives,
-                                d_col_pose_xz, d_row_pose_xz ? d_row_pose_xz + 2 * (size_t)r0 : nullptr, d_pos, d_neg, k,
-                                d_values + (size_t)r0 * k, d_indices + (size_t)r0 * k, h->d_status, s);
+    if (M == 0 || has_fused_epilogues(h)) return launch_score_mine(h, rect, elig, mine, out, d_workspace, s);
+    auto select = [&](const ScoreBlock& block, unsigned char*, int r0) {
+        return launch_mine_rows(block, elig.from(r0), mine.from(r0), out.at(r0), h->d_status, s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, 0, d_workspace, workspace_bytes, stream, select);
+    return score_row_blocks(h, rect, 0, d_workspace, workspace_bytes, stream, select);
 }
 
 size_t sgpr_mine_rows_workspace_bytes(const sgpr_handle* h, int R, int M, int k, int flags) {
@@ -1466,24 +1493,25 @@ int sgpr_mine_rows(const sgpr_handle* h, const float* d_score, int R, int M, int
                    void* stream) {
     (void)d_workspace;
     (void)workspace_bytes;
-    if (!mine_args_ok("sgpr_mine_rows", h, R, M, d_col_pose_xz, row0, flags, d_pos, d_neg, k, d_values, d_indices))
-        return SGPR_E_INVALID;
+    const MineSpec mine = mine_spec(flags, d_col_pose_xz, d_row_pose_xz, d_pos, d_neg);
+    const ListOut out = {d_values, d_indices, k, nullptr};
+    if (!mine_args_ok("sgpr_mine_rows", h, R, M, row0, flags, mine, out)) return SGPR_E_INVALID;
     if (!d_score || ld < M) {
         set_error("sgpr_mine_rows: NULL score matrix or leading dimension below M");
         return SGPR_E_INVALID;
     }
     if (R == 0) return SGPR_OK;
+    const ScoreBlock block = {d_score, R, M, ld};
     DeviceGuard guard(h->device);
-    return launch_mine_rows(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0,
-                            (flags & SGPR_MINE_POSITIVES) ? 1 : 0, d_col_pose_xz, d_row_pose_xz, d_pos, d_neg, k,
-                            d_values, d_indices, h->d_status, static_cast<hipStream_t>(stream));
+    return launch_mine_rows(block, eligible(d_row_self, row0, window, flags), mine, out, h->d_status,
+                            static_cast<hipStream_t>(stream));
 }
 
 // ---- sgpr_score_above / sgpr_rows_above: the fused two-pass kernel on the production handle; the other handles score
 //      bounded row blocks with their own tail and select from each block, positions continuing on the device
 static bool above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int row0, int flags, float threshold,
-                          int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity, unsigned long long* d_count) {
-    if (!h || R < 0 || M < 0 || capacity < 0 || !d_count || (capacity > 0 && (!d_rows || !d_cols || !d_values))) {
+                          const RangeOut& out) {
+    if (!h || R < 0 || M < 0 || out.cap < 0 || !out.count || (out.cap > 0 && (!out.rows || !out.cols || !out.vals))) {
         set_error(std::string(fn) + ": NULL argument, negative count or negative capacity");
         return false;
     }
@@ -1514,28 +1542,27 @@ int sgpr_score_above(const sgpr_handle* h, const float* d_pooled_rows, int R, co
                      const int32_t* d_row_self, int row0, int window, int flags, float threshold, int32_t* d_rows,
                      int32_t* d_cols, float* d_values, int64_t capacity, int64_t* d_row_ptr, unsigned long long* d_count,
                      void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!above_args_ok("sgpr_score_above", h, R, M, row0, flags, threshold, d_rows, d_cols, d_values, capacity, d_count))
-        return SGPR_E_INVALID;
+    // (the output bundle carries the handle's status word: read only once the checks have seen h)
+    RangeOut out = range_out(d_rows, d_cols, d_values, nullptr, capacity, d_row_ptr, d_count, h ? h->d_status : nullptr);
+    if (!above_args_ok("sgpr_score_above", h, R, M, row0, flags, threshold, out)) return SGPR_E_INVALID;
     if (R > 0 && M > 0 && (!d_pooled_rows || !d_pooled_cols)) {
         set_error("sgpr_score_above: NULL pooled vectors");
         return SGPR_E_INVALID;
     }
     if (!workspace_ok("sgpr_score_above", sgpr_score_above_workspace_bytes(h, R, M, flags), d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0;
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const Eligible elig = eligible(d_row_self, row0, window, flags);
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (R == 0 || M == 0 || has_fused_epilogues(h))
-        return launch_score_above(h, d_pooled_rows, R, d_pooled_cols, M, d_row_self, row0, window, causal, threshold,
-                                  d_rows, d_cols, d_values, capacity, d_row_ptr, d_count, d_workspace, s);
+        return launch_score_above(h, rect, elig, threshold, out.at(0, d_workspace), s);
     const size_t cnt_bytes = a256((size_t)score_block_rows(R, M) * 4);
-    auto select = [&](const float* block, unsigned char* cnt, int r0, int n) {
-        int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(cnt + cnt_bytes);
-        return launch_rows_above(block, n, M, M, d_row_self ? d_row_self + r0 : nullptr, row0 + r0, window, causal, threshold,
-                                 d_rows, d_cols, d_values, capacity, rp + r0, r0, d_count, r0 > 0, cnt, h->d_status, s);
+    if (!out.row_ptr) out.row_ptr = reinterpret_cast<int64_t*>(row_blocks_head(d_workspace, R, M) + cnt_bytes);
+    auto select = [&](const ScoreBlock& block, unsigned char* cnt, int r0) {
+        return launch_rows_above(block, elig.from(r0), threshold, out.at(r0, cnt), s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, above_head_bytes(R, M), d_workspace, workspace_bytes,
-                            stream, select);
+    return score_row_blocks(h, rect, above_head_bytes(R, M), d_workspace, workspace_bytes, stream, select);
 }
 
 size_t sgpr_rows_above_workspace_bytes(const sgpr_handle* h, int R, int M) {
@@ -1547,8 +1574,8 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
                     int row0, int window, int flags, float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values,
                     int64_t capacity, int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace,
                     size_t workspace_bytes, void* stream) {
-    if (!above_args_ok("sgpr_rows_above", h, R, M, row0, flags, threshold, d_rows, d_cols, d_values, capacity, d_count))
-        return SGPR_E_INVALID;
+    RangeOut out = range_out(d_rows, d_cols, d_values, nullptr, capacity, d_row_ptr, d_count, h ? h->d_status : nullptr);
+    if (!above_args_ok("sgpr_rows_above", h, R, M, row0, flags, threshold, out)) return SGPR_E_INVALID;
     if (ld < M || (R > 0 && M > 0 && !d_score)) {
         set_error("sgpr_rows_above: NULL score or ld < M");
         return SGPR_E_INVALID;
@@ -1559,18 +1586,16 @@ int sgpr_rows_above(const sgpr_handle* h, const float* d_score, int R, int M, in
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (R == 0 || M == 0) return launch_above_empty(R, d_row_ptr, d_count, s);
     unsigned char* cnt = static_cast<unsigned char*>(d_workspace);
-    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(cnt + a256((size_t)R * 4));
-    return launch_rows_above(d_score, R, M, ld, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, threshold,
-                             d_rows, d_cols, d_values, capacity, rp, 0, d_count, 0, cnt, h->d_status, s);
+    if (!out.row_ptr) out.row_ptr = reinterpret_cast<int64_t*>(cnt + a256((size_t)R * 4));
+    const ScoreBlock block = {d_score, R, M, ld};
+    return launch_rows_above(block, eligible(d_row_self, row0, window, flags), threshold, out.at(0, cnt), s);
 }
 
 // ---- sgpr_seq_rows_above / sgpr_score_seq_above: the range selection on the sequence-matched score (seq_above_kernel,
 //      sgpr_seq.hip) on a resident matrix, and on sgpr_score_seq_topk's row blocks with context - no Q or dir block
 static bool seq_above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int ctx, int row0, int flags, int L,
-                              float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity,
-                              unsigned long long* d_count) {
-    if (!above_args_ok(fn, h, R, M, row0, flags & SGPR_TOPK_CAUSAL, threshold, d_rows, d_cols, d_values, capacity, d_count))
-        return false;
+                              float threshold, const RangeOut& out) {
+    if (!above_args_ok(fn, h, R, M, row0, flags & SGPR_TOPK_CAUSAL, threshold, out)) return false;
     return seq_args_ok(fn, R, ctx, L, flags, kSeqFlags);
 }
 
@@ -1590,9 +1615,8 @@ int sgpr_seq_rows_above(const sgpr_handle* h, const float* d_score, int R, int M
                         int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_dirs, int64_t capacity,
                         int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
                         void* stream) {
-    if (!seq_above_args_ok("sgpr_seq_rows_above", h, R, M, ctx, row0, flags, L, threshold, d_rows, d_cols, d_values,
-                           capacity, d_count))
-        return SGPR_E_INVALID;
+    RangeOut out = range_out(d_rows, d_cols, d_values, d_dirs, capacity, d_row_ptr, d_count, h ? h->d_status : nullptr);
+    if (!seq_above_args_ok("sgpr_seq_rows_above", h, R, M, ctx, row0, flags, L, threshold, out)) return SGPR_E_INVALID;
     if (ld < M || (R > ctx && M > 0 && !d_score)) {
         set_error("sgpr_seq_rows_above: NULL score or ld < M");
         return SGPR_E_INVALID;
@@ -1604,9 +1628,10 @@ int sgpr_seq_rows_above(const sgpr_handle* h, const float* d_score, int R, int M
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
     unsigned char* ws = static_cast<unsigned char*>(d_workspace);
-    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(ws + seq_above_ws_bytes(R - ctx, M));
-    return launch_seq_above(d_score, R, M, ld, ctx, L, flags, d_row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0,
-                            threshold, d_rows, d_cols, d_values, d_dirs, capacity, rp, 0, d_count, 0, ws, h->d_status, s);
+    if (!out.row_ptr) out.row_ptr = reinterpret_cast<int64_t*>(ws + seq_above_ws_bytes(R - ctx, M));
+    const ScoreBlock block = {d_score, R, M, ld};
+    return launch_seq_above(block, seq_spec(ctx, L, flags), eligible(d_row_self, row0, window, flags), threshold,
+                            out.at(0, ws), s);
 }
 
 // head of sgpr_score_seq_above: the call's f16 range (a float4) | seg, cnt for one block | row_ptr [R - ctx + 1] i64
@@ -1615,54 +1640,31 @@ static size_t seq_above_head_bytes(int R, int M, int ctx, int L) {
     return 256 + seq_above_ws_bytes(score_block_rows(R, M, L - 1), M) + a256((size_t)(R - ctx + 1) * 8);
 }
 
-struct RangeSessions {     // what sgpr_score_session_above adds to sgpr_score_seq_above
-    const int32_t* offsets;
-    int n_paths;
-    const int32_t* row_starts;
-    int n_row;
-    const int32_t* col_starts;
-    int n_col;
-    int min_terms;
-};
-
-// the range pipeline of sgpr_score_seq_above (ss == nullptr: seq_above_kernel) and sgpr_score_session_above
+// the range pipeline of sgpr_score_seq_above (seq_above_kernel) and, `sessions`, sgpr_score_session_above
 // (session_above_kernel) on the ranking pipeline's row blocks with context - no Q or code block.  Arguments and
-// workspace already checked
-static int range_row_blocks(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols, int M,
-                            int ctx, const int32_t* d_row_self, int row0, int window, int flags, int L,
-                            const RangeSessions* ss, float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values,
-                            unsigned char* d_codes, int64_t capacity, int64_t* d_row_ptr, unsigned long long* d_count,
-                            void* d_workspace, size_t workspace_bytes, void* stream) {
-    const int causal = (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, seq_flags = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE);
+// workspace already checked; out.row_ptr == nullptr: the head holds it
+static int range_row_blocks(const sgpr_handle* h, const PooledRect& p, const SeqSpec& seq, bool sessions,
+                            const Eligible& elig, float threshold, const RangeOut& out, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
+    const int R = p.R, M = p.M, ctx = seq.ctx, L = seq.L;
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t sel_bytes = seq_above_ws_bytes(rb, M);
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(d_workspace) +
-                                           a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
-    auto select = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);              // the block's first output row
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        // the rectangle starts c rows before r0 (the ranking pipeline's): its row 0 is row `base` of the call, and
-        // row_self / row0 and the row table move with it (a depth of L from either start, so min_terms sees the same)
-        const int c = std::min(L - 1, r0), base = r0 - c, o = first - ctx;
-        const float* rect = block - (size_t)c * M;
-        const int32_t* rs = d_row_self ? d_row_self + base : nullptr;
-        int64_t* rp = (d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(head + 256 + sel_bytes)) + o;
-        if (!ss)
-            return launch_seq_above(rect, c + n, M, M, first - base, L, seq_flags, rs, row0 + base, window, causal,
-                                    threshold, d_rows, d_cols, d_values, d_codes, capacity, rp, o, d_count, o > 0 ? 1 : 0,
-                                    head + 256, h->d_status, s);
-        int32_t local[SGPR_SESSION_MAX];
-        return launch_session_above(rect, c + n, M, M, first - base, L, seq_flags, ss->offsets, ss->n_paths,
-                                    shift_row_table(ss->row_starts, ss->n_row, base, c + n, local), ss->n_row,
-                                    ss->col_starts, ss->n_col, rs, row0 + base, window, causal, ss->min_terms, threshold,
-                                    d_rows, d_cols, d_values, d_codes, capacity, rp, o, d_count, o > 0 ? 1 : 0, head + 256,
-                                    h->d_status, s);
+    if (R == ctx || M == 0) return launch_above_empty(R - ctx, out.row_ptr, out.count, s);
+    unsigned char* crng = row_blocks_head(d_workspace, R, M, L - 1);
+    RangeOut call = out;
+    if (!call.row_ptr)
+        call.row_ptr = reinterpret_cast<int64_t*>(crng + 256 + seq_above_ws_bytes(score_block_rows(R, M, L - 1), M));
+    auto select = [&](const ScoreBlock& scored, unsigned char* head, int r0) {
+        const BlockView v(scored, r0, ctx, L);
+        if (v.no <= 0) return (int)SGPR_OK;               // context rows only
+        // row_self / row0 and the row table move with the rectangle
+        const ShiftedSeq sq(seq, v);
+        const RangeOut o = call.at(v.first - ctx, head + 256);
+        return sessions ? launch_session_above(v.rect, sq, elig.from(v.base), threshold, o, s)
+                        : launch_seq_above(v.rect, sq, elig.from(v.base), threshold, o, s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, seq_above_head_bytes(R, M, ctx, L), d_workspace,
-                            workspace_bytes, stream, select, crng, L - 1);
+    return score_row_blocks(h, p, seq_above_head_bytes(R, M, ctx, L), d_workspace, workspace_bytes, stream, select,
+                            reinterpret_cast<float*>(crng), L - 1);
 }
 
 size_t sgpr_score_seq_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int flags) {
@@ -1676,9 +1678,9 @@ int sgpr_score_seq_above(const sgpr_handle* h, const float* d_pooled_rows, int R
                          int32_t* d_rows, int32_t* d_cols, float* d_values, unsigned char* d_dirs, int64_t capacity,
                          int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
                          void* stream) {
-    if (!seq_above_args_ok("sgpr_score_seq_above", h, R, M, ctx, row0, flags, L, threshold, d_rows, d_cols, d_values,
-                           capacity, d_count))
-        return SGPR_E_INVALID;
+    const RangeOut out = range_out(d_rows, d_cols, d_values, d_dirs, capacity, d_row_ptr, d_count,
+                                   h ? h->d_status : nullptr);
+    if (!seq_above_args_ok("sgpr_score_seq_above", h, R, M, ctx, row0, flags, L, threshold, out)) return SGPR_E_INVALID;
     if (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols)) {
         set_error("sgpr_score_seq_above: NULL pooled vectors");
         return SGPR_E_INVALID;
@@ -1686,31 +1688,27 @@ int sgpr_score_seq_above(const sgpr_handle* h, const float* d_pooled_rows, int R
     if (!workspace_ok("sgpr_score_seq_above", sgpr_score_seq_above_workspace_bytes(h, R, M, ctx, L, flags), d_workspace,
                       workspace_bytes))
         return SGPR_E_WORKSPACE;
-    return range_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, L, nullptr,
-                            threshold, d_rows, d_cols, d_values, d_dirs, capacity, d_row_ptr, d_count, d_workspace,
-                            workspace_bytes, stream);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    return range_row_blocks(h, rect, seq_spec(ctx, L, flags), false, eligible(d_row_self, row0, window, flags), threshold,
+                            out, d_workspace, workspace_bytes, stream);
 }
 
 // ---- sgpr_session_rows_above / sgpr_score_session_above: the range selection on the session-aware path-set score with a
 //      minimum term count (session_above_kernel) on a resident matrix, and on
 //      sgpr_score_seq_above's row blocks with the row table shifted per block as sgpr_score_session_topk shifts it
-static bool session_above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int ctx, int row0, int window,
-                                  int flags, int L, const int32_t* h_offsets, int n_paths, const int32_t* h_row_starts,
-                                  int n_row_sessions, const int32_t* h_col_starts, int n_col_sessions, int min_terms,
-                                  float threshold, int32_t* d_rows, int32_t* d_cols, float* d_values, int64_t capacity,
-                                  unsigned long long* d_count) {
-    if (!seq_above_args_ok(fn, h, R, M, ctx, row0, flags, L, threshold, d_rows, d_cols, d_values, capacity, d_count))
-        return false;
+static bool session_above_args_ok(const char* fn, const sgpr_handle* h, int R, int M, int row0, int window, int flags,
+                                  const SeqSpec& seq, float threshold, const RangeOut& out) {
+    if (!seq_above_args_ok(fn, h, R, M, seq.ctx, row0, flags, seq.L, threshold, out)) return false;
     if (window < -1) {
         set_error(std::string(fn) + ": window below -1");
         return false;
     }
-    if (!session_paths_ok(fn, h_offsets, n_paths, L)) return false;
-    if (!session_table_ok(fn, "row", h_row_starts, n_row_sessions, R) ||
-        !session_table_ok(fn, "column", h_col_starts, n_col_sessions, M))
+    if (!session_paths_ok(fn, seq.offsets, seq.n_paths, seq.L)) return false;
+    if (!session_table_ok(fn, "row", seq.row_starts, seq.n_row, R) ||
+        !session_table_ok(fn, "column", seq.col_starts, seq.n_col, M))
         return false;
-    if (min_terms < 1 || min_terms > L) {
-        set_error(std::string(fn) + ": min_terms must lie in 1..L, got " + std::to_string(min_terms));
+    if (seq.min_terms < 1 || seq.min_terms > seq.L) {
+        set_error(std::string(fn) + ": min_terms must lie in 1..L, got " + std::to_string(seq.min_terms));
         return false;
     }
     return true;
@@ -1727,10 +1725,10 @@ int sgpr_session_rows_above(const sgpr_handle* h, const float* d_score, int R, i
                             float* d_values, unsigned char* d_codes, int64_t capacity, int64_t* d_row_ptr,
                             unsigned long long* d_count, void* d_workspace, size_t workspace_bytes, void* stream) {
     const char* fn = "sgpr_session_rows_above";
-    if (!session_above_args_ok(fn, h, R, M, ctx, row0, window, flags, L, h_offsets, n_paths, h_row_starts, n_row_sessions,
-                               h_col_starts, n_col_sessions, min_terms, threshold, d_rows, d_cols, d_values, capacity,
-                               d_count))
-        return SGPR_E_INVALID;
+    const SeqSpec seq = seq_spec(ctx, L, flags, min_terms).paths(h_offsets, n_paths)
+                            .sessions(h_row_starts, n_row_sessions, h_col_starts, n_col_sessions);
+    RangeOut out = range_out(d_rows, d_cols, d_values, d_codes, capacity, d_row_ptr, d_count, h ? h->d_status : nullptr);
+    if (!session_above_args_ok(fn, h, R, M, row0, window, flags, seq, threshold, out)) return SGPR_E_INVALID;
     if (ld < M || (R > ctx && M > 0 && !d_score)) {
         set_error("sgpr_session_rows_above: NULL score or ld < M");
         return SGPR_E_INVALID;
@@ -1741,11 +1739,9 @@ int sgpr_session_rows_above(const sgpr_handle* h, const float* d_score, int R, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (R == ctx || M == 0) return launch_above_empty(R - ctx, d_row_ptr, d_count, s);
     unsigned char* ws = static_cast<unsigned char*>(d_workspace);
-    int64_t* rp = d_row_ptr ? d_row_ptr : reinterpret_cast<int64_t*>(ws + seq_above_ws_bytes(R - ctx, M));
-    return launch_session_above(d_score, R, M, ld, ctx, L, flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE), h_offsets,
-                                n_paths, h_row_starts, n_row_sessions, h_col_starts, n_col_sessions, d_row_self, row0,
-                                window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0, min_terms, threshold, d_rows, d_cols, d_values,
-                                d_codes, capacity, rp, 0, d_count, 0, ws, h->d_status, s);
+    if (!out.row_ptr) out.row_ptr = reinterpret_cast<int64_t*>(ws + seq_above_ws_bytes(R - ctx, M));
+    const ScoreBlock block = {d_score, R, M, ld};
+    return launch_session_above(block, seq, eligible(d_row_self, row0, window, flags), threshold, out.at(0, ws), s);
 }
 
 size_t sgpr_score_session_above_workspace_bytes(const sgpr_handle* h, int R, int M, int ctx, int L, int n_paths, int flags,
@@ -1764,10 +1760,11 @@ int sgpr_score_session_above(const sgpr_handle* h, const float* d_pooled_rows, i
                              int64_t* d_row_ptr, unsigned long long* d_count, void* d_workspace, size_t workspace_bytes,
                              void* stream) {
     const char* fn = "sgpr_score_session_above";
-    if (!session_above_args_ok(fn, h, R, M, ctx, row0, window, flags, L, h_offsets, n_paths, h_row_starts, n_row_sessions,
-                               h_col_starts, n_col_sessions, min_terms, threshold, d_rows, d_cols, d_values, capacity,
-                               d_count))
-        return SGPR_E_INVALID;
+    const SeqSpec seq = seq_spec(ctx, L, flags, min_terms).paths(h_offsets, n_paths)
+                            .sessions(h_row_starts, n_row_sessions, h_col_starts, n_col_sessions);
+    const RangeOut out = range_out(d_rows, d_cols, d_values, d_codes, capacity, d_row_ptr, d_count,
+                                   h ? h->d_status : nullptr);
+    if (!session_above_args_ok(fn, h, R, M, row0, window, flags, seq, threshold, out)) return SGPR_E_INVALID;
     if (R > ctx && M > 0 && (!d_pooled_rows || !d_pooled_cols)) {
         set_error("sgpr_score_session_above: NULL pooled vectors");
         return SGPR_E_INVALID;
@@ -1776,10 +1773,9 @@ int sgpr_score_session_above(const sgpr_handle* h, const float* d_pooled_rows, i
                                                                    n_col_sessions),
                       d_workspace, workspace_bytes))
         return SGPR_E_WORKSPACE;
-    const RangeSessions ss = {h_offsets, n_paths, h_row_starts, n_row_sessions, h_col_starts, n_col_sessions, min_terms};
-    return range_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, d_row_self, row0, window, flags, L, &ss, threshold,
-                            d_rows, d_cols, d_values, d_codes, capacity, d_row_ptr, d_count, d_workspace, workspace_bytes,
-                            stream);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    return range_row_blocks(h, rect, seq, true, eligible(d_row_self, row0, window, flags), threshold, out, d_workspace,
+                            workspace_bytes, stream);
 }
 
 // ---- sgpr_score_positives / sgpr_score_threshold_counts: the fused evaluation epilogues on the production handle; the
@@ -1804,6 +1800,14 @@ static PairTruth eval_truth(int row0, const double* pose, double d_pos, double d
     t.gt = pose ? nullptr : gt;
     t.ldg = ldg;
     return t;
+}
+
+// the truth of the rows from `r` on, whose explicit labels start `g` label rows in
+static PairTruth truth_from(const PairTruth& t, int r, int g) {
+    PairTruth tb = t;
+    tb.row0 += r;
+    if (tb.gt) tb.gt += (int64_t)g * t.ldg;
+    return tb;
 }
 
 // head of sgpr_score_threshold_counts' row-block path: the counting slabs (every block's counts fold into d_out)
@@ -1844,13 +1848,12 @@ int sgpr_score_positives(const sgpr_handle* h, const float* d_pooled_rows, int R
                                  0, nullptr, nullptr, d_workspace, s);
     hipError_t e = hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_positives: memset");
-    auto count = [&](const float* block, unsigned char*, int r0, int n) {
-        PairTruth tb = truth;
-        tb.row0 = row0 + r0;
-        if (tb.gt) tb.gt += (int64_t)r0 * ldg;
-        return launch_pair_positives_more(h, block, n, M, M, tb, out, capacity, d_count, s);
+    auto count = [&](const ScoreBlock& block, unsigned char*, int r0) {
+        return launch_pair_positives_more(h, block.score, block.R, M, M, truth_from(truth, r0, r0), out, capacity, d_count,
+                                          s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, 0, d_workspace, workspace_bytes, stream, count);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    return score_row_blocks(h, rect, 0, d_workspace, workspace_bytes, stream, count);
 }
 
 int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
@@ -1881,15 +1884,12 @@ int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows
                                  groups_per_threshold, d_at_least, d_out, d_workspace, s);
     hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_threshold_counts: memset");
-    auto count = [&](const float* block, unsigned char* head, int r0, int n) {
-        PairTruth tb = truth;
-        tb.row0 = row0 + r0;
-        if (tb.gt) tb.gt += (int64_t)r0 * ldg;
-        return launch_pair_counts_more(h, block, n, M, M, tb, d_thresholds, T, d_rank, groups_per_threshold, d_at_least,
-                                       d_out, reinterpret_cast<unsigned*>(head), 1, s);
+    auto count = [&](const ScoreBlock& block, unsigned char* head, int r0) {
+        return launch_pair_counts_more(h, block.score, block.R, M, M, truth_from(truth, r0, r0), d_thresholds, T, d_rank,
+                                       groups_per_threshold, d_at_least, d_out, reinterpret_cast<unsigned*>(head), 1, s);
     };
-    return score_row_blocks(h, d_pooled_rows, R, d_pooled_cols, M, counts_head_bytes(h, T), d_workspace, workspace_bytes,
-                            stream, count);
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    return score_row_blocks(h, rect, counts_head_bytes(h, T), d_workspace, workspace_bytes, stream, count);
 }
 
 // ---- sgpr_score_seq_positives / sgpr_score_seq_threshold_counts: the evaluation of the sequence-matched score on
@@ -1897,18 +1897,18 @@ int sgpr_score_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows
 //      to the matrix kernels, row0 and d_gt advanced to the block's first output row - the wide-range path above with
 //      the filter in between.  (The counting kernels carry a threshold tree and rank sums: they are not fused into the
 //      filter.)
-static bool seq_eval_args_ok(const char* fn, const sgpr_handle* h, const float* rows, int R, const float* cols, int M,
-                             int ctx, int L, int flags, int row0, const double* pose, const signed char* gt, int64_t ldg) {
-    if (!h || R < 0 || M < 0 || (!pose && !gt) || (gt && !pose && ldg < M)) {
+static bool seq_eval_args_ok(const char* fn, const sgpr_handle* h, const PooledRect& p, int ctx, int L, int flags,
+                             const PairTruth& truth) {
+    if (!h || p.R < 0 || p.M < 0 || (!truth.pose && !truth.gt) || (truth.gt && truth.ldg < p.M)) {
         set_error(std::string(fn) + ": NULL argument, negative count, no ground truth or ldg below M");
         return false;
     }
-    if (!seq_args_ok(fn, R, ctx, L, flags, SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)) return false;
-    if (R > ctx && M > 0 && (!rows || !cols)) {
+    if (!seq_args_ok(fn, p.R, ctx, L, flags, SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE)) return false;
+    if (p.R > ctx && p.M > 0 && (!p.rows || !p.cols)) {
         set_error(std::string(fn) + ": NULL pooled vectors");
         return false;
     }
-    return row0_ok(fn, row0, R);
+    return row0_ok(fn, truth.row0, p.R);
 }
 
 static bool seq_eval_query_ok(const sgpr_handle* h, int R, int M, int ctx, int L, int flags) {
@@ -1934,23 +1934,22 @@ size_t sgpr_score_seq_threshold_counts_workspace_bytes(const sgpr_handle* h, int
 
 extern "C++" {
 // score_row_blocks with L - 1 context rows; each block with output rows is filtered into the Q block and
-// consume(q, tail, first, no) sees Q of the call's rows [first, first + no) (ld M); tail: the head behind the Q block
+// consume(q, tail, first) sees Q of the call's rows [first, first + q.R) (ld M); tail: the head behind the Q block
 template <class Consume>
-static int seq_eval_blocks(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, int ctx, int L,
-                           int flags, size_t head_bytes, void* ws, size_t ws_bytes, void* stream, Consume&& consume) {
-    const int rb = score_block_rows(R, M, L - 1);
-    const size_t q_bytes = a256((size_t)rb * M * sizeof(float));
-    float* crng = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + a256(((size_t)(L - 1) + rb) * M * sizeof(float)));
+static int seq_eval_blocks(const sgpr_handle* h, const PooledRect& p, const SeqSpec& seq, size_t head_bytes, void* ws,
+                           size_t ws_bytes, void* stream, Consume&& consume) {
+    const int M = p.M;
+    const size_t q_bytes = a256((size_t)score_block_rows(p.R, M, seq.L - 1) * M * sizeof(float));
+    float* crng = reinterpret_cast<float*>(row_blocks_head(ws, p.R, M, seq.L - 1));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto filter = [&](const float* block, unsigned char* head, int r0, int n) {
-        const int first = std::max(r0, ctx);
-        if (first >= r0 + n) return (int)SGPR_OK;         // context rows only
-        const int c = std::min(L - 1, r0);
-        float* q = reinterpret_cast<float*>(head + 256);
-        const int rc = launch_seq_filter(block - (size_t)c * M, c + n, M, M, c + first - r0, L, flags, q, M, nullptr, M, s);
-        return rc != SGPR_OK ? rc : consume(q, head + 256 + q_bytes, first, r0 + n - first);
+    auto filter = [&](const ScoreBlock& scored, unsigned char* head, int r0) {
+        const BlockView v(scored, r0, seq.ctx, seq.L);
+        if (v.no <= 0) return (int)SGPR_OK;               // context rows only
+        const FilterOut q = {reinterpret_cast<float*>(head + 256), M, nullptr, M};
+        const int rc = launch_seq_filter(v.rect, ShiftedSeq(seq, v), q, s);
+        return rc != SGPR_OK ? rc : consume(ScoreBlock{q.out, v.no, M, M}, head + 256 + q_bytes, v.first);
     };
-    return score_row_blocks(h, rows, R, cols, M, head_bytes, ws, ws_bytes, stream, filter, crng, L - 1);
+    return score_row_blocks(h, p, head_bytes, ws, ws_bytes, stream, filter, crng, seq.L - 1);
 }
 }  // extern "C++"
 
@@ -1958,9 +1957,9 @@ int sgpr_score_seq_positives(const sgpr_handle* h, const float* d_pooled_rows, i
                              int ctx, int L, int flags, int row0, const double* d_pose_xz, double d_pos, double d_neg,
                              const signed char* d_gt, int64_t ldg, float* d_out, int64_t capacity,
                              unsigned long long* d_count, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!seq_eval_args_ok("sgpr_score_seq_positives", h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags, row0,
-                          d_pose_xz, d_gt, ldg))
-        return SGPR_E_INVALID;
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
+    if (!seq_eval_args_ok("sgpr_score_seq_positives", h, rect, ctx, L, flags, truth)) return SGPR_E_INVALID;
     if (!d_count || capacity < 0 || (capacity > 0 && !d_out)) {
         set_error("sgpr_score_seq_positives: NULL count buffer or capacity without an output buffer");
         return SGPR_E_INVALID;
@@ -1973,16 +1972,13 @@ int sgpr_score_seq_positives(const sgpr_handle* h, const float* d_pooled_rows, i
     hipError_t e = hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_seq_positives: memset");
     if (R == ctx || M == 0) return SGPR_OK;
-    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
     float* out = capacity > 0 ? d_out : nullptr;
-    auto count = [&](const float* q, unsigned char*, int first, int no) {
-        PairTruth tb = truth;
-        tb.row0 = row0 + first;
-        if (tb.gt) tb.gt += (int64_t)(first - ctx) * ldg;
-        return launch_pair_positives_more(h, q, no, M, M, tb, out, capacity, d_count, s);
+    auto count = [&](const ScoreBlock& q, unsigned char*, int first) {
+        return launch_pair_positives_more(h, q.score, q.R, M, M, truth_from(truth, first, first - ctx), out, capacity,
+                                          d_count, s);
     };
-    return seq_eval_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags, seq_eval_head_bytes(R, M, L), d_workspace,
-                           workspace_bytes, stream, count);
+    return seq_eval_blocks(h, rect, seq_spec(ctx, L, flags), seq_eval_head_bytes(R, M, L), d_workspace, workspace_bytes,
+                           stream, count);
 }
 
 int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_rows, int R, const float* d_pooled_cols,
@@ -1991,9 +1987,9 @@ int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_
                                     const sgpr_rank_group* d_rank, int groups_per_threshold,
                                     const unsigned long long* d_at_least, unsigned long long* d_out, void* d_workspace,
                                     size_t workspace_bytes, void* stream) {
-    if (!seq_eval_args_ok("sgpr_score_seq_threshold_counts", h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags, row0,
-                          d_pose_xz, d_gt, ldg))
-        return SGPR_E_INVALID;
+    const PooledRect rect = {d_pooled_rows, R, d_pooled_cols, M};
+    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
+    if (!seq_eval_args_ok("sgpr_score_seq_threshold_counts", h, rect, ctx, L, flags, truth)) return SGPR_E_INVALID;
     if (!d_out || T < 0 || T > SGPR_SCORE_COUNT_MAX_THRESHOLDS || (T > 0 && !d_thresholds)) {
         set_error("sgpr_score_seq_threshold_counts: 0.." + std::to_string(SGPR_SCORE_COUNT_MAX_THRESHOLDS) +
                   " thresholds and an output buffer");
@@ -2012,17 +2008,12 @@ int sgpr_score_seq_threshold_counts(const sgpr_handle* h, const float* d_pooled_
     hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(T + 3) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_seq_threshold_counts: memset");
     if (R == ctx || M == 0) return SGPR_OK;
-    const PairTruth truth = eval_truth(row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
-    auto count = [&](const float* q, unsigned char* tail, int first, int no) {
-        PairTruth tb = truth;
-        tb.row0 = row0 + first;
-        if (tb.gt) tb.gt += (int64_t)(first - ctx) * ldg;
-        return launch_pair_counts_more(h, q, no, M, M, tb, d_thresholds, T, d_rank, groups_per_threshold, d_at_least, d_out,
-                                       reinterpret_cast<unsigned*>(tail), 1, s);
+    auto count = [&](const ScoreBlock& q, unsigned char* tail, int first) {
+        return launch_pair_counts_more(h, q.score, q.R, M, M, truth_from(truth, first, first - ctx), d_thresholds, T, d_rank,
+                                       groups_per_threshold, d_at_least, d_out, reinterpret_cast<unsigned*>(tail), 1, s);
     };
-    return seq_eval_blocks(h, d_pooled_rows, R, d_pooled_cols, M, ctx, L, flags,
-                           seq_eval_head_bytes(R, M, L) + counts_head_bytes(h, T), d_workspace, workspace_bytes, stream,
-                           count);
+    return seq_eval_blocks(h, rect, seq_spec(ctx, L, flags), seq_eval_head_bytes(R, M, L) + counts_head_bytes(h, T),
+                           d_workspace, workspace_bytes, stream, count);
 }
 
 size_t sgpr_score_all_pairs_multi_workspace_bytes(const sgpr_handle* h, int n_jobs, const sgpr_pairs_job* jobs) {

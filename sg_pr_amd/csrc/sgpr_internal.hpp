@@ -239,6 +239,144 @@ __device__ __forceinline__ int classify_pose_exact(const double* __restrict__ po
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
+// after a kernel launch: SGPR_OK, or hip_fail of what hipGetLastError() reports
+int launched(const char* what);
+
+inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- the argument bundles of the retrieval launchers ("Launcher bundles").  Plain host structs: a public
+//      entry point fills each once, by named members or the maker beside the struct, and hands it on by const&; a
+//      launcher fills its kernel's own argument struct from them.  A new retrieval launcher takes these.
+struct ScoreBlock {            // a resident matrix, or one score block of a row-blocked call
+    const float* score;        // [R][ld]
+    int R, M;
+    int64_t ld;
+};
+
+struct PooledRect {            // the pooled operands of the fused forms
+    const float* rows;
+    int R;
+    const float* cols;
+    int M;
+};
+
+struct Eligible {              // which columns a row may list (tk_bounds)
+    const int32_t* row_self;   // [rows] the column of each row's own frame, or nullptr: row0 + r
+    int row0, window, causal;  // window < 0: none
+    // the same rule for the rows from r on: the one place that rebases row_self and row0
+    Eligible from(int r) const { return {row_self ? row_self + r : nullptr, row0 + r, window, causal}; }
+    // the session pipeline's selection: the filter has applied the window
+    Eligible without_window() const { return {row_self, row0, -1, causal}; }
+};
+inline Eligible eligible(const int32_t* row_self, int row0, int window, int flags) {
+    return {row_self, row0, window, (flags & SGPR_TOPK_CAUSAL) ? 1 : 0};
+}
+
+struct SeqSpec {               // the sequence match: diagonal, path set or sessions
+    int ctx, L, dirs;          // dirs: SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE, at least one
+    const int32_t* offsets;    // host table [n_paths][L] (already checked; copied into the launch), nullptr: the unit diagonal
+    int n_paths;
+    const int32_t* row_starts; // host session tables (already checked; copied into the launch), nullptr: one session
+    int n_row;
+    const int32_t* col_starts;
+    int n_col;
+    int min_terms;             // 1..L (the session range selection)
+    SeqSpec paths(const int32_t* off, int n) const {
+        SeqSpec s = *this;
+        s.offsets = off;
+        s.n_paths = n;
+        return s;
+    }
+    SeqSpec sessions(const int32_t* rows, int nr, const int32_t* cols, int nc) const {
+        SeqSpec s = *this;
+        s.row_starts = rows;
+        s.n_row = nr;
+        s.col_starts = cols;
+        s.n_col = nc;
+        return s;
+    }
+};
+inline SeqSpec seq_spec(int ctx, int L, int flags, int min_terms = 1) {   // the unit diagonal in one session
+    SeqSpec s = {};
+    s.ctx = ctx;
+    s.L = L;
+    s.dirs = flags & (SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE);
+    s.min_terms = min_terms;
+    return s;
+}
+
+struct RangeOut {              // where a range selection's result goes
+    int32_t* rows;
+    int32_t* cols;
+    float* vals;
+    unsigned char* codes;      // directions / codes of the sequence forms, or nullptr
+    int64_t cap;
+    int64_t* row_ptr;          // [output rows + 1] of this launch's first output row
+    int rout0;                 // output row of that row
+    unsigned long long* count;
+    int accumulate;            // positions continue from *count
+    void* ws;
+    int32_t* status;
+    // the launch whose first output row is the call's row o, with its workspace
+    RangeOut at(int o, void* w) const {
+        RangeOut r = *this;
+        r.row_ptr = row_ptr + o;
+        r.rout0 = o;
+        r.accumulate = o > 0;
+        r.ws = w;
+        return r;
+    }
+};
+// a call's output before any launch: row 0, nothing accumulated, no workspace yet
+inline RangeOut range_out(int32_t* rows, int32_t* cols, float* vals, unsigned char* codes, int64_t cap, int64_t* row_ptr,
+                          unsigned long long* count, int32_t* status) {
+    RangeOut r = {};
+    r.rows = rows;
+    r.cols = cols;
+    r.vals = vals;
+    r.codes = codes;
+    r.cap = cap;
+    r.row_ptr = row_ptr;
+    r.count = count;
+    r.status = status;
+    return r;
+}
+
+struct ListOut {               // k-entry lists per row
+    float* val;                // [rows][k]
+    int32_t* idx;
+    int k;
+    unsigned char* codes;      // [rows][k] directions / codes of the ranking pipeline (launch_seq_dirs), or nullptr
+    ListOut at(size_t row) const { return {val + row * k, idx + row * k, k, codes ? codes + row * k : nullptr}; }
+};
+
+struct MineSpec {              // the pose-class condition of mined pairs
+    int positives;             // SGPR_MINE_POSITIVES, else the negatives
+    const double* col_pose;
+    const double* row_pose;    // [rows][2] or nullptr: the pose of the row's own column
+    double d_pos, d_neg;
+    MineSpec from(int r) const {
+        MineSpec m = *this;
+        if (m.row_pose) m.row_pose += 2 * (size_t)r;
+        return m;
+    }
+};
+inline MineSpec mine_spec(int flags, const double* col_pose, const double* row_pose, double d_pos, double d_neg) {
+    MineSpec m;
+    m.positives = (flags & SGPR_MINE_POSITIVES) ? 1 : 0;
+    m.col_pose = col_pose;
+    m.row_pose = row_pose;
+    m.d_pos = d_pos;
+    m.d_neg = d_neg;
+    return m;
+}
+
+struct FilterOut {             // a filter's Q block and the direction / code taken
+    float* out;                // [rows][ldo]
+    int64_t ldo;
+    unsigned char* code;       // [rows][ldc] or nullptr
+    int64_t ldc;
+};
 
 int launch_embed(const sgpr_handle* h, const EmbedPlan& plan, const EmbedArgs& a, hipStream_t stream);
 // fills table[kSemTableFloats] (layout: sem_g | sem_xx | sem_a2 | sem_b2) and *vmax_out (largest |layer-1 output|)
@@ -255,85 +393,67 @@ int launch_call_range(const sgpr_handle* h, const float* rows, int R, const floa
 size_t score_all_pairs_multi_ws_bytes(int n, const sgpr_pairs_job* jobs);
 int launch_score_all_pairs_multi(const sgpr_handle* h, int n, const sgpr_pairs_job* jobs, void* ws, hipStream_t stream);
 size_t score_topk_ws_bytes(const sgpr_handle* h, int R, int M, int k);
-int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
-                      int row0, int window, int causal, int k, float* val, int32_t* idx, void* ws, hipStream_t stream);
+int launch_score_topk(const sgpr_handle* h, const PooledRect& p, const Eligible& e, const ListOut& out, void* ws,
+                      hipStream_t stream);
 // sgpr_topk_rows' selection with a row_self table, the causal rule and an output row stride of k (sgpr_metrics.hip)
-int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                         int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
+int launch_topk_rows_ext(const ScoreBlock& b, const Eligible& e, const ListOut& out, int32_t* status, hipStream_t stream);
 // the large-k selection of a resident n x M block into [n][k] (sgpr_select.hip); ws_clean: ws is what an earlier call on
 // the same stream left (its histograms are clear)
 size_t select_ws_bytes(int n, int M);
 // ws_clean holds only for a block whose select_group_rows is at most that of the call before it on the same ws: a call
 // leaves its own histogram rows clear and its state / counts right behind them
 int select_group_rows(int n);
-int launch_select_rows(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                       int causal, int k, float* val, int32_t* idx, void* ws, bool ws_clean, int32_t* status,
-                       hipStream_t stream);
+int launch_select_rows(const ScoreBlock& b, const Eligible& e, const ListOut& out, void* ws, bool ws_clean,
+                       int32_t* status, hipStream_t stream);
 // the diagonal score filter of a resident R x M matrix (sgpr_seq.hip): Q for rows ctx .. R-1 into out [R - ctx][ldo],
-// the direction taken into dir [R - ctx][ldd] (or nullptr); flags: SGPR_SEQ_FORWARD | SGPR_SEQ_REVERSE, at least one
-int launch_seq_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, float* out, int64_t ldo,
-                      unsigned char* dir, int64_t ldd, hipStream_t stream);
+// the direction taken into code [R - ctx][ldc] (or nullptr); of `seq`: ctx, L, dirs
+int launch_seq_filter(const ScoreBlock& b, const SeqSpec& seq, const FilterOut& out, hipStream_t stream);
 // out [n][k] = dir [n][ld] at the selected columns idx [n][k] (dir == nullptr: `fixed`); 0 where idx is -1
 int launch_seq_dirs(const int32_t* idx, int n, int k, const unsigned char* dir, int64_t ld, int fixed,
                     unsigned char* out, hipStream_t stream);
-// the path-set score filter of a resident R x M matrix (seq_path_kernel, sgpr_seq.hip): launch_seq_filter's arguments with a host
-// table offsets [n_paths][L] (already checked; copied into the launch) and the winner's code (direction bit | path << 1)
-// into code [R - ctx][ldc] (or nullptr)
-int launch_seq_path_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
-                           int n_paths, float* out, int64_t ldo, unsigned char* code, int64_t ldc, hipStream_t stream);
-// the session-aware path-set filter of a resident R x M matrix (session_kernel, sgpr_seq.hip): launch_seq_path_filter's arguments
-// (offsets == nullptr: the unit diagonal) with host session tables (already checked; nullptr: one session; copied into
-// the launch) and the session window on the end point (row_self [R] / row0 belong to the matrix's row 0; window < 0: none)
-int launch_session_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
-                          int n_paths, const int32_t* row_starts, int n_row, const int32_t* col_starts, int n_col,
-                          const int32_t* row_self, int row0, int window, float* out, int64_t ldo, unsigned char* code,
-                          int64_t ldc, hipStream_t stream);
+// the path-set score filter of a resident R x M matrix (seq_path_kernel, sgpr_seq.hip): launch_seq_filter's arguments with
+// seq's path table and the winner's code (direction bit | path << 1) into out.code
+int launch_seq_path_filter(const ScoreBlock& b, const SeqSpec& seq, const FilterOut& out, hipStream_t stream);
+// the session-aware path-set filter of a resident R x M matrix (session_kernel, sgpr_seq.hip): launch_seq_path_filter's
+// arguments (seq.offsets == nullptr: the unit diagonal) with seq's session tables and the session window on the end point
+// (e.row_self [R] / e.row0 belong to the matrix's row 0; e.causal is not the filter's)
+int launch_session_filter(const ScoreBlock& b, const SeqSpec& seq, const Eligible& e, const FilterOut& out,
+                          hipStream_t stream);
 // the peak filter of a resident n x M block (sgpr_peak.hip): out [n][ldo] = score at a peak within `radius` columns, -inf
-// elsewhere; eligibility as launch_select_rows (row_self [n] / row0 belong to the block's row 0)
-int launch_peak_filter(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                       int causal, int radius, float* out, int64_t ldo, hipStream_t stream);
+// elsewhere; eligibility as launch_select_rows (e.row_self [n] / e.row0 belong to the block's row 0)
+int launch_peak_filter(const ScoreBlock& b, const Eligible& e, int radius, float* out, int64_t ldo, hipStream_t stream);
 // sgpr_score_mine on the production handle (positives: SGPR_MINE_POSITIVES, else the negatives) and its selection on a
 // resident block (sgpr_mine_rows, the chunked path of the other handles; sgpr_metrics.hip)
 size_t score_mine_ws_bytes(const sgpr_handle* h, int R, int M, int k);
-int launch_score_mine(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
-                      int row0, int window, int causal, int positives, const double* col_pose, const double* row_pose,
-                      double d_pos, double d_neg, int k, float* val, int32_t* idx, void* ws, hipStream_t stream);
-int launch_mine_rows(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                     int causal, int positives, const double* col_pose, const double* row_pose, double d_pos, double d_neg,
-                     int k, float* val, int32_t* idx, int32_t* status, hipStream_t stream);
+int launch_score_mine(const sgpr_handle* h, const PooledRect& p, const Eligible& e, const MineSpec& mine,
+                      const ListOut& out, void* ws, hipStream_t stream);
+int launch_mine_rows(const ScoreBlock& b, const Eligible& e, const MineSpec& mine, const ListOut& out, int32_t* status,
+                     hipStream_t stream);
 size_t score_above_ws_bytes(const sgpr_handle* h, int R, int M);
 size_t rows_above_ws_bytes(int R);
 int launch_above_empty(int R, int64_t* row_ptr, unsigned long long* count, hipStream_t stream);
-int launch_score_above(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
-                       int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
-                       int64_t cap, int64_t* row_ptr, unsigned long long* count, void* ws, hipStream_t stream);
-// the range selection of a resident R x M block (sgpr_rows_above, the chunked path of sgpr_score_above): row_ptr [R + 1]
-// of the block's rows, output rows rout0 + r; accumulate: positions continue from *count
-int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                      int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals, int64_t cap, int64_t* row_ptr,
-                      int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status, hipStream_t stream);
+// (out.row_ptr == nullptr: the front of out.ws holds it; out.status is not read: the handle's)
+int launch_score_above(const sgpr_handle* h, const PooledRect& p, const Eligible& e, float thr, const RangeOut& out,
+                       hipStream_t stream);
+// the range selection of a resident R x M block (sgpr_rows_above, the chunked path of sgpr_score_above): out.row_ptr
+// [R + 1] of the block's rows, output rows out.rout0 + r
+int launch_rows_above(const ScoreBlock& b, const Eligible& e, float thr, const RangeOut& out, hipStream_t stream);
 // above_scan_kernel on its own: cnt [n] -> row_ptr [n + 1] and *count, both continuing from *count with accumulate
 int launch_above_scan(const int32_t* cnt, int n, int64_t* row_ptr, unsigned long long* count, int accumulate,
                       hipStream_t stream);
 // the range selection of the sequence-matched score of a resident R x M block (sgpr_seq.hip; sgpr_seq_rows_above and
 // each row block of sgpr_score_seq_above): the eligible pairs of rows ctx .. R-1 with Q >= thr, row-major, as output
-// rows rout0 + r - ctx; row_self [R] / row0 belong to the block's row 0, row_ptr [R - ctx + 1] to its first output row;
-// accumulate: positions continue from *count.  ws: seq_above_ws_bytes(R - ctx, M)
+// rows out.rout0 + r - ctx; e.row_self [R] / e.row0 belong to the block's row 0, out.row_ptr [R - ctx + 1] to its first
+// output row.  out.ws: seq_above_ws_bytes(R - ctx, M)
 size_t seq_above_ws_bytes(int n, int M);
-int launch_seq_above(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* row_self,
-                     int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
-                     unsigned char* odirs, int64_t cap, int64_t* row_ptr, int rout0, unsigned long long* count,
-                     int accumulate, void* ws, int32_t* status, hipStream_t stream);
+int launch_seq_above(const ScoreBlock& b, const SeqSpec& seq, const Eligible& e, float thr, const RangeOut& out,
+                     hipStream_t stream);
 // seq_above_rowscan_kernel on its own (sgpr_seq.hip): seg [n][nseg] -> exclusive offsets in place, cnt [n] = row totals
 int launch_seq_above_rowscan(int32_t* seg, int n, int nseg, int32_t* cnt, hipStream_t stream);
 // launch_seq_above on the session-aware path-set score with a minimum term count (session_above_kernel, sgpr_seq.hip; sgpr_session_rows_above
 // and each row block of sgpr_score_session_above): launch_session_filter's paths, tables and session window, codes in
-// place of directions.  ws: seq_above_ws_bytes(R - ctx, M)
-int launch_session_above(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
-                         int n_paths, const int32_t* row_starts, int n_row, const int32_t* col_starts, int n_col,
-                         const int32_t* row_self, int row0, int window, int causal, int min_terms, float thr,
-                         int32_t* orows, int32_t* ocols, float* ovals, unsigned char* ocodes, int64_t cap,
-                         int64_t* row_ptr, int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status,
+// place of directions.  out.ws: seq_above_ws_bytes(R - ctx, M)
+int launch_session_above(const ScoreBlock& b, const SeqSpec& seq, const Eligible& e, float thr, const RangeOut& out,
                          hipStream_t stream);
 // the fused evaluation epilogues of the all-pairs tail (production handle): T >= 0 the threshold counts (count == NULL,
 // d_out [T + 3]), T < 0 the positives (out [cap], count [2])

@@ -139,7 +139,7 @@ __device__ __forceinline__ int uf_root_final(const int* parent, int x) {
 }
 
 // ------------------------------------------------------------------ host: workspace carving
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline size_t align256(size_t v) { return a256(v); }   // (the map back end's name for it)
 
 // slots of a table for n keys: a power of two, at least 1024 and at least 2 n (SIZING above)
 inline size_t table_slots(size_t n) {

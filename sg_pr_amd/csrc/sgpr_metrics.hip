@@ -219,8 +219,7 @@ int launch_slab_fold(const unsigned* slabs, int n_slabs, int words, int T, unsig
                      unsigned long long* out_t, int per, hipStream_t stream) {
     hipLaunchKernelGGL(slab_fold_kernel, dim3((unsigned)((T + 3 + 31) / 32)), dim3(1024), 0, stream, slabs, n_slabs, words, T,
                        out, accumulate, out_t, per);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "slab_fold_kernel launch");
+    return launched("slab_fold_kernel launch");
 }
 
 // ------------------------------------------------------------------ F1-max in one call (sgpr_f1_max)
@@ -1427,17 +1426,16 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     }
 }
 
-int launch_topk_rows_ext(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                         int causal, int k, float* val, int32_t* idx, int32_t* status, hipStream_t s) {
-    if (R == 0) return SGPR_OK;
-    const dim3 grid((R + 3) / 4), block(256);
-    return launch_list_k(k, "topk_rows_kernel launch", [&](auto K) {
-        if (causal)
-            hipLaunchKernelGGL((topk_rows_kernel<K, true, true>), grid, block, 0, s, score, R, M, ld, row0, window, val, idx,
-                               row_self, k, status);
+int launch_topk_rows_ext(const ScoreBlock& b, const Eligible& e, const ListOut& out, int32_t* status, hipStream_t s) {
+    if (b.R == 0) return SGPR_OK;
+    const dim3 grid((b.R + 3) / 4), block(256);
+    return launch_list_k(out.k, "topk_rows_kernel launch", [&](auto K) {
+        if (e.causal)
+            hipLaunchKernelGGL((topk_rows_kernel<K, true, true>), grid, block, 0, s, b.score, b.R, b.M, b.ld, e.row0,
+                               e.window, out.val, out.idx, e.row_self, out.k, status);
         else
-            hipLaunchKernelGGL((topk_rows_kernel<K, true, false>), grid, block, 0, s, score, R, M, ld, row0, window, val, idx,
-                               row_self, k, status);
+            hipLaunchKernelGGL((topk_rows_kernel<K, true, false>), grid, block, 0, s, b.score, b.R, b.M, b.ld, e.row0,
+                               e.window, out.val, out.idx, e.row_self, out.k, status);
     });
 }
 
@@ -1534,27 +1532,26 @@ __global__ __launch_bounds__(256) void mine_rows_kernel(const float* __restrict_
     }
 }
 
-int launch_mine_rows(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                     int causal, int positives, const double* col_pose, const double* row_pose, double d_pos, double d_neg,
-                     int k, float* val, int32_t* idx, int32_t* status, hipStream_t s) {
-    if (R == 0) return SGPR_OK;
+int launch_mine_rows(const ScoreBlock& b, const Eligible& e, const MineSpec& mine, const ListOut& out, int32_t* status,
+                     hipStream_t s) {
+    if (b.R == 0) return SGPR_OK;
     PairTruth t;
     memset(&t, 0, sizeof(t));
-    t.pose = col_pose;
-    t.d_pos = d_pos;
-    t.d_neg = d_neg;
-    const dim3 grid((R + 3) / 4), block(256);
-    return launch_list_k(k, "mine_rows_kernel launch", [&](auto K) {
-        auto go = [&](auto mine, auto is_causal) {
-            hipLaunchKernelGGL((mine_rows_kernel<K, mine, is_causal>), grid, block, 0, s, score, R, M, ld, row_self, row0,
-                               window, t, row_pose, k, val, idx, status);
+    t.pose = mine.col_pose;
+    t.d_pos = mine.d_pos;
+    t.d_neg = mine.d_neg;
+    const dim3 grid((b.R + 3) / 4), block(256);
+    return launch_list_k(out.k, "mine_rows_kernel launch", [&](auto K) {
+        auto go = [&](auto which, auto is_causal) {
+            hipLaunchKernelGGL((mine_rows_kernel<K, which, is_causal>), grid, block, 0, s, b.score, b.R, b.M, b.ld,
+                               e.row_self, e.row0, e.window, t, mine.row_pose, out.k, out.val, out.idx, status);
         };
         using Neg = std::integral_constant<int, 1>;
         using Pos = std::integral_constant<int, 2>;
-        if (positives)
-            causal ? go(Pos(), std::true_type()) : go(Pos(), std::false_type());
+        if (mine.positives)
+            e.causal ? go(Pos(), std::true_type()) : go(Pos(), std::false_type());
         else
-            causal ? go(Neg(), std::true_type()) : go(Neg(), std::false_type());
+            e.causal ? go(Neg(), std::true_type()) : go(Neg(), std::false_type());
     });
 }
 
@@ -1605,9 +1602,7 @@ int sgpr_pair_positives(const sgpr_handle* h, const float* d_score, int R, int M
     const PairScan sc = make_scan(d_score, R, M, ld, row0, d_pose_xz, d_pos, d_neg, d_gt, ldg);
     hipLaunchKernelGGL(pair_positives_kernel, dim3(h->num_cus * 8), dim3(256), 0, s, sc, capacity > 0 ? d_out : nullptr,
                        (long long)capacity, d_count);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "pair_positives_kernel launch");
-    return SGPR_OK;
+    return launched("pair_positives_kernel launch");
 }
 
 namespace sgpr {
@@ -1617,8 +1612,7 @@ int launch_pair_positives_more(const sgpr_handle* h, const float* score, int R, 
     const PairScan sc = make_scan(score, R, M, ld, truth.row0, truth.pose, truth.d_pos, truth.d_neg, truth.gt, truth.ldg);
     hipLaunchKernelGGL(pair_positives_kernel, dim3(h->num_cus * 8), dim3(256), 0, stream, sc, cap > 0 ? out : nullptr,
                        (long long)cap, count);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "pair_positives_kernel launch");
+    return launched("pair_positives_kernel launch");
 }
 
 int launch_pair_counts_more(const sgpr_handle* h, const float* score, int R, int M, int64_t ld, const PairTruth& truth,
@@ -1642,8 +1636,7 @@ int launch_pair_counts_more(const sgpr_handle* h, const float* score, int R, int
     const size_t lds = ((size_t)1 << thr_levels(T)) * sizeof(float) + (size_t)slab_counters(T) * sizeof(unsigned) +
                        (rank ? (size_t)T * sizeof(unsigned long long) : 0);
     hipLaunchKernelGGL(pair_threshold_count_kernel, dim3(h->num_cus), dim3(PC_THREADS), lds, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "pair_threshold_count_kernel launch");
+    if (int rc = launched("pair_threshold_count_kernel launch")) return rc;
     return launch_slab_fold(slabs, h->num_cus, slab_words(T), T, d_out, accumulate, nullptr, 1, stream);
 }
 }  // namespace sgpr
@@ -1687,7 +1680,6 @@ int sgpr_pair_threshold_counts(const sgpr_handle* h, const float* d_score, int R
 
 // ---- sgpr_f1_max: workspace = header (counts, control block, device-side sizes) | negatives by bin | pairs from a bin on
 //      (two arrays) | candidate-bin marks | thresholds, their info, negatives by bucket of pass B | positives | counter slabs
-static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct F1Layout {
     size_t off_posb, off_negb, off_negbt, off_tpge, off_fpge, off_mark, off_thr, off_info, off_neg2, off_pos, off_slabs, off_cls, total;
     long long cap;
@@ -1780,9 +1772,7 @@ int sgpr_f1_max(const sgpr_handle* h, const float* d_score, int R, int M, int64_
                        ctrl, reinterpret_cast<unsigned long long*>(ws + 128), posb, negb_t);
     hipLaunchKernelGGL(f1_refine_kernel, dim3(L.slabs_b), dim3(F1_THREADS), 0, s, sc, mark, thr, dT2, neg2, cls, info, ctrl,
                        reinterpret_cast<unsigned*>(ws + 200), d_result);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "sgpr_f1_max launches");
-    return SGPR_OK;
+    return launched("sgpr_f1_max launches");
 }
 
 int sgpr_topk_rows(const sgpr_handle* h, const float* d_score, int R, int M, int64_t ld, int row0, int window, int k,

@@ -117,18 +117,18 @@ __global__ __launch_bounds__(PEAK_NT) void peak_filter_kernel(const PeakArgs a) 
 }
 
 // arguments already checked (0 <= rho <= SGPR_PEAK_MAX_RADIUS, ld, ldo >= M)
-int launch_peak_filter(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                       int causal, int rho, float* out, int64_t ldo, hipStream_t s) {
+int launch_peak_filter(const ScoreBlock& b, const Eligible& el, int rho, float* out, int64_t ldo, hipStream_t s) {
+    const int n = b.R, M = b.M;
     if (n <= 0 || M <= 0) return SGPR_OK;
     PeakArgs a;
-    a.score = score;
+    a.score = b.score;
     a.n = n;
     a.M = M;
-    a.ld = ld;
-    a.row_self = row_self;
-    a.row0 = row0;
-    a.window = window;
-    a.causal = causal;
+    a.ld = b.ld;
+    a.row_self = el.row_self;
+    a.row0 = el.row0;
+    a.window = el.window;
+    a.causal = el.causal;
     a.rho = rho;
     a.steps = 0;
     while ((2 << a.steps) <= rho) ++a.steps;
@@ -143,8 +143,7 @@ int launch_peak_filter(const float* score, int n, int M, int64_t ld, const int32
     const int arrays = a.steps == 0 ? 1 : (a.steps == 1 ? 2 : 3);
     const size_t lds = (size_t)arrays * (PEAK_STRIP + 2 * rho) * sizeof(unsigned);
     hipLaunchKernelGGL(peak_filter_kernel, dim3((unsigned)blocks), dim3(PEAK_NT), lds, s, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "peak_filter_kernel launch");
+    return launched("peak_filter_kernel launch");
 }
 
 }  // namespace sgpr

@@ -102,9 +102,7 @@ int launch_ntn(const float* w, const float* wb, const float* bias, const float* 
         return SGPR_E_INVALID;
     }
     hipLaunchKernelGGL(ntn_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, w, wb, bias, e1, e2, B, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ntn_kernel launch");
-    return SGPR_OK;
+    return launched("ntn_kernel launch");
 }
 
 int launch_score_pairs(const sgpr_handle* h, const float* p1, const int32_t* i1, const float* p2, const int32_t* i2,
@@ -116,9 +114,7 @@ int launch_score_pairs(const sgpr_handle* h, const float* p1, const int32_t* i1,
         return SGPR_E_INVALID;
     }
     hipLaunchKernelGGL(score_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, h->w, p1, i1, p2, i2, P, score);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_pairs_kernel launch");
-    return SGPR_OK;
+    return launched("score_pairs_kernel launch");
 }
 
 // ------------------------------------------------------------------ dense all-pairs
@@ -1865,8 +1861,7 @@ __global__ __launch_bounds__(256) void score_all_pairs_exact_kernel(const DevWei
 static int launch_ntn_prep(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const ApOperands& o,
                            int nrng, hipStream_t stream) {
     hipLaunchKernelGGL(ntn_prep_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, o.Ab, o.ur, o.rng, o.Cb);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "ntn_prep_kernel launch");
+    return launched("ntn_prep_kernel launch");
 }
 
 // one call's range partials folded into g (a float4, max with what g holds): its launches then read g alone (nrng = 1)
@@ -1891,8 +1886,7 @@ int launch_call_range(const sgpr_handle* h, const float* rows, int R, const floa
         const int rc = launch_ntn_prep(h, rows + (size_t)r0 * F, n, cols, M, o, nrng, stream);
         if (rc != SGPR_OK) return rc;
         hipLaunchKernelGGL(ap_range_fold_kernel, dim3(1), dim3(256), 0, stream, o.rng, nrng, g);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "ap_range_fold_kernel launch");
+        if (int rc = launched("ap_range_fold_kernel launch")) return rc;
     }
     return SGPR_OK;
 }
@@ -1906,20 +1900,16 @@ int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const
     if (wide) {                                            // three bf16 planes: the reference's operand width, fp32's range
         hipLaunchKernelGGL(ntn_prep_wide_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, R, cols, M, o.Ab, o.ur, o.rng,
                            o.Cb);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "ntn_prep_wide_kernel launch");
+        if (int rc = launched("ntn_prep_wide_kernel launch")) return rc;
         const int64_t slots = (int64_t)h->num_cus * APW_OCC;
         const unsigned grid = (unsigned)(items < slots ? items : slots);
         hipLaunchKernelGGL(score_all_pairs_wide_kernel, dim3(grid), dim3(256), 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, score,
                            ld);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "score_all_pairs_wide_kernel launch");
+        if (int rc = launched("score_all_pairs_wide_kernel launch")) return rc;
         const int64_t eslots = (int64_t)h->num_cus * AP_OCC;      // (every workgroup reads the partials, as the f16 tail's do)
         hipLaunchKernelGGL(score_all_pairs_exact_kernel, dim3((unsigned)(items < eslots ? items : eslots)), dim3(256), 0,
                            stream, h->w, R, M, o.rng, nrng, rows, cols, score, ld);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "score_all_pairs_exact_kernel launch");
-        return SGPR_OK;
+        return launched("score_all_pairs_exact_kernel launch");
     }
     const int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
     if (rc != SGPR_OK) return rc;
@@ -1927,15 +1917,13 @@ int launch_score_all_pairs(const sgpr_handle* h, const float* rows, int R, const
     const unsigned grid = (unsigned)(items < slots ? items : slots);
     hipLaunchKernelGGL((score_all_pairs_kernel<AP_OCC, AP_NI, 0>), dim3(grid), dim3(256), 0, stream, h->w, R, M, o.Ab, o.Cb,
                        o.ur, crng ? crng : o.rng, crng ? 1 : nrng, rows, cols, score, ld);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_all_pairs_kernel launch");
-    return SGPR_OK;
+    return launched("score_all_pairs_kernel launch");
 }
 
 
 size_t score_all_pairs_multi_ws_bytes(int n, const sgpr_pairs_job* jobs) {
     size_t total = 0;
-    for (int j = 0; j < n; ++j) total += align256(score_all_pairs_ws_bytes(jobs[j].R, jobs[j].M));
+    for (int j = 0; j < n; ++j) total += a256(score_all_pairs_ws_bytes(jobs[j].R, jobs[j].M));
     return total;
 }
 
@@ -1962,7 +1950,7 @@ int launch_score_all_pairs_multi(const sgpr_handle* h, int n, const sgpr_pairs_j
         q.rng = o.rng;
         q.Ab = o.Ab;
         q.Cb = o.Cb;
-        base += align256(score_all_pairs_ws_bytes(R, M));
+        base += a256(score_all_pairs_ws_bytes(R, M));
         a.block0[a.n] = blocks;
         a.item0[a.n] = (int)items;
         blocks += nrng;
@@ -1977,17 +1965,14 @@ int launch_score_all_pairs_multi(const sgpr_handle* h, int n, const sgpr_pairs_j
     a.block0[a.n] = blocks;
     a.item0[a.n] = (int)items;
     hipLaunchKernelGGL(ntn_prep_multi_kernel, dim3(blocks), dim3(256), 0, stream, h->w, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ntn_prep_multi_kernel launch");
+    if (int rc = launched("ntn_prep_multi_kernel launch")) return rc;
     const int64_t slots = (int64_t)h->num_cus * AP_MULTI_OCC;
     const unsigned grid = (unsigned)(items < slots ? items : slots);
     // (one row graph at a time here: at four workgroups per CU interleaving two cost this instance - two instantiations
     //  of the loop in one job loop - 380 -> ~900 bytes of scratch per lane, 334 -> 420 us on the five KITTI matrices; at
     //  three per CU nothing spills either way and the two are on par, 358.9 / 360.8 us: same-box A/Bs, round 5)
     hipLaunchKernelGGL((score_all_pairs_multi_kernel<AP_MULTI_OCC, 1>), dim3(grid), dim3(256), 0, stream, h->w, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_all_pairs_multi_kernel launch");
-    return SGPR_OK;
+    return launched("score_all_pairs_multi_kernel launch");
 }
 
 // ------------------------------------------------------------------ fused score + top-k (sgpr_score_topk)
@@ -2001,31 +1986,41 @@ static int64_t topk_grid(const sgpr_handle* h, int R, int M) {
 size_t score_topk_ws_bytes(const sgpr_handle* h, int R, int M, int k) {
     if (R == 0 || M == 0) return 0;
     const size_t lists = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS * k;
-    return align256(score_all_pairs_ws_bytes(R, M)) + align256(lists * sizeof(float)) + lists * sizeof(int32_t);
+    return a256(score_all_pairs_ws_bytes(R, M)) + a256(lists * sizeof(float)) + lists * sizeof(int32_t);
 }
 
 // the list arguments of sgpr_score_topk / sgpr_score_mine: the result, and the partial lists behind the operands
-static TopkArgs topk_args(const sgpr_handle* h, int R, int M, const int32_t* row_self, int row0, int window, int causal,
-                          int k, float* val, int32_t* idx, void* ws) {
-    const size_t lists = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS * k;
-    float* pval = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + align256(score_all_pairs_ws_bytes(R, M)));
-    int32_t* pidx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(pval) + align256(lists * sizeof(float)));
-    return TopkArgs{row_self, row0, window, causal, k, 0, val, idx, pval, pidx, h->d_status};
+static TopkArgs topk_args(const sgpr_handle* h, int R, int M, const Eligible& e, const ListOut& out, void* ws) {
+    const size_t lists = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS * out.k;
+    TopkArgs a;
+    a.row_self = e.row_self;
+    a.row0 = e.row0;
+    a.window = e.window;
+    a.causal = e.causal;
+    a.k = out.k;
+    a.wg = 0;
+    a.val = out.val;
+    a.idx = out.idx;
+    a.pval = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + a256(score_all_pairs_ws_bytes(R, M)));
+    a.pidx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(a.pval) + a256(lists * sizeof(float)));
+    a.status = h->d_status;
+    return a;
 }
 
-int launch_score_topk(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
-                      int row0, int window, int causal, int k, float* val, int32_t* idx, void* ws, hipStream_t stream) {
+int launch_score_topk(const sgpr_handle* h, const PooledRect& p, const Eligible& e, const ListOut& out, void* ws,
+                      hipStream_t stream) {
+    const int R = p.R, M = p.M, k = out.k;
+    const float *rows = p.rows, *cols = p.cols;
     if (R == 0) return SGPR_OK;
     if (M == 0) {                                          // no column at all: every slot is empty
         const int64_t n = (int64_t)R * k;
-        hipLaunchKernelGGL(topk_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, val, idx);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SGPR_OK : hip_fail(e, "topk_fill_kernel launch");
+        hipLaunchKernelGGL(topk_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, out.val, out.idx);
+        return launched("topk_fill_kernel launch");
     }
     const int nrng = 2 * ap_prep_groups(R, M);
     const ApOperands o = ap_operands(ws, R, nrng, 2);
     const int64_t grid = topk_grid(h, R, M);
-    const TopkArgs a = topk_args(h, R, M, row_self, row0, window, causal, k, val, idx, ws);
+    const TopkArgs a = topk_args(h, R, M, e, out, ws);
     int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
     if (rc != SGPR_OK) return rc;
     const dim3 gd((unsigned)grid), bd(256), gm((unsigned)((R + AP_ROWS - 1) / AP_ROWS));
@@ -2050,15 +2045,15 @@ constexpr int AB_ROWS = 131072;
 static size_t above_block_ws_bytes(const sgpr_handle* h, int R, int M) {
     const size_t items = (size_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
     const size_t slots = (size_t)topk_grid(h, R, M) * 2 * AP_ROWS;
-    return align256(score_all_pairs_ws_bytes(R, M)) + align256(items) + align256((size_t)R * 4) + 2 * align256(slots * 4);
+    return a256(score_all_pairs_ws_bytes(R, M)) + a256(items) + a256((size_t)R * 4) + 2 * a256(slots * 4);
 }
 
 size_t score_above_ws_bytes(const sgpr_handle* h, int R, int M) {
     if (R == 0 || M == 0) return 0;
-    return align256((size_t)(R + 1) * 8) + above_block_ws_bytes(h, R < AB_ROWS ? R : AB_ROWS, M) + (R > AB_ROWS ? 256 : 0);
+    return a256((size_t)(R + 1) * 8) + above_block_ws_bytes(h, R < AB_ROWS ? R : AB_ROWS, M) + (R > AB_ROWS ? 256 : 0);
 }
 
-size_t rows_above_ws_bytes(int R) { return R == 0 ? 0 : align256((size_t)R * 4) + align256((size_t)(R + 1) * 8); }
+size_t rows_above_ws_bytes(int R) { return R == 0 ? 0 : a256((size_t)R * 4) + a256((size_t)(R + 1) * 8); }
 
 int launch_above_empty(int R, int64_t* row_ptr, unsigned long long* count, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), stream);
@@ -2066,12 +2061,13 @@ int launch_above_empty(int R, int64_t* row_ptr, unsigned long long* count, hipSt
     return e == hipSuccess ? SGPR_OK : hip_fail(e, "sgpr_score_above: clearing the counts");
 }
 
-// one row block: rows [rout0, rout0 + R) of the call; rp = the call's row_ptr + rout0; crng: the call's range (or
-// nullptr: the block is the call, its own partials are)
-static int launch_above_block(const sgpr_handle* h, const float* rows, int R, const float* cols, int M,
-                              const int32_t* row_self, int row0, int window, int causal, float thr, int32_t* orows,
-                              int32_t* ocols, float* ovals, int64_t cap, int64_t* rp, int rout0,
-                              unsigned long long* count, const float* crng, void* ws, hipStream_t stream) {
+// one row block: rows [out.rout0, out.rout0 + R) of the call; out.row_ptr = the call's row_ptr + out.rout0; crng: the
+// call's range (or nullptr: the block is the call, its own partials are)
+static int launch_above_block(const sgpr_handle* h, const PooledRect& p, const Eligible& el, float thr, const RangeOut& out,
+                              const float* crng, hipStream_t stream) {
+    const int R = p.R, M = p.M;
+    const float *rows = p.rows, *cols = p.cols;
+    void* ws = out.ws;
     const int nrng = 2 * ap_prep_groups(R, M);
     const ApOperands o = ap_operands(ws, R, nrng, 2);
     const float* krng = crng ? crng : o.rng;
@@ -2079,60 +2075,56 @@ static int launch_above_block(const sgpr_handle* h, const float* rows, int R, co
     const int64_t grid = topk_grid(h, R, M);
     const size_t items = (size_t)((M + AP_COLS - 1) / AP_COLS) * ((R + AP_ROWS - 1) / AP_ROWS);
     const size_t slots = (size_t)grid * 2 * AP_ROWS;
-    unsigned char* p = static_cast<unsigned char*>(ws) + align256(score_all_pairs_ws_bytes(R, M));
+    unsigned char* q = static_cast<unsigned char*>(ws) + a256(score_all_pairs_ws_bytes(R, M));
     AboveArgs a;
-    a.row_self = row_self;
-    a.row0 = row0;
-    a.window = window;
-    a.causal = causal;
+    a.row_self = el.row_self;
+    a.row0 = el.row0;
+    a.window = el.window;
+    a.causal = el.causal;
     a.pass = 1;
     a.wg = 0;
     a.thr = thr;
-    a.flag = p;
-    p += align256(items);
-    a.cnt = reinterpret_cast<int32_t*>(p);
-    p += align256((size_t)R * 4);
-    a.pcnt = reinterpret_cast<int32_t*>(p);
-    p += align256(slots * 4);
-    a.poff = reinterpret_cast<int32_t*>(p);
-    a.rout0 = rout0;
-    a.row_ptr = rp;
-    a.rows = orows;
-    a.cols = ocols;
-    a.vals = ovals;
-    a.cap = cap;
+    a.flag = q;
+    q += a256(items);
+    a.cnt = reinterpret_cast<int32_t*>(q);
+    q += a256((size_t)R * 4);
+    a.pcnt = reinterpret_cast<int32_t*>(q);
+    q += a256(slots * 4);
+    a.poff = reinterpret_cast<int32_t*>(q);
+    a.rout0 = out.rout0;
+    a.row_ptr = out.row_ptr;
+    a.rows = out.rows;
+    a.cols = out.cols;
+    a.vals = out.vals;
+    a.cap = out.cap;
     a.status = h->d_status;
-    hipError_t e = hipMemsetAsync(a.flag, 0, items, stream);
+    const hipError_t e = hipMemsetAsync(a.flag, 0, items, stream);
     if (e != hipSuccess) return hip_fail(e, "sgpr_score_above: clearing the item flags");
     const int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
     if (rc != SGPR_OK) return rc;
     const dim3 gd((unsigned)grid), bd(256);
     hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, krng, knrng,
                        rows, cols, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 1)");
+    if (int rc = launched("score_above_kernel launch (pass 1)")) return rc;
     hipLaunchKernelGGL(above_fold_kernel, dim3((unsigned)((R + AP_ROWS - 1) / AP_ROWS)), dim3(64), 0, stream, R, M, (int)grid, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "above_fold_kernel launch");
-    hipLaunchKernelGGL(above_scan_kernel, dim3(1), dim3(1024), 0, stream, a.cnt, R, rp, count, rout0 > 0 ? 1 : 0);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "above_scan_kernel launch");
-    if (cap == 0) return SGPR_OK;                          // count only
+    if (int rc = launched("above_fold_kernel launch")) return rc;
+    if (int rc = launch_above_scan(a.cnt, R, out.row_ptr, out.count, out.accumulate, stream)) return rc;
+    if (out.cap == 0) return SGPR_OK;                      // count only
     a.pass = 2;
     hipLaunchKernelGGL((score_above_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, R, M, o.Ab, o.Cb, o.ur, krng, knrng,
                        rows, cols, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_above_kernel launch (pass 2)");
-    return SGPR_OK;
+    return launched("score_above_kernel launch (pass 2)");
 }
 
-int launch_score_above(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
-                       int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
-                       int64_t cap, int64_t* row_ptr, unsigned long long* count, void* ws, hipStream_t stream) {
-    if (R == 0 || M == 0) return launch_above_empty(R, row_ptr, count, stream);
-    unsigned char* base = static_cast<unsigned char*>(ws);
-    int64_t* rp = row_ptr ? row_ptr : reinterpret_cast<int64_t*>(base);
-    void* bws = base + align256((size_t)(R + 1) * 8);
+int launch_score_above(const sgpr_handle* h, const PooledRect& p, const Eligible& e, float thr, const RangeOut& out,
+                       hipStream_t stream) {
+    const int R = p.R, M = p.M;
+    const float *rows = p.rows, *cols = p.cols;
+    if (R == 0 || M == 0) return launch_above_empty(R, out.row_ptr, out.count, stream);
+    unsigned char* base = static_cast<unsigned char*>(out.ws);
+    RangeOut call = out;
+    if (!call.row_ptr) call.row_ptr = reinterpret_cast<int64_t*>(base);
+    void* bws = base + a256((size_t)(R + 1) * 8);
     float* crng = nullptr;
     if (R > AB_ROWS) {
         crng = reinterpret_cast<float*>(static_cast<unsigned char*>(bws) + above_block_ws_bytes(h, AB_ROWS, M));
@@ -2141,9 +2133,8 @@ int launch_score_above(const sgpr_handle* h, const float* rows, int R, const flo
     }
     for (int r0 = 0; r0 < R; r0 += AB_ROWS) {
         const int n = R - r0 < AB_ROWS ? R - r0 : AB_ROWS;
-        const int rc = launch_above_block(h, rows + (size_t)r0 * F, n, cols, M, row_self ? row_self + r0 : nullptr,
-                                          row0 + r0, window, causal, thr, orows, ocols, ovals, cap, rp + r0, r0, count,
-                                          crng, bws, stream);
+        const PooledRect pb = {rows + (size_t)r0 * F, n, cols, M};
+        const int rc = launch_above_block(h, pb, e.from(r0), thr, call.at(r0, bws), crng, stream);
         if (rc != SGPR_OK) return rc;
     }
     return SGPR_OK;
@@ -2152,29 +2143,23 @@ int launch_score_above(const sgpr_handle* h, const float* rows, int R, const flo
 int launch_above_scan(const int32_t* cnt, int n, int64_t* row_ptr, unsigned long long* count, int accumulate,
                       hipStream_t stream) {
     hipLaunchKernelGGL(above_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, n, row_ptr, count, accumulate);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "above_scan_kernel launch");
+    return launched("above_scan_kernel launch");
 }
 
-int launch_rows_above(const float* score, int R, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                      int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals, int64_t cap, int64_t* row_ptr,
-                      int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status, hipStream_t stream) {
-    if (R == 0) return SGPR_OK;
-    int32_t* cnt = static_cast<int32_t*>(ws);
-    const dim3 grid((unsigned)((R + 3) / 4)), block(256);
-    hipLaunchKernelGGL(rows_above_kernel<1>, grid, block, 0, stream, score, R, M, ld, row_self, row0, window, causal, thr,
-                       cnt, row_ptr, rout0, orows, ocols, ovals, cap, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rows_above_kernel launch (pass 1)");
-    hipLaunchKernelGGL(above_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, R, row_ptr, count, accumulate);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "above_scan_kernel launch");
-    if (cap == 0) return SGPR_OK;
-    hipLaunchKernelGGL(rows_above_kernel<2>, grid, block, 0, stream, score, R, M, ld, row_self, row0, window, causal, thr,
-                       cnt, row_ptr, rout0, orows, ocols, ovals, cap, status);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rows_above_kernel launch (pass 2)");
-    return SGPR_OK;
+int launch_rows_above(const ScoreBlock& b, const Eligible& e, float thr, const RangeOut& out, hipStream_t stream) {
+    if (b.R == 0) return SGPR_OK;
+    int32_t* cnt = static_cast<int32_t*>(out.ws);
+    const dim3 grid((unsigned)((b.R + 3) / 4)), block(256);
+    auto pass = [&](auto P, const char* what) {
+        hipLaunchKernelGGL(rows_above_kernel<decltype(P)::value>, grid, block, 0, stream, b.score, b.R, b.M, b.ld,
+                           e.row_self, e.row0, e.window, e.causal, thr, cnt, out.row_ptr, out.rout0, out.rows, out.cols,
+                           out.vals, out.cap, out.status);
+        return launched(what);
+    };
+    if (int rc = pass(std::integral_constant<int, 1>(), "rows_above_kernel launch (pass 1)")) return rc;
+    if (int rc = launch_above_scan(cnt, b.R, out.row_ptr, out.count, out.accumulate, stream)) return rc;
+    if (out.cap == 0) return SGPR_OK;
+    return pass(std::integral_constant<int, 2>(), "rows_above_kernel launch (pass 2)");
 }
 
 // ------------------------------------------------------------------ fused evaluation (sgpr_score_positives / sgpr_score_threshold_counts)
@@ -2305,8 +2290,8 @@ size_t score_eval_ws_bytes(const sgpr_handle* h, int R, int M, int T) {
     if (R == 0 || M == 0) return 0;
     const int rb = eval_block_rows(h, R, M);
     const size_t ncc = (size_t)(M + AP_COLS - 1) / AP_COLS;
-    size_t b = align256(ncc * 4 * sizeof(double)) + align256(score_all_pairs_ws_bytes(rb, M));
-    if (T >= 0) b += align256((size_t)topk_grid(h, rb, M) * slab_words(T) * sizeof(unsigned));
+    size_t b = a256(ncc * 4 * sizeof(double)) + a256(score_all_pairs_ws_bytes(rb, M));
+    if (T >= 0) b += a256((size_t)topk_grid(h, rb, M) * slab_words(T) * sizeof(unsigned));
     return b + (rb < R ? 256 : 0);                        // (more than one block: the call's range, launch_call_range)
 }
 
@@ -2331,17 +2316,16 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
     const int rb = eval_block_rows(h, R, M), ncc = (M + AP_COLS - 1) / AP_COLS;
     unsigned char* p = static_cast<unsigned char*>(ws);
     double* cbox = reinterpret_cast<double*>(p);
-    p += align256((size_t)ncc * 4 * sizeof(double));
+    p += a256((size_t)ncc * 4 * sizeof(double));
     unsigned* slabs = nullptr;
     const int sw = slab_words(T < 0 ? 0 : T);
     if (counts) {
         slabs = reinterpret_cast<unsigned*>(p);
-        p += align256((size_t)topk_grid(h, rb, M) * sw * sizeof(unsigned));
+        p += a256((size_t)topk_grid(h, rb, M) * sw * sizeof(unsigned));
     }
     if (truth.pose) {
         hipLaunchKernelGGL(eval_colbox_kernel, dim3((unsigned)ncc), dim3(64), 0, stream, truth.pose, M, cbox);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "eval_colbox_kernel launch");
+        if (int rc = launched("eval_colbox_kernel launch")) return rc;
     }
     EvalArgs a;
     memset(&a, 0, sizeof(a));
@@ -2356,7 +2340,7 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
     a.th.T = T < 0 ? 0 : T;
     float* crng = nullptr;                                // more than one block: the f16 range of the whole rectangle
     if (rb < R) {
-        crng = reinterpret_cast<float*>(p + align256(score_all_pairs_ws_bytes(rb, M)));
+        crng = reinterpret_cast<float*>(p + a256(score_all_pairs_ws_bytes(rb, M)));
         const int rc = launch_call_range(h, rows, R, cols, M, rb, p, crng, stream);
         if (rc != SGPR_OK) return rc;
     }
@@ -2376,14 +2360,12 @@ int launch_score_eval(const sgpr_handle* h, const float* rows, int R, const floa
         if (!counts) {
             hipLaunchKernelGGL((score_positives_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, krng,
                                knrng, brows, cols, a);
-            e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "score_positives_kernel launch");
+            if (int rc = launched("score_positives_kernel launch")) return rc;
             continue;
         }
         hipLaunchKernelGGL((score_counts_kernel<TK_OCC, AP_NI>), gd, bd, 0, stream, h->w, n, M, o.Ab, o.Cb, o.ur, krng, knrng,
                            brows, cols, a, thr, at_least, slabs);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "score_counts_kernel launch");
+        if (int rc = launched("score_counts_kernel launch")) return rc;
         const int rc2 = launch_slab_fold(slabs, (int)grid, sw, T, d_out, r0 > 0 ? 1 : 0, nullptr, 1, stream);
         if (rc2 != SGPR_OK) return rc2;
     }
@@ -2436,48 +2418,48 @@ __global__ __launch_bounds__(256) void mine_fill_kernel(int64_t n, float v, floa
 
 size_t score_mine_ws_bytes(const sgpr_handle* h, int R, int M, int k) {
     if (R == 0 || M == 0) return 0;
-    return align256(score_topk_ws_bytes(h, R, M, k)) + align256((size_t)((M + AP_COLS - 1) / AP_COLS) * 4 * sizeof(double)) +
-           align256((size_t)R * 2 * sizeof(double)) + (size_t)((R + 3) / 4) * 4 * sizeof(double);
+    return a256(score_topk_ws_bytes(h, R, M, k)) + a256((size_t)((M + AP_COLS - 1) / AP_COLS) * 4 * sizeof(double)) +
+           a256((size_t)R * 2 * sizeof(double)) + (size_t)((R + 3) / 4) * 4 * sizeof(double);
 }
 
-int launch_score_mine(const sgpr_handle* h, const float* rows, int R, const float* cols, int M, const int32_t* row_self,
-                      int row0, int window, int causal, int positives, const double* col_pose, const double* row_pose,
-                      double d_pos, double d_neg, int k, float* val, int32_t* idx, void* ws, hipStream_t stream) {
+int launch_score_mine(const sgpr_handle* h, const PooledRect& p, const Eligible& e, const MineSpec& mine,
+                      const ListOut& out, void* ws, hipStream_t stream) {
+    const int R = p.R, M = p.M, k = out.k, positives = mine.positives;
+    const float *rows = p.rows, *cols = p.cols;
+    const double *col_pose = mine.col_pose, d_pos = mine.d_pos, d_neg = mine.d_neg;
     if (R == 0) return SGPR_OK;
-    hipError_t e;
     if (M == 0) {                                          // no column at all: every slot is empty
         const int64_t n = (int64_t)R * k;
         hipLaunchKernelGGL(mine_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n,
-                           positives ? INFINITY : -INFINITY, val, idx);
-        e = hipGetLastError();
-        return e == hipSuccess ? SGPR_OK : hip_fail(e, "mine_fill_kernel launch");
+                           positives ? INFINITY : -INFINITY, out.val, out.idx);
+        return launched("mine_fill_kernel launch");
     }
     const int nrng = 2 * ap_prep_groups(R, M), ncc = (M + AP_COLS - 1) / AP_COLS;
     const ApOperands o = ap_operands(ws, R, nrng, 2);
     const int64_t items = (int64_t)ncc * ((R + AP_ROWS - 1) / AP_ROWS);
     const int64_t grid = std::min<int64_t>(items, (int64_t)h->num_cus * MN_OCC);   // (<= topk_grid: the lists fit)
     // (c != self_r: a window of at least 0 cuts the own frame out)
-    const TopkArgs a = topk_args(h, R, M, row_self, row0, window < 0 ? 0 : window, causal, k, val, idx, ws);
+    Eligible cut = e;
+    if (cut.window < 0) cut.window = 0;
+    const TopkArgs a = topk_args(h, R, M, cut, out, ws);
     MineArgs m;
     memset(&m, 0, sizeof(m));
     m.truth.pose = col_pose;
     m.truth.d_pos = d_pos;
     m.truth.d_neg = d_neg;
     unsigned char* base = static_cast<unsigned char*>(ws);
-    double* cbox = reinterpret_cast<double*>(base + align256(score_topk_ws_bytes(h, R, M, k)));
-    double* rpose = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(cbox) + align256((size_t)ncc * 4 * sizeof(double)));
-    double* rbox = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(rpose) + align256((size_t)R * 2 * sizeof(double)));
+    double* cbox = reinterpret_cast<double*>(base + a256(score_topk_ws_bytes(h, R, M, k)));
+    double* rpose = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(cbox) + a256((size_t)ncc * 4 * sizeof(double)));
+    double* rbox = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(rpose) + a256((size_t)R * 2 * sizeof(double)));
     m.cbox = cbox;
     m.rpose = rpose;
     m.rbox = rbox;
     set_pose_cuts(m, d_pos, d_neg);
     hipLaunchKernelGGL(eval_colbox_kernel, dim3((unsigned)ncc), dim3(64), 0, stream, col_pose, M, cbox);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "eval_colbox_kernel launch");
-    hipLaunchKernelGGL(mine_rowpose_kernel, dim3((unsigned)(((R + 3) / 4 + 255) / 256)), dim3(256), 0, stream, R, M, row_self,
-                       row0, row_pose, col_pose, rpose, rbox);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "mine_rowpose_kernel launch");
+    if (int rc = launched("eval_colbox_kernel launch")) return rc;
+    hipLaunchKernelGGL(mine_rowpose_kernel, dim3((unsigned)(((R + 3) / 4 + 255) / 256)), dim3(256), 0, stream, R, M,
+                       e.row_self, e.row0, mine.row_pose, col_pose, rpose, rbox);
+    if (int rc = launched("mine_rowpose_kernel launch")) return rc;
     int rc = launch_ntn_prep(h, rows, R, cols, M, o, nrng, stream);
     if (rc != SGPR_OK) return rc;
     const dim3 gd((unsigned)grid), bd(256), gm((unsigned)((R + AP_ROWS - 1) / AP_ROWS));
@@ -2636,16 +2618,13 @@ int launch_score_pair_list(const sgpr_handle* h, const float* rows, const float*
     const ApOperands o = ap_operands(ws, NR, nrng, 2);
     hipLaunchKernelGGL(ntn_prep_list_kernel, dim3(nrng), dim3(256), 0, stream, h->w, rows, pl.row_ids, NR, cols, M, o.Ab, o.ur,
                        o.rng, o.Cb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ntn_prep_list_kernel launch");
+    if (int rc = launched("ntn_prep_list_kernel launch")) return rc;
     const int64_t wgs = ((int64_t)(NI + 3) / 4 + 3) / 4;          // one quad of items per wave, four waves per workgroup
     const int64_t slots = (int64_t)h->num_cus * 8;
     const unsigned grid = (unsigned)(wgs < slots ? wgs : slots);
     hipLaunchKernelGGL(score_pair_list_kernel, dim3(grid), dim3(256), 0, stream, h->w, pl, o.Ab, o.Cb, o.ur, o.rng, nrng, rows,
                        cols, score, exact ? 1 : 0);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "score_pair_list_kernel launch");
-    return SGPR_OK;
+    return launched("score_pair_list_kernel launch");
 }
 
 }  // namespace sgpr

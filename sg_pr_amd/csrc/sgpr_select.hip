@@ -343,8 +343,6 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_fill_kernel(int n, int k, con
     if (row_self && i < n) atomicOr(status, 16);
 }
 
-static size_t a256s(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // wide chunks while the grid has enough of them; a few long rows take narrow ones to reach every CU
 static int sel_chunk(int n, int M) {
     const int64_t wide = (int64_t)n * ((M + 4 * SEL_TILE - 1) / (4 * SEL_TILE));
@@ -355,41 +353,39 @@ static int sel_chunk(int n, int M) {
 size_t select_ws_bytes(int n, int M) {
     if (n <= 0 || M <= 0) return 0;
     const size_t g = (size_t)std::min(n, SEL_GROUP), nch = (size_t)((M + SEL_TILE - 1) / SEL_TILE);
-    return a256s(g * SEL_BINS * 4) + a256s(g * 16) + a256s(g * nch * 8);
+    return a256(g * SEL_BINS * 4) + a256(g * 16) + a256(g * nch * 8);
 }
 
 // rows per round of launches for a block of n rows: what the workspace's layout depends on (the histograms of
 // select_group_rows(n) rows come first, state and chunk counts behind them)
 int select_group_rows(int n) { return std::min(n, SEL_GROUP); }
 
-int launch_select_rows(const float* score, int n, int M, int64_t ld, const int32_t* row_self, int row0, int window,
-                       int causal, int k, float* val, int32_t* idx, void* ws, bool ws_clean, int32_t* status,
-                       hipStream_t s) {
+int launch_select_rows(const ScoreBlock& b, const Eligible& el, const ListOut& out, void* ws, bool ws_clean,
+                       int32_t* status, hipStream_t s) {
+    const int n = b.R, M = b.M, k = out.k;
     if (n == 0) return SGPR_OK;
-    hipError_t e;
     if (M == 0) {
         const int64_t total = std::max<int64_t>((int64_t)n * k, n);
         hipLaunchKernelGGL(sel_fill_kernel, dim3((unsigned)((total + SEL_THREADS - 1) / SEL_THREADS)), dim3(SEL_THREADS),
-                           0, s, n, k, row_self, val, idx, status);
-        e = hipGetLastError();
-        return e == hipSuccess ? SGPR_OK : hip_fail(e, "sel_fill_kernel launch");
+                           0, s, n, k, el.row_self, out.val, out.idx, status);
+        return launched("sel_fill_kernel launch");
     }
     const int G = std::min(n, SEL_GROUP), chunk = sel_chunk(n, M), nch = (M + chunk - 1) / chunk;
     unsigned char* p = static_cast<unsigned char*>(ws);
     SelRows a;
     a.M = M;
-    a.ld = ld;
-    a.window = window;
-    a.causal = causal;
+    a.ld = b.ld;
+    a.window = el.window;
+    a.causal = el.causal;
     a.k = k;
     a.chunk = chunk;
     a.nch = nch;
     a.hist = reinterpret_cast<unsigned*>(p);
-    a.state = reinterpret_cast<unsigned*>(p + a256s((size_t)G * SEL_BINS * 4));
-    a.cnt = reinterpret_cast<unsigned*>(p + a256s((size_t)G * SEL_BINS * 4) + a256s((size_t)G * 16));
+    a.state = reinterpret_cast<unsigned*>(p + a256((size_t)G * SEL_BINS * 4));
+    a.cnt = reinterpret_cast<unsigned*>(p + a256((size_t)G * SEL_BINS * 4) + a256((size_t)G * 16));
     a.status = status;
     if (!ws_clean) {                                      // every pick clears what it read: one clear per call
-        e = hipMemsetAsync(a.hist, 0, (size_t)G * SEL_BINS * 4, s);
+        const hipError_t e = hipMemsetAsync(a.hist, 0, (size_t)G * SEL_BINS * 4, s);
         if (e != hipSuccess) return hip_fail(e, "large top-k: clearing the histograms");
     }
     int P = 1;
@@ -397,11 +393,13 @@ int launch_select_rows(const float* score, int n, int M, int64_t ld, const int32
     const dim3 blk(SEL_THREADS);
     for (int r0 = 0; r0 < n; r0 += G) {
         const int g = std::min(G, n - r0);
-        a.score = score + (int64_t)r0 * ld;
-        a.row_self = row_self ? row_self + r0 : nullptr;
-        a.row0 = row0 + r0;
-        a.val = val + (size_t)r0 * k;
-        a.idx = idx + (size_t)r0 * k;
+        const Eligible eg = el.from(r0);
+        const ListOut og = out.at(r0);
+        a.score = b.score + (int64_t)r0 * b.ld;
+        a.row_self = eg.row_self;
+        a.row0 = eg.row0;
+        a.val = og.val;
+        a.idx = og.idx;
         const dim3 grid2((unsigned)nch, (unsigned)g), grid1((unsigned)g);
         hipLaunchKernelGGL(sel_hist_kernel<0>, grid2, blk, 0, s, a);
         hipLaunchKernelGGL(sel_pick_kernel<0>, grid1, blk, 0, s, a);
@@ -412,8 +410,8 @@ int launch_select_rows(const float* score, int n, int M, int64_t ld, const int32
         hipLaunchKernelGGL(sel_count_kernel, grid2, blk, 0, s, a);
         hipLaunchKernelGGL(sel_scatter_kernel, grid2, blk, 0, s, a);
         hipLaunchKernelGGL(sel_sort_kernel, grid1, blk, (size_t)P * 8, s, a, P);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "large top-k launches");
+        const int rc = launched("large top-k launches");
+        if (rc != SGPR_OK) return rc;
     }
     return SGPR_OK;
 }

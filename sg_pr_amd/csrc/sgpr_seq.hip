@@ -496,33 +496,33 @@ static void fill_rcp(float* rcp) {
 
 // the common prefix, the grid and the tile's LDS for a halo of H columns either side
 template <class A>
-static int fill_tile(A& a, const float* score, int R, int M, int64_t ld, int ctx, int L, int H, const char* what, Grid* g) {
-    a.score = score;
-    a.R = R;
-    a.M = M;
-    a.ld = ld;
-    a.ctx = ctx;
-    a.L = L;
-    const int64_t tx = (M + SEQ_TC - 1) / SEQ_TC, ty = (R - ctx + SEQ_TR - 1) / SEQ_TR;
+static int fill_tile(A& a, const ScoreBlock& b, const SeqSpec& seq, int H, const char* what, Grid* g) {
+    a.score = b.score;
+    a.R = b.R;
+    a.M = b.M;
+    a.ld = b.ld;
+    a.ctx = seq.ctx;
+    a.L = seq.L;
+    const int64_t tx = (b.M + SEQ_TC - 1) / SEQ_TC, ty = (b.R - seq.ctx + SEQ_TR - 1) / SEQ_TR;
     if (tx * ty > 0x7fffffffLL) {
         set_error(std::string(what) + ": more than 2^31 tiles");
         return SGPR_E_INVALID;
     }
     a.tiles_x = (int)tx;
     g->blocks = (unsigned)(tx * ty);
-    g->lds = (size_t)(std::min(SEQ_TR, R - ctx) + L - 1) * (SEQ_TC + 2 * H) * sizeof(float);
+    g->lds = (size_t)(std::min(SEQ_TR, b.R - seq.ctx) + seq.L - 1) * (SEQ_TC + 2 * H) * sizeof(float);
     return SGPR_OK;
 }
 
-// offsets [n_paths][L] packed into bytes (already checked; nullptr: the unit diagonal), H and rcp
+// seq.offsets [n_paths][L] packed into bytes (already checked; nullptr: the unit diagonal), H and rcp
 template <class A>
-static void fill_paths(A& a, const int32_t* offsets, int n_paths, int L) {
-    a.n_paths = offsets ? n_paths : 1;
+static void fill_paths(A& a, const SeqSpec& seq) {
+    a.n_paths = seq.offsets ? seq.n_paths : 1;
     a.H = 0;
     for (int p = 0; p < SGPR_SEQ_MAX_PATHS; ++p) {
         for (int j = 0; j < SEQ_WORDS; ++j) a.pt.off[p][j] = 0u;
-        for (int d = 0; p < a.n_paths && d < L; ++d) {
-            const int o = offsets ? offsets[(size_t)p * L + d] : d;
+        for (int d = 0; p < a.n_paths && d < seq.L; ++d) {
+            const int o = seq.offsets ? seq.offsets[(size_t)p * seq.L + d] : d;
             a.pt.off[p][d >> 2] |= (uint32_t)o << (8 * (d & 3));
             a.H = std::max(a.H, o);
         }
@@ -532,13 +532,22 @@ static void fill_paths(A& a, const int32_t* offsets, int n_paths, int L) {
 
 // the two session tables (already checked: 1..64 entries, the first 0, non-decreasing, <= R / <= M; nullptr: one session)
 template <class A>
-static void fill_sessions(A& a, const int32_t* row_starts, int n_row, const int32_t* col_starts, int n_col, int R, int M) {
-    a.n_row = row_starts ? n_row : 1;
-    a.n_col = col_starts ? n_col : 1;
+static void fill_sessions(A& a, const SeqSpec& seq, int R, int M) {
+    a.n_row = seq.row_starts ? seq.n_row : 1;
+    a.n_col = seq.col_starts ? seq.n_col : 1;
     for (int j = 0; j < SGPR_SESSION_MAX; ++j) {
-        a.row_starts[j] = row_starts && j < n_row ? row_starts[j] : (j == 0 ? 0 : R);
-        a.col_starts[j] = col_starts && j < n_col ? col_starts[j] : (j == 0 ? 0 : M);
+        a.row_starts[j] = seq.row_starts && j < seq.n_row ? seq.row_starts[j] : (j == 0 ? 0 : R);
+        a.col_starts[j] = seq.col_starts && j < seq.n_col ? seq.col_starts[j] : (j == 0 ? 0 : M);
     }
+}
+
+// where a filter writes
+template <class A>
+static void fill_out(A& a, const FilterOut& o) {
+    a.out = o.out;
+    a.ldo = o.ldo;
+    a.code = o.code;
+    a.ldc = o.ldc;
 }
 
 // one instantiation: its LDS limit raised once (halo_max: the largest halo it can be asked for), then the launch
@@ -549,50 +558,41 @@ static int launch_tile(const A& a, const Grid& g, int halo_max, const char* what
     const int rc = raise_lds_limit(&once, reinterpret_cast<const void*>(Kernel), lds_max, what);
     if (rc != SGPR_OK) return rc;
     hipLaunchKernelGGL(Kernel, dim3(g.blocks), dim3(SEQ_TC), g.lds, s, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, fail);
+    return launched(fail);
 }
 
-// f(FWD, REV) with the directions of `flags` as compile-time constants
+// f(FWD, REV) with the directions of `dirs` as compile-time constants
 template <class F>
-static int by_direction(int flags, F&& f) {
-    const bool fwd = (flags & SGPR_SEQ_FORWARD) != 0, rev = (flags & SGPR_SEQ_REVERSE) != 0;
+static int by_direction(int dirs, F&& f) {
+    const bool fwd = (dirs & SGPR_SEQ_FORWARD) != 0, rev = (dirs & SGPR_SEQ_REVERSE) != 0;
     if (fwd && rev) return f(std::true_type{}, std::true_type{});
     return fwd ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::true_type{});
 }
 
 // ------------------------------------------------------------------ the filters
-int launch_seq_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, float* out, int64_t ldo,
-                      unsigned char* dir, int64_t ldd, hipStream_t s) {
-    if (R - ctx <= 0 || M <= 0) return SGPR_OK;
+int launch_seq_filter(const ScoreBlock& b, const SeqSpec& seq, const FilterOut& out, hipStream_t s) {
+    if (b.R - seq.ctx <= 0 || b.M <= 0) return SGPR_OK;
     SeqArgs a;
     Grid g;
-    const int rc = fill_tile(a, score, R, M, ld, ctx, L, L - 1, "sequence filter", &g);
+    const int rc = fill_tile(a, b, seq, seq.L - 1, "sequence filter", &g);
     if (rc != SGPR_OK) return rc;
-    a.fwd = (flags & SGPR_SEQ_FORWARD) ? 1 : 0;
-    a.rev = (flags & SGPR_SEQ_REVERSE) ? 1 : 0;
-    a.out = out;
-    a.ldo = ldo;
-    a.code = dir;
-    a.ldc = ldd;
+    a.fwd = (seq.dirs & SGPR_SEQ_FORWARD) ? 1 : 0;
+    a.rev = (seq.dirs & SGPR_SEQ_REVERSE) ? 1 : 0;
+    fill_out(a, out);
     fill_rcp(a.rcp);
     return launch_tile<seq_filter_kernel>(a, g, SGPR_SEQ_MAX_LEN - 1, "sequence filter", "seq_filter_kernel launch", s);
 }
 
 // arguments already checked (paths: off[p][0] = 0, non-decreasing, <= SGPR_SEQ_PATH_MAX_OFFSET; 1 <= n_paths <= 16)
-int launch_seq_path_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
-                           int n_paths, float* out, int64_t ldo, unsigned char* code, int64_t ldc, hipStream_t s) {
-    if (R - ctx <= 0 || M <= 0) return SGPR_OK;
+int launch_seq_path_filter(const ScoreBlock& b, const SeqSpec& seq, const FilterOut& out, hipStream_t s) {
+    if (b.R - seq.ctx <= 0 || b.M <= 0) return SGPR_OK;
     SeqPathArgs a;
     Grid g;
-    fill_paths(a, offsets, n_paths, L);
-    const int rc = fill_tile(a, score, R, M, ld, ctx, L, a.H, "sequence path filter", &g);
+    fill_paths(a, seq);
+    const int rc = fill_tile(a, b, seq, a.H, "sequence path filter", &g);
     if (rc != SGPR_OK) return rc;
-    a.out = out;
-    a.ldo = ldo;
-    a.code = code;
-    a.ldc = ldc;
-    return by_direction(flags, [&](auto F, auto V) {
+    fill_out(a, out);
+    return by_direction(seq.dirs, [&](auto F, auto V) {
         return launch_tile<seq_path_kernel<decltype(F)::value, decltype(V)::value>>(
             a, g, SGPR_SEQ_PATH_MAX_OFFSET, "sequence path filter", "seq_path_kernel launch", s);
     });
@@ -600,25 +600,20 @@ int launch_seq_path_filter(const float* score, int R, int M, int64_t ld, int ctx
 
 // arguments already checked (paths as launch_seq_path_filter's, offsets == nullptr: the unit diagonal; tables: see
 // fill_sessions)
-int launch_session_filter(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
-                          int n_paths, const int32_t* row_starts, int n_row, const int32_t* col_starts, int n_col,
-                          const int32_t* row_self, int row0, int window, float* out, int64_t ldo, unsigned char* code,
-                          int64_t ldc, hipStream_t s) {
-    if (R - ctx <= 0 || M <= 0) return SGPR_OK;
+int launch_session_filter(const ScoreBlock& b, const SeqSpec& seq, const Eligible& e, const FilterOut& out,
+                          hipStream_t s) {
+    if (b.R - seq.ctx <= 0 || b.M <= 0) return SGPR_OK;
     SessionArgs a;
     Grid g;
-    fill_paths(a, offsets, n_paths, L);
-    const int rc = fill_tile(a, score, R, M, ld, ctx, L, a.H, "session filter", &g);
+    fill_paths(a, seq);
+    const int rc = fill_tile(a, b, seq, a.H, "session filter", &g);
     if (rc != SGPR_OK) return rc;
-    fill_sessions(a, row_starts, n_row, col_starts, n_col, R, M);
-    a.out = out;
-    a.ldo = ldo;
-    a.code = code;
-    a.ldc = ldc;
-    a.row_self = row_self;
-    a.row0 = row0;
-    a.window = window;
-    return by_direction(flags, [&](auto F, auto V) {
+    fill_sessions(a, seq, b.R, b.M);
+    fill_out(a, out);
+    a.row_self = e.row_self;
+    a.row0 = e.row0;
+    a.window = e.window;
+    return by_direction(seq.dirs, [&](auto F, auto V) {
         return launch_tile<session_kernel<decltype(F)::value, decltype(V)::value>>(
             a, g, SGPR_SEQ_PATH_MAX_OFFSET, "session filter", "session_kernel launch", s);
     });
@@ -627,44 +622,26 @@ int launch_session_filter(const float* score, int R, int M, int64_t ld, int ctx,
 // ------------------------------------------------------------------ range selection
 int launch_seq_above_rowscan(int32_t* seg, int n, int nseg, int32_t* cnt, hipStream_t s) {
     hipLaunchKernelGGL(seq_above_rowscan_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, seg, n, nseg, cnt);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "seq_above_rowscan_kernel launch");
+    return launched("seq_above_rowscan_kernel launch");
 }
 
-static size_t seq_a256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the workspace of a range selection: seg [n][ceil(M / 64)] i32 | cnt [n] i32
-static size_t seq_seg_bytes(int n, int M) { return seq_a256((size_t)n * ((M + 63) / 64) * 4); }
+static size_t seq_seg_bytes(int n, int M) { return a256((size_t)n * ((M + 63) / 64) * 4); }
 
 size_t seq_above_ws_bytes(int n, int M) {
     if (n <= 0 || M <= 0) return 0;
-    return seq_seg_bytes(n, M) + seq_a256((size_t)n * 4);
+    return seq_seg_bytes(n, M) + a256((size_t)n * 4);
 }
-
-struct RangeOut {          // where a range selection's result goes (launch_seq_above's arguments)
-    int32_t* rows;
-    int32_t* cols;
-    float* vals;
-    unsigned char* codes;
-    int64_t cap;
-    int64_t* row_ptr;
-    int rout0;
-    unsigned long long* count;
-    int accumulate;
-    void* ws;
-    int32_t* status;
-};
 
 // fills a.nseg and a.rg, then: pass(1), the row scan, the scan, and unless the capacity is 0 (count only) pass(2)
 template <class A, class Pass>
-static int run_range(A& a, const int32_t* row_self, int row0, int window, int causal, float thr, const RangeOut& o,
-                     hipStream_t s, Pass&& pass) {
+static int run_range(A& a, const Eligible& e, float thr, const RangeOut& o, hipStream_t s, Pass&& pass) {
     const int n = a.R - a.ctx;
     a.nseg = (a.M + 63) / 64;
-    a.rg.row_self = row_self;
-    a.rg.row0 = row0;
-    a.rg.window = window;
-    a.rg.causal = causal;
+    a.rg.row_self = e.row_self;
+    a.rg.row0 = e.row0;
+    a.rg.window = e.window;
+    a.rg.causal = e.causal;
     a.rg.thr = thr;
     a.rg.seg = static_cast<int32_t*>(o.ws);
     int32_t* cnt = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(o.ws) + seq_seg_bytes(n, a.M));
@@ -685,44 +662,36 @@ static int run_range(A& a, const int32_t* row_self, int row0, int window, int ca
     return pass(std::integral_constant<int, 2>{});
 }
 
-int launch_seq_above(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* row_self,
-                     int row0, int window, int causal, float thr, int32_t* orows, int32_t* ocols, float* ovals,
-                     unsigned char* odirs, int64_t cap, int64_t* row_ptr, int rout0, unsigned long long* count,
-                     int accumulate, void* ws, int32_t* status, hipStream_t s) {
-    if (R - ctx <= 0 || M <= 0) return SGPR_OK;
+int launch_seq_above(const ScoreBlock& b, const SeqSpec& seq, const Eligible& e, float thr, const RangeOut& out,
+                     hipStream_t s) {
+    if (b.R - seq.ctx <= 0 || b.M <= 0) return SGPR_OK;
     SeqAboveArgs a;
     Grid g;
-    const int rc = fill_tile(a, score, R, M, ld, ctx, L, L - 1, "sequence range selection", &g);
+    const int rc = fill_tile(a, b, seq, seq.L - 1, "sequence range selection", &g);
     if (rc != SGPR_OK) return rc;
-    a.fwd = (flags & SGPR_SEQ_FORWARD) ? 1 : 0;
-    a.rev = (flags & SGPR_SEQ_REVERSE) ? 1 : 0;
+    a.fwd = (seq.dirs & SGPR_SEQ_FORWARD) ? 1 : 0;
+    a.rev = (seq.dirs & SGPR_SEQ_REVERSE) ? 1 : 0;
     fill_rcp(a.rcp);
-    const RangeOut o = {orows, ocols, ovals, odirs, cap, row_ptr, rout0, count, accumulate, ws, status};
-    return run_range(a, row_self, row0, window, causal, thr, o, s, [&](auto P) {
+    return run_range(a, e, thr, out, s, [&](auto P) {
         return launch_tile<seq_above_kernel<decltype(P)::value>>(
             a, g, SGPR_SEQ_MAX_LEN - 1, "sequence range selection",
             decltype(P)::value == 1 ? "seq_above_kernel launch (pass 1)" : "seq_above_kernel launch (pass 2)", s);
     });
 }
 
-// arguments already checked (launch_session_filter's and launch_seq_above's, min_terms in 1..L)
-int launch_session_above(const float* score, int R, int M, int64_t ld, int ctx, int L, int flags, const int32_t* offsets,
-                         int n_paths, const int32_t* row_starts, int n_row, const int32_t* col_starts, int n_col,
-                         const int32_t* row_self, int row0, int window, int causal, int min_terms, float thr,
-                         int32_t* orows, int32_t* ocols, float* ovals, unsigned char* ocodes, int64_t cap,
-                         int64_t* row_ptr, int rout0, unsigned long long* count, int accumulate, void* ws, int32_t* status,
+// arguments already checked (launch_session_filter's and launch_seq_above's, seq.min_terms in 1..L)
+int launch_session_above(const ScoreBlock& b, const SeqSpec& seq, const Eligible& e, float thr, const RangeOut& out,
                          hipStream_t s) {
-    if (R - ctx <= 0 || M <= 0) return SGPR_OK;
+    if (b.R - seq.ctx <= 0 || b.M <= 0) return SGPR_OK;
     SessionAboveArgs a;
     Grid g;
-    fill_paths(a, offsets, n_paths, L);
-    const int rc = fill_tile(a, score, R, M, ld, ctx, L, a.H, "session range selection", &g);
+    fill_paths(a, seq);
+    const int rc = fill_tile(a, b, seq, a.H, "session range selection", &g);
     if (rc != SGPR_OK) return rc;
-    fill_sessions(a, row_starts, n_row, col_starts, n_col, R, M);
-    a.min_terms = min_terms;
-    const RangeOut o = {orows, ocols, ovals, ocodes, cap, row_ptr, rout0, count, accumulate, ws, status};
-    return run_range(a, row_self, row0, window, causal, thr, o, s, [&](auto P) {
-        return by_direction(flags, [&](auto F, auto V) {
+    fill_sessions(a, seq, b.R, b.M);
+    a.min_terms = seq.min_terms;
+    return run_range(a, e, thr, out, s, [&](auto P) {
+        return by_direction(seq.dirs, [&](auto F, auto V) {
             return launch_tile<session_above_kernel<decltype(F)::value, decltype(V)::value, decltype(P)::value>>(
                 a, g, SGPR_SEQ_PATH_MAX_OFFSET, "session range selection",
                 decltype(P)::value == 1 ? "session_above_kernel launch (pass 1)" : "session_above_kernel launch (pass 2)",
@@ -737,8 +706,7 @@ int launch_seq_dirs(const int32_t* idx, int n, int k, const unsigned char* dir, 
     if (total <= 0) return SGPR_OK;
     hipLaunchKernelGGL(seq_dirs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idx, total, k, dir, ld,
                        fixed, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, "seq_dirs_kernel launch");
+    return launched("seq_dirs_kernel launch");
 }
 
 }  // namespace sgpr

@@ -325,11 +325,6 @@ static int check_sizes(const char* what, int B, int F, int N, int K, float eps, 
     return SGPR_OK;
 }
 
-static int launched(const char* what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SGPR_OK : hip_fail(e, what);
-}
-
 static int reduce(const double2* slab, int B, int F, double M, int mode, float* o0, float* o1, hipStream_t st) {
     hipLaunchKernelGGL(reduce_kernel, dim3((F + TR_THREADS - 1) / TR_THREADS), dim3(TR_THREADS), 0, st, slab, B, F, M,
                        mode, o0, o1);
