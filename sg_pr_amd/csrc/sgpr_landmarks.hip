@@ -47,7 +47,6 @@ constexpr int LM_SCAN_THREADS = 1024;
 constexpr double LM_FIX = 16777216.0;          // 2^24
 constexpr double LM_LIMIT = 137438953472.0;    // 2^37
 constexpr double LM_D2_CAP = 1048576.0;        // 2^20
-constexpr double LM_MIN_CELL = 0.5;
 
 struct LmWs {
     double* m;                     // [P][3] map point
@@ -84,28 +83,8 @@ struct LmArgs {
     int32_t starts[SGPR_SESSION_MAX];
 };
 
-// Cell width of a label: a hair wider than its radius, and never below LM_MIN_CELL.
-//
-// Two nodes in range are never two cells apart.  Let a >= b be one coordinate of two nodes that link, w the width.
-// The rule gives fl(dx dx) <= fl(r r) up to the roundings of the products and the sum, i.e. |dx| <= r (1 + 2^-50), and
-// dx = fl(a - b), so a - b <= r (1 + 2^-49).  w >= r 1.001 (1 - 2^-52), so (a - b) / w < 1 - 9e-4.  Both quotients are
-// rounded: |a|, |b| <= 2^37 and w >= 0.5 bound them by 2^38 and each rounding error by 2^-53 2^38 = 2^-15, together
-// 6.2e-5.  So fl(a / w) - fl(b / w) < 1, and floor() of two numbers less than 1 apart differs by at most 1 (division
-// by a positive w is monotone, so the difference is not negative either).  |quotient| <= 2^38 fits a long long.
-// A width above the radius only adds candidates; the pair test is the header's, exact.  r = +inf: w = inf, every
-// quotient is +-0, one cell.
-__device__ __forceinline__ double lm_cell_width(double r) { return fmax(r * 1.001, LM_MIN_CELL); }
-__device__ __forceinline__ long long lm_cell_coord(double v, double w) { return (long long)floor(v / w); }
-
-// The key is a HASH of (label, ix, iy), not a packing: 2 x 39 bits of cell coordinate and 6 of label do not fit.  Two
-// cells with one key share a list, and one list may be met twice among the 9 neighbours; the pair test compares the
-// labels and the distance itself and uniting is idempotent, so a collision costs time and never an answer.
-__device__ __forceinline__ unsigned long long lm_cell_key(int label, long long ix, long long iy) {
-    unsigned long long k = mix64((unsigned long long)ix + 0x9e3779b97f4a7c15ull * (unsigned long long)(label + 1));
-    k = mix64(k ^ ((unsigned long long)iy * 0xd6e8feb86659fd93ull));
-    return k == TABLE_EMPTY ? 0ull : k;
-}
-
+// The cell width of a label, the cell of a coordinate and the key of a cell (lm_cell_width, lm_cell_coord, lm_cell_key)
+// are sgpr_map.hpp's, with the proof that two nodes in range are never two cells apart.
 __device__ __forceinline__ bool lm_in_limit(double v) { return isfinite(v) && fabs(v) <= LM_LIMIT; }
 
 __global__ __launch_bounds__(LM_THREADS) void lm_transform_kernel(const LmWs w, const LmArgs a) {

@@ -94,6 +94,38 @@ __device__ __forceinline__ I table_find(const unsigned long long* keys, I mask, 
     }
 }
 
+// ------------------------------------------------------------------ cells of the map frame (landmarks, landmark_align)
+// Cell width of a label: a hair wider than its radius, and never below LM_MIN_CELL.
+//
+// Two points in range are never two cells apart.  Let a >= b be one coordinate of two points that link, w the width.
+// The rule gives fl(dx dx) <= fl(r r) up to the roundings of the products and the sum, i.e. |dx| <= r (1 + 2^-50), and
+// dx = fl(a - b), so a - b <= r (1 + 2^-49).  w >= r 1.001 (1 - 2^-52), so (a - b) / w < 1 - 9e-4.  Both quotients are
+// rounded: |a|, |b| <= 2^37 and w >= 0.5 bound them by 2^38 and each rounding error by 2^-53 2^38 = 2^-15, together
+// 6.2e-5.  So fl(a / w) - fl(b / w) < 1, and floor() of two numbers less than 1 apart differs by at most 1 (division
+// by a positive w is monotone, so the difference is not negative either).  |quotient| <= 2^38 fits a long long.
+// A width above the radius only adds candidates; the pair test is the caller's, exact.  r = +inf: w = inf, every
+// quotient is +-0, one cell.  (One product, one quotient: nothing here can contract; the pragma keeps it so.)
+constexpr double LM_MIN_CELL = 0.5;
+
+__device__ __forceinline__ double lm_cell_width(double r) {
+#pragma clang fp contract(off)
+    return fmax(r * 1.001, LM_MIN_CELL);
+}
+__device__ __forceinline__ long long lm_cell_coord(double v, double w) {
+#pragma clang fp contract(off)
+    return (long long)floor(v / w);
+}
+
+// The key is a HASH of (label, ix, iy), not a packing: 2 x 39 bits of cell coordinate and 6 of label do not fit.  Two
+// cells with one key share a list, and one list may be met twice among the 9 neighbours; the pair test compares the
+// labels and the distance itself and its consequence (uniting, a minimum) is idempotent, so a collision costs time and
+// never an answer.
+__device__ __forceinline__ unsigned long long lm_cell_key(int label, long long ix, long long iy) {
+    unsigned long long k = mix64((unsigned long long)ix + 0x9e3779b97f4a7c15ull * (unsigned long long)(label + 1));
+    k = mix64(k ^ ((unsigned long long)iy * 0xd6e8feb86659fd93ull));
+    return k == TABLE_EMPTY ? 0ull : k;
+}
+
 // ------------------------------------------------------------------ the lock-free lowest-root union-find
 // parent[x] = x initially; uf_unite always hooks the LARGER root under the smaller, so a component's root is its
 // lowest index whatever the execution order.

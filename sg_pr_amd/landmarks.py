@@ -1,7 +1,8 @@
 """The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h),
-and the refinement of the poses on that map (include/sgpr_landmark_refine.h).
+the refinement of the poses on that map (include/sgpr_landmark_refine.h) and the alignment of further
+scans to it (include/sgpr_landmark_align.h).
 
-The entry points are declared in the fourth and fifth public headers; this module has engine.bind_header parse them and
+The entry points are declared in the fourth, fifth and sixth public headers; this module has engine.bind_header parse them and
 set the signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -18,6 +19,9 @@ _C = _ABI.constants
 ABI_SYMBOLS = [name for name, _, _ in _ABI.functions]
 REFINE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_refine.h")
 REFINE_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(REFINE_HEADER)).functions]
+ALIGN_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_align.h")
+ALIGN_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(ALIGN_HEADER)).functions]
+ALIGN_NONFINITE, ALIGN_KEPT = 1, 2       # flags of sgpr_landmark_align (d_stat[q][3])
 MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
 DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
 DEFAULT_MAX_LANDMARKS = 1 << 22          # the default capacity is G N, capped here; build() re-runs past it
@@ -25,10 +29,11 @@ _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L floa
 
 
 def load_library():
-    """engine.load_library() with the signatures of include/sgpr_landmarks.h and include/sgpr_landmark_refine.h set on
-    it"""
+    """engine.load_library() with the signatures of include/sgpr_landmarks.h, include/sgpr_landmark_refine.h and
+    include/sgpr_landmark_align.h set on it"""
     engine.bind_header(os.path.basename(HEADER))
     engine.bind_header(os.path.basename(REFINE_HEADER))
+    engine.bind_header(os.path.basename(ALIGN_HEADER))
     return engine.load_library()
 
 
@@ -197,6 +202,80 @@ def refine(centers, labels, poses, lm, use=None, fixed=None, iters=10, min_nodes
     used, seen, refit, kept = (int(v) for v in out["info"].tolist())
     return out["poses"], {"cost": out["cost"].cpu().numpy(), "used_nodes": used, "landmarks": seen, "refitted": refit,
                           "kept": kept}
+
+
+def align_workspace_bytes(Q, N, L):
+    return int(load_library().sgpr_landmark_align_workspace_bytes(int(Q), int(N), int(L)))
+
+
+def align_async(centers, labels, poses, lm, use=None, radius=None, tau_z=DEFAULT_TAU_Z, iters=10, min_nodes=6, workspace=None,
+                device=None):
+    """sgpr_landmark_align without reading anything back -> dict of device tensors, asynchronous on the current stream:
+    poses f64 [Q,4], node_landmark i32 [Q,N] (the landmark of a node, -2 = live without one, -1 = dead), stat i32 [Q,4] =
+    (matched, live, steps that re-fitted, flags: ALIGN_NONFINITE, ALIGN_KEPT), rms f64 [Q].  centers f32 [Q,N,3], labels
+    i32 [Q,N]: the query scans, which need not be part of the map; poses [Q,4]: their approximate planar poses in the
+    map frame; lm: the dict of build / build_async ("center", "label"); use: a mask over the landmarks (select makes
+    one; None: all of them); radius: the gate in metres, a scalar or one value per label; tau_z: the height tolerance.
+    workspace: a uint8 device tensor of at least align_workspace_bytes(Q, N, L) to reuse."""
+    lib = load_library()
+    if device is None:
+        device = engine._device_of(centers, labels, poses, lm["center"])
+    lab = engine._on(labels, device, torch.int32)
+    if lab.dim() != 2:
+        raise ValueError("landmarks.align: labels must be [Q, N]")
+    q, n = lab.shape
+    cen = engine._on(centers, device, torch.float32)
+    if cen.numel() != q * n * 3:
+        raise ValueError("landmarks.align: centers must be [Q, N, 3]")
+    x = engine._on(poses, device, torch.float64)
+    if x.numel() != q * 4:
+        raise ValueError("landmarks.align: poses must hold one planar pose (c, s, x, y) per scan")
+    lm_c = engine._on(lm["center"], device, torch.float64)
+    lm_l = engine._on(lm["label"], device, torch.int32)
+    n_lm = int(lm_l.numel())
+    if lm_c.numel() != 3 * n_lm:
+        raise ValueError("landmarks.align: the map must hold center [L,3] and label [L]")
+    mask = None
+    if use is not None:
+        mask = engine._on(torch.as_tensor(use).reshape(-1) != 0, device, torch.bool).to(torch.uint8)
+        if mask.numel() != n_lm:
+            raise ValueError("landmarks.align: use must hold one entry per landmark")
+    rad = _radius_table(radius)
+    out = {"poses": torch.empty(q, 4, dtype=torch.float64, device=device),
+           "node_landmark": torch.full((q, n), -1, dtype=torch.int32, device=device),
+           "stat": torch.zeros(q, 4, dtype=torch.int32, device=device),
+           "rms": torch.full((q,), float("nan"), dtype=torch.float64, device=device)}   # (Q N == 0: the call writes nothing)
+    need = align_workspace_bytes(q, n, n_lm)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks.align: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_align(
+            engine._ptr(cen), engine._ptr(lab), q, n, engine._ptr(x), engine._ptr(lm_c) if n_lm else None,
+            engine._ptr(lm_l) if n_lm else None, engine._ptr(mask) if n_lm else None, n_lm, rad.ctypes.data, rad.shape[0],
+            float(tau_z), int(iters), int(min_nodes), engine._ptr(out["poses"]), engine._ptr(out["node_landmark"]),
+            engine._ptr(out["stat"]), engine._ptr(out["rms"]), engine._ptr(workspace), workspace.numel(),
+            engine._stream(device)))
+    if q * n == 0:
+        out["poses"].copy_(x.reshape(q, 4))
+    return out
+
+
+def align(centers, labels, poses, lm, use=None, radius=None, tau_z=DEFAULT_TAU_Z, iters=10, min_nodes=6, workspace=None,
+          device=None):
+    """Align Q scans to the landmark map `lm` from approximate poses: `iters` rounds of "every node takes
+    the nearest landmark of its label within `radius`" and "the scan is re-fitted rigidly to its matches"; every scan on
+    its own.  Arguments as align_async; a scan with fewer than min_nodes matches keeps its pose.  One call converges
+    inside its gate only: SG.align_to_map runs a schedule of gates.
+    -> (poses f64 [Q,4] on the device, info dict of numpy arrays: matched, live, steps, flags i32 [Q], rms f64 [Q] (the
+    planar RMS distance of the matched nodes to their landmarks, NaN without one), node_landmark i32 [Q,N] (-2 = a live
+    node no landmark of the map explains, -1 = a dead node))."""
+    out = align_async(centers, labels, poses, lm, use=use, radius=radius, tau_z=tau_z, iters=iters, min_nodes=min_nodes,
+                      workspace=workspace, device=device)
+    stat = out["stat"].cpu().numpy()
+    return out["poses"], {"matched": stat[:, 0], "live": stat[:, 1], "steps": stat[:, 2], "flags": stat[:, 3],
+                          "rms": out["rms"].cpu().numpy(), "node_landmark": out["node_landmark"].cpu().numpy()}
 
 
 def virtual_scans(lm, poses, sensor_range=50.0, node_num=100, keep=None):

@@ -83,6 +83,15 @@ own landmarks (SG.refine_map, landmarks.refine): R rounds (defau
 two or more observations, T alternations (default 10) of centre means and closed-form pose fits, the first scan fixed.
 Printed are landmarks, sharpness and shared before and after and the trajectory error against the sequence's own poses
 before and after; the landmark map above is then the one on the refined poses, and --save-poses FILE gets them.
+
+With --landmarks --align [--align-radii 2,0.75] [--align-iters T] every scan is then aligned to that landmark map
+(SG.align_to_map, landmarks.align): one call of T iterations per gate of the schedule, every node to the
+nearest landmark of its label inside the gate, the scan re-fitted to its matches.  With --localize the scans that were
+given a pose start from it, every other scan - and without --localize every scan - from the pose the map was built on.
+THE MAP HERE CONTAINS THE SCAN BEING ALIGNED: the figures say how well a scan sits on a map it helped to make, not how a
+new drive would fare.  Printed are median and 95 % translation and yaw error against the sequence's own poses before and
+after, the median share of a scan's live nodes that matched and the live nodes no landmark explains;
+`<seq>_align.npz` holds poses, start [M,4], matched, live, steps, flags, rms, accept, node_landmark, radii, iters.
 """
 import argparse
 import math
@@ -411,6 +420,14 @@ def main(argv=None):
     ap.add_argument("--optimize", action="store_true",
                     help="with --consistent: relax the planar pose graph of the map over the consistent closures "
                          "(DESIGN.md §25) and print the trajectory error before and after")
+    ap.add_argument("--align", action="store_true",
+                    help="with --landmarks: align every scan to the landmark map (DESIGN.md §31) from its localised pose "
+                         "(--localize) or the pose the map was built on, and write <seq>_align.npz; the map contains the "
+                         "scan being aligned")
+    ap.add_argument("--align-radii", default="2,0.75", metavar="R,R,..",
+                    help="with --align: the gate schedule in metres, one call per gate")
+    ap.add_argument("--align-iters", type=int, default=10, metavar="T",
+                    help="with --align: association and fit rounds per gate")
     ap.add_argument("--save-poses", default=None, metavar="FILE",
                     help="with --optimize: write the optimised planar poses [M,4] (c, s, x, y) to FILE (.npy)")
     ap.add_argument("--localize", action="store_true",
@@ -472,6 +489,15 @@ def main(argv=None):
         ap.error("--refine needs --landmarks")
     if opt.refine and not (opt.refine_rounds >= 1 and opt.refine_iters >= 0):
         ap.error("--refine-rounds must be >= 1, --refine-iters >= 0")
+    if opt.align and not opt.landmarks:
+        ap.error("--align needs --landmarks")
+    if opt.align:
+        try:
+            opt.align_radii = [float(t) for t in opt.align_radii.split(",") if t.strip()]
+        except ValueError:
+            ap.error("--align-radii is a comma-separated list of metres")
+        if not (opt.align_radii and all(r > 0 for r in opt.align_radii) and opt.align_iters >= 0):
+            ap.error("--align-radii must be positive, --align-iters >= 0")
     if opt.save_poses is not None and not (opt.optimize or opt.refine):
         ap.error("--save-poses needs --optimize")
     if opt.consistent and (opt.max_trans < 0 or opt.lever_gain < 0 or not 0 <= opt.max_yaw_deg <= 180):
@@ -609,6 +635,17 @@ def main(argv=None):
                   "best verified candidate alone: %.4f, median %.3f m, 95%% %.3f m; median %.3f deg, 95%% %.3f deg"
                   % tuple(lreport["single_" + n] for n in ("localized", "median_trans_m", "p95_trans_m", "median_yaw_deg",
                                                            "p95_yaw_deg")))
+        if opt.align:
+            areport = align_lists(trainer.model, seq, mreport, located=lreport if opt.localize else None,
+                                  radii=opt.align_radii, iters=opt.align_iters, tau_z=opt.lm_tau_z)
+            np.savez(os.path.join(args.output_path, sequence + "_align.npz"), frame=np.arange(m), **areport)
+            print("sequence", sequence, "aligned to its landmark map (which contains the scans), gates %s m x %d iterations:"
+                  % (", ".join("%g" % r for r in opt.align_radii), opt.align_iters),
+                  "translation %.4f / %.4f m -> %.4f / %.4f m (median / 95%%), yaw %.4f / %.4f deg -> %.4f / %.4f deg,"
+                  % tuple(areport[a + n] for n in ("trans_m", "yaw_deg") for a in ("before_median_", "before_p95_", "median_", "p95_")),
+                  "matched share %.4f (median), unmatched live nodes %d, accepted %d of %d, started from a localised pose %d"
+                  % (areport["matched_share"], int(areport["unmatched"]), int(areport["accept"].sum()), m,
+                     int(areport["from_localize"].sum())))
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
@@ -872,6 +909,37 @@ def landmark_lists(model, seq, poses=None, sessions=None, before=False, radius=0
     if before:
         first = model.landmark_map(seq.centers, seq.labels, own, sessions=sessions, radius=radius, tau_z=tau_z)
         out.update({"before_" + k: v for k, v in metrics.map_sharpness(first).items()})
+    return out
+
+
+def align_lists(model, seq, lm, located=None, radii=(2.0, 0.75), iters=10, min_nodes=6, tau_z=0.75):
+    """Every scan of `seq` aligned to the landmark map `lm` - the dict of landmark_lists: center, label, keep and the poses
+    it was built on (SG.align_to_map).  located: the dict of localize_lists; its accepted scans start from its pose, every
+    other scan from lm's.  The map contains the scans being aligned.
+    -> dict: poses, start f64 [M,4], matched, live, steps, flags i32 [M], rms f64 [M], accept bool [M], node_landmark i32
+    [M,N], from_localize bool [M], radii, iters, min_nodes; against the sequence's own poses (metrics.localization_errors)
+    median_ / p95_ trans_m and yaw_deg with and without the prefix before_; matched_share (the median of matched / live
+    over the scans with a live node), unmatched (the live nodes without a landmark)."""
+    own = metrics.planar_odometry(seq.poses)
+    start = np.array(np.asarray(lm["poses"], dtype=np.float64).reshape(-1, 4))
+    given = np.zeros(start.shape[0], dtype=bool)
+    if located is not None:
+        given = np.asarray(located["accept"], dtype=bool).reshape(-1) & np.isfinite(located["pose"]).all(axis=1)
+        start[given] = located["pose"][given]
+    X, info = model.align_to_map(seq.centers, seq.labels, start, lm, keep=lm["keep"], radii=radii, iters=iters,
+                                 min_nodes=min_nodes, tau_z=tau_z)
+    X = X.cpu().numpy()
+    out = {"poses": X, "start": start, "from_localize": given, "radii": np.asarray(radii, dtype=np.float64),
+           "iters": np.int64(iters), "min_nodes": np.int64(min_nodes)}
+    out.update({k: info[k] for k in ("matched", "live", "steps", "flags", "rms", "accept", "node_landmark")})
+    for prefix, poses in (("before_", start), ("", X)):
+        err = metrics.localization_errors(poses, own)
+        for name in ("trans_m", "yaw_deg"):
+            out[prefix + "median_" + name] = np.float64(np.median(err[name]))
+            out[prefix + "p95_" + name] = np.float64(np.percentile(err[name], 95))
+    seen = info["live"] > 0
+    out["matched_share"] = np.float64(np.median(info["matched"][seen] / info["live"][seen]) if seen.any() else 0.0)
+    out["unmatched"] = np.int64((info["node_landmark"] == -2).sum())
     return out
 
 

@@ -394,6 +394,34 @@ class SG(torch.nn.Module):
             costs.append(info["cost"])
         return x, _landmarks.build(centers, labels, x, starts=sessions, device=dev, **landmark_kw), costs
 
+    def align_to_map(self, centers, labels, poses, lm, keep=None, radii=(2.0, 0.75), iters=10, min_nodes=6, min_matched=None,
+                     tau_z=None):
+        """Align scans to a landmark map from approximate poses (landmarks.align): one call per gate of
+        the schedule `radii` (metres, wide to narrow), each starting from the poses of the one before; in a call every
+        node takes the nearest landmark of its label inside the gate and the scan is re-fitted rigidly to its matches,
+        `iters` times, every scan on its own.  The scans need not be part of the map, and the map is not changed.
+        centers [Q,N,3], labels [Q,N]: the packed node arrays of the scans; poses: KITTI rows [Q,12] or planar [Q,4] in
+        the frame of the map - what localize returned, odometry carried from a localised scan, a stored pose; lm: the
+        dict of landmark_map; keep: a mask over its landmarks (landmarks.select; None: all); min_matched: a scan is
+        accepted with that many matches at the end (None: min_nodes); tau_z: the height tolerance (None: the default of
+        landmarks.build).
+        -> (planar poses f64 [Q,4] device tensor, info dict of numpy arrays from the last call: matched, live, steps,
+        flags, rms, node_landmark (-2 = a live node no landmark explains: an object the map does not know, -1 = dead), and
+        accept = matched >= min_matched)."""
+        from . import landmarks as _landmarks
+        dev = self.engine().device
+        x = poses if isinstance(poses, torch.Tensor) and poses.dim() == 2 and poses.shape[1] == 4 else _planar(poses)
+        x = _engine._on(x, dev, torch.float64)
+        radii = [float(r) for r in np.atleast_1d(np.asarray(radii, dtype=np.float64))]
+        if not radii:
+            raise ValueError("align_to_map: the gate schedule is empty")
+        info = None
+        for r in radii:
+            x, info = _landmarks.align(centers, labels, x, lm, use=keep, radius=r, iters=iters, min_nodes=min_nodes,
+                                       tau_z=_landmarks.DEFAULT_TAU_Z if tau_z is None else tau_z, device=dev)
+        info["accept"] = info["matched"] >= (int(min_nodes) if min_matched is None else int(min_matched))
+        return x, info
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming
