@@ -25,6 +25,10 @@
 // Everything else is handed from one kernel to the next on one stream.  No floating-point atomics, no inline assembly,
 // plain vector stores.
 //
+// The launch sequence is lm_core_launch (sgpr_landmark_core.hpp): sgpr_landmark_map runs it on every node of a map,
+// sgpr_landmark_update (sgpr_landmark_update.hip) on the nodes its map does not explain, with a masked label array, an
+// id base, a `first` base and a session shift; all three are 0 here.
+//
 // Cells are a linked list per cell; the cell-sorted layout (count, scan, scatter, a wave per cell with the cell in LDS)
 // is not built.
 #include <math.h>
@@ -33,6 +37,7 @@
 #include <string>
 
 #include "sgpr_internal.hpp"
+#include "sgpr_landmark_core.hpp"
 #include "sgpr_landmarks.h"
 #include "sgpr_map.hpp"
 
@@ -42,11 +47,7 @@ namespace sgpr {
 
 namespace {
 
-constexpr int LM_THREADS = 256;
-constexpr int LM_SCAN_THREADS = 1024;
-constexpr double LM_FIX = 16777216.0;          // 2^24
-constexpr double LM_LIMIT = 137438953472.0;    // 2^37
-constexpr double LM_D2_CAP = 1048576.0;        // 2^20
+constexpr int LM_SCAN_THREADS = 1024;         // (LM_THREADS and the fixed-point constants: sgpr_landmark_core.hpp)
 
 struct LmWs {
     double* m;                     // [P][3] map point
@@ -78,29 +79,23 @@ struct LmArgs {
     int32_t* node_landmark;
     int32_t* num;
     int P, N, n_labels, n_sessions, max_landmarks, B;
+    int id_base, first_base, session_shift;
     double tau_z;
     double radius[SGPR_LANDMARK_MAX_LABELS];
     int32_t starts[SGPR_SESSION_MAX];
 };
 
 // The cell width of a label, the cell of a coordinate and the key of a cell (lm_cell_width, lm_cell_coord, lm_cell_key)
-// are sgpr_map.hpp's, with the proof that two nodes in range are never two cells apart.
-__device__ __forceinline__ bool lm_in_limit(double v) { return isfinite(v) && fabs(v) <= LM_LIMIT; }
+// are sgpr_map.hpp's, with the proof that two nodes in range are never two cells apart; the map point and the live rule
+// (lm_map_point) are sgpr_landmark_core.hpp's.
 
 __global__ __launch_bounds__(LM_THREADS) void lm_transform_kernel(const LmWs w, const LmArgs a) {
     const int p = blockIdx.x * LM_THREADS + threadIdx.x;
     if (p >= a.P) return;
-    const int g = p / a.N;
     const int l = a.labels[p];
-    const double x = (double)a.centers[3 * (size_t)p], y = (double)a.centers[3 * (size_t)p + 1],
-                 z = (double)a.centers[3 * (size_t)p + 2];
-    const double c = a.poses[4 * (size_t)g], s = a.poses[4 * (size_t)g + 1], X = a.poses[4 * (size_t)g + 2],
-                 Y = a.poses[4 * (size_t)g + 3];
-    const double mx = (c * x - s * y) + X, my = (s * x + c * y) + Y, mz = z;
-    bool live = l >= 0 && l < a.n_labels;
-    const double r = live ? a.radius[l] : 0.0;
-    live = live && r > 0.0 && isfinite(c) && isfinite(s) && isfinite(X) && isfinite(Y) && lm_in_limit(mx) &&
-           lm_in_limit(my) && lm_in_limit(mz);
+    double m[3];
+    const bool live = lm_map_point(a.centers, a.poses, a.radius, a.n_labels, p, p / a.N, l, m);
+    const double mx = m[0], my = m[1], mz = m[2];
     w.m[3 * (size_t)p] = mx;
     w.m[3 * (size_t)p + 1] = my;
     w.m[3 * (size_t)p + 2] = mz;
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_transform_kernel(const LmWs w, 
         a.node_landmark[p] = -1;
         return;
     }
-    const double cw = lm_cell_width(r);
+    const double cw = lm_cell_width(a.radius[l]);
     const unsigned long long slot = table_insert(w.cell_key, w.hmask, lm_cell_key(l, lm_cell_coord(mx, cw), lm_cell_coord(my, cw)));
     w.next[p] = atomicExch(&w.cell_head[slot], p);
 }
@@ -171,7 +166,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_flatten_kernel(const LmWs w, co
         for (int k = 0; k < 3; ++k)
             atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)root + k]),
                       (unsigned long long)llrint(w.m[3 * (size_t)p + k] * LM_FIX));
-        atomicOr(&w.sess[root], 1ull << sess);
+        atomicOr(&w.sess[root], 1ull << (a.session_shift + sess));
     }
     const int roots = lm_block_sum(live && root == p ? 1 : 0, wsum);
     const int lives = lm_block_sum(live ? 1 : 0, wsum);
@@ -209,7 +204,7 @@ __global__ __launch_bounds__(LM_SCAN_THREADS) void lm_scan_kernel(const LmWs w, 
         run += c;
     }
     if (t == LM_SCAN_THREADS - 1) {
-        a.num[0] = part[t];
+        a.num[0] = a.id_base + part[t];
         a.num[1] = live_part[t];
     }
 }
@@ -227,7 +222,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_record_kernel(const LmWs w, con
     if (lane == 0) wcount[wave] = __popcll(ball);
     __syncthreads();
     if (!root) return;
-    int id = w.blk_roots[blockIdx.x] + __popcll(ball & ((1ull << lane) - 1ull));
+    int id = a.id_base + w.blk_roots[blockIdx.x] + __popcll(ball & ((1ull << lane) - 1ull));
     for (int v = 0; v < wave; ++v) id += wcount[v];
     w.id[p] = id;
     if (id >= a.max_landmarks) return;
@@ -236,7 +231,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_record_kernel(const LmWs w, con
     for (int k = 0; k < 3; ++k) a.lm_center[3 * (size_t)id + k] = lm_center(w, p, k, cnt);
     a.lm_label[id] = w.lab[p];
     a.lm_count[id] = n;
-    a.lm_first[id] = p;
+    a.lm_first[id] = a.first_base + p;
     a.lm_sessions[id] = w.sess[p];
 }
 
@@ -259,13 +254,79 @@ __global__ __launch_bounds__(LM_THREADS) void lm_finish_kernel(const LmWs w, con
     a.lm_spread[id] = sqrt((double)w.q[p] / ((double)w.cnt[p] * LM_FIX));
 }
 
-size_t lm_ws_bytes(size_t P) {
+bool lm_size_ok(int G, int N) { return G >= 0 && N >= 0 && (long long)G * (long long)N <= 0x7fffffffll; }
+
+}  // namespace
+
+size_t lm_core_workspace_bytes(size_t P) {
     const size_t h = table_slots(P), b = (P + LM_THREADS - 1) / LM_THREADS;
     return align256(P * 24) * 2 + align256(P * 4) * 5 + align256(P * 8) * 2 + align256(h * 8) + align256(h * 4) +
            align256(b * 4) * 2;
 }
 
-bool lm_size_ok(int G, int N) { return G >= 0 && N >= 0 && (long long)G * (long long)N <= 0x7fffffffll; }
+int lm_core_launch(const char* fn, const LmCoreJob& job, void* d_workspace, hipStream_t s) {
+    const size_t P = (size_t)job.G * (size_t)job.N;
+    Carver ws{static_cast<unsigned char*>(d_workspace)};
+    LmWs w;
+    const size_t H = table_slots(P);
+    const int B = (int)((P + LM_THREADS - 1) / LM_THREADS);
+    w.hmask = H - 1;
+    w.m = ws.take<double>(3 * P);
+    w.sum = ws.take<long long>(3 * P);
+    w.lab = ws.take<int>(P);
+    w.parent = ws.take<int>(P);
+    w.next = ws.take<int>(P);
+    w.cnt = ws.take<int>(P);
+    w.id = ws.take<int>(P);
+    w.q = ws.take<unsigned long long>(P);
+    w.sess = ws.take<unsigned long long>(P);
+    w.cell_key = ws.take<unsigned long long>(H);
+    w.cell_head = ws.take<int>(H);
+    w.blk_roots = ws.take<int>(B);
+    w.blk_live = ws.take<int>(B);
+
+    LmArgs a = {};
+    a.centers = job.centers;
+    a.labels = job.labels;
+    a.poses = job.poses;
+    a.lm_center = job.lm_center;
+    a.lm_label = job.lm_label;
+    a.lm_count = job.lm_count;
+    a.lm_first = job.lm_first;
+    a.lm_sessions = reinterpret_cast<unsigned long long*>(job.lm_sessions);
+    a.lm_spread = job.lm_spread;
+    a.node_landmark = job.node_landmark;
+    a.num = job.num;
+    a.P = (int)P;
+    a.N = job.N;
+    a.n_labels = job.n_labels;
+    a.max_landmarks = job.max_landmarks;
+    a.B = B;
+    a.id_base = job.id_base;
+    a.first_base = job.first_base;
+    a.session_shift = job.session_shift;
+    a.tau_z = job.tau_z;
+    for (int l = 0; l < job.n_labels; ++l) a.radius[l] = job.h_radius[l];
+    fill_session_table(a.starts, &a.n_sessions, job.h_starts, job.n_sessions);
+
+    const std::string what = fn;
+    // cell_key | cell_head: empty keys, list ends (-1)
+    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, align256(H * 8) + align256(H * 4), s);
+    if (e != hipSuccess) return hip_fail(e, (what + ": memset").c_str());
+    const dim3 grid(B), block(LM_THREADS);
+    hipLaunchKernelGGL(lm_transform_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_union_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_flatten_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_scan_kernel, dim3(1), dim3(LM_SCAN_THREADS), 0, s, w, a);
+    hipLaunchKernelGGL(lm_record_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_spread_kernel, grid, block, 0, s, w, a);
+    hipLaunchKernelGGL(lm_finish_kernel, grid, block, 0, s, w, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, (what + ": launch").c_str());
+    return SGPR_OK;
+}
+
+namespace {
 
 }  // namespace
 }  // namespace sgpr
@@ -276,7 +337,7 @@ extern "C" {
 
 size_t sgpr_landmark_workspace_bytes(int G, int N) {
     if (!lm_size_ok(G, N) || G == 0 || N == 0) return 0;
-    return lm_ws_bytes((size_t)G * (size_t)N);
+    return lm_core_workspace_bytes((size_t)G * (size_t)N);
 }
 
 int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, int N, const double* d_poses,
@@ -320,67 +381,33 @@ int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, in
         return SGPR_E_INVALID;
     }
     const size_t P = (size_t)G * (size_t)N;
-    const size_t need = lm_ws_bytes(P);
+    const size_t need = lm_core_workspace_bytes(P);
     if (workspace_bytes < need) {
         set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
         return SGPR_E_INVALID;
     }
 
-    Carver ws{static_cast<unsigned char*>(d_workspace)};
-    LmWs w;
-    const size_t H = table_slots(P);
-    const int B = (int)((P + LM_THREADS - 1) / LM_THREADS);
-    w.hmask = H - 1;
-    w.m = ws.take<double>(3 * P);
-    w.sum = ws.take<long long>(3 * P);
-    w.lab = ws.take<int>(P);
-    w.parent = ws.take<int>(P);
-    w.next = ws.take<int>(P);
-    w.cnt = ws.take<int>(P);
-    w.id = ws.take<int>(P);
-    w.q = ws.take<unsigned long long>(P);
-    w.sess = ws.take<unsigned long long>(P);
-    w.cell_key = ws.take<unsigned long long>(H);
-    w.cell_head = ws.take<int>(H);
-    w.blk_roots = ws.take<int>(B);
-    w.blk_live = ws.take<int>(B);
-
-    LmArgs a = {};
-    a.centers = d_centers;
-    a.labels = d_labels;
-    a.poses = d_poses;
-    a.lm_center = d_lm_center;
-    a.lm_label = d_lm_label;
-    a.lm_count = d_lm_count;
-    a.lm_first = d_lm_first;
-    a.lm_sessions = reinterpret_cast<unsigned long long*>(d_lm_sessions);
-    a.lm_spread = d_lm_spread;
-    a.node_landmark = d_node_landmark;
-    a.num = d_num;
-    a.P = (int)P;
-    a.N = N;
-    a.n_labels = n_labels;
-    a.max_landmarks = max_landmarks;
-    a.B = B;
-    a.tau_z = tau_z;
-    for (int l = 0; l < n_labels; ++l) a.radius[l] = h_radius[l];
-    fill_session_table(a.starts, &a.n_sessions, h_starts, n_sessions);
-
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    // cell_key | cell_head: empty keys, list ends (-1)
-    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, align256(H * 8) + align256(H * 4), s);
-    if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_map: memset");
-    const dim3 grid(B), block(LM_THREADS);
-    hipLaunchKernelGGL(lm_transform_kernel, grid, block, 0, s, w, a);
-    hipLaunchKernelGGL(lm_union_kernel, grid, block, 0, s, w, a);
-    hipLaunchKernelGGL(lm_flatten_kernel, grid, block, 0, s, w, a);
-    hipLaunchKernelGGL(lm_scan_kernel, dim3(1), dim3(LM_SCAN_THREADS), 0, s, w, a);
-    hipLaunchKernelGGL(lm_record_kernel, grid, block, 0, s, w, a);
-    hipLaunchKernelGGL(lm_spread_kernel, grid, block, 0, s, w, a);
-    hipLaunchKernelGGL(lm_finish_kernel, grid, block, 0, s, w, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_map: launch");
-    return SGPR_OK;
+    LmCoreJob job = {};
+    job.centers = d_centers;
+    job.labels = d_labels;
+    job.poses = d_poses;
+    job.G = G;
+    job.N = N;
+    job.h_starts = h_starts;
+    job.n_sessions = n_sessions;
+    job.h_radius = h_radius;
+    job.n_labels = n_labels;
+    job.tau_z = tau_z;
+    job.max_landmarks = max_landmarks;
+    job.lm_center = d_lm_center;
+    job.lm_label = d_lm_label;
+    job.lm_count = d_lm_count;
+    job.lm_first = d_lm_first;
+    job.lm_sessions = d_lm_sessions;
+    job.lm_spread = d_lm_spread;
+    job.node_landmark = d_node_landmark;
+    job.num = d_num;
+    return lm_core_launch("sgpr_landmark_map", job, d_workspace, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 """The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h),
-the refinement of the poses on that map (include/sgpr_landmark_refine.h) and the alignment of further
-scans to it (include/sgpr_landmark_align.h).
+the refinement of the poses on that map (include/sgpr_landmark_refine.h), the alignment of further
+scans to it (include/sgpr_landmark_align.h) and the folding of aligned scans into it
+(include/sgpr_landmark_update.h).
 
-The entry points are declared in the fourth, fifth and sixth public headers; this module has engine.bind_header parse them and
+The entry points are declared in the fourth to seventh public headers; this module has engine.bind_header parse them and
 set the signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -21,6 +22,8 @@ REFINE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_refine.h")
 REFINE_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(REFINE_HEADER)).functions]
 ALIGN_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_align.h")
 ALIGN_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(ALIGN_HEADER)).functions]
+UPDATE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_update.h")
+UPDATE_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(UPDATE_HEADER)).functions]
 ALIGN_NONFINITE, ALIGN_KEPT = 1, 2       # flags of sgpr_landmark_align (d_stat[q][3])
 MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
 DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
@@ -29,11 +32,12 @@ _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L floa
 
 
 def load_library():
-    """engine.load_library() with the signatures of include/sgpr_landmarks.h, include/sgpr_landmark_refine.h and
-    include/sgpr_landmark_align.h set on it"""
+    """engine.load_library() with the signatures of include/sgpr_landmarks.h, include/sgpr_landmark_refine.h,
+    include/sgpr_landmark_align.h and include/sgpr_landmark_update.h set on it"""
     engine.bind_header(os.path.basename(HEADER))
     engine.bind_header(os.path.basename(REFINE_HEADER))
     engine.bind_header(os.path.basename(ALIGN_HEADER))
+    engine.bind_header(os.path.basename(UPDATE_HEADER))
     return engine.load_library()
 
 
@@ -276,6 +280,93 @@ def align(centers, labels, poses, lm, use=None, radius=None, tau_z=DEFAULT_TAU_Z
     stat = out["stat"].cpu().numpy()
     return out["poses"], {"matched": stat[:, 0], "live": stat[:, 1], "steps": stat[:, 2], "flags": stat[:, 3],
                           "rms": out["rms"].cpu().numpy(), "node_landmark": out["node_landmark"].cpu().numpy()}
+
+
+def update_workspace_bytes(Q, N, L):
+    return int(load_library().sgpr_landmark_update_workspace_bytes(int(Q), int(N), int(L)))
+
+
+_RECORD = (("center", torch.float64), ("label", torch.int32), ("count", torch.int32), ("first", torch.int32),
+           ("sessions", torch.int64), ("spread", torch.float64))
+
+
+def update_async(centers, labels, poses, assoc, lm, starts=None, session_base=0, node_base=0, radius=None, tau_z=DEFAULT_TAU_Z,
+                 max_landmarks=None, workspace=None, device=None):
+    """sgpr_landmark_update without reading anything back -> dict of device tensors, asynchronous on the current stream:
+    the six record arrays of the updated map with max_landmarks rows (center f64 [.,3], label, count, first i32, sessions
+    i64, spread f64), node_landmark i32 [Q,N] (the id in the updated map, -1 = dead or rejected), num i32 [4] = (landmarks
+    of the updated map, live nodes, observations, new nodes).  Only the first min(num[0], max_landmarks) records are
+    written.  centers f32 [Q,N,3], labels i32 [Q,N], poses [Q,4]: the new scans at their ALIGNED poses; assoc i32 [Q,N]:
+    node_landmark of align / align_async against the whole map; lm: the dict of build / update (its six records; the
+    inputs are left as they are); starts: the session table of the Q scans; session_base: the number of the first of
+    their sessions in the map; node_base: the flat index the map gives their first node (`first` of a new landmark);
+    radius, tau_z: the link rule among the new nodes; max_landmarks: default L + Q N, capped at DEFAULT_MAX_LANDMARKS."""
+    lib = load_library()
+    if device is None:
+        device = engine._device_of(centers, labels, poses, lm["center"])
+    lab = engine._on(labels, device, torch.int32)
+    if lab.dim() != 2:
+        raise ValueError("landmarks.update: labels must be [Q, N]")
+    q, n = lab.shape
+    cen = engine._on(centers, device, torch.float32)
+    if cen.numel() != q * n * 3:
+        raise ValueError("landmarks.update: centers must be [Q, N, 3]")
+    x = engine._on(poses, device, torch.float64)
+    if x.numel() != q * 4:
+        raise ValueError("landmarks.update: poses must hold one planar pose (c, s, x, y) per scan")
+    asc = engine._on(assoc, device, torch.int32)
+    if asc.numel() != q * n:
+        raise ValueError("landmarks.update: assoc must be [Q, N]")
+    old = {k: engine._on(lm[k].view(np.int64) if isinstance(lm[k], np.ndarray) and lm[k].dtype == np.uint64 else lm[k], device, t)
+           for k, t in _RECORD}                                     # (a uint64 host mask: its bits)
+    n_lm = int(old["label"].numel())
+    if old["center"].numel() != 3 * n_lm or any(old[k].numel() != n_lm for k, _ in _RECORD[1:]):
+        raise ValueError("landmarks.update: the map must hold center [L,3] and label, count, first, sessions, spread [L]")
+    table = engine._session_table(starts)
+    rad = _radius_table(radius)
+    cap = max(n_lm, min(n_lm + q * n, DEFAULT_MAX_LANDMARKS)) if max_landmarks is None else int(max_landmarks)
+    rows = max(cap, 0)
+    out = {k: torch.empty((rows, 3) if k == "center" else (rows,), dtype=t, device=device) for k, t in _RECORD}
+    out["node_landmark"] = torch.full((q, n), -1, dtype=torch.int32, device=device)
+    out["num"] = torch.tensor([n_lm, 0, 0, 0], dtype=torch.int32, device=device)
+    if q * n == 0 and rows >= n_lm:                                  # the call writes nothing: the map is what it was
+        for k, _ in _RECORD:
+            out[k][:n_lm] = old[k].reshape(out[k][:n_lm].shape)
+    need = update_workspace_bytes(q, n, n_lm)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks.update: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_update(
+            engine._ptr(cen), engine._ptr(lab), q, n, engine._ptr(x), engine._ptr(asc), *engine._table_args(table),
+            int(session_base), int(node_base), rad.ctypes.data, rad.shape[0], float(tau_z),
+            *[engine._ptr(old[k]) if n_lm else None for k, _ in _RECORD], n_lm, cap,
+            *[engine._ptr(out[k]) if rows else None for k, _ in _RECORD], engine._ptr(out["node_landmark"]),
+            engine._ptr(out["num"]), engine._ptr(workspace), workspace.numel(), engine._stream(device)))
+    return out
+
+
+def update(centers, labels, poses, assoc, lm, starts=None, session_base=0, node_base=0, radius=None, tau_z=DEFAULT_TAU_Z,
+           max_landmarks=None, workspace=None, device=None):
+    """Fold Q aligned scans into the landmark map `lm`: a node that `assoc` puts on a landmark of its
+    label becomes one more observation of it (count, centre, sessions and spread move as if it had been a member), the
+    nodes with assoc -2 are fused among themselves into new landmarks behind the old ones; old landmarks keep their ids
+    and never merge.  Arguments as update_async.
+    -> the dict of build - center, label, count, first, sessions, spread trimmed to the landmarks of the updated map,
+    node_landmark i32 [Q,N] of the NEW scans, num_landmarks, live_nodes - plus observed and new_nodes; select, align,
+    virtual_scans and the next update take it as they take build's, refine takes it together with the new scans (its
+    node_landmark is theirs).  If max_landmarks was too small the call is repeated once with the reported count."""
+    kw = dict(starts=starts, session_base=session_base, node_base=node_base, radius=radius, tau_z=tau_z, workspace=workspace,
+              device=device)
+    out = update_async(centers, labels, poses, assoc, lm, max_landmarks=max_landmarks, **kw)
+    found, live, seen, new = (int(v) for v in out["num"].tolist())
+    if found > out["label"].shape[0]:
+        out = update_async(centers, labels, poses, assoc, lm, max_landmarks=found, **kw)
+    res = {k: out[k][:found] for k, _ in _RECORD}
+    res["node_landmark"] = out["node_landmark"]
+    res["num_landmarks"], res["live_nodes"], res["observed"], res["new_nodes"] = found, live, seen, new
+    return res
 
 
 def virtual_scans(lm, poses, sensor_range=50.0, node_num=100, keep=None):

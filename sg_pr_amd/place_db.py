@@ -92,6 +92,16 @@ THE MAP HERE CONTAINS THE SCAN BEING ALIGNED: the figures say how well a scan si
 new drive would fare.  Printed are median and 95 % translation and yaw error against the sequence's own poses before and
 after, the median share of a scan's live nodes that matched and the live nodes no landmark explains;
 `<seq>_align.npz` holds poses, start [M,4], matched, live, steps, flags, rms, accept, node_landmark, radii, iters.
+
+With --landmarks --sessions N --update the last of the N sessions is taken as a NEW DRIVE: a landmark map is built on
+the other sessions (the sequence's own poses), the scans of the last are aligned to it with --align-radii and
+--align-iters (all landmarks take part) and folded into it (SG.update_map, landmarks.update): matched
+nodes become further observations of their landmarks, the others new landmarks behind the old ones.  Printed are the
+landmarks before and after, the new landmarks, the observed and the new nodes, and the share of the updated landmarks
+whose count is that of the landmark holding their first node in the map built on every session at once on the same poses;
+`<seq>_update.npz` holds the records of the updated map, node_landmark of the new scans, num = (landmarks, live,
+observed, new nodes), landmarks_before, batch_landmarks, same_count, poses, start, first_scan, session, node_base,
+radii, iters.
 """
 import argparse
 import math
@@ -425,9 +435,12 @@ def main(argv=None):
                          "(--localize) or the pose the map was built on, and write <seq>_align.npz; the map contains the "
                          "scan being aligned")
     ap.add_argument("--align-radii", default="2,0.75", metavar="R,R,..",
-                    help="with --align: the gate schedule in metres, one call per gate")
+                    help="with --align or --update: the gate schedule in metres, one call per gate")
     ap.add_argument("--align-iters", type=int, default=10, metavar="T",
-                    help="with --align: association and fit rounds per gate")
+                    help="with --align or --update: association and fit rounds per gate")
+    ap.add_argument("--update", action="store_true",
+                    help="with --landmarks --sessions N: build the landmark map on every session but the last, align the "
+                         "last session to it and fold it in (DESIGN.md §32); writes <seq>_update.npz")
     ap.add_argument("--save-poses", default=None, metavar="FILE",
                     help="with --optimize: write the optimised planar poses [M,4] (c, s, x, y) to FILE (.npy)")
     ap.add_argument("--localize", action="store_true",
@@ -491,7 +504,9 @@ def main(argv=None):
         ap.error("--refine-rounds must be >= 1, --refine-iters >= 0")
     if opt.align and not opt.landmarks:
         ap.error("--align needs --landmarks")
-    if opt.align:
+    if opt.update and not (opt.landmarks and opt.sessions is not None):
+        ap.error("--update needs --landmarks and --sessions N")
+    if opt.align or opt.update:
         try:
             opt.align_radii = [float(t) for t in opt.align_radii.split(",") if t.strip()]
         except ValueError:
@@ -646,6 +661,16 @@ def main(argv=None):
                   "matched share %.4f (median), unmatched live nodes %d, accepted %d of %d, started from a localised pose %d"
                   % (areport["matched_share"], int(areport["unmatched"]), int(areport["accept"].sum()), m,
                      int(areport["from_localize"].sum())))
+        if opt.update:
+            ureport = update_lists(trainer.model, seq, opt.sessions, radii=opt.align_radii, iters=opt.align_iters,
+                                   radius=opt.lm_radius, tau_z=opt.lm_tau_z)
+            np.savez(os.path.join(args.output_path, sequence + "_update.npz"), **ureport)
+            print("sequence", sequence, "session %d of %d folded into the landmark map of the others, gates %s m x %d iterations:"
+                  % (int(ureport["session"]), opt.sessions, ", ".join("%g" % r for r in opt.align_radii), opt.align_iters),
+                  "landmarks %d -> %d (%d new), observed nodes %d, new nodes %d,"
+                  % (int(ureport["landmarks_before"]), int(ureport["num"][0]), int(ureport["num"][0] - ureport["landmarks_before"]),
+                     int(ureport["num"][2]), int(ureport["num"][3])),
+                  "count as in the batch map of %d landmarks: %.4f" % (int(ureport["batch_landmarks"]), ureport["same_count"]))
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
@@ -940,6 +965,37 @@ def align_lists(model, seq, lm, located=None, radii=(2.0, 0.75), iters=10, min_n
     seen = info["live"] > 0
     out["matched_share"] = np.float64(np.median(info["matched"][seen] / info["live"][seen]) if seen.any() else 0.0)
     out["unmatched"] = np.int64((info["node_landmark"] == -2).sum())
+    return out
+
+
+def update_lists(model, seq, sessions, radii=(2.0, 0.75), iters=10, min_nodes=6, radius=0.75, tau_z=0.75):
+    """The last of `sessions` consecutive near-equal sessions of `seq` (session_lists' split) folded into the landmark map
+    of the others: the map is built on the sequence's own poses (SG.landmark_map), the scans of the last session are
+    aligned to all of its landmarks from their own poses (SG.align_to_map) and folded in (SG.update_map).  The yardstick
+    is the batch map of every session on the same poses.
+    -> dict of numpy arrays: center, label, count, first, sessions, spread of the updated map, node_landmark [Q,N] of the
+    new scans, num = (landmarks, live, observed, new nodes), landmarks_before, batch_landmarks, same_count (the share of
+    the updated landmarks whose count equals that of the batch landmark holding their first node), poses, start [Q,4],
+    first_scan, session, node_base, radii, iters."""
+    m, n = seq.labels.shape[0], seq.labels.shape[1]
+    bounds = np.asarray([(j * m) // int(sessions) for j in range(int(sessions))], dtype=np.int32)
+    b, last = int(bounds[-1]), int(sessions) - 1
+    own = metrics.planar_odometry(seq.poses)
+    lm = model.landmark_map(seq.centers[:b], seq.labels[:b], own[:b], sessions=bounds[:-1], radius=radius, tau_z=tau_z)
+    X, _ = model.align_to_map(seq.centers[b:], seq.labels[b:], own[b:], lm, radii=radii, iters=iters, min_nodes=min_nodes,
+                              tau_z=tau_z)
+    up = model.update_map(seq.centers[b:], seq.labels[b:], X, lm, last, node_base=b * n, radius=radius, tau_z=tau_z)
+    X = X.cpu().numpy()
+    batch = model.landmark_map(seq.centers, seq.labels, np.concatenate((own[:b], X)), sessions=bounds, radius=radius,
+                               tau_z=tau_z)
+    out = {name: up[name].cpu().numpy() for name in ("center", "label", "count", "first", "sessions", "spread", "node_landmark")}
+    holder = batch["node_landmark"].cpu().numpy().reshape(-1)[out["first"]]
+    same = batch["count"].cpu().numpy()[holder] == out["count"]
+    out.update({"num": np.asarray([up["num_landmarks"], up["live_nodes"], up["observed"], up["new_nodes"]], dtype=np.int64),
+                "landmarks_before": np.int64(lm["num_landmarks"]), "batch_landmarks": np.int64(batch["num_landmarks"]),
+                "same_count": np.float64(same.mean() if same.size else 1.0), "poses": X, "start": own[b:],
+                "first_scan": np.int64(b), "session": np.int64(last), "node_base": np.int64(b * n),
+                "radii": np.asarray(radii, dtype=np.float64), "iters": np.int64(iters)})
     return out
 
 

@@ -422,6 +422,32 @@ class SG(torch.nn.Module):
         info["accept"] = info["matched"] >= (int(min_nodes) if min_matched is None else int(min_matched))
         return x, info
 
+    def update_map(self, centers, labels, poses, lm, session, node_base=None, radius=0.75, tau_z=None):
+        """Fold the scans of a further drive into a landmark map (landmarks.update).  Every node is
+        associated with the nearest landmark of its label within `radius` of the WHOLE map - one landmarks.align call
+        with iters=0 and no keep mask, because a landmark seen once must be able to grow - and becomes one more
+        observation of it; the live nodes without a landmark are fused among themselves (same radius, tau_z) into new
+        landmarks behind the old ones.  Old landmarks keep their ids and never merge.
+        ALIGN FIRST (align_to_map) and pass the poses it returned: from poses 0.3 m off, only 0.6 of the nodes of
+        permanent objects fall within 0.75 m of their landmark, and the rest enter the map as duplicates beside it.
+        centers [Q,N,3], labels [Q,N]; poses: KITTI rows [Q,12] or planar [Q,4] in the frame of the map; lm: the dict
+        of landmark_map or of an earlier update_map; session: the number of the drive in the map (its bit in
+        `sessions`; the scans are one session); node_base: the flat index the map gives the drive's first node (`first`
+        of a new landmark; None: the largest `first` of the map + 1, rounded up to a multiple of N).
+        -> the dict of landmarks.update: the records of the updated map, node_landmark [Q,N] of these scans,
+        num_landmarks, live_nodes, observed, new_nodes."""
+        from . import landmarks as _landmarks
+        dev = self.engine().device
+        x = poses if isinstance(poses, torch.Tensor) and poses.dim() == 2 and poses.shape[1] == 4 else _planar(poses)
+        x = _engine._on(x, dev, torch.float64)
+        tz = _landmarks.DEFAULT_TAU_Z if tau_z is None else tau_z
+        assoc = _landmarks.align_async(centers, labels, x, lm, radius=radius, tau_z=tz, iters=0, device=dev)["node_landmark"]
+        if node_base is None:
+            first, n = torch.as_tensor(lm["first"]), int(assoc.shape[1])
+            node_base = 0 if first.numel() == 0 or n == 0 else (int(first.max()) + n) // n * n
+        return _landmarks.update(centers, labels, x, assoc, lm, session_base=int(session), node_base=int(node_base),
+                                 radius=radius, tau_z=tz, device=dev)
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming
