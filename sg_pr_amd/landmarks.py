@@ -1,9 +1,10 @@
 """The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h),
 the refinement of the poses on that map (include/sgpr_landmark_refine.h), the alignment of further
-scans to it (include/sgpr_landmark_align.h) and the folding of aligned scans into it
-(include/sgpr_landmark_update.h).
+scans to it (include/sgpr_landmark_align.h), the folding of aligned scans into it
+(include/sgpr_landmark_update.h) and the tallies of what a drive should have seen of it and did see
+(include/sgpr_landmark_persist.h).
 
-The entry points are declared in the fourth to seventh public headers; this module has engine.bind_header parse them and
+The entry points are declared in the fourth to eighth public headers; this module has engine.bind_header parse them and
 set the signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -24,6 +25,8 @@ ALIGN_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_align.h")
 ALIGN_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(ALIGN_HEADER)).functions]
 UPDATE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_update.h")
 UPDATE_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(UPDATE_HEADER)).functions]
+PERSIST_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_persist.h")
+PERSIST_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(PERSIST_HEADER)).functions]
 ALIGN_NONFINITE, ALIGN_KEPT = 1, 2       # flags of sgpr_landmark_align (d_stat[q][3])
 MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
 DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
@@ -33,11 +36,12 @@ _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L floa
 
 def load_library():
     """engine.load_library() with the signatures of include/sgpr_landmarks.h, include/sgpr_landmark_refine.h,
-    include/sgpr_landmark_align.h and include/sgpr_landmark_update.h set on it"""
+    include/sgpr_landmark_align.h, include/sgpr_landmark_update.h and include/sgpr_landmark_persist.h set on it"""
     engine.bind_header(os.path.basename(HEADER))
     engine.bind_header(os.path.basename(REFINE_HEADER))
     engine.bind_header(os.path.basename(ALIGN_HEADER))
     engine.bind_header(os.path.basename(UPDATE_HEADER))
+    engine.bind_header(os.path.basename(PERSIST_HEADER))
     return engine.load_library()
 
 
@@ -132,10 +136,17 @@ def _popcount64(words):
     return n
 
 
-def select(lm, min_count=1, min_sessions=1):
-    """mask bool [L] of the landmarks with at least min_count observations, seen by at least min_sessions sessions"""
+def select(lm, min_count=1, min_sessions=1, keep=None):
+    """mask bool [L] of the landmarks with at least min_count observations, seen by at least min_sessions sessions; keep:
+    a further mask over the landmarks that is ANDed in, e.g. persist's (None: none)"""
     count = torch.as_tensor(lm["count"])
-    return (count >= int(min_count)) & (_popcount64(lm["sessions"]).to(count.device) >= int(min_sessions))
+    mask = (count >= int(min_count)) & (_popcount64(lm["sessions"]).to(count.device) >= int(min_sessions))
+    if keep is not None:
+        more = torch.as_tensor(keep).to(count.device).reshape(-1) != 0
+        if more.numel() != mask.numel():
+            raise ValueError("landmarks.select: keep must hold one entry per landmark")
+        mask = mask & more
+    return mask
 
 
 def refine_workspace_bytes(G, N, L):
@@ -367,6 +378,99 @@ def update(centers, labels, poses, assoc, lm, starts=None, session_base=0, node_
     res["node_landmark"] = out["node_landmark"]
     res["num_landmarks"], res["live_nodes"], res["observed"], res["new_nodes"] = found, live, seen, new
     return res
+
+
+def persist_workspace_bytes(Q, N, L):
+    return int(load_library().sgpr_landmark_persist_workspace_bytes(int(Q), int(N), int(L)))
+
+
+def persist_async(centers, labels, poses, assoc, lm, use=None, radius=None, max_range=50.0, margin=2.0, min_expected=5,
+                  max_seen_ratio=0.3, workspace=None, device=None):
+    """sgpr_landmark_persist without reading anything back -> dict of device tensors, asynchronous on the current stream:
+    expected, seen i32 [L] (the scans that should have seen the landmark / that did), keep u8 [L] (0 = retired),
+    scan_stat i32 [Q,4] = (landmarks the scan should have seen, landmarks it saw, live nodes, flags: ALIGN_NONFINITE),
+    view f64 [Q] (the view range of the scan, metres), num i32 [4] = (retired, eligible landmarks with expected >=
+    min_expected, eligible landmarks, scans with a view).  centers f32 [Q,N,3], labels i32 [Q,N], poses [Q,4]: the scans
+    of ONE drive at their aligned poses; assoc i32 [Q,N]: node_landmark of align (iters=0, every landmark) or of update; lm:
+    the dict of build / update ("center", "label"); use: a mask over the landmarks that take part (None: all); radius:
+    the table that says which labels take part (a label of radius 0 does not); max_range: the sensor range, margin: what
+    is taken off a scan's range, both metres; a landmark is retired with expected >= min_expected and seen <
+    max_seen_ratio * expected.  workspace: a uint8 device tensor of at least persist_workspace_bytes(Q, N, L) to reuse."""
+    lib = load_library()
+    if device is None:
+        device = engine._device_of(centers, labels, poses, lm["center"])
+    lab = engine._on(labels, device, torch.int32)
+    if lab.dim() != 2:
+        raise ValueError("landmarks.persist: labels must be [Q, N]")
+    q, n = lab.shape
+    cen = engine._on(centers, device, torch.float32)
+    if cen.numel() != q * n * 3:
+        raise ValueError("landmarks.persist: centers must be [Q, N, 3]")
+    x = engine._on(poses, device, torch.float64)
+    if x.numel() != q * 4:
+        raise ValueError("landmarks.persist: poses must hold one planar pose (c, s, x, y) per scan")
+    asc = engine._on(assoc, device, torch.int32)
+    if asc.numel() != q * n:
+        raise ValueError("landmarks.persist: assoc must be [Q, N]")
+    lm_c = engine._on(lm["center"], device, torch.float64)
+    lm_l = engine._on(lm["label"], device, torch.int32)
+    n_lm = int(lm_l.numel())
+    if lm_c.numel() != 3 * n_lm:
+        raise ValueError("landmarks.persist: the map must hold center [L,3] and label [L]")
+    mask = None
+    if use is not None:
+        mask = engine._on(torch.as_tensor(use).reshape(-1) != 0, device, torch.bool).to(torch.uint8)
+        if mask.numel() != n_lm:
+            raise ValueError("landmarks.persist: use must hold one entry per landmark")
+    rad = _radius_table(radius)
+    out = {"expected": torch.zeros(n_lm, dtype=torch.int32, device=device),
+           "seen": torch.zeros(n_lm, dtype=torch.int32, device=device),
+           "keep": torch.ones(n_lm, dtype=torch.uint8, device=device),
+           "scan_stat": torch.zeros(q, 4, dtype=torch.int32, device=device),
+           "view": torch.zeros(q, dtype=torch.float64, device=device),
+           "num": torch.zeros(4, dtype=torch.int32, device=device)}       # (Q N == 0: the call writes nothing)
+    need = persist_workspace_bytes(q, n, n_lm)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks.persist: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_persist(
+            engine._ptr(cen), engine._ptr(lab), q, n, engine._ptr(x), engine._ptr(asc), engine._ptr(lm_c) if n_lm else None,
+            engine._ptr(lm_l) if n_lm else None, engine._ptr(mask) if n_lm else None, n_lm, rad.ctypes.data, rad.shape[0],
+            float(max_range), float(margin), int(min_expected), float(max_seen_ratio),
+            engine._ptr(out["expected"]) if n_lm else None, engine._ptr(out["seen"]) if n_lm else None,
+            engine._ptr(out["keep"]) if n_lm else None, engine._ptr(out["scan_stat"]), engine._ptr(out["view"]),
+            engine._ptr(out["num"]), engine._ptr(workspace), workspace.numel(), engine._stream(device)))
+    return out
+
+
+def persist(centers, labels, poses, assoc, lm, use=None, radius=None, max_range=50.0, margin=2.0, min_expected=5,
+            max_seen_ratio=0.3, prior=None, workspace=None, device=None):
+    """What one drive should have seen of the landmark map `lm` and what it saw.  A scan sees what lies
+    within the range of its farthest live node, capped by max_range, less margin; a landmark is EXPECTED by every scan
+    that has it in view or observes it, SEEN by every scan with a node on it (assoc), and retired - keep 0 - when the
+    drive expected it at least min_expected times and saw it in less than max_seen_ratio of those.  There is no
+    occlusion model.  Arguments as persist_async; prior: (expected, seen) of earlier drives, added into the tallies
+    returned - lifetime tallies; keep stays THIS drive's decision.
+    -> dict: expected, seen i32 [L] and keep bool [L] on the device (select(lm, keep=...) takes it); numpy arrays
+    scan_expected, scan_seen, scan_live, flags i32 [Q], view f64 [Q], num i32 [4] = (retired, eligible landmarks with expected >= min_expected,
+    eligible landmarks, scans with a view)."""
+    out = persist_async(centers, labels, poses, assoc, lm, use=use, radius=radius, max_range=max_range, margin=margin,
+                        min_expected=min_expected, max_seen_ratio=max_seen_ratio, workspace=workspace, device=device)
+    expected, seen = out["expected"], out["seen"]
+    if prior is not None:
+        dev = expected.device
+        p_exp, p_seen = (engine._on(torch.as_tensor(t).reshape(-1), dev, torch.int32) for t in prior)
+        if p_exp.numel() > expected.numel() or p_seen.numel() != p_exp.numel():
+            raise ValueError("landmarks.persist: prior holds (expected, seen) of at most the map's landmarks")
+        expected, seen = expected.clone(), seen.clone()              # (a map that grew: the new landmarks have no prior)
+        expected[:p_exp.numel()] += p_exp
+        seen[:p_seen.numel()] += p_seen
+    stat = out["scan_stat"].cpu().numpy()
+    return {"expected": expected, "seen": seen, "keep": out["keep"] != 0, "scan_expected": stat[:, 0], "scan_seen": stat[:, 1],
+            "scan_live": stat[:, 2], "flags": stat[:, 3], "view": out["view"].cpu().numpy(),
+            "num": out["num"].cpu().numpy()}
 
 
 def virtual_scans(lm, poses, sensor_range=50.0, node_num=100, keep=None):

@@ -102,6 +102,15 @@ whose count is that of the landmark holding their first node in the map built on
 `<seq>_update.npz` holds the records of the updated map, node_landmark of the new scans, num = (landmarks, live,
 observed, new nodes), landmarks_before, batch_landmarks, same_count, poses, start, first_scan, session, node_base,
 radii, iters.
+With --retire [--view-range R] [--view-margin M] [--min-expected E] [--max-seen-ratio r] on top of that the drive just
+folded in is tallied on the UPDATED map (SG.map_persistence, landmarks.persist) with the node_landmark the
+update returned: a scan sees what lies within the range of its farthest node, at most R (default 50 m), less M (2 m); a
+landmark the drive should have seen at least E times (5) and saw in less than r (0.3) of them is retired - a mask, the
+records stay.  THERE IS NO OCCLUSION MODEL: a landmark hidden behind a lorry counts as missed, and M and r absorb that.
+Printed are the landmarks in use (three or more observations) before and after retiring and the median over the scans of
+landmarks seen / landmarks expected; `<seq>_persist.npz` holds expected, seen, keep per landmark, scan_expected,
+scan_seen, scan_live, flags, view per scan, num = (retired, judged, eligible, scans with a view), in_use_before,
+in_use_after, scan_ratio_median and the parameters.  Without --retire every output is as before.
 """
 import argparse
 import math
@@ -441,6 +450,18 @@ def main(argv=None):
     ap.add_argument("--update", action="store_true",
                     help="with --landmarks --sessions N: build the landmark map on every session but the last, align the "
                          "last session to it and fold it in (DESIGN.md §32); writes <seq>_update.npz")
+    ap.add_argument("--retire", action="store_true",
+                    help="with --update: tally what the drive folded in should have seen of the updated map and what it saw, "
+                         "and retire the landmarks it should have seen and did not (DESIGN.md §33); writes <seq>_persist.npz. "
+                         "There is no occlusion model: a hidden landmark counts as missed")
+    ap.add_argument("--view-range", type=float, default=50.0, metavar="R",
+                    help="with --retire: the sensor range in metres; a scan sees as far as its farthest node, at most R")
+    ap.add_argument("--view-margin", type=float, default=2.0, metavar="M",
+                    help="with --retire: metres taken off a scan's range")
+    ap.add_argument("--min-expected", type=int, default=5, metavar="E",
+                    help="with --retire: a landmark is judged when at least E scans should have seen it")
+    ap.add_argument("--max-seen-ratio", type=float, default=0.3, metavar="r",
+                    help="with --retire: ... and retired when fewer than r of them did (0..1)")
     ap.add_argument("--save-poses", default=None, metavar="FILE",
                     help="with --optimize: write the optimised planar poses [M,4] (c, s, x, y) to FILE (.npy)")
     ap.add_argument("--localize", action="store_true",
@@ -506,6 +527,11 @@ def main(argv=None):
         ap.error("--align needs --landmarks")
     if opt.update and not (opt.landmarks and opt.sessions is not None):
         ap.error("--update needs --landmarks and --sessions N")
+    if opt.retire and not opt.update:
+        ap.error("--retire needs --update")
+    if opt.retire and not (opt.view_range >= 0 and 0 <= opt.view_margin < math.inf and opt.min_expected >= 0
+                           and 0 <= opt.max_seen_ratio <= 1):
+        ap.error("--view-range, --view-margin and --min-expected must be >= 0, --max-seen-ratio in 0..1")
     if opt.align or opt.update:
         try:
             opt.align_radii = [float(t) for t in opt.align_radii.split(",") if t.strip()]
@@ -671,6 +697,16 @@ def main(argv=None):
                   % (int(ureport["landmarks_before"]), int(ureport["num"][0]), int(ureport["num"][0] - ureport["landmarks_before"]),
                      int(ureport["num"][2]), int(ureport["num"][3])),
                   "count as in the batch map of %d landmarks: %.4f" % (int(ureport["batch_landmarks"]), ureport["same_count"]))
+            if opt.retire:
+                preport = persist_lists(trainer.model, seq, ureport, max_range=opt.view_range, margin=opt.view_margin,
+                                        min_expected=opt.min_expected, max_seen_ratio=opt.max_seen_ratio, radius=opt.lm_radius)
+                np.savez(os.path.join(args.output_path, sequence + "_persist.npz"), **preport)
+                print("sequence", sequence, "session %d tallied on the updated map (view %g m less %g m, no occlusion model):"
+                      % (int(ureport["session"]), opt.view_range, opt.view_margin),
+                      "landmarks in use %d -> %d, retired %d of %d judged (expected >= %d, seen < %g of expected),"
+                      % (int(preport["in_use_before"]), int(preport["in_use_after"]), int(preport["num"][0]), int(preport["num"][1]),
+                         opt.min_expected, opt.max_seen_ratio),
+                      "per-scan seen / expected %.4f (median)" % preport["scan_ratio_median"])
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
@@ -996,6 +1032,30 @@ def update_lists(model, seq, sessions, radii=(2.0, 0.75), iters=10, min_nodes=6,
                 "same_count": np.float64(same.mean() if same.size else 1.0), "poses": X, "start": own[b:],
                 "first_scan": np.int64(b), "session": np.int64(last), "node_base": np.int64(b * n),
                 "radii": np.asarray(radii, dtype=np.float64), "iters": np.int64(iters)})
+    return out
+
+
+def persist_lists(model, seq, updated, max_range=50.0, margin=2.0, min_expected=5, max_seen_ratio=0.3, radius=0.75, min_count=3):
+    """The drive update_lists folded in, tallied on the map it left (SG.map_persistence): `updated` is update_lists' dict -
+    the records of the updated map, node_landmark and poses of the new scans, first_scan.  There is no occlusion model.
+    -> dict of numpy arrays: expected, seen i32 [L], keep bool [L]; scan_expected, scan_seen, scan_live, flags i32 [Q],
+    view f64 [Q]; num = (retired, landmarks judged, eligible landmarks, scans with a view); in_use_before / in_use_after
+    (the landmarks with at least min_count observations, and those of them that are kept), scan_ratio_median (the median
+    of scan_seen / scan_expected over the scans that expected a landmark), and the parameters."""
+    b = int(updated["first_scan"])
+    lm = {k: updated[k] for k in ("center", "label", "count", "first", "sessions", "spread")}
+    got = model.map_persistence(seq.centers[b:], seq.labels[b:], updated["poses"], lm, node_landmark=updated["node_landmark"],
+                                max_range=max_range, margin=margin, min_expected=min_expected, max_seen_ratio=max_seen_ratio,
+                                radius=radius)
+    out = {k: got[k].cpu().numpy() for k in ("expected", "seen", "keep")}
+    out.update({k: got[k] for k in ("scan_expected", "scan_seen", "scan_live", "flags", "view")})
+    in_use = np.asarray(updated["count"]) >= int(min_count)
+    asked = out["scan_expected"] > 0
+    out.update({"num": np.asarray(got["num"], dtype=np.int64), "in_use_before": np.int64(in_use.sum()),
+                "in_use_after": np.int64((in_use & out["keep"]).sum()),
+                "scan_ratio_median": np.float64(np.median(out["scan_seen"][asked] / out["scan_expected"][asked]) if asked.any() else 0.0),
+                "max_range": np.float64(max_range), "margin": np.float64(margin), "min_expected": np.int64(min_expected),
+                "max_seen_ratio": np.float64(max_seen_ratio), "min_count": np.int64(min_count), "first_scan": np.int64(b)})
     return out
 
 

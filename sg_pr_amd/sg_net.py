@@ -448,6 +448,34 @@ class SG(torch.nn.Module):
         return _landmarks.update(centers, labels, x, assoc, lm, session_base=int(session), node_base=int(node_base),
                                  radius=radius, tau_z=tz, device=dev)
 
+    def map_persistence(self, centers, labels, poses, lm, node_landmark=None, max_range=50.0, margin=2.0, min_expected=5,
+                        max_seen_ratio=0.3, radius=0.75, tau_z=None):
+        """What a drive should have seen of a landmark map and what it saw (landmarks.persist): per
+        landmark the scans that had it within their view range or observed it (expected) and the scans with a node on
+        it (seen), and keep = False for the landmarks the drive expected at least min_expected times and saw in less
+        than max_seen_ratio of them - the parked car that has left.  The map is not changed: pass keep to
+        landmarks.select, align_to_map or landmarks.virtual_scans.  A scan's view range is the range of its farthest
+        live node, at most max_range, less margin (metres).  There is no occlusion model.
+        ALIGN FIRST (align_to_map) and pass the poses it returned, as for update_map: from poses 0.3 m off, nodes of
+        permanent objects miss their landmarks and the landmarks count as unseen.  Run it on the drive JUST FOLDED IN,
+        on the UPDATED map, with the node_landmark that update_map returned: the drive's new landmarks are then seen by
+        it, and a lifetime ratio cannot tell "gone since last week" from "new since last week".
+        centers [Q,N,3], labels [Q,N]; poses: KITTI rows [Q,12] or planar [Q,4] in the frame of the map; lm: the dict
+        of landmark_map or update_map; node_landmark [Q,N]: the association of the nodes with lm (None: as update_map
+        makes it - one landmarks.align call with iters=0 and no use mask, gate `radius`, tau_z).
+        -> the dict of landmarks.persist: expected, seen, keep per landmark, scan_expected, scan_seen, scan_live, flags,
+        view per scan, num."""
+        from . import landmarks as _landmarks
+        dev = self.engine().device
+        x = poses if isinstance(poses, torch.Tensor) and poses.dim() == 2 and poses.shape[1] == 4 else _planar(poses)
+        x = _engine._on(x, dev, torch.float64)
+        if node_landmark is None:
+            tz = _landmarks.DEFAULT_TAU_Z if tau_z is None else tau_z
+            node_landmark = _landmarks.align_async(centers, labels, x, lm, radius=radius, tau_z=tz, iters=0,
+                                                   device=dev)["node_landmark"]
+        return _landmarks.persist(centers, labels, x, node_landmark, lm, radius=radius, max_range=max_range, margin=margin,
+                                  min_expected=min_expected, max_seen_ratio=max_seen_ratio, device=dev)
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming
