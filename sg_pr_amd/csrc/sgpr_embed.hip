@@ -706,6 +706,9 @@ __device__ __forceinline__ unsigned ord_u32(float f) {
 // it is does not matter to the caller below, which visits all fifteen distances and carries the lane's identity along)
 template <int S>
 __device__ __forceinline__ int row_rot(int v) {
+    // (the `old` operand costs a register copy and a hazard nop ahead of every move - 2 of a counting step's 6 vector
+    //  instructions; a move without it was built and measured: fewer instructions, the same launch time - candidate S4 of
+    //  profiles/embed_sem_gemm_stream.txt)
     return __builtin_amdgcn_update_dpp(v, v, 0x120 + S, 0xF, 0xF, false);   // row_ror:S
 }
 // super-node counting selection: nodes of the labels ranked ahead of label j = sum of the counts of the other 15
@@ -1771,6 +1774,58 @@ __device__ __forceinline__ void gemm_cols(unsigned char* __restrict__ X, float* 
     constexpr int NCA = COUT / 16, NCT = 2 * NCA;
     constexpr int XR = xrow<FMT>();
     const unsigned char* xp = X + l15 * XR;
+    if constexpr (NWC == 4 && (COUT == 64 || COUT == 32)) {
+        // ---- lean instances, four waves: the tile assignment is a constant of the instance.  64 channels: a wave owns exactly
+        //      ONE a-tile (tile `wave`) and ONE b-tile (tile wave + 4), so it walks the row tiles ONCE and feeds both products
+        //      from one X fragment; 32 channels: waves 0, 1 own one a-tile, waves 2, 3 one b-tile.  No search for the b-tile, no
+        //      tile loop, no "next tile" bookkeeping; every tile16 sees the operands (and issues the matrix instructions) of the
+        //      general walk below, so every result bit is that walk's.
+        constexpr bool BOTH = COUT == 64;
+        FragT<FMT> w[2], wn[2], xf[2];
+        f32x4 kb[4];
+        if (pre) {
+            w[0] = pre[0];
+            if (NKB != 1) w[1] = pre[1];
+        } else {
+            load_wfrag<NKB>(Wb + (size_t)wave * wtile<NKB, FMT>(), w, constw);
+        }
+        if constexpr (BOTH) load_wfrag<NKB>(Wb + (size_t)(wave + NCA) * wtile<NKB, FMT>(), wn, constw);
+        const bool is_a = BOTH || wave < NCA;                     // (wave-uniform)
+        const int cb = BOTH ? wave : wave - NCA;                  // the b-tile's place among the b-tiles
+        if (is_a) {
+            float* ap = A + l15 * pitchA + wave * 16 + 4 * lq;
+            f32x4 t = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (BOTH) {
+                const float4 t4 = *reinterpret_cast<const float4*>(tb + cb * 16 + 4 * lq);
+                t = f32x4{t4.x, t4.y, t4.z, t4.w};
+            }
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt)
+                if (rt < nrt) {
+                    load_xfrag<NKB>(xp + rt * 16 * XR, lq, xf);
+                    const f32x4 r = (ex & 1024) ? f32x4{1.f, 2.f, 3.f, 4.f} : tile16<NKB>(w, xf);
+                    *reinterpret_cast<float4*>(ap + rt * 16 * pitchA) = make_float4(r[0], r[1], r[2], r[3]);
+                    if constexpr (BOTH) kb[rt] = ((ex & 1024) ? f32x4{1.f, 2.f, 3.f, 4.f} : tile16<NKB>(wn, xf)) + t;
+                }
+        } else {
+            const float4 t4 = *reinterpret_cast<const float4*>(tb + cb * 16 + 4 * lq);
+            const f32x4 t = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt)
+                if (rt < nrt) {
+                    load_xfrag<NKB>(xp + rt * 16 * XR, lq, xf);
+                    kb[rt] = ((ex & 1024) ? f32x4{1.f, 2.f, 3.f, 4.f} : tile16<NKB>(w, xf)) + t;
+                }
+        }
+        if (!(ex & 2048)) __syncthreads();                                             // every wave is done reading X
+        if (BOTH || !is_a) {
+            unsigned char* bp = X + l15 * XR + 16 * lq + cb * 64;
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt)
+                if (rt < nrt) *reinterpret_cast<float4*>(bp + rt * 16 * XR) = make_float4(kb[rt][0], kb[rt][1], kb[rt][2], kb[rt][3]);
+        }
+        return;
+    }
     // this wave's b-tiles: the first ct >= NCA congruent to wave (mod NW), and the one after it
     int ctb0 = wave;
     while (ctb0 < NCA) ctb0 += NW;
@@ -2120,8 +2175,13 @@ __device__ __forceinline__ void supernode_branch(const DevWeights& w, const int 
     }
     group_sync<WAVE>();
     // layers 2 and 3 on the 13 virtual rows
+    // (the two layers differ in shape - 64 channels from the tables, then 32 channels on the matrix pipe: the tuned kernels
+    //  run on the built architecture alone (dims_supported), so the widths are constants and each trip gets its own stream)
+    static_assert(kF2 == 64 && kF3 == 32, "supernode_branch: layer widths");
+    constexpr int kLayerStreams = LEAN > 0 ? 2 : 1;                    // (the big instance keeps one stream: registers)
+#pragma unroll kLayerStreams
     for (int Lv = (skip & 16384) ? 3 : 1; Lv < 3; ++Lv) {      // (ablation bit 14: super-node layers 2 and 3 off)
-        const int cout = w.cout[Lv];
+        const int cout = Lv == 1 ? kF2 : kF3;
         const unsigned short* wl = FMT == FMT_H2 ? w.wh[Lv] : w.wb[Lv];
         // the keys of the 16 virtual rows sit beside the 16 rows of A, so that in the lean instance the Gram tile
         // (wave 0) and the a / b column tiles (the other waves) run side by side: three barriers per layer
@@ -2738,7 +2798,7 @@ __device__ __forceinline__ void embed_graph(const KParams& kp, const EmbedPlan& 
         lq = lane >> 4;
         if (L == 3 && !((BIG && SGPR_BIG_SEM_WAVE != 0) && sem_conc)) {
             // ---- stage the second branch's input (xyz, zero padded to 16 channels / NP rows) + (x, y, z, |x|^2) in fp32
-            if (tid < NP) {
+            if (tid < NP && !(skip & 524288)) {          // (ablation bit 19: no staging - only with selection, GEMMs and gather off)
                 const bool live = tid < N;
                 unsigned char* xr = X + tid * XROW;
                 xstore<FMT>(xr, 0, live ? make_float4(fx, fy, fz, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f), vmax);
