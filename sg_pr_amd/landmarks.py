@@ -1,10 +1,11 @@
 """The semantic landmark map: the nodes of every scan fused in the map frame (include/sgpr_landmarks.h),
 the refinement of the poses on that map (include/sgpr_landmark_refine.h), the alignment of further
 scans to it (include/sgpr_landmark_align.h), the folding of aligned scans into it
-(include/sgpr_landmark_update.h) and the tallies of what a drive should have seen of it and did see
-(include/sgpr_landmark_persist.h).
+(include/sgpr_landmark_update.h), the tallies of what a drive should have seen of it and did see
+(include/sgpr_landmark_persist.h) and the tracking of a drive through it, scan by scan
+(include/sgpr_landmark_track.h).
 
-The entry points are declared in the fourth to eighth public headers; this module has engine.bind_header parse them and
+The entry points are declared in the fourth to ninth public headers; this module has engine.bind_header parse them and
 set the signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -27,7 +28,14 @@ UPDATE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_update.h")
 UPDATE_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(UPDATE_HEADER)).functions]
 PERSIST_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_persist.h")
 PERSIST_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(PERSIST_HEADER)).functions]
+TRACK_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_track.h")
+_TRACK_ABI = engine.public_header(os.path.basename(TRACK_HEADER))
+TRACK_ABI_SYMBOLS = [name for name, _, _ in _TRACK_ABI.functions]
 ALIGN_NONFINITE, ALIGN_KEPT = 1, 2       # flags of sgpr_landmark_align (d_stat[q][3])
+_T = _TRACK_ABI.constants
+TRACK_MAX_STAGES, TRACK_START_LOST = _T["SGPR_TRACK_MAX_STAGES"], _T["SGPR_TRACK_START_LOST"]
+TRACK_NONFINITE, TRACK_KEPT, TRACK_LOST, TRACK_NO_ODOM, TRACK_REACQUIRE = (
+    _T["SGPR_TRACK_" + k] for k in ("NONFINITE", "KEPT", "LOST", "NO_ODOM", "REACQUIRE"))   # flags of a tracked scan
 MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
 DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
 DEFAULT_MAX_LANDMARKS = 1 << 22          # the default capacity is G N, capped here; build() re-runs past it
@@ -36,12 +44,14 @@ _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L floa
 
 def load_library():
     """engine.load_library() with the signatures of include/sgpr_landmarks.h, include/sgpr_landmark_refine.h,
-    include/sgpr_landmark_align.h, include/sgpr_landmark_update.h and include/sgpr_landmark_persist.h set on it"""
+    include/sgpr_landmark_align.h, include/sgpr_landmark_update.h, include/sgpr_landmark_persist.h and
+    include/sgpr_landmark_track.h set on it"""
     engine.bind_header(os.path.basename(HEADER))
     engine.bind_header(os.path.basename(REFINE_HEADER))
     engine.bind_header(os.path.basename(ALIGN_HEADER))
     engine.bind_header(os.path.basename(UPDATE_HEADER))
     engine.bind_header(os.path.basename(PERSIST_HEADER))
+    engine.bind_header(os.path.basename(TRACK_HEADER))
     return engine.load_library()
 
 
@@ -291,6 +301,111 @@ def align(centers, labels, poses, lm, use=None, radius=None, tau_z=DEFAULT_TAU_Z
     stat = out["stat"].cpu().numpy()
     return out["poses"], {"matched": stat[:, 0], "live": stat[:, 1], "steps": stat[:, 2], "flags": stat[:, 3],
                           "rms": out["rms"].cpu().numpy(), "node_landmark": out["node_landmark"].cpu().numpy()}
+
+
+def track_workspace_bytes(Q, N, L, n_stages):
+    return int(load_library().sgpr_landmark_track_workspace_bytes(int(Q), int(N), int(L), int(n_stages)))
+
+
+def _stage_table(radii, reacquire_radii):
+    """the stages of a tracking call: reacquire_radii in front of radii, each entry a scalar or one value per label ->
+    (float64 [n_stages, n_labels] C-contiguous, n_reacquire)"""
+    def stages(v):
+        return [] if v is None else (list(v) if hasattr(v, "__len__") else [v])
+    front, rest = stages(reacquire_radii), stages(radii)
+    rows = [_radius_table(r) for r in front + rest]
+    if not rows or len({r.shape[0] for r in rows}) != 1:
+        raise ValueError("landmarks.track: every stage takes a scalar radius or one value per label, the same labels in each")
+    return np.ascontiguousarray(np.stack(rows)), len(front)
+
+
+def track_async(centers, labels, odom, init, lm, use=None, starts=None, radii=(2.0, DEFAULT_RADIUS), reacquire_radii=(8.0,),
+                tau_z=DEFAULT_TAU_Z, iters=10, min_nodes=6, min_matched=10, max_shift=float("inf"), start_lost=False,
+                workspace=None, device=None):
+    """sgpr_landmark_track without reading anything back -> dict of device tensors, asynchronous on the current stream:
+    poses, pred f64 [Q,4] (the tracked pose and the prediction it started from), node_landmark i32 [Q,N], stat i32 [Q,4] =
+    (matched, live, steps that re-fitted, flags: TRACK_NONFINITE, TRACK_KEPT, TRACK_LOST, TRACK_NO_ODOM,
+    TRACK_REACQUIRE), rms f64 [Q], num i32 [4] = (scans tracked, scans lost, longest run of lost scans, tracks).  centers
+    f32 [Q,N,3], labels i32 [Q,N]: the scans of the drives, in order; odom [Q,4]: their planar poses in a frame of the
+    drive's own; starts: the first scan of every track (None: one track); init [n_tracks,4]: the map-frame pose of every
+    track's first scan; lm, use, tau_z, iters, min_nodes: as align_async takes them; radii: the gates every scan runs,
+    reacquire_radii: the gates run in front of them after a lost scan (None or empty: none) - each a scalar or one value
+    per label; a scan with fewer than min_matched matches, or fitted more than max_shift metres from its prediction, is
+    lost and keeps the prediction; start_lost: the first scan of a track runs the re-acquisition gates too.  workspace: a
+    uint8 device tensor of at least track_workspace_bytes(Q, N, L, n_stages) to reuse."""
+    lib = load_library()
+    if device is None:
+        device = engine._device_of(centers, labels, odom, lm["center"])
+    lab = engine._on(labels, device, torch.int32)
+    if lab.dim() != 2:
+        raise ValueError("landmarks.track: labels must be [Q, N]")
+    q, n = lab.shape
+    cen = engine._on(centers, device, torch.float32)
+    if cen.numel() != q * n * 3:
+        raise ValueError("landmarks.track: centers must be [Q, N, 3]")
+    odo = engine._on(odom, device, torch.float64)
+    if odo.numel() != q * 4:
+        raise ValueError("landmarks.track: odom must hold one planar pose (c, s, x, y) per scan")
+    table = engine._session_table(starts)
+    n_tracks = 1 if table is None else table.shape[0]
+    x0 = engine._on(init, device, torch.float64)
+    if x0.numel() != n_tracks * 4:
+        raise ValueError("landmarks.track: init must hold one planar pose (c, s, x, y) per track")
+    lm_c = engine._on(lm["center"], device, torch.float64)
+    lm_l = engine._on(lm["label"], device, torch.int32)
+    n_lm = int(lm_l.numel())
+    if lm_c.numel() != 3 * n_lm:
+        raise ValueError("landmarks.track: the map must hold center [L,3] and label [L]")
+    mask = None
+    if use is not None:
+        mask = engine._on(torch.as_tensor(use).reshape(-1) != 0, device, torch.bool).to(torch.uint8)
+        if mask.numel() != n_lm:
+            raise ValueError("landmarks.track: use must hold one entry per landmark")
+    rad, n_reacquire = _stage_table(radii, reacquire_radii)
+    n_stages = rad.shape[0]
+    out = {"poses": torch.empty(q, 4, dtype=torch.float64, device=device),
+           "pred": torch.empty(q, 4, dtype=torch.float64, device=device),
+           "node_landmark": torch.full((q, n), -1, dtype=torch.int32, device=device),
+           "stat": torch.zeros(q, 4, dtype=torch.int32, device=device),
+           "rms": torch.full((q,), float("nan"), dtype=torch.float64, device=device),
+           "num": torch.zeros(4, dtype=torch.int32, device=device)}       # (Q N == 0: the call writes nothing)
+    need = track_workspace_bytes(q, n, n_lm, n_stages)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks.track: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_track(
+            engine._ptr(cen), engine._ptr(lab), q, n, engine._ptr(odo), *engine._table_args(table), engine._ptr(x0),
+            engine._ptr(lm_c) if n_lm else None, engine._ptr(lm_l) if n_lm else None, engine._ptr(mask) if n_lm else None, n_lm,
+            rad.ctypes.data, n_stages, n_reacquire, rad.shape[1], float(tau_z), int(iters), int(min_nodes), int(min_matched),
+            float(max_shift), TRACK_START_LOST if start_lost else 0, engine._ptr(out["poses"]), engine._ptr(out["pred"]),
+            engine._ptr(out["node_landmark"]), engine._ptr(out["stat"]), engine._ptr(out["rms"]), engine._ptr(out["num"]),
+            engine._ptr(workspace), workspace.numel(), engine._stream(device)))
+    if q * n == 0:
+        out["poses"].zero_()
+        out["pred"].zero_()
+    return out
+
+
+def track(centers, labels, odom, init, lm, use=None, starts=None, radii=(2.0, DEFAULT_RADIUS), reacquire_radii=(8.0,),
+          tau_z=DEFAULT_TAU_Z, iters=10, min_nodes=6, min_matched=10, max_shift=float("inf"), start_lost=False, workspace=None,
+          device=None):
+    """Track drives through the landmark map `lm`: the scans of a track in order, each predicted from the
+    tracked pose of its predecessor and the odometry between the two, then aligned to the map through the gates `radii`
+    (every stage an align of that scan).  A scan that ends with fewer than min_matched matches, or more than max_shift
+    from its prediction, is LOST: it keeps the prediction - the track dead-reckons on - and the next scan runs the wider
+    reacquire_radii first.  Arguments as track_async.
+    -> (poses f64 [Q,4] on the device, info dict of numpy arrays: pred f64 [Q,4], matched, live, steps, flags i32 [Q], lost
+    bool [Q], rms f64 [Q], node_landmark i32 [Q,N] (of a lost scan too: what its last stage saw), num i32 [4] = (scans
+    tracked, scans lost, longest run of lost scans, tracks))."""
+    out = track_async(centers, labels, odom, init, lm, use=use, starts=starts, radii=radii, reacquire_radii=reacquire_radii,
+                      tau_z=tau_z, iters=iters, min_nodes=min_nodes, min_matched=min_matched, max_shift=max_shift,
+                      start_lost=start_lost, workspace=workspace, device=device)
+    stat = out["stat"].cpu().numpy()
+    return out["poses"], {"pred": out["pred"].cpu().numpy(), "matched": stat[:, 0], "live": stat[:, 1], "steps": stat[:, 2],
+                          "flags": stat[:, 3], "lost": (stat[:, 3] & TRACK_LOST) != 0, "rms": out["rms"].cpu().numpy(),
+                          "node_landmark": out["node_landmark"].cpu().numpy(), "num": out["num"].cpu().numpy()}
 
 
 def update_workspace_bytes(Q, N, L):

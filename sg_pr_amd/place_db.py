@@ -18,7 +18,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
                                             [--verify] [--min-inliers I] [--consistent] [--distinct RHO] [--seq-slopes S,S,...]
-                                            [--sessions N] [--optimize] [--save-poses FILE]
+                                            [--sessions N] [--optimize] [--save-poses FILE] [--landmarks] [--track]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -111,6 +111,17 @@ Printed are the landmarks in use (three or more observations) before and after r
 landmarks seen / landmarks expected; `<seq>_persist.npz` holds expected, seen, keep per landmark, scan_expected,
 scan_seen, scan_live, flags, view per scan, num = (retired, judged, eligible, scans with a view), in_use_before,
 in_use_after, scan_ratio_median and the parameters.  Without --retire every output is as before.
+
+With --landmarks --sessions N --track [--track-radii 2,0.75] [--reacquire-radii 8] [--min-matched M] the last of the N
+sessions is TRACKED through the landmark map of the others (SG.track_in_map, landmarks.track): its first
+scan starts from its localised pose (--localize, when that scan was localised) or its stored pose, every further scan
+from the tracked pose of the one before moved by the sequence's own relative motion; a scan is aligned through the
+gates of --track-radii (--align-iters rounds each), is lost with fewer than M matches (default 10) and then keeps its
+prediction, and the scan after a lost one runs the gates of --reacquire-radii first.  Printed are the scans tracked and
+lost, the longest run of lost scans and the median matched share; `<seq>_track.npz` holds poses, pred [Q,4], matched, live,
+steps, flags, lost, rms, node_landmark, num = (tracked, lost, longest lost run, tracks), init, from_localize, first_scan,
+session, radii, reacquire_radii, iters, min_matched, matched_share and the translation error against the sequence's own
+poses.  Without --track every output is as before.
 """
 import argparse
 import math
@@ -450,6 +461,15 @@ def main(argv=None):
     ap.add_argument("--update", action="store_true",
                     help="with --landmarks --sessions N: build the landmark map on every session but the last, align the "
                          "last session to it and fold it in (DESIGN.md §32); writes <seq>_update.npz")
+    ap.add_argument("--track", action="store_true",
+                    help="with --landmarks --sessions N: track the last session through the landmark map of the others from "
+                         "one initial pose (DESIGN.md §34); writes <seq>_track.npz")
+    ap.add_argument("--track-radii", default="2,0.75", metavar="R,R,..",
+                    help="with --track: the gates every scan runs, metres, wide to narrow")
+    ap.add_argument("--reacquire-radii", default="8", metavar="R,..",
+                    help="with --track: the gates run in front of them on the scan after a lost one (empty: none)")
+    ap.add_argument("--min-matched", type=int, default=10, metavar="M",
+                    help="with --track: a scan with fewer matches is lost and keeps its predicted pose")
     ap.add_argument("--retire", action="store_true",
                     help="with --update: tally what the drive folded in should have seen of the updated map and what it saw, "
                          "and retire the landmarks it should have seen and did not (DESIGN.md §33); writes <seq>_persist.npz. "
@@ -529,6 +549,20 @@ def main(argv=None):
         ap.error("--update needs --landmarks and --sessions N")
     if opt.retire and not opt.update:
         ap.error("--retire needs --update")
+    if opt.track:
+        if not (opt.landmarks and opt.sessions is not None):
+            ap.error("--track needs --landmarks and --sessions N")
+        try:
+            opt.track_radii = [float(t) for t in opt.track_radii.split(",") if t.strip()]
+            opt.reacquire_radii = [float(t) for t in opt.reacquire_radii.split(",") if t.strip()]
+        except ValueError:
+            ap.error("--track-radii and --reacquire-radii are comma-separated lists of metres")
+        from .landmarks import TRACK_MAX_STAGES
+        if not (opt.track_radii and all(r > 0 for r in opt.track_radii + opt.reacquire_radii)
+                and len(opt.track_radii) + len(opt.reacquire_radii) <= TRACK_MAX_STAGES and opt.min_matched >= 0
+                and opt.align_iters >= 0):
+            ap.error("--track-radii and --reacquire-radii must be positive, at most %d gates together; --min-matched and "
+                     "--align-iters >= 0" % TRACK_MAX_STAGES)
     if opt.retire and not (opt.view_range >= 0 and 0 <= opt.view_margin < math.inf and opt.min_expected >= 0
                            and 0 <= opt.max_seen_ratio <= 1):
         ap.error("--view-range, --view-margin and --min-expected must be >= 0, --max-seen-ratio in 0..1")
@@ -707,6 +741,20 @@ def main(argv=None):
                       % (int(preport["in_use_before"]), int(preport["in_use_after"]), int(preport["num"][0]), int(preport["num"][1]),
                          opt.min_expected, opt.max_seen_ratio),
                       "per-scan seen / expected %.4f (median)" % preport["scan_ratio_median"])
+        if opt.track:
+            treport = track_lists(trainer.model, seq, opt.sessions, located=lreport if opt.localize else None,
+                                  radii=opt.track_radii, reacquire_radii=opt.reacquire_radii, iters=opt.align_iters,
+                                  min_matched=opt.min_matched, radius=opt.lm_radius, tau_z=opt.lm_tau_z)
+            np.savez(os.path.join(args.output_path, sequence + "_track.npz"), **treport)
+            print("sequence", sequence, "session %d of %d tracked through the landmark map of the others, gates %s m (after a lost "
+                  "scan %s m first) x %d iterations:"
+                  % (int(treport["session"]), opt.sessions, ", ".join("%g" % r for r in opt.track_radii),
+                     ", ".join("%g" % r for r in opt.reacquire_radii) or "-", opt.align_iters),
+                  "tracked %d, lost %d of %d scans (fewer than %d matches), longest lost run %d, matched share %.4f (median),"
+                  % (int(treport["num"][0]), int(treport["num"][1]), treport["lost"].shape[0], opt.min_matched,
+                     int(treport["num"][2]), treport["matched_share"]),
+                  "translation %.4f / %.4f m (median / 95%%), first pose from %s"
+                  % (treport["median_trans_m"], treport["p95_trans_m"], "localize" if treport["from_localize"] else "the stored pose"))
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
@@ -1032,6 +1080,40 @@ def update_lists(model, seq, sessions, radii=(2.0, 0.75), iters=10, min_nodes=6,
                 "same_count": np.float64(same.mean() if same.size else 1.0), "poses": X, "start": own[b:],
                 "first_scan": np.int64(b), "session": np.int64(last), "node_base": np.int64(b * n),
                 "radii": np.asarray(radii, dtype=np.float64), "iters": np.int64(iters)})
+    return out
+
+
+def track_lists(model, seq, sessions, located=None, radii=(2.0, 0.75), reacquire_radii=(8.0,), iters=10, min_nodes=6,
+                min_matched=10, radius=0.75, tau_z=0.75):
+    """The last of `sessions` consecutive near-equal sessions of `seq` (session_lists' split) tracked through the landmark
+    map of the others (SG.track_in_map): the map is built on the sequence's own poses (SG.landmark_map), all of its
+    landmarks take part, the odometry of the drive is the sequence's own poses.  located: the dict of localize_lists;
+    when it accepted the drive's first scan the track starts from its pose, else from the stored one.
+    -> dict of numpy arrays: poses, pred f64 [Q,4], matched, live, steps, flags i32 [Q], lost bool [Q], rms f64 [Q],
+    node_landmark i32 [Q,N], num = (tracked, lost, longest lost run, tracks), init [1,4], from_localize, first_scan,
+    session, radii, reacquire_radii, iters, min_nodes, min_matched, matched_share (the median of matched / live over the
+    scans with a live node), median_trans_m / p95_trans_m against the sequence's own poses."""
+    m = seq.labels.shape[0]
+    bounds = np.asarray([(j * m) // int(sessions) for j in range(int(sessions))], dtype=np.int32)
+    b, last = int(bounds[-1]), int(sessions) - 1
+    own = metrics.planar_odometry(seq.poses)
+    lm = model.landmark_map(seq.centers[:b], seq.labels[:b], own[:b], sessions=bounds[:-1], radius=radius, tau_z=tau_z)
+    init = np.array(own[b:b + 1])
+    given = bool(located is not None and np.asarray(located["accept"], dtype=bool).reshape(-1)[b]
+                 and np.isfinite(located["pose"][b]).all())
+    if given:
+        init[0] = located["pose"][b]
+    X, info = model.track_in_map(seq.centers[b:], seq.labels[b:], own[b:], init, lm, radii=radii, reacquire_radii=reacquire_radii,
+                                 iters=iters, min_nodes=min_nodes, min_matched=min_matched, tau_z=tau_z)
+    X = X.cpu().numpy()
+    out = {"poses": X, "init": init, "from_localize": np.bool_(given), "first_scan": np.int64(b), "session": np.int64(last),
+           "radii": np.asarray(radii, dtype=np.float64), "reacquire_radii": np.asarray(reacquire_radii, dtype=np.float64),
+           "iters": np.int64(iters), "min_nodes": np.int64(min_nodes), "min_matched": np.int64(min_matched)}
+    out.update({k: info[k] for k in ("pred", "matched", "live", "steps", "flags", "lost", "rms", "node_landmark", "num")})
+    err = metrics.localization_errors(X, own[b:])["trans_m"]
+    out["median_trans_m"], out["p95_trans_m"] = np.float64(np.median(err)), np.float64(np.percentile(err, 95))
+    seen = info["live"] > 0
+    out["matched_share"] = np.float64(np.median(info["matched"][seen] / info["live"][seen]) if seen.any() else 0.0)
     return out
 
 

@@ -422,6 +422,38 @@ class SG(torch.nn.Module):
         info["accept"] = info["matched"] >= (int(min_nodes) if min_matched is None else int(min_matched))
         return x, info
 
+    def track_in_map(self, centers, labels, odom, init, lm, use=None, starts=None, radii=(2.0, 0.75), reacquire_radii=(8.0,),
+                     iters=10, min_nodes=6, min_matched=10, max_shift=float("inf"), start_lost=False, tau_z=None):
+        """Track drives through a landmark map (landmarks.track): the run-time use of the map.  One initial
+        pose per drive - what localize returned - then the drive's own odometry, and the map correcting it scan by scan, in
+        ONE call: scan i starts from the tracked pose of scan i - 1 moved by the odometry between the two, is aligned to
+        the map through the gates `radii` (align_to_map's schedule, on that one scan) and accepted, or LOST - fewer than
+        min_matched matches at the end, or fitted more than max_shift metres from where the odometry put it: then it keeps
+        the predicted pose, so the track dead-reckons on, and the next scan runs the wider gates reacquire_radii first.
+        centers [Q,N,3], labels [Q,N]: the packed node arrays of the drives' scans, in order; odom: KITTI rows [Q,12] or
+        planar [Q,4] in a frame of the drive's own (only the motion between consecutive scans is read); starts: the first
+        scan of every drive (None: one drive); init: the pose of every drive's first scan in the frame of the map, KITTI
+        rows or planar [n_drives,4]; lm: the dict of landmark_map or update_map; use: a mask over its landmarks
+        (landmarks.select; None: all); start_lost: run the wide gates on a drive's first scan too (an uncertain init).
+        A TRACK THAT STAYS LOST - info["lost"] up to its last scan, num[2] growing from call to call - has left the reach
+        of its gates: dead reckoning drifts on without bound, and only localize can place it again.  THE ROWS OF LOST
+        SCANS MUST NOT BE FED TO update_map: their pose is a prediction and their node_landmark what a failed alignment
+        saw; fold in the scans with ~info["lost"] only.
+        -> (planar poses f64 [Q,4] device tensor, info dict of numpy arrays: pred [Q,4] (the prediction of every scan),
+        matched, live, steps, flags (landmarks.TRACK_*), lost bool [Q], rms, node_landmark [Q,N], num = (scans tracked,
+        scans lost, longest run of lost scans, drives))."""
+        from . import landmarks as _landmarks
+        dev = self.engine().device
+
+        def planar(p):
+            if not (isinstance(p, torch.Tensor) and p.dim() == 2 and p.shape[1] == 4):
+                p = _planar(np.atleast_2d(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)))
+            return _engine._on(p, dev, torch.float64)
+        return _landmarks.track(centers, labels, planar(odom), planar(init), lm, use=use, starts=starts, radii=radii,
+                                reacquire_radii=reacquire_radii, iters=iters, min_nodes=min_nodes, min_matched=min_matched,
+                                max_shift=max_shift, start_lost=start_lost,
+                                tau_z=_landmarks.DEFAULT_TAU_Z if tau_z is None else tau_z, device=dev)
+
     def update_map(self, centers, labels, poses, lm, session, node_base=None, radius=0.75, tau_z=None):
         """Fold the scans of a further drive into a landmark map (landmarks.update).  Every node is
         associated with the nearest landmark of its label within `radius` of the WHOLE map - one landmarks.align call
