@@ -2,10 +2,11 @@
 the refinement of the poses on that map (include/sgpr_landmark_refine.h), the alignment of further
 scans to it (include/sgpr_landmark_align.h), the folding of aligned scans into it
 (include/sgpr_landmark_update.h), the tallies of what a drive should have seen of it and did see
-(include/sgpr_landmark_persist.h) and the tracking of a drive through it, scan by scan
-(include/sgpr_landmark_track.h).
+(include/sgpr_landmark_persist.h), the tracking of a drive through it, scan by scan
+(include/sgpr_landmark_track.h) and the relocalisation of a scan in it with no prior pose
+(include/sgpr_landmark_relocalize.h).
 
-The entry points are declared in the fourth to ninth public headers; this module has engine.bind_header parse them and
+The entry points are declared in the fourth to tenth public headers; this module has engine.bind_header parse them and
 set the signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -36,6 +37,13 @@ _T = _TRACK_ABI.constants
 TRACK_MAX_STAGES, TRACK_START_LOST = _T["SGPR_TRACK_MAX_STAGES"], _T["SGPR_TRACK_START_LOST"]
 TRACK_NONFINITE, TRACK_KEPT, TRACK_LOST, TRACK_NO_ODOM, TRACK_REACQUIRE = (
     _T["SGPR_TRACK_" + k] for k in ("NONFINITE", "KEPT", "LOST", "NO_ODOM", "REACQUIRE"))   # flags of a tracked scan
+RELOCALIZE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_relocalize.h")
+_RELOC_ABI = engine.public_header(os.path.basename(RELOCALIZE_HEADER))
+RELOCALIZE_ABI_SYMBOLS = [name for name, _, _ in _RELOC_ABI.functions]
+_R = _RELOC_ABI.constants
+RELOC_MAX_STAGES = _R["SGPR_RELOC_MAX_STAGES"]
+RELOC_FOUND, RELOC_KEPT, RELOC_TRUNCATED, RELOC_NO_HYPOTHESIS = (
+    _R["SGPR_RELOC_" + k] for k in ("FOUND", "KEPT", "TRUNCATED", "NO_HYPOTHESIS"))          # flags of a relocalised scan
 MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
 DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
 DEFAULT_MAX_LANDMARKS = 1 << 22          # the default capacity is G N, capped here; build() re-runs past it
@@ -44,14 +52,15 @@ _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L floa
 
 def load_library():
     """engine.load_library() with the signatures of include/sgpr_landmarks.h, include/sgpr_landmark_refine.h,
-    include/sgpr_landmark_align.h, include/sgpr_landmark_update.h, include/sgpr_landmark_persist.h and
-    include/sgpr_landmark_track.h set on it"""
+    include/sgpr_landmark_align.h, include/sgpr_landmark_update.h, include/sgpr_landmark_persist.h,
+    include/sgpr_landmark_track.h and include/sgpr_landmark_relocalize.h set on it"""
     engine.bind_header(os.path.basename(HEADER))
     engine.bind_header(os.path.basename(REFINE_HEADER))
     engine.bind_header(os.path.basename(ALIGN_HEADER))
     engine.bind_header(os.path.basename(UPDATE_HEADER))
     engine.bind_header(os.path.basename(PERSIST_HEADER))
     engine.bind_header(os.path.basename(TRACK_HEADER))
+    engine.bind_header(os.path.basename(RELOCALIZE_HEADER))
     return engine.load_library()
 
 
@@ -405,6 +414,102 @@ def track(centers, labels, odom, init, lm, use=None, starts=None, radii=(2.0, DE
     stat = out["stat"].cpu().numpy()
     return out["poses"], {"pred": out["pred"].cpu().numpy(), "matched": stat[:, 0], "live": stat[:, 1], "steps": stat[:, 2],
                           "flags": stat[:, 3], "lost": (stat[:, 3] & TRACK_LOST) != 0, "rms": out["rms"].cpu().numpy(),
+                          "node_landmark": out["node_landmark"].cpu().numpy(), "num": out["num"].cpu().numpy()}
+
+
+def relocalize_workspace_bytes(Q, N, L, n_stages):
+    return int(load_library().sgpr_landmark_relocalize_workspace_bytes(int(Q), int(N), int(L), int(n_stages)))
+
+
+def relocalize_async(centers, labels, lm, use=None, radius_in=None, radii=(2.0, DEFAULT_RADIUS), tau_z=DEFAULT_TAU_Z,
+                     tau_edge=0.5, min_base=5.0, max_base=30.0, max_hyp=65536, min_inliers=12, sep=10.0, iters=10, min_nodes=6,
+                     workspace=None, device=None):
+    """sgpr_landmark_relocalize without reading anything back -> dict of device tensors, asynchronous on the current
+    stream: poses, coarse, other f64 [Q,4] (the refined pose, the winning hypothesis' pose, the best hypothesis' pose at
+    another place; NaN where there is none), node_landmark i32 [Q,N], stat i32 [Q,8] = (inliers, inliers of the other
+    place, matched, live, steps that re-fitted, flags: RELOC_FOUND, RELOC_KEPT, RELOC_TRUNCATED, RELOC_NO_HYPOTHESIS,
+    base pairs started, 0), win i32 [Q,4] = (i, i', j, j') of the winner, hypotheses i64 [Q], rms f64 [Q], num i32 [4] =
+    (scans found, scans truncated, scans without a hypothesis, 0).  centers f32 [Q,N,3], labels i32 [Q,N]: the query
+    scans - NO pose is taken; lm, use, tau_z, iters, min_nodes: as align_async takes them; radius_in: the inlier gate, a
+    scalar or one value per label; radii: the refine stages, each a scalar or one value per label (None or empty: the
+    coarse pose is returned); two nodes between min_base and max_base metres apart are laid on two landmarks of their
+    labels whose distance differs by at most tau_edge; max_hyp: no further base pair is started once that many
+    hypotheses are counted; a scan is found with min_inliers inliers; sep: how far another place is, metres.  workspace:
+    a uint8 device tensor of at least relocalize_workspace_bytes(Q, N, L, n_stages) to reuse."""
+    lib = load_library()
+    if device is None:
+        device = engine._device_of(centers, labels, lm["center"])
+    lab = engine._on(labels, device, torch.int32)
+    if lab.dim() != 2:
+        raise ValueError("landmarks.relocalize: labels must be [Q, N]")
+    q, n = lab.shape
+    cen = engine._on(centers, device, torch.float32)
+    if cen.numel() != q * n * 3:
+        raise ValueError("landmarks.relocalize: centers must be [Q, N, 3]")
+    lm_c = engine._on(lm["center"], device, torch.float64)
+    lm_l = engine._on(lm["label"], device, torch.int32)
+    n_lm = int(lm_l.numel())
+    if lm_c.numel() != 3 * n_lm:
+        raise ValueError("landmarks.relocalize: the map must hold center [L,3] and label [L]")
+    mask = None
+    if use is not None:
+        mask = engine._on(torch.as_tensor(use).reshape(-1) != 0, device, torch.bool).to(torch.uint8)
+        if mask.numel() != n_lm:
+            raise ValueError("landmarks.relocalize: use must hold one entry per landmark")
+    rad_in = _radius_table(radius_in)
+    stages = [] if radii is None else (list(radii) if hasattr(radii, "__len__") else [radii])
+    rows = [_radius_table(r) for r in stages]
+    if any(r.shape[0] != rad_in.shape[0] for r in rows):
+        raise ValueError("landmarks.relocalize: every stage takes a scalar radius or one value per label, as radius_in does")
+    rad = np.ascontiguousarray(np.stack(rows)) if rows else None
+    n_stages = len(rows)
+    nan = float("nan")
+    out = {"poses": torch.full((q, 4), nan, dtype=torch.float64, device=device),
+           "coarse": torch.full((q, 4), nan, dtype=torch.float64, device=device),
+           "other": torch.full((q, 4), nan, dtype=torch.float64, device=device),
+           "node_landmark": torch.full((q, n), -1, dtype=torch.int32, device=device),
+           "stat": torch.zeros(q, 8, dtype=torch.int32, device=device),
+           "win": torch.full((q, 4), -1, dtype=torch.int32, device=device),
+           "hypotheses": torch.zeros(q, dtype=torch.int64, device=device),
+           "rms": torch.full((q,), nan, dtype=torch.float64, device=device),
+           "num": torch.zeros(4, dtype=torch.int32, device=device)}       # (Q N == 0: the call writes nothing)
+    need = relocalize_workspace_bytes(q, n, n_lm, n_stages)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks.relocalize: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_relocalize(
+            engine._ptr(cen), engine._ptr(lab), q, n, engine._ptr(lm_c) if n_lm else None, engine._ptr(lm_l) if n_lm else None,
+            engine._ptr(mask) if n_lm else None, n_lm, rad_in.ctypes.data, rad.ctypes.data if n_stages else None, n_stages,
+            rad_in.shape[0], float(tau_z), float(tau_edge), float(min_base), float(max_base), int(max_hyp), int(min_inliers),
+            float(sep), int(iters), int(min_nodes), engine._ptr(out["poses"]), engine._ptr(out["coarse"]),
+            engine._ptr(out["other"]), engine._ptr(out["node_landmark"]), engine._ptr(out["stat"]), engine._ptr(out["win"]),
+            engine._ptr(out["hypotheses"]), engine._ptr(out["rms"]), engine._ptr(out["num"]), engine._ptr(workspace),
+            workspace.numel(), engine._stream(device)))
+    return out
+
+
+def relocalize(centers, labels, lm, use=None, radius_in=None, radii=(2.0, DEFAULT_RADIUS), tau_z=DEFAULT_TAU_Z, tau_edge=0.5,
+               min_base=5.0, max_base=30.0, max_hyp=65536, min_inliers=12, sep=10.0, iters=10, min_nodes=6, workspace=None,
+               device=None):
+    """Relocalise Q scans in the landmark map `lm` with no prior pose: every pair of nodes of a scan is
+    laid on the pairs of landmarks of their labels that are as far apart, the pose with the most nodes on landmarks
+    wins, and it is refined through the gates `radii` (every stage an align of that scan).  `inliers_other` is the best
+    count among the poses more than `sep` metres from the winner: where it comes close to `inliers` the map repeats
+    itself there, and the answer is one of several.  Arguments as relocalize_async.
+    -> (poses f64 [Q,4] on the device, NaN for a scan that is not found; info dict of numpy arrays: found bool [Q],
+    inliers, inliers_other i32 [Q], coarse, other f64 [Q,4], win i32 [Q,4], hypotheses i64 [Q], matched, live, steps,
+    flags i32 [Q], rms f64 [Q], node_landmark i32 [Q,N], num i32 [4] = (scans found, scans truncated, scans without a
+    hypothesis, 0))."""
+    out = relocalize_async(centers, labels, lm, use=use, radius_in=radius_in, radii=radii, tau_z=tau_z, tau_edge=tau_edge,
+                           min_base=min_base, max_base=max_base, max_hyp=max_hyp, min_inliers=min_inliers, sep=sep, iters=iters,
+                           min_nodes=min_nodes, workspace=workspace, device=device)
+    stat = out["stat"].cpu().numpy()
+    return out["poses"], {"found": (stat[:, 5] & RELOC_FOUND) != 0, "inliers": stat[:, 0], "inliers_other": stat[:, 1],
+                          "coarse": out["coarse"].cpu().numpy(), "other": out["other"].cpu().numpy(),
+                          "win": out["win"].cpu().numpy(), "hypotheses": out["hypotheses"].cpu().numpy(), "matched": stat[:, 2],
+                          "live": stat[:, 3], "steps": stat[:, 4], "flags": stat[:, 5], "rms": out["rms"].cpu().numpy(),
                           "node_landmark": out["node_landmark"].cpu().numpy(), "num": out["num"].cpu().numpy()}
 
 

@@ -18,7 +18,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
     python -m sg_pr_amd.place_db config.yml [--k K] [--window W] [--causal] [--threshold T] [--hard K]
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
                                             [--verify] [--min-inliers I] [--consistent] [--distinct RHO] [--seq-slopes S,S,...]
-                                            [--sessions N] [--optimize] [--save-poses FILE] [--landmarks] [--track]
+                                            [--sessions N] [--optimize] [--save-poses FILE] [--landmarks] [--track] [--relocalize]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -122,6 +122,18 @@ lost, the longest run of lost scans and the median matched share; `<seq>_track.n
 steps, flags, lost, rms, node_landmark, num = (tracked, lost, longest lost run, tracks), init, from_localize, first_scan,
 session, radii, reacquire_radii, iters, min_matched, matched_share and the translation error against the sequence's own
 poses.  Without --track every output is as before.
+
+With --landmarks --sessions N --relocalize [--reloc-min-inliers I] [--reloc-max-base B] [--reloc-sep S] every scan of the
+last of the N sessions is RELOCALISED in the landmark map of the others with no pose at all (SG.relocalize_in_map,
+landmarks.relocalize): pairs of its nodes up to B metres apart (default 30) are laid on pairs of landmarks
+of their labels, the pose with the most nodes on landmarks wins, is found with I of them (default 12) and is refined
+through the gates of --align-radii (--align-iters rounds each); a scan is ambiguous when a pose more than S metres away
+(default 10) collects 0.7 of the winner's count.  Printed are the share found, the share ambiguous and the median and
+largest translation error of the found scans against the sequence's own poses; `<seq>_relocalize.npz` holds poses [Q,4],
+found, ambiguous, inliers, inliers_other, coarse, other, win, hypotheses, matched, live, steps, flags, rms, node_landmark,
+num = (found, truncated, without a hypothesis, 0), trans_m, first_scan, session and the parameters.  With --track and
+without --localize the track starts from the relocalised pose of the session's first scan when that scan is found and
+not ambiguous.  Without --relocalize every output is as before.
 """
 import argparse
 import math
@@ -470,6 +482,15 @@ def main(argv=None):
                     help="with --track: the gates run in front of them on the scan after a lost one (empty: none)")
     ap.add_argument("--min-matched", type=int, default=10, metavar="M",
                     help="with --track: a scan with fewer matches is lost and keeps its predicted pose")
+    ap.add_argument("--relocalize", action="store_true",
+                    help="with --landmarks --sessions N: relocalise every scan of the last session in the landmark map of the "
+                         "others with no prior pose (DESIGN.md §35); writes <seq>_relocalize.npz")
+    ap.add_argument("--reloc-min-inliers", type=int, default=12, metavar="I",
+                    help="with --relocalize: a scan is found when its best pose puts that many nodes on landmarks")
+    ap.add_argument("--reloc-max-base", type=float, default=30.0, metavar="B",
+                    help="with --relocalize: the largest distance of the two nodes of a hypothesis, metres")
+    ap.add_argument("--reloc-sep", type=float, default=10.0, metavar="S",
+                    help="with --relocalize: how far from the answer another place is, metres")
     ap.add_argument("--retire", action="store_true",
                     help="with --update: tally what the drive folded in should have seen of the updated map and what it saw, "
                          "and retire the landmarks it should have seen and did not (DESIGN.md §33); writes <seq>_persist.npz. "
@@ -563,10 +584,15 @@ def main(argv=None):
                 and opt.align_iters >= 0):
             ap.error("--track-radii and --reacquire-radii must be positive, at most %d gates together; --min-matched and "
                      "--align-iters >= 0" % TRACK_MAX_STAGES)
+    if opt.relocalize:
+        if not (opt.landmarks and opt.sessions is not None):
+            ap.error("--relocalize needs --landmarks and --sessions N")
+        if not (opt.reloc_min_inliers >= 2 and 5.0 <= opt.reloc_max_base < math.inf and opt.reloc_sep >= 0):
+            ap.error("--reloc-min-inliers must be >= 2, --reloc-max-base a finite number of metres >= 5, --reloc-sep >= 0")
     if opt.retire and not (opt.view_range >= 0 and 0 <= opt.view_margin < math.inf and opt.min_expected >= 0
                            and 0 <= opt.max_seen_ratio <= 1):
         ap.error("--view-range, --view-margin and --min-expected must be >= 0, --max-seen-ratio in 0..1")
-    if opt.align or opt.update:
+    if opt.align or opt.update or opt.relocalize:
         try:
             opt.align_radii = [float(t) for t in opt.align_radii.split(",") if t.strip()]
         except ValueError:
@@ -741,8 +767,27 @@ def main(argv=None):
                       % (int(preport["in_use_before"]), int(preport["in_use_after"]), int(preport["num"][0]), int(preport["num"][1]),
                          opt.min_expected, opt.max_seen_ratio),
                       "per-scan seen / expected %.4f (median)" % preport["scan_ratio_median"])
+        rreport = None
+        if opt.relocalize:
+            rreport = relocalize_lists(trainer.model, seq, opt.sessions, radii=opt.align_radii, iters=opt.align_iters,
+                                       min_inliers=opt.reloc_min_inliers, max_base=opt.reloc_max_base, sep=opt.reloc_sep,
+                                       radius=opt.lm_radius, tau_z=opt.lm_tau_z)
+            np.savez(os.path.join(args.output_path, sequence + "_relocalize.npz"), **rreport)
+            print("sequence", sequence, "session %d of %d relocalised in the landmark map of the others with no prior pose, base "
+                  "pairs up to %g m, %d inliers, gates %s m x %d iterations:"
+                  % (int(rreport["session"]), opt.sessions, opt.reloc_max_base, opt.reloc_min_inliers,
+                     ", ".join("%g" % r for r in opt.align_radii), opt.align_iters),
+                  "found %.4f, ambiguous %.4f of %d scans (another place beyond %g m with 0.7 of the inliers),"
+                  % (rreport["found"].mean() if rreport["found"].size else 0.0,
+                     rreport["ambiguous"].mean() if rreport["found"].size else 0.0, rreport["found"].shape[0], opt.reloc_sep),
+                  "translation of the found %.4f / %.4f m (median / max), hypotheses %d / %d (median / max)"
+                  % (rreport["median_trans_m"], rreport["max_trans_m"], int(np.median(rreport["hypotheses"])) if
+                     rreport["found"].size else 0, int(rreport["hypotheses"].max()) if rreport["found"].size else 0))
         if opt.track:
-            treport = track_lists(trainer.model, seq, opt.sessions, located=lreport if opt.localize else None,
+            seed = None
+            if rreport is not None and not opt.localize:
+                seed = relocalized_start(rreport, seq.labels.shape[0])
+            treport = track_lists(trainer.model, seq, opt.sessions, located=lreport if opt.localize else seed,
                                   radii=opt.track_radii, reacquire_radii=opt.reacquire_radii, iters=opt.align_iters,
                                   min_matched=opt.min_matched, radius=opt.lm_radius, tau_z=opt.lm_tau_z)
             np.savez(os.path.join(args.output_path, sequence + "_track.npz"), **treport)
@@ -754,7 +799,8 @@ def main(argv=None):
                   % (int(treport["num"][0]), int(treport["num"][1]), treport["lost"].shape[0], opt.min_matched,
                      int(treport["num"][2]), treport["matched_share"]),
                   "translation %.4f / %.4f m (median / 95%%), first pose from %s"
-                  % (treport["median_trans_m"], treport["p95_trans_m"], "localize" if treport["from_localize"] else "the stored pose"))
+                  % (treport["median_trans_m"], treport["p95_trans_m"], ("relocalize" if rreport is not None and not opt.localize else "localize") if treport["from_localize"]
+                     else "the stored pose"))
         if opt.distinct is not None:
             if opt.seq_len > 1:
                 dvals, didx, ddirs = db.query_ids_seq(0, m, opt.seq_len, k=k, window=opt.window, causal=opt.causal,
@@ -1115,6 +1161,47 @@ def track_lists(model, seq, sessions, located=None, radii=(2.0, 0.75), reacquire
     seen = info["live"] > 0
     out["matched_share"] = np.float64(np.median(info["matched"][seen] / info["live"][seen]) if seen.any() else 0.0)
     return out
+
+
+def relocalize_lists(model, seq, sessions, radii=(2.0, 0.75), iters=10, min_nodes=6, min_inliers=12, max_base=30.0, sep=10.0,
+                     ratio=0.7, radius=0.75, tau_z=0.75):
+    """The scans of the last of `sessions` consecutive near-equal sessions of `seq` (session_lists' split) relocalised in
+    the landmark map of the others with no prior pose (SG.relocalize_in_map): the map is built on the sequence's own
+    poses (SG.landmark_map), all of its landmarks take part.
+    -> dict of numpy arrays: poses f64 [Q,4] (NaN where not found), found, ambiguous bool [Q], inliers, inliers_other,
+    matched, live, steps, flags i32 [Q], coarse, other f64 [Q,4], win i32 [Q,4], hypotheses i64 [Q], rms f64 [Q],
+    node_landmark i32 [Q,N], num, trans_m f64 [Q] (against the sequence's own poses; NaN where not found), first_scan,
+    session, radii, iters, min_nodes, min_inliers, max_base, sep, ratio, median_trans_m / max_trans_m of the found scans."""
+    m = seq.labels.shape[0]
+    bounds = np.asarray([(j * m) // int(sessions) for j in range(int(sessions))], dtype=np.int32)
+    b, last = int(bounds[-1]), int(sessions) - 1
+    own = metrics.planar_odometry(seq.poses)
+    lm = model.landmark_map(seq.centers[:b], seq.labels[:b], own[:b], sessions=bounds[:-1], radius=radius, tau_z=tau_z)
+    X, info = model.relocalize_in_map(seq.centers[b:], seq.labels[b:], lm, radii=radii, iters=iters, min_nodes=min_nodes,
+                                      min_inliers=min_inliers, ratio=ratio, max_base=max_base, sep=sep, tau_z=tau_z)
+    X = X.cpu().numpy()
+    found = info["found"]
+    err = np.full(X.shape[0], np.nan)
+    if found.any():
+        err[found] = metrics.localization_errors(X[found], own[b:][found])["trans_m"]
+    out = {"poses": X, "trans_m": err, "first_scan": np.int64(b), "session": np.int64(last),
+           "radii": np.asarray(radii, dtype=np.float64), "iters": np.int64(iters), "min_nodes": np.int64(min_nodes),
+           "min_inliers": np.int64(min_inliers), "max_base": np.float64(max_base), "sep": np.float64(sep), "ratio": np.float64(ratio),
+           "median_trans_m": np.float64(np.median(err[found]) if found.any() else np.nan),
+           "max_trans_m": np.float64(err[found].max() if found.any() else np.nan)}
+    out.update({k: info[k] for k in ("found", "ambiguous", "inliers", "inliers_other", "coarse", "other", "win", "hypotheses",
+                                     "matched", "live", "steps", "flags", "rms", "node_landmark", "num")})
+    return out
+
+
+def relocalized_start(report, scans):
+    """relocalize_lists' dict as the `located` argument of track_lists: the session's first scan is given its relocalised
+    pose when it was found and is not ambiguous, no other scan is given one"""
+    b = int(report["first_scan"])
+    accept, pose = np.zeros(int(scans), dtype=bool), np.full((int(scans), 4), np.nan)
+    if report["found"].size and report["found"][0] and not report["ambiguous"][0]:
+        accept[b], pose[b] = True, report["poses"][0]
+    return {"accept": accept, "pose": pose}
 
 
 def persist_lists(model, seq, updated, max_range=50.0, margin=2.0, min_expected=5, max_seen_ratio=0.3, radius=0.75, min_count=3):

@@ -454,6 +454,34 @@ class SG(torch.nn.Module):
                                 max_shift=max_shift, start_lost=start_lost,
                                 tau_z=_landmarks.DEFAULT_TAU_Z if tau_z is None else tau_z, device=dev)
 
+    def relocalize_in_map(self, centers, labels, lm, use=None, radii=(2.0, 0.75), iters=10, min_nodes=6, min_inliers=12,
+                          ratio=0.7, radius_in=0.75, tau_edge=0.5, min_base=5.0, max_base=30.0, max_hyp=65536, sep=10.0,
+                          tau_z=None):
+        """Relocalise scans in a landmark map with NO prior pose (landmarks.relocalize): the answer to
+        "where am I?" from the landmarks alone - no scan of the map, no descriptor, no initial pose.  Every pair of nodes
+        of a scan min_base..max_base metres apart is laid on the pairs of landmarks of their labels whose distance agrees
+        within tau_edge; the pose under which the most nodes lie within radius_in of a landmark of their label wins, is
+        FOUND with min_inliers of them, and is refined through the gates `radii` (align_to_map's schedule, on that scan).
+        centers [Q,N,3], labels [Q,N]: the packed node arrays of the scans; lm: the dict of landmark_map or update_map;
+        use: a mask over its landmarks (landmarks.select; None: all) - it also restricts the search to a part of the
+        map; max_hyp: the hypotheses after which no further pair of nodes is started; sep: how many metres away another
+        place is.
+        A map that repeats itself - an avenue, a car park - answers with one of several places.  info["inliers_other"]
+        is the best count more than `sep` from the answer; a scan is AMBIGUOUS when inliers_other >= ratio * inliers.
+        A SCAN THAT IS AMBIGUOUS OR NOT FOUND MUST NOT SEED track_in_map (its `init`) AND MUST NOT BE FED TO
+        update_map: its pose is NaN or one candidate among equals; wait for a scan that is found and unambiguous.
+        -> (planar poses f64 [Q,4] device tensor, NaN where not found; info dict of numpy arrays: found, ambiguous bool
+        [Q], inliers, inliers_other, coarse, other [Q,4], win [Q,4], hypotheses, matched, live, steps, flags
+        (landmarks.RELOC_*), rms, node_landmark [Q,N], num = (scans found, scans truncated, scans without a hypothesis,
+        0))."""
+        from . import landmarks as _landmarks
+        x, info = _landmarks.relocalize(centers, labels, lm, use=use, radius_in=radius_in, radii=radii,
+                                        tau_z=_landmarks.DEFAULT_TAU_Z if tau_z is None else tau_z, tau_edge=tau_edge,
+                                        min_base=min_base, max_base=max_base, max_hyp=max_hyp, min_inliers=min_inliers, sep=sep,
+                                        iters=iters, min_nodes=min_nodes, device=self.engine().device)
+        info["ambiguous"] = info["found"] & (info["inliers_other"] >= float(ratio) * info["inliers"])
+        return x, info
+
     def update_map(self, centers, labels, poses, lm, session, node_base=None, radius=0.75, tau_z=None):
         """Fold the scans of a further drive into a landmark map (landmarks.update).  Every node is
         associated with the nearest landmark of its label within `radius` of the WHOLE map - one landmarks.align call

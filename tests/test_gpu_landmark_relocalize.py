@@ -1,0 +1,360 @@
+"""The relocalisation of scans in a landmark map on the GPU (sgpr_landmark_relocalize,
+include/sgpr_landmark_relocalize.h): poses, coarse, other, node_landmark, stat, win, hyp, rms and num equal
+to the NumPy definition (tests/landmark_relocalize_ref.py) to the bit - on the planted world, at the slot counts where a
+lane's share and the staging of a scan change, on every stage layout, at every rule of the definition and at the
+kernel's own structural points (a batch of hypotheses one short of full, full and one past it, more landmarks than one
+chunk of lanes, several j' per j, a base pair that contributes nothing, waves without a live node) - then the equality
+of the refinement with sgpr_landmark_align chained on the GPU, streams, the Python layer, SG.relocalize_in_map and the command line.
+Every output and the workspace are pre-filled with 0xFF, and the outputs carry a margin that must stay 0xFF."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import landmark_relocalize_ref as ref  # noqa: E402
+import landmark_track_ref as tref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+MARGIN = 5
+SHAPES = (("poses", 4, torch.float64), ("coarse", 4, torch.float64), ("other", 4, torch.float64), ("node_landmark", None, torch.int32),
+          ("stat", 8, torch.int32), ("win", 4, torch.int32), ("hyp", 1, torch.int64), ("rms", 1, torch.float64))
+
+
+def device_relocalize(centers, labels, lm_center, lm_label, lm_use=None, radius_in=0.75, radii=(2.0, 0.75), tau_z=0.75, tau_edge=0.5,
+                      min_base=5.0, max_base=30.0, max_hyp=65536, min_inliers=12, sep=10.0, iters=10, min_nodes=6, n_labels=None,
+                      stream=None):
+    """the C call with every output (and a margin behind it) and the workspace full of 0xFF; the inputs must come back
+    as they went in -> dict of host arrays"""
+    from sg_pr_amd import engine, landmarks
+    lib = landmarks.load_library()
+    dev = torch.device("cuda", 0)
+    lab = torch.as_tensor(np.ascontiguousarray(labels, np.int32)).to(dev)
+    Q, N = lab.shape
+    rows = [np.atleast_1d(np.asarray(r, np.float64)) for r in ([] if radii is None else radii)]
+    rin = np.atleast_1d(np.asarray(radius_in, np.float64))
+    if n_labels is None:
+        n_labels = max([r.size for r in rows + [rin] if r.size > 1], default=12)
+    rad_in = np.ascontiguousarray(ref.radius_table(rin, n_labels))
+    rad = np.ascontiguousarray(np.stack([ref.radius_table(r, n_labels) for r in rows])) if rows else None
+    S = len(rows)
+    host = {"centers": np.ascontiguousarray(centers, F32).reshape(Q, N, 3),
+            "lm_center": np.ascontiguousarray(lm_center, np.float64).reshape(-1, 3),
+            "lm_label": np.ascontiguousarray(lm_label, np.int32).reshape(-1)}
+    L = host["lm_label"].size
+    if lm_use is not None:
+        host["lm_use"] = np.ascontiguousarray(lm_use, np.uint8).reshape(L)
+    d = {k: torch.as_tensor(v).to(dev) for k, v in host.items()}
+
+    def dirty(n, dtype):
+        return torch.full((n,), -1, dtype=torch.int64 if dtype == torch.float64 else dtype, device=dev).view(dtype)
+
+    out = {k: dirty((Q * N if w is None else w * Q) + (MARGIN if w is None else w * MARGIN), t) for k, w, t in SHAPES}
+    out["num"] = dirty(4 + MARGIN, torch.int32)
+    need = landmarks.relocalize_workspace_bytes(Q, N, L, S)
+    assert need == ref.workspace_bytes(Q, N, L, S)
+    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev)
+    p = engine._ptr
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        rc = lib.sgpr_landmark_relocalize(
+            p(d["centers"]), p(lab), Q, N, p(d["lm_center"]) if L else None, p(d["lm_label"]) if L else None, p(d.get("lm_use")), L,
+            rad_in.ctypes.data, rad.ctypes.data if S else None, S, n_labels, float(tau_z), float(tau_edge), float(min_base),
+            float(max_base), int(max_hyp), int(min_inliers), float(sep), int(iters), int(min_nodes), p(out["poses"]), p(out["coarse"]),
+            p(out["other"]), p(out["node_landmark"]), p(out["stat"]), p(out["win"]), p(out["hyp"]), p(out["rms"]), p(out["num"]), p(ws),
+            need, engine._stream(dev))
+    assert rc == 0, lib.sgpr_last_error()
+    torch.cuda.synchronize()
+    for k, v in host.items():                                    # no output overlaps an input: they are what they were
+        assert d[k].cpu().numpy().tobytes() == v.tobytes(), k + " was written"
+    assert lab.cpu().numpy().tobytes() == np.ascontiguousarray(labels, np.int32).tobytes()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def same(got, want, Q, N):
+    """the outputs equal the reference to the bit (NaN as NaN: bytes), nothing written past them"""
+    for name, w, _ in SHAPES + (("num", None, None),):
+        n = 4 if name == "num" else (Q * N if w is None else w * Q)
+        assert got[name][:n].tobytes() == want[name].tobytes(), (name, got[name][:n], want[name].reshape(-1))
+        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+
+
+def check(w, stream=None, **over):
+    """a world dict of the reference through the call and the reference"""
+    kw = dict(w["kw"])
+    lm_use = over.pop("lm_use", w.get("lm_use"))
+    kw.update(over)
+    args = (w["centers"], w["labels"], w["lm"], w["lm_label"], lm_use)
+    got = device_relocalize(*args, stream=stream, **kw)
+    want = ref.relocalize(*args, **kw)
+    same(got, want, *w["labels"].shape)
+    return want
+
+
+@pytest.fixture(scope="module")
+def world():
+    """the recipe of DESIGN.md §34 / §35 on seed 0 cut to 70 scans per drive: the map of drives 0 and 1 at the true
+    poses, its landmarks with three or more observations, and 8 scans of drive 2 as queries"""
+    p = tref.planted_drive(0, scans=70)
+    idx = np.arange(0, 70, 9)
+    return {"centers": p["centers"][idx], "labels": p["labels"][idx], "truth": p["truth"][idx], "lm": p["lm"]["center"],
+            "lm_label": p["lm"]["label"], "lm_use": p["use"], "kw": {}}
+
+
+# ------------------------------------------------------------------ the planted world
+@pytest.mark.parametrize("masked", [True, False])
+def test_world(world, masked):
+    want = check(world) if masked else check(world, lm_use=None)
+    found = (want["stat"][:, 5] & ref.FOUND) != 0
+    err = np.hypot(want["poses"][:, 2] - world["truth"][:, 2], want["poses"][:, 3] - world["truth"][:, 3])
+    assert found.sum() >= 7 and err[found].max() < 0.5 and want["num"][0] == found.sum()
+
+
+@pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 100, 256, 257, 300])
+def test_slot_counts(world, N):
+    """a lane's share of the refinement changes at 64 and 128 slots; a scan is staged in the LDS up to 256 slots and
+    read from global memory past that, its live slots then kept in the workspace"""
+    w = dict(world)
+    Q = 3
+    cen, lab = np.zeros((Q, N, 3), F32), np.full((Q, N), -1, np.int32)
+    n = min(N, 100)
+    at = np.sort(np.random.default_rng(N).permutation(N)[:n])    # the scan's slots spread over the N
+    cen[:, at], lab[:, at] = world["centers"][:Q, :n], world["labels"][:Q, :n]
+    w["centers"], w["labels"] = cen, lab
+    want = check(w, min_inliers=min(12, max(2, n // 8)))
+    if N >= 100:
+        assert ((want["stat"][:, 5] & ref.FOUND) != 0).all()
+
+
+@pytest.mark.parametrize("radii", [(), (0.75,), (2.0, 0.75), (8.0, 4.0, 2.0, 0.75)])
+def test_stage_layouts_and_no_iterations(world, radii):
+    w = {k: (v[:3] if k in ("centers", "labels", "truth") else v) for k, v in world.items()}
+    want = check(w, radii=radii)
+    assert ((want["stat"][:, 5] & ref.FOUND) != 0).all()
+    if not radii:
+        assert want["poses"].tobytes() == want["coarse"].tobytes() and (want["stat"][:, 0] == want["stat"][:, 2]).all()
+    else:
+        zero = check(w, radii=radii, iters=0)
+        assert zero["poses"].tobytes() == zero["coarse"].tobytes() and (zero["stat"][:, 4] == 0).all()
+
+
+@pytest.mark.parametrize("max_hyp", [1, 50, 500, 1 << 20])
+def test_the_cap_on_the_world(world, max_hyp):
+    want = check(world, max_hyp=max_hyp)
+    cut = (want["stat"][:, 5] & ref.TRUNCATED) != 0
+    assert cut.all() if max_hyp <= 50 else not cut.any()
+
+
+def test_nothing_found_and_the_separation(world):
+    want = check(world, min_inliers=90)
+    assert want["num"].tolist() == [0, 0, 0, 0] and np.isnan(want["poses"]).all() and not np.isnan(want["coarse"]).any()
+    assert ((want["node_landmark"] == -2) == (world["labels"] >= 0)).all()
+    near = check(world, sep=0.0)
+    far = check(world, sep=np.inf)
+    assert (far["stat"][:, 1] == 0).all() and np.isnan(far["other"]).all() and (near["stat"][:, 1] >= check(world)["stat"][:, 1]).all()
+
+
+def test_a_label_of_radius_zero_in_one_stage(world):
+    r = np.full(12, 0.75)
+    r[int(np.bincount(world["labels"][world["labels"] >= 0]).argmax())] = 0.0
+    want = check(world, radii=(2.0, r))
+    base = check(world)
+    assert (want["stat"][:, 3] < base["stat"][:, 3]).all() and want["coarse"].tobytes() == base["coarse"].tobytes()
+    assert want["poses"].tobytes() != base["poses"].tobytes()
+    check(world, radii=(np.where(r > 0, 2.0, 0.0), 0.75))
+
+
+def test_no_landmarks_and_few(world):
+    for L in (0, 1, 2):
+        w = dict(world)
+        w["lm"], w["lm_label"], w["lm_use"] = world["lm"][:L], world["lm_label"][:L], None
+        want = check(w)
+        assert want["num"][0] == 0
+        if L < 2:
+            assert want["num"].tolist() == [0, 0, 8, 0]
+
+
+# ------------------------------------------------------------------ the rules, on the hand-made cases of the host test
+@pytest.mark.parametrize("name", sorted(ref.hand_cases()))
+def test_hand_made_cases(name):
+    w, over = ref.hand_cases()[name]
+    check(w, **over)
+
+
+@pytest.mark.parametrize("name", sorted(ref.mutant_cases()))
+def test_mutant_cases(name):
+    """the cases on which the host test shows every mutant of the definition to change an output: a kernel with one of
+    those faults differs from the reference here"""
+    w, over = ref.mutant_cases()[name]
+    check(w, **over)
+
+
+def test_lattice_cap_and_separation_boundaries():
+    la = ref.lattice_world()
+    caps, m = [], 1
+    for _ in range(6):                                           # C_1 .. C_6: the count after every base pair
+        caps.append(int(ref.run(la, max_hyp=m)["hyp"][0]))
+        m = caps[-1] + 1
+    assert caps == sorted(set(caps))
+    for c in caps:
+        for max_hyp in (c, c + 1):
+            check(la, max_hyp=max_hyp)
+    at, past = check(la, sep=8.0), check(la, sep=ref.down(8.0))
+    assert at["other"].tobytes() != past["other"].tobytes() or at["stat"][0, 1] != past["stat"][0, 1]
+
+
+# ------------------------------------------------------------------ the kernel's structural points
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 255, 256, 257, 511, 512, 513, 600])
+def test_batches_of_hypotheses(n):
+    """one base pair with exactly n hypotheses, one per landmark j: a batch one short of an evaluation, exactly one, one
+    past it; a second chunk of lanes; a last flush of a few; fewer hypotheses than waves"""
+    want = check(ref.line_world(n))
+    assert want["hyp"][0] == n and want["win"][0].tolist() == [0, 1, 0, 1] and want["stat"][0, 6] == 1
+    if n in (257, 513):
+        check(ref.line_world(n), max_hyp=n - 1)
+        check(ref.line_world(n), sep=150.0, min_inliers=2)
+
+
+def test_many_candidates_per_lane_and_a_full_chunk():
+    """400 landmarks of one label: two chunks of j, several j' per j, batches that fill in the middle of a round"""
+    w = ref.dense_world()
+    want = check(w)
+    assert want["hyp"][0] > 5000 and want["stat"][0, 5] & ref.FOUND
+    assert np.hypot(want["poses"][0, 2] - w["truth"][2], want["poses"][0, 3] - w["truth"][3]) < 1e-3
+    check(w, max_hyp=3000)
+    use = np.ones(400, np.uint8)
+    use[::3] = 0
+    check(w, lm_use=use, radii=())
+
+
+def test_empty_waves_and_a_base_pair_that_contributes_nothing():
+    """live nodes in slots 0..2 and 200..202 only: waves 1 and 2 stage and compact nothing; label 1 has no landmark, so
+    the base pairs that end on it are started and add nothing"""
+    la = ref.lattice_world(N=256)
+    cen, lab = la["centers"].copy(), la["labels"].copy()
+    cen[0, 200:202], lab[0, 200:202] = cen[0, 2:4], 0
+    cen[0, 202], lab[0, 202] = (4.0, 4.0, 0.0), 1
+    cen[0, 2:4], lab[0, 2:4] = 0, -1
+    la["centers"], la["labels"] = cen, lab
+    want = check(la, n_labels=2)
+    assert want["win"][0].tolist() == [0, 1, 0, 6] and want["stat"][0, 6] > 6 and want["stat"][0, 3] == 5
+
+
+# ------------------------------------------------------------------ refinement is alignment; streams; the Python layer
+def test_refinement_is_the_alignment_chained_on_the_gpu(world):
+    from sg_pr_amd import landmarks
+    got = device_relocalize(world["centers"][:2], world["labels"][:2], world["lm"], world["lm_label"], world["lm_use"])
+    lm = {"center": torch.as_tensor(world["lm"]).cuda(), "label": torch.as_tensor(world["lm_label"]).cuda()}
+    X, steps = got["coarse"][:8].reshape(2, 4), 0
+    for r in (2.0, 0.75):
+        X, info = landmarks.align(world["centers"][:2], world["labels"][:2], X, lm, use=world["lm_use"], radius=r, iters=10, min_nodes=6)
+        steps = steps + info["steps"]
+    assert got["poses"][:8].tobytes() == X.cpu().numpy().tobytes() and got["rms"][:2].tobytes() == info["rms"].tobytes()
+    assert got["node_landmark"][:200].tobytes() == info["node_landmark"].tobytes()
+    st = got["stat"][:16].reshape(2, 8)
+    assert st[:, 2].tolist() == info["matched"].tolist() and st[:, 4].tolist() == steps.tolist() and (st[:, 5] & ref.FOUND).all()
+
+
+def test_two_streams_two_dirty_workspaces(world):
+    args = (world["centers"], world["labels"], world["lm"], world["lm_label"], world["lm_use"])
+    outs = [device_relocalize(*args, stream=torch.cuda.Stream(), max_hyp=300) for _ in range(2)]
+    want = ref.relocalize(*args, max_hyp=300)
+    for o in outs:
+        same(o, want, 8, 100)
+
+
+def test_python_layer_and_a_short_workspace(world):
+    from sg_pr_amd import landmarks
+    lm = {"center": world["lm"], "label": world["lm_label"]}
+    X, info = landmarks.relocalize(world["centers"], world["labels"], lm, use=world["lm_use"])
+    want = ref.relocalize(world["centers"], world["labels"], world["lm"], world["lm_label"], world["lm_use"])
+    assert X.is_cuda and X.cpu().numpy().tobytes() == want["poses"].tobytes()
+    for k, j in (("inliers", 0), ("inliers_other", 1), ("matched", 2), ("live", 3), ("steps", 4), ("flags", 5)):
+        assert info[k].tolist() == want["stat"][:, j].tolist(), k
+    assert info["found"].tolist() == ((want["stat"][:, 5] & ref.FOUND) != 0).tolist() and info["num"].tolist() == want["num"].tolist()
+    for k, r in (("coarse", "coarse"), ("other", "other"), ("win", "win"), ("hypotheses", "hyp"), ("rms", "rms"), ("node_landmark", "node_landmark")):
+        assert info[k].tobytes() == want[r].tobytes(), k
+    assert (landmarks.RELOC_FOUND, landmarks.RELOC_KEPT, landmarks.RELOC_TRUNCATED, landmarks.RELOC_NO_HYPOTHESIS) == (1, 2, 4, 8)
+    out = landmarks.relocalize_async(world["centers"], world["labels"], lm, radii=None, radius_in=[0.75] * 12, max_hyp=100)
+    want = ref.relocalize(world["centers"], world["labels"], world["lm"], world["lm_label"], radii=(), max_hyp=100)
+    assert all(out[k].cpu().numpy().tobytes() == want[r].tobytes() for k, r in (("poses", "poses"), ("stat", "stat"), ("hypotheses", "hyp"), ("num", "num")))
+    short = torch.empty(landmarks.relocalize_workspace_bytes(8, 100, lm["label"].size, 2) - 1, dtype=torch.uint8, device="cuda")
+    with pytest.raises(Exception, match="workspace"):
+        landmarks.relocalize_async(world["centers"], world["labels"], lm, workspace=short)
+    with pytest.raises(Exception, match="n_stages"):
+        landmarks.relocalize_async(world["centers"], world["labels"], lm, radii=[1.0] * 17)
+    none = landmarks.relocalize_async(np.zeros((0, 100, 3), F32), np.zeros((0, 100), np.int32), lm)
+    assert none["poses"].shape == (0, 4) and none["num"].tolist() == [0, 0, 0, 0]
+
+
+@pytest.fixture(scope="module")
+def model(ckpt_path):
+    from sg_pr_amd import sg_net
+    from sg_pr_amd.parser_sg import sgpr_args
+    args = sgpr_args()
+    args.model = ckpt_path
+    trainer = sg_net.SGTrainer(args, False)
+    trainer.model.eval()
+    return trainer.model
+
+
+def test_relocalize_in_map_and_the_aliased_map(model, world):
+    lm = {"center": world["lm"], "label": world["lm_label"]}
+    X, info = model.relocalize_in_map(world["centers"], world["labels"], lm, use=world["lm_use"])
+    want = ref.relocalize(world["centers"], world["labels"], world["lm"], world["lm_label"], world["lm_use"])
+    assert X.cpu().numpy().tobytes() == want["poses"].tobytes() and not info["ambiguous"].any() and info["found"].sum() >= 7
+    al = ref.aliased_map()
+    amap = {"center": al["lm"], "label": al["lm_label"]}
+    X, info = model.relocalize_in_map(al["centers"], al["labels"], amap, min_inliers=8)
+    assert info["found"][0] and info["ambiguous"][0] and info["inliers"][0] == 14 and info["inliers_other"][0] == 13
+    assert abs(info["other"][0, 2] - info["coarse"][0, 2] - al["gap"]) < 1e-6
+    assert np.hypot(*(X.cpu().numpy()[0, 2:] - al["truth"][2:])) < 0.05
+    masked = np.ones(27, bool)
+    masked[14:] = False
+    X, info = model.relocalize_in_map(al["centers"], al["labels"], amap, use=masked, min_inliers=8)
+    assert info["found"][0] and not info["ambiguous"][0] and info["inliers_other"][0] == 3
+    doc = model.relocalize_in_map.__doc__
+    assert "track_in_map" in doc and "update_map" in doc and "AMBIGUOUS" in doc
+
+
+def test_place_db_relocalize_cli(model, tmp_path, ckpt_path, capsys):
+    """--landmarks --sessions 3 --relocalize --track: the file holds the reference's relocalisation of the last session
+    in the reference's map of the first two, and the track starts from the first scan's relocalised pose"""
+    import landmark_ref as lref
+    from sg_pr_amd import graph_store, metrics, place_db, synth
+    centers, labels, _, poses = synth.world_sequence(90, 100, seed=4)
+    seq = graph_store.PackedSequence(centers, labels, poses, ["%d.json" % j for j in range(90)])
+    os.makedirs(tmp_path / "eva")
+    seq.save(str(tmp_path / "eva" / "07_packed.npz"))
+    cfg = tmp_path / "config.yml"
+    cfg.write_text("""
+common: {model: "%s", cuda: "0", batch_size: 128, p_thresh: 3, graph_pairs_dir: "%s", pair_list_dir: '%s'}
+arch: {keep_node: 1, filters_1: 64, filters_2: 64, filters_3: 32, tensor_neurons: 16, bottle_neck_neurons: 16, K: 10}
+train: {epochs: 500, train_sequences: ['00'], eval_sequences: ["08"], dropout: 0, learning_rate: 0.001,
+        weight_decay: 0.0005, gpu: 0, logdir: "./logs_k10", node_num: 100}
+eva_batch: {sequences: ["07"], output_path: "%s", show: False}
+eva_pair: {pair_file: ["a.json", "b.json"]}
+""" % (ckpt_path, tmp_path / "graphs", tmp_path, tmp_path / "eva"))
+    place_db.main([str(cfg), "--window", "30", "--landmarks", "--sessions", "3", "--relocalize", "--reloc-min-inliers", "10",
+                   "--reloc-max-base", "25", "--reloc-sep", "8", "--align-radii", "1.5,0.75", "--align-iters", "4", "--track"])
+    lines = capsys.readouterr().out.splitlines()
+    own = metrics.planar_odometry(poses)
+    m = lref.landmark_map(centers[:60], labels[:60], own[:60], starts=[0, 30])
+    want = ref.relocalize(centers[60:], labels[60:], m["center"], m["label"], radii=(1.5, 0.75), iters=4, min_inliers=10, max_base=25.0,
+                          sep=8.0)
+    z = np.load(tmp_path / "eva" / "07_relocalize.npz")
+    for k, r in (("poses", "poses"), ("coarse", "coarse"), ("other", "other"), ("win", "win"), ("hypotheses", "hyp"), ("rms", "rms"),
+                 ("node_landmark", "node_landmark"), ("num", "num")):
+        assert z[k].tobytes() == want[r].tobytes(), k
+    assert np.stack([z[k] for k in ("inliers", "inliers_other", "matched", "live", "steps", "flags")], axis=1).tolist() == want["stat"][:, :6].tolist()
+    assert z["found"].all() and not z["ambiguous"].any() and int(z["first_scan"]) == 60 and np.nanmax(z["trans_m"]) < 0.2
+    line = [ln for ln in lines if "relocalised" in ln]
+    assert len(line) == 1 and "found 1.0000, ambiguous 0.0000 of 30 scans" in line[0]
+    t = np.load(tmp_path / "eva" / "07_track.npz")
+    assert bool(t["from_localize"]) and t["init"].tobytes() == want["poses"][:1].tobytes()
+    assert any("first pose from relocalize" in ln for ln in lines)
+    with pytest.raises(SystemExit):
+        place_db.main([str(cfg), "--relocalize"])
