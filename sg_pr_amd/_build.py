@@ -25,7 +25,8 @@ SOURCES = ["sgpr_embed.hip", "sgpr_score.hip", "sgpr_metrics.hip", "sgpr_modules
            "sgpr_generic.hip", "sgpr_wide.hip", "sgpr_prep.hip", "sgpr_train.hip", "sgpr_train_pairs.hip", "sgpr_select.hip",
            "sgpr_seq.hip", "sgpr_peak.hip", "sgpr_verify.hip", "sgpr_consistency.hip", "sgpr_api.hip", "sgpr_posegraph.hip",
            "sgpr_localize.hip", "sgpr_landmarks.hip", "sgpr_landmark_refine.hip", "sgpr_landmark_align.hip",
-           "sgpr_landmark_update.hip", "sgpr_landmark_persist.hip", "sgpr_landmark_track.hip", "sgpr_landmark_relocalize.hip"]
+           "sgpr_landmark_update.hip", "sgpr_landmark_persist.hip", "sgpr_landmark_track.hip", "sgpr_landmark_relocalize.hip",
+           "sgpr_landmark_merge.hip"]
 HEADERS = [os.path.join(REPO, "include", "sgpr.h"), os.path.join(CSRC, "sgpr_internal.hpp"),
            os.path.join(CSRC, "sgpr_model.hpp"), os.path.join(CSRC, "sgpr_map.hpp"), os.path.join(CSRC, "sgpr_eval.hpp"),
            os.path.join(REPO, "include", "sgpr_localize.h"), os.path.join(REPO, "include", "sgpr_landmarks.h"),
@@ -33,7 +34,7 @@ HEADERS = [os.path.join(REPO, "include", "sgpr.h"), os.path.join(CSRC, "sgpr_int
            os.path.join(REPO, "include", "sgpr_landmark_update.h"), os.path.join(CSRC, "sgpr_landmark_core.hpp"),
            os.path.join(REPO, "include", "sgpr_landmark_persist.h"), os.path.join(CSRC, "sgpr_landmark_align_core.hpp"),
            os.path.join(REPO, "include", "sgpr_landmark_track.h"), os.path.join(REPO, "include", "sgpr_landmark_relocalize.h"),
-           os.path.join(REPO, "include", "sgpr_posegraph.h")]
+           os.path.join(REPO, "include", "sgpr_landmark_merge.h"), os.path.join(REPO, "include", "sgpr_posegraph.h")]
 MAX_COMPILERS = 16     # compilers at once: one per source, up to this many
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed"]
 

@@ -3,10 +3,11 @@ the refinement of the poses on that map (include/sgpr_landmark_refine.h, DESIGN.
 scans to it (include/sgpr_landmark_align.h), the folding of aligned scans into it
 (include/sgpr_landmark_update.h), the tallies of what a drive should have seen of it and did see
 (include/sgpr_landmark_persist.h), the tracking of a drive through it, scan by scan
-(include/sgpr_landmark_track.h) and the relocalisation of a scan in it with no prior pose
-(include/sgpr_landmark_relocalize.h).
+(include/sgpr_landmark_track.h), the relocalisation of a scan in it with no prior pose
+(include/sgpr_landmark_relocalize.h) and the joining and compaction of maps on their records alone
+(include/sgpr_landmark_merge.h).
 
-The entry points are declared in the fourth to tenth public headers; this module has engine.bind_header parse them and
+The entry points are declared in the fourth to eleventh public headers; this module has engine.bind_header parse them and
 set the signatures on the library engine.load_library() returns - there is no table of them in Python.  No CPU fallback.
 """
 import os
@@ -44,6 +45,8 @@ _R = _RELOC_ABI.constants
 RELOC_MAX_STAGES = _R["SGPR_RELOC_MAX_STAGES"]
 RELOC_FOUND, RELOC_KEPT, RELOC_TRUNCATED, RELOC_NO_HYPOTHESIS = (
     _R["SGPR_RELOC_" + k] for k in ("FOUND", "KEPT", "TRUNCATED", "NO_HYPOTHESIS"))          # flags of a relocalised scan
+MERGE_HEADER = os.path.join(_build.REPO, "include", "sgpr_landmark_merge.h")
+MERGE_ABI_SYMBOLS = [name for name, _, _ in engine.public_header(os.path.basename(MERGE_HEADER)).functions]
 MAX_LABELS = _C["SGPR_LANDMARK_MAX_LABELS"]
 DEFAULT_RADIUS, DEFAULT_TAU_Z = 0.75, 0.75
 DEFAULT_MAX_LANDMARKS = 1 << 22          # the default capacity is G N, capped here; build() re-runs past it
@@ -53,7 +56,7 @@ _CHUNK_BYTES = 1 << 28                   # virtual_scans: the largest Q x L floa
 def load_library():
     """engine.load_library() with the signatures of include/sgpr_landmarks.h, include/sgpr_landmark_refine.h,
     include/sgpr_landmark_align.h, include/sgpr_landmark_update.h, include/sgpr_landmark_persist.h,
-    include/sgpr_landmark_track.h and include/sgpr_landmark_relocalize.h set on it"""
+    include/sgpr_landmark_track.h, include/sgpr_landmark_relocalize.h and include/sgpr_landmark_merge.h set on it"""
     engine.bind_header(os.path.basename(HEADER))
     engine.bind_header(os.path.basename(REFINE_HEADER))
     engine.bind_header(os.path.basename(ALIGN_HEADER))
@@ -61,6 +64,7 @@ def load_library():
     engine.bind_header(os.path.basename(PERSIST_HEADER))
     engine.bind_header(os.path.basename(TRACK_HEADER))
     engine.bind_header(os.path.basename(RELOCALIZE_HEADER))
+    engine.bind_header(os.path.basename(MERGE_HEADER))
     return engine.load_library()
 
 
@@ -598,6 +602,135 @@ def update(centers, labels, poses, assoc, lm, starts=None, session_base=0, node_
     res["node_landmark"] = out["node_landmark"]
     res["num_landmarks"], res["live_nodes"], res["observed"], res["new_nodes"] = found, live, seen, new
     return res
+
+
+def merge_workspace_bytes(L_a, L_b=0):
+    return int(load_library().sgpr_landmark_merge_workspace_bytes(int(L_a), int(L_b)))
+
+
+def _records_on(lm, device, who):
+    """the six record arrays of a map dict on `device`, in the ABI's types -> (dict, L)"""
+    rec = {k: engine._on(lm[k].view(np.int64) if isinstance(lm[k], np.ndarray) and lm[k].dtype == np.uint64 else lm[k], device, t)
+           for k, t in _RECORD}                                     # (a uint64 host mask: its bits)
+    n_lm = int(rec["label"].numel())
+    if rec["center"].numel() != 3 * n_lm or any(rec[k].numel() != n_lm for k, _ in _RECORD[1:]):
+        raise ValueError("%s: a map must hold center [L,3] and label, count, first, sessions, spread [L]" % who)
+    return rec, n_lm
+
+
+def _keep_on(keep, n_lm, device, who):
+    if keep is None:
+        return None
+    mask = engine._on(torch.as_tensor(keep).reshape(-1) != 0, device, torch.bool).to(torch.uint8)
+    if mask.numel() != n_lm:
+        raise ValueError("%s: a keep mask must hold one entry per landmark of its map" % who)
+    return mask
+
+
+def merge_async(a, b=None, keep_a=None, keep_b=None, pose=None, session_shift=0, first_base=0, radius=DEFAULT_RADIUS,
+                tau_z=None, max_landmarks=None, workspace=None, device=None):
+    """sgpr_landmark_merge without reading anything back -> dict of device tensors, asynchronous on the current stream: the
+    six record arrays of the merged map with max_landmarks rows (center f64 [.,3], label, count, first i32, sessions i64,
+    spread f64), old_to_new i32 [L_a + L_b] (the new id of every input record - A's first, then B's - or -1 of a dropped
+    one), num i32 [4] = (landmarks of the merged map, records dropped by a keep mask, kept records dropped as
+    ineligible, landmarks fused from more than one record).  Only the first min(num[0], max_landmarks) records are
+    written.  a, b: the dicts of build / update / merge (their six records; b None: a is compacted); keep_a, keep_b: masks
+    over their landmarks, 0 = drop (persist's keep; None: keep all); pose: planar (c, s, X, Y) that carries b's frame
+    into a's (None: b's centres are taken bit for bit); session_shift: b's session bits move up by this many (a bit
+    shifted out is lost here - merge raises); first_base: added to b's `first`; radius, tau_z: the link rule among the
+    records, as build takes them; max_landmarks: default L_a + L_b, capped at DEFAULT_MAX_LANDMARKS.  workspace: a uint8
+    device tensor of at least merge_workspace_bytes(L_a, L_b) to reuse.  The inputs are left as they are."""
+    lib = load_library()
+    who = "landmarks.merge"
+    if device is None:
+        device = engine._device_of(a["center"], None if b is None else b["center"])
+    rec_a, n_a = _records_on(a, device, who)
+    rec_b, n_b = _records_on(b, device, who) if b is not None else (None, 0)
+    mask_a = _keep_on(keep_a, n_a, device, who)
+    mask_b = _keep_on(keep_b, n_b, device, who) if b is not None else None
+    x = None
+    if pose is not None:
+        x = np.ascontiguousarray(np.asarray(pose.detach().cpu() if isinstance(pose, torch.Tensor) else pose, dtype=np.float64).reshape(-1))
+        if x.size != 4:
+            raise ValueError("landmarks.merge: pose must be one planar pose (c, s, x, y)")
+    rad = _radius_table(radius)
+    total = n_a + n_b
+    cap = min(total, DEFAULT_MAX_LANDMARKS) if max_landmarks is None else int(max_landmarks)
+    rows = max(cap, 0)
+    out = {k: torch.empty((rows, 3) if k == "center" else (rows,), dtype=t, device=device) for k, t in _RECORD}
+    out["old_to_new"] = torch.full((total,), -1, dtype=torch.int32, device=device)
+    out["num"] = torch.zeros(4, dtype=torch.int32, device=device)       # (L_a + L_b == 0: the call writes nothing)
+    need = merge_workspace_bytes(n_a, n_b)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    elif workspace.device != device or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError("landmarks.merge: the workspace must be a contiguous uint8 tensor on %s" % (device,))
+    with torch.cuda.device(device):
+        engine._check(lib.sgpr_landmark_merge(
+            *[engine._ptr(rec_a[k]) if n_a else None for k, _ in _RECORD], engine._ptr(mask_a) if n_a else None, n_a,
+            *[engine._ptr(rec_b[k]) if n_b else None for k, _ in _RECORD], engine._ptr(mask_b) if n_b else None, n_b,
+            None if x is None else x.ctypes.data, int(session_shift), int(first_base), rad.ctypes.data, rad.shape[0],
+            float(DEFAULT_TAU_Z if tau_z is None else tau_z), cap, *[engine._ptr(out[k]) if rows else None for k, _ in _RECORD],
+            engine._ptr(out["old_to_new"]), engine._ptr(out["num"]), engine._ptr(workspace), workspace.numel(),
+            engine._stream(device)))
+    return out
+
+
+def merge(a, b=None, keep_a=None, keep_b=None, pose=None, session_shift=0, first_base=0, radius=DEFAULT_RADIUS, tau_z=None,
+          max_landmarks=None, workspace=None, device=None):
+    """Join the landmark maps `a` and `b` on their records alone: what a keep mask drops is gone, records
+    of one label within `radius` (and tau_z in height) fuse as if their observations had been fused - inside a, inside b
+    and across - and the result is numbered densely, by the lowest input record of every landmark.  Arguments as
+    merge_async.  Raises ValueError when session_shift would push a session bit of any record of b out of the 64-bit mask.
+    -> the dict of build - center, label, count, first, sessions, spread trimmed to the landmarks of the merged map,
+    num_landmarks - plus old_to_new i32 [L_a + L_b] on the device (-1 = dropped; remap carries a node_landmark array
+    through it), dropped = (by a keep mask, as ineligible) and fused (landmarks made of more than one record); select,
+    align, update, persist, track, relocalize and virtual_scans take it as they take build's.  It holds no node_landmark:
+    the node arrays are not read.  If max_landmarks was too small the call is repeated once with the reported count."""
+    shift = int(session_shift)
+    if b is not None and 0 < shift < 64:
+        sess = torch.as_tensor(b["sessions"].view(np.int64) if isinstance(b["sessions"], np.ndarray) and
+                               b["sessions"].dtype == np.uint64 else b["sessions"]).to(torch.int64)
+        if sess.numel() and bool(((sess >> (64 - shift)) != 0).any()):
+            raise ValueError("landmarks.merge: session_shift %d shifts a session bit of b out of the 64-bit mask" % shift)
+    kw = dict(keep_a=keep_a, keep_b=keep_b, pose=pose, session_shift=session_shift, first_base=first_base, radius=radius,
+              tau_z=tau_z, workspace=workspace, device=device)
+    out = merge_async(a, b, max_landmarks=max_landmarks, **kw)
+    found, masked, unfit, fused = (int(v) for v in out["num"].tolist())
+    if found > out["label"].shape[0]:
+        out = merge_async(a, b, max_landmarks=found, **kw)
+    res = {k: out[k][:found] for k, _ in _RECORD}
+    res["old_to_new"] = out["old_to_new"]
+    res["num_landmarks"], res["dropped"], res["fused"] = found, (masked, unfit), fused
+    return res
+
+
+def compact(lm, keep=None, radius=DEFAULT_RADIUS, tau_z=None, max_landmarks=None, workspace=None, device=None):
+    """merge with no second map: the landmarks `keep` drops (None: none) and the ineligible ones are removed, duplicates
+    within `radius` fuse, the rest keep their order and their bits -> as merge"""
+    return merge(lm, None, keep_a=keep, radius=radius, tau_z=tau_z, max_landmarks=max_landmarks, workspace=workspace, device=device)
+
+
+def remap(node_landmark, old_to_new):
+    """Carry a node_landmark array (of build, align, update, track or relocalize; any shape) through merge's old_to_new
+    table: an id >= 0 becomes its new id, or -2 - "the map does not explain this node" - where its landmark was dropped;
+    -1 and -2 stay.  For the nodes of map b the ids are first raised by L_a by the caller.  -> int32, a tensor on
+    node_landmark's device when that is a tensor, else a numpy array."""
+    if isinstance(node_landmark, torch.Tensor):
+        node = node_landmark.to(torch.int64)
+        table = torch.as_tensor(old_to_new).to(device=node.device, dtype=torch.int64).reshape(-1)
+        if table.numel() == 0:
+            return torch.where(node >= 0, torch.full_like(node, -2), node).to(torch.int32)
+        new = table[node.clamp(0, table.numel() - 1)]
+        new = torch.where(new >= 0, new, torch.full_like(new, -2))
+        return torch.where((node >= 0) & (node < table.numel()), new, torch.where(node >= 0, torch.full_like(node, -2), node)).to(torch.int32)
+    node = np.asarray(node_landmark).astype(np.int64)
+    table = np.asarray(old_to_new.cpu() if isinstance(old_to_new, torch.Tensor) else old_to_new).astype(np.int64).reshape(-1)
+    out = np.where(node >= 0, -2, node)
+    inside = (node >= 0) & (node < table.size)
+    new = table[node[inside]]
+    out[inside] = np.where(new >= 0, new, -2)
+    return out.astype(np.int32)
 
 
 def persist_workspace_bytes(Q, N, L):

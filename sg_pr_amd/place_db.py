@@ -19,6 +19,7 @@ the architecture and a sha256 of the checkpoint's weight blob: vectors of one ch
                                             [--recall-percent P] [--seq-len L] [--seq-reverse {off,on,both}]
                                             [--verify] [--min-inliers I] [--consistent] [--distinct RHO] [--seq-slopes S,S,...]
                                             [--sessions N] [--optimize] [--save-poses FILE] [--landmarks] [--track] [--relocalize]
+                                            [--update [--retire] [--compact]] [--merge-maps]
 
 runs every `eva_batch.sequences` entry (packed and cached like graph_store): `<output_path>/<seq>_topk.npz` with
 frame, indices [M,K], scores [M,K] and recall@1..K (K up to 4096); with --recall-percent P the lists hold
@@ -111,6 +112,15 @@ Printed are the landmarks in use (three or more observations) before and after r
 landmarks seen / landmarks expected; `<seq>_persist.npz` holds expected, seen, keep per landmark, scan_expected,
 scan_seen, scan_live, flags, view per scan, num = (retired, judged, eligible, scans with a view), in_use_before,
 in_use_after, scan_ratio_median and the parameters.  Without --retire every output is as before.
+With --compact after --update [--retire] the updated map is compacted on its records alone (SG.compact_map,
+landmarks.merge): what --retire retired is removed (without --retire no mask is applied), records of one
+label within --lm-radius of one another are fused, the rest are renumbered densely in their order.  Printed are the
+landmarks before -> after, dropped and fused; `<seq>_compact.npz` holds the records, old_to_new, node_landmark of the new
+scans carried through it, num = (landmarks, dropped by the mask, dropped as ineligible, fused) and landmarks_before.
+With --landmarks --sessions N --merge-maps one landmark map is built per session on the sequence's own poses and the N
+maps are merged left to right on their records (SG.merge_maps); printed beside the result is the landmark count of the
+batch map of every session; `<seq>_merge.npz` holds the records, num, landmarks_per_session, fused, batch_landmarks and
+same_count.  Without the two flags every output is as before.
 
 With --landmarks --sessions N --track [--track-radii 2,0.75] [--reacquire-radii 8] [--min-matched M] the last of the N
 sessions is TRACKED through the landmark map of the others (SG.track_in_map, landmarks.track): its first
@@ -495,6 +505,12 @@ def main(argv=None):
                     help="with --update: tally what the drive folded in should have seen of the updated map and what it saw, "
                          "and retire the landmarks it should have seen and did not (DESIGN.md §33); writes <seq>_persist.npz. "
                          "There is no occlusion model: a hidden landmark counts as missed")
+    ap.add_argument("--compact", action="store_true",
+                    help="with --update [--retire]: compact the updated map on its records alone - drop what --retire "
+                         "retired, fuse duplicates within --lm-radius, renumber (DESIGN.md §36); writes <seq>_compact.npz")
+    ap.add_argument("--merge-maps", action="store_true",
+                    help="with --landmarks --sessions N: build one landmark map per session and merge them left to right "
+                         "on their records alone (DESIGN.md §36); writes <seq>_merge.npz")
     ap.add_argument("--view-range", type=float, default=50.0, metavar="R",
                     help="with --retire: the sensor range in metres; a scan sees as far as its farthest node, at most R")
     ap.add_argument("--view-margin", type=float, default=2.0, metavar="M",
@@ -570,6 +586,10 @@ def main(argv=None):
         ap.error("--update needs --landmarks and --sessions N")
     if opt.retire and not opt.update:
         ap.error("--retire needs --update")
+    if opt.compact and not opt.update:
+        ap.error("--compact needs --update")
+    if opt.merge_maps and not (opt.landmarks and opt.sessions is not None):
+        ap.error("--merge-maps needs --landmarks and --sessions N")
     if opt.track:
         if not (opt.landmarks and opt.sessions is not None):
             ap.error("--track needs --landmarks and --sessions N")
@@ -767,6 +787,22 @@ def main(argv=None):
                       % (int(preport["in_use_before"]), int(preport["in_use_after"]), int(preport["num"][0]), int(preport["num"][1]),
                          opt.min_expected, opt.max_seen_ratio),
                       "per-scan seen / expected %.4f (median)" % preport["scan_ratio_median"])
+            if opt.compact:
+                kreport = compact_lists(trainer.model, ureport, keep=preport["keep"] if opt.retire else None,
+                                        radius=opt.lm_radius, tau_z=opt.lm_tau_z)
+                np.savez(os.path.join(args.output_path, sequence + "_compact.npz"), **kreport)
+                print("sequence", sequence, "updated map compacted on its records (%s, radius %g m):"
+                      % ("under the retire mask" if opt.retire else "no mask", opt.lm_radius),
+                      "landmarks %d -> %d, dropped %d, fused %d"
+                      % (int(kreport["landmarks_before"]), int(kreport["num"][0]), int(kreport["num"][1] + kreport["num"][2]),
+                         int(kreport["num"][3])))
+        if opt.merge_maps:
+            greport = merge_lists(trainer.model, seq, opt.sessions, radius=opt.lm_radius, tau_z=opt.lm_tau_z)
+            np.savez(os.path.join(args.output_path, sequence + "_merge.npz"), **greport)
+            print("sequence", sequence, "landmark maps of %d sessions merged on their records (radius %g m):" % (opt.sessions, opt.lm_radius),
+                  "landmarks %s -> %d, fused %d; the batch map of every session has %d landmarks, count as in it: %.4f"
+                  % (" + ".join(str(int(v)) for v in greport["landmarks_per_session"]), int(greport["num"][0]),
+                     int(greport["fused"].sum()), int(greport["batch_landmarks"]), greport["same_count"]))
         rreport = None
         if opt.relocalize:
             rreport = relocalize_lists(trainer.model, seq, opt.sessions, radii=opt.align_radii, iters=opt.align_iters,
@@ -1225,6 +1261,55 @@ def persist_lists(model, seq, updated, max_range=50.0, margin=2.0, min_expected=
                 "scan_ratio_median": np.float64(np.median(out["scan_seen"][asked] / out["scan_expected"][asked]) if asked.any() else 0.0),
                 "max_range": np.float64(max_range), "margin": np.float64(margin), "min_expected": np.int64(min_expected),
                 "max_seen_ratio": np.float64(max_seen_ratio), "min_count": np.int64(min_count), "first_scan": np.int64(b)})
+    return out
+
+
+def compact_lists(model, updated, keep=None, radius=0.75, tau_z=0.75):
+    """The map update_lists left, compacted on its records alone (SG.compact_map): `updated` is update_lists' dict; keep:
+    persist_lists' keep mask (None: no landmark is dropped by a mask).
+    -> dict of numpy arrays: center, label, count, first, sessions, spread of the compacted map, old_to_new i32 [L] (-1 =
+    dropped), node_landmark [Q,N] of update_lists' scans carried through it (landmarks.remap), num = (landmarks, dropped by
+    the mask, dropped as ineligible, landmarks fused from several), landmarks_before, radius, tau_z."""
+    from . import landmarks as _landmarks
+    lm = {k: updated[k] for k in ("center", "label", "count", "first", "sessions", "spread")}
+    got = model.compact_map(lm, keep=keep, radius=radius, tau_z=tau_z)
+    out = {k: got[k].cpu().numpy() for k in ("center", "label", "count", "first", "sessions", "spread", "old_to_new")}
+    out.update({"node_landmark": _landmarks.remap(np.asarray(updated["node_landmark"]), out["old_to_new"]),
+                "num": np.asarray([got["num_landmarks"], got["dropped"][0], got["dropped"][1], got["fused"]], dtype=np.int64),
+                "landmarks_before": np.int64(len(updated["count"])), "radius": np.float64(radius), "tau_z": np.float64(tau_z)})
+    return out
+
+
+def merge_lists(model, seq, sessions, radius=0.75, tau_z=0.75):
+    """One landmark map per session of `seq` (session_lists' split; SG.landmark_map on the sequence's own poses), merged
+    left to right on their records (SG.merge_maps: session j's bit is j, its `first` counts from its first node in the
+    sequence).  The yardstick is the batch map of every session on the same poses.
+    -> dict of numpy arrays: center, label, count, first, sessions, spread of the merged map, num = (landmarks, 0, dropped
+    as ineligible, landmarks fused from several - all of the last merge), landmarks_per_session, fused (per merge),
+    batch_landmarks, same_count (the share of the merged landmarks whose count equals that of the batch landmark holding
+    their first node), radius, tau_z."""
+    if int(sessions) < 2:
+        raise ValueError("merge_lists: there is nothing to merge with fewer than two sessions")
+    m, n = seq.labels.shape[0], seq.labels.shape[1]
+    bounds = [(j * m) // int(sessions) for j in range(int(sessions))] + [m]
+    own = metrics.planar_odometry(seq.poses)
+    maps = [model.landmark_map(seq.centers[lo:hi], seq.labels[lo:hi], own[lo:hi], radius=radius, tau_z=tau_z)
+            for lo, hi in zip(bounds[:-1], bounds[1:])]
+    merged, fused, last = maps[0], [], None
+    for j in range(1, int(sessions)):
+        last = model.merge_maps(merged, maps[j], session_shift=j, first_base=bounds[j] * n, radius=radius, tau_z=tau_z)
+        merged = last
+        fused.append(last["fused"])
+    batch = model.landmark_map(seq.centers, seq.labels, own, sessions=np.asarray(bounds[:-1], dtype=np.int32), radius=radius,
+                               tau_z=tau_z)
+    out = {name: merged[name].cpu().numpy() for name in ("center", "label", "count", "first", "sessions", "spread")}
+    holder = batch["node_landmark"].cpu().numpy().reshape(-1)[out["first"]]
+    same = batch["count"].cpu().numpy()[holder] == out["count"]
+    out.update({"num": np.asarray([last["num_landmarks"], last["dropped"][0], last["dropped"][1], last["fused"]], dtype=np.int64),
+                "landmarks_per_session": np.asarray([lm["num_landmarks"] for lm in maps], dtype=np.int64),
+                "fused": np.asarray(fused, dtype=np.int64), "batch_landmarks": np.int64(batch["num_landmarks"]),
+                "same_count": np.float64(same.mean() if same.size else 1.0), "radius": np.float64(radius),
+                "tau_z": np.float64(tau_z)})
     return out
 
 

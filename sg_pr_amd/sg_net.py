@@ -536,6 +536,95 @@ class SG(torch.nn.Module):
         return _landmarks.persist(centers, labels, x, node_landmark, lm, radius=radius, max_range=max_range, margin=margin,
                                   min_expected=min_expected, max_seen_ratio=max_seen_ratio, device=dev)
 
+    def compact_map(self, lm, keep=None, radius=0.75, tau_z=None):
+        """Compact a landmark map on its records alone (landmarks.compact): the landmarks `keep` drops -
+        map_persistence's keep, or any mask; None: none - are removed, duplicates of one label within `radius` of one
+        another are fused as if their observations had been, and the rest are renumbered densely in their old order,
+        bit for bit what they were.  No node array is read.  lm: the dict of landmark_map, update_map or merge_maps.
+        -> the dict of landmarks.merge: the six records, num_landmarks, old_to_new (landmarks.remap carries a
+        node_landmark array through it), dropped, fused."""
+        from . import landmarks as _landmarks
+        return _landmarks.compact(lm, keep=keep, radius=radius, tau_z=tau_z, device=self.engine().device)
+
+    def register_maps(self, a, b, use_a=None, use_b=None, min_count=3, ratio=0.7, **relocalize_kw):
+        """The planar pose that carries the frame of landmark map `b` into the frame of map `a`, from the landmarks alone
+        (DESIGN.md §36): b's selected landmarks - count >= min_count, and use_b where given - become ONE query scan
+        (their centres less their planar mean, formed in float64, then float32) that landmarks.relocalize places among
+        a's selected landmarks with no prior pose; the answer is composed with the centring shift by the `a o b` rule
+        of sgpr_landmark_track.h.  A host-level composition of existing calls with ONE synchronisation of its own - b's
+        selected records cross to the host in one transfer - before landmarks.relocalize, which reads its answer back.
+        A MAP b TOO LARGE TO BE ONE SCAN - relocalize pairs every two of its nodes min_base..max_base apart, and stops
+        starting pairs at max_hyp hypotheses - IS THE CALLER'S TO CUT WITH use_b: a part of b that overlaps a is enough,
+        the pose holds for all of b.  relocalize_kw: radii, min_inliers, radius_in, tau_edge, min_base, max_base,
+        max_hyp, sep, iters, min_nodes, tau_z of landmarks.relocalize.
+        -> (pose f64 [4] numpy (c, s, X, Y), or None when the scan is not found or another place holds at least `ratio`
+        of its inliers; info: found, ambiguous, inliers, inliers_other, hypotheses, nodes (the landmarks of b used))."""
+        from . import landmarks as _landmarks
+        dev = self.engine().device
+        pick_a = _landmarks.select(a, min_count=min_count, keep=use_a)
+        pick_b = _landmarks.select(b, min_count=min_count, keep=use_b)
+        # b's centres, labels and mask cross to the host together: one transfer, one synchronisation
+        where = pick_b.device
+        packed = torch.cat((torch.as_tensor(b["center"]).to(device=where, dtype=torch.float64).reshape(-1, 3),
+                            torch.as_tensor(b["label"]).to(device=where, dtype=torch.float64).reshape(-1, 1),
+                            pick_b.to(torch.float64).reshape(-1, 1)), dim=1).detach().cpu().numpy()
+        idx = np.flatnonzero(packed[:, 4] != 0)
+        cen, lab = packed[idx, :3], packed[idx, 3].astype(np.int32)
+        mean = cen[:, :2].mean(axis=0) if cen.shape[0] else np.zeros(2)
+        q = cen.copy()
+        q[:, :2] -= mean
+        x, info = _landmarks.relocalize(q.astype(np.float32)[None], lab[None], a, use=pick_a, device=dev, **relocalize_kw)
+        found = bool(info["found"][0])
+        ambiguous = found and bool(info["inliers_other"][0] >= float(ratio) * info["inliers"][0])
+        out = {"found": found, "ambiguous": ambiguous, "inliers": int(info["inliers"][0]),
+               "inliers_other": int(info["inliers_other"][0]), "hypotheses": int(info["hypotheses"][0]), "nodes": int(cen.shape[0])}
+        if not found or ambiguous:
+            return None, out
+        tc, ts, tx, ty = (np.float64(v) for v in x[0].cpu().numpy())
+        bx, by = np.float64(-mean[0]), np.float64(-mean[1])
+        # a o b with b = (1, 0, bx, by): every product, sum and difference rounded once, in the order written
+        one, zero = np.float64(1.0), np.float64(0.0)
+        pose = np.array([tc * one - ts * zero, ts * one + tc * zero, (tc * bx - ts * by) + tx, (ts * bx + tc * by) + ty])
+        return pose, out
+
+    def merge_maps(self, a, b, pose=None, keep_a=None, keep_b=None, session_shift=None, first_base=None, radius=0.75, tau_z=None,
+                   **register_kw):
+        """Join two landmark maps that were built apart - two vehicles, two days - on their records alone
+        (landmarks.merge): records of one label within `radius` fuse, inside a map and across the two,
+        as if their observations had been fused; no node array is read.  pose: planar (c, s, X, Y) that carries b's
+        frame into a's; None: the maps share a frame; "register": register_maps(a, b, **register_kw) finds it, and the
+        call raises where that answers None.  keep_a, keep_b: masks that drop landmarks first (None: none);
+        session_shift: b's session bits move up by this (None: the number of session bits a uses); first_base: added to
+        b's `first` (None: the largest `first` of a + 1).
+        -> the dict of landmarks.merge - the records of the joined map, num_landmarks, old_to_new [L_a + L_b] (b's
+        landmark j is entry L_a + j), dropped, fused - plus pose (numpy [4], or None)."""
+        from . import landmarks as _landmarks
+        if isinstance(pose, str):
+            if pose != "register":
+                raise ValueError("merge_maps: pose is a planar pose, None or \"register\"")
+            pose, info = self.register_maps(a, b, use_a=keep_a, use_b=keep_b, **register_kw)
+            if pose is None:
+                raise RuntimeError("merge_maps: map b could not be registered in map a (%s)" % (info,))
+        elif register_kw:
+            raise TypeError("merge_maps: %s only go with pose=\"register\"" % ", ".join(sorted(register_kw)))
+        if session_shift is None:
+            sess = torch.as_tensor(a["sessions"].view(np.int64) if isinstance(a["sessions"], np.ndarray) and
+                                   a["sessions"].dtype == np.uint64 else a["sessions"]).to(torch.int64).reshape(-1)
+            # the highest bit in use is that of the largest mask as an unsigned number: bit 63 where a mask is negative
+            # as int64, else the bit length of the maximum - two reductions where the masks are, one read-back
+            session_shift = 0
+            if sess.numel():
+                low, high = torch.stack((sess.min(), sess.max())).tolist()
+                session_shift = 64 if low < 0 else int(high).bit_length()
+        if first_base is None:
+            first = torch.as_tensor(a["first"])
+            first_base = 0 if first.numel() == 0 else max(int(first.max()) + 1, 0)
+        out = _landmarks.merge(a, b, keep_a=keep_a, keep_b=keep_b, pose=pose, session_shift=int(session_shift),
+                               first_base=int(first_base), radius=radius, tau_z=tau_z, device=self.engine().device)
+        out["pose"] = None if pose is None else np.asarray(pose.detach().cpu() if isinstance(pose, torch.Tensor) else pose,
+                                                            dtype=np.float64).reshape(4)
+        return out
+
     def hard_pairs(self, pooled_rows, pooled_cols, col_pose, k=1, positives=False, d_pos=3.0, d_neg=20.0, window=-1,
                    row0=0, causal=False, row_self=None, row_pose=None):
         """The k hardest negatives (or, positives=True, positives) per row of pooled_rows x pooled_cols without forming
