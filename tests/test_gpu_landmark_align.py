@@ -23,8 +23,9 @@ IDENT = (1.0, 0.0, 0.0, 0.0)
 
 
 def device_align(centers, labels, poses, lm_center, lm_label, lm_use=None, radius=0.75, tau_z=0.75, iters=10, min_nodes=6,
-                 n_labels=None, stream=None, in_place=False):
-    """the C call with every output (and a margin behind it) and the workspace full of 0xFF -> dict of host arrays"""
+                 n_labels=None, stream=None, in_place=False, ws_fill=0xFF, out_fill=0xFF, workspace=None):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is) -> dict of host arrays"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -41,7 +42,7 @@ def device_align(centers, labels, poses, lm_center, lm_label, lm_use=None, radiu
     rad = np.ascontiguousarray(rad)
 
     def dirty(n, dtype):
-        return torch.full((n,), -1, dtype=torch.int64 if dtype == torch.float64 else dtype, device=dev).view(dtype)
+        return torch.full((n * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype)
 
     out = {"poses": dirty(4 * (Q + MARGIN), torch.float64), "node_landmark": dirty(Q * N + MARGIN, torch.int32),
            "stat": dirty(4 * (Q + MARGIN), torch.int32), "rms": dirty(Q + MARGIN, torch.float64)}
@@ -51,8 +52,10 @@ def device_align(centers, labels, poses, lm_center, lm_label, lm_use=None, radiu
         X = out["poses"]
     need = landmarks.align_workspace_bytes(Q, N, L)
     assert need == ref.workspace_bytes(Q, N, L)
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev)
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rc = lib.sgpr_landmark_align(p(cen), p(lab), Q, N, p(X), p(lmc) if L else None, p(lml) if L else None, p(use), L,
                                      rad.ctypes.data, rad.size, float(tau_z), int(iters), int(min_nodes), p(out["poses"]),
@@ -62,24 +65,26 @@ def device_align(centers, labels, poses, lm_center, lm_label, lm_use=None, radiu
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def same(got, want, Q, N):
+def same(got, want, Q, N, out_fill=0xFF):
     """the outputs equal the reference to the bit (NaN as NaN: bytes), nothing written past them"""
     for name, n in (("poses", 4 * Q), ("node_landmark", Q * N), ("stat", 4 * Q), ("rms", Q)):
         assert got[name][:n].tobytes() == want[name].tobytes(), (name, got[name][:n], want[name].reshape(-1))
-        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
 
 
 def check(centers, labels, poses, lm_center, lm_label, **kw):
     stream, in_place = kw.pop("stream", None), kw.pop("in_place", False)
-    got = device_align(centers, labels, poses, lm_center, lm_label, stream=stream, in_place=in_place, **kw)
+    extra = {k: kw.pop(k) for k in ("ws_fill", "out_fill", "workspace") if k in kw}
+    out_fill = extra.get("out_fill", 0xFF)
+    got = device_align(centers, labels, poses, lm_center, lm_label, stream=stream, in_place=in_place, **extra, **kw)
     want = ref.align(centers, labels, poses, lm_center, lm_label, **kw)
     Q, N = np.asarray(labels).shape
     if Q * N == 0:                                               # nothing is written
         for name, v in got.items():
             tail = v[4 * Q:] if in_place and name == "poses" else v
-            assert (tail.view(np.uint8) == 0xFF).all(), name
+            assert (tail.view(np.uint8) == out_fill).all(), name
         return want
-    same(got, want, Q, N)
+    same(got, want, Q, N, out_fill)
     return want
 
 

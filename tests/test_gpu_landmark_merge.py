@@ -33,9 +33,9 @@ def to_device(lm, dev):
             for k in ref.RECORD}
 
 
-def launch(case, max_out=None, stream=None, workspace=None):
-    """the C call with every output (and a margin behind it) and the workspace full of 0xFF, asynchronous -> what finish
-    needs"""
+def launch(case, max_out=None, stream=None, workspace=None, ws_fill=0xFF, out_fill=0xFF):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is), asynchronous -> what finish needs"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -52,14 +52,14 @@ def launch(case, max_out=None, stream=None, workspace=None):
     pose = None if kw.get("pose") is None else np.ascontiguousarray(kw["pose"], np.float64)
 
     def dirty(n, dtype):
-        return torch.full((n,), -1, dtype=torch.int64 if dtype == torch.float64 else dtype, device=dev).view(dtype)
+        return torch.full((n * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype)
 
     out = {k: dirty((3 if k == "center" else 1) * (cap + MARGIN), DTYPES[k]) for k in ref.RECORD}
     out["old_to_new"] = dirty(T + MARGIN, torch.int32)
     out["num"] = dirty(4 + MARGIN, torch.int32)
     need = landmarks.merge_workspace_bytes(L_a, L_b)
     assert need == ref.workspace_bytes(L_a, L_b)
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())           # (the inputs were filled on the current stream)
@@ -71,19 +71,20 @@ def launch(case, max_out=None, stream=None, workspace=None):
             rad.ctypes.data, rad.size, float(kw.get("tau_z", 0.75)), cap, *[p(out[k]) for k in ref.RECORD], p(out["old_to_new"]),
             p(out["num"]), p(ws), need, engine._stream(dev))
     assert rc == 0, lib.sgpr_last_error()
-    return {"out": out, "cap": cap, "T": T, "a": a, "b": b, "keeps": keeps, "case": case, "ws": ws}
+    return {"out": out, "cap": cap, "T": T, "a": a, "b": b, "keeps": keeps, "case": case, "ws": ws,
+            "out_fill": out_fill}
 
 
 def finish(run):
     """-> the reference's outputs, after the device's were found equal to them to the bit (NaN as NaN: bytes), nothing
     written past the records found or past any output, and the inputs unchanged"""
     torch.cuda.synchronize()
-    case, cap, T = run["case"], run["cap"], run["T"]
+    case, cap, T, out_fill = run["case"], run["cap"], run["T"], run["out_fill"]
     want = ref.run(case, max_out=cap)
     got = {k: v.cpu().numpy() for k, v in run["out"].items()}
     got["sessions"] = got["sessions"].view(np.uint64)
     if T == 0:                                                   # nothing is written
-        assert all((v.view(np.uint8) == 0xFF).all() for v in got.values())
+        assert all((v.view(np.uint8) == out_fill).all() for v in got.values())
         return want
     rows = min(int(want["num"][0]), cap)
     for name in ref.RECORD:
@@ -91,10 +92,10 @@ def finish(run):
         assert len(want[name]) == rows
         assert got[name][:w * rows].tobytes() == np.ascontiguousarray(want[name], HOST[name]).tobytes(), \
             (name, got[name][:w * rows], want[name].reshape(-1))
-        assert (got[name][w * rows:].view(np.uint8) == 0xFF).all(), name + ": written past the records"
+        assert (got[name][w * rows:].view(np.uint8) == out_fill).all(), name + ": written past the records"
     for name, n in (("old_to_new", T), ("num", 4)):
         assert got[name][:n].tobytes() == want[name].tobytes(), (name, got[name][:n], want[name].reshape(-1))
-        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
     for lm, dev_lm in ((case["a"], run["a"]), (case["b"], run["b"])):
         if lm is not None:
             for k in ref.RECORD:

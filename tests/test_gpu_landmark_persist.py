@@ -27,8 +27,9 @@ DTYPES = {"expected": torch.int32, "seen": torch.int32, "keep": torch.uint8, "sc
 
 
 def device_persist(centers, labels, poses, assoc, lm, radius=0.75, n_labels=None, max_range=50.0, margin=2.0, min_expected=5,
-                   max_seen_ratio=0.3, stream=None, workspace=None):
-    """the C call with every output (and a margin behind it) and the workspace full of 0xFF -> dict of host arrays"""
+                   max_seen_ratio=0.3, stream=None, workspace=None, ws_fill=0xFF, out_fill=0xFF):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is) -> dict of host arrays"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -46,12 +47,13 @@ def device_persist(centers, labels, poses, assoc, lm, radius=0.75, n_labels=None
         rad = np.full(12 if n_labels is None else n_labels, rad[0])
     rad = np.ascontiguousarray(rad)
     sizes = {"expected": L, "seen": L, "keep": L, "scan_stat": 4 * Q, "view": Q, "num": 4}
-    out = {k: torch.full((sizes[k] + MARGIN,), -1, dtype=torch.int64 if t == torch.float64 else torch.int32 if t == torch.int32 else torch.int8,
-                         device=dev).view(t) for k, t in DTYPES.items()}
+    out = {k: torch.full(((sizes[k] + MARGIN) * t.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(t) for k, t in DTYPES.items()}
     need = landmarks.persist_workspace_bytes(Q, N, L)
     assert need == ref.workspace_bytes(Q, N, L)
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rc = lib.sgpr_landmark_persist(
             p(cen), p(lab), Q, N, p(X), p(asc), p(lm_c) if L else None, p(lm_l) if L else None, p(use) if use is not None and L else None,
@@ -65,17 +67,18 @@ def device_persist(centers, labels, poses, assoc, lm, radius=0.75, n_labels=None
 
 def check(centers, labels, poses, assoc, lm, **kw):
     """the outputs equal the reference byte for byte, nothing is written past any output -> the reference's dict"""
-    extra = {k: kw.pop(k) for k in ("stream", "workspace") if k in kw}
+    extra = {k: kw.pop(k) for k in ("stream", "workspace", "ws_fill", "out_fill") if k in kw}
+    out_fill = extra.get("out_fill", 0xFF)
     Q, N = np.asarray(labels).shape
     want = ref.persist(centers, labels, poses, assoc, lm, **kw)
     got, sizes = device_persist(centers, labels, poses, assoc, lm, **kw, **extra)
     if Q * N == 0:                                               # nothing is written
-        assert all((v.view(np.uint8) == 0xFF).all() for v in got.values())
+        assert all((v.view(np.uint8) == out_fill).all() for v in got.values())
         return want
     for name in ref.OUTPUTS:
         n = sizes[name]
         assert got[name][:n].tobytes() == np.ascontiguousarray(want[name]).tobytes(), (name, got[name][:n], want[name].reshape(-1))
-        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
     return want
 
 

@@ -22,8 +22,10 @@ F32 = np.float32
 MARGIN = 5
 
 
-def device_refine(centers, node_landmark, poses, lm_use, fixed=None, iters=10, min_nodes=6, stream=None):
-    """the C call with every output (and a margin behind it) and the workspace full of 0xFF -> dict of host arrays"""
+def device_refine(centers, node_landmark, poses, lm_use, fixed=None, iters=10, min_nodes=6, stream=None, ws_fill=0xFF,
+                  out_fill=0xFF, workspace=None):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is) -> dict of host arrays"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -36,14 +38,16 @@ def device_refine(centers, node_landmark, poses, lm_use, fixed=None, iters=10, m
     fix = None if fixed is None else torch.as_tensor(np.ascontiguousarray(fixed, np.uint8).reshape(G)).to(dev)
 
     def dirty(n, dtype):
-        return torch.full((n,), -1, dtype=torch.int64 if dtype == torch.float64 else dtype, device=dev).view(dtype)
+        return torch.full((n * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype)
 
     out = {"poses": dirty(4 * (G + MARGIN), torch.float64), "cost": dirty(iters + 1 + MARGIN, torch.float64),
            "info": dirty(4 + MARGIN, torch.int32)}
     need = landmarks.refine_workspace_bytes(G, N, L)
     assert need == ref.workspace_bytes(G, N, L)
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev)
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rc = lib.sgpr_landmark_refine(p(cen), G, N, p(X), p(node), p(use) if L else None, L, p(fix), int(iters), int(min_nodes),
                                       p(out["poses"]), p(out["cost"]), p(out["info"]), p(ws), need, engine._stream(dev))
@@ -55,18 +59,20 @@ def device_refine(centers, node_landmark, poses, lm_use, fixed=None, iters=10, m
 def check(centers, node_landmark, poses, lm_use, **kw):
     """the device call equals the reference to the bit (NaN as NaN: bytes), nothing written past the outputs"""
     kw.pop("stream", None)
-    got = device_refine(centers, node_landmark, poses, lm_use, **kw)
+    extra = {k: kw.pop(k) for k in ("ws_fill", "out_fill", "workspace") if k in kw}
+    out_fill = extra.get("out_fill", 0xFF)
+    got = device_refine(centers, node_landmark, poses, lm_use, **extra, **kw)
     want = ref.refine(centers, node_landmark, poses, lm_use, **kw)
     G, N = np.asarray(node_landmark).shape
     T = want["cost"].size - 1
     if G * N == 0:
-        assert all((v.view(np.uint8) == 0xFF).all() for v in got.values())            # nothing is written
+        assert all((v.view(np.uint8) == out_fill).all() for v in got.values())        # nothing is written
         return want
     assert got["cost"][:T + 1].tobytes() == want["cost"].tobytes(), (got["cost"][:T + 1], want["cost"])
     assert got["info"][:4].tolist() == want["info"].tolist()
     assert got["poses"][:4 * G].tobytes() == want["poses"].tobytes()
     for name, n in (("poses", 4 * G), ("cost", T + 1), ("info", 4)):
-        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
     return want
 
 

@@ -27,9 +27,9 @@ SHAPES = (("poses", 4, torch.float64), ("coarse", 4, torch.float64), ("other", 4
 
 def device_relocalize(centers, labels, lm_center, lm_label, lm_use=None, radius_in=0.75, radii=(2.0, 0.75), tau_z=0.75, tau_edge=0.5,
                       min_base=5.0, max_base=30.0, max_hyp=65536, min_inliers=12, sep=10.0, iters=10, min_nodes=6, n_labels=None,
-                      stream=None):
-    """the C call with every output (and a margin behind it) and the workspace full of 0xFF; the inputs must come back
-    as they went in -> dict of host arrays"""
+                      stream=None, ws_fill=0xFF, out_fill=0xFF, workspace=None):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is); the inputs must come back as they went in -> dict of host arrays"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -51,14 +51,16 @@ def device_relocalize(centers, labels, lm_center, lm_label, lm_use=None, radius_
     d = {k: torch.as_tensor(v).to(dev) for k, v in host.items()}
 
     def dirty(n, dtype):
-        return torch.full((n,), -1, dtype=torch.int64 if dtype == torch.float64 else dtype, device=dev).view(dtype)
+        return torch.full((n * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype)
 
     out = {k: dirty((Q * N if w is None else w * Q) + (MARGIN if w is None else w * MARGIN), t) for k, w, t in SHAPES}
     out["num"] = dirty(4 + MARGIN, torch.int32)
     need = landmarks.relocalize_workspace_bytes(Q, N, L, S)
     assert need == ref.workspace_bytes(Q, N, L, S)
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev)
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rc = lib.sgpr_landmark_relocalize(
             p(d["centers"]), p(lab), Q, N, p(d["lm_center"]) if L else None, p(d["lm_label"]) if L else None, p(d.get("lm_use")), L,
@@ -74,12 +76,12 @@ def device_relocalize(centers, labels, lm_center, lm_label, lm_use=None, radius_
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def same(got, want, Q, N):
+def same(got, want, Q, N, out_fill=0xFF):
     """the outputs equal the reference to the bit (NaN as NaN: bytes), nothing written past them"""
     for name, w, _ in SHAPES + (("num", None, None),):
         n = 4 if name == "num" else (Q * N if w is None else w * Q)
         assert got[name][:n].tobytes() == want[name].tobytes(), (name, got[name][:n], want[name].reshape(-1))
-        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
 
 
 def check(w, stream=None, **over):
@@ -87,10 +89,11 @@ def check(w, stream=None, **over):
     kw = dict(w["kw"])
     lm_use = over.pop("lm_use", w.get("lm_use"))
     kw.update(over)
+    extra = {k: kw.pop(k) for k in ("ws_fill", "out_fill", "workspace") if k in kw}
     args = (w["centers"], w["labels"], w["lm"], w["lm_label"], lm_use)
-    got = device_relocalize(*args, stream=stream, **kw)
+    got = device_relocalize(*args, stream=stream, **extra, **kw)
     want = ref.relocalize(*args, **kw)
-    same(got, want, *w["labels"].shape)
+    same(got, want, *w["labels"].shape, out_fill=extra.get("out_fill", 0xFF))
     return want
 
 

@@ -23,9 +23,10 @@ OUTPUTS = ("poses", "pred", "node_landmark", "stat", "rms", "num")
 
 
 def device_track(centers, labels, odom, init, lm_center, lm_label, lm_use=None, starts=None, radii=(2.0, 0.75), n_reacquire=0,
-                 tau_z=0.75, iters=10, min_nodes=6, min_matched=10, max_shift=np.inf, flags=0, n_labels=None, stream=None):
-    """the C call with every output (and a margin behind it) and the workspace full of 0xFF; the inputs must come back
-    as they went in -> dict of host arrays"""
+                 tau_z=0.75, iters=10, min_nodes=6, min_matched=10, max_shift=np.inf, flags=0, n_labels=None, stream=None,
+                 ws_fill=0xFF, out_fill=0xFF, workspace=None):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is); the inputs must come back as they went in -> dict of host arrays"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -44,15 +45,17 @@ def device_track(centers, labels, odom, init, lm_center, lm_label, lm_use=None, 
     d = {k: torch.as_tensor(v).to(dev) for k, v in host.items()}
 
     def dirty(n, dtype):
-        return torch.full((n,), -1, dtype=torch.int64 if dtype == torch.float64 else dtype, device=dev).view(dtype)
+        return torch.full((n * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype)
 
     out = {"poses": dirty(4 * (Q + MARGIN), torch.float64), "pred": dirty(4 * (Q + MARGIN), torch.float64),
            "node_landmark": dirty(Q * N + MARGIN, torch.int32), "stat": dirty(4 * (Q + MARGIN), torch.int32),
            "rms": dirty(Q + MARGIN, torch.float64), "num": dirty(4 + MARGIN, torch.int32)}
     need = landmarks.track_workspace_bytes(Q, N, L, rad.shape[0])
     assert need == ref.workspace_bytes(Q, N, L, rad.shape[0])
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev)
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rc = lib.sgpr_landmark_track(p(d["centers"]), p(lab), Q, N, p(d["odom"]), None if table is None else table.ctypes.data,
                                      0 if table is None else table.size, p(d["init"]), p(d["lm_center"]) if L else None,
@@ -67,11 +70,11 @@ def device_track(centers, labels, odom, init, lm_center, lm_label, lm_use=None, 
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def same(got, want, Q, N):
+def same(got, want, Q, N, out_fill=0xFF):
     """the outputs equal the reference to the bit (NaN as NaN: bytes), nothing written past them"""
     for name, n in (("poses", 4 * Q), ("pred", 4 * Q), ("node_landmark", Q * N), ("stat", 4 * Q), ("rms", Q), ("num", 4)):
         assert got[name][:n].tobytes() == want[name].tobytes(), (name, got[name][:n], want[name].reshape(-1))
-        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
 
 
 def check(d, **kw):
@@ -80,13 +83,15 @@ def check(d, **kw):
     kw.setdefault("iters", 3)
     args = (d["centers"], d["labels"], d["odom"], kw.pop("init", d["init"]), kw.pop("lm", d["lm"]), kw.pop("lm_label", d["lm_label"]))
     stream = kw.pop("stream", None)
-    got = device_track(*args, stream=stream, **kw)
+    extra = {k: kw.pop(k) for k in ("ws_fill", "out_fill", "workspace") if k in kw}
+    out_fill = extra.get("out_fill", 0xFF)
+    got = device_track(*args, stream=stream, **extra, **kw)
     want = ref.track(*args, **kw)
     Q, N = d["labels"].shape
     if Q * N == 0:                                               # nothing is written
-        assert all((v.view(np.uint8) == 0xFF).all() for v in got.values())
+        assert all((v.view(np.uint8) == out_fill).all() for v in got.values())
         return want
-    same(got, want, Q, N)
+    same(got, want, Q, N, out_fill)
     return want
 
 

@@ -27,8 +27,9 @@ HOST = {"center": np.float64, "label": np.int32, "count": np.int32, "first": np.
 
 
 def device_update(centers, labels, poses, assoc, lm, starts=None, session_base=0, node_base=0, radius=0.75, tau_z=0.75,
-                  n_labels=None, max_landmarks=None, stream=None, in_place=False, workspace=None):
-    """the C call with every output (and a margin behind it) and the workspace full of 0xFF -> (dict of host arrays, cap)"""
+                  n_labels=None, max_landmarks=None, stream=None, in_place=False, workspace=None, ws_fill=0xFF, out_fill=0xFF):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is) -> (dict of host arrays, cap)"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -48,7 +49,7 @@ def device_update(centers, labels, poses, assoc, lm, starts=None, session_base=0
     table = None if starts is None else np.ascontiguousarray(starts, np.int32)
 
     def dirty(n, dtype):
-        return torch.full((n,), -1, dtype=torch.int64 if dtype == torch.float64 else dtype, device=dev).view(dtype)
+        return torch.full((n * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype)
 
     out = {k: dirty((3 if k == "center" else 1) * (cap + MARGIN), DTYPES[k]) for k in ref.RECORD}
     out["node_landmark"] = dirty(Q * N + MARGIN, torch.int32)
@@ -60,8 +61,10 @@ def device_update(centers, labels, poses, assoc, lm, starts=None, session_base=0
         old, asc = out, out["node_landmark"]
     need = landmarks.update_workspace_bytes(Q, N, L)
     assert need == ref.workspace_bytes(Q, N, L)
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rc = lib.sgpr_landmark_update(
             p(cen), p(lab), Q, N, p(X), p(asc), None if table is None else table.ctypes.data, 0 if table is None else table.size,
@@ -75,7 +78,7 @@ def device_update(centers, labels, poses, assoc, lm, starts=None, session_base=0
     return got, cap
 
 
-def same(got, want, cap, Q, N):
+def same(got, want, cap, Q, N, out_fill=0xFF):
     """the outputs equal the reference to the bit (NaN as NaN: bytes), nothing written past the records found or past any
     output"""
     rows = min(int(want["num"][0]), cap)
@@ -84,14 +87,15 @@ def same(got, want, cap, Q, N):
         assert len(want[name]) == rows
         assert got[name][:w * rows].tobytes() == np.ascontiguousarray(want[name], HOST[name]).tobytes(), \
             (name, got[name][:w * rows], want[name].reshape(-1))
-        assert (got[name][w * rows:].view(np.uint8) == 0xFF).all(), name + ": written past the records"
+        assert (got[name][w * rows:].view(np.uint8) == out_fill).all(), name + ": written past the records"
     for name, n in (("node_landmark", Q * N), ("num", 4)):
         assert got[name][:n].tobytes() == want[name].tobytes(), (name, got[name][:n], want[name].reshape(-1))
-        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
 
 
 def check(centers, labels, poses, assoc, lm, **kw):
-    extra = {k: kw.pop(k) for k in ("stream", "in_place", "workspace") if k in kw}
+    extra = {k: kw.pop(k) for k in ("stream", "in_place", "workspace", "ws_fill", "out_fill") if k in kw}
+    out_fill = extra.get("out_fill", 0xFF)
     Q, N = np.asarray(labels).shape
     L = len(lm["label"])
     cap = kw.pop("max_landmarks", None)
@@ -99,9 +103,9 @@ def check(centers, labels, poses, assoc, lm, **kw):
     want = ref.update(centers, labels, poses, assoc, lm, max_landmarks=cap, **kw)
     got, cap = device_update(centers, labels, poses, assoc, lm, max_landmarks=cap, **kw, **extra)
     if Q * N == 0:                                               # nothing is written
-        assert all((v.view(np.uint8) == 0xFF).all() for v in got.values())
+        assert all((v.view(np.uint8) == out_fill).all() for v in got.values())
         return want
-    same(got, want, cap, Q, N)
+    same(got, want, cap, Q, N, out_fill)
     return want
 
 

@@ -20,8 +20,10 @@ IDENT = (1.0, 0.0, 0.0, 0.0)
 F32 = np.float32
 
 
-def device_map(centers, labels, poses, starts=None, radius=0.75, tau_z=0.75, n_labels=12, max_landmarks=None, stream=None):
-    """the C call with every output and the workspace full of 0xFF -> dict of host arrays (all max_landmarks rows)"""
+def device_map(centers, labels, poses, starts=None, radius=0.75, tau_z=0.75, n_labels=12, max_landmarks=None, stream=None,
+               ws_fill=0xFF, out_fill=0xFF, workspace=None):
+    """the C call with every output full of the byte out_fill and the workspace full of ws_fill (a given workspace is used
+    as it is) -> dict of host arrays (all max_landmarks rows)"""
     from sg_pr_amd import engine, landmarks
     lib = landmarks.load_library()
     dev = torch.device("cuda", 0)
@@ -35,16 +37,17 @@ def device_map(centers, labels, poses, starts=None, radius=0.75, tau_z=0.75, n_l
     table = None if starts is None else np.ascontiguousarray(starts, np.int32)
 
     def dirty(shape, dtype):
-        return torch.full(shape, -1, dtype=dtype, device=dev) if dtype != torch.float64 else \
-            torch.full(shape, -1, dtype=torch.int64, device=dev).view(torch.float64)
+        return torch.full((math.prod(shape) * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype).reshape(shape)
 
     out = {"center": dirty((cap, 3), torch.float64), "label": dirty((cap,), torch.int32), "count": dirty((cap,), torch.int32),
            "first": dirty((cap,), torch.int32), "sessions": dirty((cap,), torch.int64), "spread": dirty((cap,), torch.float64),
            "node_landmark": dirty((G, N), torch.int32), "num": dirty((2,), torch.int32)}
     need = landmarks.workspace_bytes(G, N)
     assert need == ref.workspace_bytes(G, N)
-    ws = torch.full((max(need, 1),), 0xFF, dtype=torch.uint8, device=dev)
+    ws = torch.full((max(need, 1),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
     p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
     with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
         rc = lib.sgpr_landmark_map(p(cen), p(lab), G, N, p(X), None if table is None else table.ctypes.data,
                                    0 if table is None else table.shape[0], rad.ctypes.data, rad.shape[0], float(tau_z), cap,
@@ -58,19 +61,21 @@ def device_map(centers, labels, poses, starts=None, radius=0.75, tau_z=0.75, n_l
 
 def check(centers, labels, poses, **kw):
     """the device call equals the reference: records to the bit (NaN as NaN: bytes), nothing written past them"""
-    got = device_map(centers, labels, poses, **kw)
+    extra = {k: kw.pop(k) for k in ("stream", "ws_fill", "out_fill", "workspace") if k in kw}
+    out_fill = extra.get("out_fill", 0xFF)
+    got = device_map(centers, labels, poses, **extra, **kw)
     want = ref.landmark_map(centers, labels, poses, **kw)
     labels = np.asarray(labels)
     if labels.size:
         assert got["num"].tolist() == want["num"].tolist()
         assert got["node_landmark"].tobytes() == want["node_landmark"].tobytes()
     else:
-        assert got["num"].tolist() == [-1, -1]                    # nothing is written
+        assert (got["num"].view(np.uint8) == out_fill).all()      # nothing is written
     k = want["label"].shape[0]
     for name in ("center", "label", "count", "first", "sessions", "spread"):
         g = got[name]
         assert g[:k].tobytes() == want[name].tobytes(), name
-        assert (g[k:].view(np.uint8) == 0xFF).all(), name + ": written past the records"
+        assert (g[k:].view(np.uint8) == out_fill).all(), name + ": written past the records"
     return want
 
 

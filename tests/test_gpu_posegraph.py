@@ -21,6 +21,51 @@ def same(got, want):
     return got.dtype == want.dtype and got.shape == want.shape and got.numpy().tobytes() == want.numpy().tobytes()
 
 
+MARGIN = 5
+
+
+def device_optimize(X, rows, cols, T, starts=None, fixed=None, weight=None, w_odo=None, w_clo=None, max_iters=1000, rel_tol=1e-9,
+                    stream=None, ws_fill=0xFF, out_fill=0xFF, workspace=None):
+    """the C call with every output (and a margin behind it) full of the byte out_fill and the workspace full of ws_fill
+    (a given workspace is used as it is) -> dict of host arrays"""
+    from sg_pr_amd import engine, posegraph
+    lib = posegraph.load_library()
+    dev = torch.device("cuda", 0)
+    w_odo, w_clo = posegraph.W_ODO if w_odo is None else w_odo, posegraph.W_CLO if w_clo is None else w_clo
+    x = torch.as_tensor(np.ascontiguousarray(X, np.float64).reshape(-1, 4)).to(dev)
+    r, c = (torch.as_tensor(np.ascontiguousarray(v, np.int32).reshape(-1)).to(dev) for v in (rows, cols))
+    t = torch.as_tensor(np.ascontiguousarray(T, np.float64).reshape(-1, 4)).to(dev)
+    M, C = x.shape[0], r.numel()
+    wgt = None if weight is None else torch.as_tensor(np.ascontiguousarray(weight, np.float64).reshape(C)).to(dev)
+    fx = None if fixed is None else torch.as_tensor(np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(M)).to(dev)
+    table = engine._session_table(starts)
+
+    def dirty(n, dtype):
+        return torch.full((n * dtype.itemsize,), out_fill, dtype=torch.uint8, device=dev).view(dtype)
+
+    out = {"X_out": dirty(4 * (M + MARGIN), torch.float64), "info": dirty(8 + MARGIN, torch.int32),
+           "resid": dirty(4 + MARGIN, torch.float64)}
+    need = posegraph.workspace_bytes(M, C)
+    ws = torch.full((max(need, 16),), ws_fill, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    p = engine._ptr
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())           # (the inputs and the fills were made on the current stream)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        rc = lib.sgpr_posegraph_optimize(p(x), M, *engine._table_args(table), p(r), p(c), p(t), p(wgt), C, p(fx), float(w_odo[0]),
+                                         float(w_odo[1]), float(w_clo[0]), float(w_clo[1]), int(max_iters), float(rel_tol),
+                                         p(out["X_out"]), p(out["info"]), p(out["resid"]), p(ws), ws.numel(), engine._stream(dev))
+    assert rc == 0, lib.sgpr_last_error()
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def same_outputs(got, want, M, out_fill=0xFF):
+    """device_optimize's outputs equal the reference's (X_out, info, resid) to the bit, nothing written past them"""
+    for name, n, w in (("X_out", 4 * M, want[0]), ("info", 8, want[1]), ("resid", 4, want[2])):
+        assert got[name][:n].tobytes() == np.ascontiguousarray(w).tobytes(), (name, got[name][:n], np.asarray(w).reshape(-1))
+        assert (got[name][n:].view(np.uint8) == out_fill).all(), name + ": written past the output"
+
+
 def check(X, rows, cols, T, **kw):
     """the call against the reference -> the reference's (X_out, info, resid)"""
     from sg_pr_amd import posegraph

@@ -53,6 +53,21 @@ Workspace and output audit: what initialises each region in the same call before
 | sgpr_cluster_scan | node_of_root, cell hash (keys + values), instance hash, instance minima, class flags / counters | memsets (0xFF, 0xFF, 0xFF, 0x7F, 0) at the top of the call |
 | | d_num_nodes, node arrays (outputs) | producer: stored by the last kernel |
 | every entry point taking a handle | the status word `h->d_status` | belongs to the handle, not the call: raised by any call, reported and cleared by sgpr_check_status |
+
+The map back end, one row per entry point; region by region, with the byte counts against the carves, in the docstring
+of tests/test_gpu_map_stateless.py, which runs them under these fills.
+
+| entry point | region | initialised by |
+|---|---|---|
+| sgpr_landmark_map | cell_key \\| cell_head | one memset 0xff of align256(H * 8) + align256(H * 4), the two carves; every per-node array and the per-workgroup counts by producer (`lm_transform_kernel`, `lm_flatten_kernel`) |
+| sgpr_landmark_refine | acc [2][L][3] \\| scal [32] | one memset 0 of both carves; the two pose arrays by producer (`rf_fit_kernel`) |
+| sgpr_landmark_align | cell_key \\| cell_head | memset 0xff of `la_table_clear_bytes(L)`, the carve of `la_table_carve`; elab and next by producer (`la_prep_landmark`) |
+| sgpr_landmark_update | sums \\| q \\| sess \\| cnt \\| tally | one memset 0 of `upd_zero_bytes(L)`, the five carves; the core's part as sgpr_landmark_map; mlab, obs, centre, core_num by producer |
+| sgpr_landmark_persist | elab | producer (`lp_prep_kernel`); the table regions are read only by the -DSGPR_PERSIST_SEARCH=1 build, which clears cell_key (0xff, H * 8 = its carve) and cell_cnt \\| total (0) |
+| sgpr_landmark_track | cell_key \\| cell_head of each of the n_stages tables | one memset 0xff of `la_table_clear_bytes(L)` per stage; d_num by a memset 0 of 16 bytes |
+| sgpr_landmark_relocalize | cell_key \\| cell_head of each of the n_stages + 2 tables | one memset 0xff of `la_table_clear_bytes(L)` per table; lab_count \\| lab_cursor and d_num by memsets 0; list, stage radii, live slots by producer |
+| sgpr_landmark_merge | cell_key \\| cell_head; tally | memset 0xff of the two carves; memset 0 of 64 * 4 bytes; every per-record array by producer (`mrg_prepare_kernel`) |
+| sgpr_posegraph_optimize | every region | producer: the one workgroup of `pg_solve_kernel` stores each array, counts included, before the barrier after which it is read; no memset |
 """
 import ctypes
 import os
