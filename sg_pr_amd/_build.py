@@ -28,7 +28,7 @@ SOURCES = ["sgpr_embed.hip", "sgpr_score.hip", "sgpr_metrics.hip", "sgpr_modules
            "sgpr_landmark_update.hip", "sgpr_landmark_persist.hip", "sgpr_landmark_track.hip", "sgpr_landmark_relocalize.hip",
            "sgpr_landmark_merge.hip"]
 HEADERS = [os.path.join(REPO, "include", "sgpr.h"), os.path.join(CSRC, "sgpr_internal.hpp"),
-           os.path.join(CSRC, "sgpr_model.hpp"), os.path.join(CSRC, "sgpr_map.hpp"), os.path.join(CSRC, "sgpr_eval.hpp"),
+           os.path.join(CSRC, "sgpr_model.hpp"), os.path.join(CSRC, "sgpr_map.hpp"), os.path.join(CSRC, "sgpr_map_grid.hpp"), os.path.join(CSRC, "sgpr_eval.hpp"),
            os.path.join(REPO, "include", "sgpr_localize.h"), os.path.join(REPO, "include", "sgpr_landmarks.h"),
            os.path.join(REPO, "include", "sgpr_landmark_refine.h"), os.path.join(REPO, "include", "sgpr_landmark_align.h"),
            os.path.join(REPO, "include", "sgpr_landmark_update.h"), os.path.join(CSRC, "sgpr_landmark_core.hpp"),

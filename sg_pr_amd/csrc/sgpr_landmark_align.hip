@@ -18,7 +18,8 @@
 //
 // What a wave does with a scan - the eligible rule, the match, the sums, the fit, the keep rule - is la_prep_landmark and
 // la_fit_scan of sgpr_landmark_align_core.hpp, which sgpr_landmark_track.hip runs per scan and stage; the
-// kernels here are the launch shapes around them.
+// kernels here are the launch shapes around them.  The cell grid, the wave sums and the closed-form fit those two are
+// made of are sgpr_map_grid.hpp's.
 //
 // The cell table is the search of this build: it was the faster at every size measured, from 106 landmarks up (DESIGN.md
 // §31 has the timings).  -DSGPR_ALIGN_SEARCH=2 builds the form that tests every landmark instead - the variant those
@@ -32,7 +33,7 @@
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_align.h"
 #include "sgpr_landmark_align_core.hpp"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 #ifndef SGPR_ALIGN_SEARCH
 #define SGPR_ALIGN_SEARCH 1
@@ -110,32 +111,13 @@ int sgpr_landmark_align(const float* d_centers, const int32_t* d_labels, int Q, 
                         double* d_poses_out, int32_t* d_node_landmark, int32_t* d_stat, double* d_rms,
                         void* d_workspace, size_t workspace_bytes, void* stream) {
     const std::string fn = "sgpr_landmark_align";
-    if (Q < 0 || N < 0 || L < 0 || iters < 0) {
-        set_error(fn + ": " + (Q < 0 ? "Q " + std::to_string(Q) : N < 0 ? "N " + std::to_string(N)
-                               : L < 0 ? "L " + std::to_string(L) : "iters " + std::to_string(iters)) + " is negative");
-        return SGPR_E_INVALID;
-    }
+    if (!no_negative(fn, {{"Q", Q}, {"N", N}, {"L", L}, {"iters", iters}})) return SGPR_E_INVALID;
     if (min_nodes < 2) {
         set_error(fn + ": min_nodes " + std::to_string(min_nodes) + " is below 2");
         return SGPR_E_INVALID;
     }
-    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
-        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
-        return SGPR_E_INVALID;
-    }
-    if (!h_radius) {
-        set_error(fn + ": NULL h_radius");
-        return SGPR_E_INVALID;
-    }
-    for (int l = 0; l < n_labels; ++l)
-        if (!(h_radius[l] >= 0.0)) {
-            set_error(fn + ": radius of label " + std::to_string(l) + " is negative or NaN");
-            return SGPR_E_INVALID;
-        }
-    if (!(tau_z >= 0.0)) {
-        set_error(fn + ": tau_z is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+    if (!landmark_labels_ok(fn, h_radius, n_labels) || !radii_ok(fn, h_radius, n_labels)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "tau_z", tau_z)) return SGPR_E_INVALID;
     if (!la_size_ok(Q, N, L)) {
         set_error(fn + ": Q N = " + std::to_string((long long)Q * N) + " exceeds the int32 node index");
         return SGPR_E_INVALID;
@@ -147,10 +129,7 @@ int sgpr_landmark_align(const float* d_centers, const int32_t* d_labels, int Q, 
         return SGPR_E_INVALID;
     }
     const size_t need = la_table_bytes((size_t)L);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, need)) return SGPR_E_INVALID;
 
     Carver ws{static_cast<unsigned char*>(d_workspace)};
     LaArgs a = {};
@@ -172,7 +151,7 @@ int sgpr_landmark_align(const float* d_centers, const int32_t* d_labels, int Q, 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (LA_TABLE) {
         // cell_key | cell_head: empty keys, list ends (-1)
-        const hipError_t e = hipMemsetAsync(a.t.cell_key, 0xff, la_table_clear_bytes((size_t)L), s);
+        const hipError_t e = hipMemsetAsync(a.t.g.cell_key, 0xff, grid_clear_bytes((size_t)L), s);
         if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_align: memset");
     }
     const dim3 block(LA_THREADS), scan_grid((Q + LA_WAVES - 1) / LA_WAVES);

@@ -2,8 +2,9 @@
 // one search table - the eligible rule and the cell table of a stage, the match by (d2, id), the scan sums W, the
 // closed-form fit and the keep rule of include/sgpr_landmark_align.h.  sgpr_landmark_align.hip runs it once per scan,
 // sgpr_landmark_track.hip once per scan and stage, so a stage of the tracker IS an alignment, to the bit.  It is not in
-// sgpr_map.hpp: that header holds building blocks many files share (§28), this one the step of one file, declared for one
-// other.
+// sgpr_map.hpp: that header holds building blocks many files share (§28), this one the step of one file, declared for
+// the two that run it too.  The cell grid and its 9-cell walk, the wave sums, the map point and the closed-form fit it is
+// made of are sgpr_map_grid.hpp's.
 //
 // A scan is read through a small accessor (LaScanGlobal here; the tracker adds one over its LDS copy): both widen the
 // same float32 bits, so where the scan lies decides no result.
@@ -12,13 +13,12 @@
 
 #include "sgpr_internal.hpp"
 #include "sgpr_landmarks.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 namespace sgpr {
 
 #pragma clang fp contract(off)
 
-constexpr double LA_LIMIT = 137438953472.0;    // 2^37
 enum { LA_NONFINITE = 1, LA_KEPT = 2 };
 
 // the landmarks of the map, as the caller passed them
@@ -33,34 +33,20 @@ struct LaMap {
 // the search structure of one radius table: a slice of the workspace
 struct LaTable {
     int* elab;                     // [L] label of an eligible landmark, -1 of any other
-    int* next;                     // [L] linked list of the landmark's cell
-    unsigned long long* cell_key;  // [H]
-    int* cell_head;                // [H]
-    unsigned long long hmask;      // H - 1 (H a power of two)
+    CellGrid g;                    // the eligible landmarks by (label, cell)
 };
 
-inline size_t la_table_bytes(size_t L) {
-    const size_t h = table_slots(L);
-    return align256(L * 4) * 2 + align256(h * 8) + align256(h * 4);
-}
+inline size_t la_table_bytes(size_t L) { return align256(L * 4) + grid_bytes(L); }
 
-// the next la_table_bytes(L) bytes of a workspace; cell_key | cell_head are contiguous (one memset of 0xff: empty keys,
-// list ends)
+// the next la_table_bytes(L) bytes of a workspace
 inline LaTable la_table_carve(Carver& ws, size_t L) {
-    const size_t H = table_slots(L);
     LaTable t;
     t.elab = ws.take<int>(L);
-    t.next = ws.take<int>(L);
-    t.cell_key = ws.take<unsigned long long>(H);
-    t.cell_head = ws.take<int>(H);
-    t.hmask = H - 1;
+    t.g = grid_carve(ws, L);
     return t;
 }
-inline size_t la_table_clear_bytes(size_t L) { return align256(table_slots(L) * 8) + align256(table_slots(L) * 4); }
 
 inline bool la_size_ok(int Q, int N, int L) { return Q >= 0 && N >= 0 && L >= 0 && (long long)Q * (long long)N <= 0x7fffffffll; }
-
-__device__ __forceinline__ bool la_in_limit(double v) { return isfinite(v) && fabs(v) <= LA_LIMIT; }
 
 // landmark i under the radii of one table: eligible or not - its label, or -1 - and, with TABLE, an eligible landmark
 // enters the cell table and is pushed on its cell's list
@@ -71,23 +57,10 @@ __device__ __forceinline__ void la_prep_landmark(const LaMap& m, const LaTable& 
     bool ok = (!m.lm_use || m.lm_use[i] != 0) && l >= 0 && l < m.n_labels;
     const double r = ok ? radius[l] : 0.0;
     const double cx = m.lm_center[3 * (size_t)i], cy = m.lm_center[3 * (size_t)i + 1], cz = m.lm_center[3 * (size_t)i + 2];
-    ok = ok && r > 0.0 && la_in_limit(cx) && la_in_limit(cy) && la_in_limit(cz);
+    ok = ok && r > 0.0 && in_limit37(cx) && in_limit37(cy) && in_limit37(cz);
     t.elab[i] = ok ? l : -1;
     if (!ok || !TABLE) return;
-    const double cw = lm_cell_width(r);
-    const unsigned long long slot = table_insert(t.cell_key, t.hmask, lm_cell_key(l, lm_cell_coord(cx, cw), lm_cell_coord(cy, cw)));
-    t.next[i] = atomicExch(&t.cell_head[slot], i);
-}
-
-// the halving tree of W over the 64 partials of a wave; every lane gets v[0]
-__device__ __forceinline__ double la_tree(double v) {
-    for (int h = 32; h > 0; h >>= 1) v += __shfl_down(v, h);    // (lanes i < h hold v[i] + v[i + h]; the others are not read)
-    return __shfl(v, 0);
-}
-
-__device__ __forceinline__ int la_wave_sum(int v) {
-    for (int h = 32; h > 0; h >>= 1) v += __shfl_down(v, h);
-    return __shfl(v, 0);
+    grid_push(t.g, i, l, lm_cell_width(r), cx, cy);
 }
 
 // the match of a map point of label l: landmark o is better than the best so far when it passes the gate and comes
@@ -116,15 +89,9 @@ __device__ __forceinline__ void la_match(const LaMap& m, const LaTable& t, int l
 #pragma clang fp contract(off)
     const double r2 = r * r;
     if (TABLE) {
-        const double cw = lm_cell_width(r);
-        const long long ix = lm_cell_coord(mx, cw), iy = lm_cell_coord(my, cw);
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                const unsigned long long slot = table_find(t.cell_key, t.hmask, lm_cell_key(l, ix + dx, iy + dy));
-                if (slot == TABLE_EMPTY) continue;
-                for (int o = t.cell_head[slot]; o >= 0; o = t.next[o])
-                    if (t.elab[o] == l) la_test(m, o, mx, my, mz, r2, b);     // (a shared list: see lm_cell_key)
-            }
+        grid_near(t.g, l, lm_cell_width(r), mx, my, [&](int o) {
+            if (t.elab[o] == l) la_test(m, o, mx, my, mz, r2, b);
+        });
     } else {
         for (int o = 0; o < m.L; ++o)
             if (t.elab[o] == l) la_test(m, o, mx, my, mz, r2, b);
@@ -170,10 +137,11 @@ __device__ __forceinline__ LaFit la_fit_scan(const LaMap& m, const LaTable& t, c
         for (int n = lane; n < N; n += 64) {
             const int l = sc.label(n);
             const double x = sc.x(n), y = sc.y(n), mz = sc.z(n);
-            const double mx = (X.c * x - X.s * y) + X.x, my = (X.s * x + X.c * y) + X.y;
+            double mx, my;
+            se2_apply(X, x, y, &mx, &my);
             bool alive = l >= 0 && l < m.n_labels;
             const double r = alive ? radius[l] : 0.0;
-            alive = alive && r > 0.0 && la_in_limit(mx) && la_in_limit(my) && la_in_limit(mz);
+            alive = alive && r > 0.0 && in_limit37(mx) && in_limit37(my) && in_limit37(mz);
             LaBest b = {-2, 0.0, 0.0, 0.0};
             if (alive) la_match<TABLE>(m, t, l, r, mx, my, mz, b);
             row[n] = alive ? b.id : -1;
@@ -186,15 +154,15 @@ __device__ __forceinline__ LaFit la_fit_scan(const LaMap& m, const LaTable& t, c
             sly += b.cy;
             f.sd2 += b.d2;
         }
-        f.matched = la_wave_sum(cnt);
-        f.live = la_wave_sum(lv);
+        f.matched = wave_sum(cnt);
+        f.live = wave_sum(lv);
         if (k == iters) break;
         if (f.matched < min_nodes) {
             f.flags |= LA_KEPT;
             break;
         }
         const double dn = (double)f.matched;
-        const double pbx = la_tree(spx) / dn, pby = la_tree(spy) / dn, lbx = la_tree(slx) / dn, lby = la_tree(sly) / dn;
+        const double pbx = wave_tree(spx) / dn, pby = wave_tree(spy) / dn, lbx = wave_tree(slx) / dn, lby = wave_tree(sly) / dn;
         double ar = 0.0, ai = 0.0;
         for (int n = lane; n < N; n += 64) {
             const int id = row[n];
@@ -205,19 +173,14 @@ __device__ __forceinline__ LaFit la_fit_scan(const LaMap& m, const LaTable& t, c
             ar += px * qx + py * qy;
             ai += px * qy - py * qx;
         }
-        ar = la_tree(ar);
-        ai = la_tree(ai);
-        const double h = sqrt(ar * ar + ai * ai);
-        Se2 F;
-        F.c = ar / h;
-        F.s = ai / h;
-        F.x = lbx - (F.c * pbx - F.s * pby);
-        F.y = lby - (F.s * pbx + F.c * pby);
-        if (!(h > 0.0 && isfinite(h)) || !se2_finite(F)) {      // (the same bits in every lane: a uniform branch)
+        ar = wave_tree(ar);
+        ai = wave_tree(ai);
+        const Se2Fit fit = se2_fit(pbx, pby, lbx, lby, ar, ai);
+        if (fit.degenerate()) {                                 // (the same bits in every lane: a uniform branch)
             f.flags |= LA_KEPT;
             break;
         }
-        X = F;
+        X = fit.F;
         ++f.refits;
     }
     return f;
@@ -226,7 +189,7 @@ __device__ __forceinline__ LaFit la_fit_scan(const LaMap& m, const LaTable& t, c
 // d_rms of a fitted scan: sqrt(W(d2) / matched), the quiet NaN without a match; every lane of the wave calls it
 __device__ __forceinline__ double la_rms(const LaFit& f) {
 #pragma clang fp contract(off)
-    const double total = la_tree(f.sd2);
+    const double total = wave_tree(f.sd2);
     return f.matched > 0 ? sqrt(total / (double)f.matched) : __longlong_as_double(0x7ff8000000000000ll);
 }
 

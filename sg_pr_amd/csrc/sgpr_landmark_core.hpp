@@ -3,20 +3,16 @@
 // sgpr_landmark_update over the nodes a map does not explain.  It is not in sgpr_map.hpp: that header holds building
 // blocks many files share (§28), this one the launch sequence of one file, declared for one other.
 //
-// Also here, because both files must form them with the same bits: the constants of the fixed-point sums and the map
-// point / live rule of include/sgpr_landmarks.h.
+// Also here, because both files must form it with the same bits: the map point / live rule of include/sgpr_landmarks.h.
+// The constants of the fixed-point sums, the 2^37 limit and the map point itself are sgpr_map_grid.hpp's.
 #pragma once
 #include "sgpr_internal.hpp"
 #include "sgpr_landmarks.h"
+#include "sgpr_map_grid.hpp"
 
 namespace sgpr {
 
-constexpr int LM_THREADS = 256;
-constexpr double LM_FIX = 16777216.0;          // 2^24
-constexpr double LM_LIMIT = 137438953472.0;    // 2^37
-constexpr double LM_D2_CAP = 1048576.0;        // 2^20
-
-__device__ __forceinline__ bool lm_in_limit(double v) { return isfinite(v) && fabs(v) <= LM_LIMIT; }
+constexpr int LM_THREADS = NUMBER_THREADS;
 
 // MAP POINT and LIVE of node p of scan g = p / N under poses[g]; `radius` is the table in the kernel's arguments.
 // -> live; m = the map point (written whether live or not)
@@ -24,14 +20,12 @@ __device__ __forceinline__ bool lm_map_point(const float* centers, const double*
                                              int p, int g, int l, double m[3]) {
 #pragma clang fp contract(off)
     const double x = (double)centers[3 * (size_t)p], y = (double)centers[3 * (size_t)p + 1], z = (double)centers[3 * (size_t)p + 2];
-    const double c = poses[4 * (size_t)g], s = poses[4 * (size_t)g + 1], X = poses[4 * (size_t)g + 2], Y = poses[4 * (size_t)g + 3];
-    m[0] = (c * x - s * y) + X;
-    m[1] = (s * x + c * y) + Y;
+    const Se2 X = {poses[4 * (size_t)g], poses[4 * (size_t)g + 1], poses[4 * (size_t)g + 2], poses[4 * (size_t)g + 3]};
+    se2_apply(X, x, y, &m[0], &m[1]);
     m[2] = z;
     bool live = l >= 0 && l < n_labels;
     const double r = live ? radius[l] : 0.0;
-    return live && r > 0.0 && isfinite(c) && isfinite(s) && isfinite(X) && isfinite(Y) && lm_in_limit(m[0]) && lm_in_limit(m[1]) &&
-           lm_in_limit(m[2]);
+    return live && r > 0.0 && se2_finite(X) && in_limit37(m[0]) && in_limit37(m[1]) && in_limit37(m[2]);
 }
 
 // One fusing job.  The arguments are checked by the caller; G N > 0.

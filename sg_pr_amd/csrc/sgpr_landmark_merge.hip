@@ -26,7 +26,9 @@
 // The cell table and the union-find are sgpr_map.hpp's, with their SIZING, VISIBILITY and TERMINATION arguments: the
 // table has table_slots(L_a + L_b) slots and every key in it belongs to some record; the lists are complete before the
 // kernel that walks them starts; the forest is the only memory another workgroup rewrites while it is read.  Every loop
-// is bounded by a list's length or the forest's depth, and no wave waits for another workgroup.
+// is bounded by a list's length or the forest's depth, and no wave waits for another workgroup.  The push on a cell's
+// list, the linking step of mrg_union_kernel, the count, the scan and the rank of the numbering and the eligible rule are
+// sgpr_map_grid.hpp's (grid_push, link_item, block_count, scan_block_counts, rank_in_block, record_eligible).
 //
 // CELLS.  An eligible centre obeys |p_k| <= |p_k n| <= 2^38, one bit more than the 2^37 of sgpr_map.hpp's proof that two
 // points in range are never two cells apart: the two rounded quotients then err by 2^-14 each, 1.3e-4 together, still
@@ -44,7 +46,7 @@
 
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_merge.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 namespace sgpr {
 
@@ -52,12 +54,7 @@ namespace sgpr {
 
 namespace {
 
-constexpr int MRG_THREADS = 256;
-constexpr int MRG_SCAN_THREADS = 1024;
-constexpr double MRG_FIX = 16777216.0;                 // 2^24
-constexpr double MRG_V_CAP = 1048576.0;                // 2^20
-constexpr int MRG_MAX_COUNT = 262144;                  // 2^18
-constexpr double MRG_SUM_LIMIT = 274877906944.0;       // 2^38
+constexpr int MRG_THREADS = NUMBER_THREADS;
 constexpr long long MRG_COUNT_TOP = 0x7fffffffll;
 
 struct MrgWs {
@@ -78,6 +75,8 @@ struct MrgWs {
     int* blk_roots;                // [B] roots per workgroup; after the scan: roots before the workgroup
     int* tally;                    // [64] (dropped by a mask, dropped as ineligible, fused components, L')
     unsigned long long hmask;      // H - 1 (H a power of two)
+    // (next, cell_key, cell_head, hmask) as the grid the shared steps take
+    __device__ __forceinline__ CellGrid grid() const { return CellGrid{next, cell_key, cell_head, hmask}; }
 };
 
 struct MrgMap {
@@ -138,22 +137,13 @@ __global__ __launch_bounds__(MRG_THREADS) void mrg_prepare_kernel(const MrgWs w,
         const int i = in_b ? t - a.L_a : t;
         double px = m.center[3 * (size_t)i], py = m.center[3 * (size_t)i + 1];
         const double pz = m.center[3 * (size_t)i + 2];
-        if (in_b && a.has_pose) {
-            const double x = px, y = py, c = a.pose[0], s = a.pose[1];
-            px = (c * x - s * y) + a.pose[2];
-            py = (s * x + c * y) + a.pose[3];
-        }
+        if (in_b && a.has_pose) se2_apply(Se2{a.pose[0], a.pose[1], a.pose[2], a.pose[3]}, px, py, &px, &py);
         w.p[3 * (size_t)t] = px;
         w.p[3 * (size_t)t + 1] = py;
         w.p[3 * (size_t)t + 2] = pz;
         const int l = m.label[i], n = m.count[i];
-        const double sp = m.spread[i], n0 = (double)n;
         const bool kept = !m.keep || m.keep[i] != 0;
-        bool ok = l >= 0 && l < a.n_labels && n >= 1 && n <= MRG_MAX_COUNT;
-        ok = ok && a.radius[ok ? l : 0] > 0.0;
-        ok = ok && isfinite(sp) && sp >= 0.0;
-        ok = ok && isfinite(px) && fabs(px * n0) <= MRG_SUM_LIMIT && isfinite(py) && fabs(py * n0) <= MRG_SUM_LIMIT &&
-             isfinite(pz) && fabs(pz * n0) <= MRG_SUM_LIMIT;
+        const bool ok = record_eligible(l, n, m.spread[i], px, py, pz, a.radius, a.n_labels);
         masked = !kept;
         unfit = kept && !ok;
         const bool live = kept && ok;
@@ -168,14 +158,8 @@ __global__ __launch_bounds__(MRG_THREADS) void mrg_prepare_kernel(const MrgWs w,
         w.sum[3 * (size_t)t] = 0;
         w.sum[3 * (size_t)t + 1] = 0;
         w.sum[3 * (size_t)t + 2] = 0;
-        if (live) {
-            const double cw = lm_cell_width(a.radius[l]);
-            const unsigned long long slot =
-                table_insert(w.cell_key, w.hmask, lm_cell_key(l, lm_cell_coord(px, cw), lm_cell_coord(py, cw)));
-            w.next[t] = atomicExch(&w.cell_head[slot], t);
-        } else {
-            w.next[t] = -1;
-        }
+        if (live) grid_push(w.grid(), t, l, lm_cell_width(a.radius[l]), px, py);
+        else w.next[t] = -1;
     }
     const unsigned long long masks = __ballot(masked), unfits = __ballot(unfit);
     if ((threadIdx.x & 63) == 0) {
@@ -187,23 +171,7 @@ __global__ __launch_bounds__(MRG_THREADS) void mrg_prepare_kernel(const MrgWs w,
 __global__ __launch_bounds__(MRG_THREADS) void mrg_union_kernel(const MrgWs w, const MrgArgs a) {
     const int t = blockIdx.x * MRG_THREADS + threadIdx.x;
     if (t >= a.T) return;
-    const int l = w.lab[t];
-    if (l < 0) return;
-    const double r = a.radius[l], r2 = r * r, tau_z = a.tau_z;
-    const double cw = lm_cell_width(r);
-    const double px = w.p[3 * (size_t)t], py = w.p[3 * (size_t)t + 1], pz = w.p[3 * (size_t)t + 2];
-    const long long ix = lm_cell_coord(px, cw), iy = lm_cell_coord(py, cw);
-    for (int dy = -1; dy <= 1; ++dy)
-        for (int dx = -1; dx <= 1; ++dx) {
-            const unsigned long long slot = table_find(w.cell_key, w.hmask, lm_cell_key(l, ix + dx, iy + dy));
-            if (slot == TABLE_EMPTY) continue;
-            for (int o = w.cell_head[slot]; o >= 0; o = w.next[o]) {
-                if (o >= t || w.lab[o] != l) continue;          // every unordered pair once; (a shared list: see lm_cell_key)
-                const double ex = px - w.p[3 * (size_t)o], ey = py - w.p[3 * (size_t)o + 1];
-                const double d2 = ex * ex + ey * ey;
-                if (d2 <= r2 && fabs(pz - w.p[3 * (size_t)o + 2]) <= tau_z) uf_unite(w.parent, t, o);
-            }
-        }
+    link_item(w.grid(), w.p, w.lab, w.parent, a.radius, a.tau_z, t);
 }
 
 __global__ __launch_bounds__(MRG_THREADS) void mrg_flatten_kernel(const MrgWs w, const MrgArgs a) {
@@ -220,42 +188,18 @@ __global__ __launch_bounds__(MRG_THREADS) void mrg_flatten_kernel(const MrgWs w,
         atomicAdd(&w.members[root], 1);
         for (int k = 0; k < 3; ++k)
             atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)root + k]),
-                      (unsigned long long)llrint((w.p[3 * (size_t)t + k] * n) * MRG_FIX));
+                      (unsigned long long)llrint((w.p[3 * (size_t)t + k] * n) * MAP_FIX));
         atomicOr(&w.sess[root], rec.sessions);
         atomicMin(&w.first[root], rec.first);
     }
-    const unsigned long long ball = __ballot(live && root == t);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(ball);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int i = 0; i < MRG_THREADS / 64; ++i) s += wsum[i];
-        w.blk_roots[blockIdx.x] = s;
-    }
+    const int roots = block_count(live && root == t, wsum);
+    if (threadIdx.x == 0) w.blk_roots[blockIdx.x] = roots;
 }
 
-__global__ __launch_bounds__(MRG_SCAN_THREADS) void mrg_scan_kernel(const MrgWs w, const MrgArgs a) {
-    __shared__ int part[MRG_SCAN_THREADS];
-    const int t = threadIdx.x;
-    const int seg = (a.B + MRG_SCAN_THREADS - 1) / MRG_SCAN_THREADS;
-    const int lo = min(t * seg, a.B), hi = min(lo + seg, a.B);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += w.blk_roots[i];
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < MRG_SCAN_THREADS; off <<= 1) {      // inclusive scan of the segment sums
-        const int u = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += u;
-        __syncthreads();
-    }
-    int run = part[t] - s;
-    for (int i = lo; i < hi; ++i) {
-        const int c = w.blk_roots[i];
-        w.blk_roots[i] = run;
-        run += c;
-    }
-    if (t == MRG_SCAN_THREADS - 1) w.tally[3] = part[t];
+__global__ __launch_bounds__(SCAN_THREADS) void mrg_scan_kernel(const MrgWs w, const MrgArgs a) {
+    __shared__ int part[SCAN_THREADS];
+    scan_block_counts<false>(w.blk_roots, nullptr, a.B, part, nullptr);
+    if (threadIdx.x == SCAN_THREADS - 1) w.tally[3] = part[threadIdx.x];
 }
 
 __global__ __launch_bounds__(MRG_THREADS) void mrg_record_kernel(const MrgWs w, const MrgArgs a) {
@@ -263,22 +207,17 @@ __global__ __launch_bounds__(MRG_THREADS) void mrg_record_kernel(const MrgWs w, 
     const int t = blockIdx.x * MRG_THREADS + threadIdx.x;
     const bool root = t < a.T && w.lab[t] >= 0 && w.next[t] == t;
     const int members = root ? w.members[t] : 0;
-    const unsigned long long ball = __ballot(root), fused = __ballot(members > 1);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        wcount[wave] = __popcll(ball);
-        if (fused) atomicAdd(&w.tally[2], __popcll(fused));
-    }
-    __syncthreads();
+    const unsigned long long fused = __ballot(members > 1);
+    if ((threadIdx.x & 63) == 0 && fused) atomicAdd(&w.tally[2], __popcll(fused));
+    const int rank = rank_in_block(root, wcount);
     if (!root) return;
-    int id = w.blk_roots[blockIdx.x] + __popcll(ball & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) id += wcount[v];
+    const int id = w.blk_roots[blockIdx.x] + rank;
     w.id[t] = id;
     double c[3];
     if (members > 1) {
         const double cnt = (double)(long long)w.cnt[t];
         for (int k = 0; k < 3; ++k) {
-            c[k] = (double)w.sum[3 * (size_t)t + k] / (cnt * MRG_FIX);
+            c[k] = (double)w.sum[3 * (size_t)t + k] / (cnt * MAP_FIX);
             w.centre[3 * (size_t)t + k] = c[k];
         }
     } else {
@@ -314,7 +253,7 @@ __global__ __launch_bounds__(MRG_THREADS) void mrg_spread_kernel(const MrgWs w, 
     const MrgRest rec = mrg_rest(a, t);
     const double ax = w.p[3 * (size_t)t] - w.centre[3 * (size_t)root], ay = w.p[3 * (size_t)t + 1] - w.centre[3 * (size_t)root + 1];
     const double v = rec.spread * rec.spread + (ax * ax + ay * ay);
-    atomicAdd(&w.q[root], (unsigned long long)llrint((fmin(v, MRG_V_CAP) * (double)rec.count) * MRG_FIX));
+    atomicAdd(&w.q[root], (unsigned long long)llrint((fmin(v, MAP_D2_CAP) * (double)rec.count) * MAP_FIX));
 }
 
 __global__ __launch_bounds__(MRG_THREADS) void mrg_finish_kernel(const MrgWs w, const MrgArgs a) {
@@ -328,15 +267,14 @@ __global__ __launch_bounds__(MRG_THREADS) void mrg_finish_kernel(const MrgWs w, 
     if (t >= a.T || w.lab[t] < 0 || w.next[t] != t || w.members[t] < 2) return;
     const int id = w.id[t];
     if (id >= a.max_out) return;
-    a.out_spread[id] = sqrt((double)w.q[t] / ((double)(long long)w.cnt[t] * MRG_FIX));
+    a.out_spread[id] = sqrt((double)w.q[t] / ((double)(long long)w.cnt[t] * MAP_FIX));
 }
 
 bool mrg_size_ok(int L_a, int L_b) { return L_a >= 0 && L_b >= 0 && (long long)L_a + (long long)L_b <= 0x7fffffffll; }
 
 size_t mrg_ws_bytes(size_t T) {
-    const size_t h = table_slots(T), b = (T + MRG_THREADS - 1) / MRG_THREADS;
-    return align256(T * 24) * 3 + align256(T * 8) * 3 + align256(T * 4) * 6 + align256(h * 8) + align256(h * 4) + align256(b * 4) +
-           align256(64 * 4);
+    const size_t b = (T + MRG_THREADS - 1) / MRG_THREADS;
+    return align256(T * 24) * 3 + align256(T * 8) * 3 + align256(T * 4) * 5 + grid_bytes(T) + align256(b * 4) + align256(64 * 4);
 }
 
 }  // namespace
@@ -361,15 +299,7 @@ int sgpr_landmark_merge(const double* d_a_center, const int32_t* d_a_label, cons
                         int32_t* d_out_first, uint64_t* d_out_sessions, double* d_out_spread, int32_t* d_old_to_new,
                         int32_t* d_num, void* d_workspace, size_t workspace_bytes, void* stream) {
     const std::string fn = "sgpr_landmark_merge";
-    const struct {
-        const char* name;
-        int v;
-    } signs[] = {{"L_a", L_a}, {"L_b", L_b}, {"max_out", max_out}, {"first_base", first_base}};
-    for (const auto& s : signs)
-        if (s.v < 0) {
-            set_error(fn + ": " + s.name + " " + std::to_string(s.v) + " is negative");
-            return SGPR_E_INVALID;
-        }
+    if (!no_negative(fn, {{"L_a", L_a}, {"L_b", L_b}, {"max_out", max_out}, {"first_base", first_base}})) return SGPR_E_INVALID;
     if (!mrg_size_ok(L_a, L_b)) {
         set_error(fn + ": L_a + L_b = " + std::to_string((long long)L_a + L_b) + " exceeds the int32 record index");
         return SGPR_E_INVALID;
@@ -378,23 +308,8 @@ int sgpr_landmark_merge(const double* d_a_center, const int32_t* d_a_label, cons
         set_error(fn + ": session_shift " + std::to_string(session_shift) + " outside [0, 63]");
         return SGPR_E_INVALID;
     }
-    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
-        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
-        return SGPR_E_INVALID;
-    }
-    if (!h_radius) {
-        set_error(fn + ": NULL h_radius");
-        return SGPR_E_INVALID;
-    }
-    for (int l = 0; l < n_labels; ++l)
-        if (!(h_radius[l] >= 0.0)) {
-            set_error(fn + ": radius of label " + std::to_string(l) + " is negative or NaN");
-            return SGPR_E_INVALID;
-        }
-    if (!(tau_z >= 0.0)) {
-        set_error(fn + ": tau_z is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+    if (!landmark_labels_ok(fn, h_radius, n_labels) || !radii_ok(fn, h_radius, n_labels)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "tau_z", tau_z)) return SGPR_E_INVALID;
     if (h_pose)
         for (int k = 0; k < 4; ++k)
             if (!std::isfinite(h_pose[k])) {
@@ -410,11 +325,7 @@ int sgpr_landmark_merge(const double* d_a_center, const int32_t* d_a_label, cons
         set_error(fn + ": NULL argument");
         return SGPR_E_INVALID;
     }
-    const size_t need = mrg_ws_bytes(T);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, mrg_ws_bytes(T))) return SGPR_E_INVALID;
 
     const size_t H = table_slots(T);
     const int B = (int)((T + MRG_THREADS - 1) / MRG_THREADS);
@@ -465,14 +376,14 @@ int sgpr_landmark_merge(const double* d_a_center, const int32_t* d_a_label, cons
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     // cell_key | cell_head: empty keys, list ends (-1)
-    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, align256(H * 8) + align256(H * 4), s);
+    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, grid_clear_bytes(T), s);
     if (e == hipSuccess) e = hipMemsetAsync(w.tally, 0, 64 * 4, s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_merge: memset");
     const dim3 grid(B), block(MRG_THREADS);
     hipLaunchKernelGGL(mrg_prepare_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(mrg_union_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(mrg_flatten_kernel, grid, block, 0, s, w, a);
-    hipLaunchKernelGGL(mrg_scan_kernel, dim3(1), dim3(MRG_SCAN_THREADS), 0, s, w, a);
+    hipLaunchKernelGGL(mrg_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, w, a);
     hipLaunchKernelGGL(mrg_record_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(mrg_spread_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(mrg_finish_kernel, grid, block, 0, s, w, a);

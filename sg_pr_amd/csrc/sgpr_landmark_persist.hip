@@ -28,6 +28,8 @@
 // list to ONE lane, and with max_range = +inf one cell holds every landmark.  Two memsets instead of one: the table's
 // empty key is all ones (sgpr_map.hpp), the cell counts start at zero.  The workspace is the same for both.
 // No floating-point atomics, no inline assembly, plain vector stores; no workgroup waits for another.
+// The 2^37 limit, the map point, the wave sum and the slot of a cell are sgpr_map_grid.hpp's (in_limit37, se2_apply,
+// wave_sum, grid_cell_slot); the rectangular walk of pass C visits another neighbourhood than grid_near's and stays here.
 #include <math.h>
 
 #include <cmath>
@@ -35,7 +37,7 @@
 
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_persist.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 #ifndef SGPR_PERSIST_SEARCH
 #define SGPR_PERSIST_SEARCH 2
@@ -49,7 +51,6 @@ namespace {
 
 constexpr int LP_THREADS = 256;
 constexpr int LP_WAVES = LP_THREADS / 64;
-constexpr double LP_LIMIT = 137438953472.0;        // 2^37
 constexpr double LP_CELL_CLAMP = 549755813888.0;   // 2^39: past every cell coordinate of a landmark
 constexpr double LP_MIN_PAD = 1e-100;
 constexpr int LP_OWNER_STEP = 8;     // lower slots looked at between two looks at the answer (pass B)
@@ -83,8 +84,6 @@ struct LpArgs {
     double max_range, margin, ratio, cell_w;
     double radius[SGPR_LANDMARK_MAX_LABELS];
 };
-
-__device__ __forceinline__ bool lp_in_limit(double v) { return isfinite(v) && fabs(v) <= LP_LIMIT; }
 
 // Width of a coarse cell, from the largest view range any scan of the call can have: vcap = max_range - margin >= v_q
 // (min(max_range, .) <= max_range and a difference is rounded monotonically).  Half of it, and never below LM_MIN_CELL:
@@ -127,12 +126,12 @@ __global__ __launch_bounds__(LP_THREADS) void lp_prep_kernel(const LpArgs a) {
     bool ok = (!a.lm_use || a.lm_use[i] != 0) && l >= 0 && l < a.n_labels;
     const double r = ok ? a.radius[l] : 0.0;
     const double cx = a.lm_center[3 * (size_t)i], cy = a.lm_center[3 * (size_t)i + 1], cz = a.lm_center[3 * (size_t)i + 2];
-    ok = ok && r > 0.0 && lp_in_limit(cx) && lp_in_limit(cy) && lp_in_limit(cz);
+    ok = ok && r > 0.0 && in_limit37(cx) && in_limit37(cy) && in_limit37(cz);
     a.elab[i] = ok ? l : -1;
     a.expected[i] = 0;
     a.seen[i] = 0;
     if (!ok || !LP_TABLE) return;
-    const unsigned long long slot = table_insert(a.cell_key, a.hmask, lm_cell_key(0, lm_cell_coord(cx, a.cell_w), lm_cell_coord(cy, a.cell_w)));
+    const unsigned long long slot = grid_cell_slot(a.cell_key, a.hmask, 0, a.cell_w, cx, cy);     // (counted, not listed: see above)
     a.lslot[i] = (unsigned)slot;
     atomicAdd(&a.cell_cnt[slot], 1);
 }
@@ -150,11 +149,6 @@ __global__ __launch_bounds__(LP_THREADS) void lp_fill_kernel(const LpArgs a) {
     a.item[atomicSub(&a.cell_pos[a.lslot[i]], 1) - 1] = i;
 }
 
-__device__ __forceinline__ int lp_wave_sum(int v) {
-    for (int h = 32; h > 0; h >>= 1) v += __shfl_down(v, h);
-    return __shfl(v, 0);
-}
-
 // the live rule for slot n of a scan under X; x, y: the widened centre in the sensor frame
 __device__ __forceinline__ bool lp_live(const LpArgs& a, const Se2& X, bool finite, const float* cen, const int32_t* lab, size_t n,
                                         int& l, double& x, double& y) {
@@ -162,10 +156,11 @@ __device__ __forceinline__ bool lp_live(const LpArgs& a, const Se2& X, bool fini
     x = (double)cen[3 * n];
     y = (double)cen[3 * n + 1];
     const double mz = (double)cen[3 * n + 2];
-    const double mx = (X.c * x - X.s * y) + X.x, my = (X.s * x + X.c * y) + X.y;
+    double mx, my;
+    se2_apply(X, x, y, &mx, &my);
     bool alive = finite && l >= 0 && l < a.n_labels;
     const double r = alive ? a.radius[l] : 0.0;
-    return alive && r > 0.0 && lp_in_limit(mx) && lp_in_limit(my) && lp_in_limit(mz);
+    return alive && r > 0.0 && in_limit37(mx) && in_limit37(my) && in_limit37(mz);
 }
 
 // slot n observes landmark id: the node is live and the landmark is eligible and of its label
@@ -212,7 +207,7 @@ __global__ __launch_bounds__(LP_THREADS) void lp_tally_kernel(const LpArgs a) {
         far2 = fmax(far2, x * x + y * y);
     }
     for (int h = 32; h > 0; h >>= 1) far2 = fmax(far2, __shfl_xor(far2, h));     // (finite and >= 0: a maximum is exact)
-    const int live = lp_wave_sum(lv);
+    const int live = wave_sum(lv);
     const double v = fmin(a.max_range, sqrt(far2)) - a.margin;
     const bool has_view = v > 0.0;
     const double v2 = v * v;
@@ -281,8 +276,8 @@ __global__ __launch_bounds__(LP_THREADS) void lp_tally_kernel(const LpArgs a) {
             }
         }
     }
-    n_exp = lp_wave_sum(n_exp);
-    n_seen = lp_wave_sum(n_seen);
+    n_exp = wave_sum(n_exp);
+    n_seen = wave_sum(n_seen);
     if (lane != 0) return;
     a.view[q] = v;
     int32_t* st = a.scan_stat + 4 * (size_t)q;
@@ -336,28 +331,9 @@ int sgpr_landmark_persist(const float* d_centers, const int32_t* d_labels, int Q
                           int32_t* d_expected, int32_t* d_seen, uint8_t* d_keep, int32_t* d_scan_stat,
                           double* d_view, int32_t* d_num, void* d_workspace, size_t workspace_bytes, void* stream) {
     const std::string fn = "sgpr_landmark_persist";
-    if (Q < 0 || N < 0 || L < 0 || min_expected < 0) {
-        set_error(fn + ": " + (Q < 0 ? "Q " + std::to_string(Q) : N < 0 ? "N " + std::to_string(N)
-                               : L < 0 ? "L " + std::to_string(L) : "min_expected " + std::to_string(min_expected)) + " is negative");
-        return SGPR_E_INVALID;
-    }
-    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
-        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
-        return SGPR_E_INVALID;
-    }
-    if (!h_radius) {
-        set_error(fn + ": NULL h_radius");
-        return SGPR_E_INVALID;
-    }
-    for (int l = 0; l < n_labels; ++l)
-        if (!(h_radius[l] >= 0.0)) {
-            set_error(fn + ": radius of label " + std::to_string(l) + " is negative or NaN");
-            return SGPR_E_INVALID;
-        }
-    if (!(max_range >= 0.0)) {
-        set_error(fn + ": max_range is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+    if (!no_negative(fn, {{"Q", Q}, {"N", N}, {"L", L}, {"min_expected", min_expected}})) return SGPR_E_INVALID;
+    if (!landmark_labels_ok(fn, h_radius, n_labels) || !radii_ok(fn, h_radius, n_labels)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "max_range", max_range)) return SGPR_E_INVALID;
     if (!(margin >= 0.0 && std::isfinite(margin))) {
         set_error(fn + ": margin is negative or not finite");
         return SGPR_E_INVALID;
@@ -377,10 +353,7 @@ int sgpr_landmark_persist(const float* d_centers, const int32_t* d_labels, int Q
         return SGPR_E_INVALID;
     }
     const size_t need = lp_ws_bytes((size_t)L);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, need)) return SGPR_E_INVALID;
 
     Carver ws{static_cast<unsigned char*>(d_workspace)};
     const size_t H = table_slots((size_t)L);

@@ -2,7 +2,9 @@
 // T alternations of "every landmark's centre is the mean of its observations" and "every scan is rigidly re-fitted to
 // the centres of its nodes' landmarks in closed form".  Float64 with every operation rounded on its own; the sums over a
 // landmark and over the map are fixed-point integer atomics (any order, same sums), the sums over one scan are the
-// header's W: a lane's slots in ascending order, then a halving tree of shuffles.
+// header's W: a lane's slots in ascending order, then a halving tree of shuffles (wave_tree).  The tree, the wave sums,
+// the map point, the closed-form fit and the fixed-point constants are sgpr_map_grid.hpp's, shared with
+// sgpr_landmark_align_core.hpp.
 //
 //   rf_accumulate_kernel  step k, one thread per node: the map point under X_k; a used node adds 1 and its two
 //                         fixed-point coordinates to its landmark's slots of accumulator set k & 1 (three 64-bit integer
@@ -25,7 +27,7 @@
 
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_refine.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 namespace sgpr {
 
@@ -36,9 +38,6 @@ namespace {
 constexpr int RF_THREADS = 256;
 constexpr int RF_WAVES = RF_THREADS / 64;
 constexpr int RF_FINISH_THREADS = 1024;
-constexpr double RF_FIX = 16777216.0;          // 2^24
-constexpr double RF_LIMIT = 137438953472.0;    // 2^37
-constexpr double RF_D2_CAP = 1048576.0;        // 2^20
 constexpr int RF_SCALARS = 32;                 // uint64 words: Q[2], n[2], re-fitted, kept (the rest pads to 256 bytes)
 
 enum { RF_Q = 0, RF_N = 2, RF_REFIT = 4, RF_KEPT = 5 };
@@ -54,8 +53,6 @@ struct RfArgs {
     int G, N, L, P, min_nodes;
 };
 
-__device__ __forceinline__ bool rf_in_limit(double v) { return isfinite(v) && fabs(v) <= RF_LIMIT; }
-
 __device__ __forceinline__ Se2 rf_load_pose(const double* X, int g) {
     const double* p = X + 4 * (size_t)g;
     return Se2{p[0], p[1], p[2], p[3]};
@@ -69,13 +66,12 @@ __device__ __forceinline__ bool rf_node(const RfArgs& a, const Se2& X, bool pose
     used = used && a.lm_use[id] != 0;
     x = (double)a.centers[3 * (size_t)p];
     y = (double)a.centers[3 * (size_t)p + 1];
-    mx = (X.c * x - X.s * y) + X.x;
-    my = (X.s * x + X.c * y) + X.y;
-    return used && rf_in_limit(mx) && rf_in_limit(my);
+    se2_apply(X, x, y, &mx, &my);
+    return used && in_limit37(mx) && in_limit37(my);
 }
 
 __device__ __forceinline__ double rf_cost(u64 q, u64 n) {
-    return n == 0 ? __longlong_as_double(0x7ff8000000000000ll) : sqrt((double)q / ((double)n * RF_FIX));
+    return n == 0 ? __longlong_as_double(0x7ff8000000000000ll) : sqrt((double)q / ((double)n * MAP_FIX));
 }
 
 __global__ __launch_bounds__(RF_THREADS) void rf_accumulate_kernel(const RfArgs a, const double* X, u64* acc, u64* scal,
@@ -92,19 +88,8 @@ __global__ __launch_bounds__(RF_THREADS) void rf_accumulate_kernel(const RfArgs 
     int id;
     if (!rf_node(a, Xg, se2_finite(Xg), p, x, y, mx, my, id)) return;
     atomicAdd(&acc[3 * (size_t)id], 1ull);
-    atomicAdd(&acc[3 * (size_t)id + 1], (u64)llrint(mx * RF_FIX));
-    atomicAdd(&acc[3 * (size_t)id + 2], (u64)llrint(my * RF_FIX));
-}
-
-// the halving tree of W over the 64 partials of a wave; every lane gets v[0]
-__device__ __forceinline__ double rf_tree(double v) {
-    for (int h = 32; h > 0; h >>= 1) v += __shfl_down(v, h);    // (lanes i < h hold v[i] + v[i + h]; the others are not read)
-    return __shfl(v, 0);
-}
-
-__device__ __forceinline__ u64 rf_wave_sum(u64 v) {
-    for (int h = 32; h > 0; h >>= 1) v += __shfl_down(v, h);
-    return __shfl(v, 0);
+    atomicAdd(&acc[3 * (size_t)id + 1], (u64)llrint(mx * MAP_FIX));
+    atomicAdd(&acc[3 * (size_t)id + 2], (u64)llrint(my * MAP_FIX));
 }
 
 __global__ __launch_bounds__(RF_THREADS) void rf_fit_kernel(const RfArgs a, const double* X, double* X_next,
@@ -124,19 +109,19 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fit_kernel(const RfArgs a, cons
         double x, y, mx, my;
         int id;
         if (!rf_node(a, Xg, pose_ok, base + n, x, y, mx, my, id)) continue;
-        const double den = (double)acc[3 * (size_t)id] * RF_FIX;
+        const double den = (double)acc[3 * (size_t)id] * MAP_FIX;
         const double lx = (double)(long long)acc[3 * (size_t)id + 1] / den, ly = (double)(long long)acc[3 * (size_t)id + 2] / den;
         const double ex = mx - lx, ey = my - ly;
         const double d2 = ex * ex + ey * ey;
-        q += (u64)llrint(fmin(d2, RF_D2_CAP) * RF_FIX);
+        q += (u64)llrint(fmin(d2, MAP_D2_CAP) * MAP_FIX);
         cnt += 1ull;
         spx += x;
         spy += y;
         slx += lx;
         sly += ly;
     }
-    q = rf_wave_sum(q);
-    const int ng = (int)rf_wave_sum(cnt);
+    q = wave_sum(q);
+    const int ng = (int)wave_sum(cnt);
     if (lane == 0 && ng > 0) {
         atomicAdd(&scal[RF_Q + slot], q);
         atomicAdd(&scal[RF_N + slot], (u64)ng);
@@ -152,31 +137,26 @@ __global__ __launch_bounds__(RF_THREADS) void rf_fit_kernel(const RfArgs a, cons
         return;
     }
     const double dn = (double)ng;
-    const double pbx = rf_tree(spx) / dn, pby = rf_tree(spy) / dn, lbx = rf_tree(slx) / dn, lby = rf_tree(sly) / dn;
+    const double pbx = wave_tree(spx) / dn, pby = wave_tree(spy) / dn, lbx = wave_tree(slx) / dn, lby = wave_tree(sly) / dn;
 
     double ar = 0.0, ai = 0.0;
     for (int n = lane; n < a.N; n += 64) {
         double x, y, mx, my;
         int id;
         if (!rf_node(a, Xg, pose_ok, base + n, x, y, mx, my, id)) continue;
-        const double den = (double)acc[3 * (size_t)id] * RF_FIX;
+        const double den = (double)acc[3 * (size_t)id] * MAP_FIX;
         const double lx = (double)(long long)acc[3 * (size_t)id + 1] / den, ly = (double)(long long)acc[3 * (size_t)id + 2] / den;
         const double px = x - pbx, py = y - pby, qx = lx - lbx, qy = ly - lby;
         ar += px * qx + py * qy;
         ai += px * qy - py * qx;
     }
-    ar = rf_tree(ar);
-    ai = rf_tree(ai);
-    const double h = sqrt(ar * ar + ai * ai);
-    Se2 F;
-    F.c = ar / h;
-    F.s = ai / h;
-    F.x = lbx - (F.c * pbx - F.s * pby);
-    F.y = lby - (F.s * pbx + F.c * pby);
+    ar = wave_tree(ar);
+    ai = wave_tree(ai);
+    const Se2Fit fit = se2_fit(pbx, pby, lbx, lby, ar, ai);
     if (lane != 0) return;
     const bool fixed = a.fixed && a.fixed[g] != 0;
-    const bool keep = fixed || ng < a.min_nodes || !(h > 0.0 && isfinite(h)) || !se2_finite(F);
-    const Se2 R = keep ? Xg : F;
+    const bool keep = fixed || ng < a.min_nodes || fit.degenerate();
+    const Se2 R = keep ? Xg : fit.F;
     double* o = X_next + 4 * (size_t)g;
     o[0] = R.c;
     o[1] = R.s;
@@ -231,11 +211,7 @@ int sgpr_landmark_refine(const float* d_centers, int G, int N, const double* d_p
                          double* d_poses_out, double* d_cost, int32_t* d_info, void* d_workspace,
                          size_t workspace_bytes, void* stream) {
     const std::string fn = "sgpr_landmark_refine";
-    if (G < 0 || N < 0 || L < 0 || iters < 0) {
-        set_error(fn + ": " + (G < 0 ? "G " + std::to_string(G) : N < 0 ? "N " + std::to_string(N)
-                               : L < 0 ? "L " + std::to_string(L) : "iters " + std::to_string(iters)) + " is negative");
-        return SGPR_E_INVALID;
-    }
+    if (!no_negative(fn, {{"G", G}, {"N", N}, {"L", L}, {"iters", iters}})) return SGPR_E_INVALID;
     if (min_nodes < 2) {
         set_error(fn + ": min_nodes " + std::to_string(min_nodes) + " is below 2");
         return SGPR_E_INVALID;
@@ -250,10 +226,7 @@ int sgpr_landmark_refine(const float* d_centers, int G, int N, const double* d_p
         return SGPR_E_INVALID;
     }
     const size_t need = rf_ws_bytes((size_t)G, (size_t)L);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, need)) return SGPR_E_INVALID;
 
     Carver ws{static_cast<unsigned char*>(d_workspace)};
     u64* acc = ws.take<u64>(2 * 3 * (size_t)L);                 // two sets of [L](cnt, S_x, S_y)

@@ -31,6 +31,10 @@
 //
 // Every loop is bounded by slot counts, list lengths and the cap (a base pair adds at most L^2 past it).  No wave waits
 // for another workgroup.  Integer atomics only, no inline assembly, plain vector stores.
+//
+// Both tables are sgpr_map_grid.hpp's cell grid: landmarks enter them by grid_push, and the inlier test (lr_exists) is
+// grid_near with a way out at the first hit.  The cursor over the pair table stays written out: a lane must be able to
+// stop in the middle of a list and go on in the next round, which a visitor cannot.
 #include <math.h>
 
 #include <cmath>
@@ -40,7 +44,7 @@
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_align_core.hpp"
 #include "sgpr_landmark_relocalize.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 namespace sgpr {
 
@@ -98,11 +102,7 @@ __global__ __launch_bounds__(LR_THREADS) void lr_prep_kernel(const LrPrepArgs a)
     la_prep_landmark<true>(a.m, a.t, a.radius, i);
     const int l = a.t.elab[i];
     if (!a.with_pair || l < 0) return;
-    const double cw = lm_cell_width(a.pair_r);
-    const double cx = a.m.lm_center[3 * (size_t)i], cy = a.m.lm_center[3 * (size_t)i + 1];
-    const unsigned long long slot =
-        table_insert(a.pair.cell_key, a.pair.hmask, lm_cell_key(l, lm_cell_coord(cx, cw), lm_cell_coord(cy, cw)));
-    a.pair.next[i] = atomicExch(&a.pair.cell_head[slot], i);
+    grid_push(a.pair.g, i, l, lm_cell_width(a.pair_r), a.m.lm_center[3 * (size_t)i], a.m.lm_center[3 * (size_t)i + 1]);
     atomicAdd(&a.lab_count[l], 1);
 }
 
@@ -165,20 +165,12 @@ __device__ __forceinline__ bool lr_pose(const LrBase& b, double cx, double cy, d
 __device__ __forceinline__ bool lr_exists(const LaMap& m, const LaTable& t, int l, double r, double mx, double my, double mz) {
 #pragma clang fp contract(off)
     const double r2 = r * r;
-    const double cw = lm_cell_width(r);
-    const long long ix = lm_cell_coord(mx, cw), iy = lm_cell_coord(my, cw);
-    for (int dy = -1; dy <= 1; ++dy)
-        for (int dx = -1; dx <= 1; ++dx) {
-            const unsigned long long slot = table_find(t.cell_key, t.hmask, lm_cell_key(l, ix + dx, iy + dy));
-            if (slot == TABLE_EMPTY) continue;
-            for (int o = t.cell_head[slot]; o >= 0; o = t.next[o]) {
-                if (t.elab[o] != l) continue;
-                const double cx = m.lm_center[3 * (size_t)o], cy = m.lm_center[3 * (size_t)o + 1], cz = m.lm_center[3 * (size_t)o + 2];
-                const double ex = mx - cx, ey = my - cy;
-                if (ex * ex + ey * ey <= r2 && fabs(mz - cz) <= m.tau_z) return true;
-            }
-        }
-    return false;
+    return grid_near(t.g, l, lm_cell_width(r), mx, my, [&](int o) {
+        if (t.elab[o] != l) return false;
+        const double cx = m.lm_center[3 * (size_t)o], cy = m.lm_center[3 * (size_t)o + 1], cz = m.lm_center[3 * (size_t)o + 2];
+        const double ex = mx - cx, ey = my - cy;
+        return ex * ex + ey * ey <= r2 && fabs(mz - cz) <= m.tau_z;
+    });
 }
 
 template <bool LDS>
@@ -220,7 +212,7 @@ __global__ __launch_bounds__(LR_THREADS) void lr_reloc_kernel(const LrArgs a) {
     auto node_live = [&](int n) {
         const int l = sc.label(n);
         if (!(l >= 0 && l < a.m.n_labels)) return false;
-        return a.radius_in[l] > 0.0 && la_in_limit(sc.x(n)) && la_in_limit(sc.y(n)) && la_in_limit(sc.z(n));
+        return a.radius_in[l] > 0.0 && in_limit37(sc.x(n)) && in_limit37(sc.y(n)) && in_limit37(sc.z(n));
     };
 
     // ---- the live slots, in slot order
@@ -279,8 +271,9 @@ __global__ __launch_bounds__(LR_THREADS) void lr_reloc_kernel(const LrArgs a) {
                         const int n = live[n0 + lane];
                         const int l = sc.label(n);
                         const double x = sc.x(n), y = sc.y(n), mz = sc.z(n);
-                        const double mx = (X.c * x - X.s * y) + X.x, my = (X.s * x + X.c * y) + X.y;
-                        hit = la_in_limit(mx) && la_in_limit(my) && lr_exists(a.m, a.t_in, l, a.radius_in[l], mx, my, mz);
+                        double mx, my;
+                        se2_apply(X, x, y, &mx, &my);
+                        hit = in_limit37(mx) && in_limit37(my) && lr_exists(a.m, a.t_in, l, a.radius_in[l], mx, my, mz);
                     }
                     inl += __popcll(__ballot(hit));
                 }
@@ -338,12 +331,12 @@ __global__ __launch_bounds__(LR_THREADS) void lr_reloc_kernel(const LrArgs a) {
                                 wx_ = ix + (k % 3 - 1);
                                 wy_ = iy + (k / 3 - 1);
                                 ++k;
-                                const unsigned long long slot = table_find(a.pair.cell_key, a.pair.hmask, lm_cell_key(lp, wx_, wy_));
-                                o = slot == TABLE_EMPTY ? -1 : a.pair.cell_head[slot];
+                                const unsigned long long slot = table_find(a.pair.g.cell_key, a.pair.g.hmask, lm_cell_key(lp, wx_, wy_));
+                                o = slot == TABLE_EMPTY ? -1 : a.pair.g.cell_head[slot];
                                 continue;
                             }
                             const int cand = o;
-                            o = a.pair.next[cand];
+                            o = a.pair.g.next[cand];
                             if (cand == j || a.t_in.elab[cand] != lp) continue;
                             const double dx = a.m.lm_center[3 * (size_t)cand], dy = a.m.lm_center[3 * (size_t)cand + 1];
                             if (lm_cell_coord(dx, cw) != wx_ || lm_cell_coord(dy, cw) != wy_) continue;   // (not ITS cell)
@@ -510,50 +503,22 @@ int sgpr_landmark_relocalize(const float* d_centers, const int32_t* d_labels, in
                              int32_t* d_node_landmark, int32_t* d_stat, int32_t* d_win, int64_t* d_hyp, double* d_rms,
                              int32_t* d_num, void* d_workspace, size_t workspace_bytes, void* stream) {
     const std::string fn = "sgpr_landmark_relocalize";
-    if (Q < 0 || N < 0 || L < 0 || iters < 0) {
-        set_error(fn + ": " + (Q < 0 ? "Q " + std::to_string(Q) : N < 0 ? "N " + std::to_string(N)
-                               : L < 0 ? "L " + std::to_string(L) : "iters " + std::to_string(iters)) + " is negative");
-        return SGPR_E_INVALID;
-    }
+    if (!no_negative(fn, {{"Q", Q}, {"N", N}, {"L", L}, {"iters", iters}})) return SGPR_E_INVALID;
     if (!lr_stages_ok(n_stages)) {
         set_error(fn + ": n_stages " + std::to_string(n_stages) + " outside [0, " + std::to_string(SGPR_RELOC_MAX_STAGES) + "]");
         return SGPR_E_INVALID;
     }
-    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
-        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
-        return SGPR_E_INVALID;
-    }
-    if (!h_radius_in) {
-        set_error(fn + ": NULL h_radius_in");
-        return SGPR_E_INVALID;
-    }
+    if (!landmark_labels_ok(fn, h_radius_in, n_labels, "h_radius_in")) return SGPR_E_INVALID;
     if (!h_radii && n_stages > 0) {
         set_error(fn + ": NULL h_radii with n_stages " + std::to_string(n_stages));
         return SGPR_E_INVALID;
     }
-    for (int l = 0; l < n_labels; ++l)
-        if (!(h_radius_in[l] >= 0.0)) {
-            set_error(fn + ": inlier radius of label " + std::to_string(l) + " is negative or NaN");
-            return SGPR_E_INVALID;
-        }
+    if (!radii_ok(fn, h_radius_in, n_labels, "inlier radius")) return SGPR_E_INVALID;
     for (int j = 0; j < n_stages; ++j)
-        for (int l = 0; l < n_labels; ++l)
-            if (!(h_radii[(size_t)j * n_labels + l] >= 0.0)) {
-                set_error(fn + ": radius of label " + std::to_string(l) + " in stage " + std::to_string(j) + " is negative or NaN");
-                return SGPR_E_INVALID;
-            }
-    if (!(tau_z >= 0.0)) {
-        set_error(fn + ": tau_z is negative or NaN");
-        return SGPR_E_INVALID;
-    }
-    if (!(tau_edge >= 0.0)) {
-        set_error(fn + ": tau_edge is negative or NaN");
-        return SGPR_E_INVALID;
-    }
-    if (!(min_base >= 0.0)) {
-        set_error(fn + ": min_base is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+        if (!radii_ok(fn, h_radii + (size_t)j * n_labels, n_labels, "radius", j)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "tau_z", tau_z)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "tau_edge", tau_edge)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "min_base", min_base)) return SGPR_E_INVALID;
     if (!(max_base >= min_base) || !std::isfinite(max_base)) {
         set_error(fn + ": max_base is below min_base or not finite");
         return SGPR_E_INVALID;
@@ -570,10 +535,7 @@ int sgpr_landmark_relocalize(const float* d_centers, const int32_t* d_labels, in
         set_error(fn + ": min_nodes " + std::to_string(min_nodes) + " is below 2");
         return SGPR_E_INVALID;
     }
-    if (!(sep >= 0.0)) {
-        set_error(fn + ": sep is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+    if (!not_negative(fn, "sep", sep)) return SGPR_E_INVALID;
     if (!la_size_ok(Q, N, L)) {
         set_error(fn + ": Q N = " + std::to_string((long long)Q * N) + " exceeds the int32 node index");
         return SGPR_E_INVALID;
@@ -585,10 +547,7 @@ int sgpr_landmark_relocalize(const float* d_centers, const int32_t* d_labels, in
         return SGPR_E_INVALID;
     }
     const size_t need = lr_workspace(Q, N, L, n_stages);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, need)) return SGPR_E_INVALID;
 
     Carver ws{static_cast<unsigned char*>(d_workspace)};
     LrArgs a = {};
@@ -631,9 +590,9 @@ int sgpr_landmark_relocalize(const float* d_centers, const int32_t* d_labels, in
     hipError_t e = hipMemsetAsync(d_num, 0, 4 * sizeof(int32_t), s);
     if (e == hipSuccess) e = hipMemsetAsync(lab_count, 0, 2 * LR_LABELS * sizeof(int), s);
     // cell_key | cell_head of every table: empty keys, list ends (-1)
-    if (e == hipSuccess) e = hipMemsetAsync(a.t_in.cell_key, 0xff, la_table_clear_bytes((size_t)L), s);
-    if (e == hipSuccess) e = hipMemsetAsync(a.pair.cell_key, 0xff, la_table_clear_bytes((size_t)L), s);
-    for (int j = 0; j < n_stages && e == hipSuccess; ++j) e = hipMemsetAsync(a.t[j].cell_key, 0xff, la_table_clear_bytes((size_t)L), s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.t_in.g.cell_key, 0xff, grid_clear_bytes((size_t)L), s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.pair.g.cell_key, 0xff, grid_clear_bytes((size_t)L), s);
+    for (int j = 0; j < n_stages && e == hipSuccess; ++j) e = hipMemsetAsync(a.t[j].g.cell_key, 0xff, grid_clear_bytes((size_t)L), s);
     if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_relocalize: memset");
 
     const dim3 block(LR_THREADS);

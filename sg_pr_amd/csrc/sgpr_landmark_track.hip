@@ -17,7 +17,8 @@
 //                     scan's outputs; the four counts of d_num are integer atomics at the end of a track.
 //
 // -DSGPR_ALIGN_SEARCH=2 builds the form that tests every landmark, as in sgpr_landmark_align.hip.  Integer atomics only,
-// no inline assembly, plain vector stores.
+// no inline assembly, plain vector stores.  The argument checks are sgpr_map.hpp's and sgpr_map_grid.hpp's, the stage-
+// worded radius message included (radii_ok).
 #include <math.h>
 
 #include <cmath>
@@ -26,7 +27,7 @@
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_align_core.hpp"
 #include "sgpr_landmark_track.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 #ifndef SGPR_ALIGN_SEARCH
 #define SGPR_ALIGN_SEARCH 1
@@ -205,11 +206,7 @@ int sgpr_landmark_track(const float* d_centers, const int32_t* d_labels, int Q, 
                         int32_t* d_stat, double* d_rms, int32_t* d_num, void* d_workspace, size_t workspace_bytes,
                         void* stream) {
     const std::string fn = "sgpr_landmark_track";
-    if (Q < 0 || N < 0 || L < 0 || iters < 0) {
-        set_error(fn + ": " + (Q < 0 ? "Q " + std::to_string(Q) : N < 0 ? "N " + std::to_string(N)
-                               : L < 0 ? "L " + std::to_string(L) : "iters " + std::to_string(iters)) + " is negative");
-        return SGPR_E_INVALID;
-    }
+    if (!no_negative(fn, {{"Q", Q}, {"N", N}, {"L", L}, {"iters", iters}})) return SGPR_E_INVALID;
     if (!lt_stages_ok(n_stages)) {
         set_error(fn + ": n_stages " + std::to_string(n_stages) + " outside [1, " + std::to_string(SGPR_TRACK_MAX_STAGES) + "]");
         return SGPR_E_INVALID;
@@ -226,28 +223,11 @@ int sgpr_landmark_track(const float* d_centers, const int32_t* d_labels, int Q, 
         set_error(fn + ": min_matched " + std::to_string(min_matched) + " is negative");
         return SGPR_E_INVALID;
     }
-    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
-        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
-        return SGPR_E_INVALID;
-    }
-    if (!h_radius) {
-        set_error(fn + ": NULL h_radius");
-        return SGPR_E_INVALID;
-    }
+    if (!landmark_labels_ok(fn, h_radius, n_labels)) return SGPR_E_INVALID;
     for (int j = 0; j < n_stages; ++j)
-        for (int l = 0; l < n_labels; ++l)
-            if (!(h_radius[(size_t)j * n_labels + l] >= 0.0)) {
-                set_error(fn + ": radius of label " + std::to_string(l) + " in stage " + std::to_string(j) + " is negative or NaN");
-                return SGPR_E_INVALID;
-            }
-    if (!(tau_z >= 0.0)) {
-        set_error(fn + ": tau_z is negative or NaN");
-        return SGPR_E_INVALID;
-    }
-    if (!(max_shift >= 0.0)) {
-        set_error(fn + ": max_shift is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+        if (!radii_ok(fn, h_radius + (size_t)j * n_labels, n_labels, "radius", j)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "tau_z", tau_z)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "max_shift", max_shift)) return SGPR_E_INVALID;
     if (!session_table_ok(fn.c_str(), "track", h_starts, n_tracks, Q)) return SGPR_E_INVALID;
     if (!la_size_ok(Q, N, L)) {
         set_error(fn + ": Q N = " + std::to_string((long long)Q * N) + " exceeds the int32 node index");
@@ -260,10 +240,7 @@ int sgpr_landmark_track(const float* d_centers, const int32_t* d_labels, int Q, 
         return SGPR_E_INVALID;
     }
     const size_t need = (size_t)n_stages * la_table_bytes((size_t)L);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, need)) return SGPR_E_INVALID;
 
     Carver ws{static_cast<unsigned char*>(d_workspace)};
     LtArgs a = {};
@@ -298,7 +275,7 @@ int sgpr_landmark_track(const float* d_centers, const int32_t* d_labels, int Q, 
     if (LT_TABLE)
         for (int j = 0; j < n_stages; ++j) {
             // cell_key | cell_head of stage j: empty keys, list ends (-1)
-            e = hipMemsetAsync(a.t[j].cell_key, 0xff, la_table_clear_bytes((size_t)L), s);
+            e = hipMemsetAsync(a.t[j].g.cell_key, 0xff, grid_clear_bytes((size_t)L), s);
             if (e != hipSuccess) return hip_fail(e, "sgpr_landmark_track: memset");
         }
     const dim3 block(LT_THREADS), track_grid((a.n_tracks + LT_WAVES - 1) / LT_WAVES);

@@ -24,6 +24,8 @@
 // is tested for its bits, not tuned).
 //
 // The accumulators are zeroed by one memset on the stream; nothing else of the workspace is read before it is written.
+// The eligible rule and the fixed-point constants are sgpr_map_grid.hpp's (record_eligible, MAP_FIX, MAP_D2_CAP), shared
+// with sgpr_landmark_merge.hip.
 // No floating-point atomics, no inline assembly, plain vector stores.
 #include <math.h>
 
@@ -33,16 +35,13 @@
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_core.hpp"
 #include "sgpr_landmark_update.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 namespace sgpr {
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int UPD_MAX_COUNT = 262144;                  // 2^18
-constexpr double UPD_SUM_LIMIT = 274877906944.0;       // 2^38
 
 struct UpdWs {
     int* mlab;                     // [P] the label of a new node, -1 of any other
@@ -84,15 +83,8 @@ struct UpdArgs {
 
 // ELIGIBLE of the header, on the input record
 __device__ __forceinline__ bool upd_eligible(const UpdArgs& a, int id) {
-    const int l = a.lm_label[id], n = a.lm_count[id];
-    if (l < 0 || l >= a.n_labels || !(a.radius[l] > 0.0) || n < 1 || n > UPD_MAX_COUNT) return false;
-    const double n0 = (double)n, sp = a.lm_spread[id];
-    bool ok = isfinite(sp) && sp >= 0.0;
-    for (int k = 0; k < 3; ++k) {
-        const double c = a.lm_center[3 * (size_t)id + k];
-        ok = ok && isfinite(c) && fabs(c * n0) <= UPD_SUM_LIMIT;
-    }
-    return ok;
+    const double* c = a.lm_center + 3 * (size_t)id;
+    return record_eligible(a.lm_label[id], a.lm_count[id], a.lm_spread[id], c[0], c[1], c[2], a.radius, a.n_labels);
 }
 
 __global__ __launch_bounds__(LM_THREADS) void upd_classify_kernel(const UpdWs w, const UpdArgs a) {
@@ -108,7 +100,7 @@ __global__ __launch_bounds__(LM_THREADS) void upd_classify_kernel(const UpdWs w,
         w.obs[p] = seen ? id : -1;
         if (seen) {
             for (int k = 0; k < 3; ++k)
-                atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)id + k]), (unsigned long long)llrint(m[k] * LM_FIX));
+                atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)id + k]), (unsigned long long)llrint(m[k] * MAP_FIX));
             atomicAdd(&w.cnt[id], 1);
             atomicOr(&w.sess[id], 1ull << (a.session_base + session_of(a.starts, a.n_sessions, q)));
         }
@@ -127,9 +119,9 @@ __global__ __launch_bounds__(LM_THREADS) void upd_centre_kernel(const UpdWs w, c
     if (n1 == 0) return;                                        // (n1 > 0: the landmark is eligible)
     const double n0 = (double)a.lm_count[id], cnt = (double)(a.lm_count[id] + n1);
     for (int k = 0; k < 3; ++k) {
-        const unsigned long long S = (unsigned long long)llrint((a.lm_center[3 * (size_t)id + k] * n0) * LM_FIX) +
+        const unsigned long long S = (unsigned long long)llrint((a.lm_center[3 * (size_t)id + k] * n0) * MAP_FIX) +
                                      (unsigned long long)w.sum[3 * (size_t)id + k];
-        w.centre[3 * (size_t)id + k] = (double)(long long)S / (cnt * LM_FIX);
+        w.centre[3 * (size_t)id + k] = (double)(long long)S / (cnt * MAP_FIX);
     }
 }
 
@@ -142,7 +134,7 @@ __global__ __launch_bounds__(LM_THREADS) void upd_spread_kernel(const UpdWs w, c
     lm_map_point(a.centers, a.poses, a.radius, a.n_labels, p, p / a.N, a.labels[p], m);
     const double ex = m[0] - w.centre[3 * (size_t)id], ey = m[1] - w.centre[3 * (size_t)id + 1];
     const double d2 = ex * ex + ey * ey;
-    atomicAdd(&w.q[id], (unsigned long long)llrint(fmin(d2, LM_D2_CAP) * LM_FIX));
+    atomicAdd(&w.q[id], (unsigned long long)llrint(fmin(d2, MAP_D2_CAP) * MAP_FIX));
 }
 
 __global__ __launch_bounds__(LM_THREADS) void upd_finish_kernel(const UpdWs w, const UpdArgs a) {
@@ -174,13 +166,13 @@ __global__ __launch_bounds__(LM_THREADS) void upd_finish_kernel(const UpdWs w, c
     const double d0 = w.centre[3 * (size_t)id], d1 = w.centre[3 * (size_t)id + 1], d2 = w.centre[3 * (size_t)id + 2];
     const double ax = c0 - d0, ay = c1 - d1;
     const double v = spread * spread + (ax * ax + ay * ay);
-    const unsigned long long Q = (unsigned long long)llrint((fmin(v, LM_D2_CAP) * n0) * LM_FIX) + w.q[id];
+    const unsigned long long Q = (unsigned long long)llrint((fmin(v, MAP_D2_CAP) * n0) * MAP_FIX) + w.q[id];
     a.out_center[3 * (size_t)id] = d0;
     a.out_center[3 * (size_t)id + 1] = d1;
     a.out_center[3 * (size_t)id + 2] = d2;
     a.out_count[id] = count + n1;
     a.out_sessions[id] = sessions | w.sess[id];
-    a.out_spread[id] = sqrt((double)Q / (cnt * LM_FIX));
+    a.out_spread[id] = sqrt((double)Q / (cnt * MAP_FIX));
 }
 
 __global__ __launch_bounds__(LM_THREADS) void upd_merge_kernel(const UpdWs w, const UpdArgs a) {
@@ -221,36 +213,15 @@ int sgpr_landmark_update(const float* d_centers, const int32_t* d_labels, int Q,
                          uint64_t* d_out_sessions, double* d_out_spread, int32_t* d_node_landmark, int32_t* d_num,
                          void* d_workspace, size_t workspace_bytes, void* stream) {
     const std::string fn = "sgpr_landmark_update";
-    const struct {
-        const char* name;
-        int v;
-    } signs[] = {{"Q", Q}, {"N", N}, {"L", L}, {"max_landmarks", max_landmarks}, {"node_base", node_base}, {"session_base", session_base}};
-    for (const auto& s : signs)
-        if (s.v < 0) {
-            set_error(fn + ": " + s.name + " " + std::to_string(s.v) + " is negative");
-            return SGPR_E_INVALID;
-        }
+    if (!no_negative(fn, {{"Q", Q}, {"N", N}, {"L", L}, {"max_landmarks", max_landmarks}, {"node_base", node_base},
+                          {"session_base", session_base}}))
+        return SGPR_E_INVALID;
     if (max_landmarks < L) {
         set_error(fn + ": max_landmarks " + std::to_string(max_landmarks) + " is below L " + std::to_string(L));
         return SGPR_E_INVALID;
     }
-    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
-        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
-        return SGPR_E_INVALID;
-    }
-    if (!h_radius) {
-        set_error(fn + ": NULL h_radius");
-        return SGPR_E_INVALID;
-    }
-    for (int l = 0; l < n_labels; ++l)
-        if (!(h_radius[l] >= 0.0)) {
-            set_error(fn + ": radius of label " + std::to_string(l) + " is negative or NaN");
-            return SGPR_E_INVALID;
-        }
-    if (!(tau_z >= 0.0)) {
-        set_error(fn + ": tau_z is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+    if (!landmark_labels_ok(fn, h_radius, n_labels) || !radii_ok(fn, h_radius, n_labels)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "tau_z", tau_z)) return SGPR_E_INVALID;
     if (!session_table_ok(fn.c_str(), "", h_starts, n_sessions, Q)) return SGPR_E_INVALID;
     if ((long long)session_base + (n_sessions > 0 ? n_sessions : 1) > 64) {
         set_error(fn + ": session_base " + std::to_string(session_base) + " + " + std::to_string(n_sessions > 0 ? n_sessions : 1) +
@@ -273,10 +244,7 @@ int sgpr_landmark_update(const float* d_centers, const int32_t* d_labels, int Q,
     }
     const size_t P = (size_t)nodes, Ls = (size_t)L;
     const size_t need = upd_ws_bytes(P, Ls);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, need)) return SGPR_E_INVALID;
 
     unsigned char* base = static_cast<unsigned char*>(d_workspace);
     Carver ws{base + lm_core_workspace_bytes(P)};                // (the core's part comes first)

@@ -21,7 +21,9 @@
 //
 // The cell table and the union-find are sgpr_map.hpp's, with their SIZING, VISIBILITY and TERMINATION arguments: the
 // table has table_slots(G N) slots and every key in it belongs to some node; the cell lists are complete before the
-// kernel that walks them starts; the forest is the only memory another workgroup rewrites while it is read.
+// kernel that walks them starts; the forest is the only memory another workgroup rewrites while it is read.  The push
+// on a cell's list, the linking step of lm_union_kernel, the scan and the rank of the numbering are sgpr_map_grid.hpp's
+// (grid_push, link_item, scan_block_counts, rank_in_block), shared with sgpr_landmark_merge.hip.
 // Everything else is handed from one kernel to the next on one stream.  No floating-point atomics, no inline assembly,
 // plain vector stores.
 //
@@ -39,15 +41,13 @@
 #include "sgpr_internal.hpp"
 #include "sgpr_landmark_core.hpp"
 #include "sgpr_landmarks.h"
-#include "sgpr_map.hpp"
+#include "sgpr_map_grid.hpp"
 
 namespace sgpr {
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int LM_SCAN_THREADS = 1024;         // (LM_THREADS and the fixed-point constants: sgpr_landmark_core.hpp)
 
 struct LmWs {
     double* m;                     // [P][3] map point
@@ -64,6 +64,8 @@ struct LmWs {
     int* blk_roots;                // [B] roots per workgroup; after the scan: roots before the workgroup
     int* blk_live;                 // [B] live nodes per workgroup
     unsigned long long hmask;      // H - 1 (H a power of two)
+    // (next, cell_key, cell_head, hmask) as the grid the shared steps take
+    __device__ __forceinline__ CellGrid grid() const { return CellGrid{next, cell_key, cell_head, hmask}; }
 };
 
 struct LmArgs {
@@ -113,31 +115,13 @@ __global__ __launch_bounds__(LM_THREADS) void lm_transform_kernel(const LmWs w, 
         a.node_landmark[p] = -1;
         return;
     }
-    const double cw = lm_cell_width(a.radius[l]);
-    const unsigned long long slot = table_insert(w.cell_key, w.hmask, lm_cell_key(l, lm_cell_coord(mx, cw), lm_cell_coord(my, cw)));
-    w.next[p] = atomicExch(&w.cell_head[slot], p);
+    grid_push(w.grid(), p, l, lm_cell_width(a.radius[l]), mx, my);
 }
 
 __global__ __launch_bounds__(LM_THREADS) void lm_union_kernel(const LmWs w, const LmArgs a) {
     const int p = blockIdx.x * LM_THREADS + threadIdx.x;
     if (p >= a.P) return;
-    const int l = w.lab[p];
-    if (l < 0) return;
-    const double r = a.radius[l], r2 = r * r, tau_z = a.tau_z;
-    const double cw = lm_cell_width(r);
-    const double mx = w.m[3 * (size_t)p], my = w.m[3 * (size_t)p + 1], mz = w.m[3 * (size_t)p + 2];
-    const long long ix = lm_cell_coord(mx, cw), iy = lm_cell_coord(my, cw);
-    for (int dy = -1; dy <= 1; ++dy)
-        for (int dx = -1; dx <= 1; ++dx) {
-            const unsigned long long slot = table_find(w.cell_key, w.hmask, lm_cell_key(l, ix + dx, iy + dy));
-            if (slot == TABLE_EMPTY) continue;
-            for (int o = w.cell_head[slot]; o >= 0; o = w.next[o]) {
-                if (o >= p || w.lab[o] != l) continue;          // every unordered pair once; (a shared list: see lm_cell_key)
-                const double ex = mx - w.m[3 * (size_t)o], ey = my - w.m[3 * (size_t)o + 1];
-                const double d2 = ex * ex + ey * ey;
-                if (d2 <= r2 && fabs(mz - w.m[3 * (size_t)o + 2]) <= tau_z) uf_unite(w.parent, p, o);
-            }
-        }
+    link_item(w.grid(), w.m, w.lab, w.parent, a.radius, a.tau_z, p);
 }
 
 // the sum of v over the workgroup, valid in thread 0
@@ -165,7 +149,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_flatten_kernel(const LmWs w, co
         atomicAdd(&w.cnt[root], 1);
         for (int k = 0; k < 3; ++k)
             atomicAdd(reinterpret_cast<unsigned long long*>(&w.sum[3 * (size_t)root + k]),
-                      (unsigned long long)llrint(w.m[3 * (size_t)p + k] * LM_FIX));
+                      (unsigned long long)llrint(w.m[3 * (size_t)p + k] * MAP_FIX));
         atomicOr(&w.sess[root], 1ull << (a.session_shift + sess));
     }
     const int roots = lm_block_sum(live && root == p ? 1 : 0, wsum);
@@ -176,54 +160,27 @@ __global__ __launch_bounds__(LM_THREADS) void lm_flatten_kernel(const LmWs w, co
     }
 }
 
-__global__ __launch_bounds__(LM_SCAN_THREADS) void lm_scan_kernel(const LmWs w, const LmArgs a) {
-    __shared__ int part[LM_SCAN_THREADS];
-    __shared__ int live_part[LM_SCAN_THREADS];
-    const int t = threadIdx.x;
-    const int seg = (a.B + LM_SCAN_THREADS - 1) / LM_SCAN_THREADS;
-    const int lo = min(t * seg, a.B), hi = min(lo + seg, a.B);
-    int s = 0, lv = 0;
-    for (int i = lo; i < hi; ++i) {
-        s += w.blk_roots[i];
-        lv += w.blk_live[i];
-    }
-    part[t] = s;
-    live_part[t] = lv;
-    __syncthreads();
-    for (int off = 1; off < LM_SCAN_THREADS; off <<= 1) {       // inclusive scan of the segment sums
-        const int u = t >= off ? part[t - off] : 0, v = t >= off ? live_part[t - off] : 0;
-        __syncthreads();
-        part[t] += u;
-        live_part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;
-    for (int i = lo; i < hi; ++i) {
-        const int c = w.blk_roots[i];
-        w.blk_roots[i] = run;
-        run += c;
-    }
-    if (t == LM_SCAN_THREADS - 1) {
-        a.num[0] = a.id_base + part[t];
-        a.num[1] = live_part[t];
+__global__ __launch_bounds__(SCAN_THREADS) void lm_scan_kernel(const LmWs w, const LmArgs a) {
+    __shared__ int part[SCAN_THREADS];
+    __shared__ int live_part[SCAN_THREADS];
+    scan_block_counts<true>(w.blk_roots, w.blk_live, a.B, part, live_part);
+    if (threadIdx.x == SCAN_THREADS - 1) {
+        a.num[0] = a.id_base + part[threadIdx.x];
+        a.num[1] = live_part[threadIdx.x];
     }
 }
 
 __device__ __forceinline__ double lm_center(const LmWs& w, int root, int k, double cnt) {
-    return (double)w.sum[3 * (size_t)root + k] / (cnt * LM_FIX);
+    return (double)w.sum[3 * (size_t)root + k] / (cnt * MAP_FIX);
 }
 
 __global__ __launch_bounds__(LM_THREADS) void lm_record_kernel(const LmWs w, const LmArgs a) {
     __shared__ int wcount[LM_THREADS / 64];
     const int p = blockIdx.x * LM_THREADS + threadIdx.x;
     const bool root = p < a.P && w.lab[p] >= 0 && w.next[p] == p;
-    const unsigned long long ball = __ballot(root);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wcount[wave] = __popcll(ball);
-    __syncthreads();
+    const int rank = rank_in_block(root, wcount);
     if (!root) return;
-    int id = a.id_base + w.blk_roots[blockIdx.x] + __popcll(ball & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) id += wcount[v];
+    const int id = a.id_base + w.blk_roots[blockIdx.x] + rank;
     w.id[p] = id;
     if (id >= a.max_landmarks) return;
     const int n = w.cnt[p];
@@ -243,7 +200,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_spread_kernel(const LmWs w, con
     const double cnt = (double)w.cnt[root];
     const double ex = w.m[3 * (size_t)p] - lm_center(w, root, 0, cnt), ey = w.m[3 * (size_t)p + 1] - lm_center(w, root, 1, cnt);
     const double d2 = ex * ex + ey * ey;
-    atomicAdd(&w.q[root], (unsigned long long)llrint(fmin(d2, LM_D2_CAP) * LM_FIX));
+    atomicAdd(&w.q[root], (unsigned long long)llrint(fmin(d2, MAP_D2_CAP) * MAP_FIX));
 }
 
 __global__ __launch_bounds__(LM_THREADS) void lm_finish_kernel(const LmWs w, const LmArgs a) {
@@ -251,7 +208,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_finish_kernel(const LmWs w, con
     if (p >= a.P || w.lab[p] < 0 || w.next[p] != p) return;
     const int id = w.id[p];
     if (id >= a.max_landmarks) return;
-    a.lm_spread[id] = sqrt((double)w.q[p] / ((double)w.cnt[p] * LM_FIX));
+    a.lm_spread[id] = sqrt((double)w.q[p] / ((double)w.cnt[p] * MAP_FIX));
 }
 
 bool lm_size_ok(int G, int N) { return G >= 0 && N >= 0 && (long long)G * (long long)N <= 0x7fffffffll; }
@@ -259,9 +216,8 @@ bool lm_size_ok(int G, int N) { return G >= 0 && N >= 0 && (long long)G * (long 
 }  // namespace
 
 size_t lm_core_workspace_bytes(size_t P) {
-    const size_t h = table_slots(P), b = (P + LM_THREADS - 1) / LM_THREADS;
-    return align256(P * 24) * 2 + align256(P * 4) * 5 + align256(P * 8) * 2 + align256(h * 8) + align256(h * 4) +
-           align256(b * 4) * 2;
+    const size_t b = (P + LM_THREADS - 1) / LM_THREADS;
+    return align256(P * 24) * 2 + align256(P * 4) * 4 + align256(P * 8) * 2 + grid_bytes(P) + align256(b * 4) * 2;
 }
 
 int lm_core_launch(const char* fn, const LmCoreJob& job, void* d_workspace, hipStream_t s) {
@@ -311,13 +267,13 @@ int lm_core_launch(const char* fn, const LmCoreJob& job, void* d_workspace, hipS
 
     const std::string what = fn;
     // cell_key | cell_head: empty keys, list ends (-1)
-    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, align256(H * 8) + align256(H * 4), s);
+    hipError_t e = hipMemsetAsync(w.cell_key, 0xff, grid_clear_bytes(P), s);
     if (e != hipSuccess) return hip_fail(e, (what + ": memset").c_str());
     const dim3 grid(B), block(LM_THREADS);
     hipLaunchKernelGGL(lm_transform_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(lm_union_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(lm_flatten_kernel, grid, block, 0, s, w, a);
-    hipLaunchKernelGGL(lm_scan_kernel, dim3(1), dim3(LM_SCAN_THREADS), 0, s, w, a);
+    hipLaunchKernelGGL(lm_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, w, a);
     hipLaunchKernelGGL(lm_record_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(lm_spread_kernel, grid, block, 0, s, w, a);
     hipLaunchKernelGGL(lm_finish_kernel, grid, block, 0, s, w, a);
@@ -326,9 +282,6 @@ int lm_core_launch(const char* fn, const LmCoreJob& job, void* d_workspace, hipS
     return SGPR_OK;
 }
 
-namespace {
-
-}  // namespace
 }  // namespace sgpr
 
 using namespace sgpr;
@@ -346,29 +299,9 @@ int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, in
                       int32_t* d_lm_first, uint64_t* d_lm_sessions, double* d_lm_spread, int32_t* d_node_landmark,
                       int32_t* d_num, void* d_workspace, size_t workspace_bytes, void* stream) {
     const std::string fn = "sgpr_landmark_map";
-    if (G < 0 || N < 0 || max_landmarks < 0) {
-        set_error(fn + ": " + (G < 0 ? "G " + std::to_string(G) : N < 0 ? "N " + std::to_string(N)
-                                                                         : "max_landmarks " + std::to_string(max_landmarks)) +
-                  " is negative");
-        return SGPR_E_INVALID;
-    }
-    if (n_labels < 1 || n_labels > SGPR_LANDMARK_MAX_LABELS) {
-        set_error(fn + ": n_labels " + std::to_string(n_labels) + " outside [1, " + std::to_string(SGPR_LANDMARK_MAX_LABELS) + "]");
-        return SGPR_E_INVALID;
-    }
-    if (!h_radius) {
-        set_error(fn + ": NULL h_radius");
-        return SGPR_E_INVALID;
-    }
-    for (int l = 0; l < n_labels; ++l)
-        if (!(h_radius[l] >= 0.0)) {
-            set_error(fn + ": radius of label " + std::to_string(l) + " is negative or NaN");
-            return SGPR_E_INVALID;
-        }
-    if (!(tau_z >= 0.0)) {
-        set_error(fn + ": tau_z is negative or NaN");
-        return SGPR_E_INVALID;
-    }
+    if (!no_negative(fn, {{"G", G}, {"N", N}, {"max_landmarks", max_landmarks}})) return SGPR_E_INVALID;
+    if (!landmark_labels_ok(fn, h_radius, n_labels) || !radii_ok(fn, h_radius, n_labels)) return SGPR_E_INVALID;
+    if (!not_negative(fn, "tau_z", tau_z)) return SGPR_E_INVALID;
     if (!session_table_ok(fn.c_str(), "", h_starts, n_sessions, G)) return SGPR_E_INVALID;
     if (!lm_size_ok(G, N)) {
         set_error(fn + ": G N = " + std::to_string((long long)G * N) + " exceeds the int32 node index");
@@ -381,11 +314,7 @@ int sgpr_landmark_map(const float* d_centers, const int32_t* d_labels, int G, in
         return SGPR_E_INVALID;
     }
     const size_t P = (size_t)G * (size_t)N;
-    const size_t need = lm_core_workspace_bytes(P);
-    if (workspace_bytes < need) {
-        set_error(fn + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed");
-        return SGPR_E_INVALID;
-    }
+    if (!workspace_ok(fn, workspace_bytes, lm_core_workspace_bytes(P))) return SGPR_E_INVALID;
 
     LmCoreJob job = {};
     job.centers = d_centers;

@@ -1,11 +1,15 @@
 // The building blocks the map back end shares: planar poses, the lock-free union-find, the
-// open-addressing cell table, the session rule, workspace carving and the host-side session-table check.  One
-// definition of each; sgpr_cluster / landmarks / consistency / localize / posegraph / score / api include it.
+// open-addressing cell table, the cells of the map frame, the session rule, workspace carving and the host-side checks
+// of a session table and of the arguments the entry points have in common.  One definition of each; sgpr_cluster /
+// consistency / localize / posegraph / score / api include it, and the landmark files through sgpr_map_grid.hpp, which
+// adds what only they share (the cell grid, the linking step, the numbering of roots, the planar fit).
 //
 // Floating-point contraction: a header included above a file's `#pragma clang fp contract(off)` is not covered by it,
 // and files without that line include this one too.  Every function here that multiplies and adds carries the pragma
 // in its own body, so its products are rounded on their own wherever it is inlined.
 #pragma once
+#include <initializer_list>
+
 #include "sgpr_internal.hpp"
 
 namespace sgpr {
@@ -94,7 +98,7 @@ __device__ __forceinline__ I table_find(const unsigned long long* keys, I mask, 
     }
 }
 
-// ------------------------------------------------------------------ cells of the map frame (landmarks, landmark_align)
+// ------------------------------------------------------------------ cells of the map frame (the landmark files)
 // Cell width of a label: a hair wider than its radius, and never below LM_MIN_CELL.
 //
 // Two points in range are never two cells apart.  Let a >= b be one coordinate of two points that link, w the width.
@@ -117,9 +121,8 @@ __device__ __forceinline__ long long lm_cell_coord(double v, double w) {
 }
 
 // The key is a HASH of (label, ix, iy), not a packing: 2 x 39 bits of cell coordinate and 6 of label do not fit.  Two
-// cells with one key share a list, and one list may be met twice among the 9 neighbours; the pair test compares the
-// labels and the distance itself and its consequence (uniting, a minimum) is idempotent, so a collision costs time and
-// never an answer.
+// cells with one key share a list; why that never costs an answer is argued where the lists are walked (grid_near,
+// sgpr_map_grid.hpp).
 __device__ __forceinline__ unsigned long long lm_cell_key(int label, long long ix, long long iy) {
     unsigned long long k = mix64((unsigned long long)ix + 0x9e3779b97f4a7c15ull * (unsigned long long)(label + 1));
     k = mix64(k ^ ((unsigned long long)iy * 0xd6e8feb86659fd93ull));
@@ -224,6 +227,34 @@ inline bool session_table_ok(const char* fn, const char* which, const int32_t* s
 inline void fill_session_table(int32_t* dst, int* n_dst, const int32_t* h_starts, int n_sessions) {
     *n_dst = n_sessions > 0 ? n_sessions : 1;
     for (int s = 0; s < *n_dst; ++s) dst[s] = n_sessions > 0 ? h_starts[s] : 0;
+}
+
+// ------------------------------------------------------------------ host: the argument checks of the landmark entry points
+// false: the message is set.  The words are what the host tests match; the return code and the order of an entry
+// point's checks stay its own.
+struct NamedInt {
+    const char* name;
+    int v;
+};
+// the first negative of the list: "<name> <v> is negative"
+inline bool no_negative(const std::string& fn, std::initializer_list<NamedInt> values) {
+    for (const NamedInt& s : values)
+        if (s.v < 0) {
+            set_error(fn + ": " + s.name + " " + std::to_string(s.v) + " is negative");
+            return false;
+        }
+    return true;
+}
+// v >= 0, so not NaN either
+inline bool not_negative(const std::string& fn, const char* name, double v) {
+    if (v >= 0.0) return true;
+    set_error(fn + ": " + name + " is negative or NaN");
+    return false;
+}
+inline bool workspace_ok(const std::string& fn, size_t have, size_t need) {
+    if (have >= need) return true;
+    set_error(fn + ": workspace of " + std::to_string(have) + " bytes, " + std::to_string(need) + " needed");
+    return false;
 }
 
 }  // namespace sgpr

@@ -130,6 +130,79 @@ def test_sizes(T):
     check(with_kw(case, radius=[0.75, 0.0, 2.0], tau_z=0.3, n_labels=3))
 
 
+def test_numbering_scan_with_segments_of_two_workgroups():
+    """1025 workgroups of 256 records: every thread of the one-workgroup numbering scan owns a SEGMENT of two workgroup
+    counts, which no smaller merge reaches.  The expected values are closed forms, not the reference's (its pure-Python
+    linking would take minutes here): the input records lie on a lattice of pitch 2 > radius (B's through an integer
+    translation), so every kept eligible record is copied - but for three planted pairs 0.5 apart with counts 1 and
+    spreads 0: across the workgroups 0 | 1 (255, 256: inside thread 0's segment), across the workgroups 601 | 602
+    (154111, 154112: the last of thread 300's segment, the first of thread 301's) and across the maps (199999, 200000).
+    263 records are dropped at the indices 100 + 1000 k - by a keep mask and by a count of 0 in turn - so an id is "roots
+    before me", never the index."""
+    L_a, L_b, ROW, SHIFT, BASE = 200000, 62400, 512, 3, 1 << 20
+    T = L_a + L_b
+    t = np.arange(T)
+    assert T == 1025 * 256
+    rec = {"center": np.stack((2.0 * (t % ROW), 2.0 * (t // ROW), 0.125 * (t % 7)), axis=1), "label": (t % 3).astype(np.int32),
+           "count": (1 + t % 5).astype(np.int32), "first": ((t * 7) % 100003).astype(np.int32),
+           "sessions": (np.uint64(1) << (t % 11).astype(np.uint64)), "spread": 0.25 * (t % 4)}
+    pairs = [(255, 256), (602 * 256 - 1, 602 * 256), (L_a - 1, L_a)]
+    for a, b in pairs:
+        rec["center"][b] = rec["center"][a] + (0.5, 0.0, 0.0)
+        rec["label"][b] = rec["label"][a]
+        rec["count"][[a, b]] = 1
+        rec["spread"][[a, b]] = 0.0
+    drop = np.arange(100, T, 1000)
+    masked, unfit = drop[0::2], drop[1::2]
+    rec["count"][unfit] = 0
+    keep = np.ones(T, np.uint8)
+    keep[masked] = 0
+    assert drop.size == 263 and not set(drop) & {i + d for pr in pairs for i in pr for d in (-1, 0, 1)}
+    lm_a = {k: v[:L_a].copy() for k, v in rec.items()}
+    lm_b = {k: v[L_a:].copy() for k, v in rec.items()}
+    lm_b["center"][:, 0] -= 4096.0                               # B's frame; the pose brings it back, exactly
+    case = {"a": lm_a, "b": lm_b, "kw": dict(keep_a=keep[:L_a], keep_b=keep[L_a:], pose=(1.0, 0.0, 4096.0, 0.0),
+                                             session_shift=SHIFT, first_base=BASE)}
+    run = launch(case)
+    torch.cuda.synchronize()
+    got = {k: v.cpu().numpy() for k, v in run["out"].items()}
+    got["sessions"] = got["sessions"].view(np.uint64)
+
+    rec["first"][L_a:] += BASE                                    # the INPUT RECORDS of B
+    rec["sessions"][L_a:] <<= np.uint64(SHIFT)
+    live = np.ones(T, bool)
+    live[drop] = False
+    root = live.copy()
+    root[[b for _, b in pairs]] = False
+    ids = np.cumsum(root) - 1                                     # of a root: the roots before it
+    n_roots = int(root.sum())
+    assert got["num"][:4].tolist() == [n_roots, masked.size, unfit.size, len(pairs)] and n_roots == T - 263 - 3
+    old_to_new = np.where(root, ids, -1).astype(np.int32)
+    for a, b in pairs:
+        old_to_new[b] = ids[a]
+    assert got["old_to_new"][:T].tobytes() == old_to_new.tobytes()
+    r = np.flatnonzero(root)
+    want = {k: v[r].copy() for k, v in rec.items()}
+    for a, b in pairs:
+        i = ids[a]
+        want["center"][i, 0] += 0.25                              # the mean of x and x + 0.5, weights 1 and 1: exact
+        want["count"][i] = 2
+        want["first"][i] = min(rec["first"][a], rec["first"][b])
+        want["sessions"][i] = rec["sessions"][a] | rec["sessions"][b]
+        want["spread"][i] = 0.25                                  # sqrt of the mean of 0^2 + 0.25^2 twice
+    for a, b in pairs:                                            # the planted pairs and their neighbours, by name first
+        for j in (a - 1, a, b + 1):
+            for name in ref.RECORD:
+                w = 3 if name == "center" else 1
+                assert got[name][w * ids[j]:w * (ids[j] + 1)].tobytes() == want[name][ids[j]].tobytes(), (name, j)
+    for name in ref.RECORD:
+        w = 3 if name == "center" else 1
+        assert got[name][:w * n_roots].tobytes() == np.ascontiguousarray(want[name], HOST[name]).tobytes(), name
+        assert (got[name][w * n_roots:].view(np.uint8) == 0xFF).all(), name + ": written past the records"
+    for name, n in (("old_to_new", T), ("num", 4)):
+        assert (got[name][n:].view(np.uint8) == 0xFF).all(), name + ": written past the output"
+
+
 def test_hand_made_cases():
     for name, case in ref.hand_cases().items():
         check(case, max_out=case["kw"].get("max_out"))

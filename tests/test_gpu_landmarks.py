@@ -172,6 +172,58 @@ def test_heavy_cells():
     assert want["num"].tolist() == [2, 600] and want["count"].tolist() == [300, 300]
 
 
+# ------------------------------------------------------------------ more than 1024 workgroups
+def test_numbering_scan_with_segments_of_two_workgroups():
+    """1025 workgroups of 256 nodes: every thread of the one-workgroup numbering scan owns a SEGMENT of two workgroup
+    counts, which no smaller map reaches.  The expected values are closed forms, not the reference's (its pure-Python
+    linking would take minutes here): the nodes lie on a lattice of pitch 2 > radius, so every live node is its own
+    landmark - its centre is its point exactly, its spread 0 - but for two planted pairs 0.5 apart, one across the
+    workgroups 0 | 1 (nodes 255, 256: inside thread 0's segment), one across the workgroups 601 | 602 (nodes 154111,
+    154112: the last of thread 300's segment and the first of thread 301's).  263 nodes are dead at the indices
+    100 + 1000 k, so an id is "live roots before me", never the index."""
+    G, N, ROW = 1025, 256, 512
+    P = G * N
+    p = np.arange(P)
+    pts = np.stack((2.0 * (p % ROW), 2.0 * (p // ROW), 0.125 * (p % 7)), axis=1)
+    labels = (p % 3).astype(np.int32)
+    pairs = [(255, 256), (602 * N - 1, 602 * N)]
+    for a, b in pairs:
+        pts[b] = pts[a] + (0.5, 0.0, 0.0)
+        labels[b] = labels[a]
+    dead = np.arange(100, P, 1000)
+    labels[dead[0::2]] = -1
+    labels[dead[1::2]] = 12                                       # n_labels = 12: out of range
+    assert dead.size == 263 and not set(dead) & {i + d for pr in pairs for i in pr for d in (-1, 0, 1)}
+    got = device_map(pts.astype(F32).reshape(G, N, 3), labels.reshape(G, N), np.tile(IDENT, (G, 1)))
+
+    live = np.ones(P, bool)
+    live[dead] = False
+    root = live.copy()
+    root[[b for _, b in pairs]] = False
+    ids = np.cumsum(root) - 1                                     # of a root: the roots before it
+    n_roots, n_live = int(root.sum()), int(live.sum())
+    assert got["num"].tolist() == [n_roots, n_live] == [P - 263 - 2, P - 263]
+    node = np.where(root, ids, -1).astype(np.int32)
+    for a, b in pairs:
+        node[b] = ids[a]
+    assert got["node_landmark"].tobytes() == node.reshape(G, N).tobytes()
+    r = np.flatnonzero(root)
+    center, count, spread = pts[r].copy(), np.ones(n_roots, np.int32), np.zeros(n_roots)
+    for a, _ in pairs:
+        center[ids[a], 0] += 0.25                                 # the mean of x and x + 0.5: exact
+        count[ids[a]] = 2
+        spread[ids[a]] = 0.25                                     # sqrt of the mean of 0.25^2, 0.25^2
+    want = {"center": center, "label": labels[r], "count": count, "first": r.astype(np.int32),
+            "sessions": np.ones(n_roots, np.int64), "spread": spread}
+    for a, b in pairs:                                            # the planted pairs and their neighbours, by name first
+        for i in (a - 1, a, b + 1):
+            for name in want:
+                assert got[name][ids[i]].tobytes() == want[name][ids[i]].tobytes(), (name, i)
+    for name in want:
+        assert got[name][:n_roots].tobytes() == want[name].tobytes(), name
+        assert (got[name][n_roots:].view(np.uint8) == 0xFF).all(), name + ": written past the records"
+
+
 # ------------------------------------------------------------------ labels and dead nodes
 def test_labels_and_dead_nodes():
     rng = np.random.default_rng(11)
